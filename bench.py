@@ -8,7 +8,12 @@
 A "step" is one pass of the whole hot path (audio already resident in HBM -> log-mel -> encoder ->
 cross-KV -> 1024 greedy decode steps -> token ids, then the all-gather of the token streams across
 ranks).  Weak scaling: every rank transcribes its own 64 segments, no data-path collective except
-that all-gather.  Rank 0 prints ONE JSON line (contract: task prompt / DESIGN.md "Measurement").
+that all-gather.  Rank 0 prints ONE JSON line (DESIGN.md "Measurement").
+
+A plain run sets up, warms up, times the K steps and prints the headline line.  `--full` adds what takes runs of its own: the
+live rooflines and MFMA utilisation (one eager, event-bracketed decode of the same batch) and the CPU oracle baselines.
+`--dump-outputs DIR` writes the token ids of the last timed step to DIR/token_ids.npy (float32; seeded inputs, so two builds
+run with the same arguments can be compared output for output).
 """
 from __future__ import annotations
 
@@ -35,10 +40,17 @@ def parse_args(argv=None):
     ap.add_argument("--decode-len", type=int, default=0, help="override L (0 = config's 1024); non-default runs are not the headline metric")
     ap.add_argument("--frames", type=int, default=256, choices=(256, 512),
                     help="encoder frames per segment: 256 = the 2.048 s headline shape; 512 = BASELINE configs[1]'s '512-frame encoder' wording (4.096 s segments)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-roofline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="after the headline, also measure the rooflines / MFMA utilisation and the CPU baselines (off by default)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: leave out the CPU baselines")
+    ap.add_argument("--no-roofline", action="store_true", help="with --full: leave out the rooflines and MFMA utilisation")
     ap.add_argument("--profile-stride", type=int, default=32)
-    return ap.parse_args(argv)
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the token ids of the last timed step to DIR/token_ids.npy (float32)")
+    args = ap.parse_args(argv)
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
+    return args
 
 
 def synthetic_audio(n: int, cfg, seed: int, device):
@@ -274,10 +286,13 @@ def run(args):
         },
     }
 
-    if rank == 0 and not args.no_roofline:
+    if rank == 0 and args.dump_outputs:
+        dump_outputs(args.dump_outputs, out)
+
+    if rank == 0 and args.full and not args.no_roofline:
         result.update(roofline_block(model, cfg, audio, B, L, args.profile_stride, sec_per_batch))
 
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
+    if rank == 0 and world == 1 and args.full and not args.no_cpu_baseline:
         result["cpu_baseline"] = cpu_baseline()
 
     if rank == 0:
@@ -286,6 +301,14 @@ def run(args):
     if world > 1:
         torch.distributed.barrier()             # rank 0 profiles after the timed region: leave the group together
         torch.distributed.destroy_process_group()
+
+
+def dump_outputs(directory: str, token_ids) -> None:
+    """What a caller of the timed path receives from its last step: the (segments, channels, L) token ids of every rank, in
+    segment order, as float32 (ids < 2^24 are exact)."""
+    import numpy as np
+    os.makedirs(directory, exist_ok=True)
+    np.save(os.path.join(directory, "token_ids.npy"), token_ids.cpu().numpy().astype(np.float32))
 
 
 def roofline_block(model, cfg, audio, B, L, stride, sec_per_batch) -> dict:

@@ -9,5 +9,6 @@ run DEBUG_CLR_GRAPH_PACKET_CAPTURE=0
 run YMT3_NO_GRAPH=1
 run YMT3_NO_GRAPH=1 HIP_FORCE_DEV_KERNARG=1
 bash scripts/gpu_pmc.sh && python3 scripts/pmc_collect.py
-timeout -k 10 600 python bench.py > gpurun_out/r02_bench_line.json 2> gpurun_out/bench.err; echo "bench exit=$?"
-python -c "import json; d=json.loads(open('gpurun_out/r02_bench_line.json').read().strip().splitlines()[-1]); print({k: d[k] for k in ('value','ms_per_step','p50_segment_latency_ms')}, d['roofline']['frac'], d['roofline']['traffic'], d['cpu_baseline']['value'])"
+OUT=${OUT:-results}; mkdir -p "$OUT"      # where the bench line goes
+timeout -k 10 600 python bench.py --full > "$OUT"/r02_bench_line.json 2> "$OUT"/bench.err; echo "bench exit=$?"
+python -c "import json; d=json.loads(open('$OUT/r02_bench_line.json').read().strip().splitlines()[-1]); print({k: d[k] for k in ('value','ms_per_step','p50_segment_latency_ms')}, d['roofline']['frac'], d['roofline']['traffic'], d['cpu_baseline']['value'])"

@@ -2,13 +2,22 @@
 
 The reference tree holds no fixtures (parity unpinned), so these vectors are produced by
 this build's own oracle, which tests/test_oracle_vs_thirdparty.py pins against torch.stft and HF T5.
-Run:  python tests/scripts/make_golden.py      (CPU only, ~1 min)
+Run:  python tests/scripts/make_golden.py [OUT_DIR]      (CPU only, ~1 min; OUT_DIR defaults to tests/golden)
+
+The oracle's fp32 GEMMs run on MKL, whose default kernels -- and with them the last bit of a dot product -- depend on the CPU model
+and the thread count, and the bf16 rounding between layers carries such a bit on into whole values and, at a close step, into another
+id.  So the fixtures are made with MKL's strict reproducibility mode (the same code path on every x86 CPU, whatever the thread count)
+and a fixed torch thread count (ATen's parallel reductions split by it).  MKL reads the mode once, at its first call: it is set here
+before torch is imported, which is why tests/test_cpu_host.py re-runs this script in a process of its own to check the stored fixtures.
 """
 import os
 import sys
 
-import numpy as np
-import torch
+os.environ["MKL_CBWR"] = "COMPATIBLE,STRICT"
+ORACLE_THREADS = 8
+
+import numpy as np  # noqa: E402
+import torch  # noqa: E402
 
 ROOT = os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 sys.path.insert(0, ROOT)
@@ -29,8 +38,8 @@ LONG_CASE = ("full_t256_l1024", YMT3Config(max_decode_len=1024, eos_id=-1), 2, 1
 LONG_LOGIT_STEPS = (0, 127, 382, 383, 384, 767, 1023)
 
 
-def main():
-    out_dir = os.path.join(ROOT, "tests", "golden")
+def main(out_dir=os.path.join(ROOT, "tests", "golden")):
+    torch.set_num_threads(ORACLE_THREADS)
     os.makedirs(out_dir, exist_ok=True)
     for name, (cfg, B, n_steps) in CASES.items():
         W = make_weights(cfg, seed=1234)
@@ -70,4 +79,4 @@ def main():
 
 
 if __name__ == "__main__":
-    main()
+    main(*sys.argv[1:2])
