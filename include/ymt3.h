@@ -12,6 +12,7 @@
  *   spectrogram module forward           ->  ymt3_logmel()
  *   encoder forward                      ->  ymt3_encode()
  *   decoder generate (greedy, KV cache)  ->  ymt3_decode_greedy()
+ *   inference(x, task_tokens, ...)       ->  ymt3_transcribe_segments_prompted() / ymt3_decode_prompted()
  *
  * Conventions
  *   - every pointer named *_dev is DEVICE memory on the handle's GPU, owned by the caller;
@@ -94,6 +95,30 @@ int ymt3_encode(ymt3_handle h, const float* mel_dev, int B, void* enc_dev, void*
 int ymt3_decode_greedy(ymt3_handle h, const void* enc_dev, int B, int n_steps, int32_t* tokens_dev,
                        const int32_t* forced_dev, float* logits_dev, void* stream);
 
+/* Task prompts (the `task_tokens` of inference(x, task_tokens, max_token_length)): a prefix of ids fed to the decoder before
+ * it emits, in the convention of HF `generate(decoder_input_ids=[[pad_id, *prompt]])`.
+ *   - prompt_dev: (B, n_channels, n_prompt) int32 on the device; n_prompt = P is the same for every row of a call, the ids may
+ *     differ per row.  P = 0 (prompt_dev may then be NULL) is exactly the unprompted call: ymt3_decode_greedy,
+ *     ymt3_transcribe_segments and ymt3_transcribe_stream are the P = 0 cases of the *_prompted entry points.
+ *   - step 0 consumes the decoder start id (pad_id); steps 0 .. P-1 feed prompt[r][t] instead of their argmax; the argmax of
+ *     step P + j is emitted token j.  A call launches P + n_steps steps and needs P + n_steps <= max_decode_len (the cache).
+ *   - prompt positions emit nothing: they write no token and no logits, and an argmax equal to eos_id there does not finish the
+ *     row.  tokens_dev, forced_dev and logits_dev keep their shapes (B, n_channels, n_steps[, vocab]) and index emitted tokens
+ *     only; forced_dev overrides the feed at emitted columns exactly as in ymt3_decode_greedy.
+ *   - prompt ids are clamped into [0, vocab) where they are fed, as forced ids are.
+ *   - ymt3_set_early_stop counts emitted steps only (the prompt's steps always run); ymt3_last_decode_steps reports LAUNCHED
+ *     steps, the prompt's included.
+ *   - YMT3_ERR_ARG (the handle stays usable): n_prompt < 0, n_prompt > 0 with a NULL prompt, P + n_steps > max_decode_len, or
+ *     P > 0 while ymt3_debug_decode_start is pending.
+ * Every decode kernel reads the prompt from device memory: no captured graph depends on it. */
+int ymt3_decode_prompted(ymt3_handle h, const void* enc_dev, int B, int n_steps, const int32_t* prompt_dev, int n_prompt,
+                         int32_t* tokens_dev, const int32_t* forced_dev, float* logits_dev, void* stream);
+int ymt3_transcribe_segments_prompted(ymt3_handle h, const float* audio_dev, int B, int n_steps, const int32_t* prompt_dev,
+                                      int n_prompt, int32_t* tokens_dev, void* stream);
+/* As ymt3_transcribe_stream; prompt_dev is (n_segments, n_channels, n_prompt), each segment's rows fed their own prompt. */
+int ymt3_transcribe_stream_prompted(ymt3_handle h, const float* audio_dev, int n_segments, int n_steps, const int32_t* prompt_dev,
+                                    int n_prompt, int32_t* tokens_dev, int slots, int interval, void* stream);
+
 /* Opt-in early stop (first step): with eos_id >= 0 and interval > 0, ymt3_decode_greedy /
  * ymt3_transcribe_segments check on the host every `interval` steps whether every row has emitted EOS and stop
  * launching once all have (the remainder of each row is PAD, exactly what the full-length run produces).  In this mode the
@@ -115,7 +140,8 @@ int ymt3_transcribe_stream(ymt3_handle h, const float* audio_dev, int n_segments
                            int slots, int interval, void* stream);
 
 /* Number of decoder steps the last decode call on this handle actually launched (ymt3_decode_greedy,
- * ymt3_transcribe_segments: n_steps unless ymt3_set_early_stop cut it short; ymt3_transcribe_stream: every step of every round). */
+ * ymt3_transcribe_segments: n_steps unless ymt3_set_early_stop cut it short; ymt3_transcribe_stream: every step of every round).
+ * Prompted calls count the prompt's steps too: n_prompt + n_steps without an early stop. */
 int ymt3_last_decode_steps(ymt3_handle h);
 
 /* The merged decode kernels (up to 64 rows, one channel: a layer's two attentions as one launch, its four skinny GEMMs as one launch)

@@ -17,6 +17,7 @@ SYMBOLS = [
     "ymt3_logmel", "ymt3_encode", "ymt3_decode_greedy", "ymt3_transcribe_segments", "ymt3_test_gemm", "ymt3_profile_decode", "ymt3_debug_decode_start", "ymt3_debug_force_stage_abort", "ymt3_set_early_stop", "ymt3_last_decode_steps",
     "ymt3_ingest_plan", "ymt3_ingest", "ymt3_transcribe_stream", "ymt3_debug_step_stamps", "ymt3_debug_kernel_stamps",
     "ymt3_set_abort_recovery", "ymt3_merged_fallbacks", "ymt3_debug_moe_trace", "ymt3_last_decode_chains",
+    "ymt3_decode_prompted", "ymt3_transcribe_segments_prompted", "ymt3_transcribe_stream_prompted",
 ]
 
 _lib = None
@@ -70,6 +71,12 @@ def load() -> ctypes.CDLL:
     lib.ymt3_ingest.restype = i32
     lib.ymt3_transcribe_stream.argtypes = [vp, vp, i32, i32, vp, i32, i32, vp]
     lib.ymt3_transcribe_stream.restype = i32
+    lib.ymt3_decode_prompted.argtypes = [vp, vp, i32, i32, vp, i32, vp, vp, vp, vp]
+    lib.ymt3_decode_prompted.restype = i32
+    lib.ymt3_transcribe_segments_prompted.argtypes = [vp, vp, i32, i32, vp, i32, vp, vp]
+    lib.ymt3_transcribe_segments_prompted.restype = i32
+    lib.ymt3_transcribe_stream_prompted.argtypes = [vp, vp, i32, i32, vp, i32, vp, i32, i32, vp]
+    lib.ymt3_transcribe_stream_prompted.restype = i32
     lib.ymt3_debug_step_stamps.argtypes = [vp, vp, vp, vp, ctypes.POINTER(ctypes.c_int)]
     lib.ymt3_debug_step_stamps.restype = i32
     lib.ymt3_debug_kernel_stamps.argtypes = [vp, i32, vp, i32]

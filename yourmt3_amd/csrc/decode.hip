@@ -21,7 +21,9 @@
 //                       computes its own query projection (FUSEQ) while its K/V loads are in flight.
 //  argmax_embed_kernel  fp32 argmax (first index wins ties, TP: utils.py:2925), EOS -> PAD fill
 //                       (:2928-2929), token store, next-token embedding gather into the residual
-//                       stream, and the step counter advance by the last workgroup to finish.
+//                       stream, and the step counter advance by the last workgroup to finish.  The first
+//                       n_prompt steps of a call (a task prompt, HF `decoder_input_ids` after the start id)
+//                       feed the caller's ids instead and emit nothing.
 //
 // Oracle: oracle/ymt3_oracle.py::decoder_step / greedy_decode.
 #include <cstdlib>
@@ -989,15 +991,20 @@ __global__ __launch_bounds__(256) void argmax_embed_kernel(const float* __restri
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int r = row0 + blockIdx.x;
     DecodeShared* sh = pShared;
-    const int t = sh->step, n_steps = sh->n_steps, col = t - sh->step0;   // col: index within this call
+    // col: emitted index within this call; the first n_prompt steps (col < 0) feed prompt ids and emit nothing
+    const int t = sh->step, n_steps = sh->n_steps, n_prompt = sh->n_prompt, col = t - sh->step0 - n_prompt;
     const float* row = pLogits + (size_t)r * V;
     // everything thread 0 needs after the argmax is requested now (workgroup-uniform addresses), under the logits loads,
     // instead of as a chain of round trips behind them
     int32_t* const tokens_out = sh->tokens_out;
     const int32_t* const forced = sh->forced;
     float* const logits_out = sh->logits_out;
+    const int32_t* const prompt = sh->prompt;
     const int was_finished = pFinished[r];
-    const int forced_tok = forced ? forced[(size_t)r * n_steps + col] : 0;
+    const int forced_tok = forced && col >= 0 ? forced[(size_t)r * n_steps + col] : 0;
+    // (a prompt id is read by thread 0 behind the argmax, at prompt positions only.  Requested here, its conditional load split
+    // this block, the kernel-argument loads moved behind it and every step's argmax waited for pFinished first: the whole
+    // decode ran ~1 ms per 1024-step batch slower)
     const int pos0 = pRowPos ? pRowPos[r] : 0;
     const long long out0 = pRowPos ? pRowOut[r] : 0;
 
@@ -1034,14 +1041,21 @@ __global__ __launch_bounds__(256) void argmax_embed_kernel(const float* __restri
         for (int w = 1; w < 4; ++w)
             if (sv[w] > bv || (sv[w] == bv && si[w] < bi)) { bv = sv[w]; bi = si[w]; }
         int feed = a.pad_id;
-        if (!was_finished) {
-            const int p = pos0;
+        if (!was_finished && pos0 < n_prompt) {           // a prompt position: feed the prompt id, emit nothing
+            pRowPos[r] = pos0 + 1;
+            feed = prompt[a.row_prompt[r] + pos0];
+        } else if (!was_finished) {
+            const int p = pos0 - n_prompt;
             tokens_out[out0 + p] = bi;
             if ((a.eos_id >= 0 && bi == a.eos_id) || p + 1 >= n_steps) pFinished[r] = 1;
-            else pRowPos[r] = p + 1;
+            else pRowPos[r] = pos0 + 1;
             feed = bi;
         }
-        s_feed = feed;
+        s_feed = feed < 0 ? 0 : (feed >= V ? V - 1 : feed);
+    } else if (tid == 0 && col < 0) {
+        // a prompt position: feed the prompt id; no token, no logits, no EOS flag
+        const int p = prompt[(size_t)r * n_prompt + (t - sh->step0)];
+        s_feed = p < 0 ? 0 : (p >= V ? V - 1 : p);
     } else if (tid == 0) {
 #pragma unroll
         for (int w = 1; w < 4; ++w)
@@ -1060,7 +1074,7 @@ __global__ __launch_bounds__(256) void argmax_embed_kernel(const float* __restri
     const bf16_t* e = pEmbed + (size_t)feed * a.d;
     const bf16_t* c = a.chan_embed ? a.chan_embed + (size_t)(r % a.n_channels) * a.d : nullptr;
     embed_row(a, r, e, c, sv);
-    if (logits_out && !pRowPos) {
+    if (logits_out && !pRowPos && col >= 0) {
         float* dst = logits_out + ((size_t)r * n_steps + col) * V;
         for (int i = tid; i < V; i += 256) dst[i] = row[i];
     }
@@ -1099,7 +1113,7 @@ __global__ __launch_bounds__(256) void argmax_embed_kernel(const float* __restri
 }
 
 __global__ __launch_bounds__(256) void decode_init_kernel(ArgmaxArgs a, int n_chains, int n_steps, int step0, int32_t* tokens_out,
-                                                          const int32_t* forced, float* logits_out) {
+                                                          const int32_t* forced, float* logits_out, const int32_t* prompt, int n_prompt) {
     const int r = blockIdx.x, tid = threadIdx.x;
     const bf16_t* e = a.embed + (size_t)a.pad_id * a.d;
     const bf16_t* c = a.chan_embed ? a.chan_embed + (size_t)(r % a.n_channels) * a.d : nullptr;
@@ -1116,10 +1130,13 @@ __global__ __launch_bounds__(256) void decode_init_kernel(ArgmaxArgs a, int n_ch
         sh->tokens_out = tokens_out;
         sh->forced = forced;
         sh->logits_out = logits_out;
+        sh->prompt = prompt;
+        sh->n_prompt = n_prompt;
     }
 }
 
-__global__ __launch_bounds__(256) void slot_start_kernel(ArgmaxArgs a, int row0, long long first_out, int n_steps, long long* row_out) {
+__global__ __launch_bounds__(256) void slot_start_kernel(ArgmaxArgs a, int row0, long long first_out, int n_steps, long long* row_out,
+                                                         long long first_prompt, int n_prompt, long long* row_prompt) {
     const int r = row0 + blockIdx.x, tid = threadIdx.x;
     const bf16_t* e = a.embed + (size_t)a.pad_id * a.d;
     const bf16_t* c = a.chan_embed ? a.chan_embed + (size_t)(r % a.n_channels) * a.d : nullptr;
@@ -1129,13 +1146,14 @@ __global__ __launch_bounds__(256) void slot_start_kernel(ArgmaxArgs a, int row0,
         a.finished[r] = 0;
         a.row_pos[r] = 0;
         row_out[r] = first_out + (long long)blockIdx.x * n_steps;
+        row_prompt[r] = first_prompt + (long long)blockIdx.x * n_prompt;
     }
 }
 
-__global__ void slot_retire_kernel(ArgmaxArgs a, int row0, int n_steps, int32_t* tokens_out) {
+__global__ void slot_retire_kernel(ArgmaxArgs a, int row0, int n_steps, int n_prompt, int32_t* tokens_out) {
     const int r = row0 + blockIdx.x;
     int32_t* row = tokens_out + a.row_out[r];
-    for (int i = a.row_pos[r] + 1 + threadIdx.x; i < n_steps; i += blockDim.x) row[i] = a.pad_id;
+    for (int i = max(a.row_pos[r] + 1 - n_prompt, 0) + threadIdx.x; i < n_steps; i += blockDim.x) row[i] = a.pad_id;
 }
 
 __global__ void pad_tail_kernel(int32_t* tokens_out, int row0, int n_steps, int from, int pad_id) {
@@ -1308,21 +1326,23 @@ int launch_argmax_embed(const ArgmaxArgs& a, hipStream_t stream) {
 }
 
 int launch_decode_init(const ArgmaxArgs& a, int n_chains, int n_steps, int step0, int32_t* tokens_out, const int32_t* forced,
-                       float* logits_out, hipStream_t stream) {
+                       float* logits_out, const int32_t* prompt, int n_prompt, hipStream_t stream) {
     if (a.R <= 0) return 0;
-    decode_init_kernel<<<a.R, 256, 0, stream>>>(a, n_chains, n_steps, step0, tokens_out, forced, logits_out);
+    if (n_prompt < 0 || (n_prompt > 0 && !prompt)) return -1;
+    decode_init_kernel<<<a.R, 256, 0, stream>>>(a, n_chains, n_steps, step0, tokens_out, forced, logits_out, prompt, n_prompt);
     return 0;
 }
 
-int launch_slot_start(const ArgmaxArgs& a, int row0, long long first_out, int n_steps, long long* row_out, hipStream_t stream) {
-    if (!a.row_pos || !row_out || a.n_channels <= 0) return -1;
-    slot_start_kernel<<<a.n_channels, 256, 0, stream>>>(a, row0, first_out, n_steps, row_out);
+int launch_slot_start(const ArgmaxArgs& a, int row0, long long first_out, int n_steps, long long* row_out, long long first_prompt,
+                      int n_prompt, long long* row_prompt, hipStream_t stream) {
+    if (!a.row_pos || !row_out || !row_prompt || a.n_channels <= 0) return -1;
+    slot_start_kernel<<<a.n_channels, 256, 0, stream>>>(a, row0, first_out, n_steps, row_out, first_prompt, n_prompt, row_prompt);
     return 0;
 }
 
-int launch_slot_retire(const ArgmaxArgs& a, int row0, int n_rows, int n_steps, int32_t* tokens_out, hipStream_t stream) {
+int launch_slot_retire(const ArgmaxArgs& a, int row0, int n_rows, int n_steps, int n_prompt, int32_t* tokens_out, hipStream_t stream) {
     if (!a.row_pos || !a.row_out || n_rows <= 0) return -1;
-    slot_retire_kernel<<<n_rows, 256, 0, stream>>>(a, row0, n_steps, tokens_out);
+    slot_retire_kernel<<<n_rows, 256, 0, stream>>>(a, row0, n_steps, n_prompt, tokens_out);
     return 0;
 }
 

@@ -83,10 +83,11 @@ struct DecodeShared {           // device-resident loop state, read by every dec
     int n_steps;                // row stride of tokens_out / forced / logits_out
     int step0;                  // first position of this call (0 except under the debug hook ymt3_debug_decode_start)
     int n_unfinished;           // rows of this chain that have not emitted EOS yet (maintained when eos_id >= 0)
-    int pad1;
+    int n_prompt;               // P: the first P steps of the call feed prompt ids and emit nothing (0: none)
     int32_t* tokens_out;        // [R][n_steps]
     const int32_t* forced;      // [R][n_steps] or null
     float* logits_out;          // [R][n_steps][V] or null
+    const int32_t* prompt;      // [R][n_prompt] (lock-step) or indexed through row_prompt (slot mode); null when n_prompt = 0
 };
 
 constexpr int SSQ_TILES = 32;    // sum(h^2) partials per row = d_model / 16 column tiles of the RESID epilogue
@@ -249,26 +250,29 @@ struct ArgmaxArgs {
     float* ssq;                 // [SSQ_TILES][ssq_stride]
     int ssq_stride;
     int row0, R, V, d, n_channels, eos_id, pad_id;
-    // slot mode (ymt3_transcribe_stream; both null otherwise): every row decodes at its own position row_pos[r] and
-    // writes token p to tokens_out[row_out[r] + p]; a row stops (finished = 1, position frozen) after EOS or n_steps tokens
+    // slot mode (ymt3_transcribe_stream; all null otherwise): every row decodes at its own position row_pos[r], feeds
+    // prompt[row_prompt[r] + p] at positions p < n_prompt and writes the token of position p >= n_prompt to
+    // tokens_out[row_out[r] + p - n_prompt]; a row stops (finished = 1, position frozen) after EOS or n_steps emitted tokens
     int* row_pos;               // [R]
     const long long* row_out;   // [R]
     unsigned long long* stamp;  // measurement: as DecGemmArgs::stamp
     unsigned* ticket;           // or null: [rows / 32 + 1] sub-counters, one 128-byte line each (zero between launches): a two-level ticket for many rows
     unsigned* zero_sync;        // or null: counter lines (CHAIN_LINE words each) to leave zeroed for the next step's dec_step_kernel
     int zero_lines;
+    const long long* row_prompt;   // slot mode, or null: [R] offset of the row's prompt (see row_pos)
 };
 int launch_argmax_embed(const ArgmaxArgs& a, hipStream_t stream);
-// tokens_out[r][from .. n_steps) = pad for rows [row0, row0 + R): the tail of a decode that stopped early
+// tokens_out[r][from .. n_steps) = pad for rows [row0, row0 + R): the tail of a decode that stopped early (`from`: emitted index)
 int launch_pad_tail(int32_t* tokens_out, int row0, int R, int n_steps, int from, int pad_id, hipStream_t stream);
 // slot mode: (re)start rows [row0, row0 + n_channels) on a new segment: h = embed[pad] (+ channel), position 0,
-// finished = 0, row_out = first_out + channel * n_steps
-int launch_slot_start(const ArgmaxArgs& a, int row0, long long first_out, int n_steps, long long* row_out, hipStream_t stream);
-// slot mode: PAD the unwritten tail [row_pos + 1, n_steps) of rows [row0, row0 + n_rows)
-int launch_slot_retire(const ArgmaxArgs& a, int row0, int n_rows, int n_steps, int32_t* tokens_out, hipStream_t stream);
-// all rows: h[r] = embed[pad] (+ chan_embed), finished = 0; a.shared[0..n_chains) reset
+// finished = 0, row_out = first_out + channel * n_steps, row_prompt = first_prompt + channel * n_prompt
+int launch_slot_start(const ArgmaxArgs& a, int row0, long long first_out, int n_steps, long long* row_out, long long first_prompt,
+                      int n_prompt, long long* row_prompt, hipStream_t stream);
+// slot mode: PAD the unwritten tail [row_pos + 1 - n_prompt, n_steps) of rows [row0, row0 + n_rows)
+int launch_slot_retire(const ArgmaxArgs& a, int row0, int n_rows, int n_steps, int n_prompt, int32_t* tokens_out, hipStream_t stream);
+// all rows: h[r] = embed[pad] (+ chan_embed), finished = 0; a.shared[0..n_chains) reset (prompt / n_prompt: every chain's)
 int launch_decode_init(const ArgmaxArgs& a, int n_chains, int n_steps, int step0, int32_t* tokens_out, const int32_t* forced,
-                       float* logits_out, hipStream_t stream);
+                       float* logits_out, const int32_t* prompt, int n_prompt, hipStream_t stream);
 
 // ---------------------------------------------------------------- MoE decoder FFN (moe.hip)
 struct MoeArgs {

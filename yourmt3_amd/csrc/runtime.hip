@@ -86,6 +86,7 @@ struct ymt3_ctx {
     // slot mode (ymt3_transcribe_stream): per-row positions and output offsets; launch_step wires them in while set
     int* row_pos = nullptr;             // [maxR]
     long long* row_out = nullptr;       // [maxR]
+    long long* row_prompt = nullptr;    // [maxR]: slot mode, offset of the row's prompt in the caller's prompt buffer
     int* host_rows = nullptr;           // pinned [maxR]: copy of `finished` for the host's retire/admit decisions
     bool slot_mode = false;
     DecodeShared* shared = nullptr;     // [MAX_CHAINS] per-chain loop state
@@ -364,6 +365,7 @@ static int create_impl(ymt3_ctx* c, const ymt3_config* cfg, const void* blob, si
     if (dev_alloc(c, (void**)&c->finished, R * 4)) return YMT3_ERR_HIP;
     if (dev_alloc(c, (void**)&c->row_pos, R * 4)) return YMT3_ERR_HIP;
     if (dev_alloc(c, (void**)&c->row_out, R * 8)) return YMT3_ERR_HIP;
+    if (dev_alloc(c, (void**)&c->row_prompt, R * 8)) return YMT3_ERR_HIP;
     if (dev_alloc(c, (void**)&c->ssq, (size_t)SSQ_TILES * R * 4)) return YMT3_ERR_HIP;
     if (dev_alloc(c, (void**)&c->opart, R * k.n_heads * d * 4)) return YMT3_ERR_HIP;
     if (dev_alloc(c, (void**)&c->ticket, (R / 32 + 1) * CHAIN_LINE * sizeof(unsigned))) return YMT3_ERR_HIP;
@@ -912,7 +914,7 @@ static int launch_step(ymt3_handle h, int B, int row0, int R, DecodeShared* shar
     g.R = R; g.V = k.vocab; g.d = d; g.n_channels = k.n_channels; g.eos_id = k.eos_id; g.pad_id = k.pad_id;
     GET(h, "dec.embed", 1u, const_cast<bf16_t**>(&g.embed), (size_t)k.vocab * d);
     if (k.n_channels > 1) GET(h, "dec.chan_embed", 1u, const_cast<bf16_t**>(&g.chan_embed), (size_t)k.n_channels * d);
-    if (h->slot_mode) { g.row_pos = h->row_pos; g.row_out = h->row_out; }
+    if (h->slot_mode) { g.row_pos = h->row_pos; g.row_out = h->row_out; g.row_prompt = h->row_prompt; }
     if (solo) g.ticket = h->ticket;                  // (row ranges of several chains would share groups)
     if (stepk) { g.zero_sync = h->step_sync; g.zero_lines = k.n_dec_layers * STEP_SYNC_LINES_PER_LAYER; }
     g.stamp = next_stamp(h, PC_ARGMAX, R);
@@ -920,21 +922,28 @@ static int launch_step(ymt3_handle h, int B, int row0, int R, DecodeShared* shar
     return YMT3_OK;
 }
 
-static int decode_run(ymt3_handle h, const bf16_t* enc, int B, int n_steps, int32_t* tokens, const int32_t* forced,
-                      float* logits_out, hipStream_t s, int prof_stride, int step0);
+static int decode_run(ymt3_handle h, const bf16_t* enc, int B, int n_steps, const int32_t* prompt, int n_prompt, int32_t* tokens,
+                      const int32_t* forced, float* logits_out, hipStream_t s, int prof_stride, int step0);
 
-static int decode_impl(ymt3_handle h, const bf16_t* enc, int B, int n_steps, int32_t* tokens, const int32_t* forced,
-                       float* logits_out, hipStream_t s, int prof_stride = 0) {
+// A call launches n_prompt + n_steps steps: the first n_prompt feed prompt[r][t] and emit nothing (argmax_embed_kernel), the rest
+// emit tokens 0 .. n_steps-1.  n_prompt = 0 is the plain decode.
+static int decode_impl(ymt3_handle h, const bf16_t* enc, int B, int n_steps, const int32_t* prompt, int n_prompt, int32_t* tokens,
+                       const int32_t* forced, float* logits_out, hipStream_t s, int prof_stride = 0) {
     const int step0 = h->prof_step0;          // one shot (debug hook): consumed by this call whatever its outcome
     h->prof_step0 = 0;
-    return decode_run(h, enc, B, n_steps, tokens, forced, logits_out, s, prof_stride, step0);
+    if (n_prompt < 0) FAIL(YMT3_ERR_ARG, "n_prompt=%d < 0", n_prompt);
+    if (n_prompt > 0 && !prompt) FAIL(YMT3_ERR_ARG, "n_prompt=%d with a null prompt", n_prompt);
+    if (n_prompt > 0 && step0 > 0) FAIL(YMT3_ERR_ARG, "ymt3_debug_decode_start does not combine with a prompt (n_prompt=%d)", n_prompt);
+    return decode_run(h, enc, B, n_steps, prompt, n_prompt, tokens, forced, logits_out, s, prof_stride, step0);
 }
 
-static int decode_run(ymt3_handle h, const bf16_t* enc, int B, int n_steps, int32_t* tokens, const int32_t* forced,
-                      float* logits_out, hipStream_t s, int prof_stride, int step0) {
+static int decode_run(ymt3_handle h, const bf16_t* enc, int B, int n_steps, const int32_t* prompt, int n_prompt, int32_t* tokens,
+                      const int32_t* forced, float* logits_out, hipStream_t s, int prof_stride, int step0) {
     const ymt3_config& k = h->cfg;
     bool merged = false;                      // some step of this call ran merged kernels
-    if (n_steps <= 0 || step0 + n_steps > k.max_decode_len) FAIL(YMT3_ERR_ARG, "n_steps=%d outside [1, max_decode_len=%d]", n_steps, k.max_decode_len - step0);
+    if (n_steps <= 0 || step0 + n_prompt + n_steps > k.max_decode_len)
+        FAIL(YMT3_ERR_ARG, "n_steps=%d outside [1, max_decode_len - n_prompt=%d]", n_steps, k.max_decode_len - step0 - n_prompt);
+    const int n_total = n_prompt + n_steps;   // steps launched
     const int d = k.d_model, R = B * k.n_channels;
     // a6: cross-attention K/V of every decoder layer in one GEMM, stored as per-(segment, head) slabs
     GemmArgs g{enc, h->wkv_all, h->ckv, nullptr, B * h->T, k.n_dec_layers * 2 * h->inner, d, d, d, 0, h->T, k.n_heads, B};
@@ -953,8 +962,8 @@ static int decode_run(ymt3_handle h, const bf16_t* enc, int B, int n_steps, int3
     if (n_chains > R) n_chains = R;
     h->last_chains = n_chains;
     if (h->step_kernel && h->step_sync) HIP_TRY(hipMemsetAsync(h->step_sync, 0, (size_t)STEP_SYNC_LINES * CHAIN_LINE * sizeof(unsigned), s));
-    LAUNCH(launch_decode_init(a, n_chains, n_steps, step0, tokens, forced, logits_out, s));
-    h->last_steps = n_steps;
+    LAUNCH(launch_decode_init(a, n_chains, n_steps, step0, tokens, forced, logits_out, prompt, n_prompt, s));
+    h->last_steps = n_total;
     int row0[9];
     row0[0] = 0;
     for (int c = 0; c < n_chains; ++c) row0[c + 1] = row0[c] + R / n_chains + (c < R % n_chains ? 1 : 0);
@@ -963,9 +972,9 @@ static int decode_run(ymt3_handle h, const bf16_t* enc, int B, int n_steps, int3
         // sampled steps (mid-stride: unbiased mean position) bracket every launch; the stride-1 unsampled steps that
         // follow each of them are bracketed as ONE span, which gives the true step time the per-launch brackets are
         // calibrated against (an event pair adds stream time of its own)
-        for (int t = 0; t < n_steps; ++t) {
+        for (int t = 0; t < n_total; ++t) {
             const bool sampled = prof_stride > 0 && (t % prof_stride) == prof_stride / 2;
-            const bool span_begin = prof_stride > 1 && (t % prof_stride) == prof_stride / 2 + 1 && t + prof_stride - 1 <= n_steps;
+            const bool span_begin = prof_stride > 1 && (t % prof_stride) == prof_stride / 2 + 1 && t + prof_stride - 1 <= n_total;
             const bool span_end = prof_stride > 1 && t >= prof_stride && (t % prof_stride) == prof_stride / 2 && !h->prof_ev.empty() && h->prof_span_open;
             if (span_end) { (void)hipEventRecord(h->prof_ev[h->prof_span_idx], s); h->prof_span_open = false; }
             if (span_begin) {
@@ -1006,7 +1015,9 @@ static int decode_run(ymt3_handle h, const bf16_t* enc, int B, int n_steps, int3
         if (n_chains == 1 && h->early_stop_interval > 0 && k.eos_id >= 0 && !forced) {
             // opt-in (ymt3_set_early_stop): every `interval` steps the host reads how many rows are still decoding and
             // stops launching once none is; the rest of every row is PAD by the EOS fill rule.  This path synchronises
-            // the stream (the only one that does); with forced tokens the trajectory is fixed, so it is not used.
+            // the stream (the only one that does); with forced tokens the trajectory is fixed, so it is not used.  Only emitted
+            // steps count: the prompt's steps go first, then the host checks every `interval` emitted steps.
+            for (int i = 0; i < n_prompt; ++i) HIP_TRY(hipGraphLaunch(exec[0], s));
             int t = 0;
             while (t < n_steps) {
                 const int chunk = std::min(h->early_stop_interval, n_steps - t);
@@ -1017,7 +1028,7 @@ static int decode_run(ymt3_handle h, const bf16_t* enc, int B, int n_steps, int3
                 HIP_TRY(hipStreamSynchronize(s));
                 if (*h->host_flag == 0) break;
             }
-            h->last_steps = t;
+            h->last_steps = n_prompt + t;
             LAUNCH(launch_pad_tail(tokens, 0, R, n_steps, t, k.pad_id, s));
         } else if (n_chains == 1) {
             // graph_steps consecutive steps are ONE replayed graph (every kernel reads the position from device memory, so a graph of G
@@ -1025,7 +1036,7 @@ static int decode_run(ymt3_handle h, const bf16_t* enc, int B, int n_steps, int3
             // boundary inside a graph does not (eager launches ran 2.9 % faster than one-step graphs, profiles/r02_graph_steps.txt)
             const int G = h->graph_steps;
             int t = 0;
-            if (G > 1 && n_steps >= G) {
+            if (G > 1 && n_total >= G) {
                 StepGraph& mg = h->step_graphs[(((long)B * 16 + 1) * 16) | (1L << 40) | ((long)G << 32)];
                 if (!mg.exec) {
                     HIP_TRY(hipStreamBeginCapture(h->cap_stream, hipStreamCaptureModeThreadLocal));
@@ -1038,9 +1049,9 @@ static int decode_run(ymt3_handle h, const bf16_t* enc, int B, int n_steps, int3
                     mg.merged = h->step_merged;
                 }
                 merged = merged || mg.merged;
-                for (; t + G <= n_steps; t += G) HIP_TRY(hipGraphLaunch(mg.exec, s));
+                for (; t + G <= n_total; t += G) HIP_TRY(hipGraphLaunch(mg.exec, s));
             }
-            for (; t < n_steps; ++t) HIP_TRY(hipGraphLaunch(exec[0], s));
+            for (; t < n_total; ++t) HIP_TRY(hipGraphLaunch(exec[0], s));
         } else {
             // fork: every chain stream waits for the cross-KV GEMM + init on the caller's stream
             HIP_TRY(hipEventRecord(h->fork_ev, s));
@@ -1049,7 +1060,7 @@ static int decode_run(ymt3_handle h, const bf16_t* enc, int B, int n_steps, int3
             // of stream time that a kernel boundary inside a graph does not)
             const int G = h->graph_steps;
             hipGraphExec_t mexec[8] = {};
-            if (G > 1 && n_steps >= G) {
+            if (G > 1 && n_total >= G) {
                 for (int c = 0; c < n_chains; ++c) {
                     StepGraph& mg = h->step_graphs[((((long)B * 16 + n_chains) * 16 + c)) | (1L << 40) | ((long)G << 32)];
                     if (!mg.exec) {
@@ -1068,9 +1079,9 @@ static int decode_run(ymt3_handle h, const bf16_t* enc, int B, int n_steps, int3
             auto feed = [&](int c) -> bool {
                 int t = 0;
                 if (mexec[c])
-                    for (; t + G <= n_steps; t += G)
+                    for (; t + G <= n_total; t += G)
                         if (hipGraphLaunch(mexec[c], h->chain_stream[c]) != hipSuccess) return false;
-                for (; t < n_steps; ++t)
+                for (; t < n_total; ++t)
                     if (hipGraphLaunch(exec[c], h->chain_stream[c]) != hipSuccess) return false;
                 return true;
             };
@@ -1089,7 +1100,7 @@ static int decode_run(ymt3_handle h, const bf16_t* enc, int B, int n_steps, int3
                 if (bad) FAIL(YMT3_ERR_HIP, "hipGraphLaunch failed on a decode chain: %s", hipGetErrorString(hipGetLastError()));
             } else {
                 // (the caller's thread feeds all chains: step by step, so that no chain runs ahead of the others' launches)
-                for (int t = 0; t < n_steps; ++t)
+                for (int t = 0; t < n_total; ++t)
                     for (int c = 0; c < n_chains; ++c) HIP_TRY(hipGraphLaunch(exec[c], h->chain_stream[c]));
             }
             // join: the caller's stream continues only after every chain has emitted its last token
@@ -1112,7 +1123,7 @@ static int decode_run(ymt3_handle h, const bf16_t* enc, int B, int n_steps, int3
             if (h->chain_host_abort && *static_cast<volatile unsigned*>(h->chain_host_abort)) {
                 int rc = merged_fallback(h);
                 if (rc) return rc;
-                return decode_run(h, enc, B, n_steps, tokens, forced, logits_out, s, prof_stride, step0);
+                return decode_run(h, enc, B, n_steps, prompt, n_prompt, tokens, forced, logits_out, s, prof_stride, step0);
             }
         } else if (h->forced_abort && h->chain_host_abort) {
             *h->chain_host_abort = 1u;            // asynchronous mode: the next call on the handle finds the word (check_call)
@@ -1123,26 +1134,41 @@ static int decode_run(ymt3_handle h, const bf16_t* enc, int B, int n_steps, int3
     return YMT3_OK;
 }
 
-extern "C" int ymt3_decode_greedy(ymt3_handle h, const void* enc_dev, int B, int n_steps, int32_t* tokens_dev,
-                                  const int32_t* forced_dev, float* logits_dev, void* stream) {
+extern "C" int ymt3_decode_prompted(ymt3_handle h, const void* enc_dev, int B, int n_steps, const int32_t* prompt_dev, int n_prompt,
+                                    int32_t* tokens_dev, const int32_t* forced_dev, float* logits_dev, void* stream) {
     int rc = check_call(h, B);
     if (rc) return rc;
     if (B == 0) return YMT3_OK;
     if (!enc_dev || !tokens_dev) FAIL(YMT3_ERR_ARG, "null buffer");
-    return decode_impl(h, static_cast<const bf16_t*>(enc_dev), B, n_steps, tokens_dev, forced_dev, logits_dev, (hipStream_t)stream);
+    return decode_impl(h, static_cast<const bf16_t*>(enc_dev), B, n_steps, prompt_dev, n_prompt, tokens_dev, forced_dev, logits_dev,
+                       (hipStream_t)stream);
 }
 
-extern "C" int ymt3_transcribe_segments(ymt3_handle h, const float* audio_dev, int B, int n_steps, int32_t* tokens_dev,
-                                        void* stream) {
+extern "C" int ymt3_decode_greedy(ymt3_handle h, const void* enc_dev, int B, int n_steps, int32_t* tokens_dev,
+                                  const int32_t* forced_dev, float* logits_dev, void* stream) {
+    return ymt3_decode_prompted(h, enc_dev, B, n_steps, nullptr, 0, tokens_dev, forced_dev, logits_dev, stream);
+}
+
+extern "C" int ymt3_transcribe_segments_prompted(ymt3_handle h, const float* audio_dev, int B, int n_steps, const int32_t* prompt_dev,
+                                                 int n_prompt, int32_t* tokens_dev, void* stream) {
     int rc = check_call(h, B);
     if (rc) return rc;
     if (B == 0) return YMT3_OK;
     if (!audio_dev || !tokens_dev) FAIL(YMT3_ERR_ARG, "null buffer");
+    // the prompt is checked before any work is queued (decode_impl checks it again)
+    if (n_prompt < 0 || (n_prompt > 0 && !prompt_dev)) FAIL(YMT3_ERR_ARG, "n_prompt=%d with prompt %s", n_prompt, prompt_dev ? "set" : "null");
+    if (n_steps <= 0 || n_prompt + n_steps > h->cfg.max_decode_len)
+        FAIL(YMT3_ERR_ARG, "n_steps=%d outside [1, max_decode_len - n_prompt=%d]", n_steps, h->cfg.max_decode_len - n_prompt);
     hipStream_t s = (hipStream_t)stream;
     LAUNCH(launch_logmel(h->fe, audio_dev, h->mel, B, s));
     rc = encode_impl(h, h->mel, B, h->enc_out, s);
     if (rc) return rc;
-    return decode_impl(h, h->enc_out, B, n_steps, tokens_dev, nullptr, nullptr, s);
+    return decode_impl(h, h->enc_out, B, n_steps, prompt_dev, n_prompt, tokens_dev, nullptr, nullptr, s);
+}
+
+extern "C" int ymt3_transcribe_segments(ymt3_handle h, const float* audio_dev, int B, int n_steps, int32_t* tokens_dev,
+                                        void* stream) {
+    return ymt3_transcribe_segments_prompted(h, audio_dev, B, n_steps, nullptr, 0, tokens_dev, stream);
 }
 
 // continuous batching.  `slots` decoder slots are kept busy from a queue of segments: each row
@@ -1150,15 +1176,17 @@ extern "C" int ymt3_transcribe_segments(ymt3_handle h, const float* audio_dev, i
 // `interval` steps, pads and retires segments whose rows have all stopped, and encodes the next pending segments straight
 // into the freed slots (log-mel + encoder batched over the admissions, cross-K/V written into each slot's slabs).  Rows are
 // independent in every kernel, so the ids equal those of lock-step batches bit for bit.
-extern "C" int ymt3_transcribe_stream(ymt3_handle h, const float* audio_dev, int n_segments, int n_steps, int32_t* tokens_dev,
-                                      int slots, int interval, void* stream) {
+extern "C" int ymt3_transcribe_stream_prompted(ymt3_handle h, const float* audio_dev, int n_segments, int n_steps, const int32_t* prompt_dev,
+                                               int n_prompt, int32_t* tokens_dev, int slots, int interval, void* stream) {
     int rc = check_call(h, 0);
     if (rc) return rc;
     if (n_segments < 0) FAIL(YMT3_ERR_ARG, "n_segments=%d", n_segments);
     if (n_segments == 0) return YMT3_OK;
     if (!audio_dev || !tokens_dev) FAIL(YMT3_ERR_ARG, "null buffer");
     const ymt3_config& k = h->cfg;
-    if (n_steps <= 0 || n_steps > k.max_decode_len) FAIL(YMT3_ERR_ARG, "n_steps=%d outside [1, max_decode_len=%d]", n_steps, k.max_decode_len);
+    if (n_prompt < 0 || (n_prompt > 0 && !prompt_dev)) FAIL(YMT3_ERR_ARG, "n_prompt=%d with prompt %s", n_prompt, prompt_dev ? "set" : "null");
+    if (n_steps <= 0 || n_prompt + n_steps > k.max_decode_len)
+        FAIL(YMT3_ERR_ARG, "n_steps=%d outside [1, max_decode_len - n_prompt=%d]", n_steps, k.max_decode_len - n_prompt);
     if (interval < 0) FAIL(YMT3_ERR_ARG, "interval=%d", interval);
     if (h->prof_step0) FAIL(YMT3_ERR_UNSUPPORTED, "ymt3_debug_decode_start is pending: it applies to lock-step decode calls only");
     if (interval == 0) interval = 8;
@@ -1172,7 +1200,7 @@ extern "C" int ymt3_transcribe_stream(ymt3_handle h, const float* audio_dev, int
     ArgmaxArgs a{};
     a.h = h->h_dec; a.shared = h->shared; a.finished = h->finished; a.ssq = h->ssq; a.ssq_stride = h->maxR;
     a.R = R; a.V = k.vocab; a.d = d; a.n_channels = K; a.eos_id = k.eos_id; a.pad_id = k.pad_id;
-    a.row_pos = h->row_pos; a.row_out = h->row_out;
+    a.row_pos = h->row_pos; a.row_out = h->row_out; a.row_prompt = h->row_prompt;
     GET(h, "dec.embed", 1u, const_cast<bf16_t**>(&a.embed), (size_t)k.vocab * d);
     if (K > 1) GET(h, "dec.chan_embed", 1u, const_cast<bf16_t**>(&a.chan_embed), (size_t)K * d);
 
@@ -1180,10 +1208,11 @@ extern "C" int ymt3_transcribe_stream(ymt3_handle h, const float* audio_dev, int
     h->slot_mode = true;
     // loop state: every row starts stopped; admissions start them
     if (h->step_kernel && h->step_sync) HIP_TRY(hipMemsetAsync(h->step_sync, 0, (size_t)STEP_SYNC_LINES * CHAIN_LINE * sizeof(unsigned), s));
-    LAUNCH(launch_decode_init(a, 1, n_steps, 0, tokens_dev, nullptr, nullptr, s));
+    LAUNCH(launch_decode_init(a, 1, n_steps, 0, tokens_dev, nullptr, nullptr, prompt_dev, n_prompt, s));
     HIP_TRY(hipMemsetD32Async(reinterpret_cast<hipDeviceptr_t>(h->finished), 1, (size_t)R, s));
     HIP_TRY(hipMemsetAsync(h->row_pos, 0, (size_t)R * sizeof(int), s));
     HIP_TRY(hipMemsetAsync(h->row_out, 0, (size_t)R * sizeof(long long), s));
+    HIP_TRY(hipMemsetAsync(h->row_prompt, 0, (size_t)R * sizeof(long long), s));
 
     hipGraphExec_t exec = nullptr;
     // one replayed graph per round of `interval` steps when that is at most 64 steps (a graph launch costs ~7 us of stream time on
@@ -1214,7 +1243,8 @@ extern "C" int ymt3_transcribe_stream(ymt3_handle h, const float* audio_dev, int
             GemmArgs g{h->enc_out + (size_t)i * T * d, h->wkv_all, h->ckv + (size_t)slot * H * T * 64, nullptr,
                        T, k.n_dec_layers * 2 * h->inner, d, d, d, 0, T, H, slots};
             LAUNCH(launch_gemm(EPI_KV_HEADMAJOR, g, s));
-            LAUNCH(launch_slot_start(a, slot * K, (long long)(first_seg + i) * K * n_steps, n_steps, h->row_out, s));
+            LAUNCH(launch_slot_start(a, slot * K, (long long)(first_seg + i) * K * n_steps, n_steps, h->row_out,
+                                     (long long)(first_seg + i) * K * n_prompt, n_prompt, h->row_prompt, s));
             slot_seg[(size_t)slot] = first_seg + i;
         }
         return YMT3_OK;
@@ -1223,8 +1253,8 @@ extern "C" int ymt3_transcribe_stream(ymt3_handle h, const float* audio_dev, int
     rc = admit(0, slots);
     if (rc) return rc;
     int next = slots, live = slots;
-    // every live segment stops within n_steps steps, so the loop is bounded; the guard only catches a logic error
-    const long max_rounds = ((long)n_segments / slots + 2) * ((n_steps + interval - 1) / interval + 1);
+    // every live segment stops within n_prompt + n_steps steps, so the loop is bounded; the guard only catches a logic error
+    const long max_rounds = ((long)n_segments / slots + 2) * ((n_prompt + n_steps + interval - 1) / interval + 1);
     h->last_steps = 0;
     for (long round = 0; live > 0; ++round) {
         h->last_steps += interval;
@@ -1240,7 +1270,7 @@ extern "C" int ymt3_transcribe_stream(ymt3_handle h, const float* audio_dev, int
             // a merged kernel gave up (the stream is idle here): start the queue again on the separate launches -- same ids
             rc = merged_fallback(h);
             if (rc) return rc;
-            return ymt3_transcribe_stream(h, audio_dev, n_segments, n_steps, tokens_dev, slots, interval, stream);
+            return ymt3_transcribe_stream_prompted(h, audio_dev, n_segments, n_steps, prompt_dev, n_prompt, tokens_dev, slots, interval, stream);
         }
         free_slots.clear();
         for (int slot = 0; slot < slots; ++slot) {
@@ -1248,7 +1278,7 @@ extern "C" int ymt3_transcribe_stream(ymt3_handle h, const float* audio_dev, int
             bool all = true;
             for (int c = 0; c < K; ++c) all = all && h->host_rows[slot * K + c] != 0;
             if (!all) continue;
-            LAUNCH(launch_slot_retire(a, slot * K, K, n_steps, tokens_dev, s));
+            LAUNCH(launch_slot_retire(a, slot * K, K, n_steps, n_prompt, tokens_dev, s));
             slot_seg[(size_t)slot] = -1;
             --live;
             free_slots.push_back(slot);
@@ -1263,6 +1293,11 @@ extern "C" int ymt3_transcribe_stream(ymt3_handle h, const float* audio_dev, int
     }
     HIP_TRY(hipGetLastError());
     return YMT3_OK;
+}
+
+extern "C" int ymt3_transcribe_stream(ymt3_handle h, const float* audio_dev, int n_segments, int n_steps, int32_t* tokens_dev,
+                                      int slots, int interval, void* stream) {
+    return ymt3_transcribe_stream_prompted(h, audio_dev, n_segments, n_steps, nullptr, 0, tokens_dev, slots, interval, stream);
 }
 
 extern "C" int ymt3_test_gemm(ymt3_handle h, const void* a_dev, const void* w_dev, float* c_dev, int M, int N, int K, void* stream) {
@@ -1282,7 +1317,7 @@ extern "C" int ymt3_profile_decode(ymt3_handle h, const void* enc_dev, int B, in
     hipStream_t s = (hipStream_t)stream;
     h->prof_ev.clear();
     h->prof_cls.clear();
-    rc = decode_impl(h, static_cast<const bf16_t*>(enc_dev), B, n_steps, tokens_dev, nullptr, nullptr, s, stride);
+    rc = decode_impl(h, static_cast<const bf16_t*>(enc_dev), B, n_steps, nullptr, 0, tokens_dev, nullptr, nullptr, s, stride);
     hipError_t e = hipStreamSynchronize(s);
     for (int i = 0; i < YMT3_PROFILE_CLASSES; ++i) { ms_by_class[i] = 0.f; launches_by_class[i] = 0; }
     for (size_t i = 0; i < h->prof_cls.size(); ++i) {

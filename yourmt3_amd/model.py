@@ -68,9 +68,38 @@ class YourMT3:
             raise ValueError(f"batch {audio.shape[0]} exceeds max_batch {self.max_batch}")
         return audio.to(self.device, torch.float32).contiguous()
 
+    def _prompt(self, task_tokens, B: int, n_steps: int) -> Optional[torch.Tensor]:
+        """task_tokens -> (B, K, P) int32 device prompt (include/ymt3.h, task prompts), or None for None.  Accepted shapes: (P,)
+        for every row, (B, P) per segment (repeated over the channels) or (B, K, P); ids must lie in [0, vocab)."""
+        if task_tokens is None:
+            return None
+        cfg = self.cfg
+        t = torch.as_tensor(task_tokens)
+        if t.dtype.is_floating_point or t.dtype == torch.bool or t.dtype.is_complex:
+            raise ValueError(f"task_tokens must be integer ids, got {t.dtype}")
+        K = cfg.n_channels
+        if t.dim() == 1:
+            t = t[None, None, :].expand(B, K, t.shape[0])
+        elif t.dim() == 2:
+            if t.shape[0] != B:
+                raise ValueError(f"task_tokens (B, P) needs B = {B} rows, got {tuple(t.shape)}")
+            t = t[:, None, :].expand(B, K, t.shape[1])
+        elif t.dim() == 3:
+            if tuple(t.shape[:2]) != (B, K):
+                raise ValueError(f"task_tokens (B, K, P) must be ({B}, {K}, P), got {tuple(t.shape)}")
+        else:
+            raise ValueError(f"task_tokens must be (P,), (B, P) or (B, K, P), got {tuple(t.shape)}")
+        P = int(t.shape[-1])
+        if t.numel() and (int(t.min()) < 0 or int(t.max()) >= cfg.vocab):
+            raise ValueError(f"task_tokens ids must lie in [0, {cfg.vocab})")
+        if P + n_steps > cfg.max_decode_len:
+            raise ValueError(f"{P} prompt + {n_steps} emitted steps exceed max_decode_len {cfg.max_decode_len}")
+        return t.to(self.device, torch.int32).contiguous()
+
     @property
     def last_decode_steps(self) -> int:
-        """Decoder steps the last decode / inference call launched (fewer than asked for after an early stop)."""
+        """Decoder steps the last decode / inference call launched (fewer than asked for after an early stop; a task prompt's
+        steps included)."""
         return int(self._lib.ymt3_last_decode_steps(self._handle))
 
     @property
@@ -131,50 +160,76 @@ class YourMT3:
         return enc
 
     def decode(self, enc: torch.Tensor, n_steps: Optional[int] = None, forced: Optional[torch.Tensor] = None,
-               return_logits: bool = False):
+               return_logits: bool = False, prompt=None):
+        """Greedy decode of n_steps emitted tokens per row.  `prompt` ((P,), (B, P) or (B, K, P) ids): fed after the start id before
+        anything is emitted (HF decoder_input_ids = [pad, *prompt]); tokens / forced / logits index emitted steps only."""
         cfg = self.cfg
-        n_steps = int(n_steps or cfg.max_decode_len)
         enc = enc.to(self.device, torch.bfloat16).contiguous()
         B = enc.shape[0]
+        p = self._prompt(prompt, B, int(n_steps or 1))
+        n_steps = int(n_steps or cfg.max_decode_len - (p.shape[-1] if p is not None else 0))
         tokens = torch.empty(B, cfg.n_channels, n_steps, device=self.device, dtype=torch.int32)
         f = forced.to(self.device, torch.int32).contiguous() if forced is not None else None
         if f is not None and tuple(f.shape) != (B, cfg.n_channels, n_steps):
             raise ValueError("forced must be (B, n_channels, n_steps)")
         lg = torch.empty(B, cfg.n_channels, n_steps, cfg.vocab, device=self.device, dtype=torch.float32) if return_logits else None
-        _lib.check(self._lib.ymt3_decode_greedy(self._handle, _ptr(enc), B, n_steps, _ptr(tokens), _ptr(f), _ptr(lg), self._stream()))
+        if p is None:
+            _lib.check(self._lib.ymt3_decode_greedy(self._handle, _ptr(enc), B, n_steps, _ptr(tokens), _ptr(f), _ptr(lg), self._stream()))
+        else:
+            _lib.check(self._lib.ymt3_decode_prompted(self._handle, _ptr(enc), B, n_steps, _ptr(p), int(p.shape[-1]), _ptr(tokens), _ptr(f),
+                                                      _ptr(lg), self._stream()))
         return (tokens, lg) if return_logits else tokens
 
     # ------------------------------------------------------------------ reference-shaped API
     def inference(self, audio: torch.Tensor, task_tokens=None, max_token_length: Optional[int] = None) -> torch.Tensor:
-        """(B, 1, S) or (B, S) audio -> (B, K, L) int32 token ids: the whole hot path, one C call."""
+        """(B, 1, S) or (B, S) audio -> (B, K, L) int32 token ids: the whole hot path, one C call.  `task_tokens` ((P,), (B, P) or
+        (B, K, P) ids, e.g. TaskManager.task_prompt): the decoder is prompted with them and L tokens are emitted after them."""
         a = self._audio2d(audio)
         B = a.shape[0]
         L = int(max_token_length or self.cfg.max_decode_len)
+        p = self._prompt(task_tokens, B, L)
         tokens = torch.empty(B, self.cfg.n_channels, L, device=self.device, dtype=torch.int32)
-        _lib.check(self._lib.ymt3_transcribe_segments(self._handle, _ptr(a), B, L, _ptr(tokens), self._stream()))
+        if p is None:
+            _lib.check(self._lib.ymt3_transcribe_segments(self._handle, _ptr(a), B, L, _ptr(tokens), self._stream()))
+        elif B:
+            _lib.check(self._lib.ymt3_transcribe_segments_prompted(self._handle, _ptr(a), B, L, _ptr(p), int(p.shape[-1]), _ptr(tokens),
+                                                                   self._stream()))
         return tokens
 
     def inference_stream(self, audio_segments: torch.Tensor, max_token_length: Optional[int] = None, slots: int = 0,
-                         interval: int = 8) -> torch.Tensor:
+                         interval: int = 8, task_tokens=None) -> torch.Tensor:
         """(N, 1, S) or (N, S) audio, any N -> (N, K, L) int32 ids with continuous batching: `slots` decoder slots are
-        refilled from the queue as segments emit EOS (needs eos_id >= 0 to gain anything).  Ids equal inference()'s."""
+        refilled from the queue as segments emit EOS (needs eos_id >= 0 to gain anything).  Ids equal inference()'s, with the
+        same `task_tokens` ((P,), (N, P) or (N, K, P))."""
         a = audio_segments[:, 0, :] if audio_segments.dim() == 3 else audio_segments
         if a.shape[-1] != self.cfg.segment_samples:
             raise ValueError(f"segments must have {self.cfg.segment_samples} samples, got {a.shape[-1]}")
         a = a.to(self.device, torch.float32).contiguous()
         N = a.shape[0]
         L = int(max_token_length or self.cfg.max_decode_len)
+        p = self._prompt(task_tokens, N, L)
         tokens = torch.empty(N, self.cfg.n_channels, L, device=self.device, dtype=torch.int32)
-        _lib.check(self._lib.ymt3_transcribe_stream(self._handle, _ptr(a) if N else None, N, L, _ptr(tokens) if N else None,
-                                                    int(slots), int(interval), self._stream()))
+        if p is None:
+            _lib.check(self._lib.ymt3_transcribe_stream(self._handle, _ptr(a) if N else None, N, L, _ptr(tokens) if N else None,
+                                                        int(slots), int(interval), self._stream()))
+        elif N:
+            _lib.check(self._lib.ymt3_transcribe_stream_prompted(self._handle, _ptr(a), N, L, _ptr(p), int(p.shape[-1]), _ptr(tokens),
+                                                                 int(slots), int(interval), self._stream()))
         return tokens
 
-    def inference_file(self, bsz: int, audio_segments: torch.Tensor, max_token_length: Optional[int] = None) -> List[np.ndarray]:
-        """Split (N, 1, S) segments into batches of `bsz`; one (b, K, L) int array per batch."""
+    def inference_file(self, bsz: int, audio_segments: torch.Tensor, max_token_length: Optional[int] = None,
+                       task_tokens=None) -> List[np.ndarray]:
+        """Split (N, 1, S) segments into batches of `bsz`; one (b, K, L) int array per batch.  `task_tokens`: (P,) for every
+        segment, or (N, P) / (N, K, P), sliced with the batches."""
         bsz = min(int(bsz), self.max_batch)
+        N = audio_segments.shape[0]
+        tt = None if task_tokens is None else torch.as_tensor(task_tokens)
+        if tt is not None and tt.dim() > 1 and tt.shape[0] != N:
+            raise ValueError(f"task_tokens has {tt.shape[0]} rows for {N} segments")
         out = []
-        for i in range(0, audio_segments.shape[0], bsz):
-            out.append(self.inference(audio_segments[i:i + bsz], max_token_length=max_token_length).cpu().numpy())
+        for i in range(0, N, bsz):
+            ti = tt if tt is None or tt.dim() == 1 else tt[i:i + bsz]
+            out.append(self.inference(audio_segments[i:i + bsz], task_tokens=ti, max_token_length=max_token_length).cpu().numpy())
         return out
 
     PROFILE_CLASSES = ["qkv_cache_gemm", "self_attn", "self_o_gemm", "cross_q_gemm", "cross_attn", "cross_o_gemm",

@@ -9,6 +9,13 @@ Token grammar of one segment (MT3 style):
     then events in time order:  SHIFT n (time += n*10 ms) | VELOCITY v | PROGRAM p | PITCH k | DRUM k
     EOS, then PAD.
 VELOCITY 1 makes the following pitches onsets, VELOCITY 0 offsets; drums have onsets only.
+
+Task-conditioned tasks (`singing_drum_v1`) prefix every segment's decode with task tokens that select a sub-task
+("transcribe everything", "singing only", "drums only"): `task_prompt(subtask, n)` gives the ids, which
+YourMT3.inference(audio, task_tokens=...) feeds to the decoder before it emits (include/ymt3.h, task prompts).
+BUILD-DEFINED: the task-token names, their ids and the sub-task prefixes are shaped after an unverified recollection
+of upstream; nothing in the reference pins them.  The ids sit right after the codec's events
+(Codec.size ...) inside the 1536-wide head; a real checkpoint's ids are an entry of the `task_token_ids` table.
 """
 from __future__ import annotations
 
@@ -17,7 +24,7 @@ from typing import Dict, Iterable, List, Optional, Sequence, Tuple
 
 import numpy as np
 
-from .vocab import Codec, Event, EOS, PAD, UNK
+from .vocab import Codec, Event, EOS, NUM_SPECIAL, PAD, UNK
 
 DRUM_PROGRAM = 128
 DRUM_NOTE_SEC = 0.01          # drums carry no offset: fixed nominal duration
@@ -50,15 +57,30 @@ MC13_GROUPS: List[Tuple[str, Sequence[int]]] = [
     ("singing", (129,)), ("drums", (128,)),
 ]
 
+# task-token names in id order: by default they take the ids Codec.size, Codec.size + 1, ... (build-defined, see above)
+TASK_TOKEN_NAMES: Tuple[str, ...] = ("task", "transcribe_all", "transcribe_singing", "transcribe_drum")
+DEFAULT_VOCAB = 1536          # YMT3Config.vocab: the head the ids must fit in
+
 TASKS: Dict[str, dict] = {
     "mt3_full_plus": {"channels": 1, "max_tokens": 1024},
     "mc13_full_plus_256": {"channels": 13, "max_tokens": 256},
+    # sub-task -> prefix of task-token names (build-defined, shaped after an unverified recollection of upstream)
+    "singing_drum_v1": {"channels": 1, "max_tokens": 1024, "subtasks": {
+        "default": ("transcribe_all", "task"),
+        "singing-only": ("transcribe_singing", "task"),
+        "drum-only": ("transcribe_drum", "task"),
+    }},
 }
 
 
+def default_task_token_ids(codec: Codec) -> Dict[str, int]:
+    return {name: codec.size + i for i, name in enumerate(TASK_TOKEN_NAMES)}
+
+
 class NoteEventTokenizer:
-    def __init__(self, codec: Codec):
+    def __init__(self, codec: Codec, skip_ids: Iterable[int] = ()):
         self.codec = codec
+        self.skip_ids = frozenset(int(i) for i in skip_ids)     # task-token ids: skipped when decoding (neither events nor invalid)
 
     # ---------------------------------------------------------------- notes -> tokens (for tests / data)
     def encode_segment(self, events: Sequence[NoteEvent], tie_notes: Sequence[Tuple[int, int]], start_sec: float,
@@ -108,6 +130,8 @@ class NoteEventTokenizer:
             tk = int(tk)
             if tk in (EOS, PAD):
                 break
+            if tk in self.skip_ids:
+                continue
             ev = c.decode(tk)
             if ev.type == "special":                       # UNK or an id beyond the codec
                 bad += 1
@@ -177,16 +201,45 @@ def note_events_to_notes(segments: Sequence[Tuple[float, List[NoteEvent], List[T
 
 
 class TaskManager:
-    def __init__(self, task_name: str = "mt3_full_plus", max_shift_steps: int = 206, debug_mode: bool = False):
+    """`vocab_size`: the decoder head the task-token ids must fit in; `task_token_ids`: name -> id entries replacing the
+    build-defined defaults (default_task_token_ids), e.g. the ids a real checkpoint was trained with."""
+
+    def __init__(self, task_name: str = "mt3_full_plus", max_shift_steps: int = 206, debug_mode: bool = False,
+                 vocab_size: int = DEFAULT_VOCAB, task_token_ids: Optional[Dict[str, int]] = None):
         if task_name not in TASKS:
             raise ValueError(f"unknown task {task_name!r}; known: {sorted(TASKS)}")
         self.task_name = task_name
         self.task = TASKS[task_name]
         self.codec = Codec(max_shift_steps=max_shift_steps)
-        self.tokenizer = NoteEventTokenizer(self.codec)
+        self.subtasks: Dict[str, Tuple[str, ...]] = dict(self.task.get("subtasks", {}))
+        self.task_token_ids: Dict[str, int] = {}
+        if self.subtasks:
+            ids = default_task_token_ids(self.codec)
+            for name, i in (task_token_ids or {}).items():
+                if name not in ids:
+                    raise ValueError(f"unknown task token {name!r}; known: {list(TASK_TOKEN_NAMES)}")
+                ids[name] = int(i)
+            bad = {n: i for n, i in ids.items() if not (NUM_SPECIAL <= i < vocab_size)}
+            if bad:
+                raise ValueError(f"task-token ids {bad} do not fit a vocabulary of {vocab_size} (specials below {NUM_SPECIAL})")
+            if len(set(ids.values())) != len(ids) or any(i < self.codec.size for i in ids.values()):
+                raise ValueError(f"task-token ids {ids} must be distinct and must not reuse a codec event id (< {self.codec.size})")
+            self.task_token_ids = ids
+        self.tokenizer = NoteEventTokenizer(self.codec, self.task_token_ids.values())
         self.num_decoding_channels = self.task["channels"]
         self.max_note_token_length = self.task["max_tokens"]
         self.debug_mode = debug_mode
+
+    def task_prompt(self, subtask: Optional[str] = None, n_segments: int = 1) -> np.ndarray:
+        """(n_segments, channels, P) int32 task-token prefix of `subtask` (None: "default") for YourMT3.inference(task_tokens=...).
+        A task without task tokens has no prompt: it raises."""
+        if not self.subtasks:
+            raise ValueError(f"task {self.task_name!r} defines no task tokens")
+        name = "default" if subtask is None else subtask
+        if name not in self.subtasks:
+            raise ValueError(f"unknown sub-task {name!r} of {self.task_name!r}; known: {sorted(self.subtasks)}")
+        ids = np.array([self.task_token_ids[t] for t in self.subtasks[name]], np.int32)
+        return np.array(np.broadcast_to(ids, (int(n_segments), self.num_decoding_channels, ids.size)))     # (a writable copy)
 
     def channel_of_program(self, program: int) -> int:
         if self.num_decoding_channels == 1:

@@ -16,9 +16,11 @@ from .task_manager import TaskManager
 
 def transcribe(model, audio_info: Union[str, dict, np.ndarray], task_manager: Optional[TaskManager] = None, bsz: int = 8,
                output_dir: str = ".", max_token_length: Optional[int] = None, return_notes: bool = False,
-               continuous: bool = False):
+               continuous: bool = False, subtask: Optional[str] = None):
     """`continuous=True` decodes the file's segments through `bsz` slots with continuous batching
-    (YourMT3.inference_stream: segments leave at EOS and the next ones enter) instead of fixed batches; same ids."""
+    (YourMT3.inference_stream: segments leave at EOS and the next ones enter) instead of fixed batches; same ids.
+    `subtask`: for a task-conditioned TaskManager (e.g. "singing_drum_v1"), the sub-task whose task tokens prompt every
+    segment's decode (None: its "default"); tasks without task tokens take no prompt and refuse a subtask."""
     cfg = model.cfg
     if task_manager is None:
         task_manager = TaskManager("mc13_full_plus_256" if cfg.n_channels == 13 else "mt3_full_plus")
@@ -37,11 +39,18 @@ def transcribe(model, audio_info: Union[str, dict, np.ndarray], task_manager: Op
     segments = model.ingest(torch.from_numpy(np.ascontiguousarray(x)), sr)
     n_samples = model.last_ingest_samples
     start_secs = [i * cfg.segment_samples / cfg.sample_rate for i in range(segments.shape[0])]
-    L = max_token_length or task_manager.max_note_token_length
+    prompt = None
+    if task_manager.subtasks:
+        prompt = torch.tensor(task_manager.task_prompt(subtask, 1)[0, 0])             # (P,): the same prefix for every segment
+    elif subtask is not None:
+        raise ValueError(f"task {task_manager.task_name!r} has no sub-tasks (asked for {subtask!r})")
+    n_prompt = 0 if prompt is None else int(prompt.numel())
+    L = min(max_token_length or task_manager.max_note_token_length, cfg.max_decode_len - n_prompt)
+    kw = {} if prompt is None else {"task_tokens": prompt}
     if continuous:
-        batches = [model.inference_stream(segments, max_token_length=min(L, cfg.max_decode_len), slots=bsz).cpu().numpy()]
+        batches = [model.inference_stream(segments, max_token_length=L, slots=bsz, **kw).cpu().numpy()]
     else:
-        batches = model.inference_file(bsz, segments, max_token_length=min(L, cfg.max_decode_len))
+        batches = model.inference_file(bsz, segments, max_token_length=L, **kw)
     notes = task_manager.tokens_to_notes(batches, start_secs, end_sec=n_samples / cfg.sample_rate)
     os.makedirs(output_dir, exist_ok=True)
     midi_path = write_midi(notes, os.path.join(output_dir, name + ".mid"))
