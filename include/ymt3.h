@@ -13,6 +13,8 @@
  *   encoder forward                      ->  ymt3_encode()
  *   decoder generate (greedy, KV cache)  ->  ymt3_decode_greedy()
  *   inference(x, task_tokens, ...)       ->  ymt3_transcribe_segments_prompted() / ymt3_decode_prompted()
+ *   generate(output_scores=True) + compute_transition_scores(normalize_logits=True)
+ *                                        ->  ymt3_transcribe_segments_scored() / ymt3_decode_scored()
  *
  * Conventions
  *   - every pointer named *_dev is DEVICE memory on the handle's GPU, owned by the caller;
@@ -118,6 +120,29 @@ int ymt3_transcribe_segments_prompted(ymt3_handle h, const float* audio_dev, int
 /* As ymt3_transcribe_stream; prompt_dev is (n_segments, n_channels, n_prompt), each segment's rows fed their own prompt. */
 int ymt3_transcribe_stream_prompted(ymt3_handle h, const float* audio_dev, int n_segments, int n_steps, const int32_t* prompt_dev,
                                     int n_prompt, int32_t* tokens_dev, int slots, int interval, void* stream);
+
+/* Token scores: the log-probability of every emitted step, from the same f32 logits the argmax reads (HF `generate(output_scores=
+ * True)` + `compute_transition_scores(normalize_logits=True)`), without writing the logits themselves.
+ *   - scores_dev: (B, n_channels, n_steps) f32 on the device, indexed exactly as tokens_dev (emitted steps only; in
+ *     ymt3_transcribe_stream_scored (n_segments, n_channels, n_steps)).
+ *   - score[r][col] = log_softmax(logits of that step)[id], where id is the id fed to the next step: the emitted argmax token
+ *     when the call is not forced, forced[r][col] (clamped into [0, vocab) like the feed) when it is.  Unforced scores are the
+ *     log-probabilities of the emitted tokens, always <= 0; with forcing, the sum of a row is the teacher-forced
+ *     log-likelihood of the forced sequence.
+ *   - an unforced row that has already finished (EOS emitted, eos_id >= 0) scores its PAD columns exactly 0.0.
+ *   - columns never launched score 0.0, like their PAD ids: the tail after an early stop (ymt3_set_early_stop) and the tail of
+ *     a retired segment in ymt3_transcribe_stream_scored.
+ *   - prompt positions write nothing, as for tokens.
+ *   - a call whose ids are poisoned to INT32_MIN (ymt3_set_abort_recovery(h, 0)) has NaN scores.
+ *   - the ids are bit-identical with and without scores_dev, in every decode regime; scores_dev == NULL makes each entry point
+ *     exactly its *_prompted counterpart (which are these calls with scores_dev = NULL).
+ * The kernels read the scores pointer from device memory: no captured graph depends on it. */
+int ymt3_decode_scored(ymt3_handle h, const void* enc_dev, int B, int n_steps, const int32_t* prompt_dev, int n_prompt,
+                       int32_t* tokens_dev, float* scores_dev, const int32_t* forced_dev, float* logits_dev, void* stream);
+int ymt3_transcribe_segments_scored(ymt3_handle h, const float* audio_dev, int B, int n_steps, const int32_t* prompt_dev,
+                                    int n_prompt, int32_t* tokens_dev, float* scores_dev, void* stream);
+int ymt3_transcribe_stream_scored(ymt3_handle h, const float* audio_dev, int n_segments, int n_steps, const int32_t* prompt_dev,
+                                  int n_prompt, int32_t* tokens_dev, float* scores_dev, int slots, int interval, void* stream);
 
 /* Opt-in early stop (first step): with eos_id >= 0 and interval > 0, ymt3_decode_greedy /
  * ymt3_transcribe_segments check on the host every `interval` steps whether every row has emitted EOS and stop

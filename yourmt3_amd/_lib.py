@@ -18,6 +18,7 @@ SYMBOLS = [
     "ymt3_ingest_plan", "ymt3_ingest", "ymt3_transcribe_stream", "ymt3_debug_step_stamps", "ymt3_debug_kernel_stamps",
     "ymt3_set_abort_recovery", "ymt3_merged_fallbacks", "ymt3_debug_moe_trace", "ymt3_last_decode_chains",
     "ymt3_decode_prompted", "ymt3_transcribe_segments_prompted", "ymt3_transcribe_stream_prompted",
+    "ymt3_decode_scored", "ymt3_transcribe_segments_scored", "ymt3_transcribe_stream_scored",
 ]
 
 _lib = None
@@ -77,6 +78,12 @@ def load() -> ctypes.CDLL:
     lib.ymt3_transcribe_segments_prompted.restype = i32
     lib.ymt3_transcribe_stream_prompted.argtypes = [vp, vp, i32, i32, vp, i32, vp, i32, i32, vp]
     lib.ymt3_transcribe_stream_prompted.restype = i32
+    lib.ymt3_decode_scored.argtypes = [vp, vp, i32, i32, vp, i32, vp, vp, vp, vp, vp]
+    lib.ymt3_decode_scored.restype = i32
+    lib.ymt3_transcribe_segments_scored.argtypes = [vp, vp, i32, i32, vp, i32, vp, vp, vp]
+    lib.ymt3_transcribe_segments_scored.restype = i32
+    lib.ymt3_transcribe_stream_scored.argtypes = [vp, vp, i32, i32, vp, i32, vp, vp, i32, i32, vp]
+    lib.ymt3_transcribe_stream_scored.restype = i32
     lib.ymt3_debug_step_stamps.argtypes = [vp, vp, vp, vp, ctypes.POINTER(ctypes.c_int)]
     lib.ymt3_debug_step_stamps.restype = i32
     lib.ymt3_debug_kernel_stamps.argtypes = [vp, i32, vp, i32]

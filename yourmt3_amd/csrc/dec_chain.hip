@@ -35,9 +35,12 @@ __global__ __launch_bounds__(512) void dec_chain_kernel(const bf16_t* __restrict
     chain_stages<MODE3, W2F>(pW0, pW1, pW2, pW3, pAttn, pH, row0, R, c, smem, blockIdx.x);
 }
 
-__global__ void chain_poison_kernel(const unsigned* sync, int32_t* tokens, long long n) {
+__global__ void chain_poison_kernel(const unsigned* sync, int32_t* tokens, float* scores, long long n) {
     if (sync[CHAIN_ABORT_WORD] == 0u) return;
-    for (long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (long long)gridDim.x * blockDim.x) tokens[i] = INT32_MIN;
+    for (long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (long long)gridDim.x * blockDim.x) {
+        tokens[i] = INT32_MIN;
+        if (scores) scores[i] = __builtin_nanf("");
+    }
 }
 
 constexpr size_t CHAIN_LDS = (size_t)(8 * 16 * 16 + 16) * 4 + (size_t)8 * 2 * 16 * (2048 / 8 * 2 + 16);     // stage 2's; the NORM stages need less
@@ -95,8 +98,8 @@ int launch_dec_chain(const ChainArgs& c, hipStream_t stream) {
     return 0;
 }
 
-int launch_chain_poison(const unsigned* sync, int32_t* tokens, long long n, hipStream_t stream) {
+int launch_chain_poison(const unsigned* sync, int32_t* tokens, float* scores, long long n, hipStream_t stream) {
     if (!sync || !tokens || n <= 0) return 0;
-    chain_poison_kernel<<<64, 256, 0, stream>>>(sync, tokens, n);
+    chain_poison_kernel<<<64, 256, 0, stream>>>(sync, tokens, scores, n);
     return 0;
 }

@@ -23,7 +23,8 @@
 //                       (:2928-2929), token store, next-token embedding gather into the residual
 //                       stream, and the step counter advance by the last workgroup to finish.  The first
 //                       n_prompt steps of a call (a task prompt, HF `decoder_input_ids` after the start id)
-//                       feed the caller's ids instead and emit nothing.
+//                       feed the caller's ids instead and emit nothing.  With a scores buffer it also writes
+//                       log_softmax(logits)[fed id] per emitted token: a second pass over the row for sum(exp(v - max)).
 //
 // Oracle: oracle/ymt3_oracle.py::decoder_step / greedy_decode.
 #include <cstdlib>
@@ -988,6 +989,7 @@ __global__ __launch_bounds__(256) void argmax_embed_kernel(const float* __restri
     __shared__ float sv[4];
     __shared__ int si[4];
     __shared__ int s_feed;
+    __shared__ float s_sum[4];             // the score pass's wave partials (sv is embed_row's scratch by then)
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int r = row0 + blockIdx.x;
     DecodeShared* sh = pShared;
@@ -1000,6 +1002,8 @@ __global__ __launch_bounds__(256) void argmax_embed_kernel(const float* __restri
     const int32_t* const forced = sh->forced;
     float* const logits_out = sh->logits_out;
     const int32_t* const prompt = sh->prompt;
+    // (unconditionally, with the other pointers: with scores off this load is the only change to the kernel)
+    float* const scores_out = sh->scores_out;
     const int was_finished = pFinished[r];
     const int forced_tok = forced && col >= 0 ? forced[(size_t)r * n_steps + col] : 0;
     // (a prompt id is read by thread 0 behind the argmax, at prompt positions only.  Requested here, its conditional load split
@@ -1033,6 +1037,10 @@ __global__ __launch_bounds__(256) void argmax_embed_kernel(const float* __restri
 #undef ARGMAX_TAKE
     if (lane == 63) { sv[wave] = bv; si[wave] = bi; }
     __syncthreads();
+    // score pass: the row maximum is the argmax value (every thread takes it now: embed_row reuses sv below)
+    const float row_max = scores_out ? fmaxf(fmaxf(sv[0], sv[1]), fmaxf(sv[2], sv[3])) : 0.f;
+    long long score_at = -1;               // thread 0: where this step's score goes (-1: nowhere) ...
+    int score_id = -1;                     // ... and the id it scores (-1: 0.0, an unforced row after its EOS)
     if (tid == 0) { bv = sv[0]; bi = si[0]; }      // (the wave's pair sits in its last row)
     if (tid == 0 && pRowPos) {
         // slot mode: this row's own position; a stopped row writes nothing and stays where it is (its slot is refilled
@@ -1050,6 +1058,8 @@ __global__ __launch_bounds__(256) void argmax_embed_kernel(const float* __restri
             if ((a.eos_id >= 0 && bi == a.eos_id) || p + 1 >= n_steps) pFinished[r] = 1;
             else pRowPos[r] = pos0 + 1;
             feed = bi;
+            score_at = out0 + p;
+            score_id = bi;
         }
         s_feed = feed < 0 ? 0 : (feed >= V ? V - 1 : feed);
     } else if (tid == 0 && col < 0) {
@@ -1067,7 +1077,10 @@ __global__ __launch_bounds__(256) void argmax_embed_kernel(const float* __restri
         }
         tokens_out[(size_t)r * n_steps + col] = tok;
         int feed = forced ? forced_tok : tok;
-        s_feed = feed < 0 ? 0 : (feed >= V ? V - 1 : feed);       // caller-supplied ids must not index outside the table
+        feed = feed < 0 ? 0 : (feed >= V ? V - 1 : feed);         // caller-supplied ids must not index outside the table
+        s_feed = feed;
+        score_at = (long long)r * n_steps + col;
+        score_id = !forced && a.eos_id >= 0 && was_finished ? -1 : feed;
     }
     __syncthreads();
     const int feed = s_feed;
@@ -1078,12 +1091,21 @@ __global__ __launch_bounds__(256) void argmax_embed_kernel(const float* __restri
         float* dst = logits_out + ((size_t)r * n_steps + col) * V;
         for (int i = tid; i < V; i += 256) dst[i] = row[i];
     }
+    if (scores_out) {
+        // log-sum-exp of the row the argmax read (still in cache): per-thread partials, the wave butterfly, the 4 waves below
+        float q = 0.f;
+        for (int i = tid; i < V; i += 256) q += __expf(row[i] - row_max);
+        q = wave_sum(q);
+        if (lane == 0) s_sum[wave] = q;
+    }
     // the per-step kernel's arrival counters (dec_step.hip), left at zero for the next step's launch
     if (a.zero_sync)
         for (int i = blockIdx.x * 256 + tid; i < a.zero_lines; i += gridDim.x * 256) a.zero_sync[(size_t)i * CHAIN_LINE] = 0u;
     // the last workgroup to finish advances the position; every workgroup has read `t` by then
     __syncthreads();
     if (tid == 0) {
+        if (scores_out && score_at >= 0)           // (the barrier above also published s_sum)
+            scores_out[score_at] = score_id < 0 ? 0.f : (row[score_id] - row_max) - __logf((s_sum[0] + s_sum[1]) + (s_sum[2] + s_sum[3]));
         if (a.eos_id >= 0) __threadfence();      // only the flags the last arriver counts below need to be visible to it
         // Who is last?  One atomic per workgroup on ONE word serialises at the memory side (~12 ns each: 10 us of the 13-channel decoder's
         // 832 workgroups); beyond 64 workgroups groups of 32 count on lines of their own and only each group's last one takes the shared ticket.
@@ -1113,7 +1135,8 @@ __global__ __launch_bounds__(256) void argmax_embed_kernel(const float* __restri
 }
 
 __global__ __launch_bounds__(256) void decode_init_kernel(ArgmaxArgs a, int n_chains, int n_steps, int step0, int32_t* tokens_out,
-                                                          const int32_t* forced, float* logits_out, const int32_t* prompt, int n_prompt) {
+                                                          const int32_t* forced, float* logits_out, const int32_t* prompt, int n_prompt,
+                                                          float* scores_out) {
     const int r = blockIdx.x, tid = threadIdx.x;
     const bf16_t* e = a.embed + (size_t)a.pad_id * a.d;
     const bf16_t* c = a.chan_embed ? a.chan_embed + (size_t)(r % a.n_channels) * a.d : nullptr;
@@ -1132,6 +1155,7 @@ __global__ __launch_bounds__(256) void decode_init_kernel(ArgmaxArgs a, int n_ch
         sh->logits_out = logits_out;
         sh->prompt = prompt;
         sh->n_prompt = n_prompt;
+        sh->scores_out = scores_out;
     }
 }
 
@@ -1150,15 +1174,21 @@ __global__ __launch_bounds__(256) void slot_start_kernel(ArgmaxArgs a, int row0,
     }
 }
 
-__global__ void slot_retire_kernel(ArgmaxArgs a, int row0, int n_steps, int n_prompt, int32_t* tokens_out) {
+__global__ void slot_retire_kernel(ArgmaxArgs a, int row0, int n_steps, int n_prompt, int32_t* tokens_out, float* scores_out) {
     const int r = row0 + blockIdx.x;
-    int32_t* row = tokens_out + a.row_out[r];
-    for (int i = max(a.row_pos[r] + 1 - n_prompt, 0) + threadIdx.x; i < n_steps; i += blockDim.x) row[i] = a.pad_id;
+    const long long o = a.row_out[r];
+    for (int i = max(a.row_pos[r] + 1 - n_prompt, 0) + threadIdx.x; i < n_steps; i += blockDim.x) {
+        tokens_out[o + i] = a.pad_id;
+        if (scores_out) scores_out[o + i] = 0.f;
+    }
 }
 
-__global__ void pad_tail_kernel(int32_t* tokens_out, int row0, int n_steps, int from, int pad_id) {
-    int32_t* row = tokens_out + (size_t)(row0 + blockIdx.x) * n_steps;
-    for (int i = from + threadIdx.x; i < n_steps; i += blockDim.x) row[i] = pad_id;
+__global__ void pad_tail_kernel(int32_t* tokens_out, float* scores_out, int row0, int n_steps, int from, int pad_id) {
+    const size_t o = (size_t)(row0 + blockIdx.x) * n_steps;
+    for (int i = from + threadIdx.x; i < n_steps; i += blockDim.x) {
+        tokens_out[o + i] = pad_id;
+        if (scores_out) scores_out[o + i] = 0.f;
+    }
 }
 
 template <int MODE, int K, int NT, bool PEND = false>
@@ -1326,10 +1356,10 @@ int launch_argmax_embed(const ArgmaxArgs& a, hipStream_t stream) {
 }
 
 int launch_decode_init(const ArgmaxArgs& a, int n_chains, int n_steps, int step0, int32_t* tokens_out, const int32_t* forced,
-                       float* logits_out, const int32_t* prompt, int n_prompt, hipStream_t stream) {
+                       float* logits_out, const int32_t* prompt, int n_prompt, float* scores_out, hipStream_t stream) {
     if (a.R <= 0) return 0;
     if (n_prompt < 0 || (n_prompt > 0 && !prompt)) return -1;
-    decode_init_kernel<<<a.R, 256, 0, stream>>>(a, n_chains, n_steps, step0, tokens_out, forced, logits_out, prompt, n_prompt);
+    decode_init_kernel<<<a.R, 256, 0, stream>>>(a, n_chains, n_steps, step0, tokens_out, forced, logits_out, prompt, n_prompt, scores_out);
     return 0;
 }
 
@@ -1340,14 +1370,15 @@ int launch_slot_start(const ArgmaxArgs& a, int row0, long long first_out, int n_
     return 0;
 }
 
-int launch_slot_retire(const ArgmaxArgs& a, int row0, int n_rows, int n_steps, int n_prompt, int32_t* tokens_out, hipStream_t stream) {
+int launch_slot_retire(const ArgmaxArgs& a, int row0, int n_rows, int n_steps, int n_prompt, int32_t* tokens_out, float* scores_out,
+                       hipStream_t stream) {
     if (!a.row_pos || !a.row_out || n_rows <= 0) return -1;
-    slot_retire_kernel<<<n_rows, 256, 0, stream>>>(a, row0, n_steps, n_prompt, tokens_out);
+    slot_retire_kernel<<<n_rows, 256, 0, stream>>>(a, row0, n_steps, n_prompt, tokens_out, scores_out);
     return 0;
 }
 
-int launch_pad_tail(int32_t* tokens_out, int row0, int R, int n_steps, int from, int pad_id, hipStream_t stream) {
+int launch_pad_tail(int32_t* tokens_out, float* scores_out, int row0, int R, int n_steps, int from, int pad_id, hipStream_t stream) {
     if (R <= 0 || from >= n_steps) return 0;
-    pad_tail_kernel<<<R, 256, 0, stream>>>(tokens_out, row0, n_steps, from, pad_id);
+    pad_tail_kernel<<<R, 256, 0, stream>>>(tokens_out, scores_out, row0, n_steps, from, pad_id);
     return 0;
 }

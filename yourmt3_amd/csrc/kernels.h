@@ -80,7 +80,7 @@ int launch_spec_embed(const float* mel, const float* w, const bf16_t* pos, const
 struct DecodeShared {           // device-resident loop state, read by every decode kernel
     int step;                   // position being decoded (tokens already in the cache)
     int done_count;             // ticket counter of the argmax kernel
-    int n_steps;                // row stride of tokens_out / forced / logits_out
+    int n_steps;                // row stride of tokens_out / forced / logits_out / scores_out
     int step0;                  // first position of this call (0 except under the debug hook ymt3_debug_decode_start)
     int n_unfinished;           // rows of this chain that have not emitted EOS yet (maintained when eos_id >= 0)
     int n_prompt;               // P: the first P steps of the call feed prompt ids and emit nothing (0: none)
@@ -88,6 +88,7 @@ struct DecodeShared {           // device-resident loop state, read by every dec
     const int32_t* forced;      // [R][n_steps] or null
     float* logits_out;          // [R][n_steps][V] or null
     const int32_t* prompt;      // [R][n_prompt] (lock-step) or indexed through row_prompt (slot mode); null when n_prompt = 0
+    float* scores_out;          // [R][n_steps] log_softmax(logits)[fed id] per emitted token (indexed as tokens_out), or null
 };
 
 constexpr int SSQ_TILES = 32;    // sum(h^2) partials per row = d_model / 16 column tiles of the RESID epilogue
@@ -154,7 +155,8 @@ int init_chain_kernels();
 bool dec_chain_fits(int n_cus);                 // occupancy x CUs covers the chain's grid (all its workgroups wait for each other)
 bool dec_attention_pair_fits(int n_cus);        // the same for the attention pair at 64 rows
 int launch_dec_chain(const ChainArgs& c, hipStream_t stream);       // 0 launched, < 0: not this kernel's shape
-int launch_chain_poison(const unsigned* sync, int32_t* tokens, long long n, hipStream_t stream);   // tokens = INT32_MIN if the chain aborted
+// tokens = INT32_MIN (and scores, if not null, = NaN) if the chain aborted
+int launch_chain_poison(const unsigned* sync, int32_t* tokens, float* scores, long long n, hipStream_t stream);
 
 // One decode step's layers as ONE launch (dec_step.hip): per layer the attention pair and the GEMM chain, handed over inside the kernel.
 struct StepLayer {
@@ -262,17 +264,19 @@ struct ArgmaxArgs {
     const long long* row_prompt;   // slot mode, or null: [R] offset of the row's prompt (see row_pos)
 };
 int launch_argmax_embed(const ArgmaxArgs& a, hipStream_t stream);
-// tokens_out[r][from .. n_steps) = pad for rows [row0, row0 + R): the tail of a decode that stopped early (`from`: emitted index)
-int launch_pad_tail(int32_t* tokens_out, int row0, int R, int n_steps, int from, int pad_id, hipStream_t stream);
+// tokens_out[r][from .. n_steps) = pad (scores_out, if not null: 0.0) for rows [row0, row0 + R): the tail of a decode that stopped
+// early (`from`: emitted index)
+int launch_pad_tail(int32_t* tokens_out, float* scores_out, int row0, int R, int n_steps, int from, int pad_id, hipStream_t stream);
 // slot mode: (re)start rows [row0, row0 + n_channels) on a new segment: h = embed[pad] (+ channel), position 0,
 // finished = 0, row_out = first_out + channel * n_steps, row_prompt = first_prompt + channel * n_prompt
 int launch_slot_start(const ArgmaxArgs& a, int row0, long long first_out, int n_steps, long long* row_out, long long first_prompt,
                       int n_prompt, long long* row_prompt, hipStream_t stream);
-// slot mode: PAD the unwritten tail [row_pos + 1 - n_prompt, n_steps) of rows [row0, row0 + n_rows)
-int launch_slot_retire(const ArgmaxArgs& a, int row0, int n_rows, int n_steps, int n_prompt, int32_t* tokens_out, hipStream_t stream);
+// slot mode: PAD the unwritten tail [row_pos + 1 - n_prompt, n_steps) of rows [row0, row0 + n_rows) (scores_out, if not null: 0.0)
+int launch_slot_retire(const ArgmaxArgs& a, int row0, int n_rows, int n_steps, int n_prompt, int32_t* tokens_out, float* scores_out,
+                       hipStream_t stream);
 // all rows: h[r] = embed[pad] (+ chan_embed), finished = 0; a.shared[0..n_chains) reset (prompt / n_prompt: every chain's)
 int launch_decode_init(const ArgmaxArgs& a, int n_chains, int n_steps, int step0, int32_t* tokens_out, const int32_t* forced,
-                       float* logits_out, const int32_t* prompt, int n_prompt, hipStream_t stream);
+                       float* logits_out, const int32_t* prompt, int n_prompt, float* scores_out, hipStream_t stream);
 
 // ---------------------------------------------------------------- MoE decoder FFN (moe.hip)
 struct MoeArgs {

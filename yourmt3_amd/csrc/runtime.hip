@@ -923,22 +923,23 @@ static int launch_step(ymt3_handle h, int B, int row0, int R, DecodeShared* shar
 }
 
 static int decode_run(ymt3_handle h, const bf16_t* enc, int B, int n_steps, const int32_t* prompt, int n_prompt, int32_t* tokens,
-                      const int32_t* forced, float* logits_out, hipStream_t s, int prof_stride, int step0);
+                      float* scores, const int32_t* forced, float* logits_out, hipStream_t s, int prof_stride, int step0);
 
 // A call launches n_prompt + n_steps steps: the first n_prompt feed prompt[r][t] and emit nothing (argmax_embed_kernel), the rest
-// emit tokens 0 .. n_steps-1.  n_prompt = 0 is the plain decode.
+// emit tokens 0 .. n_steps-1.  n_prompt = 0 is the plain decode.  `scores` (or null): [R][n_steps] f32, the log-probability of the id
+// fed after each emitted token (include/ymt3.h, token scores), written by the same kernels as the tokens.
 static int decode_impl(ymt3_handle h, const bf16_t* enc, int B, int n_steps, const int32_t* prompt, int n_prompt, int32_t* tokens,
-                       const int32_t* forced, float* logits_out, hipStream_t s, int prof_stride = 0) {
+                       float* scores, const int32_t* forced, float* logits_out, hipStream_t s, int prof_stride = 0) {
     const int step0 = h->prof_step0;          // one shot (debug hook): consumed by this call whatever its outcome
     h->prof_step0 = 0;
     if (n_prompt < 0) FAIL(YMT3_ERR_ARG, "n_prompt=%d < 0", n_prompt);
     if (n_prompt > 0 && !prompt) FAIL(YMT3_ERR_ARG, "n_prompt=%d with a null prompt", n_prompt);
     if (n_prompt > 0 && step0 > 0) FAIL(YMT3_ERR_ARG, "ymt3_debug_decode_start does not combine with a prompt (n_prompt=%d)", n_prompt);
-    return decode_run(h, enc, B, n_steps, prompt, n_prompt, tokens, forced, logits_out, s, prof_stride, step0);
+    return decode_run(h, enc, B, n_steps, prompt, n_prompt, tokens, scores, forced, logits_out, s, prof_stride, step0);
 }
 
 static int decode_run(ymt3_handle h, const bf16_t* enc, int B, int n_steps, const int32_t* prompt, int n_prompt, int32_t* tokens,
-                      const int32_t* forced, float* logits_out, hipStream_t s, int prof_stride, int step0) {
+                      float* scores, const int32_t* forced, float* logits_out, hipStream_t s, int prof_stride, int step0) {
     const ymt3_config& k = h->cfg;
     bool merged = false;                      // some step of this call ran merged kernels
     if (n_steps <= 0 || step0 + n_prompt + n_steps > k.max_decode_len)
@@ -962,7 +963,7 @@ static int decode_run(ymt3_handle h, const bf16_t* enc, int B, int n_steps, cons
     if (n_chains > R) n_chains = R;
     h->last_chains = n_chains;
     if (h->step_kernel && h->step_sync) HIP_TRY(hipMemsetAsync(h->step_sync, 0, (size_t)STEP_SYNC_LINES * CHAIN_LINE * sizeof(unsigned), s));
-    LAUNCH(launch_decode_init(a, n_chains, n_steps, step0, tokens, forced, logits_out, prompt, n_prompt, s));
+    LAUNCH(launch_decode_init(a, n_chains, n_steps, step0, tokens, forced, logits_out, prompt, n_prompt, scores, s));
     h->last_steps = n_total;
     int row0[9];
     row0[0] = 0;
@@ -1029,7 +1030,7 @@ static int decode_run(ymt3_handle h, const bf16_t* enc, int B, int n_steps, cons
                 if (*h->host_flag == 0) break;
             }
             h->last_steps = n_prompt + t;
-            LAUNCH(launch_pad_tail(tokens, 0, R, n_steps, t, k.pad_id, s));
+            LAUNCH(launch_pad_tail(tokens, scores, 0, R, n_steps, t, k.pad_id, s));
         } else if (n_chains == 1) {
             // graph_steps consecutive steps are ONE replayed graph (every kernel reads the position from device memory, so a graph of G
             // steps is the step's kernels G times): the boundary between two graph launches costs ~7 us of stream time that a kernel
@@ -1112,7 +1113,7 @@ static int decode_run(ymt3_handle h, const bf16_t* enc, int B, int n_steps, cons
     }
     if (merged) {
         // a merged launch that gave up on a stage (dec_chain.hip, dec_attn_pair_kernel) must not leave plausible ids behind
-        LAUNCH(launch_chain_poison(h->chain_sync, tokens, (long long)R * n_steps, s));
+        LAUNCH(launch_chain_poison(h->chain_sync, tokens, scores, (long long)R * n_steps, s));
         HIP_TRY(hipGetLastError());
         if (h->abort_recovery && prof_stride == 0) {
             // Recovery (ymt3_set_abort_recovery, default on): wait for the call's own work and look at the abort word.  Raised -- a
@@ -1123,7 +1124,7 @@ static int decode_run(ymt3_handle h, const bf16_t* enc, int B, int n_steps, cons
             if (h->chain_host_abort && *static_cast<volatile unsigned*>(h->chain_host_abort)) {
                 int rc = merged_fallback(h);
                 if (rc) return rc;
-                return decode_run(h, enc, B, n_steps, prompt, n_prompt, tokens, forced, logits_out, s, prof_stride, step0);
+                return decode_run(h, enc, B, n_steps, prompt, n_prompt, tokens, scores, forced, logits_out, s, prof_stride, step0);
             }
         } else if (h->forced_abort && h->chain_host_abort) {
             *h->chain_host_abort = 1u;            // asynchronous mode: the next call on the handle finds the word (check_call)
@@ -1134,14 +1135,19 @@ static int decode_run(ymt3_handle h, const bf16_t* enc, int B, int n_steps, cons
     return YMT3_OK;
 }
 
-extern "C" int ymt3_decode_prompted(ymt3_handle h, const void* enc_dev, int B, int n_steps, const int32_t* prompt_dev, int n_prompt,
-                                    int32_t* tokens_dev, const int32_t* forced_dev, float* logits_dev, void* stream) {
+extern "C" int ymt3_decode_scored(ymt3_handle h, const void* enc_dev, int B, int n_steps, const int32_t* prompt_dev, int n_prompt,
+                                  int32_t* tokens_dev, float* scores_dev, const int32_t* forced_dev, float* logits_dev, void* stream) {
     int rc = check_call(h, B);
     if (rc) return rc;
     if (B == 0) return YMT3_OK;
     if (!enc_dev || !tokens_dev) FAIL(YMT3_ERR_ARG, "null buffer");
-    return decode_impl(h, static_cast<const bf16_t*>(enc_dev), B, n_steps, prompt_dev, n_prompt, tokens_dev, forced_dev, logits_dev,
-                       (hipStream_t)stream);
+    return decode_impl(h, static_cast<const bf16_t*>(enc_dev), B, n_steps, prompt_dev, n_prompt, tokens_dev, scores_dev, forced_dev,
+                       logits_dev, (hipStream_t)stream);
+}
+
+extern "C" int ymt3_decode_prompted(ymt3_handle h, const void* enc_dev, int B, int n_steps, const int32_t* prompt_dev, int n_prompt,
+                                    int32_t* tokens_dev, const int32_t* forced_dev, float* logits_dev, void* stream) {
+    return ymt3_decode_scored(h, enc_dev, B, n_steps, prompt_dev, n_prompt, tokens_dev, nullptr, forced_dev, logits_dev, stream);
 }
 
 extern "C" int ymt3_decode_greedy(ymt3_handle h, const void* enc_dev, int B, int n_steps, int32_t* tokens_dev,
@@ -1149,8 +1155,8 @@ extern "C" int ymt3_decode_greedy(ymt3_handle h, const void* enc_dev, int B, int
     return ymt3_decode_prompted(h, enc_dev, B, n_steps, nullptr, 0, tokens_dev, forced_dev, logits_dev, stream);
 }
 
-extern "C" int ymt3_transcribe_segments_prompted(ymt3_handle h, const float* audio_dev, int B, int n_steps, const int32_t* prompt_dev,
-                                                 int n_prompt, int32_t* tokens_dev, void* stream) {
+extern "C" int ymt3_transcribe_segments_scored(ymt3_handle h, const float* audio_dev, int B, int n_steps, const int32_t* prompt_dev,
+                                               int n_prompt, int32_t* tokens_dev, float* scores_dev, void* stream) {
     int rc = check_call(h, B);
     if (rc) return rc;
     if (B == 0) return YMT3_OK;
@@ -1163,7 +1169,12 @@ extern "C" int ymt3_transcribe_segments_prompted(ymt3_handle h, const float* aud
     LAUNCH(launch_logmel(h->fe, audio_dev, h->mel, B, s));
     rc = encode_impl(h, h->mel, B, h->enc_out, s);
     if (rc) return rc;
-    return decode_impl(h, h->enc_out, B, n_steps, prompt_dev, n_prompt, tokens_dev, nullptr, nullptr, s);
+    return decode_impl(h, h->enc_out, B, n_steps, prompt_dev, n_prompt, tokens_dev, scores_dev, nullptr, nullptr, s);
+}
+
+extern "C" int ymt3_transcribe_segments_prompted(ymt3_handle h, const float* audio_dev, int B, int n_steps, const int32_t* prompt_dev,
+                                                 int n_prompt, int32_t* tokens_dev, void* stream) {
+    return ymt3_transcribe_segments_scored(h, audio_dev, B, n_steps, prompt_dev, n_prompt, tokens_dev, nullptr, stream);
 }
 
 extern "C" int ymt3_transcribe_segments(ymt3_handle h, const float* audio_dev, int B, int n_steps, int32_t* tokens_dev,
@@ -1176,8 +1187,8 @@ extern "C" int ymt3_transcribe_segments(ymt3_handle h, const float* audio_dev, i
 // `interval` steps, pads and retires segments whose rows have all stopped, and encodes the next pending segments straight
 // into the freed slots (log-mel + encoder batched over the admissions, cross-K/V written into each slot's slabs).  Rows are
 // independent in every kernel, so the ids equal those of lock-step batches bit for bit.
-extern "C" int ymt3_transcribe_stream_prompted(ymt3_handle h, const float* audio_dev, int n_segments, int n_steps, const int32_t* prompt_dev,
-                                               int n_prompt, int32_t* tokens_dev, int slots, int interval, void* stream) {
+extern "C" int ymt3_transcribe_stream_scored(ymt3_handle h, const float* audio_dev, int n_segments, int n_steps, const int32_t* prompt_dev,
+                                             int n_prompt, int32_t* tokens_dev, float* scores_dev, int slots, int interval, void* stream) {
     int rc = check_call(h, 0);
     if (rc) return rc;
     if (n_segments < 0) FAIL(YMT3_ERR_ARG, "n_segments=%d", n_segments);
@@ -1208,7 +1219,7 @@ extern "C" int ymt3_transcribe_stream_prompted(ymt3_handle h, const float* audio
     h->slot_mode = true;
     // loop state: every row starts stopped; admissions start them
     if (h->step_kernel && h->step_sync) HIP_TRY(hipMemsetAsync(h->step_sync, 0, (size_t)STEP_SYNC_LINES * CHAIN_LINE * sizeof(unsigned), s));
-    LAUNCH(launch_decode_init(a, 1, n_steps, 0, tokens_dev, nullptr, nullptr, prompt_dev, n_prompt, s));
+    LAUNCH(launch_decode_init(a, 1, n_steps, 0, tokens_dev, nullptr, nullptr, prompt_dev, n_prompt, scores_dev, s));
     HIP_TRY(hipMemsetD32Async(reinterpret_cast<hipDeviceptr_t>(h->finished), 1, (size_t)R, s));
     HIP_TRY(hipMemsetAsync(h->row_pos, 0, (size_t)R * sizeof(int), s));
     HIP_TRY(hipMemsetAsync(h->row_out, 0, (size_t)R * sizeof(long long), s));
@@ -1270,7 +1281,8 @@ extern "C" int ymt3_transcribe_stream_prompted(ymt3_handle h, const float* audio
             // a merged kernel gave up (the stream is idle here): start the queue again on the separate launches -- same ids
             rc = merged_fallback(h);
             if (rc) return rc;
-            return ymt3_transcribe_stream_prompted(h, audio_dev, n_segments, n_steps, prompt_dev, n_prompt, tokens_dev, slots, interval, stream);
+            return ymt3_transcribe_stream_scored(h, audio_dev, n_segments, n_steps, prompt_dev, n_prompt, tokens_dev, scores_dev, slots, interval,
+                                                 stream);
         }
         free_slots.clear();
         for (int slot = 0; slot < slots; ++slot) {
@@ -1278,7 +1290,7 @@ extern "C" int ymt3_transcribe_stream_prompted(ymt3_handle h, const float* audio
             bool all = true;
             for (int c = 0; c < K; ++c) all = all && h->host_rows[slot * K + c] != 0;
             if (!all) continue;
-            LAUNCH(launch_slot_retire(a, slot * K, K, n_steps, n_prompt, tokens_dev, s));
+            LAUNCH(launch_slot_retire(a, slot * K, K, n_steps, n_prompt, tokens_dev, scores_dev, s));
             slot_seg[(size_t)slot] = -1;
             --live;
             free_slots.push_back(slot);
@@ -1293,6 +1305,11 @@ extern "C" int ymt3_transcribe_stream_prompted(ymt3_handle h, const float* audio
     }
     HIP_TRY(hipGetLastError());
     return YMT3_OK;
+}
+
+extern "C" int ymt3_transcribe_stream_prompted(ymt3_handle h, const float* audio_dev, int n_segments, int n_steps, const int32_t* prompt_dev,
+                                               int n_prompt, int32_t* tokens_dev, int slots, int interval, void* stream) {
+    return ymt3_transcribe_stream_scored(h, audio_dev, n_segments, n_steps, prompt_dev, n_prompt, tokens_dev, nullptr, slots, interval, stream);
 }
 
 extern "C" int ymt3_transcribe_stream(ymt3_handle h, const float* audio_dev, int n_segments, int n_steps, int32_t* tokens_dev,
@@ -1317,7 +1334,7 @@ extern "C" int ymt3_profile_decode(ymt3_handle h, const void* enc_dev, int B, in
     hipStream_t s = (hipStream_t)stream;
     h->prof_ev.clear();
     h->prof_cls.clear();
-    rc = decode_impl(h, static_cast<const bf16_t*>(enc_dev), B, n_steps, nullptr, 0, tokens_dev, nullptr, nullptr, s, stride);
+    rc = decode_impl(h, static_cast<const bf16_t*>(enc_dev), B, n_steps, nullptr, 0, tokens_dev, nullptr, nullptr, nullptr, s, stride);
     hipError_t e = hipStreamSynchronize(s);
     for (int i = 0; i < YMT3_PROFILE_CLASSES; ++i) { ms_by_class[i] = 0.f; launches_by_class[i] = 0; }
     for (size_t i = 0; i < h->prof_cls.size(); ++i) {

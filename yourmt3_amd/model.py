@@ -160,9 +160,11 @@ class YourMT3:
         return enc
 
     def decode(self, enc: torch.Tensor, n_steps: Optional[int] = None, forced: Optional[torch.Tensor] = None,
-               return_logits: bool = False, prompt=None):
+               return_logits: bool = False, prompt=None, return_scores: bool = False):
         """Greedy decode of n_steps emitted tokens per row.  `prompt` ((P,), (B, P) or (B, K, P) ids): fed after the start id before
-        anything is emitted (HF decoder_input_ids = [pad, *prompt]); tokens / forced / logits index emitted steps only."""
+        anything is emitted (HF decoder_input_ids = [pad, *prompt]); tokens / forced / logits index emitted steps only.
+        Returns tokens, then logits if `return_logits`, then scores if `return_scores`: (B, K, n_steps) f32 log-probabilities of
+        the fed ids (the emitted ones, or `forced`'s), include/ymt3.h, token scores."""
         cfg = self.cfg
         enc = enc.to(self.device, torch.bfloat16).contiguous()
         B = enc.shape[0]
@@ -173,22 +175,35 @@ class YourMT3:
         if f is not None and tuple(f.shape) != (B, cfg.n_channels, n_steps):
             raise ValueError("forced must be (B, n_channels, n_steps)")
         lg = torch.empty(B, cfg.n_channels, n_steps, cfg.vocab, device=self.device, dtype=torch.float32) if return_logits else None
-        if p is None:
+        sc = torch.empty(B, cfg.n_channels, n_steps, device=self.device, dtype=torch.float32) if return_scores else None
+        if sc is not None:
+            _lib.check(self._lib.ymt3_decode_scored(self._handle, _ptr(enc), B, n_steps, _ptr(p), 0 if p is None else int(p.shape[-1]),
+                                                    _ptr(tokens), _ptr(sc), _ptr(f), _ptr(lg), self._stream()))
+        elif p is None:
             _lib.check(self._lib.ymt3_decode_greedy(self._handle, _ptr(enc), B, n_steps, _ptr(tokens), _ptr(f), _ptr(lg), self._stream()))
         else:
             _lib.check(self._lib.ymt3_decode_prompted(self._handle, _ptr(enc), B, n_steps, _ptr(p), int(p.shape[-1]), _ptr(tokens), _ptr(f),
                                                       _ptr(lg), self._stream()))
-        return (tokens, lg) if return_logits else tokens
+        out = (tokens,) + ((lg,) if return_logits else ()) + ((sc,) if return_scores else ())
+        return out if len(out) > 1 else tokens
 
     # ------------------------------------------------------------------ reference-shaped API
-    def inference(self, audio: torch.Tensor, task_tokens=None, max_token_length: Optional[int] = None) -> torch.Tensor:
+    def inference(self, audio: torch.Tensor, task_tokens=None, max_token_length: Optional[int] = None, return_scores: bool = False):
         """(B, 1, S) or (B, S) audio -> (B, K, L) int32 token ids: the whole hot path, one C call.  `task_tokens` ((P,), (B, P) or
-        (B, K, P) ids, e.g. TaskManager.task_prompt): the decoder is prompted with them and L tokens are emitted after them."""
+        (B, K, P) ids, e.g. TaskManager.task_prompt): the decoder is prompted with them and L tokens are emitted after them.
+        `return_scores`: returns (tokens, scores), scores (B, K, L) f32 the log-probability of every emitted token (0.0 for the
+        PAD after a row's EOS), as HF compute_transition_scores(normalize_logits=True)."""
         a = self._audio2d(audio)
         B = a.shape[0]
         L = int(max_token_length or self.cfg.max_decode_len)
         p = self._prompt(task_tokens, B, L)
         tokens = torch.empty(B, self.cfg.n_channels, L, device=self.device, dtype=torch.int32)
+        if return_scores:
+            scores = torch.empty(B, self.cfg.n_channels, L, device=self.device, dtype=torch.float32)
+            if B:
+                _lib.check(self._lib.ymt3_transcribe_segments_scored(self._handle, _ptr(a), B, L, _ptr(p), 0 if p is None else int(p.shape[-1]),
+                                                                     _ptr(tokens), _ptr(scores), self._stream()))
+            return tokens, scores
         if p is None:
             _lib.check(self._lib.ymt3_transcribe_segments(self._handle, _ptr(a), B, L, _ptr(tokens), self._stream()))
         elif B:
@@ -197,10 +212,10 @@ class YourMT3:
         return tokens
 
     def inference_stream(self, audio_segments: torch.Tensor, max_token_length: Optional[int] = None, slots: int = 0,
-                         interval: int = 8, task_tokens=None) -> torch.Tensor:
+                         interval: int = 8, task_tokens=None, return_scores: bool = False):
         """(N, 1, S) or (N, S) audio, any N -> (N, K, L) int32 ids with continuous batching: `slots` decoder slots are
         refilled from the queue as segments emit EOS (needs eos_id >= 0 to gain anything).  Ids equal inference()'s, with the
-        same `task_tokens` ((P,), (N, P) or (N, K, P))."""
+        same `task_tokens` ((P,), (N, P) or (N, K, P)).  `return_scores`: (tokens, scores) as inference()."""
         a = audio_segments[:, 0, :] if audio_segments.dim() == 3 else audio_segments
         if a.shape[-1] != self.cfg.segment_samples:
             raise ValueError(f"segments must have {self.cfg.segment_samples} samples, got {a.shape[-1]}")
@@ -209,6 +224,12 @@ class YourMT3:
         L = int(max_token_length or self.cfg.max_decode_len)
         p = self._prompt(task_tokens, N, L)
         tokens = torch.empty(N, self.cfg.n_channels, L, device=self.device, dtype=torch.int32)
+        if return_scores:
+            scores = torch.empty(N, self.cfg.n_channels, L, device=self.device, dtype=torch.float32)
+            if N:
+                _lib.check(self._lib.ymt3_transcribe_stream_scored(self._handle, _ptr(a), N, L, _ptr(p), 0 if p is None else int(p.shape[-1]),
+                                                                   _ptr(tokens), _ptr(scores), int(slots), int(interval), self._stream()))
+            return tokens, scores
         if p is None:
             _lib.check(self._lib.ymt3_transcribe_stream(self._handle, _ptr(a) if N else None, N, L, _ptr(tokens) if N else None,
                                                         int(slots), int(interval), self._stream()))
@@ -218,19 +239,25 @@ class YourMT3:
         return tokens
 
     def inference_file(self, bsz: int, audio_segments: torch.Tensor, max_token_length: Optional[int] = None,
-                       task_tokens=None) -> List[np.ndarray]:
+                       task_tokens=None, return_scores: bool = False):
         """Split (N, 1, S) segments into batches of `bsz`; one (b, K, L) int array per batch.  `task_tokens`: (P,) for every
-        segment, or (N, P) / (N, K, P), sliced with the batches."""
+        segment, or (N, P) / (N, K, P), sliced with the batches.  `return_scores`: (token_batches, score_batches), the second a
+        list of (b, K, L) float32 arrays (inference(return_scores=True))."""
         bsz = min(int(bsz), self.max_batch)
         N = audio_segments.shape[0]
         tt = None if task_tokens is None else torch.as_tensor(task_tokens)
         if tt is not None and tt.dim() > 1 and tt.shape[0] != N:
             raise ValueError(f"task_tokens has {tt.shape[0]} rows for {N} segments")
-        out = []
+        out, scores = [], []
         for i in range(0, N, bsz):
             ti = tt if tt is None or tt.dim() == 1 else tt[i:i + bsz]
-            out.append(self.inference(audio_segments[i:i + bsz], task_tokens=ti, max_token_length=max_token_length).cpu().numpy())
-        return out
+            if return_scores:
+                t, sc = self.inference(audio_segments[i:i + bsz], task_tokens=ti, max_token_length=max_token_length, return_scores=True)
+                out.append(t.cpu().numpy())
+                scores.append(sc.cpu().numpy())
+            else:
+                out.append(self.inference(audio_segments[i:i + bsz], task_tokens=ti, max_token_length=max_token_length).cpu().numpy())
+        return (out, scores) if return_scores else out
 
     PROFILE_CLASSES = ["qkv_cache_gemm", "self_attn", "self_o_gemm", "cross_q_gemm", "cross_attn", "cross_o_gemm",
                        "ffn_wi_gemm", "ffn_wo_gemm", "lm_head_gemm", "argmax_embed", "unsampled_span", "gemm_chain", "attn_pair", "step_layers"]

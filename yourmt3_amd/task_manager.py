@@ -16,10 +16,15 @@ YourMT3.inference(audio, task_tokens=...) feeds to the decoder before it emits (
 BUILD-DEFINED: the task-token names, their ids and the sub-task prefixes are shaped after an unverified recollection
 of upstream; nothing in the reference pins them.  The ids sit right after the codec's events
 (Codec.size ...) inside the 1536-wide head; a real checkpoint's ids are an entry of the `task_token_ids` table.
+
+Confidences: with the token scores of YourMT3.inference(return_scores=True) (log-probabilities, include/ymt3.h, token
+scores), every onset event carries the score of its pitch or drum token and every note `confidence = exp(score)` of its
+onset.  Both fields are left out of comparisons, ordering and hashing: notes without scores are exactly what they were.
 """
 from __future__ import annotations
 
-from dataclasses import dataclass
+import math
+from dataclasses import dataclass, field, replace
 from typing import Dict, Iterable, List, Optional, Sequence, Tuple
 
 import numpy as np
@@ -37,6 +42,7 @@ class NoteEvent:
     program: int
     velocity: int             # 1 onset, 0 offset
     pitch: int
+    score: Optional[float] = field(default=None, compare=False)      # onsets: log-probability of the pitch / drum token
 
 
 @dataclass(frozen=True, order=True)
@@ -47,6 +53,7 @@ class Note:
     program: int
     pitch: int
     velocity: int = 100
+    confidence: Optional[float] = field(default=None, compare=False)  # exp(score) of the onset's token, if scored
 
 
 # instrument classes of the 13-channel decoder (MT3 "FULL_PLUS" grouping + singing + drums)
@@ -120,14 +127,16 @@ class NoteEventTokenizer:
         return toks
 
     # ---------------------------------------------------------------- tokens -> note events
-    def decode_segment(self, tokens: Iterable[int], start_sec: float):
-        """-> (events, tie_notes, n_invalid).  Stops at EOS/PAD; malformed tokens are counted, not fatal."""
+    def decode_segment(self, tokens: Iterable[int], start_sec: float, scores: Optional[Sequence[float]] = None):
+        """-> (events, tie_notes, n_invalid).  Stops at EOS/PAD; malformed tokens are counted, not fatal.  `scores`: one
+        log-probability per token (aligned with `tokens`); each onset event stores its pitch / drum token's as `score`."""
         c = self.codec
         events: List[NoteEvent] = []
         ties: List[Tuple[int, int]] = []
         in_tie, step, vel, prog, bad = True, 0, 1, 0, 0
-        for tk in tokens:
+        for i, tk in enumerate(tokens):
             tk = int(tk)
+            sc = None if scores is None else float(scores[i])
             if tk in (EOS, PAD):
                 break
             if tk in self.skip_ids:
@@ -149,16 +158,16 @@ class NoteEventTokenizer:
                     if in_tie:
                         bad += 1
                     elif vel:
-                        events.append(NoteEvent(start_sec + step / c.steps_per_second, True, DRUM_PROGRAM, 1, ev.value))
+                        events.append(NoteEvent(start_sec + step / c.steps_per_second, True, DRUM_PROGRAM, 1, ev.value, sc))
                 elif in_tie:
                     ties.append((prog, ev.value))
                 else:
-                    events.append(NoteEvent(start_sec + step / c.steps_per_second, False, prog, vel, ev.value))
+                    events.append(NoteEvent(start_sec + step / c.steps_per_second, False, prog, vel, ev.value, sc if vel else None))
             elif ev.type == "drum":
                 if in_tie:
                     bad += 1
                 else:
-                    events.append(NoteEvent(start_sec + step / c.steps_per_second, True, DRUM_PROGRAM, 1, ev.value))
+                    events.append(NoteEvent(start_sec + step / c.steps_per_second, True, DRUM_PROGRAM, 1, ev.value, sc))
         return events, ties, bad
 
 
@@ -168,36 +177,49 @@ def note_events_to_notes(segments: Sequence[Tuple[float, List[NoteEvent], List[T
     A note sounding at a segment boundary stays open only if the next segment's tie section lists it;
     otherwise it is closed at that segment's start.  Offsets without an onset are dropped; a repeated
     onset re-triggers (closes the old note at the new onset); a drum hit repeated at the same time and
-    pitch (the model emitting a token twice) is one hit.
+    pitch (the model emitting a token twice) is one hit.  A note's confidence is exp(score) of its onset event (None
+    without one), carried across segments with the onset; a de-duplicated drum hit keeps the larger of its confidences.
     """
-    active: Dict[Tuple[int, int], float] = {}
+    active: Dict[Tuple[int, int], Tuple[float, Optional[float]]] = {}     # (program, pitch) -> (onset, confidence)
     notes: List[Note] = []
-    drum_hits = set()
+    drum_hits: Dict[Tuple[float, int], int] = {}                          # (time, pitch) -> index in notes
     for start, events, ties in sorted(segments, key=lambda s: s[0]):
         tie_set = set(ties)
         for key in [k for k in active if k not in tie_set]:
-            on = active.pop(key)
+            on, conf = active.pop(key)
             if start > on:
-                notes.append(Note(on, start, False, key[0], key[1]))
+                notes.append(Note(on, start, False, key[0], key[1], confidence=conf))
         for ev in sorted(events):
+            conf = None if ev.score is None else math.exp(ev.score)
             if ev.is_drum:
-                if (ev.time, ev.pitch) not in drum_hits:
-                    drum_hits.add((ev.time, ev.pitch))
-                    notes.append(Note(ev.time, ev.time + DRUM_NOTE_SEC, True, DRUM_PROGRAM, ev.pitch))
+                hit = (ev.time, ev.pitch)
+                if hit not in drum_hits:
+                    drum_hits[hit] = len(notes)
+                    notes.append(Note(ev.time, ev.time + DRUM_NOTE_SEC, True, DRUM_PROGRAM, ev.pitch, confidence=conf))
+                elif conf is not None:
+                    old = notes[drum_hits[hit]]
+                    if old.confidence is None or conf > old.confidence:
+                        notes[drum_hits[hit]] = replace(old, confidence=conf)
                 continue
             key = (ev.program, ev.pitch)
             if ev.velocity:
-                if key in active and ev.time > active[key]:
-                    notes.append(Note(active[key], ev.time, False, key[0], key[1]))
-                active[key] = ev.time
+                if key in active and ev.time > active[key][0]:
+                    notes.append(Note(active[key][0], ev.time, False, key[0], key[1], confidence=active[key][1]))
+                active[key] = (ev.time, conf)
             elif key in active:
-                on = active.pop(key)
+                on, oconf = active.pop(key)
                 if ev.time > on:
-                    notes.append(Note(on, ev.time, False, key[0], key[1]))
-    for key, on in active.items():
+                    notes.append(Note(on, ev.time, False, key[0], key[1], confidence=oconf))
+    for key, (on, conf) in active.items():
         if end_sec > on:
-            notes.append(Note(on, end_sec, False, key[0], key[1]))
+            notes.append(Note(on, end_sec, False, key[0], key[1], confidence=conf))
     return sorted(notes)
+
+
+def drop_low_confidence(notes: Sequence[Note], min_confidence: float) -> List[Note]:
+    """The notes whose confidence is at least `min_confidence`, in their order.  A note without a confidence (decoded without
+    scores) has nothing to be judged by and is kept."""
+    return [n for n in notes if n.confidence is None or n.confidence >= min_confidence]
 
 
 class TaskManager:
@@ -250,23 +272,33 @@ class TaskManager:
         return 0
 
     def detokenize_list_batches(self, list_batch_token_arrays: Sequence[np.ndarray], list_start_sec: Sequence[float],
-                                return_events: bool = False):
+                                return_events: bool = False, list_batch_score_arrays: Optional[Sequence[np.ndarray]] = None):
         """list of (b, L) int arrays (ONE channel: pass arr[:, ch, :]) + start time of every segment ->
-        per-segment (start, events, ties); with return_events also the invalid-token count."""
+        per-segment (start, events, ties); with return_events also the invalid-token count.  `list_batch_score_arrays`:
+        the matching (b, L) token scores; onset events then carry their token's score."""
         flat = np.concatenate([np.asarray(a) for a in list_batch_token_arrays], 0)
         if flat.shape[0] != len(list_start_sec):
             raise ValueError(f"{flat.shape[0]} segments but {len(list_start_sec)} start times")
+        flat_sc = None
+        if list_batch_score_arrays is not None:
+            flat_sc = np.concatenate([np.asarray(a) for a in list_batch_score_arrays], 0)
+            if flat_sc.shape != flat.shape:
+                raise ValueError(f"scores {flat_sc.shape} do not match tokens {flat.shape}")
         segs, bad = [], 0
-        for row, start in zip(flat, list_start_sec):
-            ev, ties, b = self.tokenizer.decode_segment(row, float(start))
+        for i, (row, start) in enumerate(zip(flat, list_start_sec)):
+            ev, ties, b = self.tokenizer.decode_segment(row, float(start), None if flat_sc is None else flat_sc[i])
             segs.append((float(start), ev, ties))
             bad += b
         return (segs, bad) if return_events else segs
 
-    def tokens_to_notes(self, token_batches: Sequence[np.ndarray], start_secs: Sequence[float], end_sec: float) -> List[Note]:
-        """All channels: token_batches are (b, K, L); channels are decoded independently and mixed."""
+    def tokens_to_notes(self, token_batches: Sequence[np.ndarray], start_secs: Sequence[float], end_sec: float,
+                        score_batches: Optional[Sequence[np.ndarray]] = None) -> List[Note]:
+        """All channels: token_batches are (b, K, L); channels are decoded independently and mixed.  `score_batches`: the
+        matching (b, K, L) token scores (YourMT3.inference_file(return_scores=True)); every note then has
+        confidence = exp(score of its onset's token)."""
         notes: List[Note] = []
         for ch in range(self.num_decoding_channels):
-            segs = self.detokenize_list_batches([np.asarray(a)[:, ch, :] for a in token_batches], start_secs)
+            sc = None if score_batches is None else [np.asarray(a)[:, ch, :] for a in score_batches]
+            segs = self.detokenize_list_batches([np.asarray(a)[:, ch, :] for a in token_batches], start_secs, list_batch_score_arrays=sc)
             notes += note_events_to_notes(segs, end_sec)
         return sorted(notes)

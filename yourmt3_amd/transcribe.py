@@ -11,16 +11,20 @@ import torch
 
 from .audio import load_wav_pcm
 from .midi import write_midi
-from .task_manager import TaskManager
+from .task_manager import TaskManager, drop_low_confidence
 
 
 def transcribe(model, audio_info: Union[str, dict, np.ndarray], task_manager: Optional[TaskManager] = None, bsz: int = 8,
                output_dir: str = ".", max_token_length: Optional[int] = None, return_notes: bool = False,
-               continuous: bool = False, subtask: Optional[str] = None):
+               continuous: bool = False, subtask: Optional[str] = None, confidence: bool = False,
+               min_confidence: Optional[float] = None):
     """`continuous=True` decodes the file's segments through `bsz` slots with continuous batching
     (YourMT3.inference_stream: segments leave at EOS and the next ones enter) instead of fixed batches; same ids.
     `subtask`: for a task-conditioned TaskManager (e.g. "singing_drum_v1"), the sub-task whose task tokens prompt every
-    segment's decode (None: its "default"); tasks without task tokens take no prompt and refuse a subtask."""
+    segment's decode (None: its "default"); tasks without task tokens take no prompt and refuse a subtask.
+    `confidence=True` decodes with token scores (include/ymt3.h, token scores): every returned note carries
+    `confidence` = the probability of its onset's token.  `min_confidence` implies it and drops the notes below it before
+    the MIDI file is written.  The ids, and so the notes, are those of the unscored decode."""
     cfg = model.cfg
     if task_manager is None:
         task_manager = TaskManager("mc13_full_plus_256" if cfg.n_channels == 13 else "mt3_full_plus")
@@ -47,11 +51,21 @@ def transcribe(model, audio_info: Union[str, dict, np.ndarray], task_manager: Op
     n_prompt = 0 if prompt is None else int(prompt.numel())
     L = min(max_token_length or task_manager.max_note_token_length, cfg.max_decode_len - n_prompt)
     kw = {} if prompt is None else {"task_tokens": prompt}
+    scored = confidence or min_confidence is not None
+    if scored:
+        kw["return_scores"] = True
+    score_batches = None
     if continuous:
-        batches = [model.inference_stream(segments, max_token_length=L, slots=bsz, **kw).cpu().numpy()]
+        out = model.inference_stream(segments, max_token_length=L, slots=bsz, **kw)
+        batches = [(out[0] if scored else out).cpu().numpy()]
+        if scored:
+            score_batches = [out[1].cpu().numpy()]
     else:
-        batches = model.inference_file(bsz, segments, max_token_length=L, **kw)
-    notes = task_manager.tokens_to_notes(batches, start_secs, end_sec=n_samples / cfg.sample_rate)
+        out = model.inference_file(bsz, segments, max_token_length=L, **kw)
+        batches, score_batches = out if scored else (out, None)
+    notes = task_manager.tokens_to_notes(batches, start_secs, end_sec=n_samples / cfg.sample_rate, score_batches=score_batches)
+    if min_confidence is not None:
+        notes = drop_low_confidence(notes, float(min_confidence))
     os.makedirs(output_dir, exist_ok=True)
     midi_path = write_midi(notes, os.path.join(output_dir, name + ".mid"))
     return (midi_path, notes) if return_notes else midi_path
