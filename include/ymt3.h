@@ -15,6 +15,7 @@
  *   inference(x, task_tokens, ...)       ->  ymt3_transcribe_segments_prompted() / ymt3_decode_prompted()
  *   generate(output_scores=True) + compute_transition_scores(normalize_logits=True)
  *                                        ->  ymt3_transcribe_segments_scored() / ymt3_decode_scored()
+ *   generate(prefix_allowed_tokens_fn=...)  ->  ymt3_transcribe_segments_constrained() / ymt3_decode_constrained()
  *
  * Conventions
  *   - every pointer named *_dev is DEVICE memory on the handle's GPU, owned by the caller;
@@ -25,7 +26,7 @@
  *     that ran the merged decode kernels of the 64-row regime (after its last step has been queued; nothing is
  *     launched behind it unless a kernel gave up);
  *   - the library owns weights, KV caches and scratch inside the handle; nothing is
- *     allocated after ymt3_create();
+ *     allocated after ymt3_create() except by ymt3_constraint_create() (the caller's automaton tables);
  *   - return value: 0 = ok, non-zero = error; the message is in ymt3_last_error()
  *     (thread local).  No exception ever crosses this boundary;
  *   - one handle per device per host thread.  No internal host threads.
@@ -143,6 +144,44 @@ int ymt3_transcribe_segments_scored(ymt3_handle h, const float* audio_dev, int B
                                     int n_prompt, int32_t* tokens_dev, float* scores_dev, void* stream);
 int ymt3_transcribe_stream_scored(ymt3_handle h, const float* audio_dev, int n_segments, int n_steps, const int32_t* prompt_dev,
                                   int n_prompt, int32_t* tokens_dev, float* scores_dev, int slots, int interval, void* stream);
+
+/* Constraints: a token automaton limits which tokens each row may emit (HF `generate(prefix_allowed_tokens_fn=...)`, i.e. a
+ * PrefixConstrainedLogitsProcessor, greedy).
+ *   - an automaton has S states, allowed[S][V] (one bit per token, V = cfg.vocab) and next[S][V] (an int32 state for every
+ *     (state, token) pair); every decoded row has a start state, given per (segment, channel) by start_state_dev: (B,
+ *     n_channels) int32 on the device, (n_segments, n_channels) for ymt3_transcribe_stream_constrained, NULL = state 0 for all.
+ *     A start state outside [0, S) is clamped into range on the device, as fed ids are.
+ *   - at every emitted position of a live row in state s the emitted token is the lowest index among the maxima of the raw
+ *     logits over {i : allowed[s][i]}; with f the fed id (the emitted token, or forced[...] clamped into [0, vocab) when forcing),
+ *     the row's state becomes next[s][f].
+ *   - prompt positions neither mask nor advance the state: the automaton starts at the first emitted token.
+ *   - with eos_id >= 0 a row that has emitted EOS emits PAD (score 0.0 unless forced) and its state stays frozen.
+ *   - scores_dev: log_softmax of the masked row (disallowed tokens -inf) at f -- HF compute_transition_scores(normalize_logits=
+ *     True) behind the constraint's logits processor.  A forced id that is not allowed scores -inf.
+ *   - logits_dev stays the raw, unmasked logits (HF `output_logits`).
+ *   - constraint == NULL is the unconstrained call bit for bit (ids, logits, scores): each *_scored entry point is its
+ *     *_constrained counterpart with constraint = NULL and start_state_dev = NULL.  start_state_dev without a constraint
+ *     is an error.
+ * The tables live in device memory owned by the constraint object; the kernels read them through the device-resident loop
+ * state, so no captured graph depends on them.  Every decode regime selects through the same kernel. */
+typedef struct ymt3_constraint_s* ymt3_constraint;
+/* Validate once, then upload once.  allowed_bits_host: [n_states][ceil(vocab / 32)] uint32 (bit i % 32 of word i / 32 = token
+ * i; bits at or beyond vocab are ignored); next_host: [n_states][vocab] int32.  Checks: vocab == the handle's cfg.vocab,
+ * 1 <= n_states <= 1024, every next in [0, n_states), every state allows at least one token.  Synchronous (a blocking
+ * upload).  The constraint belongs to h: using it on another handle is an error.  ymt3_constraint_destroy(c) frees it
+ * (NULL is a no-op); it may run before or after the handle's ymt3_destroy(h). */
+int  ymt3_constraint_create(ymt3_handle h, int n_states, int vocab, const uint32_t* allowed_bits_host, const int32_t* next_host,
+                            ymt3_constraint* out);
+void ymt3_constraint_destroy(ymt3_constraint c);
+int ymt3_decode_constrained(ymt3_handle h, const void* enc_dev, int B, int n_steps, const int32_t* prompt_dev, int n_prompt,
+                            int32_t* tokens_dev, float* scores_dev, const int32_t* forced_dev, float* logits_dev,
+                            ymt3_constraint constraint, const int32_t* start_state_dev, void* stream);
+int ymt3_transcribe_segments_constrained(ymt3_handle h, const float* audio_dev, int B, int n_steps, const int32_t* prompt_dev,
+                                         int n_prompt, int32_t* tokens_dev, float* scores_dev, ymt3_constraint constraint,
+                                         const int32_t* start_state_dev, void* stream);
+int ymt3_transcribe_stream_constrained(ymt3_handle h, const float* audio_dev, int n_segments, int n_steps, const int32_t* prompt_dev,
+                                       int n_prompt, int32_t* tokens_dev, float* scores_dev, int slots, int interval,
+                                       ymt3_constraint constraint, const int32_t* start_state_dev, void* stream);
 
 /* Opt-in early stop (first step): with eos_id >= 0 and interval > 0, ymt3_decode_greedy /
  * ymt3_transcribe_segments check on the host every `interval` steps whether every row has emitted EOS and stop

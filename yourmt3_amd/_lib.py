@@ -19,6 +19,8 @@ SYMBOLS = [
     "ymt3_set_abort_recovery", "ymt3_merged_fallbacks", "ymt3_debug_moe_trace", "ymt3_last_decode_chains",
     "ymt3_decode_prompted", "ymt3_transcribe_segments_prompted", "ymt3_transcribe_stream_prompted",
     "ymt3_decode_scored", "ymt3_transcribe_segments_scored", "ymt3_transcribe_stream_scored",
+    "ymt3_constraint_create", "ymt3_constraint_destroy", "ymt3_decode_constrained", "ymt3_transcribe_segments_constrained",
+    "ymt3_transcribe_stream_constrained",
 ]
 
 _lib = None
@@ -84,6 +86,16 @@ def load() -> ctypes.CDLL:
     lib.ymt3_transcribe_segments_scored.restype = i32
     lib.ymt3_transcribe_stream_scored.argtypes = [vp, vp, i32, i32, vp, i32, vp, vp, i32, i32, vp]
     lib.ymt3_transcribe_stream_scored.restype = i32
+    lib.ymt3_constraint_create.argtypes = [vp, i32, i32, vp, vp, ctypes.POINTER(vp)]
+    lib.ymt3_constraint_create.restype = i32
+    lib.ymt3_constraint_destroy.argtypes = [vp]
+    lib.ymt3_constraint_destroy.restype = None
+    lib.ymt3_decode_constrained.argtypes = [vp, vp, i32, i32, vp, i32, vp, vp, vp, vp, vp, vp, vp]
+    lib.ymt3_decode_constrained.restype = i32
+    lib.ymt3_transcribe_segments_constrained.argtypes = [vp, vp, i32, i32, vp, i32, vp, vp, vp, vp, vp]
+    lib.ymt3_transcribe_segments_constrained.restype = i32
+    lib.ymt3_transcribe_stream_constrained.argtypes = [vp, vp, i32, i32, vp, i32, vp, vp, i32, i32, vp, vp, vp]
+    lib.ymt3_transcribe_stream_constrained.restype = i32
     lib.ymt3_debug_step_stamps.argtypes = [vp, vp, vp, vp, ctypes.POINTER(ctypes.c_int)]
     lib.ymt3_debug_step_stamps.restype = i32
     lib.ymt3_debug_kernel_stamps.argtypes = [vp, i32, vp, i32]

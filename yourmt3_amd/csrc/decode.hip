@@ -25,6 +25,8 @@
 //                       n_prompt steps of a call (a task prompt, HF `decoder_input_ids` after the start id)
 //                       feed the caller's ids instead and emit nothing.  With a scores buffer it also writes
 //                       log_softmax(logits)[fed id] per emitted token: a second pass over the row for sum(exp(v - max)).
+//                       Under a token automaton (include/ymt3.h, constraints) both passes skip the tokens the row's state does
+//                       not allow, and thread 0 moves the row's state along the fed id.
 //
 // Oracle: oracle/ymt3_oracle.py::decoder_step / greedy_decode.
 #include <cstdlib>
@@ -1002,8 +1004,10 @@ __global__ __launch_bounds__(256) void argmax_embed_kernel(const float* __restri
     const int32_t* const forced = sh->forced;
     float* const logits_out = sh->logits_out;
     const int32_t* const prompt = sh->prompt;
-    // (unconditionally, with the other pointers: with scores off this load is the only change to the kernel)
+    // (unconditionally, with the other pointers: with scores and constraints off these loads are the only change to the kernel;
+    // the rest of a constraint is read where it is used, under it)
     float* const scores_out = sh->scores_out;
+    const uint32_t* const c_allowed = sh->c_allowed;
     const int was_finished = pFinished[r];
     const int forced_tok = forced && col >= 0 ? forced[(size_t)r * n_steps + col] : 0;
     // (a prompt id is read by thread 0 behind the argmax, at prompt positions only.  Requested here, its conditional load split
@@ -1018,6 +1022,21 @@ __global__ __launch_bounds__(256) void argmax_embed_kernel(const float* __restri
     for (int i = tid; i < V; i += 256) {
         const float v = row[i];
         if (v > bv) { bv = v; bi = i; }       // ascending i: the first maximum is kept
+    }
+    // Constrained: the scan again (the row is in cache by now) over the tokens the row's state allows.  Behind the plain scan,
+    // which thus waits on no load of the constraint's pointers: the unconstrained kernel issues its logits loads as before.
+    int state = 0;
+    const uint32_t* mrow = nullptr;
+    if (c_allowed) {
+        state = a.row_state[r];              // (workgroup-uniform; seeded by decode_init / slot_start)
+        asm volatile("" : "+v"(state));      // kept in a VGPR: in SGPRs the mask row's address cost the kernel its 8th wave per SIMD
+        mrow = c_allowed + (size_t)state * sh->c_words;
+        bv = -3.4e38f;
+        bi = 0x7fffffff;
+        for (int i = tid; i < V; i += 256) {
+            const float v = row[i];
+            if (((mrow[i >> 5] >> (i & 31)) & 1u) && v > bv) { bv = v; bi = i; }     // disallowed tokens take no part
+        }
     }
     // wave-wide (max value, lowest index): the selection is commutative and associative, so any reduction order gives the same pair.
     // Rotations inside the 16-lane rows, then row broadcasts (all DPP; twelve dependent ds_bpermute round trips before): row 3 ends up
@@ -1037,7 +1056,8 @@ __global__ __launch_bounds__(256) void argmax_embed_kernel(const float* __restri
 #undef ARGMAX_TAKE
     if (lane == 63) { sv[wave] = bv; si[wave] = bi; }
     __syncthreads();
-    // score pass: the row maximum is the argmax value (every thread takes it now: embed_row reuses sv below)
+    // score pass: the row maximum is the argmax value, over the allowed tokens under a constraint (every thread takes it now:
+    // embed_row reuses sv below)
     const float row_max = scores_out ? fmaxf(fmaxf(sv[0], sv[1]), fmaxf(sv[2], sv[3])) : 0.f;
     long long score_at = -1;               // thread 0: where this step's score goes (-1: nowhere) ...
     int score_id = -1;                     // ... and the id it scores (-1: 0.0, an unforced row after its EOS)
@@ -1060,6 +1080,7 @@ __global__ __launch_bounds__(256) void argmax_embed_kernel(const float* __restri
             feed = bi;
             score_at = out0 + p;
             score_id = bi;
+            if (mrow) a.row_state[r] = sh->c_next[(size_t)state * V + bi];
         }
         s_feed = feed < 0 ? 0 : (feed >= V ? V - 1 : feed);
     } else if (tid == 0 && col < 0) {
@@ -1081,6 +1102,7 @@ __global__ __launch_bounds__(256) void argmax_embed_kernel(const float* __restri
         s_feed = feed;
         score_at = (long long)r * n_steps + col;
         score_id = !forced && a.eos_id >= 0 && was_finished ? -1 : feed;
+        if (mrow && !(a.eos_id >= 0 && was_finished)) a.row_state[r] = sh->c_next[(size_t)state * V + feed];   // frozen after EOS
     }
     __syncthreads();
     const int feed = s_feed;
@@ -1094,7 +1116,12 @@ __global__ __launch_bounds__(256) void argmax_embed_kernel(const float* __restri
     if (scores_out) {
         // log-sum-exp of the row the argmax read (still in cache): per-thread partials, the wave butterfly, the 4 waves below
         float q = 0.f;
-        for (int i = tid; i < V; i += 256) q += __expf(row[i] - row_max);
+        if (mrow) {
+            for (int i = tid; i < V; i += 256)
+                if ((mrow[i >> 5] >> (i & 31)) & 1u) q += __expf(row[i] - row_max);         // disallowed: exp(-inf) = 0
+        } else {
+            for (int i = tid; i < V; i += 256) q += __expf(row[i] - row_max);
+        }
         q = wave_sum(q);
         if (lane == 0) s_sum[wave] = q;
     }
@@ -1105,7 +1132,9 @@ __global__ __launch_bounds__(256) void argmax_embed_kernel(const float* __restri
     __syncthreads();
     if (tid == 0) {
         if (scores_out && score_at >= 0)           // (the barrier above also published s_sum)
-            scores_out[score_at] = score_id < 0 ? 0.f : (row[score_id] - row_max) - __logf((s_sum[0] + s_sum[1]) + (s_sum[2] + s_sum[3]));
+            scores_out[score_at] = score_id < 0 ? 0.f
+                                 : mrow && !((mrow[score_id >> 5] >> (score_id & 31)) & 1u) ? -__builtin_inff()   // a forced disallowed id
+                                 : (row[score_id] - row_max) - __logf((s_sum[0] + s_sum[1]) + (s_sum[2] + s_sum[3]));
         if (a.eos_id >= 0) __threadfence();      // only the flags the last arriver counts below need to be visible to it
         // Who is last?  One atomic per workgroup on ONE word serialises at the memory side (~12 ns each: 10 us of the 13-channel decoder's
         // 832 workgroups); beyond 64 workgroups groups of 32 count on lines of their own and only each group's last one takes the shared ticket.
@@ -1136,13 +1165,17 @@ __global__ __launch_bounds__(256) void argmax_embed_kernel(const float* __restri
 
 __global__ __launch_bounds__(256) void decode_init_kernel(ArgmaxArgs a, int n_chains, int n_steps, int step0, int32_t* tokens_out,
                                                           const int32_t* forced, float* logits_out, const int32_t* prompt, int n_prompt,
-                                                          float* scores_out) {
+                                                          float* scores_out, ConstraintView cv) {
     const int r = blockIdx.x, tid = threadIdx.x;
     const bf16_t* e = a.embed + (size_t)a.pad_id * a.d;
     const bf16_t* c = a.chan_embed ? a.chan_embed + (size_t)(r % a.n_channels) * a.d : nullptr;
     __shared__ float sv[4];
     embed_row(a, r, e, c, sv);
-    if (tid == 0) a.finished[r] = 0;
+    if (tid == 0) {
+        a.finished[r] = 0;
+        // the start state, clamped into range like a fed id
+        if (a.row_state) a.row_state[r] = cv.start ? min(max(cv.start[r], 0), cv.n_states - 1) : 0;
+    }
     if (r == 0 && tid < n_chains) {          // a.shared is the array of per-chain loop states
         DecodeShared* sh = a.shared + tid;
         sh->step = step0;
@@ -1156,11 +1189,14 @@ __global__ __launch_bounds__(256) void decode_init_kernel(ArgmaxArgs a, int n_ch
         sh->prompt = prompt;
         sh->n_prompt = n_prompt;
         sh->scores_out = scores_out;
+        sh->c_allowed = cv.allowed;
+        sh->c_next = cv.next;
+        sh->c_words = cv.words;
     }
 }
 
 __global__ __launch_bounds__(256) void slot_start_kernel(ArgmaxArgs a, int row0, long long first_out, int n_steps, long long* row_out,
-                                                         long long first_prompt, int n_prompt, long long* row_prompt) {
+                                                         long long first_prompt, int n_prompt, long long* row_prompt, ConstraintView cv) {
     const int r = row0 + blockIdx.x, tid = threadIdx.x;
     const bf16_t* e = a.embed + (size_t)a.pad_id * a.d;
     const bf16_t* c = a.chan_embed ? a.chan_embed + (size_t)(r % a.n_channels) * a.d : nullptr;
@@ -1171,6 +1207,7 @@ __global__ __launch_bounds__(256) void slot_start_kernel(ArgmaxArgs a, int row0,
         a.row_pos[r] = 0;
         row_out[r] = first_out + (long long)blockIdx.x * n_steps;
         row_prompt[r] = first_prompt + (long long)blockIdx.x * n_prompt;
+        if (a.row_state) a.row_state[r] = cv.start ? min(max(cv.start[blockIdx.x], 0), cv.n_states - 1) : 0;
     }
 }
 
@@ -1356,17 +1393,20 @@ int launch_argmax_embed(const ArgmaxArgs& a, hipStream_t stream) {
 }
 
 int launch_decode_init(const ArgmaxArgs& a, int n_chains, int n_steps, int step0, int32_t* tokens_out, const int32_t* forced,
-                       float* logits_out, const int32_t* prompt, int n_prompt, float* scores_out, hipStream_t stream) {
+                       float* logits_out, const int32_t* prompt, int n_prompt, float* scores_out, const ConstraintView& cv,
+                       hipStream_t stream) {
     if (a.R <= 0) return 0;
     if (n_prompt < 0 || (n_prompt > 0 && !prompt)) return -1;
-    decode_init_kernel<<<a.R, 256, 0, stream>>>(a, n_chains, n_steps, step0, tokens_out, forced, logits_out, prompt, n_prompt, scores_out);
+    if (cv.allowed && (!cv.next || !a.row_state || cv.n_states < 1 || cv.words * 32 < a.V)) return -1;
+    decode_init_kernel<<<a.R, 256, 0, stream>>>(a, n_chains, n_steps, step0, tokens_out, forced, logits_out, prompt, n_prompt, scores_out, cv);
     return 0;
 }
 
 int launch_slot_start(const ArgmaxArgs& a, int row0, long long first_out, int n_steps, long long* row_out, long long first_prompt,
-                      int n_prompt, long long* row_prompt, hipStream_t stream) {
+                      int n_prompt, long long* row_prompt, const ConstraintView& cv, hipStream_t stream) {
     if (!a.row_pos || !row_out || !row_prompt || a.n_channels <= 0) return -1;
-    slot_start_kernel<<<a.n_channels, 256, 0, stream>>>(a, row0, first_out, n_steps, row_out, first_prompt, n_prompt, row_prompt);
+    if (cv.start && cv.n_states < 1) return -1;
+    slot_start_kernel<<<a.n_channels, 256, 0, stream>>>(a, row0, first_out, n_steps, row_out, first_prompt, n_prompt, row_prompt, cv);
     return 0;
 }
 

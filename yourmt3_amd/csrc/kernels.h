@@ -89,6 +89,19 @@ struct DecodeShared {           // device-resident loop state, read by every dec
     float* logits_out;          // [R][n_steps][V] or null
     const int32_t* prompt;      // [R][n_prompt] (lock-step) or indexed through row_prompt (slot mode); null when n_prompt = 0
     float* scores_out;          // [R][n_steps] log_softmax(logits)[fed id] per emitted token (indexed as tokens_out), or null
+    // token automaton (include/ymt3.h, constraints), or null: every emitted token is the first maximum over the tokens
+    // allowed[row_state[r]], and the fed id f moves the row to next[row_state[r]][f]
+    const uint32_t* c_allowed;  // [n_states][c_words] one bit per token
+    const int32_t* c_next;      // [n_states][V]
+    int c_words;                // ceil(V / 32)
+};
+
+// the automaton of a call as the kernels see it (all null / 0: none)
+struct ConstraintView {
+    const uint32_t* allowed;    // [n_states][words]
+    const int32_t* next;        // [n_states][V]
+    int words, n_states;
+    const int32_t* start;       // per-row start states (lock-step: [R]; slot mode: the admitted segment's [n_channels]) or null: state 0
 };
 
 constexpr int SSQ_TILES = 32;    // sum(h^2) partials per row = d_model / 16 column tiles of the RESID epilogue
@@ -262,21 +275,25 @@ struct ArgmaxArgs {
     unsigned* zero_sync;        // or null: counter lines (CHAIN_LINE words each) to leave zeroed for the next step's dec_step_kernel
     int zero_lines;
     const long long* row_prompt;   // slot mode, or null: [R] offset of the row's prompt (see row_pos)
+    int* row_state;             // [R] automaton state of every row (read only under a constraint, see DecodeShared::c_allowed)
 };
 int launch_argmax_embed(const ArgmaxArgs& a, hipStream_t stream);
 // tokens_out[r][from .. n_steps) = pad (scores_out, if not null: 0.0) for rows [row0, row0 + R): the tail of a decode that stopped
 // early (`from`: emitted index)
 int launch_pad_tail(int32_t* tokens_out, float* scores_out, int row0, int R, int n_steps, int from, int pad_id, hipStream_t stream);
 // slot mode: (re)start rows [row0, row0 + n_channels) on a new segment: h = embed[pad] (+ channel), position 0,
-// finished = 0, row_out = first_out + channel * n_steps, row_prompt = first_prompt + channel * n_prompt
+// finished = 0, row_out = first_out + channel * n_steps, row_prompt = first_prompt + channel * n_prompt,
+// row_state = cv.start[channel] clamped into [0, cv.n_states) (0 without start states)
 int launch_slot_start(const ArgmaxArgs& a, int row0, long long first_out, int n_steps, long long* row_out, long long first_prompt,
-                      int n_prompt, long long* row_prompt, hipStream_t stream);
+                      int n_prompt, long long* row_prompt, const ConstraintView& cv, hipStream_t stream);
 // slot mode: PAD the unwritten tail [row_pos + 1 - n_prompt, n_steps) of rows [row0, row0 + n_rows) (scores_out, if not null: 0.0)
 int launch_slot_retire(const ArgmaxArgs& a, int row0, int n_rows, int n_steps, int n_prompt, int32_t* tokens_out, float* scores_out,
                        hipStream_t stream);
-// all rows: h[r] = embed[pad] (+ chan_embed), finished = 0; a.shared[0..n_chains) reset (prompt / n_prompt: every chain's)
+// all rows: h[r] = embed[pad] (+ chan_embed), finished = 0, row_state = cv.start[r] clamped into [0, cv.n_states) (0 without start
+// states); a.shared[0..n_chains) reset (prompt / n_prompt / the automaton: every chain's)
 int launch_decode_init(const ArgmaxArgs& a, int n_chains, int n_steps, int step0, int32_t* tokens_out, const int32_t* forced,
-                       float* logits_out, const int32_t* prompt, int n_prompt, float* scores_out, hipStream_t stream);
+                       float* logits_out, const int32_t* prompt, int n_prompt, float* scores_out, const ConstraintView& cv,
+                       hipStream_t stream);
 
 // ---------------------------------------------------------------- MoE decoder FFN (moe.hip)
 struct MoeArgs {

@@ -87,6 +87,7 @@ struct ymt3_ctx {
     int* row_pos = nullptr;             // [maxR]
     long long* row_out = nullptr;       // [maxR]
     long long* row_prompt = nullptr;    // [maxR]: slot mode, offset of the row's prompt in the caller's prompt buffer
+    int* row_state = nullptr;           // [maxR]: every row's token-automaton state (include/ymt3.h, constraints)
     int* host_rows = nullptr;           // pinned [maxR]: copy of `finished` for the host's retire/admit decisions
     bool slot_mode = false;
     DecodeShared* shared = nullptr;     // [MAX_CHAINS] per-chain loop state
@@ -366,6 +367,7 @@ static int create_impl(ymt3_ctx* c, const ymt3_config* cfg, const void* blob, si
     if (dev_alloc(c, (void**)&c->row_pos, R * 4)) return YMT3_ERR_HIP;
     if (dev_alloc(c, (void**)&c->row_out, R * 8)) return YMT3_ERR_HIP;
     if (dev_alloc(c, (void**)&c->row_prompt, R * 8)) return YMT3_ERR_HIP;
+    if (dev_alloc(c, (void**)&c->row_state, R * 4)) return YMT3_ERR_HIP;
     if (dev_alloc(c, (void**)&c->ssq, (size_t)SSQ_TILES * R * 4)) return YMT3_ERR_HIP;
     if (dev_alloc(c, (void**)&c->opart, R * k.n_heads * d * 4)) return YMT3_ERR_HIP;
     if (dev_alloc(c, (void**)&c->ticket, (R / 32 + 1) * CHAIN_LINE * sizeof(unsigned))) return YMT3_ERR_HIP;
@@ -511,6 +513,70 @@ static int check_call(ymt3_handle h, int B) {
         int rc = merged_fallback(h);
         if (rc) return rc;
     }
+    return 0;
+}
+
+// ---------------------------------------------------------------- constraints (include/ymt3.h)
+struct ymt3_constraint_s {
+    ymt3_ctx* owner;
+    int device, n_states, vocab, words;
+    uint32_t* allowed = nullptr;        // [n_states][words]
+    int32_t* next = nullptr;            // [n_states][vocab]
+};
+
+extern "C" void ymt3_constraint_destroy(ymt3_constraint c) {
+    if (!c) return;
+    (void)hipSetDevice(c->device);
+    if (c->allowed) (void)hipFree(c->allowed);
+    if (c->next) (void)hipFree(c->next);
+    delete c;
+}
+
+extern "C" int ymt3_constraint_create(ymt3_handle h, int n_states, int vocab, const uint32_t* allowed_bits_host, const int32_t* next_host,
+                                      ymt3_constraint* out) {
+    if (!out) FAIL(YMT3_ERR_ARG, "null output pointer");
+    *out = nullptr;
+    if (!h) FAIL(YMT3_ERR_ARG, "null handle");
+    if (!allowed_bits_host || !next_host) FAIL(YMT3_ERR_ARG, "null automaton table");
+    if (vocab != h->cfg.vocab) FAIL(YMT3_ERR_ARG, "constraint vocab=%d != the model's vocab=%d", vocab, h->cfg.vocab);
+    if (n_states < 1 || n_states > 1024) FAIL(YMT3_ERR_ARG, "n_states=%d outside [1, 1024]", n_states);
+    const int words = (vocab + 31) / 32;
+    for (int st = 0; st < n_states; ++st) {
+        bool any = false;
+        for (int i = 0; i < vocab && !any; ++i) any = (allowed_bits_host[(size_t)st * words + i / 32] >> (i % 32)) & 1u;
+        if (!any) FAIL(YMT3_ERR_ARG, "state %d allows no token", st);
+        for (int i = 0; i < vocab; ++i) {
+            const int32_t nx = next_host[(size_t)st * vocab + i];
+            if (nx < 0 || nx >= n_states) FAIL(YMT3_ERR_ARG, "next[%d][%d]=%d outside [0, %d)", st, i, nx, n_states);
+        }
+    }
+    HIP_TRY(hipSetDevice(h->device));
+    ymt3_constraint c = new ymt3_constraint_s{h, h->device, n_states, vocab, words};
+    const size_t ab = (size_t)n_states * words * sizeof(uint32_t), nb = (size_t)n_states * vocab * sizeof(int32_t);
+    if (hipMalloc(reinterpret_cast<void**>(&c->allowed), ab) != hipSuccess || hipMalloc(reinterpret_cast<void**>(&c->next), nb) != hipSuccess ||
+        hipMemcpy(c->allowed, allowed_bits_host, ab, hipMemcpyHostToDevice) != hipSuccess ||
+        hipMemcpy(c->next, next_host, nb, hipMemcpyHostToDevice) != hipSuccess) {
+        ymt3_constraint_destroy(c);
+        FAIL(YMT3_ERR_HIP, "constraint upload (%zu bytes) failed", ab + nb);
+    }
+    *out = c;
+    return YMT3_OK;
+}
+
+// the kernels' view of a call's constraint (all null without one)
+static int constraint_view(ymt3_handle h, ymt3_constraint c, const int32_t* start_state_dev, ConstraintView* cv) {
+    *cv = ConstraintView{};
+    if (!c) {
+        if (start_state_dev) FAIL(YMT3_ERR_ARG, "start states without a constraint");
+        return 0;
+    }
+    if (c->owner != h) FAIL(YMT3_ERR_ARG, "the constraint belongs to another handle");
+    if (c->vocab != h->cfg.vocab) FAIL(YMT3_ERR_ARG, "constraint vocab=%d != the model's vocab=%d", c->vocab, h->cfg.vocab);
+    cv->allowed = c->allowed;
+    cv->next = c->next;
+    cv->words = c->words;
+    cv->n_states = c->n_states;
+    cv->start = start_state_dev;
     return 0;
 }
 
@@ -915,6 +981,7 @@ static int launch_step(ymt3_handle h, int B, int row0, int R, DecodeShared* shar
     GET(h, "dec.embed", 1u, const_cast<bf16_t**>(&g.embed), (size_t)k.vocab * d);
     if (k.n_channels > 1) GET(h, "dec.chan_embed", 1u, const_cast<bf16_t**>(&g.chan_embed), (size_t)k.n_channels * d);
     if (h->slot_mode) { g.row_pos = h->row_pos; g.row_out = h->row_out; g.row_prompt = h->row_prompt; }
+    g.row_state = h->row_state;
     if (solo) g.ticket = h->ticket;                  // (row ranges of several chains would share groups)
     if (stepk) { g.zero_sync = h->step_sync; g.zero_lines = k.n_dec_layers * STEP_SYNC_LINES_PER_LAYER; }
     g.stamp = next_stamp(h, PC_ARGMAX, R);
@@ -923,23 +990,27 @@ static int launch_step(ymt3_handle h, int B, int row0, int R, DecodeShared* shar
 }
 
 static int decode_run(ymt3_handle h, const bf16_t* enc, int B, int n_steps, const int32_t* prompt, int n_prompt, int32_t* tokens,
-                      float* scores, const int32_t* forced, float* logits_out, hipStream_t s, int prof_stride, int step0);
+                      float* scores, const int32_t* forced, float* logits_out, const ConstraintView& cv, hipStream_t s, int prof_stride,
+                      int step0);
 
 // A call launches n_prompt + n_steps steps: the first n_prompt feed prompt[r][t] and emit nothing (argmax_embed_kernel), the rest
 // emit tokens 0 .. n_steps-1.  n_prompt = 0 is the plain decode.  `scores` (or null): [R][n_steps] f32, the log-probability of the id
-// fed after each emitted token (include/ymt3.h, token scores), written by the same kernels as the tokens.
+// fed after each emitted token (include/ymt3.h, token scores), written by the same kernels as the tokens.  `cv`: the call's token
+// automaton (include/ymt3.h, constraints), seeded by decode_init -- so an abort re-run starts from the same states.
 static int decode_impl(ymt3_handle h, const bf16_t* enc, int B, int n_steps, const int32_t* prompt, int n_prompt, int32_t* tokens,
-                       float* scores, const int32_t* forced, float* logits_out, hipStream_t s, int prof_stride = 0) {
+                       float* scores, const int32_t* forced, float* logits_out, const ConstraintView& cv, hipStream_t s,
+                       int prof_stride = 0) {
     const int step0 = h->prof_step0;          // one shot (debug hook): consumed by this call whatever its outcome
     h->prof_step0 = 0;
     if (n_prompt < 0) FAIL(YMT3_ERR_ARG, "n_prompt=%d < 0", n_prompt);
     if (n_prompt > 0 && !prompt) FAIL(YMT3_ERR_ARG, "n_prompt=%d with a null prompt", n_prompt);
     if (n_prompt > 0 && step0 > 0) FAIL(YMT3_ERR_ARG, "ymt3_debug_decode_start does not combine with a prompt (n_prompt=%d)", n_prompt);
-    return decode_run(h, enc, B, n_steps, prompt, n_prompt, tokens, scores, forced, logits_out, s, prof_stride, step0);
+    return decode_run(h, enc, B, n_steps, prompt, n_prompt, tokens, scores, forced, logits_out, cv, s, prof_stride, step0);
 }
 
 static int decode_run(ymt3_handle h, const bf16_t* enc, int B, int n_steps, const int32_t* prompt, int n_prompt, int32_t* tokens,
-                      float* scores, const int32_t* forced, float* logits_out, hipStream_t s, int prof_stride, int step0) {
+                      float* scores, const int32_t* forced, float* logits_out, const ConstraintView& cv, hipStream_t s, int prof_stride,
+                      int step0) {
     const ymt3_config& k = h->cfg;
     bool merged = false;                      // some step of this call ran merged kernels
     if (n_steps <= 0 || step0 + n_prompt + n_steps > k.max_decode_len)
@@ -963,7 +1034,8 @@ static int decode_run(ymt3_handle h, const bf16_t* enc, int B, int n_steps, cons
     if (n_chains > R) n_chains = R;
     h->last_chains = n_chains;
     if (h->step_kernel && h->step_sync) HIP_TRY(hipMemsetAsync(h->step_sync, 0, (size_t)STEP_SYNC_LINES * CHAIN_LINE * sizeof(unsigned), s));
-    LAUNCH(launch_decode_init(a, n_chains, n_steps, step0, tokens, forced, logits_out, prompt, n_prompt, scores, s));
+    a.row_state = h->row_state;
+    LAUNCH(launch_decode_init(a, n_chains, n_steps, step0, tokens, forced, logits_out, prompt, n_prompt, scores, cv, s));
     h->last_steps = n_total;
     int row0[9];
     row0[0] = 0;
@@ -1124,7 +1196,7 @@ static int decode_run(ymt3_handle h, const bf16_t* enc, int B, int n_steps, cons
             if (h->chain_host_abort && *static_cast<volatile unsigned*>(h->chain_host_abort)) {
                 int rc = merged_fallback(h);
                 if (rc) return rc;
-                return decode_run(h, enc, B, n_steps, prompt, n_prompt, tokens, scores, forced, logits_out, s, prof_stride, step0);
+                return decode_run(h, enc, B, n_steps, prompt, n_prompt, tokens, scores, forced, logits_out, cv, s, prof_stride, step0);
             }
         } else if (h->forced_abort && h->chain_host_abort) {
             *h->chain_host_abort = 1u;            // asynchronous mode: the next call on the handle finds the word (check_call)
@@ -1135,14 +1207,24 @@ static int decode_run(ymt3_handle h, const bf16_t* enc, int B, int n_steps, cons
     return YMT3_OK;
 }
 
-extern "C" int ymt3_decode_scored(ymt3_handle h, const void* enc_dev, int B, int n_steps, const int32_t* prompt_dev, int n_prompt,
-                                  int32_t* tokens_dev, float* scores_dev, const int32_t* forced_dev, float* logits_dev, void* stream) {
+extern "C" int ymt3_decode_constrained(ymt3_handle h, const void* enc_dev, int B, int n_steps, const int32_t* prompt_dev, int n_prompt,
+                                       int32_t* tokens_dev, float* scores_dev, const int32_t* forced_dev, float* logits_dev,
+                                       ymt3_constraint constraint, const int32_t* start_state_dev, void* stream) {
     int rc = check_call(h, B);
+    if (rc) return rc;
+    ConstraintView cv{};
+    rc = constraint_view(h, constraint, start_state_dev, &cv);
     if (rc) return rc;
     if (B == 0) return YMT3_OK;
     if (!enc_dev || !tokens_dev) FAIL(YMT3_ERR_ARG, "null buffer");
     return decode_impl(h, static_cast<const bf16_t*>(enc_dev), B, n_steps, prompt_dev, n_prompt, tokens_dev, scores_dev, forced_dev,
-                       logits_dev, (hipStream_t)stream);
+                       logits_dev, cv, (hipStream_t)stream);
+}
+
+extern "C" int ymt3_decode_scored(ymt3_handle h, const void* enc_dev, int B, int n_steps, const int32_t* prompt_dev, int n_prompt,
+                                  int32_t* tokens_dev, float* scores_dev, const int32_t* forced_dev, float* logits_dev, void* stream) {
+    return ymt3_decode_constrained(h, enc_dev, B, n_steps, prompt_dev, n_prompt, tokens_dev, scores_dev, forced_dev, logits_dev, nullptr,
+                                   nullptr, stream);
 }
 
 extern "C" int ymt3_decode_prompted(ymt3_handle h, const void* enc_dev, int B, int n_steps, const int32_t* prompt_dev, int n_prompt,
@@ -1155,9 +1237,13 @@ extern "C" int ymt3_decode_greedy(ymt3_handle h, const void* enc_dev, int B, int
     return ymt3_decode_prompted(h, enc_dev, B, n_steps, nullptr, 0, tokens_dev, forced_dev, logits_dev, stream);
 }
 
-extern "C" int ymt3_transcribe_segments_scored(ymt3_handle h, const float* audio_dev, int B, int n_steps, const int32_t* prompt_dev,
-                                               int n_prompt, int32_t* tokens_dev, float* scores_dev, void* stream) {
+extern "C" int ymt3_transcribe_segments_constrained(ymt3_handle h, const float* audio_dev, int B, int n_steps, const int32_t* prompt_dev,
+                                                    int n_prompt, int32_t* tokens_dev, float* scores_dev, ymt3_constraint constraint,
+                                                    const int32_t* start_state_dev, void* stream) {
     int rc = check_call(h, B);
+    if (rc) return rc;
+    ConstraintView cv{};
+    rc = constraint_view(h, constraint, start_state_dev, &cv);
     if (rc) return rc;
     if (B == 0) return YMT3_OK;
     if (!audio_dev || !tokens_dev) FAIL(YMT3_ERR_ARG, "null buffer");
@@ -1169,7 +1255,13 @@ extern "C" int ymt3_transcribe_segments_scored(ymt3_handle h, const float* audio
     LAUNCH(launch_logmel(h->fe, audio_dev, h->mel, B, s));
     rc = encode_impl(h, h->mel, B, h->enc_out, s);
     if (rc) return rc;
-    return decode_impl(h, h->enc_out, B, n_steps, prompt_dev, n_prompt, tokens_dev, scores_dev, nullptr, nullptr, s);
+    return decode_impl(h, h->enc_out, B, n_steps, prompt_dev, n_prompt, tokens_dev, scores_dev, nullptr, nullptr, cv, s);
+}
+
+extern "C" int ymt3_transcribe_segments_scored(ymt3_handle h, const float* audio_dev, int B, int n_steps, const int32_t* prompt_dev,
+                                               int n_prompt, int32_t* tokens_dev, float* scores_dev, void* stream) {
+    return ymt3_transcribe_segments_constrained(h, audio_dev, B, n_steps, prompt_dev, n_prompt, tokens_dev, scores_dev, nullptr, nullptr,
+                                                stream);
 }
 
 extern "C" int ymt3_transcribe_segments_prompted(ymt3_handle h, const float* audio_dev, int B, int n_steps, const int32_t* prompt_dev,
@@ -1187,9 +1279,13 @@ extern "C" int ymt3_transcribe_segments(ymt3_handle h, const float* audio_dev, i
 // `interval` steps, pads and retires segments whose rows have all stopped, and encodes the next pending segments straight
 // into the freed slots (log-mel + encoder batched over the admissions, cross-K/V written into each slot's slabs).  Rows are
 // independent in every kernel, so the ids equal those of lock-step batches bit for bit.
-extern "C" int ymt3_transcribe_stream_scored(ymt3_handle h, const float* audio_dev, int n_segments, int n_steps, const int32_t* prompt_dev,
-                                             int n_prompt, int32_t* tokens_dev, float* scores_dev, int slots, int interval, void* stream) {
+extern "C" int ymt3_transcribe_stream_constrained(ymt3_handle h, const float* audio_dev, int n_segments, int n_steps,
+                                                  const int32_t* prompt_dev, int n_prompt, int32_t* tokens_dev, float* scores_dev, int slots,
+                                                  int interval, ymt3_constraint constraint, const int32_t* start_state_dev, void* stream) {
     int rc = check_call(h, 0);
+    if (rc) return rc;
+    ConstraintView cv{};
+    rc = constraint_view(h, constraint, start_state_dev, &cv);
     if (rc) return rc;
     if (n_segments < 0) FAIL(YMT3_ERR_ARG, "n_segments=%d", n_segments);
     if (n_segments == 0) return YMT3_OK;
@@ -1211,7 +1307,7 @@ extern "C" int ymt3_transcribe_stream_scored(ymt3_handle h, const float* audio_d
     ArgmaxArgs a{};
     a.h = h->h_dec; a.shared = h->shared; a.finished = h->finished; a.ssq = h->ssq; a.ssq_stride = h->maxR;
     a.R = R; a.V = k.vocab; a.d = d; a.n_channels = K; a.eos_id = k.eos_id; a.pad_id = k.pad_id;
-    a.row_pos = h->row_pos; a.row_out = h->row_out; a.row_prompt = h->row_prompt;
+    a.row_pos = h->row_pos; a.row_out = h->row_out; a.row_prompt = h->row_prompt; a.row_state = h->row_state;
     GET(h, "dec.embed", 1u, const_cast<bf16_t**>(&a.embed), (size_t)k.vocab * d);
     if (K > 1) GET(h, "dec.chan_embed", 1u, const_cast<bf16_t**>(&a.chan_embed), (size_t)K * d);
 
@@ -1219,7 +1315,9 @@ extern "C" int ymt3_transcribe_stream_scored(ymt3_handle h, const float* audio_d
     h->slot_mode = true;
     // loop state: every row starts stopped; admissions start them
     if (h->step_kernel && h->step_sync) HIP_TRY(hipMemsetAsync(h->step_sync, 0, (size_t)STEP_SYNC_LINES * CHAIN_LINE * sizeof(unsigned), s));
-    LAUNCH(launch_decode_init(a, 1, n_steps, 0, tokens_dev, nullptr, nullptr, prompt_dev, n_prompt, scores_dev, s));
+    ConstraintView cv_init = cv;
+    cv_init.start = nullptr;                  // (the rows' states are seeded at admission, from their segment's start states)
+    LAUNCH(launch_decode_init(a, 1, n_steps, 0, tokens_dev, nullptr, nullptr, prompt_dev, n_prompt, scores_dev, cv_init, s));
     HIP_TRY(hipMemsetD32Async(reinterpret_cast<hipDeviceptr_t>(h->finished), 1, (size_t)R, s));
     HIP_TRY(hipMemsetAsync(h->row_pos, 0, (size_t)R * sizeof(int), s));
     HIP_TRY(hipMemsetAsync(h->row_out, 0, (size_t)R * sizeof(long long), s));
@@ -1254,8 +1352,10 @@ extern "C" int ymt3_transcribe_stream_scored(ymt3_handle h, const float* audio_d
             GemmArgs g{h->enc_out + (size_t)i * T * d, h->wkv_all, h->ckv + (size_t)slot * H * T * 64, nullptr,
                        T, k.n_dec_layers * 2 * h->inner, d, d, d, 0, T, H, slots};
             LAUNCH(launch_gemm(EPI_KV_HEADMAJOR, g, s));
+            ConstraintView cv_seg = cv;
+            if (cv.start) cv_seg.start = cv.start + (size_t)(first_seg + i) * K;
             LAUNCH(launch_slot_start(a, slot * K, (long long)(first_seg + i) * K * n_steps, n_steps, h->row_out,
-                                     (long long)(first_seg + i) * K * n_prompt, n_prompt, h->row_prompt, s));
+                                     (long long)(first_seg + i) * K * n_prompt, n_prompt, h->row_prompt, cv_seg, s));
             slot_seg[(size_t)slot] = first_seg + i;
         }
         return YMT3_OK;
@@ -1281,8 +1381,8 @@ extern "C" int ymt3_transcribe_stream_scored(ymt3_handle h, const float* audio_d
             // a merged kernel gave up (the stream is idle here): start the queue again on the separate launches -- same ids
             rc = merged_fallback(h);
             if (rc) return rc;
-            return ymt3_transcribe_stream_scored(h, audio_dev, n_segments, n_steps, prompt_dev, n_prompt, tokens_dev, scores_dev, slots, interval,
-                                                 stream);
+            return ymt3_transcribe_stream_constrained(h, audio_dev, n_segments, n_steps, prompt_dev, n_prompt, tokens_dev, scores_dev, slots,
+                                                      interval, constraint, start_state_dev, stream);
         }
         free_slots.clear();
         for (int slot = 0; slot < slots; ++slot) {
@@ -1305,6 +1405,12 @@ extern "C" int ymt3_transcribe_stream_scored(ymt3_handle h, const float* audio_d
     }
     HIP_TRY(hipGetLastError());
     return YMT3_OK;
+}
+
+extern "C" int ymt3_transcribe_stream_scored(ymt3_handle h, const float* audio_dev, int n_segments, int n_steps, const int32_t* prompt_dev,
+                                             int n_prompt, int32_t* tokens_dev, float* scores_dev, int slots, int interval, void* stream) {
+    return ymt3_transcribe_stream_constrained(h, audio_dev, n_segments, n_steps, prompt_dev, n_prompt, tokens_dev, scores_dev, slots, interval,
+                                              nullptr, nullptr, stream);
 }
 
 extern "C" int ymt3_transcribe_stream_prompted(ymt3_handle h, const float* audio_dev, int n_segments, int n_steps, const int32_t* prompt_dev,
@@ -1334,7 +1440,8 @@ extern "C" int ymt3_profile_decode(ymt3_handle h, const void* enc_dev, int B, in
     hipStream_t s = (hipStream_t)stream;
     h->prof_ev.clear();
     h->prof_cls.clear();
-    rc = decode_impl(h, static_cast<const bf16_t*>(enc_dev), B, n_steps, nullptr, 0, tokens_dev, nullptr, nullptr, nullptr, s, stride);
+    rc = decode_impl(h, static_cast<const bf16_t*>(enc_dev), B, n_steps, nullptr, 0, tokens_dev, nullptr, nullptr, nullptr, ConstraintView{}, s,
+                     stride);
     hipError_t e = hipStreamSynchronize(s);
     for (int i = 0; i < YMT3_PROFILE_CLASSES; ++i) { ms_by_class[i] = 0.f; launches_by_class[i] = 0; }
     for (size_t i = 0; i < h->prof_cls.size(); ++i) {

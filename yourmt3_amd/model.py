@@ -9,6 +9,7 @@ the gfx950 kernels.  torch is used for device buffers and the current HIP stream
 from __future__ import annotations
 
 import ctypes
+import weakref
 from typing import Dict, List, Optional
 
 import numpy as np
@@ -16,12 +17,45 @@ import torch
 
 from . import _lib
 from .config import YMT3Config, to_c
+from .constraint import TokenAutomaton
 from .tables import derived_tables
 from .weights import make_weights, pack_blob
 
 
 def _ptr(t: Optional[torch.Tensor]):
     return ctypes.c_void_p(t.data_ptr()) if t is not None else None
+
+
+class DecodeConstraint:
+    """A token automaton uploaded to one model's device (YourMT3.compile_constraint; include/ymt3.h, constraints).  Freed by
+    close(), or by the model's close()."""
+
+    def __init__(self, model: "YourMT3", automaton: TokenAutomaton):
+        self.automaton = automaton
+        self.n_states = automaton.n_states
+        self._lib = model._lib
+        self._c = ctypes.c_void_p()
+        bits = np.ascontiguousarray(automaton.bits())
+        nxt = np.ascontiguousarray(automaton.next, dtype=np.int32)
+        _lib.check(self._lib.ymt3_constraint_create(model._handle, automaton.n_states, automaton.vocab, bits.ctypes.data,
+                                                    nxt.ctypes.data, ctypes.byref(self._c)))
+
+    @property
+    def ptr(self):
+        if not self._c.value:
+            raise ValueError("the constraint has been closed")
+        return self._c
+
+    def close(self):
+        if getattr(self, "_c", None) is not None and self._c.value:
+            self._lib.ymt3_constraint_destroy(self._c)
+            self._c = ctypes.c_void_p()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
 
 
 class YourMT3:
@@ -39,8 +73,11 @@ class YourMT3:
         ccfg = to_c(cfg, self.max_batch)
         # `blob` is immutable bytes: c_char_p points at its buffer (no second ~91 MB host copy); ymt3_create only reads it
         _lib.check(self._lib.ymt3_create(ctypes.byref(ccfg), ctypes.c_char_p(blob), len(blob), device, ctypes.byref(self._handle)))
+        self._constraints = weakref.WeakSet()
 
     def close(self):
+        for c in list(getattr(self, "_constraints", ())):
+            c.close()
         if getattr(self, "_handle", None) and self._handle.value:
             self._lib.ymt3_destroy(self._handle)
             self._handle = ctypes.c_void_p()
@@ -94,6 +131,34 @@ class YourMT3:
             raise ValueError(f"task_tokens ids must lie in [0, {cfg.vocab})")
         if P + n_steps > cfg.max_decode_len:
             raise ValueError(f"{P} prompt + {n_steps} emitted steps exceed max_decode_len {cfg.max_decode_len}")
+        return t.to(self.device, torch.int32).contiguous()
+
+    def compile_constraint(self, automaton: TokenAutomaton) -> DecodeConstraint:
+        """Validate and upload a token automaton (yourmt3_amd/constraint.py) for decode / inference(constraint=...)."""
+        if automaton.vocab != self.cfg.vocab:
+            raise ValueError(f"automaton vocab {automaton.vocab} != the model's {self.cfg.vocab}")
+        c = DecodeConstraint(self, automaton)
+        self._constraints.add(c)
+        return c
+
+    def _start_states(self, constraint: Optional[DecodeConstraint], start_states, B: int) -> Optional[torch.Tensor]:
+        """start_states -> (B, K) int32 device tensor, or None (state 0).  (K,) is every segment's; (B, K) per segment."""
+        if constraint is None:
+            if start_states is not None:
+                raise ValueError("start_states without a constraint")
+            return None
+        if start_states is None:
+            return None
+        K = self.cfg.n_channels
+        t = torch.as_tensor(start_states)
+        if t.dtype.is_floating_point or t.dtype == torch.bool or t.dtype.is_complex:
+            raise ValueError(f"start_states must be integer states, got {t.dtype}")
+        if t.dim() == 1 and t.shape[0] == K:
+            t = t[None, :].expand(B, K)
+        elif not (t.dim() == 2 and tuple(t.shape) == (B, K)):
+            raise ValueError(f"start_states must be ({K},) or ({B}, {K}), got {tuple(t.shape)}")
+        if t.numel() and (int(t.min()) < 0 or int(t.max()) >= constraint.n_states):
+            raise ValueError(f"start states must lie in [0, {constraint.n_states})")
         return t.to(self.device, torch.int32).contiguous()
 
     @property
@@ -160,11 +225,14 @@ class YourMT3:
         return enc
 
     def decode(self, enc: torch.Tensor, n_steps: Optional[int] = None, forced: Optional[torch.Tensor] = None,
-               return_logits: bool = False, prompt=None, return_scores: bool = False):
+               return_logits: bool = False, prompt=None, return_scores: bool = False, constraint: Optional[DecodeConstraint] = None,
+               start_states=None):
         """Greedy decode of n_steps emitted tokens per row.  `prompt` ((P,), (B, P) or (B, K, P) ids): fed after the start id before
         anything is emitted (HF decoder_input_ids = [pad, *prompt]); tokens / forced / logits index emitted steps only.
         Returns tokens, then logits if `return_logits`, then scores if `return_scores`: (B, K, n_steps) f32 log-probabilities of
-        the fed ids (the emitted ones, or `forced`'s), include/ymt3.h, token scores."""
+        the fed ids (the emitted ones, or `forced`'s), include/ymt3.h, token scores.  `constraint` (compile_constraint) with
+        `start_states` ((K,) or (B, K); None: state 0): every row emits only what its automaton allows (include/ymt3.h,
+        constraints); scores are then those of the masked distribution, logits stay raw."""
         cfg = self.cfg
         enc = enc.to(self.device, torch.bfloat16).contiguous()
         B = enc.shape[0]
@@ -176,7 +244,12 @@ class YourMT3:
             raise ValueError("forced must be (B, n_channels, n_steps)")
         lg = torch.empty(B, cfg.n_channels, n_steps, cfg.vocab, device=self.device, dtype=torch.float32) if return_logits else None
         sc = torch.empty(B, cfg.n_channels, n_steps, device=self.device, dtype=torch.float32) if return_scores else None
-        if sc is not None:
+        st = self._start_states(constraint, start_states, B)
+        if constraint is not None:
+            _lib.check(self._lib.ymt3_decode_constrained(self._handle, _ptr(enc), B, n_steps, _ptr(p), 0 if p is None else int(p.shape[-1]),
+                                                         _ptr(tokens), _ptr(sc), _ptr(f), _ptr(lg), constraint.ptr, _ptr(st),
+                                                         self._stream()))
+        elif sc is not None:
             _lib.check(self._lib.ymt3_decode_scored(self._handle, _ptr(enc), B, n_steps, _ptr(p), 0 if p is None else int(p.shape[-1]),
                                                     _ptr(tokens), _ptr(sc), _ptr(f), _ptr(lg), self._stream()))
         elif p is None:
@@ -188,16 +261,26 @@ class YourMT3:
         return out if len(out) > 1 else tokens
 
     # ------------------------------------------------------------------ reference-shaped API
-    def inference(self, audio: torch.Tensor, task_tokens=None, max_token_length: Optional[int] = None, return_scores: bool = False):
+    def inference(self, audio: torch.Tensor, task_tokens=None, max_token_length: Optional[int] = None, return_scores: bool = False,
+                  constraint: Optional[DecodeConstraint] = None, start_states=None):
         """(B, 1, S) or (B, S) audio -> (B, K, L) int32 token ids: the whole hot path, one C call.  `task_tokens` ((P,), (B, P) or
         (B, K, P) ids, e.g. TaskManager.task_prompt): the decoder is prompted with them and L tokens are emitted after them.
         `return_scores`: returns (tokens, scores), scores (B, K, L) f32 the log-probability of every emitted token (0.0 for the
-        PAD after a row's EOS), as HF compute_transition_scores(normalize_logits=True)."""
+        PAD after a row's EOS), as HF compute_transition_scores(normalize_logits=True).  `constraint` / `start_states`: as
+        decode()."""
         a = self._audio2d(audio)
         B = a.shape[0]
         L = int(max_token_length or self.cfg.max_decode_len)
         p = self._prompt(task_tokens, B, L)
         tokens = torch.empty(B, self.cfg.n_channels, L, device=self.device, dtype=torch.int32)
+        st = self._start_states(constraint, start_states, B)
+        if constraint is not None:
+            scores = torch.empty(B, self.cfg.n_channels, L, device=self.device, dtype=torch.float32) if return_scores else None
+            if B:
+                _lib.check(self._lib.ymt3_transcribe_segments_constrained(
+                    self._handle, _ptr(a), B, L, _ptr(p), 0 if p is None else int(p.shape[-1]), _ptr(tokens), _ptr(scores),
+                    constraint.ptr, _ptr(st), self._stream()))
+            return (tokens, scores) if return_scores else tokens
         if return_scores:
             scores = torch.empty(B, self.cfg.n_channels, L, device=self.device, dtype=torch.float32)
             if B:
@@ -212,10 +295,12 @@ class YourMT3:
         return tokens
 
     def inference_stream(self, audio_segments: torch.Tensor, max_token_length: Optional[int] = None, slots: int = 0,
-                         interval: int = 8, task_tokens=None, return_scores: bool = False):
+                         interval: int = 8, task_tokens=None, return_scores: bool = False,
+                         constraint: Optional[DecodeConstraint] = None, start_states=None):
         """(N, 1, S) or (N, S) audio, any N -> (N, K, L) int32 ids with continuous batching: `slots` decoder slots are
         refilled from the queue as segments emit EOS (needs eos_id >= 0 to gain anything).  Ids equal inference()'s, with the
-        same `task_tokens` ((P,), (N, P) or (N, K, P)).  `return_scores`: (tokens, scores) as inference()."""
+        same `task_tokens` ((P,), (N, P) or (N, K, P)).  `return_scores`: (tokens, scores) as inference().  `constraint` /
+        `start_states` ((K,) or (N, K)): as inference(); each segment's rows start from its own states when it is admitted."""
         a = audio_segments[:, 0, :] if audio_segments.dim() == 3 else audio_segments
         if a.shape[-1] != self.cfg.segment_samples:
             raise ValueError(f"segments must have {self.cfg.segment_samples} samples, got {a.shape[-1]}")
@@ -224,6 +309,14 @@ class YourMT3:
         L = int(max_token_length or self.cfg.max_decode_len)
         p = self._prompt(task_tokens, N, L)
         tokens = torch.empty(N, self.cfg.n_channels, L, device=self.device, dtype=torch.int32)
+        st = self._start_states(constraint, start_states, N)
+        if constraint is not None:
+            scores = torch.empty(N, self.cfg.n_channels, L, device=self.device, dtype=torch.float32) if return_scores else None
+            if N:
+                _lib.check(self._lib.ymt3_transcribe_stream_constrained(
+                    self._handle, _ptr(a), N, L, _ptr(p), 0 if p is None else int(p.shape[-1]), _ptr(tokens), _ptr(scores), int(slots),
+                    int(interval), constraint.ptr, _ptr(st), self._stream()))
+            return (tokens, scores) if return_scores else tokens
         if return_scores:
             scores = torch.empty(N, self.cfg.n_channels, L, device=self.device, dtype=torch.float32)
             if N:
@@ -239,24 +332,33 @@ class YourMT3:
         return tokens
 
     def inference_file(self, bsz: int, audio_segments: torch.Tensor, max_token_length: Optional[int] = None,
-                       task_tokens=None, return_scores: bool = False):
+                       task_tokens=None, return_scores: bool = False, constraint: Optional[DecodeConstraint] = None,
+                       start_states=None):
         """Split (N, 1, S) segments into batches of `bsz`; one (b, K, L) int array per batch.  `task_tokens`: (P,) for every
         segment, or (N, P) / (N, K, P), sliced with the batches.  `return_scores`: (token_batches, score_batches), the second a
-        list of (b, K, L) float32 arrays (inference(return_scores=True))."""
+        list of (b, K, L) float32 arrays (inference(return_scores=True)).  `constraint` / `start_states` ((K,) or (N, K),
+        sliced with the batches): as inference()."""
         bsz = min(int(bsz), self.max_batch)
         N = audio_segments.shape[0]
         tt = None if task_tokens is None else torch.as_tensor(task_tokens)
         if tt is not None and tt.dim() > 1 and tt.shape[0] != N:
             raise ValueError(f"task_tokens has {tt.shape[0]} rows for {N} segments")
+        ss = None if start_states is None else torch.as_tensor(start_states)
+        if ss is not None and ss.dim() == 2 and ss.shape[0] != N:
+            raise ValueError(f"start_states has {ss.shape[0]} rows for {N} segments")
         out, scores = [], []
         for i in range(0, N, bsz):
             ti = tt if tt is None or tt.dim() == 1 else tt[i:i + bsz]
+            kw = {}
+            if constraint is not None or ss is not None:
+                kw = {"constraint": constraint, "start_states": ss if ss is None or ss.dim() != 2 else ss[i:i + bsz]}
             if return_scores:
-                t, sc = self.inference(audio_segments[i:i + bsz], task_tokens=ti, max_token_length=max_token_length, return_scores=True)
+                t, sc = self.inference(audio_segments[i:i + bsz], task_tokens=ti, max_token_length=max_token_length, return_scores=True,
+                                       **kw)
                 out.append(t.cpu().numpy())
                 scores.append(sc.cpu().numpy())
             else:
-                out.append(self.inference(audio_segments[i:i + bsz], task_tokens=ti, max_token_length=max_token_length).cpu().numpy())
+                out.append(self.inference(audio_segments[i:i + bsz], task_tokens=ti, max_token_length=max_token_length, **kw).cpu().numpy())
         return (out, scores) if return_scores else out
 
     PROFILE_CLASSES = ["qkv_cache_gemm", "self_attn", "self_o_gemm", "cross_q_gemm", "cross_attn", "cross_o_gemm",

@@ -20,6 +20,9 @@ of upstream; nothing in the reference pins them.  The ids sit
 Confidences: with the token scores of YourMT3.inference(return_scores=True) (log-probabilities, include/ymt3.h, token
 scores), every onset event carries the score of its pitch or drum token and every note `confidence = exp(score)` of its
 onset.  Both fields are left out of comparisons, ordering and hashing: notes without scores are exactly what they were.
+
+Constraints: `event_automaton(programs)` is the grammar above as a token automaton (yourmt3_amd/constraint.py) for
+YourMT3.inference(constraint=...): the decoder then emits only well-formed segments whose notes belong to the allowed programs.
 """
 from __future__ import annotations
 
@@ -29,6 +32,7 @@ from typing import Dict, Iterable, List, Optional, Sequence, Tuple
 
 import numpy as np
 
+from .constraint import TokenAutomaton, stack
 from .vocab import Codec, Event, EOS, NUM_SPECIAL, PAD, UNK
 
 DRUM_PROGRAM = 128
@@ -247,6 +251,7 @@ class TaskManager:
             if len(set(ids.values())) != len(ids) or any(i < self.codec.size for i in ids.values()):
                 raise ValueError(f"task-token ids {ids} must be distinct and must not reuse a codec event id (< {self.codec.size})")
             self.task_token_ids = ids
+        self.vocab_size = int(vocab_size)
         self.tokenizer = NoteEventTokenizer(self.codec, self.task_token_ids.values())
         self.num_decoding_channels = self.task["channels"]
         self.max_note_token_length = self.task["max_tokens"]
@@ -262,6 +267,60 @@ class TaskManager:
             raise ValueError(f"unknown sub-task {name!r} of {self.task_name!r}; known: {sorted(self.subtasks)}")
         ids = np.array([self.task_token_ids[t] for t in self.subtasks[name]], np.int32)
         return np.array(np.broadcast_to(ids, (int(n_segments), self.num_decoding_channels, ids.size)))     # (a writable copy)
+
+    def event_automaton(self, programs: Optional[Iterable[int]] = None) -> Tuple[TokenAutomaton, np.ndarray]:
+        """The segment grammar as a token automaton for the allowed programs P (`programs`; None: all of 0..129, 128 = drums,
+        129 = singing) -> (automaton, start states (channels,) int32).  With 13 channels channel k gets P & MC13_GROUPS[k]
+        (stacked: every channel's own six states).  Tokens that decode_segment counts as invalid are never allowed (PAD, UNK,
+        ids beyond the codec, task tokens included), nor are notes of programs outside P; a channel whose P is empty can only
+        emit TIE, EOS."""
+        n_prog = self.codec.range_of("program")[1] - self.codec.range_of("program")[0]
+        P = set(range(n_prog)) if programs is None else {int(p) for p in programs}
+        bad = sorted(p for p in P if not 0 <= p < n_prog)
+        if bad:
+            raise ValueError(f"programs {bad} outside [0, {n_prog})")
+        if self.num_decoding_channels == 1:
+            sets = [P]
+        else:
+            sets = [P & set(progs) for _, progs in MC13_GROUPS[:self.num_decoding_channels]]
+        aut, offsets = stack([self._segment_grammar(p) for p in sets])
+        return aut, np.array(offsets, np.int32)
+
+    def _segment_grammar(self, P) -> TokenAutomaton:
+        """Six states: section (0 tie, 1 body) x current program (0 unset -- decode_segment reads program 0 --, 1 pitched,
+        2 drum); state = 3 * section + program, start 0."""
+        c, V = self.codec, self.vocab_size
+        rng = {t: c.range_of(t) for t in ("shift", "pitch", "velocity", "tie", "program", "drum")}
+        prog0 = rng["program"][0]
+        tie_tok = rng["tie"][0]
+        allowed = np.zeros((6, V), bool)
+        nxt = np.zeros((6, V), np.int32)
+        for sec in (0, 1):
+            for prog in (0, 1, 2):
+                s = 3 * sec + prog
+                a = allowed[s]
+                pitch_ok = prog == 1 or (prog == 0 and 0 in P) or (sec == 1 and prog == 2)
+                if pitch_ok:
+                    a[slice(*rng["pitch"])] = True
+                for p in P:
+                    if sec == 1 or p != DRUM_PROGRAM:
+                        a[prog0 + p] = True
+                if sec == 0:
+                    a[tie_tok] = True
+                else:
+                    if P:                           # (with nothing to transcribe a channel says TIE, EOS and nothing else)
+                        a[slice(*rng["shift"])] = True
+                        a[slice(*rng["velocity"])] = True
+                    if DRUM_PROGRAM in P:
+                        a[slice(*rng["drum"])] = True
+                    a[EOS] = True
+                # transitions, for every token (forced ids included): TIE and SHIFT open the body, PROGRAM sets the program
+                nxt[s, :] = s
+                nxt[s, tie_tok] = 3 + prog
+                nxt[s, slice(*rng["shift"])] = 3 + prog
+                nxt[s, slice(*rng["program"])] = 3 * sec + 1
+                nxt[s, prog0 + DRUM_PROGRAM] = 3 * sec + 2
+        return TokenAutomaton(allowed, nxt)
 
     def channel_of_program(self, program: int) -> int:
         if self.num_decoding_channels == 1:

@@ -17,14 +17,17 @@ from .task_manager import TaskManager, drop_low_confidence
 def transcribe(model, audio_info: Union[str, dict, np.ndarray], task_manager: Optional[TaskManager] = None, bsz: int = 8,
                output_dir: str = ".", max_token_length: Optional[int] = None, return_notes: bool = False,
                continuous: bool = False, subtask: Optional[str] = None, confidence: bool = False,
-               min_confidence: Optional[float] = None):
+               min_confidence: Optional[float] = None, constrained: bool = False, programs=None):
     """`continuous=True` decodes the file's segments through `bsz` slots with continuous batching
     (YourMT3.inference_stream: segments leave at EOS and the next ones enter) instead of fixed batches; same ids.
     `subtask`: for a task-conditioned TaskManager (e.g. "singing_drum_v1"), the sub-task whose task tokens prompt every
     segment's decode (None: its "default"); tasks without task tokens take no prompt and refuse a subtask.
     `confidence=True` decodes with token scores (include/ymt3.h, token scores): every returned note carries
     `confidence` = the probability of its onset's token.  `min_confidence` implies it and drops the notes below it before
-    the MIDI file is written.  The ids, and so the notes, are those of the unscored decode."""
+    the MIDI file is written.  The ids, and so the notes, are those of the unscored decode.
+    `constrained=True` decodes under the TaskManager's segment grammar (TaskManager.event_automaton; include/ymt3.h,
+    constraints): no invalid tokens, and with the 13-channel decoder every channel keeps to its own instrument group.
+    `programs` (GM programs, 128 = drums, 129 = singing) implies it and limits the notes to those programs."""
     cfg = model.cfg
     if task_manager is None:
         task_manager = TaskManager("mc13_full_plus_256" if cfg.n_channels == 13 else "mt3_full_plus")
@@ -54,6 +57,27 @@ def transcribe(model, audio_info: Union[str, dict, np.ndarray], task_manager: Op
     scored = confidence or min_confidence is not None
     if scored:
         kw["return_scores"] = True
+    constraint = None
+    if constrained or programs is not None:
+        aut, starts = task_manager.event_automaton(programs)
+        constraint = model.compile_constraint(aut)
+        kw["constraint"] = constraint
+        kw["start_states"] = starts
+    try:
+        batches, score_batches = _decode(model, segments, bsz, L, continuous, scored, kw)
+    finally:
+        if constraint is not None:
+            constraint.close()
+    notes = task_manager.tokens_to_notes(batches, start_secs, end_sec=n_samples / cfg.sample_rate, score_batches=score_batches)
+    if min_confidence is not None:
+        notes = drop_low_confidence(notes, float(min_confidence))
+    os.makedirs(output_dir, exist_ok=True)
+    midi_path = write_midi(notes, os.path.join(output_dir, name + ".mid"))
+    return (midi_path, notes) if return_notes else midi_path
+
+
+def _decode(model, segments, bsz, L, continuous, scored, kw):
+    """-> (token batches, score batches or None) through continuous batching or fixed batches"""
     score_batches = None
     if continuous:
         out = model.inference_stream(segments, max_token_length=L, slots=bsz, **kw)
@@ -63,9 +87,4 @@ def transcribe(model, audio_info: Union[str, dict, np.ndarray], task_manager: Op
     else:
         out = model.inference_file(bsz, segments, max_token_length=L, **kw)
         batches, score_batches = out if scored else (out, None)
-    notes = task_manager.tokens_to_notes(batches, start_secs, end_sec=n_samples / cfg.sample_rate, score_batches=score_batches)
-    if min_confidence is not None:
-        notes = drop_low_confidence(notes, float(min_confidence))
-    os.makedirs(output_dir, exist_ok=True)
-    midi_path = write_midi(notes, os.path.join(output_dir, name + ".mid"))
-    return (midi_path, notes) if return_notes else midi_path
+    return batches, score_batches
