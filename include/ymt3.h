@@ -67,7 +67,14 @@ int         ymt3_abi_version(void);
 const char* ymt3_last_error(void);
 
 /* Parse the weight blob (format: yourmt3_amd/weights.py), upload it to `device`, derive the
- * window / twiddle / mel / relative-position tables, allocate caches and scratch. */
+ * window / twiddle / mel / relative-position tables, allocate caches and scratch.
+ * Shapes the kernels run, checked here (YMT3_ERR_UNSUPPORTED, the message names the field; nothing
+ * accepted here is refused later by a launch):
+ *   d_model 512, n_heads * d_kv = 8 * 64; vocab % 16 == 0; 0..64 encoder and 1..64 decoder layers;
+ *   n_fft 512 or 2048; n_mels % 64 == 0; hop even and <= 256;
+ *   n_frames = 1 + segment_samples / hop: 64, 128, 256 or 512 (Perceiver-TF: 64, 128 or 256);
+ *   dense FFN: d_ff 512, 1024 or 2048; MoE FFN: d_ff 2048, 2..16 experts, top-2;
+ *   Perceiver-TF: ptf_d 128 or 256, n_latents 32 or 64, n_mels 64, 128 or 256. */
 int  ymt3_create(const ymt3_config* cfg, const void* blob_host, size_t blob_bytes, int device, ymt3_handle* out);
 void ymt3_destroy(ymt3_handle h);
 

@@ -289,6 +289,18 @@ static int create_impl(ymt3_ctx* c, const ymt3_config* cfg, const void* blob, si
     if (k.segment_samples <= k.n_fft / 2) FAIL(YMT3_ERR_UNSUPPORTED, "segment_samples must exceed n_fft/2 (reflect padding)");
     if (k.pad_id < 0 || k.pad_id >= k.vocab || k.eos_id >= k.vocab) FAIL(YMT3_ERR_ARG, "pad_id / eos_id outside the vocabulary");
     if (k.vocab % 16 || k.d_ff % 128) FAIL(YMT3_ERR_UNSUPPORTED, "vocab %% 16 and d_ff %% 128 must be 0");
+    // shapes the kernels' launch guards refuse: an error here, naming the field, and not "rejected its shape" from the first encode / decode
+    if (k.n_fft != 2048 && k.n_fft != 512) FAIL(YMT3_ERR_UNSUPPORTED, "n_fft must be 2048 or 512 (got %d)", k.n_fft);
+    if (k.n_mels % 64) FAIL(YMT3_ERR_UNSUPPORTED, "n_mels must be a multiple of 64 (got %d)", k.n_mels);
+    if (k.hop > 256 || k.hop % 2)
+        FAIL(YMT3_ERR_UNSUPPORTED, "hop must be even and at most 256 (got %d): the log-mel kernel stages 8 frames in LDS and reads sample pairs", k.hop);
+    if (k.encoder_type == YMT3_ENC_T5 && c->T != 64 && c->T != 128 && c->T != 256 && c->T != 512)
+        FAIL(YMT3_ERR_UNSUPPORTED, "n_frames must be 64, 128, 256 or 512 for the T5 encoder's self-attention (got %d)", c->T);
+    if (k.encoder_type == YMT3_ENC_PERCEIVER_TF && c->T != 64 && c->T != 128 && c->T != 256)
+        FAIL(YMT3_ERR_UNSUPPORTED, "n_frames must be 64, 128 or 256 for the Perceiver-TF temporal attention (got %d)", c->T);
+    if (k.dec_ffn == YMT3_FFN_DENSE && k.d_ff != 512 && k.d_ff != 1024 && k.d_ff != 2048)
+        FAIL(YMT3_ERR_UNSUPPORTED, "a dense d_ff must be 512, 1024 or 2048 (got %d): the decoder's FFN-out kernel is instantiated at those K", k.d_ff);
+    if (k.dec_ffn != YMT3_FFN_DENSE && k.dec_ffn != YMT3_FFN_MOE) FAIL(YMT3_ERR_UNSUPPORTED, "unknown dec_ffn %d", k.dec_ffn);
 
     HIP_TRY(hipSetDevice(c->device));
     int rc = parse_blob(c, blob, nbytes);
@@ -308,8 +320,7 @@ static int create_impl(ymt3_ctx* c, const ymt3_config* cfg, const void* blob, si
     fe.n_mel_w = (int)(c->tensors["fe.mel_w"].nbytes / 4);
     fe.n_fft = nfft; fe.hop = k.hop; fe.n_mels = k.n_mels; fe.n_samples = k.segment_samples;
     fe.n_frames = c->T; fe.log_floor = k.log_floor;
-    if (nfft != 2048 && nfft != 512) FAIL(YMT3_ERR_UNSUPPORTED, "n_fft must be 2048 or 512");
-    if (k.n_mels % 64) FAIL(YMT3_ERR_UNSUPPORTED, "n_mels must be a multiple of 64");
+    if (fe.n_mel_w > 2304) FAIL(YMT3_ERR_UNSUPPORTED, "fe.mel_w holds %d filterbank weights; the log-mel kernel stages at most 2304", fe.n_mel_w);
 
     const size_t BT = (size_t)c->maxB * c->T, d = k.d_model, R = c->maxR;
     if (dev_alloc(c, (void**)&c->mel, BT * k.n_mels * 4)) return YMT3_ERR_HIP;
