@@ -549,22 +549,33 @@ def test_unfit_merged_kernel_takes_the_separate_launches(small, monkeypatch):
         m.close()
 
 
-def _moe_case(cfg, n, tol_max, tol_mean, tau, max_deficit, monkeypatch, min_safe=0.7, segments=4):
+def _moe_case(cfg, n, tol_max, tol_mean, tau, max_deficit, monkeypatch, min_safe=0.7, segments=4, enc=None, m=None, feed=None,
+              name=None, out=None):
     """Teacher-forced MoE decode vs the oracle at EVERY step.  Routing is discrete: where the 2nd and 3rd router logits are closer than
     the numerical noise, the HIP path may legitimately pick another expert than the oracle, which moves that step's logits by ~0.2.
     Rounds 1-2 excluded such (row, step) pairs by a router-gap threshold (and so covered 52 % of the fp8 steps).  Now the router's
     choices are recorded (debug hook ymt3_debug_moe_trace) and fed to the ORACLE: each choice must lie within `max_deficit` of the
-    oracle's own top-2 cut (a legitimate near-tie), and then logits and ids are compared at every step, with the usual argmax margin."""
-    monkeypatch.setenv("YMT3_DEBUG_HOOKS", "1")
-    m = _model(cfg, max_batch=segments)
-    monkeypatch.delenv("YMT3_DEBUG_HOOKS")
-    a = O.synthetic_audio(segments, cfg)
-    _, enc = O.encode(a, m.weights, cfg, True)
-    feed = O.greedy_decode(enc, m.weights, cfg, n, True)                     # the oracle's own stream (its own routing): the tokens both sides are fed
+    oracle's own top-2 cut (a legitimate near-tie), and then logits and ids are compared at every step, with the usual argmax margin.
+    By default `segments` synthetic segments go through the oracle encoder, a handle of that many rows is created and both sides are fed
+    the oracle's own stream.  Any row count instead (tests/test_row_space.py): `enc` ((B, T, d_model) fp32, host) is the encoder output
+    both sides decode, `m` a handle created under YMT3_DEBUG_HOOKS=1 with max_batch >= B, `feed` ((B, 1, n) ids) what both sides are fed;
+    `name` names the report entry, and `out` (a dict) receives the recorded choices (steps, layers, rows, 2), ids, logits and chains."""
+    if m is None:
+        monkeypatch.setenv("YMT3_DEBUG_HOOKS", "1")
+        m = _model(cfg, max_batch=segments)
+        monkeypatch.delenv("YMT3_DEBUG_HOOKS")
+    if enc is None:
+        a = O.synthetic_audio(segments, cfg)
+        _, enc = O.encode(a, m.weights, cfg, True)
+    if feed is None:
+        feed = O.greedy_decode(enc, m.weights, cfg, n, True)                 # the oracle's own stream (its own routing): the tokens both sides are fed
+    feed = feed.cpu()
+    rows = enc.shape[0] * cfg.n_channels
     trace = m.moe_trace(n)
     e = enc.bfloat16().cuda()
     got_t, got_l = m.decode(e, n, forced=feed.cuda(), return_logits=True)
-    sel = trace.cpu()                                                        # (steps, layers, rows, 2)
+    chains = m.last_decode_chains
+    sel = trace.cpu()[:, :, :rows]                                           # (steps, layers, rows, 2)
     assert int(sel.min()) >= 0 and int(sel.max()) < cfg.n_experts and bool((sel[..., 0] != sel[..., 1]).all())
     O.MOE_FORCED_SEL = iter([sel[t, l] for t in range(n) for l in range(cfg.n_dec_layers)])
     O.MOE_FORCED_DEFICIT = []
@@ -574,7 +585,7 @@ def _moe_case(cfg, n, tol_max, tol_mean, tau, max_deficit, monkeypatch, min_safe
     finally:
         O.MOE_FORCED_SEL = None
         O.MOE_FORCED_DEFICIT = None
-    name = f"moe_fp8{cfg.moe_fp8}_{n}_steps_routing_teacher_forced"
+    name = name or f"moe_fp8{cfg.moe_fp8}_{n}_steps_routing_teacher_forced"
     rec = _check_ids(name, got_t, ref_t, ref_l, got_l, tau=tau, tol_max=tol_max, tol_mean=tol_mean, min_safe=min_safe, curve=32)
     rec["router_choices"] = int(deficit.numel())
     rec["router_choices_outside_the_oracle_top2"] = int((deficit > 0).sum())
@@ -583,6 +594,8 @@ def _moe_case(cfg, n, tol_max, tol_mean, tau, max_deficit, monkeypatch, min_safe
     assert torch.equal(m.decode(e, n), m.decode(e, n))        # routing + grouped GEMM are reproducible
     _lib_check = m._lib.ymt3_debug_moe_trace(m._handle, None, 0, 0)
     assert _lib_check == 0
+    if out is not None:
+        out.update(trace=sel, got_t=got_t.cpu(), got_l=got_l.cpu(), chains=chains, rec=rec)
     return m
 
 

@@ -49,6 +49,8 @@ REGIMES = [
     ("merged", {}, {}, 4),
     ("separate", {}, {"YMT3_NO_ATTN_PAIR": "1", "YMT3_NO_GEMM_CHAIN": "1"}, 4),
     ("two_chains", {}, {}, 224),
+    ("ticket_no_fold", {}, {}, 100),          # one chain beyond 96 rows: the argmax kernel's two-level ticket, the self-O GEMM launched
+    ("two_wave_self_attn", {}, {}, 264),      # beyond 2048 (row, head) pairs: the 2-waves-per-(row, head) self-attention
     ("mc13", {"n_channels": 13, "max_decode_len": 32}, {}, 2),
     ("moe_fp8", {"dec_ffn": FFN_MOE, "moe_fp8": 1}, {}, 4),
     ("step_kernel", {}, {"YMT3_STEP_KERNEL": "1"}, 4),
