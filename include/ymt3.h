@@ -101,7 +101,20 @@ int ymt3_encode(ymt3_handle h, const float* mel_dev, int B, void* enc_dev, void*
 
 /* a6+a7+a8(+a10): encoder output bf16 -> greedy token ids (B, n_channels, n_steps) int32.
  * forced_dev (may be NULL): (B, n_channels, n_steps) int32 teacher-forcing ids fed back instead of
- * the argmax.  logits_dev (may be NULL): (B, n_channels, n_steps, vocab) f32 per-step logits. */
+ * the argmax.  logits_dev (may be NULL): (B, n_channels, n_steps, vocab) f32 per-step logits.
+ * The emitted id is the lowest index among the maxima of the row's f32 logits.
+ *
+ * Non-finite values.  Float PCM is not range-limited, so a corrupt input can reach every stage; what then happens is defined:
+ *   - front end: a NaN sample makes every frame that contains it NaN in every mel bin (a NaN power is not read as the floor); a
+ *     power beyond the f32 range gives a non-finite log-mel (+inf, or NaN where a zero filter weight meets the infinite bin).
+ *     Frames and segments without such a sample are untouched.
+ *   - a segment with a non-finite log-mel has a NaN encoder output and NaN logits in all of its rows, and only in its rows: the other
+ *     rows of the batch keep the bits they have in a clean batch, and the next call on the handle is not affected.
+ *   - argmax: NaN logits take no part in the comparison.  A row in which no (allowed) logit compares greater than -3.4e38 -- all
+ *     NaN, all -inf -- emits the lowest index, under a constraint the lowest index its state allows, as an exact tie does; the
+ *     automaton follows that id.  Every id written to tokens_dev lies in [0, vocab) (or is pad_id), and no index derived from a
+ *     logit reaches memory unclamped.
+ *   - scores: the score of a step whose logits are NaN, or all -inf, is NaN. */
 int ymt3_decode_greedy(ymt3_handle h, const void* enc_dev, int B, int n_steps, int32_t* tokens_dev,
                        const int32_t* forced_dev, float* logits_dev, void* stream);
 

@@ -331,7 +331,8 @@ def decoder_step(tokens: Tensor, state: DecoderState, ckv, W: Dict[str, Tensor],
     h = W["dec.embed"][tokens]
     if K > 1:
         h = h + W["dec.chan_embed"][torch.arange(R) % K]
-    h = h[:, None, :].float()
+    h = h[:, None, :]
+    h = h if h.dtype == torch.float64 else h.float()           # (double weights: the whole step accumulates in double, see _r)
     t = state.pos
     bias_d = decoder_bias_by_distance(W["dec.relbias"], t + 1, cfg)           # (H, t+1) by distance
     bias = bias_d[:, torch.arange(t, -1, -1)][None, :, None, :]               # key j -> distance t-j

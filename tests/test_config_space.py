@@ -100,11 +100,11 @@ def _regimes(cfg):
     return [r for r in ENVS if r != "step" or _step_ok(cfg)]
 
 
-def _create(cfg, env, monkeypatch, max_batch=4):
+def _create(cfg, env, monkeypatch, max_batch=4, **kw):
     for k, v in env.items():
         monkeypatch.setenv(k, v)
     try:
-        return _model(cfg, max_batch=max_batch)
+        return _model(cfg, max_batch=max_batch, **kw)
     finally:
         for k in env:
             monkeypatch.delenv(k)

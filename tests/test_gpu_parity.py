@@ -33,12 +33,12 @@ FULL = YMT3Config(max_decode_len=128)
 MC3 = YMT3Config(segment_samples=8191, max_decode_len=32, n_channels=3)
 
 
-def _model(cfg, max_batch=4, **kw):
+def _model(cfg, max_batch=4, weights=None, **kw):
     """A model whose close() fails the test if a merged decode kernel gave up waiting and the call was silently re-run through the separate
     launches (include/ymt3.h, ymt3_set_abort_recovery): recovery must never be what makes a parity test pass.  Tests of the recovery
-    itself set `fallback_expected`."""
+    itself set `fallback_expected`.  `weights`: another weight set than the seeded default (tests/value_regimes.py)."""
     from yourmt3_amd.model import YourMT3
-    m = YourMT3(cfg, make_weights(cfg, seed=1234), device=0, max_batch=max_batch, **kw)
+    m = YourMT3(cfg, make_weights(cfg, seed=1234) if weights is None else weights, device=0, max_batch=max_batch, **kw)
     plain_close = m.close
 
     def close():
@@ -189,6 +189,24 @@ def test_pipelined_large_m_gemm(small, M, N, K):
     assert torch.equal(got, Wp.float()[:, (torch.arange(M) * 7) % K].T.contiguous())
     for _ in range(3):                                       # repeated launches: a stage read before its DMA landed would differ
         assert torch.equal(small.test_gemm(P.cuda(), Wp.cuda()).cpu(), got)
+
+
+@pytest.mark.parametrize("M,N,K", [(200, 256, 512), (300, 512, 2048), (4224, 1024, 512), (4096, 1024, 2048)])
+@pytest.mark.parametrize("kind", ["cancel", "negative", "scale_up", "scale_down", "scale_mixed", "signed_zeros", "subnormal"])
+def test_gemm_operand_values(small, kind, M, N, K):
+    """The plain and the pipelined large-M kernel on operands that are not randn (tests/value_regimes.py: cancelling pairs of 1e4,
+    all-negative, 2^+-60 scales, signed zeros, bf16 subnormals, which MFMA does not flush), against the fp64 product of the bf16
+    values at the derived bound of any fp32-accumulated dot product: K 2^-24 sum |a_k| |w_k| per element."""
+    from value_regimes import gemm_operands, gemm_reference_and_bound
+    A, W = gemm_operands(kind, M, N, K)
+    ref, bound = gemm_reference_and_bound(A, W)
+    got = small.test_gemm(A.cuda(), W.cuda()).cpu()
+    assert bool(torch.isfinite(got).all())
+    excess = ((got.double() - ref).abs() / bound)
+    print(kind, M, N, K, "max error / bound", float(excess.max()))
+    assert float(excess.max()) <= 1.0
+    if kind == "subnormal":
+        assert float(ref.abs().max()) > 0 and float((got.double() - ref).abs().max()) < 1e-3 * float(ref.abs().max())      # not flushed to 0
 
 
 # ----------------------------------------------------------------------------- encoder

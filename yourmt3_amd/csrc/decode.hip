@@ -1017,8 +1017,10 @@ __global__ __launch_bounds__(256) void argmax_embed_kernel(const float* __restri
     const long long out0 = pRowPos ? pRowOut[r] : 0;
 
     STAMP_IN(a);
+    // A row in which no logit compares greater than -3.4e38 (all NaN, all -inf) emits the lowest index, as a tie does: every
+    // thread starts from index 0, and NaN logits take no part anywhere (include/ymt3.h, non-finite values).
     float bv = -3.4e38f;
-    int bi = 0x7fffffff;
+    int bi = 0;
     for (int i = tid; i < V; i += 256) {
         const float v = row[i];
         if (v > bv) { bv = v; bi = i; }       // ascending i: the first maximum is kept
@@ -1035,7 +1037,10 @@ __global__ __launch_bounds__(256) void argmax_embed_kernel(const float* __restri
         bi = 0x7fffffff;
         for (int i = tid; i < V; i += 256) {
             const float v = row[i];
-            if (((mrow[i >> 5] >> (i & 31)) & 1u) && v > bv) { bv = v; bi = i; }     // disallowed tokens take no part
+            if ((mrow[i >> 5] >> (i & 31)) & 1u) {                                   // disallowed tokens take no part
+                if (v > bv) { bv = v; bi = i; }
+                else bi = min(bi, i);          // (ascending i: only the start value moves) no comparable logit: the lowest allowed index
+            }
         }
     }
     // wave-wide (max value, lowest index): the selection is commutative and associative, so any reduction order gives the same pair.
@@ -1068,6 +1073,7 @@ __global__ __launch_bounds__(256) void argmax_embed_kernel(const float* __restri
 #pragma unroll
         for (int w = 1; w < 4; ++w)
             if (sv[w] > bv || (sv[w] == bv && si[w] < bi)) { bv = sv[w]; bi = si[w]; }
+        bi = min(bi, V - 1);               // (only a state that allows nothing leaves the start value) no index reaches memory unclamped
         int feed = a.pad_id;
         if (!was_finished && pos0 < n_prompt) {           // a prompt position: feed the prompt id, emit nothing
             pRowPos[r] = pos0 + 1;
@@ -1091,7 +1097,7 @@ __global__ __launch_bounds__(256) void argmax_embed_kernel(const float* __restri
 #pragma unroll
         for (int w = 1; w < 4; ++w)
             if (sv[w] > bv || (sv[w] == bv && si[w] < bi)) { bv = sv[w]; bi = si[w]; }
-        int tok = bi;
+        int tok = min(bi, V - 1);
         if (a.eos_id >= 0) {
             if (was_finished) tok = a.pad_id;
             else if (tok == a.eos_id) pFinished[r] = 1;

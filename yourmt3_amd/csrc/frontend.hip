@@ -137,7 +137,8 @@ __global__ __launch_bounds__((1 << (2 * S)) / 4) void logmel_kernel(
             float acc = 0.f;
             for (int i = tid & 1; i < ln; i += 2) acc += smw[off + i] * pw[st + i];
             acc += __shfl_xor(acc, 1, 64);
-            if ((tid & 1) == 0) dst[m] = logf(fmaxf(acc, log_floor));
+            // (a select, not fmaxf: a NaN power stays NaN, as the oracle's clamp keeps it, instead of reading as the floor)
+            if ((tid & 1) == 0) dst[m] = logf(acc < log_floor ? log_floor : acc);
         }
         __syncthreads();                                              // buffers are rewritten by the next frame
     }
