@@ -16,6 +16,8 @@
  *   generate(output_scores=True) + compute_transition_scores(normalize_logits=True)
  *                                        ->  ymt3_transcribe_segments_scored() / ymt3_decode_scored()
  *   generate(prefix_allowed_tokens_fn=...)  ->  ymt3_transcribe_segments_constrained() / ymt3_decode_constrained()
+ *   generate(num_beams=W, num_return_sequences=N, length_penalty=alpha, early_stopping=True)
+ *                                        ->  ymt3_transcribe_segments_beam() / ymt3_decode_beam()
  *
  * Conventions
  *   - every pointer named *_dev is DEVICE memory on the handle's GPU, owned by the caller;
@@ -202,6 +204,53 @@ int ymt3_transcribe_segments_constrained(ymt3_handle h, const float* audio_dev, 
 int ymt3_transcribe_stream_constrained(ymt3_handle h, const float* audio_dev, int n_segments, int n_steps, const int32_t* prompt_dev,
                                        int n_prompt, int32_t* tokens_dev, float* scores_dev, int slots, int interval,
                                        ymt3_constraint constraint, const int32_t* start_state_dev, void* stream);
+
+/* Beam search (HF `generate(num_beams=W, num_return_sequences=N, length_penalty=alpha, early_stopping=True, do_sample=False)`,
+ * i.e. GenerationMixin._beam_search of transformers 5.x with one EOS id).  Per group g = (segment, channel), with NEG = -1e9:
+ *   - state: W running beams with f32 cumulative log-probabilities run[w] (run[0] = 0, the others NEG: step 0 expands beam 0 only) and W
+ *     finished slots, empty at first.
+ *   - emitted step j (len = j + 1 tokens after it): lp[w][v] = log_softmax(logits of running beam w)[v] -- under a constraint of the row
+ *     masked by the beam's automaton state, the quantity scores_dev holds in a greedy call -- and acc[w][v] = run[w] + lp[w][v] in f32.  The
+ *     2W largest acc over the W * V candidates are taken in descending order; EQUAL scores are ordered by the lower flat index w * V + v.
+ *     A candidate is `hit` if its token is eos_id or j + 1 == n_steps (the length limit finishes every candidate).  The next running
+ *     beams are the best W of the 2W after NEG has been added to the hit ones, in order (first among equals); each records its parent beam
+ *     and token, and its automaton state is next[state[parent]][token].  A candidate enters the finished slots only if it is hit AND among
+ *     the first W of the 2W AND the group was not done before the step; its score is acc / len^alpha.  Old slots (first) and entering
+ *     candidates (in candidate order) are merged and the best W kept, best first.  A group is DONE when its W slots are full: it changes
+ *     nothing any more and its rows idle on pad_id.  Step n_steps - 1 finishes every candidate, so a call that ran all its steps has W
+ *     full slots per group.
+ *   - result: the first N = num_return slots, best first.  tokens_dev (B, n_channels, N, n_steps): a hypothesis' tokens up to and including
+ *     its EOS, then pad_id (always PAD, as the greedy calls; HF fills with EOS when pad_token_id is 0).  seq_scores_dev (B, n_channels, N), may
+ *     be NULL: acc / len^alpha (HF sequences_scores).  token_scores_dev (B, n_channels, N, n_steps), may be NULL: lp of every token of the
+ *     returned hypothesis (HF compute_transition_scores with beam_indices), 0.0 at PAD; they sum to seq_score * len^alpha.
+ *   - eos_id < 0: nothing finishes before the length limit.  num_beams = 1 is greedy search through this path.
+ *   - prompts: prompt_dev is (B, n_channels, n_prompt); prompt positions feed all W rows of a group the same ids, emit nothing and do not
+ *     touch the beam state; len counts emitted tokens only.  start_state_dev is (B, n_channels): a group's W beams start in the same state.
+ *   - non-finite values: NaN logits are no candidates; a beam whose row holds a NaN (or no comparable logit) has NaN scores, and its
+ *     candidates rank at NEG.  The groups of a non-finite segment return ids in range and NaN scores; the other groups keep their bits.
+ *   - limits (YMT3_ERR_ARG naming the limit, the handle stays usable): 1 <= num_return <= num_beams <= 8; length_penalty finite and >= 0
+ *     (a negative one breaks the early-stopping argument that lets a done group freeze); B * n_channels * num_beams <= max_batch *
+ *     n_channels, the rows the handle's caches were created for; n_channels * num_beams <= 255; max_decode_len below 48 K.
+ *   - not supported: forced ids with beams, beams in ymt3_transcribe_stream* (continuous batching would have to retire groups),
+ *     early_stopping False / "never", sampling, diverse beam groups.
+ * Rows: beam w of group g decodes as row g * W + w.  K/V of a position stays in the cache slab of the row that computed it; the
+ * self-attention kernel follows a per-row ancestry table instead of the cache being reordered every step.  Beam calls run the separate
+ * decode launches (one chain, lock-step), whatever the row count.  Asynchronous like the other decode calls (ymt3_set_early_stop: stops
+ * once every group is done, synchronising once per interval; the result is the full-length one).  All beam scratch is allocated in
+ * ymt3_create; the kernels read every per-call pointer and parameter from device memory, so no captured graph depends on them. */
+typedef struct ymt3_beam_params { int32_t num_beams, num_return; float length_penalty; } ymt3_beam_params;
+int ymt3_decode_beam(ymt3_handle h, const void* enc_dev, int B, int n_steps, const int32_t* prompt_dev, int n_prompt,
+                     const ymt3_beam_params* params, int32_t* tokens_dev, float* seq_scores_dev, float* token_scores_dev,
+                     ymt3_constraint constraint, const int32_t* start_state_dev, void* stream);
+int ymt3_transcribe_segments_beam(ymt3_handle h, const float* audio_dev, int B, int n_steps, const int32_t* prompt_dev, int n_prompt,
+                                  const ymt3_beam_params* params, int32_t* tokens_dev, float* seq_scores_dev, float* token_scores_dev,
+                                  ymt3_constraint constraint, const int32_t* start_state_dev, void* stream);
+/* Debug hook, gated like ymt3_debug_moe_trace (YMT3_DEBUG_HOOKS=1): from now on every beam call records, per emitted step, the new running
+ * beams of every group: trace_dev[step][group][W][2] int32 = (parent beam, token), run_dev[step][group][W] f32 their cumulative
+ * log-probabilities (may be NULL), logits_dev[step][group][W][V] f32 the raw logits of the running beams the step selected from (may be NULL;
+ * not written for a done group).  Steps >= n_steps and groups >= n_groups are not recorded; W is the call's num_beams; trace_dev = NULL stops
+ * recording.  The search is discrete: with the trace a test feeds the device's choices to the CPU oracle and compares every step. */
+int ymt3_debug_beam_trace(ymt3_handle h, int32_t* trace_dev, float* run_dev, float* logits_dev, int n_steps, int n_groups);
 
 /* Opt-in early stop (first step): with eos_id >= 0 and interval > 0, ymt3_decode_greedy /
  * ymt3_transcribe_segments check on the host every `interval` steps whether every row has emitted EOS and stop

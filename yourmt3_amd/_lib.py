@@ -21,9 +21,15 @@ SYMBOLS = [
     "ymt3_decode_scored", "ymt3_transcribe_segments_scored", "ymt3_transcribe_stream_scored",
     "ymt3_constraint_create", "ymt3_constraint_destroy", "ymt3_decode_constrained", "ymt3_transcribe_segments_constrained",
     "ymt3_transcribe_stream_constrained",
+    "ymt3_decode_beam", "ymt3_transcribe_segments_beam", "ymt3_debug_beam_trace",
 ]
 
 _lib = None
+
+
+class BeamParams(ctypes.Structure):
+    """ymt3_beam_params of include/ymt3.h."""
+    _fields_ = [("num_beams", ctypes.c_int32), ("num_return", ctypes.c_int32), ("length_penalty", ctypes.c_float)]
 
 
 class YMT3Error(RuntimeError):
@@ -108,6 +114,13 @@ def load() -> ctypes.CDLL:
     lib.ymt3_last_decode_chains.restype = i32
     lib.ymt3_debug_moe_trace.argtypes = [vp, vp, i32, i32]
     lib.ymt3_debug_moe_trace.restype = i32
+    bp = ctypes.POINTER(BeamParams)
+    lib.ymt3_decode_beam.argtypes = [vp, vp, i32, i32, vp, i32, bp, vp, vp, vp, vp, vp, vp]
+    lib.ymt3_decode_beam.restype = i32
+    lib.ymt3_transcribe_segments_beam.argtypes = [vp, vp, i32, i32, vp, i32, bp, vp, vp, vp, vp, vp, vp]
+    lib.ymt3_transcribe_segments_beam.restype = i32
+    lib.ymt3_debug_beam_trace.argtypes = [vp, vp, vp, vp, i32, i32]
+    lib.ymt3_debug_beam_trace.restype = i32
     for n in ("ymt3_logmel", "ymt3_encode", "ymt3_decode_greedy", "ymt3_transcribe_segments", "ymt3_test_gemm"):
         getattr(lib, n).restype = i32
     if lib.ymt3_abi_version() != 3:

@@ -571,10 +571,17 @@ __device__ __forceinline__ void pair_leave(const PairSync& ps, int r, unsigned b
     }
 }
 
-template <bool SELF, bool FUSEQ, int NW, bool OP, int PAIR>
+// BEAM (beam search, self-attention without the folded O-projection only): the history of the beam living in row r is spread over the
+// slabs of its group's W rows -- K/V of a position stays where the row that computed it appended it -- and ba.anc says, one byte per
+// position, which row of the group holds it.  The row's table is staged in LDS at entry (one 16-byte load per lane, requested together
+// with q; n_keys bytes against the 256 * n_keys of K/V the workgroup streams), so a key's slab base costs an LDS read in front of its
+// two loads and never a global round trip in front of a K/V block.  Each 8-lane key group already addresses one key per load, so
+// only the address changes, not the shape of the stream.  Every table entry is clamped into the group where it is used.
+template <bool SELF, bool FUSEQ, int NW, bool OP, int PAIR, bool BEAM = false>
 __device__ __forceinline__ void attn_body(const bf16_t* __restrict__ pK, const bf16_t* __restrict__ pV, const bf16_t* __restrict__ pQ,
                                           const float* __restrict__ pF, const void* __restrict__ p4, const void* __restrict__ p5,
-                                          unsigned geom0, unsigned geom1, const DecAttnArgs& a, const PairSync& ps) {
+                                          unsigned geom0, unsigned geom1, const DecAttnArgs& a, const PairSync& ps, const BeamAttn& ba = BeamAttn{}) {
+    static_assert(!BEAM || (SELF && !FUSEQ && !OP && PAIR == 0), "the ancestry table addresses the self-attention cache of the separate launches");
     // Leading scalar arguments (14 dwords; kernarg preload, see dec_gemm_kernel) -- everything the first loads' addresses depend
     // on: K / V slab bases, pQ = q (wq when FUSEQ), pF = the position-bias table (SELF) or the residual stream (FUSEQ),
     // p4 / p5 = loop state and per-row positions (SELF) or norm gain and sum(h^2) partials / O-projection partials (FUSEQ),
@@ -599,8 +606,10 @@ __device__ __forceinline__ void attn_body(const bf16_t* __restrict__ pK, const b
     const int sub = lane & 7, kg = lane >> 3;
     const int r = row0 + blockIdx.x / H, h = blockIdx.x % H;      // (a row's eight heads on one XCD instead -- block -> row 8 * (b / 64) + b % 8 -- measured 1 % slower)
     const int n_keys = SELF ? (pRowPos ? pRowPos[r] : pShared->step) + 1 : n_keys_const;
-    const int kv_row = r / rows_per_kv;
+    const int kv_row = BEAM ? r - r % ba.W : r / rows_per_kv;               // BEAM: the group's first row; a key adds its holder's row pitch
     const size_t slab = ((size_t)kv_row * H + h) * slab_keys * DKV;
+    const size_t row_pitch = (size_t)H * slab_keys * DKV;
+    const unsigned char* anc_s = reinterpret_cast<const unsigned char*>(wo_lds);       // BEAM: [n_keys] staged table (the dynamic LDS block)
     const bf16_t* kb = pK + slab + sub * 8;
     const bf16_t* vb = pV + slab + sub * 8;
     const float* bias = SELF ? pF + (size_t)h * slab_keys : nullptr;      // the bias table's row pitch is the cache length (launcher checks)
@@ -645,6 +654,13 @@ __device__ __forceinline__ void attn_body(const bf16_t* __restrict__ pK, const b
     } else {
         qp = *reinterpret_cast<const u32x4*>(pQ + ((size_t)r * H + h) * DKV + sub * 8);
     }
+    if constexpr (BEAM) {
+        // the buffer of the position being decoded (n_keys - 1); rows are anc_pitch (a multiple of 16, > max_decode_len) bytes apart
+        const uint8_t* tab = ba.anc + ((size_t)((n_keys - 1) & 1) * ba.anc_rows + r) * ba.anc_pitch;
+        for (int i = tid * 16; i < n_keys; i += 64 * NW * 16)
+            *reinterpret_cast<u32x4*>(wo_lds + i) = *reinterpret_cast<const u32x4*>(tab + i);
+        __syncthreads();
+    }
 
     float m = -1.0e30f, l = 0.f, acc[8];
 #pragma unroll
@@ -663,12 +679,24 @@ __device__ __forceinline__ void attn_body(const bf16_t* __restrict__ pK, const b
     auto load_block = [&](u32x4 (&ku)[U], u32x4 (&vu)[U], bool (&ok)[U], float (&bv)[U], int kw, auto full_tag) {
         constexpr bool FULL = decltype(full_tag)::value;         // FULL: all U blocks valid, no masks
         const int k0 = kw + kg;
+        int holder[BEAM ? U : 1];                                // BEAM: the block's table entries, read together in front of its loads
+        if constexpr (BEAM) {
+#pragma unroll
+            for (int u = 0; u < U; ++u) {
+                const int key = k0 + 8 * NW * u;
+                holder[u] = anc_s[FULL || key < n_keys ? key : kw];
+            }
+        }
 #pragma unroll
         for (int u = 0; u < U; ++u) {
             const int key = k0 + 8 * NW * u;
             ok[u] = FULL || key < n_keys;
             const int kc = ok[u] ? key : kw;
-            if constexpr (SELF) {
+            if constexpr (BEAM) {
+                const size_t at = (size_t)min(holder[u], ba.W - 1) * row_pitch + (size_t)kc * DKV;
+                ku[u] = __builtin_nontemporal_load(reinterpret_cast<const u32x4*>(kb + at));
+                vu[u] = __builtin_nontemporal_load(reinterpret_cast<const u32x4*>(vb + at));
+            } else if constexpr (SELF) {
                 ku[u] = __builtin_nontemporal_load(reinterpret_cast<const u32x4*>(kb + (size_t)kc * DKV));
                 vu[u] = __builtin_nontemporal_load(reinterpret_cast<const u32x4*>(vb + (size_t)kc * DKV));
             } else {
@@ -949,6 +977,14 @@ __global__ __launch_bounds__(64 * NW, 4) void dec_attn_kernel(const bf16_t* __re
                                                               const float* __restrict__ pF, const void* __restrict__ p4, const void* __restrict__ p5,
                                                               unsigned geom0, unsigned geom1, DecAttnArgs a) {   // 4 waves / SIMD -> <= 128 VGPRs
     attn_body<SELF, FUSEQ, NW, OP, 0>(pK, pV, pQ, pF, p4, p5, geom0, geom1, a, PairSync{});
+}
+
+// beam search: self-attention through the ancestry table (8 waves, or 2 per (row, head) for many rows)
+template <int NW>
+__global__ __launch_bounds__(64 * NW, 4) void dec_attn_beam_kernel(const bf16_t* __restrict__ pK, const bf16_t* __restrict__ pV, const bf16_t* __restrict__ pQ,
+                                                                   const float* __restrict__ pF, const void* __restrict__ p4, const void* __restrict__ p5,
+                                                                   unsigned geom0, unsigned geom1, DecAttnArgs a, BeamAttn ba) {
+    attn_body<true, false, NW, false, 0, true>(pK, pV, pQ, pF, p4, p5, geom0, geom1, a, PairSync{}, ba);
 }
 
 // A layer's self-attention and cross-attention as ONE launch (up to 64 rows: 512 workgroups, two per CU, all resident).  Workgroup
@@ -1367,6 +1403,21 @@ int launch_dec_attention(bool self_attn, const DecAttnArgs& a, hipStream_t strea
         else ATTN(false, false, 8, false, 512, 0, a.q, nullptr, nullptr, nullptr);
     }
 #undef ATTN
+    return 0;
+}
+
+// beam search: lock-step rows only (no per-row positions), no folded O-projection; the staged table is the kernel's dynamic LDS block
+int launch_dec_attention_beam(const DecAttnArgs& a, const BeamAttn& ba, hipStream_t stream) {
+    if (a.R <= 0) return 0;
+    if (!ba.anc || ba.W < 1 || ba.W > BEAM_MAX || a.R % ba.W || a.row0 % ba.W || ba.anc_pitch % 16 || ba.anc_pitch <= a.slab_keys || ba.anc_pitch > 48 * 1024 ||
+        a.row0 + a.R > ba.anc_rows || a.row_pos || a.wo || a.ipart || a.wq || a.chain_sync || a.rows_per_kv != 1)
+        return -1;
+    if (a.row0 < 0 || a.row0 > 0xffff || a.H < 1 || a.H > 0xff || a.slab_keys < 1 || a.slab_keys > 0xfffff || a.bias_stride != a.slab_keys) return -1;
+    const bool many = a.force_many || a.R * a.H > 2048;
+    const unsigned g0 = (unsigned)a.row0 | 1u << 16 | (unsigned)a.H << 24, g1 = (unsigned)a.slab_keys;
+    const int grid = a.R * a.H;
+    if (many) dec_attn_beam_kernel<2><<<grid, 128, ba.anc_pitch, stream>>>(a.k, a.v, a.q, a.bias, a.shared, a.row_pos, g0, g1, a, ba);
+    else dec_attn_beam_kernel<8><<<grid, 512, ba.anc_pitch, stream>>>(a.k, a.v, a.q, a.bias, a.shared, a.row_pos, g0, g1, a, ba);
     return 0;
 }
 

@@ -295,6 +295,54 @@ int launch_decode_init(const ArgmaxArgs& a, int n_chains, int n_steps, int step0
                        float* logits_out, const int32_t* prompt, int n_prompt, float* scores_out, const ConstraintView& cv,
                        hipStream_t stream);
 
+// ---------------------------------------------------------------- beam search (beam.hip; self-attention: decode.hip)
+// Rows of a beam call: r = (segment * n_channels + channel) * W + beam; a group = the W rows of one (segment, channel).  K/V of a position
+// stays in the slab of the physical row that computed it; anc[buf][r][p] (one byte: the row's index within its group) says which row of the
+// group holds position p of the history of the beam now living in row r.  Two buffers alternate by the parity of the position being decoded
+// (the selection kernel of step t reads buffer t & 1 and writes buffer (t + 1) & 1, entries 0 .. t + 1).
+constexpr int BEAM_MAX = 8;
+struct BeamAttn {               // what the ancestry-addressed self-attention needs on top of DecAttnArgs
+    const uint8_t* anc;         // [2][anc_rows][anc_pitch]
+    int anc_rows, anc_pitch, W;
+};
+int launch_dec_attention_beam(const DecAttnArgs& a, const BeamAttn& ba, hipStream_t stream);
+
+struct BeamShared {             // device-resident per-call parameters of the beam kernels: no captured graph depends on a call's arguments
+    float alpha;                // length penalty
+    int32_t* tokens_out;        // [G][N][n_steps]
+    float* seq_out;             // [G][N] or null (N = num_return: the grid of the result kernel)
+    float* tok_out;             // [G][N][n_steps] or null
+    // debug hook ymt3_debug_beam_trace (null otherwise)
+    int32_t* trace;             // [trace_steps][trace_groups][W][2] = (parent, token) of every new running beam
+    float* trace_run;           // [trace_steps][trace_groups][W] its cumulative log-probability
+    float* trace_logits;        // [trace_steps][trace_groups][W][V] raw logits of the running beams the step selected from, or null
+    int trace_steps, trace_groups;
+};
+struct BeamArgs {
+    const float* logits;        // [R][V]
+    float* h;                   // [R][d] residual stream to refill with the fed tokens' embeddings
+    const bf16_t* embed; const bf16_t* chan_embed;
+    DecodeShared* shared; BeamShared* beam;
+    int* finished;              // [R]: 1 for every row of a done group
+    float* ssq; int ssq_stride;
+    int R, V, d, n_channels, eos_id, pad_id, W;
+    int* row_state;             // [R] automaton state of every running beam
+    uint8_t* anc; int anc_rows, anc_pitch;
+    int32_t* fed_tok; float* fed_lp; int fed_pitch;    // [R][fed_pitch]: the token fed into physical row r at position p, and its log-probability
+    float* run;                 // [R] cumulative log-probability of every running beam
+    float* fin_score; int* fin_len; int* fin_store; int32_t* fin_tok; float* fin_lp;   // [R] = [G][W] finished slots, best first
+    int* n_fin;                 // [G] filled slots
+    uint8_t* slot_anc;          // [R][anc_pitch]: ancestry snapshots of the finished hypotheses, indexed by fin_store
+    unsigned long long* stamp;
+};
+int launch_beam_select(const BeamArgs& a, hipStream_t stream);
+// all rows: h[r] = embed[pad] (+ channel), run = 0 / -1e9, slots empty, anc[step0 & 1][r][0] = own index, automaton start state of the
+// row's group; loop state and beam parameters reset
+int launch_beam_init(const BeamArgs& a, int n_steps, const int32_t* prompt, int n_prompt, const ConstraintView& cv, const BeamShared& params,
+                     hipStream_t stream);
+// tokens_out / seq_out / tok_out from the finished slots
+int launch_beam_finalize(const BeamArgs& a, int N, hipStream_t stream);
+
 // ---------------------------------------------------------------- MoE decoder FFN (moe.hip)
 struct MoeArgs {
     float* h;                   // [R][d_model] fp32 residual stream (read by router, updated by combine)

@@ -144,6 +144,12 @@ struct ymt3_ctx {
     int prof_step0 = 0;                     // ymt3_debug_decode_start: the next decode call begins at this position (one shot)
     int32_t* moe_trace = nullptr;           // ymt3_debug_moe_trace: caller's [steps][layers][rows][2] buffer the MoE router records its choices in
     int moe_trace_steps = 0, moe_trace_rows = 0;
+    // beam search (include/ymt3.h): all scratch is sized at create by the handle's rows and max_decode_len.  beam_W > 0 only while a beam
+    // call builds its steps: launch_step then addresses the self-attention cache through the ancestry table and ends with the selection kernel
+    int beam_W = 0;
+    BeamArgs beam{};                        // the scratch pointers (anc, fed_tok, run, finished slots, ...)
+    BeamShared* beam_shared = nullptr;      // device: the call's parameters and the debug trace pointers
+    BeamShared beam_trace{};                // ymt3_debug_beam_trace: host copy of the trace fields (carried into every call's parameters)
     std::vector<hipEvent_t> prof_ev;        // pairs
     std::vector<int> prof_cls;
     // measurement (YMT3_STAMP=1): per-workgroup wall-clock stamps of the decode-step kernels, slot = launch order in the step
@@ -421,6 +427,23 @@ static int create_impl(ymt3_ctx* c, const ymt3_config* cfg, const void* blob, si
             dev_alloc(c, (void**)&m.hidden, P * k.d_ff * 2) || dev_alloc(c, (void**)&m.y, P * d * 4))
             return YMT3_ERR_HIP;
         m.E = k.n_experts; m.top_k = k.moe_top_k; m.d_model = d; m.d_ff = k.d_ff; m.eps = k.ln_eps;
+    }
+    {   // beam search scratch: ancestry tables (two buffers) and snapshots, one byte per (row, position); fed tokens and their log-probabilities
+        BeamArgs& b = c->beam;
+        b.anc_rows = (int)R;
+        b.anc_pitch = (k.max_decode_len + 1 + 15) / 16 * 16;
+        b.fed_pitch = k.max_decode_len + 1;
+        if (dev_alloc(c, (void**)&b.anc, (size_t)2 * R * b.anc_pitch) || dev_alloc(c, (void**)&b.slot_anc, R * b.anc_pitch) ||
+            dev_alloc(c, (void**)&b.fed_tok, R * b.fed_pitch * 4) || dev_alloc(c, (void**)&b.fed_lp, R * b.fed_pitch * 4) ||
+            dev_alloc(c, (void**)&b.run, R * 4) || dev_alloc(c, (void**)&b.fin_score, R * 4) || dev_alloc(c, (void**)&b.fin_len, R * 4) ||
+            dev_alloc(c, (void**)&b.fin_store, R * 4) || dev_alloc(c, (void**)&b.fin_tok, R * 4) || dev_alloc(c, (void**)&b.fin_lp, R * 4) ||
+            dev_alloc(c, (void**)&b.n_fin, R * 4) || dev_alloc(c, (void**)&c->beam_shared, sizeof(BeamShared)))
+            return YMT3_ERR_HIP;
+        HIP_TRY(hipMemset(b.anc, 0, (size_t)2 * R * b.anc_pitch));
+        HIP_TRY(hipMemset(b.slot_anc, 0, R * b.anc_pitch));
+        HIP_TRY(hipMemset(b.fed_tok, 0, R * b.fed_pitch * 4));
+        HIP_TRY(hipMemset(b.fed_lp, 0, R * b.fed_pitch * 4));
+        HIP_TRY(hipMemset(c->beam_shared, 0, sizeof(BeamShared)));
     }
     if (dev_alloc(c, (void**)&c->shared, 8 * sizeof(DecodeShared))) return YMT3_ERR_HIP;
     HIP_TRY(hipMemset(c->shared, 0, 8 * sizeof(DecodeShared)));
@@ -742,6 +765,19 @@ extern "C" int ymt3_encode(ymt3_handle h, const float* mel_dev, int B, void* enc
     return encode_impl(h, mel_dev, B, static_cast<bf16_t*>(enc_dev), (hipStream_t)stream);
 }
 
+// the beam kernels' arguments for R rows of W beams: the handle's scratch, the step's buffers, the embedding tables
+static int beam_args(ymt3_handle h, int R, int W, DecodeShared* shared, BeamArgs* out) {
+    const ymt3_config& k = h->cfg;
+    const int d = k.d_model;
+    BeamArgs b = h->beam;
+    b.logits = h->logits; b.h = h->h_dec; b.shared = shared; b.beam = h->beam_shared; b.finished = h->finished; b.ssq = h->ssq; b.ssq_stride = h->maxR;
+    b.R = R; b.V = k.vocab; b.d = d; b.n_channels = k.n_channels; b.eos_id = k.eos_id; b.pad_id = k.pad_id; b.W = W; b.row_state = h->row_state;
+    GET(h, "dec.embed", 1u, const_cast<bf16_t**>(&b.embed), (size_t)k.vocab * d);
+    if (k.n_channels > 1) GET(h, "dec.chan_embed", 1u, const_cast<bf16_t**>(&b.chan_embed), (size_t)k.n_channels * d);
+    *out = b;
+    return 0;
+}
+
 // one decoder step of rows [row0, row0 + R) = 8 kernels per layer + lm_head + argmax, all reading the
 // position from the chain's DecodeShared
 static int launch_step(ymt3_handle h, int B, int row0, int R, DecodeShared* shared, hipStream_t s, bool solo = true) {
@@ -791,8 +827,10 @@ static int launch_step(ymt3_handle h, int B, int row0, int R, DecodeShared* shar
     float* hcur = h->h_dec;
     const float* pend = nullptr;
     // all channels of a segment share its cross-attention K/V: one workgroup per (segment, head) serves them together (mc_cross_attn.hip)
-    const bool mc = h->fuse_q && k.n_channels >= 2 && k.n_channels <= 16 && (h->T == 128 || h->T == 256 || h->T == 512) &&
-                    row0 % k.n_channels == 0 && R % k.n_channels == 0;
+    // (a beam call: the W beams of a group share their segment's K/V exactly as channels do -- rows_kv = n_channels * W rows per segment)
+    const int bW = h->beam_W, rows_kv = k.n_channels * (bW > 0 ? bW : 1);
+    const bool mc = h->fuse_q && rows_kv >= 2 && rows_kv <= 16 && (h->T == 128 || h->T == 256 || h->T == 512) &&
+                    row0 % rows_kv == 0 && R % rows_kv == 0;
     // fold_o: the self-attention kernel leaves per-head O-projection partials; the fused cross-attention and the cross
     // O-projection's residual read sum them (one launch less per layer, same bits).  Needs the 8-wave attention kernels
     // and the per-row fused cross-attention
@@ -801,7 +839,8 @@ static int launch_step(ymt3_handle h, int B, int row0, int R, DecodeShared* shar
     const bool merged_rows = solo && k.n_channels == 1 && row0 == 0 && R <= h->merged_max_rows && h->attn_pair && h->pair_rows;     // (the pair kernel keeps the fold worthwhile beyond 96 rows)
     // (not for one of several concurrent chains: its 64 KB weight pulls per (row, head) share the chip badly -- two 96-row halves with it are no
     // faster than one 192-row chain, without it 6 % faster: profiles/r03_chains_many_rows.txt)
-    const bool fold = h->fold_o && h->fuse_q && !mc && !h->force_2wave && H == 8 && d == 512 && ((R <= 96 && solo) || merged_rows);
+    // (a beam call runs the separate launches: its self-attention follows the ancestry table and has no folded form)
+    const bool fold = bW == 0 && h->fold_o && h->fuse_q && !mc && !h->force_2wave && H == 8 && d == 512 && ((R <= 96 && solo) || merged_rows);
     // The merged kernels' regime: one channel, up to 64 rows, and this step the only decode stream of the handle (`solo`: with YMT3_CHAINS > 1
     // other row ranges replay on other streams, and the merged kernels need every CU for their own workgroups while they run).
     const bool merged_regime = fold && solo && k.n_channels == 1 && R <= h->merged_max_rows && row0 == 0;
@@ -870,7 +909,11 @@ static int launch_step(ymt3_handle h, int B, int row0, int R, DecodeShared* shar
         if (fold) { t.wo = W.wo; t.opart = h->opart; }
         const bool pair = pair_ok && fold;
         DecAttnArgs ts = t;                          // the self-attention half
-        if (!pair) {
+        if (bW > 0) {
+            const BeamAttn ba{h->beam.anc, h->beam.anc_rows, h->beam.anc_pitch, bW};
+            t.stamp = next_stamp(h, PC_SELF_ATTN, R * H);
+            PLAUNCH(PC_SELF_ATTN, launch_dec_attention_beam(t, ba, s));
+        } else if (!pair) {
             t.stamp = next_stamp(h, PC_SELF_ATTN, R * H);
             PLAUNCH(PC_SELF_ATTN, launch_dec_attention(true, t, s));
         }
@@ -883,14 +926,14 @@ static int launch_step(ymt3_handle h, int B, int row0, int R, DecodeShared* shar
         // cross-attention block: the query projection is fused into the attention kernel (YMT3_NO_FUSEQ=1 keeps
         // the separate skinny GEMM, for A/B measurements)
         t.k = h->ckv + (size_t)(2 * l) * slab; t.v = h->ckv + (size_t)(2 * l + 1) * slab; t.bias = nullptr;
-        t.n_keys_const = h->T; t.slab_keys = h->T; t.rows_per_kv = k.n_channels;
+        t.n_keys_const = h->T; t.slab_keys = h->T; t.rows_per_kv = rows_kv;
         if (fold) t.ipart = h->opart;
         if (mc) {
             // all channels of a segment share its K/V: one workgroup per (segment, head) serves them together
             McCrossArgs mcx{};
             mcx.x_f32 = hcur; mcx.gain = W.ln2; mcx.ssq = h->ssq; mcx.ssq_stride = h->maxR; mcx.eps = k.ln_eps;
-            mcx.wq = W.wq_c; mcx.k = t.k + (size_t)(row0 / k.n_channels) * H * h->T * 64; mcx.v = t.v + (size_t)(row0 / k.n_channels) * H * h->T * 64;
-            mcx.out = h->dattn; mcx.row0 = row0; mcx.n_seg = R / k.n_channels; mcx.n_channels = k.n_channels; mcx.H = H; mcx.T = h->T;
+            mcx.wq = W.wq_c; mcx.k = t.k + (size_t)(row0 / rows_kv) * H * h->T * 64; mcx.v = t.v + (size_t)(row0 / rows_kv) * H * h->T * 64;
+            mcx.out = h->dattn; mcx.row0 = row0; mcx.n_seg = R / rows_kv; mcx.n_channels = rows_kv; mcx.H = H; mcx.T = h->T;
             PLAUNCH(PC_CROSS_ATTN, launch_mc_cross_attention(mcx, s));
         } else if (h->fuse_q) {
             t.wq = W.wq_c; t.x_f32 = hcur; t.gain = W.ln2; t.ssq = h->ssq; t.ssq_stride = h->maxR; t.eps = k.ln_eps;
@@ -985,6 +1028,14 @@ static int launch_step(ymt3_handle h, int B, int row0, int R, DecodeShared* shar
     if (!lm_done) {
         a.stamp = next_stamp(h, PC_LM_HEAD, a.N / 16 * mtiles);
         PLAUNCH(PC_LM_HEAD, launch_dec_gemm(DG_NORM_LOGITS, a, s));
+    }
+    if (bW > 0) {
+        BeamArgs b{};
+        int rcb = beam_args(h, R, bW, shared, &b);
+        if (rcb) return rcb;
+        b.stamp = next_stamp(h, PC_ARGMAX, R / bW);
+        PLAUNCH(PC_ARGMAX, launch_beam_select(b, s));
+        return YMT3_OK;
     }
     ArgmaxArgs g{};
     g.logits = h->logits; g.h = h->h_dec; g.shared = shared; g.finished = h->finished; g.ssq = h->ssq; g.ssq_stride = h->maxR; g.row0 = row0;
@@ -1283,6 +1334,147 @@ extern "C" int ymt3_transcribe_segments_prompted(ymt3_handle h, const float* aud
 extern "C" int ymt3_transcribe_segments(ymt3_handle h, const float* audio_dev, int B, int n_steps, int32_t* tokens_dev,
                                         void* stream) {
     return ymt3_transcribe_segments_prompted(h, audio_dev, B, n_steps, nullptr, 0, tokens_dev, stream);
+}
+
+// ---------------------------------------------------------------- beam search (include/ymt3.h)
+static int beam_check(ymt3_handle h, int B, int n_steps, const int32_t* prompt, int n_prompt, const ymt3_beam_params* p, const int32_t* tokens) {
+    const ymt3_config& k = h->cfg;
+    if (!p) FAIL(YMT3_ERR_ARG, "null beam parameters");
+    if (p->num_beams < 1 || p->num_beams > BEAM_MAX) FAIL(YMT3_ERR_ARG, "num_beams=%d outside [1, %d]", p->num_beams, BEAM_MAX);
+    if (p->num_return < 1 || p->num_return > p->num_beams) FAIL(YMT3_ERR_ARG, "num_return=%d outside [1, num_beams=%d]", p->num_return, p->num_beams);
+    if (!(p->length_penalty >= 0.f) || p->length_penalty > 3.0e38f) FAIL(YMT3_ERR_ARG, "length_penalty=%g must be finite and >= 0", (double)p->length_penalty);
+    if ((long long)B * k.n_channels * p->num_beams > h->maxR)
+        FAIL(YMT3_ERR_ARG, "B * n_channels * num_beams = %lld rows exceed the max_batch * n_channels = %d rows the handle was created for",
+             (long long)B * k.n_channels * p->num_beams, h->maxR);
+    if (k.n_channels * p->num_beams > 255) FAIL(YMT3_ERR_ARG, "n_channels * num_beams = %d exceeds 255 rows per segment", k.n_channels * p->num_beams);
+    if (h->beam.anc_pitch > 48 * 1024) FAIL(YMT3_ERR_ARG, "beam search needs max_decode_len < %d (the staged ancestry table)", 48 * 1024 - 16);
+    if (n_prompt < 0 || (n_prompt > 0 && !prompt)) FAIL(YMT3_ERR_ARG, "n_prompt=%d with prompt %s", n_prompt, prompt ? "set" : "null");
+    if (n_steps <= 0 || n_prompt + n_steps > k.max_decode_len)
+        FAIL(YMT3_ERR_ARG, "n_steps=%d outside [1, max_decode_len - n_prompt=%d]", n_steps, k.max_decode_len - n_prompt);
+    if (h->prof_step0) FAIL(YMT3_ERR_ARG, "ymt3_debug_decode_start is pending: it does not combine with beams");
+    if (B > 0 && !tokens) FAIL(YMT3_ERR_ARG, "null buffer");
+    return 0;
+}
+
+// One chain, lock-step, the separate launches (launch_step with beam_W set); the step graphs are cached under a key of their own (B, W).
+static int decode_beam_impl(ymt3_handle h, const bf16_t* enc, int B, int n_steps, const int32_t* prompt, int n_prompt, const ymt3_beam_params* p,
+                            int32_t* tokens, float* seq_scores, float* token_scores, const ConstraintView& cv, hipStream_t s) {
+    const ymt3_config& k = h->cfg;
+    const int W = p->num_beams, d = k.d_model, R = B * k.n_channels * W, n_total = n_prompt + n_steps;
+    GemmArgs g{enc, h->wkv_all, h->ckv, nullptr, B * h->T, k.n_dec_layers * 2 * h->inner, d, d, d, 0, h->T, k.n_heads, B};
+    LAUNCH(launch_gemm(EPI_KV_HEADMAJOR, g, s));
+    BeamArgs b{};
+    int rcb = beam_args(h, R, W, h->shared, &b);
+    if (rcb) return rcb;
+    BeamShared params = h->beam_trace;
+    params.alpha = p->length_penalty; params.tokens_out = tokens; params.seq_out = seq_scores; params.tok_out = token_scores;
+    h->last_chains = 1;
+    LAUNCH(launch_beam_init(b, n_steps, prompt, n_prompt, cv, params, s));
+    h->last_steps = n_total;
+    struct BeamGuard { ymt3_ctx* c; ~BeamGuard() { c->beam_W = 0; } } guard{h};
+    h->beam_W = W;
+    auto graph_of = [&](int G, hipGraphExec_t* out) -> int {
+        StepGraph& sg = h->step_graphs[(((long)B * 16 + 14) * 16 + W) | (1L << 41) | ((long)G << 32)];      // 14: beam graphs of B segments, W beams
+        if (!sg.exec) {
+            HIP_TRY(hipStreamBeginCapture(h->cap_stream, hipStreamCaptureModeThreadLocal));
+            int rc = 0;
+            for (int i = 0; i < G && !rc; ++i) rc = launch_step(h, B, 0, R, h->shared, h->cap_stream);
+            hipError_t e = hipStreamEndCapture(h->cap_stream, &sg.graph);
+            if (rc) return rc;
+            if (e != hipSuccess) FAIL(YMT3_ERR_HIP, "hipStreamEndCapture: %s", hipGetErrorString(e));
+            HIP_TRY(hipGraphInstantiate(&sg.exec, sg.graph, nullptr, nullptr, 0));
+        }
+        *out = sg.exec;
+        return 0;
+    };
+    if (!h->use_graph) {
+        for (int t = 0; t < n_total; ++t) { int rc = launch_step(h, B, 0, R, h->shared, s); if (rc) return rc; }
+    } else if (h->early_stop_interval > 0) {
+        // opt-in (ymt3_set_early_stop): stop launching once every group is done; the finished slots are complete by then
+        hipGraphExec_t one;
+        int rc = graph_of(1, &one);
+        if (rc) return rc;
+        for (int i = 0; i < n_prompt; ++i) HIP_TRY(hipGraphLaunch(one, s));
+        int t = 0;
+        while (t < n_steps) {
+            const int chunk = std::min(h->early_stop_interval, n_steps - t);
+            for (int i = 0; i < chunk; ++i) HIP_TRY(hipGraphLaunch(one, s));
+            t += chunk;
+            if (t >= n_steps) break;
+            HIP_TRY(hipMemcpyAsync(h->host_flag, &h->shared->n_unfinished, sizeof(int), hipMemcpyDeviceToHost, s));
+            HIP_TRY(hipStreamSynchronize(s));
+            if (*h->host_flag == 0) break;
+        }
+        h->last_steps = n_prompt + t;
+    } else {
+        const int G = h->graph_steps;
+        int t = 0;
+        if (G > 1 && n_total >= G) {
+            hipGraphExec_t many;
+            int rc = graph_of(G, &many);
+            if (rc) return rc;
+            for (; t + G <= n_total; t += G) HIP_TRY(hipGraphLaunch(many, s));
+        }
+        if (t < n_total) {
+            hipGraphExec_t one;
+            int rc = graph_of(1, &one);
+            if (rc) return rc;
+            for (; t < n_total; ++t) HIP_TRY(hipGraphLaunch(one, s));
+        }
+    }
+    LAUNCH(launch_beam_finalize(b, p->num_return, s));
+    HIP_TRY(hipGetLastError());
+    return YMT3_OK;
+}
+
+extern "C" int ymt3_decode_beam(ymt3_handle h, const void* enc_dev, int B, int n_steps, const int32_t* prompt_dev, int n_prompt,
+                                const ymt3_beam_params* params, int32_t* tokens_dev, float* seq_scores_dev, float* token_scores_dev,
+                                ymt3_constraint constraint, const int32_t* start_state_dev, void* stream) {
+    int rc = check_call(h, B);
+    if (rc) return rc;
+    ConstraintView cv{};
+    rc = constraint_view(h, constraint, start_state_dev, &cv);
+    if (rc) return rc;
+    rc = beam_check(h, B, n_steps, prompt_dev, n_prompt, params, tokens_dev);
+    if (rc) return rc;
+    if (B == 0) return YMT3_OK;
+    if (!enc_dev) FAIL(YMT3_ERR_ARG, "null buffer");
+    return decode_beam_impl(h, static_cast<const bf16_t*>(enc_dev), B, n_steps, prompt_dev, n_prompt, params, tokens_dev, seq_scores_dev,
+                            token_scores_dev, cv, (hipStream_t)stream);
+}
+
+extern "C" int ymt3_transcribe_segments_beam(ymt3_handle h, const float* audio_dev, int B, int n_steps, const int32_t* prompt_dev, int n_prompt,
+                                             const ymt3_beam_params* params, int32_t* tokens_dev, float* seq_scores_dev,
+                                             float* token_scores_dev, ymt3_constraint constraint, const int32_t* start_state_dev, void* stream) {
+    int rc = check_call(h, B);
+    if (rc) return rc;
+    ConstraintView cv{};
+    rc = constraint_view(h, constraint, start_state_dev, &cv);
+    if (rc) return rc;
+    rc = beam_check(h, B, n_steps, prompt_dev, n_prompt, params, tokens_dev);
+    if (rc) return rc;
+    if (B == 0) return YMT3_OK;
+    if (!audio_dev) FAIL(YMT3_ERR_ARG, "null buffer");
+    hipStream_t s = (hipStream_t)stream;
+    LAUNCH(launch_logmel(h->fe, audio_dev, h->mel, B, s));
+    rc = encode_impl(h, h->mel, B, h->enc_out, s);
+    if (rc) return rc;
+    return decode_beam_impl(h, h->enc_out, B, n_steps, prompt_dev, n_prompt, params, tokens_dev, seq_scores_dev, token_scores_dev, cv, s);
+}
+
+extern "C" int ymt3_debug_beam_trace(ymt3_handle h, int32_t* trace_dev, float* run_dev, float* logits_dev, int n_steps, int n_groups) {
+    if (!h) FAIL(YMT3_ERR_ARG, "null handle");
+    if (!h->debug_hooks) FAIL(YMT3_ERR_UNSUPPORTED, "debug hooks are accepted only by a handle created with YMT3_DEBUG_HOOKS=1 in the environment");
+    if (trace_dev && (n_steps <= 0 || n_groups <= 0)) FAIL(YMT3_ERR_ARG, "n_steps=%d n_groups=%d", n_steps, n_groups);
+    if (!trace_dev && (run_dev || logits_dev)) FAIL(YMT3_ERR_ARG, "run / logits traces need the (parent, token) trace");
+    // (the kernels read these from the device-resident parameters every call writes: no cached graph holds them)
+    h->beam_trace = BeamShared{};
+    h->beam_trace.trace = trace_dev;
+    h->beam_trace.trace_run = trace_dev ? run_dev : nullptr;
+    h->beam_trace.trace_logits = trace_dev ? logits_dev : nullptr;
+    h->beam_trace.trace_steps = trace_dev ? n_steps : 0;
+    h->beam_trace.trace_groups = trace_dev ? n_groups : 0;
+    return YMT3_OK;
 }
 
 // continuous batching.  `slots` decoder slots are kept busy from a queue of segments: each row

@@ -133,6 +133,40 @@ class YourMT3:
             raise ValueError(f"{P} prompt + {n_steps} emitted steps exceed max_decode_len {cfg.max_decode_len}")
         return t.to(self.device, torch.int32).contiguous()
 
+    BEAM_MAX = 8
+
+    def _beam_params(self, B: int, num_beams, num_return_sequences, length_penalty) -> Optional["_lib.BeamParams"]:
+        """Validated ymt3_beam_params, or None for the plain greedy call (num_beams = num_return_sequences = 1).  Needs no GPU."""
+        W, N = int(num_beams), int(num_return_sequences)
+        if W != num_beams or N != num_return_sequences:
+            raise ValueError("num_beams and num_return_sequences must be integers")
+        alpha = float(length_penalty)
+        if not 1 <= W <= self.BEAM_MAX:
+            raise ValueError(f"num_beams={W} outside [1, {self.BEAM_MAX}]")
+        if not 1 <= N <= W:
+            raise ValueError(f"num_return_sequences={N} outside [1, num_beams={W}]")
+        if not (alpha >= 0.0) or alpha == float("inf"):
+            raise ValueError(f"length_penalty={alpha} must be finite and >= 0")
+        if W == 1 and N == 1:
+            return None
+        if B * W > self.max_batch:
+            raise ValueError(f"{B} segments x num_beams={W} need max_batch >= {B * W}, the model was created with max_batch={self.max_batch}")
+        if self.cfg.n_channels * W > 255:
+            raise ValueError(f"n_channels * num_beams = {self.cfg.n_channels * W} exceeds 255 rows per segment")
+        return _lib.BeamParams(W, N, alpha)
+
+    def beam_trace(self, n_steps: int, n_groups: int, num_beams: int, logits: bool = False):
+        """Debug hook (needs YMT3_DEBUG_HOOKS=1 at construction): from now on beam calls record, per emitted step and group, the new
+        running beams.  Returns (trace (n_steps, n_groups, W, 2) int32 = (parent, token), -1 where nothing was recorded; run (n_steps,
+        n_groups, W) f32; logits (n_steps, n_groups, W, V) f32 raw logits of the running beams, or None).  W must be the calls' num_beams."""
+        W = int(num_beams)
+        tr = torch.full((n_steps, n_groups, W, 2), -1, device=self.device, dtype=torch.int32)
+        run = torch.full((n_steps, n_groups, W), float("nan"), device=self.device, dtype=torch.float32)
+        lg = torch.full((n_steps, n_groups, W, self.cfg.vocab), float("nan"), device=self.device, dtype=torch.float32) if logits else None
+        _lib.check(self._lib.ymt3_debug_beam_trace(self._handle, _ptr(tr), _ptr(run), _ptr(lg), n_steps, n_groups))
+        self._beam_trace = (tr, run, lg)
+        return self._beam_trace
+
     def compile_constraint(self, automaton: TokenAutomaton) -> DecodeConstraint:
         """Validate and upload a token automaton (yourmt3_amd/constraint.py) for decode / inference(constraint=...)."""
         if automaton.vocab != self.cfg.vocab:
@@ -226,18 +260,37 @@ class YourMT3:
 
     def decode(self, enc: torch.Tensor, n_steps: Optional[int] = None, forced: Optional[torch.Tensor] = None,
                return_logits: bool = False, prompt=None, return_scores: bool = False, constraint: Optional[DecodeConstraint] = None,
-               start_states=None):
-        """Greedy decode of n_steps emitted tokens per row.  `prompt` ((P,), (B, P) or (B, K, P) ids): fed after the start id before
+               start_states=None, num_beams: int = 1, num_return_sequences: int = 1, length_penalty: float = 1.0, _force_beam: bool = False):
+        """Greedy decode of n_steps emitted tokens per row; with num_beams > 1 (or num_return_sequences > 1) beam search, see below.  `prompt` ((P,), (B, P) or (B, K, P) ids): fed after the start id before
         anything is emitted (HF decoder_input_ids = [pad, *prompt]); tokens / forced / logits index emitted steps only.
         Returns tokens, then logits if `return_logits`, then scores if `return_scores`: (B, K, n_steps) f32 log-probabilities of
         the fed ids (the emitted ones, or `forced`'s), include/ymt3.h, token scores.  `constraint` (compile_constraint) with
         `start_states` ((K,) or (B, K); None: state 0): every row emits only what its automaton allows (include/ymt3.h,
-        constraints); scores are then those of the masked distribution, logits stay raw."""
+        constraints); scores are then those of the masked distribution, logits stay raw.
+        Beam search (include/ymt3.h, beam search; HF generate(num_beams, num_return_sequences, length_penalty, early_stopping=True)):
+        tokens are (B, K, N, n_steps), best hypothesis first, and with `return_scores` the call returns (tokens, token_scores (B, K, N,
+        n_steps), sequence_scores (B, K, N)).  `forced` and `return_logits` do not combine with beams.  The model needs max_batch >=
+        B * num_beams.  (`_force_beam`: take the beam path for num_beams = 1 too -- greedy search through the beam kernels, for tests.)"""
         cfg = self.cfg
         enc = enc.to(self.device, torch.bfloat16).contiguous()
         B = enc.shape[0]
+        bp = self._beam_params(B, num_beams, num_return_sequences, length_penalty)
+        if bp is None and _force_beam:
+            bp = _lib.BeamParams(1, 1, float(length_penalty))
         p = self._prompt(prompt, B, int(n_steps or 1))
         n_steps = int(n_steps or cfg.max_decode_len - (p.shape[-1] if p is not None else 0))
+        if bp is not None:
+            if forced is not None or return_logits:
+                raise ValueError("forced ids and return_logits do not combine with beam search")
+            N = bp.num_return
+            tokens = torch.empty(B, cfg.n_channels, N, n_steps, device=self.device, dtype=torch.int32)
+            ts = torch.empty(B, cfg.n_channels, N, n_steps, device=self.device, dtype=torch.float32) if return_scores else None
+            ss = torch.empty(B, cfg.n_channels, N, device=self.device, dtype=torch.float32) if return_scores else None
+            st = self._start_states(constraint, start_states, B)
+            _lib.check(self._lib.ymt3_decode_beam(self._handle, _ptr(enc), B, n_steps, _ptr(p), 0 if p is None else int(p.shape[-1]),
+                                                  ctypes.byref(bp), _ptr(tokens), _ptr(ss), _ptr(ts),
+                                                  constraint.ptr if constraint is not None else None, _ptr(st), self._stream()))
+            return (tokens, ts, ss) if return_scores else tokens
         tokens = torch.empty(B, cfg.n_channels, n_steps, device=self.device, dtype=torch.int32)
         f = forced.to(self.device, torch.int32).contiguous() if forced is not None else None
         if f is not None and tuple(f.shape) != (B, cfg.n_channels, n_steps):
@@ -262,16 +315,30 @@ class YourMT3:
 
     # ------------------------------------------------------------------ reference-shaped API
     def inference(self, audio: torch.Tensor, task_tokens=None, max_token_length: Optional[int] = None, return_scores: bool = False,
-                  constraint: Optional[DecodeConstraint] = None, start_states=None):
+                  constraint: Optional[DecodeConstraint] = None, start_states=None, num_beams: int = 1, num_return_sequences: int = 1,
+                  length_penalty: float = 1.0):
         """(B, 1, S) or (B, S) audio -> (B, K, L) int32 token ids: the whole hot path, one C call.  `task_tokens` ((P,), (B, P) or
         (B, K, P) ids, e.g. TaskManager.task_prompt): the decoder is prompted with them and L tokens are emitted after them.
         `return_scores`: returns (tokens, scores), scores (B, K, L) f32 the log-probability of every emitted token (0.0 for the
         PAD after a row's EOS), as HF compute_transition_scores(normalize_logits=True).  `constraint` / `start_states`: as
-        decode()."""
+        decode().  `num_beams` / `num_return_sequences` / `length_penalty`: beam search as in decode() -- tokens (B, K, N, L), and
+        with `return_scores` (tokens, token_scores, sequence_scores)."""
         a = self._audio2d(audio)
         B = a.shape[0]
         L = int(max_token_length or self.cfg.max_decode_len)
+        bp = self._beam_params(B, num_beams, num_return_sequences, length_penalty)
         p = self._prompt(task_tokens, B, L)
+        if bp is not None:
+            N = bp.num_return
+            tokens = torch.empty(B, self.cfg.n_channels, N, L, device=self.device, dtype=torch.int32)
+            ts = torch.empty(B, self.cfg.n_channels, N, L, device=self.device, dtype=torch.float32) if return_scores else None
+            ss = torch.empty(B, self.cfg.n_channels, N, device=self.device, dtype=torch.float32) if return_scores else None
+            st = self._start_states(constraint, start_states, B)
+            if B:
+                _lib.check(self._lib.ymt3_transcribe_segments_beam(
+                    self._handle, _ptr(a), B, L, _ptr(p), 0 if p is None else int(p.shape[-1]), ctypes.byref(bp), _ptr(tokens), _ptr(ss),
+                    _ptr(ts), constraint.ptr if constraint is not None else None, _ptr(st), self._stream()))
+            return (tokens, ts, ss) if return_scores else tokens
         tokens = torch.empty(B, self.cfg.n_channels, L, device=self.device, dtype=torch.int32)
         st = self._start_states(constraint, start_states, B)
         if constraint is not None:
@@ -333,11 +400,17 @@ class YourMT3:
 
     def inference_file(self, bsz: int, audio_segments: torch.Tensor, max_token_length: Optional[int] = None,
                        task_tokens=None, return_scores: bool = False, constraint: Optional[DecodeConstraint] = None,
-                       start_states=None):
+                       start_states=None, num_beams: int = 1, num_return_sequences: int = 1, length_penalty: float = 1.0):
         """Split (N, 1, S) segments into batches of `bsz`; one (b, K, L) int array per batch.  `task_tokens`: (P,) for every
         segment, or (N, P) / (N, K, P), sliced with the batches.  `return_scores`: (token_batches, score_batches), the second a
         list of (b, K, L) float32 arrays (inference(return_scores=True)).  `constraint` / `start_states` ((K,) or (N, K),
-        sliced with the batches): as inference()."""
+        sliced with the batches): as inference().  Beam search (`num_beams` / `num_return_sequences` / `length_penalty`, as
+        inference()): the arrays are (b, K, N, L), `return_scores` gives (token_batches, token_score_batches, sequence_score_batches),
+        and `bsz` counts segments: the model must have been created with max_batch >= bsz * num_beams."""
+        beams = self._beam_params(0, num_beams, num_return_sequences, length_penalty) is not None
+        if beams and int(bsz) * int(num_beams) > self.max_batch:
+            raise ValueError(f"bsz={int(bsz)} x num_beams={int(num_beams)} need max_batch >= {int(bsz) * int(num_beams)}, "
+                             f"the model was created with max_batch={self.max_batch}")
         bsz = min(int(bsz), self.max_batch)
         N = audio_segments.shape[0]
         tt = None if task_tokens is None else torch.as_tensor(task_tokens)
@@ -346,19 +419,28 @@ class YourMT3:
         ss = None if start_states is None else torch.as_tensor(start_states)
         if ss is not None and ss.dim() == 2 and ss.shape[0] != N:
             raise ValueError(f"start_states has {ss.shape[0]} rows for {N} segments")
-        out, scores = [], []
+        out, scores, seq_scores = [], [], []
         for i in range(0, N, bsz):
             ti = tt if tt is None or tt.dim() == 1 else tt[i:i + bsz]
             kw = {}
             if constraint is not None or ss is not None:
                 kw = {"constraint": constraint, "start_states": ss if ss is None or ss.dim() != 2 else ss[i:i + bsz]}
-            if return_scores:
+            if beams:
+                kw.update(num_beams=num_beams, num_return_sequences=num_return_sequences, length_penalty=length_penalty)
+                r = self.inference(audio_segments[i:i + bsz], task_tokens=ti, max_token_length=max_token_length, return_scores=return_scores, **kw)
+                if return_scores:
+                    out.append(r[0].cpu().numpy()); scores.append(r[1].cpu().numpy()); seq_scores.append(r[2].cpu().numpy())
+                else:
+                    out.append(r.cpu().numpy())
+            elif return_scores:
                 t, sc = self.inference(audio_segments[i:i + bsz], task_tokens=ti, max_token_length=max_token_length, return_scores=True,
                                        **kw)
                 out.append(t.cpu().numpy())
                 scores.append(sc.cpu().numpy())
             else:
                 out.append(self.inference(audio_segments[i:i + bsz], task_tokens=ti, max_token_length=max_token_length, **kw).cpu().numpy())
+        if beams and return_scores:
+            return out, scores, seq_scores
         return (out, scores) if return_scores else out
 
     PROFILE_CLASSES = ["qkv_cache_gemm", "self_attn", "self_o_gemm", "cross_q_gemm", "cross_attn", "cross_o_gemm",

@@ -17,7 +17,8 @@ from .task_manager import TaskManager, drop_low_confidence
 def transcribe(model, audio_info: Union[str, dict, np.ndarray], task_manager: Optional[TaskManager] = None, bsz: int = 8,
                output_dir: str = ".", max_token_length: Optional[int] = None, return_notes: bool = False,
                continuous: bool = False, subtask: Optional[str] = None, confidence: bool = False,
-               min_confidence: Optional[float] = None, constrained: bool = False, programs=None):
+               min_confidence: Optional[float] = None, constrained: bool = False, programs=None, num_beams: int = 1,
+               length_penalty: float = 1.0):
     """`continuous=True` decodes the file's segments through `bsz` slots with continuous batching
     (YourMT3.inference_stream: segments leave at EOS and the next ones enter) instead of fixed batches; same ids.
     `subtask`: for a task-conditioned TaskManager (e.g. "singing_drum_v1"), the sub-task whose task tokens prompt every
@@ -27,7 +28,18 @@ def transcribe(model, audio_info: Union[str, dict, np.ndarray], task_manager: Op
     the MIDI file is written.  The ids, and so the notes, are those of the unscored decode.
     `constrained=True` decodes under the TaskManager's segment grammar (TaskManager.event_automaton; include/ymt3.h,
     constraints): no invalid tokens, and with the 13-channel decoder every channel keeps to its own instrument group.
-    `programs` (GM programs, 128 = drums, 129 = singing) implies it and limits the notes to those programs."""
+    `programs` (GM programs, 128 = drums, 129 = singing) implies it and limits the notes to those programs.
+    `num_beams` > 1 decodes with beam search (include/ymt3.h, beam search; `length_penalty` as HF) and takes the best hypothesis of
+    every (segment, channel); confidences are that hypothesis' token scores.  `bsz` still counts segments: the model needs
+    max_batch >= bsz * num_beams.  Beams do not combine with `continuous=True`."""
+    num_beams = int(num_beams)
+    if num_beams < 1:
+        raise ValueError(f"num_beams={num_beams} must be >= 1")
+    if num_beams > 1 and continuous:
+        raise ValueError("beam search (num_beams > 1) does not run with continuous batching (continuous=True)")
+    if num_beams > 1 and min(int(bsz), max(1, model.max_batch)) * num_beams > model.max_batch:
+        raise ValueError(f"bsz={int(bsz)} x num_beams={num_beams} need max_batch >= {int(bsz) * num_beams}, "
+                         f"the model was created with max_batch={model.max_batch}")
     cfg = model.cfg
     if task_manager is None:
         task_manager = TaskManager("mc13_full_plus_256" if cfg.n_channels == 13 else "mt3_full_plus")
@@ -63,6 +75,8 @@ def transcribe(model, audio_info: Union[str, dict, np.ndarray], task_manager: Op
         constraint = model.compile_constraint(aut)
         kw["constraint"] = constraint
         kw["start_states"] = starts
+    if num_beams > 1:
+        kw.update(num_beams=num_beams, num_return_sequences=1, length_penalty=length_penalty)
     try:
         batches, score_batches = _decode(model, segments, bsz, L, continuous, scored, kw)
     finally:
@@ -86,5 +100,9 @@ def _decode(model, segments, bsz, L, continuous, scored, kw):
             score_batches = [out[1].cpu().numpy()]
     else:
         out = model.inference_file(bsz, segments, max_token_length=L, **kw)
-        batches, score_batches = out if scored else (out, None)
+        if kw.get("num_beams", 1) > 1:                  # (b, K, 1, L): hypothesis 0 of every group
+            batches = [t[:, :, 0] for t in (out[0] if scored else out)]
+            score_batches = [t[:, :, 0] for t in out[1]] if scored else None
+        else:
+            batches, score_batches = out if scored else (out, None)
     return batches, score_batches
