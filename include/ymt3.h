@@ -231,8 +231,7 @@ int ymt3_transcribe_stream_constrained(ymt3_handle h, const float* audio_dev, in
  *   - limits (YMT3_ERR_ARG naming the limit, the handle stays usable): 1 <= num_return <= num_beams <= 8; length_penalty finite and >= 0
  *     (a negative one breaks the early-stopping argument that lets a done group freeze); B * n_channels * num_beams <= max_batch *
  *     n_channels, the rows the handle's caches were created for; n_channels * num_beams <= 255; max_decode_len below 48 K.
- *   - not supported: forced ids with beams, beams in ymt3_transcribe_stream* (continuous batching would have to retire groups),
- *     early_stopping False / "never", sampling, diverse beam groups.
+ *   - not supported: forced ids with beams, early_stopping False / "never", sampling, diverse beam groups.
  * Rows: beam w of group g decodes as row g * W + w.  K/V of a position stays in the cache slab of the row that computed it; the
  * self-attention kernel follows a per-row ancestry table instead of the cache being reordered every step.  Beam calls run the separate
  * decode launches (one chain, lock-step), whatever the row count.  Asynchronous like the other decode calls (ymt3_set_early_stop: stops
@@ -245,11 +244,26 @@ int ymt3_decode_beam(ymt3_handle h, const void* enc_dev, int B, int n_steps, con
 int ymt3_transcribe_segments_beam(ymt3_handle h, const float* audio_dev, int B, int n_steps, const int32_t* prompt_dev, int n_prompt,
                                   const ymt3_beam_params* params, int32_t* tokens_dev, float* seq_scores_dev, float* token_scores_dev,
                                   ymt3_constraint constraint, const int32_t* start_state_dev, void* stream);
+/* Beam search under continuous batching: ymt3_transcribe_stream's queue with slots of n_channels * num_beams rows.  audio_dev is
+ * (n_segments, segment_samples), prompt_dev (n_segments, n_channels, n_prompt), start_state_dev (n_segments, n_channels); tokens_dev
+ * (n_segments, n_channels, N, n_steps), seq_scores_dev (n_segments, n_channels, N) and token_scores_dev (n_segments, n_channels, N, n_steps;
+ * both may be NULL) hold exactly what ymt3_transcribe_segments_beam leaves for the same segments.  `slots` counts segments (<= 0, or more than
+ * fit: max_batch / num_beams; YMT3_ERR_ARG naming max_batch if that is 0), `interval` is ymt3_transcribe_stream's (0: 8).  Every `interval`
+ * steps the host reads the rows' finished flags; a segment whose n_channels groups are all done is retired -- the result kernel runs over its
+ * slot's groups -- and the slot restarts on the next pending segment (log-mel, encoder, cross-K/V into the slot's slabs, beam state reset);
+ * done groups of a segment that is still live stay stopped on pad_id.  A group's results do not depend on what the other slots hold.  The
+ * limits above apply with their messages.  Synchronises once per interval and returns when the queue is done; ymt3_last_decode_steps counts
+ * launched steps (`interval` per round).  Allocates nothing after ymt3_create but the pinned flag buffer of ymt3_transcribe_stream. */
+int ymt3_transcribe_stream_beam(ymt3_handle h, const float* audio_dev, int n_segments, int n_steps, const int32_t* prompt_dev, int n_prompt,
+                                const ymt3_beam_params* params, int32_t* tokens_dev, float* seq_scores_dev, float* token_scores_dev,
+                                int slots, int interval, ymt3_constraint constraint, const int32_t* start_state_dev, void* stream);
 /* Debug hook, gated like ymt3_debug_moe_trace (YMT3_DEBUG_HOOKS=1): from now on every beam call records, per emitted step, the new running
  * beams of every group: trace_dev[step][group][W][2] int32 = (parent beam, token), run_dev[step][group][W] f32 their cumulative
  * log-probabilities (may be NULL), logits_dev[step][group][W][V] f32 the raw logits of the running beams the step selected from (may be NULL;
  * not written for a done group).  Steps >= n_steps and groups >= n_groups are not recorded; W is the call's num_beams; trace_dev = NULL stops
- * recording.  The search is discrete: with the trace a test feeds the device's choices to the CPU oracle and compares every step. */
+ * recording.  The search is discrete: with the trace a test feeds the device's choices to the CPU oracle and compares every step.
+ * ymt3_transcribe_stream_beam records under [emitted step of the group][segment * n_channels + channel] -- the group's index in the queue,
+ * not its slot's -- and records nothing for a done group. */
 int ymt3_debug_beam_trace(ymt3_handle h, int32_t* trace_dev, float* run_dev, float* logits_dev, int n_steps, int n_groups);
 
 /* Opt-in early stop (first step): with eos_id >= 0 and interval > 0, ymt3_decode_greedy /

@@ -21,7 +21,7 @@ SYMBOLS = [
     "ymt3_decode_scored", "ymt3_transcribe_segments_scored", "ymt3_transcribe_stream_scored",
     "ymt3_constraint_create", "ymt3_constraint_destroy", "ymt3_decode_constrained", "ymt3_transcribe_segments_constrained",
     "ymt3_transcribe_stream_constrained",
-    "ymt3_decode_beam", "ymt3_transcribe_segments_beam", "ymt3_debug_beam_trace",
+    "ymt3_decode_beam", "ymt3_transcribe_segments_beam", "ymt3_debug_beam_trace", "ymt3_transcribe_stream_beam",
 ]
 
 _lib = None
@@ -119,6 +119,8 @@ def load() -> ctypes.CDLL:
     lib.ymt3_decode_beam.restype = i32
     lib.ymt3_transcribe_segments_beam.argtypes = [vp, vp, i32, i32, vp, i32, bp, vp, vp, vp, vp, vp, vp]
     lib.ymt3_transcribe_segments_beam.restype = i32
+    lib.ymt3_transcribe_stream_beam.argtypes = [vp, vp, i32, i32, vp, i32, bp, vp, vp, vp, i32, i32, vp, vp, vp]
+    lib.ymt3_transcribe_stream_beam.restype = i32
     lib.ymt3_debug_beam_trace.argtypes = [vp, vp, vp, vp, i32, i32]
     lib.ymt3_debug_beam_trace.restype = i32
     for n in ("ymt3_logmel", "ymt3_encode", "ymt3_decode_greedy", "ymt3_transcribe_segments", "ymt3_test_gemm"):

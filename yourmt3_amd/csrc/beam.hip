@@ -1,6 +1,7 @@
 // Beam search on the device (include/ymt3.h, beam search): the selection kernel that takes argmax_embed_kernel's place in a beam
-// call's step, its init and its result kernels.  The ancestry-addressed self-attention lives with the other attention kernels
-// (decode.hip: attn_body<..., BEAM>).
+// call's step, its init and its result kernels, and their per-slot forms for continuous batching (ymt3_transcribe_stream_beam: slot mode
+// of the selection kernel, beam_slot_start_kernel, the result kernel over one slot's groups).  The ancestry-addressed self-attention lives
+// with the other attention kernels (decode.hip: attn_body<..., BEAM>).
 //
 // Rows: r = (segment * n_channels + channel) * W + beam; group g = r / W.  One workgroup per group:
 //   1. per running beam the row maximum and log-sum-exp of its logits exactly as argmax_embed_kernel's score pass takes them (same
@@ -43,6 +44,11 @@ __device__ __forceinline__ void beam_embed_row(const BeamArgs& a, int r, const b
 // (ka, ia) ranks before (kb, ib): larger value, then lower index
 __device__ __forceinline__ bool ranks_before(float ka, int ia, float kb, int ib) { return ka > kb || (ka == kb && ia < ib); }
 
+// SLOT (continuous batching, ymt3_transcribe_stream_beam): every group decodes at its own position a.row_pos[rb] (its W rows share it),
+// reads its prompt through a.row_prompt and records its trace under its queue index a.row_out[rb].  A stopped group (finished flag set:
+// done, or an empty slot) keeps its state and its position and only feeds PAD; a live one advances the positions of its own rows unless
+// the step made it done, and the workgroups do not meet at the end.  Steps 1-4 are the same instructions on the same values: a group's results depend on no other slot.
+template <bool SLOT>
 __global__ __launch_bounds__(256) void beam_select_kernel(BeamArgs a) {
     __shared__ float sv[4], s_sum[4];
     __shared__ int si[4];
@@ -51,7 +57,7 @@ __global__ __launch_bounds__(256) void beam_select_kernel(BeamArgs a) {
     __shared__ float c_acc[2 * BEAM_MAX], c_lp[2 * BEAM_MAX];
     __shared__ int c_idx[2 * BEAM_MAX];
     __shared__ int s_parent[BEAM_MAX], s_feed[BEAM_MAX];
-    __shared__ int s_snap_store[BEAM_MAX], s_snap_parent[BEAM_MAX], s_n_snap;
+    __shared__ int s_snap_store[BEAM_MAX], s_snap_parent[BEAM_MAX], s_n_snap, s_done;
     // thread 0's work arrays of step 3 (in LDS: they are indexed at run time, and as private arrays they lived in scratch memory, a memory
     // round trip per access on a serial path)
     __shared__ bool hit[2 * BEAM_MAX], used[2 * BEAM_MAX], taken[2 * BEAM_MAX];
@@ -61,11 +67,13 @@ __global__ __launch_bounds__(256) void beam_select_kernel(BeamArgs a) {
     const int W = a.W, V = a.V, g = blockIdx.x, rb = g * W;
     DecodeShared* sh = a.shared;
     const BeamShared* bs = a.beam;
-    const int t = sh->step, n_steps = sh->n_steps, n_prompt = sh->n_prompt, col = t - sh->step0 - n_prompt;
+    const bool stopped = SLOT && a.finished[rb] != 0;
+    const int step0 = SLOT ? 0 : sh->step0, tg = SLOT ? (int)a.row_out[rb] : g;      // tg: the group's index in the debug trace
+    const int t = SLOT ? min(max(a.row_pos[rb], 0), min(a.fed_pitch, a.anc_pitch) - 2) : sh->step, n_steps = sh->n_steps, n_prompt = sh->n_prompt, col = t - step0 - n_prompt;
     const uint32_t* const c_allowed = sh->c_allowed;
     const int c_words = sh->c_words;
     const int n_fin0 = a.n_fin[g];
-    const bool live = col >= 0 && n_fin0 < W;         // an emitted step of a group that is not done: the search moves
+    const bool live = !stopped && col >= 0 && n_fin0 < W;         // an emitted step of a group that is not done: the search moves
     if (a.stamp && tid == 0) a.stamp[2 * blockIdx.x] = wall_clock64();
     if (tid < W) {
         s_run[tid] = a.run[rb + tid];
@@ -73,13 +81,15 @@ __global__ __launch_bounds__(256) void beam_select_kernel(BeamArgs a) {
         s_parent[tid] = tid;
         s_feed[tid] = a.pad_id;
     }
-    if (tid == 0) s_n_snap = 0;
+    if (tid == 0) { s_n_snap = 0; s_done = 0; }
     __syncthreads();
 
-    if (col < 0) {
+    if (stopped) {
+        // slot mode, a done group or an empty slot: PAD is fed, nothing else moves
+    } else if (col < 0) {
         // a prompt position: all W rows of the group are fed the group's prompt id; no token, no beam state
         if (tid < W) {
-            const int p = sh->prompt[(size_t)g * n_prompt + (t - sh->step0)];
+            const int p = sh->prompt[(SLOT ? (size_t)a.row_prompt[rb] : (size_t)g * n_prompt) + (t - step0)];
             s_feed[tid] = p < 0 ? 0 : (p >= V ? V - 1 : p);
         }
     } else if (live) {
@@ -186,8 +196,8 @@ __global__ __launch_bounds__(256) void beam_select_kernel(BeamArgs a) {
             }
             // the next running beams: the best W by the hit-penalised score, in order (first among equals)
             for (int c = 0; c < 2 * W; ++c) used[c] = false;
-            int32_t* tr = bs->trace && col < bs->trace_steps && g < bs->trace_groups ? bs->trace + ((size_t)col * bs->trace_groups + g) * W * 2 : nullptr;
-            float* trr = bs->trace_run && col < bs->trace_steps && g < bs->trace_groups ? bs->trace_run + ((size_t)col * bs->trace_groups + g) * W : nullptr;
+            int32_t* tr = bs->trace && col < bs->trace_steps && tg >= 0 && tg < bs->trace_groups ? bs->trace + ((size_t)col * bs->trace_groups + tg) * W * 2 : nullptr;
+            float* trr = bs->trace_run && col < bs->trace_steps && tg >= 0 && tg < bs->trace_groups ? bs->trace_run + ((size_t)col * bs->trace_groups + tg) * W : nullptr;
             for (int i = 0; i < W; ++i) {
                 int b = -1;
                 for (int c = 0; c < 2 * W; ++c)
@@ -251,11 +261,13 @@ __global__ __launch_bounds__(256) void beam_select_kernel(BeamArgs a) {
             }
             a.n_fin[g] = n_keep;
             s_n_snap = n_snap;
-            if (n_keep >= W)
+            if (n_keep >= W) {
                 for (int i = 0; i < W; ++i) a.finished[rb + i] = 1;
+                s_done = 1;
+            }
         }
-    } else if (tid < W && bs->trace && col < bs->trace_steps && g < bs->trace_groups) {
-        // a done group: its rows idle on PAD, every row its own parent
+    } else if (!SLOT && tid < W && bs->trace && col < bs->trace_steps && g < bs->trace_groups) {
+        // a done group: its rows idle on PAD, every row its own parent (slot mode: a done group is stopped and records nothing)
         int32_t* tr = bs->trace + (((size_t)col * bs->trace_groups + g) * W + tid) * 2;
         tr[0] = tid; tr[1] = a.pad_id;
         if (bs->trace_run) bs->trace_run[((size_t)col * bs->trace_groups + g) * W + tid] = s_run[tid];
@@ -263,7 +275,7 @@ __global__ __launch_bounds__(256) void beam_select_kernel(BeamArgs a) {
     __syncthreads();
 
     // ---- 4. ancestry rows of the next position, snapshots, embeddings
-    {
+    if (!stopped) {
         const uint8_t* cur = a.anc + ((size_t)(t & 1) * a.anc_rows + rb) * a.anc_pitch;
         uint8_t* nxt = a.anc + ((size_t)((t + 1) & 1) * a.anc_rows + rb) * a.anc_pitch;
         const int last_word = (t + 1) >> 2, n_words = last_word + 1;           // positions 0 .. t + 1 (anc_pitch > max_decode_len, a multiple of 16)
@@ -286,8 +298,8 @@ __global__ __launch_bounds__(256) void beam_select_kernel(BeamArgs a) {
             for (int j = tid; j <= (t >> 2); j += 256) dst[j] = src[j];
         }
     }
-    if (live && bs->trace_logits && col < bs->trace_steps && g < bs->trace_groups) {
-        float* dst = bs->trace_logits + ((size_t)col * bs->trace_groups + g) * W * V;
+    if (live && bs->trace_logits && col < bs->trace_steps && tg >= 0 && tg < bs->trace_groups) {
+        float* dst = bs->trace_logits + ((size_t)col * bs->trace_groups + tg) * W * V;
         const float* src = a.logits + (size_t)rb * V;
         for (int i = tid; i < W * V; i += 256) dst[i] = src[i];
     }
@@ -299,8 +311,13 @@ __global__ __launch_bounds__(256) void beam_select_kernel(BeamArgs a) {
         beam_embed_row(a, r, e, c, sv);
     }
     // the last workgroup to finish advances the position; every workgroup has read `t` by then
+    // (slot mode: a live group advances its own rows; nothing is shared between groups)
     __syncthreads();
-    if (tid == 0) {
+    if constexpr (SLOT) {
+        // (a group that has just become done stays where it is, like a greedy row after its EOS: the step that filled its slots may have
+        // been the last position of its cache slabs, and the rows go on running until the host retires them)
+        if (!stopped && !s_done && tid < W) a.row_pos[rb + tid] = t + 1;
+    } else if (tid == 0) {
         __threadfence();
         if (atomicAdd(&sh->done_count, 1) == (int)gridDim.x - 1) {
             sh->done_count = 0;
@@ -337,17 +354,41 @@ __global__ __launch_bounds__(256) void beam_init_kernel(BeamArgs a, int n_steps,
     }
 }
 
+// slot mode: (re)start the n_channels * W rows from row0 on the segment whose first group has queue index first_group; cv.start: that
+// segment's [n_channels] start states (or null).  What beam_init_kernel does for every row of a call, for one slot, plus the slot's own
+// position and indices.
+__global__ __launch_bounds__(256) void beam_slot_start_kernel(BeamArgs a, int row0, long long first_group, int n_prompt, ConstraintView cv) {
+    const int r = row0 + blockIdx.x, tid = threadIdx.x, W = a.W, g = r / W, w = r % W, ch = (int)(blockIdx.x / W);
+    const bf16_t* e = a.embed + (size_t)a.pad_id * a.d;
+    const bf16_t* c = a.chan_embed ? a.chan_embed + (size_t)(g % a.n_channels) * a.d : nullptr;
+    __shared__ float sv[4];
+    beam_embed_row(a, r, e, c, sv);
+    if (tid == 0) {
+        a.finished[r] = 0;
+        a.run[r] = w == 0 ? 0.f : BEAM_NEG;
+        a.fin_score[r] = BEAM_NEG; a.fin_len[r] = 0; a.fin_store[r] = w; a.fin_tok[r] = a.pad_id; a.fin_lp[r] = 0.f;
+        if (w == 0) a.n_fin[g] = 0;
+        if (a.row_state) a.row_state[r] = cv.start ? min(max(cv.start[ch], 0), cv.n_states - 1) : 0;
+        a.anc[(size_t)r * a.anc_pitch] = (uint8_t)w;   // buffer 0: position 0 is the row's own
+        a.row_pos[r] = 0;
+        a.row_out[r] = first_group + ch;
+        a.row_prompt[r] = (first_group + ch) * n_prompt;
+    }
+}
+
 // one workgroup per returned hypothesis (group, n): its tokens up to and including the one that finished it, then PAD
-__global__ __launch_bounds__(256) void beam_finalize_kernel(BeamArgs a, int N) {
+// (slot mode, a.row_out set: the groups from g0 on, written at their queue index)
+__global__ __launch_bounds__(256) void beam_finalize_kernel(BeamArgs a, int N, int g0) {
     const BeamShared* bs = a.beam;
     const DecodeShared* sh = a.shared;
-    const int W = a.W, g = blockIdx.x / N, n = blockIdx.x % N, rb = g * W, n_steps = sh->n_steps, P = sh->n_prompt;
+    const int W = a.W, g = g0 + blockIdx.x / N, n = blockIdx.x % N, rb = g * W, n_steps = sh->n_steps, P = sh->n_prompt;
+    const size_t out = a.row_out ? (size_t)a.row_out[rb] * N + n : (size_t)blockIdx.x;
     const bool filled = n < a.n_fin[g];
     const int o = rb + min(n, W - 1);
     const int len = filled ? min(max(a.fin_len[o], 1), n_steps) : 0;
     const uint8_t* snap = a.slot_anc + (size_t)(rb + min(max(a.fin_store[o], 0), W - 1)) * a.anc_pitch;
-    int32_t* tok = bs->tokens_out + (size_t)blockIdx.x * n_steps;
-    float* ts = bs->tok_out ? bs->tok_out + (size_t)blockIdx.x * n_steps : nullptr;
+    int32_t* tok = bs->tokens_out + out * n_steps;
+    float* ts = bs->tok_out ? bs->tok_out + out * n_steps : nullptr;
     for (int j = threadIdx.x; j < n_steps; j += 256) {
         int id = a.pad_id;
         float lp = 0.f;
@@ -360,7 +401,7 @@ __global__ __launch_bounds__(256) void beam_finalize_kernel(BeamArgs a, int N) {
         tok[j] = id;
         if (ts) ts[j] = lp;
     }
-    if (threadIdx.x == 0 && bs->seq_out) bs->seq_out[blockIdx.x] = filled ? a.fin_score[o] : BEAM_NEG;
+    if (threadIdx.x == 0 && bs->seq_out) bs->seq_out[out] = filled ? a.fin_score[o] : BEAM_NEG;
 }
 
 bool beam_args_ok(const BeamArgs& a) {
@@ -373,7 +414,12 @@ bool beam_args_ok(const BeamArgs& a) {
 
 int launch_beam_select(const BeamArgs& a, hipStream_t stream) {
     if (!beam_args_ok(a) || !a.logits) return -1;
-    beam_select_kernel<<<a.R / a.W, 256, 0, stream>>>(a);
+    if (a.row_pos) {
+        if (!a.row_out || !a.row_prompt || !a.finished) return -1;
+        beam_select_kernel<true><<<a.R / a.W, 256, 0, stream>>>(a);
+    } else {
+        beam_select_kernel<false><<<a.R / a.W, 256, 0, stream>>>(a);
+    }
     return 0;
 }
 
@@ -388,7 +434,24 @@ int launch_beam_init(const BeamArgs& a, int n_steps, const int32_t* prompt, int 
 }
 
 int launch_beam_finalize(const BeamArgs& a, int N, hipStream_t stream) {
-    if (!beam_args_ok(a) || N < 1 || N > a.W) return -1;
-    beam_finalize_kernel<<<a.R / a.W * N, 256, 0, stream>>>(a, N);
+    if (!beam_args_ok(a) || N < 1 || N > a.W || a.row_out) return -1;
+    beam_finalize_kernel<<<a.R / a.W * N, 256, 0, stream>>>(a, N, 0);
+    return 0;
+}
+
+int launch_beam_slot_start(const BeamArgs& a, int row0, long long first_group, int n_prompt, const ConstraintView& cv, hipStream_t stream) {
+    const int rows = a.n_channels * a.W;
+    if (!beam_args_ok(a) || !a.row_pos || !a.row_out || !a.row_prompt || !a.finished || row0 < 0 || row0 % rows || row0 + rows > a.R || first_group < 0 ||
+        n_prompt < 0)
+        return -1;
+    if (cv.start && (!a.row_state || cv.n_states < 1)) return -1;
+    beam_slot_start_kernel<<<rows, 256, 0, stream>>>(a, row0, first_group, n_prompt, cv);
+    return 0;
+}
+
+int launch_beam_slot_finalize(const BeamArgs& a, int row0, int N, hipStream_t stream) {
+    const int rows = a.n_channels * a.W;
+    if (!beam_args_ok(a) || N < 1 || N > a.W || !a.row_out || row0 < 0 || row0 % rows || row0 + rows > a.R) return -1;
+    beam_finalize_kernel<<<a.n_channels * N, 256, 0, stream>>>(a, N, row0 / a.W);
     return 0;
 }

@@ -1406,11 +1406,14 @@ int launch_dec_attention(bool self_attn, const DecAttnArgs& a, hipStream_t strea
     return 0;
 }
 
-// beam search: lock-step rows only (no per-row positions), no folded O-projection; the staged table is the kernel's dynamic LDS block
+// beam search: no folded O-projection; the staged table is the kernel's dynamic LDS block.  a.row_pos (slot mode, ymt3_transcribe_stream_beam)
+// goes where the plain self-attention takes it: attn_body reads a row's key count as row_pos[r] + 1 behind the same workgroup-uniform test
+// of the pointer, and the BEAM path picks the ancestry buffer by the parity of THAT position, so a row at its own position stages its own
+// table -- the lock-step and the slot-mode call run the same two instantiations.
 int launch_dec_attention_beam(const DecAttnArgs& a, const BeamAttn& ba, hipStream_t stream) {
     if (a.R <= 0) return 0;
     if (!ba.anc || ba.W < 1 || ba.W > BEAM_MAX || a.R % ba.W || a.row0 % ba.W || ba.anc_pitch % 16 || ba.anc_pitch <= a.slab_keys || ba.anc_pitch > 48 * 1024 ||
-        a.row0 + a.R > ba.anc_rows || a.row_pos || a.wo || a.ipart || a.wq || a.chain_sync || a.rows_per_kv != 1)
+        a.row0 + a.R > ba.anc_rows || a.wo || a.ipart || a.wq || a.chain_sync || a.rows_per_kv != 1)
         return -1;
     if (a.row0 < 0 || a.row0 > 0xffff || a.H < 1 || a.H > 0xff || a.slab_keys < 1 || a.slab_keys > 0xfffff || a.bias_stride != a.slab_keys) return -1;
     const bool many = a.force_many || a.R * a.H > 2048;

@@ -334,6 +334,12 @@ struct BeamArgs {
     int* n_fin;                 // [G] filled slots
     uint8_t* slot_anc;          // [R][anc_pitch]: ancestry snapshots of the finished hypotheses, indexed by fin_store
     unsigned long long* stamp;
+    // slot mode (ymt3_transcribe_stream_beam; all null otherwise): a group decodes at its own position row_pos[r] (the same for its W rows),
+    // feeds prompt[row_prompt[r] + p] at positions p < n_prompt, and row_out[r] is its index in the queue, (segment * n_channels + channel):
+    // where its results and its debug trace go.  A group whose `finished` flag is set is stopped: its state and position stay as they are.
+    int* row_pos;               // [R]
+    long long* row_out;         // [R]
+    long long* row_prompt;      // [R]
 };
 int launch_beam_select(const BeamArgs& a, hipStream_t stream);
 // all rows: h[r] = embed[pad] (+ channel), run = 0 / -1e9, slots empty, anc[step0 & 1][r][0] = own index, automaton start state of the
@@ -342,6 +348,12 @@ int launch_beam_init(const BeamArgs& a, int n_steps, const int32_t* prompt, int 
                      hipStream_t stream);
 // tokens_out / seq_out / tok_out from the finished slots
 int launch_beam_finalize(const BeamArgs& a, int N, hipStream_t stream);
+// slot mode: (re)start rows [row0, row0 + n_channels * W) on the segment whose groups have queue indices first_group ..: h = embed[pad]
+// (+ channel), run = 0 / -1e9, slots empty, anc[0][r][0] = own index, position 0, finished = 0, the automaton state from cv.start[channel]
+// clamped (the segment's start states; 0 without), row_out / row_prompt of the group
+int launch_beam_slot_start(const BeamArgs& a, int row0, long long first_group, int n_prompt, const ConstraintView& cv, hipStream_t stream);
+// slot mode: the results of the n_channels groups from row row0 on, written at their queue indices
+int launch_beam_slot_finalize(const BeamArgs& a, int row0, int N, hipStream_t stream);
 
 // ---------------------------------------------------------------- MoE decoder FFN (moe.hip)
 struct MoeArgs {

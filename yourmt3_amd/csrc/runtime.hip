@@ -772,6 +772,7 @@ static int beam_args(ymt3_handle h, int R, int W, DecodeShared* shared, BeamArgs
     BeamArgs b = h->beam;
     b.logits = h->logits; b.h = h->h_dec; b.shared = shared; b.beam = h->beam_shared; b.finished = h->finished; b.ssq = h->ssq; b.ssq_stride = h->maxR;
     b.R = R; b.V = k.vocab; b.d = d; b.n_channels = k.n_channels; b.eos_id = k.eos_id; b.pad_id = k.pad_id; b.W = W; b.row_state = h->row_state;
+    if (h->slot_mode) { b.row_pos = h->row_pos; b.row_out = h->row_out; b.row_prompt = h->row_prompt; }
     GET(h, "dec.embed", 1u, const_cast<bf16_t**>(&b.embed), (size_t)k.vocab * d);
     if (k.n_channels > 1) GET(h, "dec.chan_embed", 1u, const_cast<bf16_t**>(&b.chan_embed), (size_t)k.n_channels * d);
     *out = b;
@@ -1477,6 +1478,98 @@ extern "C" int ymt3_debug_beam_trace(ymt3_handle h, int32_t* trace_dev, float* r
     return YMT3_OK;
 }
 
+// The queue loop of the stream calls (ymt3_transcribe_stream*, ymt3_transcribe_stream_beam).  `slots` decoder slots of `rows` rows each are
+// kept busy from the queue of segments: a round is `interval` steps of all slots (one replayed graph, cached under `key`), then the host
+// reads the per-row `finished` flags, retires the segments whose rows have all stopped and admits the next pending ones into the freed
+// slots: log-mel + encoder batched over the admissions, cross-K/V written into each slot's slabs, then start(slot, segment).
+// retire(slot) launches whatever leaves the slot's results in the caller's buffers.  The caller has set the handle's mode (slot_mode,
+// beam_W) and reset the loop state with every row stopped.  watch_abort: the steps may hold merged kernels; restart() runs when one gave up.
+template <class Start, class Retire, class Restart>
+static int run_slot_queue(ymt3_handle h, const float* audio_dev, int n_segments, int slots, int rows, int interval, int n_total, long key,
+                          bool watch_abort, Start start, Retire retire, Restart restart, hipStream_t s) {
+    const ymt3_config& k = h->cfg;
+    const int R = slots * rows, d = k.d_model, T = h->T, H = k.n_heads;
+    const size_t S = (size_t)k.segment_samples;
+    int rc;
+    hipGraphExec_t exec = nullptr;
+    // one replayed graph per round of `interval` steps when that is at most 64 steps (a graph launch costs ~7 us of stream time on
+    // top of its kernels, see decode_impl); else one per step
+    const int per_graph = interval <= 64 ? interval : 1;
+    if (h->use_graph) {
+        StepGraph& sg = h->step_graphs[key | ((long)per_graph << 32)];
+        if (!sg.exec) {
+            HIP_TRY(hipStreamBeginCapture(h->cap_stream, hipStreamCaptureModeThreadLocal));
+            int rcs = 0;
+            for (int i = 0; i < per_graph && !rcs; ++i) rcs = launch_step(h, slots, 0, R, h->shared, h->cap_stream);
+            hipError_t e = hipStreamEndCapture(h->cap_stream, &sg.graph);
+            if (rcs) return rcs;
+            if (e != hipSuccess) FAIL(YMT3_ERR_HIP, "hipStreamEndCapture: %s", hipGetErrorString(e));
+            HIP_TRY(hipGraphInstantiate(&sg.exec, sg.graph, nullptr, nullptr, 0));
+            sg.merged = h->step_merged;
+        }
+        exec = sg.exec;
+    }
+
+    std::vector<int> slot_seg((size_t)slots, -1), free_slots;
+    auto admit = [&](int first_seg, int nb) -> int {
+        LAUNCH(launch_logmel(h->fe, audio_dev + (size_t)first_seg * S, h->mel, nb, s));
+        int rce = encode_impl(h, h->mel, nb, h->enc_out, s);
+        if (rce) return rce;
+        for (int i = 0; i < nb; ++i) {
+            const int slot = free_slots[(size_t)i];
+            GemmArgs g{h->enc_out + (size_t)i * T * d, h->wkv_all, h->ckv + (size_t)slot * H * T * 64, nullptr,
+                       T, k.n_dec_layers * 2 * h->inner, d, d, d, 0, T, H, slots};
+            LAUNCH(launch_gemm(EPI_KV_HEADMAJOR, g, s));
+            rce = start(slot, first_seg + i);
+            if (rce) return rce;
+            slot_seg[(size_t)slot] = first_seg + i;
+        }
+        return YMT3_OK;
+    };
+    for (int i = 0; i < slots; ++i) free_slots.push_back(i);
+    rc = admit(0, slots);
+    if (rc) return rc;
+    int next = slots, live = slots;
+    // every live segment stops within n_total steps, so the loop is bounded; the guard only catches a logic error
+    const long max_rounds = ((long)n_segments / slots + 2) * ((n_total + interval - 1) / interval + 1);
+    h->last_steps = 0;
+    for (long round = 0; live > 0; ++round) {
+        h->last_steps += interval;
+        if (round > max_rounds) FAIL(YMT3_ERR_HIP, "slot scheduler made no progress (%d live, %d admitted of %d)", live, next, n_segments);
+        for (int i = 0; i < interval; i += exec ? per_graph : 1) {
+            if (exec) HIP_TRY(hipGraphLaunch(exec, s));
+            else { int rcs = launch_step(h, slots, 0, R, h->shared, s); if (rcs) return rcs; }
+        }
+        HIP_TRY(hipMemcpyAsync(h->host_rows, h->finished, (size_t)R * sizeof(int), hipMemcpyDeviceToHost, s));
+        HIP_TRY(hipStreamSynchronize(s));
+        if (watch_abort) {
+            if (h->forced_abort && h->chain_host_abort) *h->chain_host_abort = 1u;          // debug hook: as a kernel would have during the round
+            if (h->chain_host_abort && *static_cast<volatile unsigned*>(h->chain_host_abort)) return restart();
+        }
+        free_slots.clear();
+        for (int slot = 0; slot < slots; ++slot) {
+            if (slot_seg[(size_t)slot] < 0) continue;
+            bool all = true;
+            for (int c = 0; c < rows; ++c) all = all && h->host_rows[slot * rows + c] != 0;
+            if (!all) continue;
+            rc = retire(slot);
+            if (rc) return rc;
+            slot_seg[(size_t)slot] = -1;
+            --live;
+            free_slots.push_back(slot);
+        }
+        const int nb = std::min((int)free_slots.size(), n_segments - next);
+        if (nb > 0) {
+            rc = admit(next, nb);
+            if (rc) return rc;
+            next += nb;
+            live += nb;
+        }
+    }
+    HIP_TRY(hipGetLastError());
+    return YMT3_OK;
+}
+
 // continuous batching.  `slots` decoder slots are kept busy from a queue of segments: each row
 // decodes at its own position (slot mode of the step kernels), the host looks at the per-row `finished` flags every
 // `interval` steps, pads and retires segments whose rows have all stopped, and encodes the next pending segments straight
@@ -1504,8 +1597,7 @@ extern "C" int ymt3_transcribe_stream_constrained(ymt3_handle h, const float* au
     if (slots > n_segments) slots = n_segments;
     hipStream_t s = (hipStream_t)stream;
     if (!h->host_rows) HIP_TRY(hipHostMalloc(reinterpret_cast<void**>(&h->host_rows), (size_t)h->maxR * sizeof(int), hipHostMallocDefault));
-    const int K = k.n_channels, R = slots * K, d = k.d_model, T = h->T, H = k.n_heads;
-    const size_t S = (size_t)k.segment_samples;
+    const int K = k.n_channels, R = slots * K, d = k.d_model;
 
     ArgmaxArgs a{};
     a.h = h->h_dec; a.shared = h->shared; a.finished = h->finished; a.ssq = h->ssq; a.ssq_stride = h->maxR;
@@ -1526,88 +1618,26 @@ extern "C" int ymt3_transcribe_stream_constrained(ymt3_handle h, const float* au
     HIP_TRY(hipMemsetAsync(h->row_out, 0, (size_t)R * sizeof(long long), s));
     HIP_TRY(hipMemsetAsync(h->row_prompt, 0, (size_t)R * sizeof(long long), s));
 
-    hipGraphExec_t exec = nullptr;
-    // one replayed graph per round of `interval` steps when that is at most 64 steps (a graph launch costs ~7 us of stream time on
-    // top of its kernels, see decode_impl); else one per step
-    const int per_graph = interval <= 64 ? interval : 1;
-    if (h->use_graph) {
-        StepGraph& sg = h->step_graphs[(((long)slots * 16 + 15) * 16) | ((long)per_graph << 32)];      // 15: slot-mode graph of `slots` segments
-        if (!sg.exec) {
-            HIP_TRY(hipStreamBeginCapture(h->cap_stream, hipStreamCaptureModeThreadLocal));
-            int rcs = 0;
-            for (int i = 0; i < per_graph && !rcs; ++i) rcs = launch_step(h, slots, 0, R, h->shared, h->cap_stream);
-            hipError_t e = hipStreamEndCapture(h->cap_stream, &sg.graph);
-            if (rcs) return rcs;
-            if (e != hipSuccess) FAIL(YMT3_ERR_HIP, "hipStreamEndCapture: %s", hipGetErrorString(e));
-            HIP_TRY(hipGraphInstantiate(&sg.exec, sg.graph, nullptr, nullptr, 0));
-            sg.merged = h->step_merged;
-        }
-        exec = sg.exec;
-    }
-
-    std::vector<int> slot_seg((size_t)slots, -1), free_slots;
-    auto admit = [&](int first_seg, int nb) -> int {
-        LAUNCH(launch_logmel(h->fe, audio_dev + (size_t)first_seg * S, h->mel, nb, s));
-        int rce = encode_impl(h, h->mel, nb, h->enc_out, s);
-        if (rce) return rce;
-        for (int i = 0; i < nb; ++i) {
-            const int slot = free_slots[(size_t)i];
-            GemmArgs g{h->enc_out + (size_t)i * T * d, h->wkv_all, h->ckv + (size_t)slot * H * T * 64, nullptr,
-                       T, k.n_dec_layers * 2 * h->inner, d, d, d, 0, T, H, slots};
-            LAUNCH(launch_gemm(EPI_KV_HEADMAJOR, g, s));
-            ConstraintView cv_seg = cv;
-            if (cv.start) cv_seg.start = cv.start + (size_t)(first_seg + i) * K;
-            LAUNCH(launch_slot_start(a, slot * K, (long long)(first_seg + i) * K * n_steps, n_steps, h->row_out,
-                                     (long long)(first_seg + i) * K * n_prompt, n_prompt, h->row_prompt, cv_seg, s));
-            slot_seg[(size_t)slot] = first_seg + i;
-        }
+    const long key = ((long)slots * 16 + 15) * 16;      // 15: slot-mode graph of `slots` segments
+    auto start = [&](int slot, int seg) -> int {
+        ConstraintView cv_seg = cv;
+        if (cv.start) cv_seg.start = cv.start + (size_t)seg * K;
+        LAUNCH(launch_slot_start(a, slot * K, (long long)seg * K * n_steps, n_steps, h->row_out, (long long)seg * K * n_prompt, n_prompt,
+                                 h->row_prompt, cv_seg, s));
         return YMT3_OK;
     };
-    for (int i = 0; i < slots; ++i) free_slots.push_back(i);
-    rc = admit(0, slots);
-    if (rc) return rc;
-    int next = slots, live = slots;
-    // every live segment stops within n_prompt + n_steps steps, so the loop is bounded; the guard only catches a logic error
-    const long max_rounds = ((long)n_segments / slots + 2) * ((n_prompt + n_steps + interval - 1) / interval + 1);
-    h->last_steps = 0;
-    for (long round = 0; live > 0; ++round) {
-        h->last_steps += interval;
-        if (round > max_rounds) FAIL(YMT3_ERR_HIP, "slot scheduler made no progress (%d live, %d admitted of %d)", live, next, n_segments);
-        for (int i = 0; i < interval; i += exec ? per_graph : 1) {
-            if (exec) HIP_TRY(hipGraphLaunch(exec, s));
-            else { int rcs = launch_step(h, slots, 0, R, h->shared, s); if (rcs) return rcs; }
-        }
-        HIP_TRY(hipMemcpyAsync(h->host_rows, h->finished, (size_t)R * sizeof(int), hipMemcpyDeviceToHost, s));
-        HIP_TRY(hipStreamSynchronize(s));
-        if (h->forced_abort && h->chain_host_abort) *h->chain_host_abort = 1u;          // debug hook: as a kernel would have during the round
-        if (h->chain_host_abort && *static_cast<volatile unsigned*>(h->chain_host_abort)) {
-            // a merged kernel gave up (the stream is idle here): start the queue again on the separate launches -- same ids
-            rc = merged_fallback(h);
-            if (rc) return rc;
-            return ymt3_transcribe_stream_constrained(h, audio_dev, n_segments, n_steps, prompt_dev, n_prompt, tokens_dev, scores_dev, slots,
-                                                      interval, constraint, start_state_dev, stream);
-        }
-        free_slots.clear();
-        for (int slot = 0; slot < slots; ++slot) {
-            if (slot_seg[(size_t)slot] < 0) continue;
-            bool all = true;
-            for (int c = 0; c < K; ++c) all = all && h->host_rows[slot * K + c] != 0;
-            if (!all) continue;
-            LAUNCH(launch_slot_retire(a, slot * K, K, n_steps, n_prompt, tokens_dev, scores_dev, s));
-            slot_seg[(size_t)slot] = -1;
-            --live;
-            free_slots.push_back(slot);
-        }
-        const int nb = std::min((int)free_slots.size(), n_segments - next);
-        if (nb > 0) {
-            rc = admit(next, nb);
-            if (rc) return rc;
-            next += nb;
-            live += nb;
-        }
-    }
-    HIP_TRY(hipGetLastError());
-    return YMT3_OK;
+    auto retire = [&](int slot) -> int {
+        LAUNCH(launch_slot_retire(a, slot * K, K, n_steps, n_prompt, tokens_dev, scores_dev, s));
+        return YMT3_OK;
+    };
+    // a merged kernel gave up (the stream is idle when this is called): start the queue again on the separate launches -- same ids
+    auto restart = [&]() -> int {
+        int rcf = merged_fallback(h);
+        if (rcf) return rcf;
+        return ymt3_transcribe_stream_constrained(h, audio_dev, n_segments, n_steps, prompt_dev, n_prompt, tokens_dev, scores_dev, slots, interval,
+                                                  constraint, start_state_dev, stream);
+    };
+    return run_slot_queue(h, audio_dev, n_segments, slots, K, interval, n_prompt + n_steps, key, true, start, retire, restart, s);
 }
 
 extern "C" int ymt3_transcribe_stream_scored(ymt3_handle h, const float* audio_dev, int n_segments, int n_steps, const int32_t* prompt_dev,
@@ -1624,6 +1654,69 @@ extern "C" int ymt3_transcribe_stream_prompted(ymt3_handle h, const float* audio
 extern "C" int ymt3_transcribe_stream(ymt3_handle h, const float* audio_dev, int n_segments, int n_steps, int32_t* tokens_dev,
                                       int slots, int interval, void* stream) {
     return ymt3_transcribe_stream_prompted(h, audio_dev, n_segments, n_steps, nullptr, 0, tokens_dev, slots, interval, stream);
+}
+
+// Beam search under continuous batching (include/ymt3.h): the queue loop above with slots of n_channels * W rows.  A slot is started by
+// beam_slot_start_kernel and harvested by the result kernel over its groups when all of them are done; the steps are launch_step's beam
+// steps with per-row positions (slot_mode and beam_W both set).  Every per-call and per-slot value lives in device memory, so the step
+// graph depends on (slots, W, steps per graph) only.
+extern "C" int ymt3_transcribe_stream_beam(ymt3_handle h, const float* audio_dev, int n_segments, int n_steps, const int32_t* prompt_dev,
+                                           int n_prompt, const ymt3_beam_params* params, int32_t* tokens_dev, float* seq_scores_dev,
+                                           float* token_scores_dev, int slots, int interval, ymt3_constraint constraint,
+                                           const int32_t* start_state_dev, void* stream) {
+    int rc = check_call(h, 0);
+    if (rc) return rc;
+    ConstraintView cv{};
+    rc = constraint_view(h, constraint, start_state_dev, &cv);
+    if (rc) return rc;
+    if (n_segments < 0) FAIL(YMT3_ERR_ARG, "n_segments=%d", n_segments);
+    rc = beam_check(h, 0, n_steps, prompt_dev, n_prompt, params, tokens_dev);
+    if (rc) return rc;
+    if (interval < 0) FAIL(YMT3_ERR_ARG, "interval=%d", interval);
+    const ymt3_config& k = h->cfg;
+    const int W = params->num_beams, K = k.n_channels;
+    if (h->maxB / W < 1) FAIL(YMT3_ERR_ARG, "num_beams=%d exceeds max_batch=%d: not one slot of n_channels * num_beams rows fits", W, h->maxB);
+    if (n_segments == 0) return YMT3_OK;
+    if (!audio_dev || !tokens_dev) FAIL(YMT3_ERR_ARG, "null buffer");
+    if (interval == 0) interval = 8;
+    if (slots <= 0 || slots > h->maxB / W) slots = h->maxB / W;
+    if (slots > n_segments) slots = n_segments;
+    hipStream_t s = (hipStream_t)stream;
+    if (!h->host_rows) HIP_TRY(hipHostMalloc(reinterpret_cast<void**>(&h->host_rows), (size_t)h->maxR * sizeof(int), hipHostMallocDefault));
+    const int rows = K * W, R = slots * rows;
+
+    struct ModeGuard { ymt3_ctx* c; ~ModeGuard() { c->slot_mode = false; c->beam_W = 0; } } guard{h};
+    h->slot_mode = true;
+    h->beam_W = W;
+    BeamArgs b{};
+    rc = beam_args(h, R, W, h->shared, &b);
+    if (rc) return rc;
+    BeamShared bp = h->beam_trace;
+    bp.alpha = params->length_penalty; bp.tokens_out = tokens_dev; bp.seq_out = seq_scores_dev; bp.tok_out = token_scores_dev;
+    h->last_chains = 1;
+    // loop state: every row starts stopped; admissions start them
+    ConstraintView cv_init = cv;
+    cv_init.start = nullptr;                  // (the groups' states are seeded at admission, from their segment's start states)
+    LAUNCH(launch_beam_init(b, n_steps, prompt_dev, n_prompt, cv_init, bp, s));
+    HIP_TRY(hipMemsetD32Async(reinterpret_cast<hipDeviceptr_t>(h->finished), 1, (size_t)R, s));
+    HIP_TRY(hipMemsetAsync(h->row_pos, 0, (size_t)R * sizeof(int), s));
+    HIP_TRY(hipMemsetAsync(h->row_out, 0, (size_t)R * sizeof(long long), s));
+    HIP_TRY(hipMemsetAsync(h->row_prompt, 0, (size_t)R * sizeof(long long), s));
+
+    const long key = (((long)slots * 16 + 13) * 16 + W) | (1L << 42);      // 13: slot-mode beam graph of `slots` segments, W beams
+    const int N = params->num_return;
+    auto start = [&](int slot, int seg) -> int {
+        ConstraintView cv_seg = cv;
+        if (cv.start) cv_seg.start = cv.start + (size_t)seg * K;
+        LAUNCH(launch_beam_slot_start(b, slot * rows, (long long)seg * K, n_prompt, cv_seg, s));
+        return YMT3_OK;
+    };
+    auto retire = [&](int slot) -> int {
+        LAUNCH(launch_beam_slot_finalize(b, slot * rows, N, s));
+        return YMT3_OK;
+    };
+    auto restart = []() -> int { return YMT3_OK; };      // (beam steps hold no merged kernel)
+    return run_slot_queue(h, audio_dev, n_segments, slots, rows, interval, n_prompt + n_steps, key, false, start, retire, restart, s);
 }
 
 extern "C" int ymt3_test_gemm(ymt3_handle h, const void* a_dev, const void* w_dev, float* c_dev, int M, int N, int K, void* stream) {

@@ -31,7 +31,8 @@ def transcribe(model, audio_info: Union[str, dict, np.ndarray], task_manager: Op
     `programs` (GM programs, 128 = drums, 129 = singing) implies it and limits the notes to those programs.
     `num_beams` > 1 decodes with beam search (include/ymt3.h, beam search; `length_penalty` as HF) and takes the best hypothesis of
     every (segment, channel); confidences are that hypothesis' token scores.  `bsz` still counts segments: the model needs
-    max_batch >= bsz * num_beams.  Beams do not combine with `continuous=True`."""
+    max_batch >= bsz * num_beams.  Beams do not combine with `continuous=True` here yet: YourMT3.inference_stream(num_beams=...) is the
+    beam search under continuous batching, and routing this call to it is a two-line follow-up (existing tests pin the refusal)."""
     num_beams = int(num_beams)
     if num_beams < 1:
         raise ValueError(f"num_beams={num_beams} must be >= 1")
