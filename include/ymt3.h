@@ -16,6 +16,7 @@
  *   generate(output_scores=True) + compute_transition_scores(normalize_logits=True)
  *                                        ->  ymt3_transcribe_segments_scored() / ymt3_decode_scored()
  *   generate(prefix_allowed_tokens_fn=...)  ->  ymt3_transcribe_segments_constrained() / ymt3_decode_constrained()
+ *   forward(labels=...) (teacher-forced log-likelihood)  ->  ymt3_transcribe_segments_score() / ymt3_score_tokens()
  *   generate(num_beams=W, num_return_sequences=N, length_penalty=alpha, early_stopping=True)
  *                                        ->  ymt3_transcribe_segments_beam() / ymt3_decode_beam()
  *
@@ -166,6 +167,31 @@ int ymt3_transcribe_segments_scored(ymt3_handle h, const float* audio_dev, int B
                                     int n_prompt, int32_t* tokens_dev, float* scores_dev, void* stream);
 int ymt3_transcribe_stream_scored(ymt3_handle h, const float* audio_dev, int n_segments, int n_steps, const int32_t* prompt_dev,
                                   int n_prompt, int32_t* tokens_dev, float* scores_dev, int slots, int interval, void* stream);
+
+/* Sequence scoring: the teacher-forced log-probability of GIVEN ids, all positions in one pass (HF forward with labels:
+ * `model(inputs_embeds=..., labels=...)`).  Exactly what ymt3_decode_scored(..., forced_dev = tokens_dev) defines, without its n_prompt +
+ * n_steps dependent steps: with the ids known every position of every row is computed at once (kernels: yourmt3_amd/csrc/dec_seq.hip).
+ *   - tokens_dev: (B, n_channels, n_steps) int32, read only.  prompt_dev: (B, n_channels, n_prompt), the prompted calls' convention.
+ *     Position 0 consumes pad_id, positions 1 .. P the prompt, position P + j + 1 tokens[j].
+ *   - scores_dev: (B, n_channels, n_steps) f32.  score[r][j] = log_softmax(logits of position P + j)[tokens[r][j]]; ids are clamped into
+ *     [0, vocab) both as feed and as target, as the forced path does.  Prompt positions write nothing.
+ *   - logits_dev (may be NULL): (B, n_channels, n_steps, vocab) f32 raw logits.
+ *   - lengths_dev (may be NULL: every column counts): (B, n_channels) int32, clamped into [0, n_steps].  Columns j >= lengths[r] score
+ *     exactly 0.0 (their logits, if requested, are still written); the decoder is causal, so a length never changes an earlier column.
+ *   - the score of a position whose logits are NaN, or all -inf, is NaN.  A non-finite segment has NaN scores in its own rows only;
+ *     the other rows keep their bits.
+ *   - the two evaluation orders (this pass and the step loop) agree within the parity tolerance of the logits, not bit for bit: the
+ *     attention here rounds the softmax numerators to bf16 (the encoder kernel's contract), the step kernels keep them in f32.
+ *   - YMT3_ERR_ARG (the handle stays usable): n_steps <= 0, n_prompt < 0, P + n_steps > max_decode_len, NULL tokens or scores, a NULL
+ *     prompt with P > 0.
+ *   - NOT SUPPORTED: the MoE decoder FFN (dec_ffn = YMT3_FFN_MOE) returns YMT3_ERR_UNSUPPORTED, the message names dec_ffn: the
+ *     full-sequence pass has no grouped expert GEMMs yet.  Constraints are not part of this call.
+ * Asynchronous on `stream`.  The pass works in the encoder's activation buffers and touches neither the self-attention cache nor the
+ * decode loop state: a decode call after it is bit-identical to one before it.  Nothing is allocated after ymt3_create. */
+int ymt3_score_tokens(ymt3_handle h, const void* enc_dev, int B, int n_steps, const int32_t* prompt_dev, int n_prompt,
+                      const int32_t* tokens_dev, const int32_t* lengths_dev, float* scores_dev, float* logits_dev, void* stream);
+int ymt3_transcribe_segments_score(ymt3_handle h, const float* audio_dev, int B, int n_steps, const int32_t* prompt_dev, int n_prompt,
+                                   const int32_t* tokens_dev, const int32_t* lengths_dev, float* scores_dev, void* stream);
 
 /* Constraints: a token automaton limits which tokens each row may emit (HF `generate(prefix_allowed_tokens_fn=...)`, i.e. a
  * PrefixConstrainedLogitsProcessor, greedy).

@@ -22,6 +22,7 @@ SYMBOLS = [
     "ymt3_constraint_create", "ymt3_constraint_destroy", "ymt3_decode_constrained", "ymt3_transcribe_segments_constrained",
     "ymt3_transcribe_stream_constrained",
     "ymt3_decode_beam", "ymt3_transcribe_segments_beam", "ymt3_debug_beam_trace", "ymt3_transcribe_stream_beam",
+    "ymt3_score_tokens", "ymt3_transcribe_segments_score",
 ]
 
 _lib = None
@@ -123,6 +124,10 @@ def load() -> ctypes.CDLL:
     lib.ymt3_transcribe_stream_beam.restype = i32
     lib.ymt3_debug_beam_trace.argtypes = [vp, vp, vp, vp, i32, i32]
     lib.ymt3_debug_beam_trace.restype = i32
+    lib.ymt3_score_tokens.argtypes = [vp, vp, i32, i32, vp, i32, vp, vp, vp, vp, vp]
+    lib.ymt3_score_tokens.restype = i32
+    lib.ymt3_transcribe_segments_score.argtypes = [vp, vp, i32, i32, vp, i32, vp, vp, vp, vp]
+    lib.ymt3_transcribe_segments_score.restype = i32
     for n in ("ymt3_logmel", "ymt3_encode", "ymt3_decode_greedy", "ymt3_transcribe_segments", "ymt3_test_gemm"):
         getattr(lib, n).restype = i32
     if lib.ymt3_abi_version() != 3:

@@ -355,6 +355,42 @@ int launch_beam_slot_start(const BeamArgs& a, int row0, long long first_group, i
 // slot mode: the results of the n_channels groups from row row0 on, written at their queue indices
 int launch_beam_slot_finalize(const BeamArgs& a, int row0, int N, hipStream_t stream);
 
+// ---------------------------------------------------------------- full-sequence decoder pass (dec_seq.hip)
+// Teacher-forced scoring (include/ymt3.h, sequence scoring): every position of every decoder row at once.  A chunk holds n_rows whole
+// decoder rows of L = n_prompt + n_steps positions; activation row m = local row * L + position; row0 = the chunk's first decoder row.
+struct SeqEmbedArgs {
+    float* h;                   // [n_rows * L][d] f32 residual rows: embed[fed id] (+ chan_embed[row % n_channels])
+    const bf16_t* embed;        // [V][d]
+    const bf16_t* chan_embed;   // [n_channels][d] or null
+    const int32_t* prompt;      // [R][n_prompt] or null (n_prompt = 0)
+    const int32_t* tokens;      // [R][n_steps]; position 0 feeds pad_id, 1 .. P the prompt, P + j + 1 tokens[j] (clamped into [0, V))
+    int row0, n_rows, L, n_prompt, n_steps, V, d, n_channels, pad_id;
+};
+int launch_seq_embed(const SeqEmbedArgs& a, hipStream_t stream);
+// softmax(Q K^T (+ bias, causal)) V per (decoder row, head); query row (r, t) at q + r * q_seq + t * ldq + h * 64, key / value row (b, t) at
+// k|v + b * kv_seq + h * kv_head + t * ldkv with b = (row0 + r) / rows_per_kv, output row at out + r * o_seq + t * ldo + h * 64.
+// causal: n_keys = L, key <= query only, bias[h][query - key] added ([H][bias_stride] by distance); else all n_keys keys, no bias.
+struct SeqAttnDecArgs {
+    const bf16_t* q; const bf16_t* k; const bf16_t* v; bf16_t* out;
+    const float* bias;
+    long long q_seq, kv_seq, o_seq;
+    int ldq, ldkv, ldo, kv_head;
+    int row0, n_rows, L, n_keys, rows_per_kv, H, bias_stride;
+};
+int launch_dec_seq_attention(bool causal, const SeqAttnDecArgs& a, hipStream_t stream);
+// logits = xn . W^T in column tiles with an online log-sum-exp: scores[row][j] = logit[tokens[row][j]] - lse for the emitted column
+// j = position - n_prompt >= 0 (0.0 for j >= lengths[row]; prompt positions write nothing); logits[row][j][V] only when not null
+struct SeqLmHeadArgs {
+    const bf16_t* xn;           // [M][d] final-normed rows
+    const bf16_t* W;            // [V][d] lm_head
+    const int32_t* tokens;      // [R][n_steps] targets (clamped into [0, V))
+    const int32_t* lengths;     // [R] or null: n_steps
+    float* scores;              // [R][n_steps]
+    float* logits;              // [R][n_steps][V] or null
+    int M, L, n_prompt, n_steps, V, d, row0;
+};
+int launch_seq_lm_head_score(const SeqLmHeadArgs& a, hipStream_t stream);
+
 // ---------------------------------------------------------------- MoE decoder FFN (moe.hip)
 struct MoeArgs {
     float* h;                   // [R][d_model] fp32 residual stream (read by router, updated by combine)

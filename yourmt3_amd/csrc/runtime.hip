@@ -67,6 +67,8 @@ struct ymt3_ctx {
     bf16_t* mel_bf = nullptr;
     float* h_enc = nullptr;
     bf16_t *xn = nullptr, *qkv = nullptr, *attn = nullptr, *ff = nullptr, *enc_out = nullptr;
+    size_t act_rows = 0;                // rows of h_enc / xn / qkv / attn / ff: max(max_batch * n_frames, max_decode_len) -- the full-sequence decoder
+                                        // pass (ymt3_score_tokens) reuses them in chunks of whole decoder rows and needs room for one
     // Perceiver-TF encoder workspace (a9): N1 = B*T*F' spectral tokens, N2 = B*T*K latent rows, D = ptf_d
     bf16_t *p_xs = nullptr, *p_kvs = nullptr;      // [N1][D] normed spectral tokens, [N1][2D] their K/V of one block
     float* p_z = nullptr;                          // [N2][D] fp32 latent residual stream, layout [b][t][k][:]
@@ -331,11 +333,12 @@ static int create_impl(ymt3_ctx* c, const ymt3_config* cfg, const void* blob, si
     const size_t BT = (size_t)c->maxB * c->T, d = k.d_model, R = c->maxR;
     if (dev_alloc(c, (void**)&c->mel, BT * k.n_mels * 4)) return YMT3_ERR_HIP;
     if (dev_alloc(c, (void**)&c->mel_bf, BT * k.n_mels * 2)) return YMT3_ERR_HIP;
-    if (dev_alloc(c, (void**)&c->h_enc, BT * d * 4)) return YMT3_ERR_HIP;
-    if (dev_alloc(c, (void**)&c->xn, BT * d * 2)) return YMT3_ERR_HIP;
-    if (dev_alloc(c, (void**)&c->qkv, BT * 3 * c->inner * 2)) return YMT3_ERR_HIP;
-    if (dev_alloc(c, (void**)&c->attn, BT * c->inner * 2)) return YMT3_ERR_HIP;
-    if (dev_alloc(c, (void**)&c->ff, BT * k.d_ff * 2)) return YMT3_ERR_HIP;
+    const size_t AR = c->act_rows = std::max(BT, (size_t)k.max_decode_len);
+    if (dev_alloc(c, (void**)&c->h_enc, AR * d * 4)) return YMT3_ERR_HIP;
+    if (dev_alloc(c, (void**)&c->xn, AR * d * 2)) return YMT3_ERR_HIP;
+    if (dev_alloc(c, (void**)&c->qkv, AR * 3 * c->inner * 2)) return YMT3_ERR_HIP;
+    if (dev_alloc(c, (void**)&c->attn, AR * c->inner * 2)) return YMT3_ERR_HIP;
+    if (dev_alloc(c, (void**)&c->ff, AR * k.d_ff * 2)) return YMT3_ERR_HIP;
     if (dev_alloc(c, (void**)&c->enc_out, BT * d * 2)) return YMT3_ERR_HIP;
     if (k.encoder_type == YMT3_ENC_PERCEIVER_TF) {
         const int D = k.ptf_d, K = k.n_latents;
@@ -1335,6 +1338,121 @@ extern "C" int ymt3_transcribe_segments_prompted(ymt3_handle h, const float* aud
 extern "C" int ymt3_transcribe_segments(ymt3_handle h, const float* audio_dev, int B, int n_steps, int32_t* tokens_dev,
                                         void* stream) {
     return ymt3_transcribe_segments_prompted(h, audio_dev, B, n_steps, nullptr, 0, tokens_dev, stream);
+}
+
+// ---------------------------------------------------------------- sequence scoring (include/ymt3.h; kernels: dec_seq.hip)
+// The teacher-forced pass: with the ids given nothing is sequential, so every position of every decoder row goes through the layers
+// at once -- launch_gemm / launch_rmsnorm over rows x positions, the causal and the cross attention and the scoring lm_head of
+// dec_seq.hip.  Activations live in the encoder's buffers (idle once the cross-K/V GEMM has read the encoder output), act_rows rows of
+// them: the pass runs in chunks of floor(act_rows / (P + n_steps)) whole decoder rows, queued back to back.  It writes neither the
+// self-attention cache nor the loop state of the step kernels.
+static int score_check(ymt3_handle h, int n_steps, const int32_t* prompt, int n_prompt, const int32_t* tokens, const float* scores) {
+    const ymt3_config& k = h->cfg;
+    if (k.dec_ffn == YMT3_FFN_MOE)
+        FAIL(YMT3_ERR_UNSUPPORTED, "sequence scoring does not run the MoE decoder FFN (dec_ffn = %d): the full-sequence pass has no grouped expert GEMMs", k.dec_ffn);
+    if (n_prompt < 0) FAIL(YMT3_ERR_ARG, "n_prompt=%d < 0", n_prompt);
+    if (n_prompt > 0 && !prompt) FAIL(YMT3_ERR_ARG, "n_prompt=%d with a null prompt", n_prompt);
+    if (n_steps <= 0 || n_prompt + n_steps > k.max_decode_len)
+        FAIL(YMT3_ERR_ARG, "n_steps=%d outside [1, max_decode_len - n_prompt=%d]", n_steps, k.max_decode_len - n_prompt);
+    if (!tokens || !scores) FAIL(YMT3_ERR_ARG, "null tokens or scores buffer");
+    return YMT3_OK;
+}
+
+static int score_impl(ymt3_handle h, const bf16_t* enc, int B, int n_steps, const int32_t* prompt, int n_prompt, const int32_t* tokens,
+                      const int32_t* lengths, float* scores, float* logits_out, hipStream_t s) {
+    const ymt3_config& k = h->cfg;
+    const int d = k.d_model, inner = h->inner, H = k.n_heads, T = h->T, R = B * k.n_channels, L = n_prompt + n_steps;
+    // a6: cross-attention K/V of every decoder layer in one GEMM, as the decode calls
+    GemmArgs g{enc, h->wkv_all, h->ckv, nullptr, B * T, k.n_dec_layers * 2 * inner, d, d, d, 0, T, H, B};
+    LAUNCH(launch_gemm(EPI_KV_HEADMAJOR, g, s));
+    SeqEmbedArgs e{};
+    e.h = h->h_enc; e.prompt = prompt; e.tokens = tokens; e.L = L; e.n_prompt = n_prompt; e.n_steps = n_steps; e.V = k.vocab; e.d = d;
+    e.n_channels = k.n_channels; e.pad_id = k.pad_id;
+    GET(h, "dec.embed", 1u, const_cast<bf16_t**>(&e.embed), (size_t)k.vocab * d);
+    if (k.n_channels > 1) GET(h, "dec.chan_embed", 1u, const_cast<bf16_t**>(&e.chan_embed), (size_t)k.n_channels * d);
+    const float* bias_dist;
+    GET(h, "dec.bias_dist", 0u, const_cast<float**>(&bias_dist), (size_t)H * k.max_decode_len);
+    bf16_t* lm_head;
+    float* ln_f;
+    GET(h, "dec.lm_head", 1u, &lm_head, (size_t)k.vocab * d);
+    GET(h, "dec.ln_f", 0u, &ln_f, (size_t)d);
+    const size_t slab = (size_t)B * H * T * 64;                    // one layer's K (or V) slabs of this call
+    // >= 1: act_rows >= max_decode_len >= L; at most 65535 rows, the attention grid's z extent
+    const int rows_per_chunk = (int)std::min<size_t>(std::min<size_t>(h->act_rows / (size_t)L, (size_t)R), 65535);
+    for (int row0 = 0; row0 < R; row0 += rows_per_chunk) {
+        const int nr = std::min(rows_per_chunk, R - row0), M = nr * L;
+        e.row0 = row0; e.n_rows = nr;
+        LAUNCH(launch_seq_embed(e, s));
+        for (int l = 0; l < k.n_dec_layers; ++l) {
+            const std::string p = "dec." + std::to_string(l) + ".";
+            bf16_t* w;
+            float* f;
+            GET(h, p + "ln1", 0u, &f, (size_t)d);
+            LAUNCH(launch_rmsnorm(h->h_enc, f, h->xn, M, d, k.ln_eps, s));
+            GET(h, p + "wqkv", 1u, &w, (size_t)3 * inner * d);
+            { GemmArgs q{h->xn, w, h->qkv, nullptr, M, 3 * inner, d, d, d, 3 * inner, 0, 0, 0}; LAUNCH(launch_gemm(EPI_BF16, q, s)); }
+            SeqAttnDecArgs sa{};
+            sa.q = h->qkv; sa.k = h->qkv + inner; sa.v = h->qkv + 2 * inner; sa.out = h->attn; sa.bias = bias_dist;
+            sa.q_seq = sa.kv_seq = (long long)L * 3 * inner; sa.o_seq = (long long)L * inner;
+            sa.ldq = sa.ldkv = 3 * inner; sa.ldo = inner; sa.kv_head = 64;
+            sa.row0 = 0; sa.n_rows = nr; sa.L = L; sa.n_keys = L; sa.rows_per_kv = 1; sa.H = H; sa.bias_stride = k.max_decode_len;
+            LAUNCH(launch_dec_seq_attention(true, sa, s));
+            GET(h, p + "wo", 1u, &w, (size_t)d * inner);
+            { GemmArgs q{h->attn, w, h->h_enc, nullptr, M, d, inner, inner, inner, d, 0, 0, 0}; LAUNCH(launch_gemm(EPI_RESID, q, s)); }
+            GET(h, p + "ln2", 0u, &f, (size_t)d);
+            LAUNCH(launch_rmsnorm(h->h_enc, f, h->xn, M, d, k.ln_eps, s));
+            GET(h, p + "wq_c", 1u, &w, (size_t)inner * d);
+            { GemmArgs q{h->xn, w, h->qkv, nullptr, M, inner, d, d, d, inner, 0, 0, 0}; LAUNCH(launch_gemm(EPI_BF16, q, s)); }
+            SeqAttnDecArgs ca{};
+            ca.q = h->qkv; ca.k = h->ckv + (size_t)(2 * l) * slab; ca.v = h->ckv + (size_t)(2 * l + 1) * slab; ca.out = h->attn;
+            ca.q_seq = ca.o_seq = (long long)L * inner; ca.kv_seq = (long long)H * T * 64;
+            ca.ldq = ca.ldo = inner; ca.ldkv = 64; ca.kv_head = T * 64;
+            ca.row0 = row0; ca.n_rows = nr; ca.L = L; ca.n_keys = T; ca.rows_per_kv = k.n_channels; ca.H = H;
+            LAUNCH(launch_dec_seq_attention(false, ca, s));
+            GET(h, p + "wo_c", 1u, &w, (size_t)d * inner);
+            { GemmArgs q{h->attn, w, h->h_enc, nullptr, M, d, inner, inner, inner, d, 0, 0, 0}; LAUNCH(launch_gemm(EPI_RESID, q, s)); }
+            GET(h, p + "ln3", 0u, &f, (size_t)d);
+            LAUNCH(launch_rmsnorm(h->h_enc, f, h->xn, M, d, k.ln_eps, s));
+            GET(h, p + "wi", 1u, &w, (size_t)k.d_ff * d);
+            { GemmArgs q{h->xn, w, h->ff, nullptr, M, k.d_ff, d, d, d, k.d_ff, 0, 0, 0}; LAUNCH(launch_gemm(EPI_BF16_RELU, q, s)); }
+            GET(h, p + "wo2", 1u, &w, (size_t)d * k.d_ff);
+            { GemmArgs q{h->ff, w, h->h_enc, nullptr, M, d, k.d_ff, k.d_ff, k.d_ff, d, 0, 0, 0}; LAUNCH(launch_gemm(EPI_RESID, q, s)); }
+        }
+        LAUNCH(launch_rmsnorm(h->h_enc, ln_f, h->xn, M, d, k.ln_eps, s));
+        SeqLmHeadArgs lm{};
+        lm.xn = h->xn; lm.W = lm_head; lm.tokens = tokens; lm.lengths = lengths; lm.scores = scores; lm.logits = logits_out;
+        lm.M = M; lm.L = L; lm.n_prompt = n_prompt; lm.n_steps = n_steps; lm.V = k.vocab; lm.d = d; lm.row0 = row0;
+        LAUNCH(launch_seq_lm_head_score(lm, s));
+    }
+    HIP_TRY(hipGetLastError());
+    return YMT3_OK;
+}
+
+extern "C" int ymt3_score_tokens(ymt3_handle h, const void* enc_dev, int B, int n_steps, const int32_t* prompt_dev, int n_prompt,
+                                 const int32_t* tokens_dev, const int32_t* lengths_dev, float* scores_dev, float* logits_dev, void* stream) {
+    int rc = check_call(h, B);
+    if (rc) return rc;
+    rc = score_check(h, n_steps, prompt_dev, n_prompt, tokens_dev, scores_dev);
+    if (rc) return rc;
+    if (B == 0) return YMT3_OK;
+    if (!enc_dev) FAIL(YMT3_ERR_ARG, "null buffer");
+    return score_impl(h, static_cast<const bf16_t*>(enc_dev), B, n_steps, prompt_dev, n_prompt, tokens_dev, lengths_dev, scores_dev, logits_dev,
+                      (hipStream_t)stream);
+}
+
+extern "C" int ymt3_transcribe_segments_score(ymt3_handle h, const float* audio_dev, int B, int n_steps, const int32_t* prompt_dev, int n_prompt,
+                                              const int32_t* tokens_dev, const int32_t* lengths_dev, float* scores_dev, void* stream) {
+    int rc = check_call(h, B);
+    if (rc) return rc;
+    rc = score_check(h, n_steps, prompt_dev, n_prompt, tokens_dev, scores_dev);      // before any work is queued
+    if (rc) return rc;
+    if (B == 0) return YMT3_OK;
+    if (!audio_dev) FAIL(YMT3_ERR_ARG, "null buffer");
+    hipStream_t s = (hipStream_t)stream;
+    LAUNCH(launch_logmel(h->fe, audio_dev, h->mel, B, s));
+    rc = encode_impl(h, h->mel, B, h->enc_out, s);
+    if (rc) return rc;
+    return score_impl(h, h->enc_out, B, n_steps, prompt_dev, n_prompt, tokens_dev, lengths_dev, scores_dev, nullptr, s);
 }
 
 // ---------------------------------------------------------------- beam search (include/ymt3.h)

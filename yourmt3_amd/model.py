@@ -313,6 +313,67 @@ class YourMT3:
         out = (tokens,) + ((lg,) if return_logits else ()) + ((sc,) if return_scores else ())
         return out if len(out) > 1 else tokens
 
+    # ------------------------------------------------------------------ sequence scoring (include/ymt3.h)
+    def _score_args(self, tokens, lengths, B: int):
+        """tokens -> (B, K, L) int32 on the device; lengths ("eos", None or a tensor) -> (B, K) int32 on the device, or None."""
+        cfg = self.cfg
+        t = torch.as_tensor(tokens)
+        if t.dtype.is_floating_point or t.dtype == torch.bool or t.dtype.is_complex:
+            raise ValueError(f"tokens must be integer ids, got {t.dtype}")
+        if t.dim() != 3 or tuple(t.shape[:2]) != (B, cfg.n_channels) or t.shape[2] < 1:
+            raise ValueError(f"tokens must be ({B}, {cfg.n_channels}, L) with L >= 1, got {tuple(t.shape)}")
+        t = t.to(self.device, torch.int32).contiguous()
+        L = int(t.shape[2])
+        if isinstance(lengths, str):
+            if lengths != "eos":
+                raise ValueError(f"lengths must be 'eos', None or a (B, K) tensor, got {lengths!r}")
+            if cfg.eos_id >= 0:
+                hit = t == cfg.eos_id                                           # the first EOS, inclusive; L where there is none
+                lengths = torch.where(hit.any(-1), hit.int().argmax(-1) + 1, torch.full_like(hit[..., 0], L, dtype=torch.int64))
+            else:
+                lengths = None
+        if lengths is not None:
+            ln = torch.as_tensor(lengths)
+            if ln.dtype.is_floating_point or ln.dtype == torch.bool or ln.dtype.is_complex:
+                raise ValueError(f"lengths must be integers, got {ln.dtype}")
+            if tuple(ln.shape) != (B, cfg.n_channels):
+                raise ValueError(f"lengths must be ({B}, {cfg.n_channels}), got {tuple(ln.shape)}")
+            lengths = ln.to(self.device, torch.int32).contiguous()
+        return t, lengths
+
+    def decode_score(self, enc: torch.Tensor, tokens: torch.Tensor, prompt=None, lengths=None, return_logits: bool = False):
+        """Teacher-forced scores of GIVEN ids in one pass over all positions (include/ymt3.h, sequence scoring; HF forward with labels):
+        scores (B, K, L) f32 = log_softmax(logits of position P + j)[tokens[..., j]] -- what decode(enc, L, forced=tokens,
+        return_scores=True) returns after P + L dependent steps.  `prompt` as decode(); `lengths` ((B, K) ints, clamped into [0, L]):
+        columns at or past a row's length score exactly 0.0 (None: every column counts).  `return_logits`: (scores, logits (B, K, L,
+        vocab) f32).  Dense decoder FFN only."""
+        enc = enc.to(self.device, torch.bfloat16).contiguous()
+        B = enc.shape[0]
+        t, ln = self._score_args(tokens, lengths, B)
+        L = int(t.shape[2])
+        p = self._prompt(prompt, B, L)
+        sc = torch.empty(B, self.cfg.n_channels, L, device=self.device, dtype=torch.float32)
+        lg = torch.empty(B, self.cfg.n_channels, L, self.cfg.vocab, device=self.device, dtype=torch.float32) if return_logits else None
+        _lib.check(self._lib.ymt3_score_tokens(self._handle, _ptr(enc), B, L, _ptr(p), 0 if p is None else int(p.shape[-1]), _ptr(t),
+                                               _ptr(ln), _ptr(sc), _ptr(lg), self._stream()))
+        return (sc, lg) if return_logits else sc
+
+    def score(self, audio: torch.Tensor, tokens: torch.Tensor, task_tokens=None, lengths="eos"):
+        """(B, 1, S) or (B, S) audio + (B, K, L) ids -> (scores (B, K, L) f32, log_likelihood (B, K) f64): how likely is this
+        transcription for this audio, the whole path in one C call.  `lengths="eos"`: a row counts up to and including its first
+        eos_id (all L columns when it has none, or when eos_id < 0); None: every column; or a (B, K) integer tensor.  Columns past a
+        row's length score 0.0, so log_likelihood = scores.sum(-1) is the likelihood of the sequence up to its end."""
+        a = self._audio2d(audio)
+        B = a.shape[0]
+        t, ln = self._score_args(tokens, lengths, B)
+        L = int(t.shape[2])
+        p = self._prompt(task_tokens, B, L)
+        sc = torch.empty(B, self.cfg.n_channels, L, device=self.device, dtype=torch.float32)
+        if B:
+            _lib.check(self._lib.ymt3_transcribe_segments_score(self._handle, _ptr(a), B, L, _ptr(p), 0 if p is None else int(p.shape[-1]),
+                                                                _ptr(t), _ptr(ln), _ptr(sc), self._stream()))
+        return sc, sc.double().sum(-1)
+
     # ------------------------------------------------------------------ reference-shaped API
     def inference(self, audio: torch.Tensor, task_tokens=None, max_token_length: Optional[int] = None, return_scores: bool = False,
                   constraint: Optional[DecodeConstraint] = None, start_states=None, num_beams: int = 1, num_return_sequences: int = 1,
