@@ -338,12 +338,24 @@ int ymt3_merged_fallbacks(ymt3_handle h);
  * not depend on it.  YMT3_CHAINS=n in the environment at ymt3_create fixes the number (1..8). */
 int ymt3_last_decode_chains(ymt3_handle h);
 
+/* Layer 0's QKV projection as a table.  The residual stream entering layer 0 of a one-channel decoder is the embedding row of the fed
+ * token and nothing else, so that projection is a function of the token id: ymt3_create builds it over the vocabulary ([vocab][3 * 512]
+ * bf16, counted in ymt3_device_bytes) with the decode step's own kernels, and the kernel that feeds a row copies the id's table row where
+ * the projection launch would have written it -- one launch less per step, the same bits.  Taken by every greedy decode call (lock-step and
+ * stream; prompted, scored, constrained) whose steps would run the 16-row-tile projection kernel; not by multi-channel handles, beam calls,
+ * ymt3_profile_decode, handles created under YMT3_STAMP or YMT3_STEP_KERNEL=1, or row counts from the mid-size tile threshold on.
+ * YMT3_NO_QKV0_TABLE=1 in the environment at ymt3_create keeps the launch (A/B).
+ * Returns 1 if the handle's last decode call skipped the layer-0 launch, else 0. */
+int ymt3_qkv0_table_active(ymt3_handle h);
+
 /* Measurement hook (bench.py `roofline`): decode eagerly (no graph) and bracket every kernel launch of
  * every `stride`-th step (positions stride/2, 3*stride/2, ...) with HIP events on `stream`; synchronises the stream before returning.
  * Classes: 0 qkv+cache GEMM, 1 self-attention, 2 self O-proj, 3 cross Q GEMM, 4 cross-attention,
  * 5 cross O-proj, 6 FFN wi, 7 FFN wo, 8 lm_head, 9 argmax+embed, 10 spans: ONE bracket around the stride-1
  * un-bracketed steps after each sampled step (true step time, used to calibrate out the stream time an
- * event pair itself costs).  Outputs are HOST arrays. */
+ * event pair itself costs).  Outputs are HOST arrays.
+ * The profiled, eager step keeps layer 0's QKV launch: this call never takes the layer-0 table (ymt3_qkv0_table_active) that the timed,
+ * graph-replayed calls use, so its launch sequence and class 0 are the pre-table ones (tests pin them). */
 #define YMT3_PROFILE_CLASSES 16
 int ymt3_profile_decode(ymt3_handle h, const void* enc_dev, int B, int n_steps, int stride, int32_t* tokens_dev,
                         float* ms_by_class, int32_t* launches_by_class, void* stream);

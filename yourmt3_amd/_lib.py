@@ -23,6 +23,7 @@ SYMBOLS = [
     "ymt3_transcribe_stream_constrained",
     "ymt3_decode_beam", "ymt3_transcribe_segments_beam", "ymt3_debug_beam_trace", "ymt3_transcribe_stream_beam",
     "ymt3_score_tokens", "ymt3_transcribe_segments_score",
+    "ymt3_qkv0_table_active",
 ]
 
 _lib = None
@@ -113,6 +114,8 @@ def load() -> ctypes.CDLL:
     lib.ymt3_merged_fallbacks.restype = i32
     lib.ymt3_last_decode_chains.argtypes = [vp]
     lib.ymt3_last_decode_chains.restype = i32
+    lib.ymt3_qkv0_table_active.argtypes = [vp]
+    lib.ymt3_qkv0_table_active.restype = i32
     lib.ymt3_debug_moe_trace.argtypes = [vp, vp, i32, i32]
     lib.ymt3_debug_moe_trace.restype = i32
     bp = ctypes.POINTER(BeamParams)

@@ -286,7 +286,9 @@ __global__ __launch_bounds__(512) void dec_gemm_kernel(const bf16_t* __restrict_
         const uint32_t pk = pack_bf16x2(s.x, s.y);
         if constexpr (MODE == DG_NORM_QKV_CACHE) {
             const int inner = a.H * DKV;
-            if (n < inner) {
+            if (a.table) {                       // the layer-0 table build (ymt3_create): the packed row as it is, row = token id
+                *reinterpret_cast<uint32_t*>(a.table + (size_t)m * N + n) = pk;
+            } else if (n < inner) {
                 *reinterpret_cast<uint32_t*>(a.out_bf16 + (size_t)m * inner + n) = pk;
             } else {
                 const int nn = n - inner, kv = nn / inner, hh = (nn % inner) >> 6, dd = nn & 63;
@@ -1020,6 +1022,43 @@ __device__ __forceinline__ void embed_row(const ArgmaxArgs& a, int r, const bf16
     if (tid < SSQ_TILES) a.ssq[(size_t)tid * a.ssq_stride + r] = tid == 0 ? (scratch4[0] + scratch4[1]) + (scratch4[2] + scratch4[3]) : 0.f;
 }
 
+// Layer 0's QKV projection as a gather (ArgmaxArgs::qkv0): thread i < 192 carries 16 bytes (8 columns) of the fed id's table row.
+// Everything but the fed id and the position is known at entry, so a thread's share of both addresses is formed there (under the logits
+// loads in the argmax kernel) and kept in VGPRs: the table's five scalar arguments held in SGPRs to the end of the kernel cost
+// argmax_embed_kernel its 8th wave per SIMD (106 SGPRs), as the constraint's mask row once did.
+struct Qkv0Lane {
+    const bf16_t* src;          // qkv0 + this thread's 8 columns, or null: no table / no chunk for this thread
+    bf16_t* dst;                // columns [0, 512): q of row r; then k and v of head (n % 512) / 64 at cache position 0 (dec_gemm_kernel's epilogue)
+    int pos_stride, L;          // elements per cache position (0 for q), cache length
+};
+__device__ __forceinline__ Qkv0Lane qkv0_lane(const ArgmaxArgs& a, int r) {
+    Qkv0Lane q{nullptr, nullptr, 0, 0};
+    if (a.qkv0 && threadIdx.x < QKV0_COLS / 8) {
+        constexpr int inner = QKV0_COLS / 3, H = inner / DKV;
+        const int n = threadIdx.x * 8, nn = n - inner;
+        q.src = a.qkv0 + n;
+        q.L = a.L;
+        if (n < inner) {
+            q.dst = a.q0 + (size_t)r * inner + n;
+        } else {
+            q.dst = (nn / inner ? a.vcache0 : a.kcache0) + ((size_t)r * H + ((nn % inner) >> 6)) * a.L * DKV + (nn & 63);
+            q.pos_stride = DKV;
+        }
+    }
+    asm volatile("" : "+v"(q.src), "+v"(q.dst), "+v"(q.pos_stride), "+v"(q.L));
+    return q;
+}
+// the load is requested in front of embed_row's loads (one round trip for both); the store follows them
+__device__ __forceinline__ u32x4 qkv0_load(const Qkv0Lane& q, int feed) {
+    u32x4 v = {0u, 0u, 0u, 0u};
+    if (q.src) v = *reinterpret_cast<const u32x4*>(q.src + (size_t)feed * QKV0_COLS);
+    return v;
+}
+// nothing goes to position L, past the (row, head) slab: the last position of a full-length decode has no next step, and the launch never ran after it
+__device__ __forceinline__ void qkv0_store(const Qkv0Lane& q, int pos, const u32x4& v) {
+    if (q.src && (pos < q.L || q.pos_stride == 0)) *reinterpret_cast<u32x4*>(q.dst + (size_t)pos * q.pos_stride) = v;
+}
+
 __global__ __launch_bounds__(256) void argmax_embed_kernel(const float* __restrict__ pLogits, DecodeShared* pShared, int* pFinished, int* pRowPos,
                                                            const long long* __restrict__ pRowOut, const bf16_t* __restrict__ pEmbed, int row0, int V,
                                                            ArgmaxArgs a) {
@@ -1027,6 +1066,7 @@ __global__ __launch_bounds__(256) void argmax_embed_kernel(const float* __restri
     __shared__ float sv[4];
     __shared__ int si[4];
     __shared__ int s_feed;
+    __shared__ int s_pos;                  // slot mode: the row's position after this step (where layer 0's k / v of the fed id go)
     __shared__ float s_sum[4];             // the score pass's wave partials (sv is embed_row's scratch by then)
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int r = row0 + blockIdx.x;
@@ -1051,6 +1091,7 @@ __global__ __launch_bounds__(256) void argmax_embed_kernel(const float* __restri
     // decode ran ~1 ms per 1024-step batch slower)
     const int pos0 = pRowPos ? pRowPos[r] : 0;
     const long long out0 = pRowPos ? pRowOut[r] : 0;
+    const Qkv0Lane ql = qkv0_lane(a, r);
 
     STAMP_IN(a);
     // A row in which no logit compares greater than -3.4e38 (all NaN, all -inf) emits the lowest index, as a tie does: every
@@ -1110,21 +1151,22 @@ __global__ __launch_bounds__(256) void argmax_embed_kernel(const float* __restri
         for (int w = 1; w < 4; ++w)
             if (sv[w] > bv || (sv[w] == bv && si[w] < bi)) { bv = sv[w]; bi = si[w]; }
         bi = min(bi, V - 1);               // (only a state that allows nothing leaves the start value) no index reaches memory unclamped
-        int feed = a.pad_id;
+        int feed = a.pad_id, pos1 = pos0;
         if (!was_finished && pos0 < n_prompt) {           // a prompt position: feed the prompt id, emit nothing
-            pRowPos[r] = pos0 + 1;
+            pRowPos[r] = pos1 = pos0 + 1;
             feed = prompt[a.row_prompt[r] + pos0];
         } else if (!was_finished) {
             const int p = pos0 - n_prompt;
             tokens_out[out0 + p] = bi;
             if ((a.eos_id >= 0 && bi == a.eos_id) || p + 1 >= n_steps) pFinished[r] = 1;
-            else pRowPos[r] = pos0 + 1;
+            else pRowPos[r] = pos1 = pos0 + 1;
             feed = bi;
             score_at = out0 + p;
             score_id = bi;
             if (mrow) a.row_state[r] = sh->c_next[(size_t)state * V + bi];
         }
         s_feed = feed < 0 ? 0 : (feed >= V ? V - 1 : feed);
+        s_pos = pos1;
     } else if (tid == 0 && col < 0) {
         // a prompt position: feed the prompt id; no token, no logits, no EOS flag
         const int p = prompt[(size_t)r * n_prompt + (t - sh->step0)];
@@ -1148,9 +1190,12 @@ __global__ __launch_bounds__(256) void argmax_embed_kernel(const float* __restri
     }
     __syncthreads();
     const int feed = s_feed;
+    const int kv_pos = pRowPos ? s_pos : t + 1;        // the position the next step decodes: a stopped row stays where it is
+    const u32x4 qkv0 = qkv0_load(ql, feed);
     const bf16_t* e = pEmbed + (size_t)feed * a.d;
     const bf16_t* c = a.chan_embed ? a.chan_embed + (size_t)(r % a.n_channels) * a.d : nullptr;
     embed_row(a, r, e, c, sv);
+    qkv0_store(ql, kv_pos, qkv0);
     if (logits_out && !pRowPos && col >= 0) {
         float* dst = logits_out + ((size_t)r * n_steps + col) * V;
         for (int i = tid; i < V; i += 256) dst[i] = row[i];
@@ -1212,7 +1257,10 @@ __global__ __launch_bounds__(256) void decode_init_kernel(ArgmaxArgs a, int n_ch
     const bf16_t* e = a.embed + (size_t)a.pad_id * a.d;
     const bf16_t* c = a.chan_embed ? a.chan_embed + (size_t)(r % a.n_channels) * a.d : nullptr;
     __shared__ float sv[4];
+    const Qkv0Lane ql = qkv0_lane(a, r);
+    const u32x4 qkv0 = qkv0_load(ql, a.pad_id);
     embed_row(a, r, e, c, sv);
+    qkv0_store(ql, step0, qkv0);
     if (tid == 0) {
         a.finished[r] = 0;
         // the start state, clamped into range like a fed id
@@ -1243,7 +1291,10 @@ __global__ __launch_bounds__(256) void slot_start_kernel(ArgmaxArgs a, int row0,
     const bf16_t* e = a.embed + (size_t)a.pad_id * a.d;
     const bf16_t* c = a.chan_embed ? a.chan_embed + (size_t)(r % a.n_channels) * a.d : nullptr;
     __shared__ float sv[4];
+    const Qkv0Lane ql = qkv0_lane(a, r);
+    const u32x4 qkv0 = qkv0_load(ql, a.pad_id);
     embed_row(a, r, e, c, sv);
+    qkv0_store(ql, 0, qkv0);
     if (tid == 0) {
         a.finished[r] = 0;
         a.row_pos[r] = 0;
@@ -1251,6 +1302,12 @@ __global__ __launch_bounds__(256) void slot_start_kernel(ArgmaxArgs a, int row0,
         row_prompt[r] = first_prompt + (long long)blockIdx.x * n_prompt;
         if (a.row_state) a.row_state[r] = cv.start ? min(max(cv.start[blockIdx.x], 0), cv.n_states - 1) : 0;
     }
+}
+
+// the layer-0 table build (ymt3_create): row blockIdx.x of the scratch stream = embed[v0 + blockIdx.x], through embed_row as every decode row
+__global__ __launch_bounds__(256) void qkv0_embed_kernel(ArgmaxArgs a, int v0) {
+    __shared__ float sv[4];
+    embed_row(a, blockIdx.x, a.embed + (size_t)(v0 + blockIdx.x) * a.d, nullptr, sv);
 }
 
 __global__ void slot_retire_kernel(ArgmaxArgs a, int row0, int n_steps, int n_prompt, int32_t* tokens_out, float* scores_out) {
@@ -1356,6 +1413,7 @@ int launch_dec_gemm(int mode, const DecGemmArgs& a, hipStream_t stream) {
     if (a.R <= 0) return 0;
     if (a.N % 16) return -1;
     const int mid_rows = a.mid_rows >= 0 ? a.mid_rows : DEC_GEMM_MID_ROWS;
+    if (a.table && (mode != DG_NORM_QKV_CACHE || a.pend_y || (mid_rows > 0 && a.R >= mid_rows))) return -1;     // the 16-row-tile kernel only
     if (mid_rows > 0 && a.R >= mid_rows && a.N % 64 == 0 && !a.part && !a.pend_y && (a.K == 512 || (a.K == 2048 && mode == DG_RESID)))
         return launch_dec_gemm_mid(mode, a, stream);
     if (mode == DG_RESID) {
@@ -1446,8 +1504,14 @@ int launch_dec_attention_pair(const DecAttnArgs& a, const DecAttnArgs& b, unsign
     return 0;
 }
 
+// the layer-0 table: one channel, rows of QKV0_COLS columns (8 heads of 64), every destination set
+static bool qkv0_args_ok(const ArgmaxArgs& a) {
+    return !a.qkv0 || (a.q0 && a.kcache0 && a.vcache0 && a.H * DKV * 3 == QKV0_COLS && a.L > 0 && !a.chan_embed && a.n_channels == 1);
+}
+
 int launch_argmax_embed(const ArgmaxArgs& a, hipStream_t stream) {
     if (a.R <= 0) return 0;
+    if (!qkv0_args_ok(a)) return -1;
     argmax_embed_kernel<<<a.R, 256, 0, stream>>>(a.logits, a.shared, a.finished, a.row_pos, a.row_out, a.embed, a.row0, a.V, a);
     return 0;
 }
@@ -1458,6 +1522,7 @@ int launch_decode_init(const ArgmaxArgs& a, int n_chains, int n_steps, int step0
     if (a.R <= 0) return 0;
     if (n_prompt < 0 || (n_prompt > 0 && !prompt)) return -1;
     if (cv.allowed && (!cv.next || !a.row_state || cv.n_states < 1 || cv.words * 32 < a.V)) return -1;
+    if (!qkv0_args_ok(a) || (a.qkv0 && (step0 < 0 || step0 >= a.L))) return -1;
     decode_init_kernel<<<a.R, 256, 0, stream>>>(a, n_chains, n_steps, step0, tokens_out, forced, logits_out, prompt, n_prompt, scores_out, cv);
     return 0;
 }
@@ -1466,6 +1531,7 @@ int launch_slot_start(const ArgmaxArgs& a, int row0, long long first_out, int n_
                       int n_prompt, long long* row_prompt, const ConstraintView& cv, hipStream_t stream) {
     if (!a.row_pos || !row_out || !row_prompt || a.n_channels <= 0) return -1;
     if (cv.start && cv.n_states < 1) return -1;
+    if (!qkv0_args_ok(a)) return -1;
     slot_start_kernel<<<a.n_channels, 256, 0, stream>>>(a, row0, first_out, n_steps, row_out, first_prompt, n_prompt, row_prompt, cv);
     return 0;
 }
@@ -1480,5 +1546,11 @@ int launch_slot_retire(const ArgmaxArgs& a, int row0, int n_rows, int n_steps, i
 int launch_pad_tail(int32_t* tokens_out, float* scores_out, int row0, int R, int n_steps, int from, int pad_id, hipStream_t stream) {
     if (R <= 0 || from >= n_steps) return 0;
     pad_tail_kernel<<<R, 256, 0, stream>>>(tokens_out, scores_out, row0, n_steps, from, pad_id);
+    return 0;
+}
+
+int launch_qkv0_embed(const ArgmaxArgs& a, int v0, int n, hipStream_t stream) {
+    if (n <= 0 || v0 < 0 || v0 + n > a.V || !a.h || !a.ssq || !a.embed || a.ssq_stride < n) return -1;
+    qkv0_embed_kernel<<<n, 256, 0, stream>>>(a, v0);
     return 0;
 }

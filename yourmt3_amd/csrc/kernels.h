@@ -132,6 +132,9 @@ struct DecGemmArgs {
     const float* pend_y;
     float* h_out;
     int mid_rows;               // row count from which the mid-size tile kernel is taken; < 0: DEC_GEMM_MID_ROWS; 0: never (handle-level: YMT3_DEC_GEMM_MID_ROWS at create)
+    // MODE_QKV_CACHE, 16-row-tile kernel only, or null: all N packed columns of row m go to table[m * N + n] instead of out_bf16 and the caches
+    // (ymt3_create builds the layer-0 QKV table with it, rows = token ids: see ArgmaxArgs::qkv0)
+    bf16_t* table;
 };
 constexpr int DEC_GEMM_MID_ROWS = 512;
 // The four skinny GEMMs between a layer's cross-attention and the next layer's self-attention as one launch (dec_chain.hip):
@@ -276,8 +279,20 @@ struct ArgmaxArgs {
     int zero_lines;
     const long long* row_prompt;   // slot mode, or null: [R] offset of the row's prompt (see row_pos)
     int* row_state;             // [R] automaton state of every row (read only under a constraint, see DecodeShared::c_allowed)
+    // Layer 0's QKV projection as a gather, or null: qkv0[V][3 * H * 64] = what dec_gemm_kernel<DG_NORM_QKV_CACHE> writes for a row fed token
+    // v (one channel: the residual stream entering layer 0 is embed[v] and nothing else).  The kernel that feeds a row also copies the fed
+    // id's table row: the q third to q0[r], the k / v thirds to layer 0's caches at the position the next step decodes (nothing at
+    // position L: the last position of a full-length decode has no next step) -- and the step launches no layer-0 projection.
+    const bf16_t* qkv0;
+    bf16_t* q0;                 // [R][H * 64]
+    bf16_t* kcache0;            // layer 0: [R][H][L][64]
+    bf16_t* vcache0;
+    int H, L;
 };
+constexpr int QKV0_COLS = 3 * 512;      // a table row: 192 chunks of 16 bytes, one per thread of the feeding kernels
 int launch_argmax_embed(const ArgmaxArgs& a, hipStream_t stream);
+// the layer-0 table build: h[i] = embed[v0 + i] with its sum(h^2) tiles, i in [0, n), through embed_row (a.h / a.ssq: scratch of n rows)
+int launch_qkv0_embed(const ArgmaxArgs& a, int v0, int n, hipStream_t stream);
 // tokens_out[r][from .. n_steps) = pad (scores_out, if not null: 0.0) for rows [row0, row0 + R): the tail of a decode that stopped
 // early (`from`: emitted index)
 int launch_pad_tail(int32_t* tokens_out, float* scores_out, int row0, int R, int n_steps, int from, int pad_id, hipStream_t stream);

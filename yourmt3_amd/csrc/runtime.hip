@@ -133,6 +133,11 @@ struct ymt3_ctx {
     bool moe_chain = false;                 // MoE decoder: a layer's five skinny launches as one (moe_chain.hip; YMT3_NO_MOE_CHAIN=1: separate launches)
     int merged_max_rows = 64;               // YMT3_MERGED_MAX_ROWS: the attention pair / GEMM chain are taken up to this many rows (<= 256)
     bool step_tiles_free = false;           // YMT3_STEP_TILES_FREE=1 (A/B): the step kernel's four row tiles as independent pipelines instead of in step
+    // Layer 0's QKV projection as a table (kernels.h, ArgmaxArgs::qkv0): [vocab][3 * inner] bf16, built at create for a one-channel decoder
+    // (YMT3_NO_QKV0_TABLE=1: not built; neither under YMT3_STAMP nor with the per-step kernel, whose launch sequences stay as they were).
+    // qkv0_call: the decode call being built gathers from it and its steps launch no layer-0 projection (decided per call, see qkv0_decide).
+    bf16_t* qkv0_table = nullptr;
+    bool qkv0_call = false;
     unsigned* ticket = nullptr;             // [maxR / 32 + 1] lines: the argmax kernel's two-level ticket (many rows)
     unsigned* step_sync = nullptr;          // [STEP_SYNC_LINES] counter lines of that kernel (zeroed by the step's argmax kernel / before a decode call)
     // sampled per-kernel-class timing (ymt3_profile_decode): events bracket single launches
@@ -275,6 +280,39 @@ extern "C" void ymt3_destroy(ymt3_handle h) {
 }
 
 extern "C" size_t ymt3_device_bytes(ymt3_handle h) { return h ? h->dev_bytes : 0; }
+extern "C" int ymt3_qkv0_table_active(ymt3_handle h) { return h && h->qkv0_call ? 1 : 0; }
+
+// Layer 0's QKV projection over the whole vocabulary (kernels.h, ArgmaxArgs::qkv0): the decode step's own two kernels -- embed_row, then the
+// 16-row-tile dec_gemm_kernel<DG_NORM_QKV_CACHE> writing its packed rows to the table -- with the token ids as rows, in chunks of 256 (below
+// every mid-tile threshold, and mid_rows = 0 says so whatever the handle's) through scratch of that size.  A row of the kernel depends on
+// that row's h and sum(h^2) tiles alone, so table[v] is what the launch writes for any row fed v, bit for bit.
+static int build_qkv0_table(ymt3_ctx* c) {
+    const ymt3_config& k = c->cfg;
+    const int d = k.d_model, V = k.vocab, N = 3 * c->inner, CH = 256;
+    if (dev_alloc(c, (void**)&c->qkv0_table, (size_t)V * N * 2)) return YMT3_ERR_HIP;
+    float *hs = nullptr, *ssq = nullptr;
+    struct Scratch { float** a; float** b; ~Scratch() { if (*a) (void)hipFree(*a); if (*b) (void)hipFree(*b); } } scratch{&hs, &ssq};
+    HIP_TRY(hipMalloc(reinterpret_cast<void**>(&hs), (size_t)CH * d * 4));
+    HIP_TRY(hipMalloc(reinterpret_cast<void**>(&ssq), (size_t)SSQ_TILES * CH * 4));
+    ArgmaxArgs e{};
+    e.h = hs; e.ssq = ssq; e.ssq_stride = CH; e.V = V; e.d = d; e.n_channels = 1;
+    GET(c, "dec.embed", 1u, const_cast<bf16_t**>(&e.embed), (size_t)V * d);
+    DecGemmArgs a{};
+    a.x_f32 = hs; a.ssq = ssq; a.ssq_stride = CH; a.N = N; a.K = d; a.eps = k.ln_eps; a.H = k.n_heads; a.L = k.max_decode_len;
+    a.shared = c->shared;                     // (the kernel requests the cache position with its operands; the table path does not use it)
+    a.mid_rows = 0;
+    GET(c, "dec.0.ln1", 0u, const_cast<float**>(&a.gain), (size_t)d);
+    GET(c, "dec.0.wqkv", 1u, const_cast<bf16_t**>(&a.W), (size_t)N * d);
+    for (int v0 = 0; v0 < V; v0 += CH) {
+        const int n = std::min(CH, V - v0);
+        hipStream_t s = nullptr;
+        LAUNCH(launch_qkv0_embed(e, v0, n, s));
+        a.row0 = 0; a.R = n; a.table = c->qkv0_table + (size_t)v0 * N;
+        LAUNCH(launch_dec_gemm(DG_NORM_QKV_CACHE, a, s));
+    }
+    HIP_TRY(hipDeviceSynchronize());
+    return YMT3_OK;
+}
 
 static int create_impl(ymt3_ctx* c, const ymt3_config* cfg, const void* blob, size_t nbytes) {
     const ymt3_config& k = c->cfg;
@@ -496,6 +534,13 @@ static int create_impl(ymt3_ctx* c, const ymt3_config* cfg, const void* blob, si
     for (int l = 0; l < nd; ++l)
         for (const char* n : dec_names)
             if (!c->tensors.count("dec." + std::to_string(l) + "." + n)) FAIL(YMT3_ERR_BLOB, "missing dec.%d.%s", l, n);
+    {
+        const char* nt = getenv("YMT3_NO_QKV0_TABLE");       // A/B: keep layer 0's QKV projection launch
+        if (!(nt && nt[0] == '1') && k.n_channels == 1 && !c->step_kernel && !c->stamp_buf && 3 * c->inner == QKV0_COLS) {
+            rc = build_qkv0_table(c);
+            if (rc) return rc;
+        }
+    }
     HIP_TRY(hipDeviceSynchronize());
     return YMT3_OK;
 }
@@ -782,6 +827,19 @@ static int beam_args(ymt3_handle h, int R, int W, DecodeShared* shared, BeamArgs
     return 0;
 }
 
+// Does a decode call whose largest step has `rows` rows take layer 0's q / k / v from the table?  Only where the launch it replaces is the
+// 16-row-tile kernel, whose bits the table holds (the mid-size tiles accumulate K differently); never a beam call (its selection kernels
+// do not gather) and never the profiled call (ymt3_profile_decode keeps the launch sequence its classes are defined by).
+static void qkv0_decide(ymt3_handle h, int rows, bool beam, bool profiled) {
+    const int mid = h->mid_rows > 0 ? h->mid_rows : (h->mid_rows < 0 ? DEC_GEMM_MID_ROWS : 1 << 30);
+    h->qkv0_call = h->qkv0_table && !beam && !profiled && h->cfg.n_channels == 1 && rows < mid;
+}
+// the feeding kernels' side of it: where the fed id's table row goes
+static void qkv0_wire(ymt3_handle h, ArgmaxArgs* a) {
+    if (!h->qkv0_call) return;
+    a->qkv0 = h->qkv0_table; a->q0 = h->dq; a->kcache0 = h->kcache; a->vcache0 = h->vcache; a->H = h->cfg.n_heads; a->L = h->cfg.max_decode_len;
+}
+
 // one decoder step of rows [row0, row0 + R) = 8 kernels per layer + lm_head + argmax, all reading the
 // position from the chain's DecodeShared
 static int launch_step(ymt3_handle h, int B, int row0, int R, DecodeShared* shared, hipStream_t s, bool solo = true) {
@@ -875,7 +933,8 @@ static int launch_step(ymt3_handle h, int B, int row0, int R, DecodeShared* shar
             a.h_out = hcur == h->h_dec ? h->h_dec2 : h->h_dec;
         }
         a.kcache = h->kcache + l * layer_cache; a.vcache = h->vcache + l * layer_cache;
-        if (!qkv_done) {
+        // (layer 0 under the table: the kernel that fed the rows has written q and this position's k / v already; no combine is ever pending here)
+        if (!qkv_done && !(l == 0 && h->qkv0_call && !pend)) {
             a.stamp = next_stamp(h, PC_QKV, a.N / 16 * mtiles);
             PLAUNCH(PC_QKV, launch_dec_gemm(DG_NORM_QKV_CACHE, a, s));
         }
@@ -1048,6 +1107,7 @@ static int launch_step(ymt3_handle h, int B, int row0, int R, DecodeShared* shar
     if (k.n_channels > 1) GET(h, "dec.chan_embed", 1u, const_cast<bf16_t**>(&g.chan_embed), (size_t)k.n_channels * d);
     if (h->slot_mode) { g.row_pos = h->row_pos; g.row_out = h->row_out; g.row_prompt = h->row_prompt; }
     g.row_state = h->row_state;
+    qkv0_wire(h, &g);
     if (solo) g.ticket = h->ticket;                  // (row ranges of several chains would share groups)
     if (stepk) { g.zero_sync = h->step_sync; g.zero_lines = k.n_dec_layers * STEP_SYNC_LINES_PER_LAYER; }
     g.stamp = next_stamp(h, PC_ARGMAX, R);
@@ -1099,6 +1159,8 @@ static int decode_run(ymt3_handle h, const bf16_t* enc, int B, int n_steps, cons
         n_chains = 2;
     if (n_chains > R) n_chains = R;
     h->last_chains = n_chains;
+    qkv0_decide(h, (R + n_chains - 1) / n_chains, false, prof_stride > 0);      // (the largest chain's rows)
+    qkv0_wire(h, &a);
     if (h->step_kernel && h->step_sync) HIP_TRY(hipMemsetAsync(h->step_sync, 0, (size_t)STEP_SYNC_LINES * CHAIN_LINE * sizeof(unsigned), s));
     a.row_state = h->row_state;
     LAUNCH(launch_decode_init(a, n_chains, n_steps, step0, tokens, forced, logits_out, prompt, n_prompt, scores, cv, s));
@@ -1488,6 +1550,7 @@ static int decode_beam_impl(ymt3_handle h, const bf16_t* enc, int B, int n_steps
     BeamShared params = h->beam_trace;
     params.alpha = p->length_penalty; params.tokens_out = tokens; params.seq_out = seq_scores; params.tok_out = token_scores;
     h->last_chains = 1;
+    qkv0_decide(h, R, true, false);
     LAUNCH(launch_beam_init(b, n_steps, prompt, n_prompt, cv, params, s));
     h->last_steps = n_total;
     struct BeamGuard { ymt3_ctx* c; ~BeamGuard() { c->beam_W = 0; } } guard{h};
@@ -1726,6 +1789,8 @@ extern "C" int ymt3_transcribe_stream_constrained(ymt3_handle h, const float* au
 
     struct ModeGuard { ymt3_ctx* c; ~ModeGuard() { c->slot_mode = false; } } guard{h};
     h->slot_mode = true;
+    qkv0_decide(h, R, false, false);
+    qkv0_wire(h, &a);
     // loop state: every row starts stopped; admissions start them
     if (h->step_kernel && h->step_sync) HIP_TRY(hipMemsetAsync(h->step_sync, 0, (size_t)STEP_SYNC_LINES * CHAIN_LINE * sizeof(unsigned), s));
     ConstraintView cv_init = cv;
@@ -1812,6 +1877,7 @@ extern "C" int ymt3_transcribe_stream_beam(ymt3_handle h, const float* audio_dev
     BeamShared bp = h->beam_trace;
     bp.alpha = params->length_penalty; bp.tokens_out = tokens_dev; bp.seq_out = seq_scores_dev; bp.tok_out = token_scores_dev;
     h->last_chains = 1;
+    qkv0_decide(h, R, true, false);
     // loop state: every row starts stopped; admissions start them
     ConstraintView cv_init = cv;
     cv_init.start = nullptr;                  // (the groups' states are seeded at admission, from their segment's start states)

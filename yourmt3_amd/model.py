@@ -211,6 +211,12 @@ class YourMT3:
         """Concurrent row ranges the last decode call cut its batch into (include/ymt3.h: 2 for 168-256 rows of one channel, else 1)."""
         return int(self._lib.ymt3_last_decode_chains(self._handle))
 
+    @property
+    def qkv0_table_active(self) -> bool:
+        """Whether the last decode call took layer 0's q / k / v from the per-token table built at construction and launched no
+        layer-0 projection (include/ymt3.h; YMT3_NO_QKV0_TABLE=1 at construction keeps the launch)."""
+        return bool(self._lib.ymt3_qkv0_table_active(self._handle))
+
     def set_abort_recovery(self, mode: int) -> None:
         """1 (default): decode calls verify at their end that no merged kernel gave up and re-run through the separate launches if
         one did; 0: fully asynchronous calls, an aborted call's ids are INT32_MIN and the next call switches over (include/ymt3.h)."""
