@@ -29,7 +29,8 @@
  *     that ran the merged decode kernels of the 64-row regime (after its last step has been queued; nothing is
  *     launched behind it unless a kernel gave up);
  *   - the library owns weights, KV caches and scratch inside the handle; nothing is
- *     allocated after ymt3_create() except by ymt3_constraint_create() (the caller's automaton tables);
+ *     allocated after ymt3_create() except by ymt3_constraint_create() (the caller's automaton tables) and
+ *     ymt3_detok_create() (the device detokeniser's scratch);
  *   - return value: 0 = ok, non-zero = error; the message is in ymt3_last_error()
  *     (thread local).  No exception ever crosses this boundary;
  *   - one handle per device per host thread.  No internal host threads.
@@ -347,6 +348,44 @@ int ymt3_last_decode_chains(ymt3_handle h);
  * YMT3_NO_QKV0_TABLE=1 in the environment at ymt3_create keeps the launch (A/B).
  * Returns 1 if the handle's last decode call skipped the layer-0 launch, else 0. */
 int ymt3_qkv0_table_active(ymt3_handle h);
+
+/* Device detokeniser: token ids -> notes without a host loop (TaskManager.tokens_to_notes_device; the specification is the host path,
+ * NoteEventTokenizer.decode_segment + note_events_to_notes of yourmt3_amd/task_manager.py, which it reproduces exactly: the same notes, the
+ * same f64 times bit for bit, the same invalid-token count).
+ *   - token table: token_table_host[vocab] uint16 = class << 12 | value (TaskManager.token_table), so the kernels know nothing of the codec's
+ *     layout.  Classes: 0 invalid (UNK, unused ids), 1 stop (PAD, EOS), 2 skip (task tokens), 3 shift, 4 pitch, 5 velocity, 6 tie,
+ *     7 program, 8 drum.  An id outside [0, vocab) on the device is class 0 (so are the INT32_MIN ids of an aborted decode call).
+ *   - tokens_dev: element (segment s, channel c, column j) is tokens_dev[s * seg_stride + c * chan_stride + j], strides in ELEMENTS, n_channels
+ *     = cfg.n_channels; a contiguous (n, K, L) tensor has strides (K * L, L), and the (b, K, N, L) output of a beam call is read in place
+ *     with hypothesis 0's strides (K * N * L, N * L).  scores_dev (may be NULL): f32 token scores in the same layout; a note then carries
+ *     the score of its onset's token, a de-duplicated drum hit the first one unless a later one compares greater (a NaN neither replaces
+ *     nor is replaced).  Without scores every record's score is NaN.
+ *   - start_sec_dev: (n_segments,) f64 start time of every segment.  It MUST be strictly increasing: the kernels take the segment index
+ *     for the host's order by start time and do not check (the Python wrapper does, and raises ValueError).  end_sec closes the notes
+ *     still sounding after the last segment.  Event times are start_sec + step / steps_per_second in f64, that division and that add.
+ *   - notes_dev: `capacity` records of 32 bytes { f64 onset, f64 offset, i32 program, i32 pitch, i32 is_drum, f32 score }, in no
+ *     particular order.  Capacity bound: capacity >= n_segments * n_channels * n_steps (a token yields at most one note), else YMT3_ERR_ARG.
+ *     counts_dev: [2] int32 = { n_notes, n_invalid }; the call zeroes it first.
+ *   - kernels (yourmt3_amd/csrc/detok.hip): one wave per (segment, channel) row runs decode_segment as wave-level scans and compacts the
+ *     row's events; one workgroup per channel buckets them by (program, pitch) with a counting sort in LDS, and one lane per key walks its
+ *     bucket with the host's tie / re-trigger / offset / drum rules.
+ * ymt3_detok_create: synchronous, like ymt3_constraint_create.  Checks (YMT3_ERR_ARG naming the argument): vocab == cfg.vocab,
+ * max_segments >= 1, 1 <= max_steps <= max_decode_len, drum_program in [0, 4095], steps_per_second >= 1, table classes 0..8, pitch and
+ * drum values below 128, velocity values 0 or 1; program values (and drum_program) above 255 are YMT3_ERR_UNSUPPORTED.  Allocates all
+ * scratch, sized by max_segments * n_channels * max_steps (18 bytes per token: items, their keys, the bucketed copy) plus the key
+ * offsets; the records are the caller's.  The object belongs to h; ymt3_detok_destroy frees it (NULL is a no-op), before or after the
+ * handle's destruction.
+ * ymt3_detokenize: asynchronous on `stream`, allocates nothing, leaves the handle's decode state alone.  YMT3_ERR_ARG, with handle and
+ * detokeniser still usable, for n_segments > max_segments, n_steps outside [1, max_steps], NULL tokens_dev / start_sec_dev / notes_dev /
+ * counts_dev, or a capacity below the bound; n_segments = 0 only zeroes the counts.  One object serves one call at a time. */
+typedef struct ymt3_detok_s* ymt3_detok;
+int  ymt3_detok_create(ymt3_handle h, const uint16_t* token_table_host, int vocab, int steps_per_second,
+                       int drum_program, int max_segments, int max_steps, ymt3_detok* out);
+void ymt3_detok_destroy(ymt3_detok d);
+int  ymt3_detokenize(ymt3_handle h, ymt3_detok d, const int32_t* tokens_dev, const float* scores_dev /* may be NULL */,
+                     int n_segments, int n_steps, long long seg_stride, long long chan_stride,
+                     const double* start_sec_dev, double end_sec,
+                     void* notes_dev, long long capacity, int32_t* counts_dev /* [2]: n_notes, n_invalid */, void* stream);
 
 /* Measurement hook (bench.py `roofline`): decode eagerly (no graph) and bracket every kernel launch of
  * every `stride`-th step (positions stride/2, 3*stride/2, ...) with HIP events on `stream`; synchronises the stream before returning.

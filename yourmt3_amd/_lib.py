@@ -24,6 +24,7 @@ SYMBOLS = [
     "ymt3_decode_beam", "ymt3_transcribe_segments_beam", "ymt3_debug_beam_trace", "ymt3_transcribe_stream_beam",
     "ymt3_score_tokens", "ymt3_transcribe_segments_score",
     "ymt3_qkv0_table_active",
+    "ymt3_detok_create", "ymt3_detok_destroy", "ymt3_detokenize",
 ]
 
 _lib = None
@@ -131,6 +132,12 @@ def load() -> ctypes.CDLL:
     lib.ymt3_score_tokens.restype = i32
     lib.ymt3_transcribe_segments_score.argtypes = [vp, vp, i32, i32, vp, i32, vp, vp, vp, vp]
     lib.ymt3_transcribe_segments_score.restype = i32
+    lib.ymt3_detok_create.argtypes = [vp, vp, i32, i32, i32, i32, i32, ctypes.POINTER(vp)]
+    lib.ymt3_detok_create.restype = i32
+    lib.ymt3_detok_destroy.argtypes = [vp]
+    lib.ymt3_detok_destroy.restype = None
+    lib.ymt3_detokenize.argtypes = [vp, vp, vp, vp, i32, i32, ctypes.c_longlong, ctypes.c_longlong, vp, ctypes.c_double, vp, ctypes.c_longlong, vp, vp]
+    lib.ymt3_detokenize.restype = i32
     for n in ("ymt3_logmel", "ymt3_encode", "ymt3_decode_greedy", "ymt3_transcribe_segments", "ymt3_test_gemm"):
         getattr(lib, n).restype = i32
     if lib.ymt3_abi_version() != 3:

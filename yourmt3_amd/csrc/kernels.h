@@ -28,6 +28,37 @@ struct IngestArgs {
 };
 int launch_ingest(const IngestArgs& a, hipStream_t stream);
 
+// ---------------------------------------------------------------- device detokeniser (detok.hip; include/ymt3.h, device detokeniser)
+constexpr int DETOK_PITCHES = 128;        // pitch / drum values per program: a merge key is program * 128 + pitch
+constexpr int DETOK_MAX_PROGRAMS = 256;   // 256 * 128 32-bit counters = 128 KB of the 160 KB of LDS
+constexpr int DETOK_MAX_STEPS = 32768;    // an item's column has 15 bits, its step 27 (32768 * 4095 < 2^27), its segment 20
+constexpr int DETOK_MAX_SEGMENTS = 1 << 20;
+struct DetokNote {                        // the 32-byte record of include/ymt3.h
+    double onset, offset;
+    int32_t program, pitch, is_drum;
+    float score;
+};
+struct DetokArgs {
+    const uint16_t* table;                // [vocab] class << 12 | value
+    int vocab, steps_per_second, drum_program, n_programs;
+    const int32_t* tokens;                // element (s, ch, col) at s * seg_stride + ch * chan_stride + col
+    const float* scores;                  // the same layout, or null
+    long long seg_stride, chan_stride;
+    int n_seg, n_chan, L;
+    const double* start;                  // [n_seg] strictly increasing
+    double end_sec;
+    unsigned long long* items;            // [n_chan][n_seg][L] row (ch, s) owns L slots: segment:20 | not-tie:1 | step:27 | velocity:1 | column:15
+    uint16_t* keys;                       // the same slots: program * 128 + pitch
+    int* row_count;                       // [n_chan][n_seg] items of the row
+    unsigned long long* sorted;           // [n_chan][n_seg * L] a channel's items bucketed by key
+    unsigned* key_off;                    // [n_chan][n_programs * 128] first slot of every key's bucket
+    DetokNote* notes;
+    long long capacity;
+    int32_t* counts;                      // [2] n_notes, n_invalid (zero at launch)
+};
+int init_detok_kernels();
+int launch_detok(const DetokArgs& a, hipStream_t stream);
+
 // ---------------------------------------------------------------- dense GEMM (gemm.hip)
 // C[M][N] (+)= A[M][K] (bf16, row stride lda) * W[N][K]^T (bf16, row stride ldw), fp32 accumulate.
 enum GemmEpilogue {

@@ -645,6 +645,96 @@ extern "C" int ymt3_constraint_create(ymt3_handle h, int n_states, int vocab, co
     return YMT3_OK;
 }
 
+// ---------------------------------------------------------------- device detokeniser (include/ymt3.h)
+struct ymt3_detok_s {
+    ymt3_ctx* owner;
+    int device, vocab, steps_per_second, drum_program, n_programs, max_segments, max_steps;
+    uint16_t* table = nullptr;              // [vocab]
+    unsigned long long* items = nullptr;    // [n_channels * max_segments * max_steps]
+    unsigned long long* sorted = nullptr;   // the same
+    uint16_t* keys = nullptr;               // the same
+    int* row_count = nullptr;               // [n_channels * max_segments]
+    unsigned* key_off = nullptr;            // [n_channels][n_programs * 128]
+};
+
+extern "C" void ymt3_detok_destroy(ymt3_detok d) {
+    if (!d) return;
+    (void)hipSetDevice(d->device);
+    for (void* p : {(void*)d->table, (void*)d->items, (void*)d->sorted, (void*)d->keys, (void*)d->row_count, (void*)d->key_off})
+        if (p) (void)hipFree(p);
+    delete d;
+}
+
+extern "C" int ymt3_detok_create(ymt3_handle h, const uint16_t* token_table_host, int vocab, int steps_per_second, int drum_program,
+                                 int max_segments, int max_steps, ymt3_detok* out) {
+    if (!out) FAIL(YMT3_ERR_ARG, "null output pointer");
+    *out = nullptr;
+    if (!h) FAIL(YMT3_ERR_ARG, "null handle");
+    if (!token_table_host) FAIL(YMT3_ERR_ARG, "token_table_host is NULL");
+    if (vocab != h->cfg.vocab) FAIL(YMT3_ERR_ARG, "detokeniser vocab=%d != the model's vocab=%d", vocab, h->cfg.vocab);
+    if (steps_per_second < 1) FAIL(YMT3_ERR_ARG, "steps_per_second=%d must be >= 1", steps_per_second);
+    if (drum_program < 0 || drum_program > 4095) FAIL(YMT3_ERR_ARG, "drum_program=%d outside [0, 4095]", drum_program);
+    if (max_segments < 1 || max_segments > DETOK_MAX_SEGMENTS) FAIL(YMT3_ERR_ARG, "max_segments=%d outside [1, %d]", max_segments, DETOK_MAX_SEGMENTS);
+    if (max_steps < 1 || max_steps > h->cfg.max_decode_len || max_steps > DETOK_MAX_STEPS)
+        FAIL(YMT3_ERR_ARG, "max_steps=%d outside [1, max_decode_len=%d]", max_steps, std::min(h->cfg.max_decode_len, DETOK_MAX_STEPS));
+    int n_programs = drum_program + 1;
+    for (int i = 0; i < vocab; ++i) {
+        const int cls = token_table_host[i] >> 12, v = token_table_host[i] & 0xfff;
+        if (cls > 8) FAIL(YMT3_ERR_ARG, "token_table_host[%d] has class %d (0..8 are defined)", i, cls);
+        if ((cls == 4 || cls == 8) && v >= DETOK_PITCHES) FAIL(YMT3_ERR_ARG, "token_table_host[%d]: pitch %d outside [0, %d)", i, v, DETOK_PITCHES);
+        if (cls == 5 && v > 1) FAIL(YMT3_ERR_ARG, "token_table_host[%d]: velocity %d is neither 0 (offsets) nor 1 (onsets)", i, v);
+        if (cls == 7) n_programs = std::max(n_programs, v + 1);
+    }
+    if (n_programs > DETOK_MAX_PROGRAMS)
+        FAIL(YMT3_ERR_UNSUPPORTED, "programs up to %d: the merge keeps one LDS counter per (program, pitch), at most %d programs", n_programs - 1, DETOK_MAX_PROGRAMS);
+    HIP_TRY(hipSetDevice(h->device));
+    if (init_detok_kernels()) FAIL(YMT3_ERR_HIP, "hipFuncSetAttribute(max dynamic LDS) failed");
+    ymt3_detok d = new ymt3_detok_s{h, h->device, vocab, steps_per_second, drum_program, n_programs, max_segments, max_steps};
+    const size_t rows = (size_t)max_segments * h->cfg.n_channels, slots = rows * max_steps;
+    const size_t koff = (size_t)h->cfg.n_channels * n_programs * DETOK_PITCHES * sizeof(unsigned);
+    if (hipMalloc(reinterpret_cast<void**>(&d->table), (size_t)vocab * 2) != hipSuccess ||
+        hipMalloc(reinterpret_cast<void**>(&d->items), slots * 8) != hipSuccess ||
+        hipMalloc(reinterpret_cast<void**>(&d->sorted), slots * 8) != hipSuccess ||
+        hipMalloc(reinterpret_cast<void**>(&d->keys), slots * 2) != hipSuccess ||
+        hipMalloc(reinterpret_cast<void**>(&d->row_count), rows * sizeof(int)) != hipSuccess ||
+        hipMalloc(reinterpret_cast<void**>(&d->key_off), koff) != hipSuccess ||
+        hipMemcpy(d->table, token_table_host, (size_t)vocab * 2, hipMemcpyHostToDevice) != hipSuccess) {
+        ymt3_detok_destroy(d);
+        FAIL(YMT3_ERR_HIP, "detokeniser scratch (%zu bytes) could not be allocated", slots * 18 + rows * sizeof(int) + koff);
+    }
+    *out = d;
+    return YMT3_OK;
+}
+
+extern "C" int ymt3_detokenize(ymt3_handle h, ymt3_detok d, const int32_t* tokens_dev, const float* scores_dev, int n_segments, int n_steps,
+                               long long seg_stride, long long chan_stride, const double* start_sec_dev, double end_sec, void* notes_dev,
+                               long long capacity, int32_t* counts_dev, void* stream) {
+    if (!h) FAIL(YMT3_ERR_ARG, "null handle");
+    if (!d) FAIL(YMT3_ERR_ARG, "null detokeniser");
+    if (d->owner != h) FAIL(YMT3_ERR_ARG, "the detokeniser belongs to another handle");
+    if (n_segments < 0 || n_segments > d->max_segments) FAIL(YMT3_ERR_ARG, "n_segments=%d outside [0, max_segments=%d]", n_segments, d->max_segments);
+    if (n_steps < 1 || n_steps > d->max_steps) FAIL(YMT3_ERR_ARG, "n_steps=%d outside [1, max_steps=%d]", n_steps, d->max_steps);
+    if (!counts_dev) FAIL(YMT3_ERR_ARG, "counts_dev is NULL");
+    if (n_segments && !tokens_dev) FAIL(YMT3_ERR_ARG, "tokens_dev is NULL");
+    if (n_segments && !start_sec_dev) FAIL(YMT3_ERR_ARG, "start_sec_dev is NULL");
+    if (n_segments && !notes_dev) FAIL(YMT3_ERR_ARG, "notes_dev is NULL");
+    const long long bound = (long long)n_segments * h->cfg.n_channels * n_steps;
+    if (capacity < bound) FAIL(YMT3_ERR_ARG, "capacity=%lld below n_segments * n_channels * n_steps = %lld records", capacity, bound);
+    HIP_TRY(hipSetDevice(h->device));
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    HIP_TRY(hipMemsetAsync(counts_dev, 0, 2 * sizeof(int32_t), s));
+    if (!n_segments) return YMT3_OK;
+    DetokArgs a{};
+    a.table = d->table; a.vocab = d->vocab; a.steps_per_second = d->steps_per_second; a.drum_program = d->drum_program; a.n_programs = d->n_programs;
+    a.tokens = tokens_dev; a.scores = scores_dev; a.seg_stride = seg_stride; a.chan_stride = chan_stride;
+    a.n_seg = n_segments; a.n_chan = h->cfg.n_channels; a.L = n_steps;
+    a.start = start_sec_dev; a.end_sec = end_sec;
+    a.items = d->items; a.keys = d->keys; a.row_count = d->row_count; a.sorted = d->sorted; a.key_off = d->key_off;
+    a.notes = static_cast<DetokNote*>(notes_dev); a.capacity = capacity; a.counts = counts_dev;
+    LAUNCH(launch_detok(a, s));
+    return YMT3_OK;
+}
+
 // the kernels' view of a call's constraint (all null without one)
 static int constraint_view(ymt3_handle h, ymt3_constraint c, const int32_t* start_state_dev, ConstraintView* cv) {
     *cv = ConstraintView{};

@@ -19,6 +19,7 @@ from . import _lib
 from .config import YMT3Config, to_c
 from .constraint import TokenAutomaton
 from .tables import derived_tables
+from .task_manager import DRUM_PROGRAM
 from .weights import make_weights, pack_blob
 
 
@@ -50,6 +51,68 @@ class DecodeConstraint:
         if getattr(self, "_c", None) is not None and self._c.value:
             self._lib.ymt3_constraint_destroy(self._c)
             self._c = ctypes.c_void_p()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+NOTE_RECORD = np.dtype([("onset", "<f8"), ("offset", "<f8"), ("program", "<i4"), ("pitch", "<i4"), ("is_drum", "<i4"), ("score", "<f4")])
+
+
+class Detokenizer:
+    """The device detokeniser of one model for one TaskManager (YourMT3.compile_detokenizer; include/ymt3.h, device detokeniser): the
+    token table and all scratch for up to `max_segments` segments of `max_steps` columns.  Freed by close(), or by the model's close()."""
+
+    def __init__(self, model: "YourMT3", task_manager, max_segments: int, max_steps: int):
+        self.max_segments, self.max_steps = int(max_segments), int(max_steps)
+        self.n_channels = model.cfg.n_channels
+        self._model = weakref.ref(model)
+        self._lib = model._lib
+        self._c = ctypes.c_void_p()
+        table = np.ascontiguousarray(task_manager.token_table(), dtype=np.uint16)
+        _lib.check(self._lib.ymt3_detok_create(model._handle, table.ctypes.data, int(table.size), int(task_manager.codec.steps_per_second),
+                                               DRUM_PROGRAM, self.max_segments, self.max_steps, ctypes.byref(self._c)))
+        self.capacity = self.max_segments * self.n_channels * self.max_steps
+        self._notes = torch.empty(self.capacity * NOTE_RECORD.itemsize, device=model.device, dtype=torch.uint8)
+        self._counts = torch.zeros(2, device=model.device, dtype=torch.int32)
+
+    @property
+    def ptr(self):
+        if not self._c.value:
+            raise ValueError("the detokenizer has been closed")
+        return self._c
+
+    def run(self, tokens: torch.Tensor, scores: Optional[torch.Tensor], start_secs: torch.Tensor, end_sec: float):
+        """(n, K, L) ids (+ scores) on the device, (n,) f64 strictly increasing start times -> (records: NOTE_RECORD array, n_invalid)."""
+        model = self._model()
+        if model is None:
+            raise ValueError("the detokenizer's model is gone")
+        n, K, L = (int(v) for v in tokens.shape)
+        if tokens.dtype != torch.int32:
+            tokens = tokens.to(torch.int32)
+        tokens = tokens.to(model.device)
+        if L > 1 and tokens.stride(2) != 1:
+            tokens = tokens.contiguous()
+        if scores is not None:
+            scores = scores.to(model.device, torch.float32)
+            if tuple(scores.stride()) != tuple(tokens.stride()):         # one pair of strides serves both
+                tokens, scores = tokens.contiguous(), scores.contiguous()
+        starts = start_secs.to(model.device, torch.float64).contiguous()
+        _lib.check(self._lib.ymt3_detokenize(model._handle, self.ptr, _ptr(tokens), _ptr(scores), n, L, tokens.stride(0), tokens.stride(1),
+                                             _ptr(starts), float(end_sec), _ptr(self._notes), self.capacity, _ptr(self._counts),
+                                             model._stream()))
+        n_notes, n_invalid = (int(v) for v in self._counts.cpu().tolist())
+        rec = self._notes[:n_notes * NOTE_RECORD.itemsize].cpu().numpy().view(NOTE_RECORD)
+        return rec, n_invalid
+
+    def close(self):
+        if getattr(self, "_c", None) is not None and self._c.value:
+            self._lib.ymt3_detok_destroy(self._c)
+            self._c = ctypes.c_void_p()
+            self._notes = self._counts = None
 
     def __del__(self):
         try:
@@ -174,6 +237,19 @@ class YourMT3:
         c = DecodeConstraint(self, automaton)
         self._constraints.add(c)
         return c
+
+    def compile_detokenizer(self, task_manager, max_segments: int, max_steps: Optional[int] = None) -> Detokenizer:
+        """The device detokeniser for `task_manager`'s vocabulary (TaskManager.tokens_to_notes_device), with scratch for `max_segments`
+        segments of up to `max_steps` columns (None: the task's max_note_token_length, at most max_decode_len)."""
+        if task_manager.num_decoding_channels != self.cfg.n_channels:
+            raise ValueError("TaskManager channel count does not match the model's decoder")
+        if task_manager.vocab_size != self.cfg.vocab:
+            raise ValueError(f"TaskManager vocab {task_manager.vocab_size} != the model's {self.cfg.vocab}")
+        if max_steps is None:
+            max_steps = min(task_manager.max_note_token_length, self.cfg.max_decode_len)
+        d = Detokenizer(self, task_manager, max_segments, max_steps)
+        self._constraints.add(d)
+        return d
 
     def _start_states(self, constraint: Optional[DecodeConstraint], start_states, B: int) -> Optional[torch.Tensor]:
         """start_states -> (B, K) int32 device tensor, or None (state 0).  (K,) is every segment's; (B, K) per segment."""

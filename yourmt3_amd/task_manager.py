@@ -21,6 +21,10 @@ Confidences: with the token scores of YourMT3.inference(return_scores=True) (log
 scores), every onset event carries the score of its pitch or drum token and every note `confidence = exp(score)` of its
 onset.  Both fields are left out of comparisons, ordering and hashing: notes without scores are exactly what they were.
 
+Device path: `tokens_to_notes_device` is `tokens_to_notes` for ids that are still on the GPU (include/ymt3.h, device detokeniser;
+yourmt3_amd/csrc/detok.hip): the same notes, confidences and invalid-token count, one small copy back instead of a Python loop over
+every token.  The host path here stays the specification; `token_table()` is all the kernels know of the codec.
+
 Constraints: `event_automaton(programs)` is the grammar above as a token automaton (yourmt3_amd/constraint.py) for
 YourMT3.inference(constraint=...): the decoder then emits only well-formed segments whose notes belong to the allowed programs.
 """
@@ -37,6 +41,9 @@ from .vocab import Codec, Event, EOS, NUM_SPECIAL, PAD, UNK
 
 DRUM_PROGRAM = 128
 DRUM_NOTE_SEC = 0.01          # drums carry no offset: fixed nominal duration
+
+# token classes of TaskManager.token_table() (include/ymt3.h, device detokeniser): class << 12 | event value
+TOKEN_CLASSES = {"invalid": 0, "stop": 1, "skip": 2, "shift": 3, "pitch": 4, "velocity": 5, "tie": 6, "program": 7, "drum": 8}
 
 
 @dataclass(frozen=True, order=True)
@@ -361,3 +368,54 @@ class TaskManager:
             segs = self.detokenize_list_batches([np.asarray(a)[:, ch, :] for a in token_batches], start_secs, list_batch_score_arrays=sc)
             notes += note_events_to_notes(segs, end_sec)
         return sorted(notes)
+
+    def token_table(self) -> np.ndarray:
+        """(vocab_size,) uint16: TOKEN_CLASSES[class] << 12 | event value for every id, as decode_segment reads it: PAD / EOS stop,
+        the tokenizer's skip_ids (task tokens) skip, UNK and every id Codec.decode calls `special` invalid, events their type and value."""
+        table = np.zeros(self.vocab_size, np.uint16)
+        for i in range(self.vocab_size):
+            if i in (EOS, PAD):
+                cls, val = "stop", 0
+            elif i in self.tokenizer.skip_ids:
+                cls, val = "skip", 0
+            else:
+                ev = self.codec.decode(i)
+                cls, val = ("invalid", 0) if ev.type == "special" else (ev.type, ev.value)
+            if not 0 <= val < 4096:
+                raise ValueError(f"event value {val} of token {i} does not fit 12 bits")
+            table[i] = TOKEN_CLASSES[cls] << 12 | val
+        return table
+
+    def tokens_to_notes_device(self, model, tokens, start_secs: Sequence[float], end_sec: float, scores=None,
+                               detokenizer=None) -> Tuple[List[Note], int]:
+        """tokens_to_notes on the device -> (notes, n_invalid).  `tokens`: (n, K, L) integer ids on `model`'s GPU (any strides whose
+        last dimension is contiguous, e.g. hypothesis 0 of a beam call's (n, K, N, L)); `scores`: the matching (n, K, L) f32 token scores
+        or None; `start_secs` must be strictly increasing.  `detokenizer`: a YourMT3.compile_detokenizer object to reuse (None: one is
+        made for this call and closed).  One copy back of the counters and the notes' records; confidence = exp(score) on the host."""
+        import torch
+
+        starts = np.asarray(list(start_secs), np.float64)
+        if tokens.dim() != 3 or tokens.shape[1] != self.num_decoding_channels:
+            raise ValueError(f"tokens must be (n, {self.num_decoding_channels}, L), got {tuple(tokens.shape)}")
+        n, K, L = (int(v) for v in tokens.shape)
+        if starts.shape != (n,):
+            raise ValueError(f"{n} segments but {starts.size} start times")
+        if n > 1 and not bool(np.all(starts[1:] > starts[:-1])):
+            raise ValueError("start_secs must be strictly increasing")
+        if scores is not None and tuple(scores.shape) != tuple(tokens.shape):
+            raise ValueError(f"scores {tuple(scores.shape)} do not match tokens {tuple(tokens.shape)}")
+        if n == 0 or L == 0:
+            return [], 0
+        own = detokenizer is None
+        if own:
+            detokenizer = model.compile_detokenizer(self, n, L)
+        try:
+            rec, n_invalid = detokenizer.run(tokens, scores, torch.from_numpy(starts), float(end_sec))
+        finally:
+            if own:
+                detokenizer.close()
+        scored = scores is not None
+        notes = [Note(on, off, bool(dr), pg, pt, confidence=math.exp(sc) if scored else None)
+                 for on, off, pg, pt, dr, sc in zip(rec["onset"].tolist(), rec["offset"].tolist(), rec["program"].tolist(),
+                                                    rec["pitch"].tolist(), rec["is_drum"].tolist(), rec["score"].astype(np.float64).tolist())]
+        return sorted(notes), n_invalid

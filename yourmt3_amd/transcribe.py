@@ -18,7 +18,7 @@ def transcribe(model, audio_info: Union[str, dict, np.ndarray], task_manager: Op
                output_dir: str = ".", max_token_length: Optional[int] = None, return_notes: bool = False,
                continuous: bool = False, subtask: Optional[str] = None, confidence: bool = False,
                min_confidence: Optional[float] = None, constrained: bool = False, programs=None, num_beams: int = 1,
-               length_penalty: float = 1.0):
+               length_penalty: float = 1.0, device_detok: bool = False):
     """`continuous=True` decodes the file's segments through `bsz` slots with continuous batching
     (YourMT3.inference_stream: segments leave at EOS and the next ones enter) instead of fixed batches; same ids.
     `subtask`: for a task-conditioned TaskManager (e.g. "singing_drum_v1"), the sub-task whose task tokens prompt every
@@ -32,7 +32,9 @@ def transcribe(model, audio_info: Union[str, dict, np.ndarray], task_manager: Op
     `num_beams` > 1 decodes with beam search (include/ymt3.h, beam search; `length_penalty` as HF) and takes the best hypothesis of
     every (segment, channel); confidences are that hypothesis' token scores.  `bsz` still counts segments: the model needs
     max_batch >= bsz * num_beams.  Beams do not combine with `continuous=True` here yet: YourMT3.inference_stream(num_beams=...) is the
-    beam search under continuous batching, and routing this call to it is a two-line follow-up (existing tests pin the refusal)."""
+    beam search under continuous batching, and routing this call to it is a two-line follow-up (existing tests pin the refusal).
+    `device_detok=True` keeps the ids (and scores) on the GPU and turns them into notes there (TaskManager.tokens_to_notes_device;
+    include/ymt3.h, device detokeniser) in every mode above: the same notes and the same MIDI bytes, without the host's loop over every token."""
     num_beams = int(num_beams)
     if num_beams < 1:
         raise ValueError(f"num_beams={num_beams} must be >= 1")
@@ -79,11 +81,17 @@ def transcribe(model, audio_info: Union[str, dict, np.ndarray], task_manager: Op
     if num_beams > 1:
         kw.update(num_beams=num_beams, num_return_sequences=1, length_penalty=length_penalty)
     try:
-        batches, score_batches = _decode(model, segments, bsz, L, continuous, scored, kw)
+        if device_detok:
+            tokens, scores = _decode_device(model, segments, bsz, L, continuous, scored, kw)
+        else:
+            batches, score_batches = _decode(model, segments, bsz, L, continuous, scored, kw)
     finally:
         if constraint is not None:
             constraint.close()
-    notes = task_manager.tokens_to_notes(batches, start_secs, end_sec=n_samples / cfg.sample_rate, score_batches=score_batches)
+    if device_detok:
+        notes, _ = task_manager.tokens_to_notes_device(model, tokens, start_secs, n_samples / cfg.sample_rate, scores=scores)
+    else:
+        notes = task_manager.tokens_to_notes(batches, start_secs, end_sec=n_samples / cfg.sample_rate, score_batches=score_batches)
     if min_confidence is not None:
         notes = drop_low_confidence(notes, float(min_confidence))
     os.makedirs(output_dir, exist_ok=True)
@@ -107,3 +115,20 @@ def _decode(model, segments, bsz, L, continuous, scored, kw):
         else:
             batches, score_batches = out if scored else (out, None)
     return batches, score_batches
+
+
+def _decode_device(model, segments, bsz, L, continuous, scored, kw):
+    """_decode with everything left on the device -> ((n, K, L) ids, (n, K, L) scores or None); a beam call's (n, K, 1, L) is viewed
+    through hypothesis 0's strides, not copied."""
+    if continuous:
+        out = model.inference_stream(segments, max_token_length=L, slots=bsz, **kw)
+        tokens, scores = (out[0], out[1]) if scored else (out, None)
+    else:
+        step = max(1, min(int(bsz), model.max_batch))                   # inference_file's batches (its prompt and start states are per call here)
+        outs = [model.inference(segments[i:i + step], max_token_length=L, **kw) for i in range(0, segments.shape[0], step)]
+        tokens = torch.cat([o[0] if scored else o for o in outs], 0)
+        scores = torch.cat([o[1] for o in outs], 0) if scored else None
+    if kw.get("num_beams", 1) > 1:
+        tokens = tokens[:, :, 0]
+        scores = scores[:, :, 0] if scored else None
+    return tokens, scores
