@@ -30,7 +30,7 @@
  *     launched behind it unless a kernel gave up);
  *   - the library owns weights, KV caches and scratch inside the handle; nothing is
  *     allocated after ymt3_create() except by ymt3_constraint_create() (the caller's automaton tables) and
- *     ymt3_detok_create() (the device detokeniser's scratch);
+ *     ymt3_detok_create() (the device detokeniser's scratch) and ymt3_tok_create() (the device tokeniser's);
  *   - return value: 0 = ok, non-zero = error; the message is in ymt3_last_error()
  *     (thread local).  No exception ever crosses this boundary;
  *   - one handle per device per host thread.  No internal host threads.
@@ -386,6 +386,49 @@ int  ymt3_detokenize(ymt3_handle h, ymt3_detok d, const int32_t* tokens_dev, con
                      int n_segments, int n_steps, long long seg_stride, long long chan_stride,
                      const double* start_sec_dev, double end_sec,
                      void* notes_dev, long long capacity, int32_t* counts_dev /* [2]: n_notes, n_invalid */, void* stream);
+
+/* Device tokeniser: notes -> token ids without a host loop, the inverse of the device detokeniser (TaskManager.notes_to_tokens_device;
+ * the specification is the host path, TaskManager.notes_to_tokens of yourmt3_amd/task_manager.py, which it reproduces exactly: the same
+ * ids and the same lengths for every row that fits).
+ *   - params: all the kernels know of the codec -- the first id of each of the shift (value 1), pitch, velocity, tie, program and drum
+ *     ranges, max_shift_steps, steps_per_second, drum_program, and the EOS and PAD ids (TaskManager.tok_params).
+ *     program_channel_host[n_programs] uint8: the decoder channel of every program (TaskManager.channel_of_program).
+ *   - notes_dev: n_notes records of 32 bytes { f64 onset, f64 offset, i32 program, i32 pitch, i32 is_drum, f32 score }, the device
+ *     detokeniser's own record, 8-byte aligned, in any order; `score` is not read, so the output of ymt3_detokenize can be fed back
+ *     without touching the host.  A record with is_drum != 0 counts as program drum_program.  Dropped without an error: an onset
+ *     outside [start_sec[0], end_sec) or NaN, a NaN offset of a pitched note, a program outside [0, n_programs), a pitch outside
+ *     [0, 128) -- the host path raises for the last two; the Python wrapper checks a note list before it uploads it.
+ *   - start_sec_dev: (n_segments,) f64 start time of every segment.  It MUST be strictly increasing: the kernels search it and do not
+ *     check (the Python wrapper does, and raises ValueError).  Steps are rint((time - start_sec) * steps_per_second) in f64, that
+ *     subtract and that multiply, half to even; they saturate at 2^31 - 2.
+ *   - tokens_dev: (n_segments, n_channels, n_steps) int32, contiguous; every row is its ties, TIE, its events, EOS, then PAD.
+ *     lengths_dev: (n_segments, n_channels) int32, the tokens the row needs, EOS included.  A row that needs more than n_steps reports a
+ *     length > n_steps (a lower bound of the count when it has more than n_steps items or a gap of more than n_steps shifts) and
+ *     holds an unspecified prefix: the caller must look at the lengths before it uses the ids.
+ *   - kernels (yourmt3_amd/csrc/tok.hip): one lane per note finds its segments by binary search and appends one 64-bit item per event
+ *     and per tied boundary to the owning row (a tie only once per segment and key, through a bitmap); one wave per row sorts its items in LDS and
+ *     runs encode_segment as wave-level scans.
+ * ymt3_tok_create: synchronous, like ymt3_detok_create.  Checks (YMT3_ERR_ARG naming the argument): params and program_channel_host not
+ * NULL, n_programs >= 1, every id range inside [0, cfg.vocab), steps_per_second >= 1, max_shift_steps >= 1, drum_program in
+ * [0, n_programs), every channel below cfg.n_channels, max_segments >= 1, 1 <= max_steps <= min(max_decode_len, 4096); n_programs above
+ * 256 is YMT3_ERR_UNSUPPORTED.  Allocates all scratch: 8 bytes per output token of max_segments * n_channels * max_steps, a counter per
+ * row and 16 * n_programs bytes per segment.  The object belongs to h; ymt3_tok_destroy frees it (NULL is a no-op), before or after the
+ * handle's destruction.
+ * ymt3_tokenize: asynchronous on `stream`, allocates nothing, leaves the handle's decode state alone.  YMT3_ERR_ARG, with handle and
+ * tokeniser still usable, for n_segments > max_segments, n_steps outside [1, max_steps], n_notes outside [0, 2^29], a misaligned
+ * notes_dev, or NULL notes_dev (with n_notes > 0) / start_sec_dev / tokens_dev / lengths_dev.  n_notes = 0 gives TIE, EOS rows;
+ * n_segments = 0 is a no-op.  One object serves one call at a time. */
+typedef struct ymt3_tok_params {
+    int32_t shift_base, pitch_base, velocity_base, tie_base, program_base, drum_base;
+    int32_t max_shift_steps, steps_per_second, drum_program;
+    int32_t eos_id, pad_id;
+} ymt3_tok_params;
+typedef struct ymt3_tok_s* ymt3_tok;
+int  ymt3_tok_create(ymt3_handle h, const ymt3_tok_params* params, const uint8_t* program_channel_host, int n_programs,
+                     int max_segments, int max_steps, ymt3_tok* out);
+void ymt3_tok_destroy(ymt3_tok t);
+int  ymt3_tokenize(ymt3_handle h, ymt3_tok t, const void* notes_dev, long long n_notes, const double* start_sec_dev,
+                   int n_segments, double end_sec, int n_steps, int32_t* tokens_dev, int32_t* lengths_dev, void* stream);
 
 /* Measurement hook (bench.py `roofline`): decode eagerly (no graph) and bracket every kernel launch of
  * every `stride`-th step (positions stride/2, 3*stride/2, ...) with HIP events on `stream`; synchronises the stream before returning.

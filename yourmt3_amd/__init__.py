@@ -1,7 +1,7 @@
 """MI355X-native audio -> MIDI-token transcription path (see README.md / DESIGN.md).  Heavy imports are lazy so that
 `import yourmt3_amd` works without a GPU or the built library."""
 
-__all__ = ["YMT3Config", "YourMT3", "TaskManager", "transcribe", "baseline_config"]
+__all__ = ["YMT3Config", "YourMT3", "TaskManager", "transcribe", "score_notes", "baseline_config"]
 
 
 def __getattr__(name):
@@ -17,4 +17,7 @@ def __getattr__(name):
     if name == "transcribe":
         from .transcribe import transcribe
         return transcribe
+    if name == "score_notes":
+        from .transcribe import score_notes
+        return score_notes
     raise AttributeError(name)

@@ -25,6 +25,7 @@ SYMBOLS = [
     "ymt3_score_tokens", "ymt3_transcribe_segments_score",
     "ymt3_qkv0_table_active",
     "ymt3_detok_create", "ymt3_detok_destroy", "ymt3_detokenize",
+    "ymt3_tok_create", "ymt3_tok_destroy", "ymt3_tokenize",
 ]
 
 _lib = None
@@ -33,6 +34,12 @@ _lib = None
 class BeamParams(ctypes.Structure):
     """ymt3_beam_params of include/ymt3.h."""
     _fields_ = [("num_beams", ctypes.c_int32), ("num_return", ctypes.c_int32), ("length_penalty", ctypes.c_float)]
+
+
+class TokParams(ctypes.Structure):
+    """ymt3_tok_params of include/ymt3.h (TaskManager.tok_params gives the fields)."""
+    _fields_ = [(n, ctypes.c_int32) for n in ("shift_base", "pitch_base", "velocity_base", "tie_base", "program_base", "drum_base",
+                                              "max_shift_steps", "steps_per_second", "drum_program", "eos_id", "pad_id")]
 
 
 class YMT3Error(RuntimeError):
@@ -138,6 +145,12 @@ def load() -> ctypes.CDLL:
     lib.ymt3_detok_destroy.restype = None
     lib.ymt3_detokenize.argtypes = [vp, vp, vp, vp, i32, i32, ctypes.c_longlong, ctypes.c_longlong, vp, ctypes.c_double, vp, ctypes.c_longlong, vp, vp]
     lib.ymt3_detokenize.restype = i32
+    lib.ymt3_tok_create.argtypes = [vp, ctypes.POINTER(TokParams), vp, i32, i32, i32, ctypes.POINTER(vp)]
+    lib.ymt3_tok_create.restype = i32
+    lib.ymt3_tok_destroy.argtypes = [vp]
+    lib.ymt3_tok_destroy.restype = None
+    lib.ymt3_tokenize.argtypes = [vp, vp, vp, ctypes.c_longlong, vp, i32, ctypes.c_double, i32, vp, vp, vp]
+    lib.ymt3_tokenize.restype = i32
     for n in ("ymt3_logmel", "ymt3_encode", "ymt3_decode_greedy", "ymt3_transcribe_segments", "ymt3_test_gemm"):
         getattr(lib, n).restype = i32
     if lib.ymt3_abi_version() != 3:

@@ -59,6 +59,30 @@ struct DetokArgs {
 int init_detok_kernels();
 int launch_detok(const DetokArgs& a, hipStream_t stream);
 
+// ---------------------------------------------------------------- device tokeniser (tok.hip; include/ymt3.h, device tokeniser)
+constexpr int TOK_PITCHES = 128;          // pitch values per program: a tie key is program * 128 + pitch
+constexpr int TOK_MAX_PROGRAMS = 256;     // an item word gives the program 8 bits
+constexpr int TOK_MAX_STEPS = 4096;       // a row's items are sorted in LDS: 4096 * 8 B = 32 KB
+constexpr int TOK_MAX_SEGMENTS = 1 << 20;
+constexpr long long TOK_MAX_NOTES = 1LL << 29;   // a row's 32-bit counter takes at most two appends per note plus the ties
+struct TokArgs {
+    int shift_base, pitch_base, velocity_base, tie_base, program_base, drum_base;     // ymt3_tok_params
+    int max_shift_steps, steps_per_second, drum_program, eos_id, pad_id;
+    int n_programs;
+    const uint8_t* program_channel;       // [n_programs], every entry < n_chan
+    const DetokNote* notes;               // [n_notes] the detokeniser's record; `score` is not read
+    long long n_notes;
+    const double* start;                  // [n_seg] strictly increasing
+    double end_sec;
+    int n_seg, n_chan, L;
+    unsigned long long* items;            // [n_seg][n_chan][L] the rows' item words, in append order
+    int* row_count;                       // [n_seg][n_chan] items appended to the row (may exceed L); zeroed by launch_tok
+    unsigned* tie_seen;                   // [n_seg][n_programs * 4] one bit per (program, pitch) tied into the segment; zeroed by launch_tok
+    int32_t* tokens;                      // [n_seg][n_chan][L]
+    int32_t* lengths;                     // [n_seg][n_chan] tokens the row needs, EOS included (> L: overflow)
+};
+int launch_tok(const TokArgs& a, hipStream_t stream);
+
 // ---------------------------------------------------------------- dense GEMM (gemm.hip)
 // C[M][N] (+)= A[M][K] (bf16, row stride lda) * W[N][K]^T (bf16, row stride ldw), fp32 accumulate.
 enum GemmEpilogue {

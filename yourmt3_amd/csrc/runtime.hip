@@ -735,6 +735,97 @@ extern "C" int ymt3_detokenize(ymt3_handle h, ymt3_detok d, const int32_t* token
     return YMT3_OK;
 }
 
+// ---------------------------------------------------------------- device tokeniser (include/ymt3.h)
+struct ymt3_tok_s {
+    ymt3_ctx* owner;
+    int device;
+    ymt3_tok_params p;
+    int n_programs, max_segments, max_steps;
+    uint8_t* program_channel = nullptr;     // [n_programs]
+    unsigned long long* items = nullptr;    // [max_segments * n_channels * max_steps]
+    int* row_count = nullptr;               // [max_segments * n_channels]
+    unsigned* tie_seen = nullptr;           // [max_segments][n_programs * 4]
+};
+
+extern "C" void ymt3_tok_destroy(ymt3_tok t) {
+    if (!t) return;
+    (void)hipSetDevice(t->device);
+    for (void* p : {(void*)t->program_channel, (void*)t->items, (void*)t->row_count, (void*)t->tie_seen})
+        if (p) (void)hipFree(p);
+    delete t;
+}
+
+extern "C" int ymt3_tok_create(ymt3_handle h, const ymt3_tok_params* params, const uint8_t* program_channel_host, int n_programs, int max_segments,
+                               int max_steps, ymt3_tok* out) {
+    if (!out) FAIL(YMT3_ERR_ARG, "null output pointer");
+    *out = nullptr;
+    if (!h) FAIL(YMT3_ERR_ARG, "null handle");
+    if (!params) FAIL(YMT3_ERR_ARG, "params is NULL");
+    if (!program_channel_host) FAIL(YMT3_ERR_ARG, "program_channel_host is NULL");
+    const ymt3_tok_params& p = *params;
+    const int V = h->cfg.vocab;
+    if (n_programs < 1) FAIL(YMT3_ERR_ARG, "n_programs=%d must be >= 1", n_programs);
+    if (n_programs > TOK_MAX_PROGRAMS) FAIL(YMT3_ERR_UNSUPPORTED, "n_programs=%d: an item gives the program 8 bits, at most %d programs", n_programs, TOK_MAX_PROGRAMS);
+    if (p.steps_per_second < 1) FAIL(YMT3_ERR_ARG, "steps_per_second=%d must be >= 1", p.steps_per_second);
+    if (p.max_shift_steps < 1) FAIL(YMT3_ERR_ARG, "max_shift_steps=%d must be >= 1", p.max_shift_steps);
+    if (p.drum_program < 0 || p.drum_program >= n_programs) FAIL(YMT3_ERR_ARG, "drum_program=%d outside [0, n_programs=%d)", p.drum_program, n_programs);
+    const struct { const char* name; int base, size; } ranges[] = {
+        {"shift_base", p.shift_base, p.max_shift_steps}, {"pitch_base", p.pitch_base, TOK_PITCHES}, {"velocity_base", p.velocity_base, 2},
+        {"tie_base", p.tie_base, 1}, {"program_base", p.program_base, n_programs}, {"drum_base", p.drum_base, TOK_PITCHES},
+        {"eos_id", p.eos_id, 1}, {"pad_id", p.pad_id, 1}};
+    for (const auto& r : ranges)
+        if (r.base < 0 || (long long)r.base + r.size > V) FAIL(YMT3_ERR_ARG, "%s=%d: its %d ids do not fit the model's vocab=%d", r.name, r.base, r.size, V);
+    for (int i = 0; i < n_programs; ++i)
+        if (program_channel_host[i] >= h->cfg.n_channels)
+            FAIL(YMT3_ERR_ARG, "program_channel_host[%d]=%d outside [0, n_channels=%d)", i, (int)program_channel_host[i], h->cfg.n_channels);
+    if (max_segments < 1 || max_segments > TOK_MAX_SEGMENTS) FAIL(YMT3_ERR_ARG, "max_segments=%d outside [1, %d]", max_segments, TOK_MAX_SEGMENTS);
+    if (max_steps < 1 || max_steps > h->cfg.max_decode_len || max_steps > TOK_MAX_STEPS)
+        FAIL(YMT3_ERR_ARG, "max_steps=%d outside [1, max_decode_len=%d]", max_steps, std::min(h->cfg.max_decode_len, TOK_MAX_STEPS));
+    HIP_TRY(hipSetDevice(h->device));
+    ymt3_tok t = new ymt3_tok_s{h, h->device, p, n_programs, max_segments, max_steps};
+    const size_t rows = (size_t)max_segments * h->cfg.n_channels, slots = rows * max_steps;
+    const size_t seen = (size_t)max_segments * n_programs * (TOK_PITCHES / 8);
+    if (hipMalloc(reinterpret_cast<void**>(&t->program_channel), (size_t)n_programs) != hipSuccess ||
+        hipMalloc(reinterpret_cast<void**>(&t->items), slots * 8) != hipSuccess ||
+        hipMalloc(reinterpret_cast<void**>(&t->row_count), rows * sizeof(int)) != hipSuccess ||
+        hipMalloc(reinterpret_cast<void**>(&t->tie_seen), seen) != hipSuccess ||
+        hipMemcpy(t->program_channel, program_channel_host, (size_t)n_programs, hipMemcpyHostToDevice) != hipSuccess) {
+        ymt3_tok_destroy(t);
+        FAIL(YMT3_ERR_HIP, "tokeniser scratch (%zu bytes) could not be allocated", slots * 8 + rows * sizeof(int) + seen + n_programs);
+    }
+    *out = t;
+    return YMT3_OK;
+}
+
+extern "C" int ymt3_tokenize(ymt3_handle h, ymt3_tok t, const void* notes_dev, long long n_notes, const double* start_sec_dev, int n_segments,
+                             double end_sec, int n_steps, int32_t* tokens_dev, int32_t* lengths_dev, void* stream) {
+    if (!h) FAIL(YMT3_ERR_ARG, "null handle");
+    if (!t) FAIL(YMT3_ERR_ARG, "null tokeniser");
+    if (t->owner != h) FAIL(YMT3_ERR_ARG, "the tokeniser belongs to another handle");
+    if (n_segments < 0 || n_segments > t->max_segments) FAIL(YMT3_ERR_ARG, "n_segments=%d outside [0, max_segments=%d]", n_segments, t->max_segments);
+    if (n_steps < 1 || n_steps > t->max_steps) FAIL(YMT3_ERR_ARG, "n_steps=%d outside [1, max_steps=%d]", n_steps, t->max_steps);
+    if (n_notes < 0 || n_notes > TOK_MAX_NOTES) FAIL(YMT3_ERR_ARG, "n_notes=%lld outside [0, %lld]", n_notes, TOK_MAX_NOTES);
+    if (!n_segments) return YMT3_OK;
+    if (n_notes && !notes_dev) FAIL(YMT3_ERR_ARG, "notes_dev is NULL");
+    if (reinterpret_cast<uintptr_t>(notes_dev) % 8) FAIL(YMT3_ERR_ARG, "notes_dev is not aligned to 8 bytes");
+    if (!start_sec_dev) FAIL(YMT3_ERR_ARG, "start_sec_dev is NULL");
+    if (!tokens_dev) FAIL(YMT3_ERR_ARG, "tokens_dev is NULL");
+    if (!lengths_dev) FAIL(YMT3_ERR_ARG, "lengths_dev is NULL");
+    HIP_TRY(hipSetDevice(h->device));
+    const ymt3_tok_params& p = t->p;
+    TokArgs a{};
+    a.shift_base = p.shift_base; a.pitch_base = p.pitch_base; a.velocity_base = p.velocity_base; a.tie_base = p.tie_base;
+    a.program_base = p.program_base; a.drum_base = p.drum_base; a.max_shift_steps = p.max_shift_steps; a.steps_per_second = p.steps_per_second;
+    a.drum_program = p.drum_program; a.eos_id = p.eos_id; a.pad_id = p.pad_id;
+    a.n_programs = t->n_programs; a.program_channel = t->program_channel;
+    a.notes = static_cast<const DetokNote*>(notes_dev); a.n_notes = n_notes;
+    a.start = start_sec_dev; a.end_sec = end_sec; a.n_seg = n_segments; a.n_chan = h->cfg.n_channels; a.L = n_steps;
+    a.items = t->items; a.row_count = t->row_count; a.tie_seen = t->tie_seen;
+    a.tokens = tokens_dev; a.lengths = lengths_dev;
+    LAUNCH(launch_tok(a, static_cast<hipStream_t>(stream)));
+    return YMT3_OK;
+}
+
 // the kernels' view of a call's constraint (all null without one)
 static int constraint_view(ymt3_handle h, ymt3_constraint c, const int32_t* start_state_dev, ConstraintView* cv) {
     *cv = ConstraintView{};

@@ -121,6 +121,62 @@ class Detokenizer:
             pass
 
 
+class Tokenizer:
+    """The device tokeniser of one model for one TaskManager (YourMT3.compile_tokenizer; include/ymt3.h, device tokeniser): the codec's
+    parameter block, the program -> channel table and all scratch for up to `max_segments` segments of `max_steps` columns.  Freed by
+    close(), or by the model's close()."""
+
+    def __init__(self, model: "YourMT3", task_manager, max_segments: int, max_steps: int):
+        self.max_segments, self.max_steps = int(max_segments), int(max_steps)
+        self.n_channels = model.cfg.n_channels
+        self._model = weakref.ref(model)
+        self._lib = model._lib
+        self._c = ctypes.c_void_p()
+        fields, chan = task_manager.tok_params()
+        self.n_programs = int(chan.size)
+        params = _lib.TokParams(**fields)
+        chan = np.ascontiguousarray(chan, dtype=np.uint8)
+        _lib.check(self._lib.ymt3_tok_create(model._handle, ctypes.byref(params), chan.ctypes.data, self.n_programs, self.max_segments,
+                                             self.max_steps, ctypes.byref(self._c)))
+
+    @property
+    def ptr(self):
+        if not self._c.value:
+            raise ValueError("the tokenizer has been closed")
+        return self._c
+
+    def run(self, records: torch.Tensor, start_secs: torch.Tensor, end_sec: float, n_steps: Optional[int] = None):
+        """NOTE_RECORD bytes on the device (uint8, a multiple of 32), (n,) f64 strictly increasing start times -> (tokens (n, K, L)
+        int32, lengths (n, K) int32) on the device, L = n_steps or max_steps.  Asynchronous: nothing is copied back."""
+        model = self._model()
+        if model is None:
+            raise ValueError("the tokenizer's model is gone")
+        if records.dtype != torch.uint8 or records.dim() != 1 or records.numel() % NOTE_RECORD.itemsize:
+            raise ValueError(f"records must be a 1-D uint8 tensor of {NOTE_RECORD.itemsize}-byte NOTE_RECORDs")
+        records = records.to(model.device).contiguous()
+        if records.numel() and records.data_ptr() % 8:
+            records = records.clone()
+        starts = start_secs.to(model.device, torch.float64).contiguous()
+        n, L = int(starts.shape[0]), int(n_steps or self.max_steps)
+        tokens = torch.empty(n, self.n_channels, L, device=model.device, dtype=torch.int32)
+        lengths = torch.empty(n, self.n_channels, device=model.device, dtype=torch.int32)
+        n_notes = records.numel() // NOTE_RECORD.itemsize
+        _lib.check(self._lib.ymt3_tokenize(model._handle, self.ptr, _ptr(records) if n_notes else None, n_notes, _ptr(starts) if n else None, n,
+                                           float(end_sec), L, _ptr(tokens) if n else None, _ptr(lengths) if n else None, model._stream()))
+        return tokens, lengths
+
+    def close(self):
+        if getattr(self, "_c", None) is not None and self._c.value:
+            self._lib.ymt3_tok_destroy(self._c)
+            self._c = ctypes.c_void_p()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
 class YourMT3:
     def __init__(self, cfg: YMT3Config, weights: Optional[Dict[str, torch.Tensor]] = None, *, seed: int = 1234,
                  device: int = 0, max_batch: int = 64):
@@ -250,6 +306,19 @@ class YourMT3:
         d = Detokenizer(self, task_manager, max_segments, max_steps)
         self._constraints.add(d)
         return d
+
+    def compile_tokenizer(self, task_manager, max_segments: int, max_steps: Optional[int] = None) -> Tokenizer:
+        """The device tokeniser for `task_manager`'s vocabulary (TaskManager.notes_to_tokens_device), with scratch for `max_segments`
+        segments of up to `max_steps` columns (None: the task's max_note_token_length, at most max_decode_len)."""
+        if task_manager.num_decoding_channels != self.cfg.n_channels:
+            raise ValueError("TaskManager channel count does not match the model's decoder")
+        if task_manager.vocab_size != self.cfg.vocab:
+            raise ValueError(f"TaskManager vocab {task_manager.vocab_size} != the model's {self.cfg.vocab}")
+        if max_steps is None:
+            max_steps = min(task_manager.max_note_token_length, self.cfg.max_decode_len)
+        t = Tokenizer(self, task_manager, max_segments, max_steps)
+        self._constraints.add(t)
+        return t
 
     def _start_states(self, constraint: Optional[DecodeConstraint], start_states, B: int) -> Optional[torch.Tensor]:
         """start_states -> (B, K) int32 device tensor, or None (state 0).  (K,) is every segment's; (B, K) per segment."""

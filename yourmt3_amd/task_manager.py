@@ -369,6 +369,92 @@ class TaskManager:
             notes += note_events_to_notes(segs, end_sec)
         return sorted(notes)
 
+    def notes_to_tokens(self, notes: Sequence[Note], start_secs: Sequence[float], end_sec: float,
+                        max_len: Optional[int] = None) -> Tuple[np.ndarray, np.ndarray]:
+        """Notes -> (tokens (n, K, L) int32 PAD-filled, lengths (n, K) int32, EOS included): the inverse of tokens_to_notes and the
+        specification of the device tokeniser (notes_to_tokens_device; include/ymt3.h, device tokeniser).  L = max_len or
+        max_note_token_length; `start_secs` must be strictly increasing.  Rules:
+          - a note whose onset is not in [start_secs[0], end_sec) is dropped (so is one with a NaN onset, or a pitched one with a NaN
+            offset); a drum note counts as program DRUM_PROGRAM; the channel is channel_of_program(program);
+          - the onset belongs to the last segment s with start[s] <= onset, at step int(round((onset - start[s]) * steps_per_second))
+            (f64, half to even), and every event's time is the canonical start[s] + step / steps_per_second;
+          - a drum note is one onset event (velocity 1), no offset, no ties;
+          - a pitched note is in the tie section of every later segment s' with start[s'] < offset; a tie section lists a (program,
+            pitch) once;
+          - its offset event (velocity 0) goes to the segment that contains `offset`, except: offset >= end_sec gives none (the
+            detokeniser closes the note at end_sec), offset == start[s'] of a later segment gives none (the missing tie closes it
+            there), and an offset that would land in the onset's segment at or before the onset's step (or before that segment) is
+            placed at the onset's step + 1, even past the segment's nominal end: a note never loses its own onset;
+          - every (segment, channel) row is encode_segment(events, sorted(ties), start[s]); an empty row is TIE, EOS.
+        A row that needs more than L tokens raises ValueError naming the segment, the channel and the count.
+        Round trip: for notes on the 10 ms grid of their segment (onset and offset are start[s] + k / steps_per_second of the segment
+        they fall in, or offset == end_sec), with no two notes of one (program, pitch) overlapping, no duplicate drum hits, drum notes
+        of program DRUM_PROGRAM and DRUM_NOTE_SEC long, tokens_to_notes([notes_to_tokens(...)[0]], start_secs, end_sec) ==
+        sorted(notes), f64 times included.  Outside these preconditions the function still defines the ids."""
+        import bisect
+
+        starts = [float(s) for s in start_secs]
+        n, K = len(starts), self.num_decoding_channels
+        L = int(max_len or self.max_note_token_length)
+        if any(b <= a for a, b in zip(starts, starts[1:])):
+            raise ValueError("start_secs must be strictly increasing")
+        end_sec = float(end_sec)
+        sps = self.codec.steps_per_second
+        events: List[List[List[NoteEvent]]] = [[[] for _ in range(K)] for _ in range(n)]
+        ties: List[List[set]] = [[set() for _ in range(K)] for _ in range(n)]
+        time_of = lambda s, step: starts[s] + step / sps
+        for note in notes if n else ():
+            onset, offset = float(note.onset), float(note.offset)
+            if not (starts[0] <= onset < end_sec):
+                continue
+            prog = DRUM_PROGRAM if note.is_drum else int(note.program)
+            pitch = int(note.pitch)
+            ch = self.channel_of_program(prog)
+            s = bisect.bisect_right(starts, onset) - 1
+            step = int(round((onset - starts[s]) * sps))
+            if note.is_drum:
+                events[s][ch].append(NoteEvent(time_of(s, step), True, DRUM_PROGRAM, 1, pitch))
+                continue
+            if offset != offset:
+                continue
+            events[s][ch].append(NoteEvent(time_of(s, step), False, prog, 1, pitch))
+            for s2 in range(s + 1, n):
+                if not starts[s2] < offset:
+                    break
+                ties[s2][ch].add((prog, pitch))
+            if offset >= end_sec:
+                continue
+            so = bisect.bisect_right(starts, offset) - 1
+            if so <= s:
+                d = (offset - starts[s]) * sps
+                so, ostep = s, (int(round(d)) if d > step else step + 1)
+                if ostep <= step:
+                    ostep = step + 1
+            elif offset == starts[so]:
+                continue
+            else:
+                ostep = int(round((offset - starts[so]) * sps))
+            events[so][ch].append(NoteEvent(time_of(so, ostep), False, prog, 0, pitch))
+        tokens = np.full((n, K, L), PAD, np.int32)
+        lengths = np.zeros((n, K), np.int32)
+        for s in range(n):
+            for ch in range(K):
+                row = self.tokenizer.encode_segment(events[s][ch], sorted(ties[s][ch]), starts[s])
+                if len(row) > L:
+                    raise ValueError(f"segment {s} channel {ch} needs {len(row)} tokens > {L}")
+                tokens[s, ch, :len(row)] = row
+                lengths[s, ch] = len(row)
+        return tokens, lengths
+
+    def tok_params(self) -> Tuple[Dict[str, int], np.ndarray]:
+        """All the device tokeniser knows of the codec (include/ymt3.h, ymt3_tok_params): the first id of every event range, the
+        shift limit, the step rate, the drum program, EOS and PAD -> (fields, program -> channel (n_programs,) uint8)."""
+        c = self.codec
+        f = {t + "_base": c.range_of(t)[0] for t in ("shift", "pitch", "velocity", "tie", "program", "drum")}
+        f.update(max_shift_steps=c.max_shift_steps, steps_per_second=c.steps_per_second, drum_program=DRUM_PROGRAM, eos_id=EOS, pad_id=PAD)
+        n_prog = c.range_of("program")[1] - c.range_of("program")[0]
+        return f, np.array([self.channel_of_program(p) for p in range(n_prog)], np.uint8)
+
     def token_table(self) -> np.ndarray:
         """(vocab_size,) uint16: TOKEN_CLASSES[class] << 12 | event value for every id, as decode_segment reads it: PAD / EOS stop,
         the tokenizer's skip_ids (task tokens) skip, UNK and every id Codec.decode calls `special` invalid, events their type and value."""
@@ -419,3 +505,45 @@ class TaskManager:
                  for on, off, pg, pt, dr, sc in zip(rec["onset"].tolist(), rec["offset"].tolist(), rec["program"].tolist(),
                                                     rec["pitch"].tolist(), rec["is_drum"].tolist(), rec["score"].astype(np.float64).tolist())]
         return sorted(notes), n_invalid
+
+    def notes_to_tokens_device(self, model, notes, start_secs: Sequence[float], end_sec: float, max_len: Optional[int] = None,
+                               tokenizer=None):
+        """notes_to_tokens on the device -> (tokens (n, K, L) int32, lengths (n, K) int32) as tensors on `model`'s GPU.  `notes`: a
+        list of Note, or a uint8 tensor of NOTE_RECORD bytes already on the GPU (e.g. the records ymt3_detokenize wrote: nothing of
+        them touches the host).  `start_secs` must be strictly increasing.  `tokenizer`: a YourMT3.compile_tokenizer object to reuse
+        (None: one is made for this call and closed).  A note list is checked like the host path checks it (program and pitch inside
+        the codec's ranges, ValueError); records outside them are dropped on the device (include/ymt3.h, device tokeniser).  One copy
+        back of the lengths: a row that needs more than L tokens raises the host path's ValueError (its count is a lower bound when the
+        row has more than L events or a gap of more than L shift tokens)."""
+        import torch
+        from .model import NOTE_RECORD
+
+        starts = np.asarray(list(start_secs), np.float64)
+        n, K = int(starts.size), self.num_decoding_channels
+        L = int(max_len or self.max_note_token_length)
+        if n > 1 and not bool(np.all(starts[1:] > starts[:-1])):
+            raise ValueError("start_secs must be strictly increasing")
+        if isinstance(notes, torch.Tensor):
+            records = notes
+        else:
+            n_prog = self.codec.range_of("program")[1] - self.codec.range_of("program")[0]
+            rec = np.zeros(len(notes), NOTE_RECORD)
+            for i, nt in enumerate(notes):
+                prog = DRUM_PROGRAM if nt.is_drum else int(nt.program)
+                if not (0 <= prog < n_prog and 0 <= int(nt.pitch) < 128):
+                    raise ValueError(f"{nt}: program outside [0, {n_prog}) or pitch outside [0, 128)")
+                rec[i] = (nt.onset, nt.offset, prog, nt.pitch, bool(nt.is_drum), 0.0)
+            records = torch.from_numpy(rec.view(np.uint8).reshape(-1)).to(model.device)
+        own = tokenizer is None
+        if own:
+            tokenizer = model.compile_tokenizer(self, max(n, 1), L)
+        try:
+            tokens, lengths = tokenizer.run(records, torch.from_numpy(starts), float(end_sec), L)
+            over = (lengths > L).nonzero().cpu().tolist()
+            if over:
+                s, ch = over[0]
+                raise ValueError(f"segment {s} channel {ch} needs {int(lengths[s, ch])} tokens > {L}")
+        finally:
+            if own:
+                tokenizer.close()
+        return tokens, lengths

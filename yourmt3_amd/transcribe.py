@@ -10,7 +10,7 @@ import numpy as np
 import torch
 
 from .audio import load_wav_pcm
-from .midi import write_midi
+from .midi import read_midi_notes, write_midi
 from .task_manager import TaskManager, drop_low_confidence
 
 
@@ -132,3 +132,42 @@ def _decode_device(model, segments, bsz, L, continuous, scored, kw):
         tokens = tokens[:, :, 0]
         scores = scores[:, :, 0] if scored else None
     return tokens, scores
+
+
+def score_notes(model, audio_info: Union[str, dict, np.ndarray], notes, task_manager: Optional[TaskManager] = None, bsz: int = 8,
+                subtask: Optional[str] = None) -> dict:
+    """How likely are these notes for this audio: the teacher-forced log-likelihood of the notes' token ids (YourMT3.score; include/ymt3.h,
+    sequence scoring).  `audio_info` as transcribe(); `notes`: a list of Note, or the path of a .mid file (midi.read_midi_notes).  The audio is
+    ingested as transcribe() ingests it, the notes become ids on the device (TaskManager.notes_to_tokens_device; a row that does not fit
+    the task's max_note_token_length raises ValueError), and every batch of `bsz` segments is one model.score call, prompted with
+    `subtask`'s task tokens where the task has them; a row counts up to and including its EOS.  The MoE decoder is refused as
+    YourMT3.score refuses it.
+    -> {"log_likelihood": float, "segment_log_likelihood": (n, K) f64 array, "n_tokens": int (EOS included), "tokens": (n, K, L) int32 device tensor}"""
+    cfg = model.cfg
+    if task_manager is None:
+        task_manager = TaskManager("mc13_full_plus_256" if cfg.n_channels == 13 else "mt3_full_plus")
+    if task_manager.num_decoding_channels != cfg.n_channels:
+        raise ValueError("TaskManager channel count does not match the model's decoder")
+    if isinstance(audio_info, dict):
+        x, sr = load_wav_pcm(audio_info["filepath"])
+    elif isinstance(audio_info, str):
+        x, sr = load_wav_pcm(audio_info)
+    else:
+        x, sr = np.asarray(audio_info, dtype=np.float32), cfg.sample_rate
+    if isinstance(notes, (str, os.PathLike)):
+        with open(notes, "rb") as f:
+            notes = read_midi_notes(f.read())
+    segments = model.ingest(torch.from_numpy(np.ascontiguousarray(x)), sr)
+    n = int(segments.shape[0])
+    start_secs = [i * cfg.segment_samples / cfg.sample_rate for i in range(n)]
+    prompt = None
+    if task_manager.subtasks:
+        prompt = torch.tensor(task_manager.task_prompt(subtask, 1)[0, 0])
+    elif subtask is not None:
+        raise ValueError(f"task {task_manager.task_name!r} has no sub-tasks (asked for {subtask!r})")
+    L = min(task_manager.max_note_token_length, cfg.max_decode_len - (0 if prompt is None else int(prompt.numel())))
+    tokens, lengths = task_manager.notes_to_tokens_device(model, notes, start_secs, model.last_ingest_samples / cfg.sample_rate, max_len=L)
+    step = max(1, min(int(bsz), model.max_batch))
+    lls = [model.score(segments[i:i + step], tokens[i:i + step], task_tokens=prompt, lengths=lengths[i:i + step])[1] for i in range(0, n, step)]
+    seg_ll = torch.cat(lls, 0).cpu().numpy() if lls else np.zeros((0, cfg.n_channels), np.float64)
+    return {"log_likelihood": float(seg_ll.sum()), "segment_log_likelihood": seg_ll, "n_tokens": int(lengths.sum()), "tokens": tokens}
