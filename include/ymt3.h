@@ -30,7 +30,8 @@
  *     launched behind it unless a kernel gave up);
  *   - the library owns weights, KV caches and scratch inside the handle; nothing is
  *     allocated after ymt3_create() except by ymt3_constraint_create() (the caller's automaton tables) and
- *     ymt3_detok_create() (the device detokeniser's scratch) and ymt3_tok_create() (the device tokeniser's);
+ *     ymt3_detok_create() (the device detokeniser's scratch), ymt3_tok_create() (the device tokeniser's) and
+ *     ymt3_metrics_create() (the note metrics');
  *   - return value: 0 = ok, non-zero = error; the message is in ymt3_last_error()
  *     (thread local).  No exception ever crosses this boundary;
  *   - one handle per device per host thread.  No internal host threads.
@@ -429,6 +430,47 @@ int  ymt3_tok_create(ymt3_handle h, const ymt3_tok_params* params, const uint8_t
 void ymt3_tok_destroy(ymt3_tok t);
 int  ymt3_tokenize(ymt3_handle h, ymt3_tok t, const void* notes_dev, long long n_notes, const double* start_sec_dev,
                    int n_segments, double end_sec, int n_steps, int32_t* tokens_dev, int32_t* lengths_dev, void* stream);
+
+/* Device note metrics: how right is a transcription -- onset, onset+offset and drum F1 of an estimate against a reference, as integers
+ * (YourMT3.compile_note_metrics, evaluate(); the specification is the host path, note_metrics of yourmt3_amd/metrics.py, which it
+ * reproduces exactly: every integer of the result).  The rules are this repository's own, shaped after the usual note-transcription
+ * metric.  Both sides are records of 32 bytes { f64 onset, f64 offset, i32 program, i32 pitch, i32 is_drum, f32 score }, the device
+ * detokeniser's own record, 8-byte aligned, in any order; `score` is not read.
+ *   - counted records: the onset is not NaN, the pitch lies in [0, 128), the effective program p lies in [0, n_programs) -- p =
+ *     drum_program if is_drum != 0, else program: the drum rule of the tokeniser -- and, if the note is pitched, the offset is not NaN.  A
+ *     record with p == drum_program is a drum note whatever is_drum says; every other counted record is pitched.  The other records are
+ *     skipped and appear in skipped[] only.
+ *   - distance rounding: d(a, b) = rint(|a - b| * 1e4) / 1e4 in f64, that subtract, multiply, round-half-even and divide, nothing
+ *     contracted (times are start + step / 100, and |1.05 - 1.00| exceeds 0.05 in f64: with the rule, 50 ms apart on the grid hits).
+ *   - hits of reference i and estimate j of one key: onset, d(on_i, on_j) <= onset_tol; onset+offset, the onset hit and d(off_i, off_j) <=
+ *     max(offset_min_tol, offset_ratio * (off_i - on_i)), the tolerance not rounded.  Drum notes never look at offsets: their
+ *     onset+offset numbers equal their onset numbers.
+ *   - counts_dev: [(n_programs + 1) * 6 + 2] int32 = counts[row][metric][3] then skipped[2]; metric 0 onset, 1 onset+offset; the three are
+ *     TP, n_ref, n_est; skipped = (ref, est) records not counted.  Row p < n_programs is instrument-aware: the notes of effective program
+ *     p, matched only under the same pitch.  Row n_programs is instrument-agnostic: all pitched notes, keyed by pitch alone (drums have
+ *     only their own row).  TP is the size of a MAXIMUM one-to-one matching of the hit graph, which is unique.
+ *   - count pointers: ref_count_dev / est_count_dev (each may be NULL) are read ON THE DEVICE: the side then has min(n, max(*count, 0))
+ *     records, and n only sizes the launches.  counts_dev[0] and notes_dev of ymt3_detokenize are an estimate in place: the host need
+ *     not know how many notes were transcribed before the metrics are done.
+ *   - kernels (yourmt3_amd/csrc/metrics.hip): one lane per record keys it and counts its keys; a scan and a scatter bucket the records'
+ *     times by key; one wave per key sorts both buckets by onset, matches onsets with a two-pointer walk (a maximum matching, the hit
+ *     intervals being monotone) and onset+offset by augmenting paths over an explicit stack.  No kernel waits on another workgroup and
+ *     every search ends on any input; the cost is cubic in the notes of ONE key that lie within one onset window of each other.
+ * ymt3_metrics_create: synchronous, like ymt3_detok_create; allocates all scratch (64 bytes per note of max_ref, 48 per note of max_est,
+ * 24 per key).  Checks (YMT3_ERR_ARG naming the argument): params not NULL, the three tolerances finite and >= 0, n_programs >= 1,
+ * drum_program in [0, n_programs), max_ref and max_est in [1, 2^24]; n_programs above 256 is YMT3_ERR_UNSUPPORTED.  The object belongs
+ * to h; ymt3_metrics_destroy frees it (NULL is a no-op), before or after the handle's destruction.
+ * ymt3_note_metrics: asynchronous on `stream`, allocates nothing, zeroes counts_dev first, leaves the handle's decode state alone.
+ * YMT3_ERR_ARG, with handle and object still usable, for n_ref outside [0, max_ref], n_est outside [0, max_est], NULL counts_dev, or a
+ * NULL or misaligned record pointer of a side with n > 0.  Either side may be empty.  One object serves one call at a time. */
+typedef struct ymt3_metrics_params { double onset_tol, offset_min_tol, offset_ratio; int32_t n_programs, drum_program; } ymt3_metrics_params;
+typedef struct ymt3_metrics_s* ymt3_metrics;
+int  ymt3_metrics_create(ymt3_handle h, const ymt3_metrics_params* p, long long max_ref, long long max_est, ymt3_metrics* out);
+void ymt3_metrics_destroy(ymt3_metrics m);
+int  ymt3_note_metrics(ymt3_handle h, ymt3_metrics m,
+                       const void* ref_notes_dev, long long n_ref, const int32_t* ref_count_dev /* may be NULL */,
+                       const void* est_notes_dev, long long n_est, const int32_t* est_count_dev /* may be NULL */,
+                       int32_t* counts_dev /* [(n_programs + 1) * 6 + 2] */, void* stream);
 
 /* Measurement hook (bench.py `roofline`): decode eagerly (no graph) and bracket every kernel launch of
  * every `stride`-th step (positions stride/2, 3*stride/2, ...) with HIP events on `stream`; synchronises the stream before returning.

@@ -1,7 +1,7 @@
 """MI355X-native audio -> MIDI-token transcription path (see README.md / DESIGN.md).  Heavy imports are lazy so that
 `import yourmt3_amd` works without a GPU or the built library."""
 
-__all__ = ["YMT3Config", "YourMT3", "TaskManager", "transcribe", "score_notes", "baseline_config"]
+__all__ = ["YMT3Config", "YourMT3", "TaskManager", "transcribe", "score_notes", "evaluate", "note_metrics", "NoteMetrics", "baseline_config"]
 
 
 def __getattr__(name):
@@ -20,4 +20,13 @@ def __getattr__(name):
     if name == "score_notes":
         from .transcribe import score_notes
         return score_notes
+    if name == "evaluate":
+        from .transcribe import evaluate
+        return evaluate
+    if name == "note_metrics":
+        from .metrics import note_metrics
+        return note_metrics
+    if name == "NoteMetrics":
+        from .model import NoteMetrics
+        return NoteMetrics
     raise AttributeError(name)

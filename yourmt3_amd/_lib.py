@@ -26,6 +26,7 @@ SYMBOLS = [
     "ymt3_qkv0_table_active",
     "ymt3_detok_create", "ymt3_detok_destroy", "ymt3_detokenize",
     "ymt3_tok_create", "ymt3_tok_destroy", "ymt3_tokenize",
+    "ymt3_metrics_create", "ymt3_metrics_destroy", "ymt3_note_metrics",
 ]
 
 _lib = None
@@ -40,6 +41,12 @@ class TokParams(ctypes.Structure):
     """ymt3_tok_params of include/ymt3.h (TaskManager.tok_params gives the fields)."""
     _fields_ = [(n, ctypes.c_int32) for n in ("shift_base", "pitch_base", "velocity_base", "tie_base", "program_base", "drum_base",
                                               "max_shift_steps", "steps_per_second", "drum_program", "eos_id", "pad_id")]
+
+
+class MetricsParams(ctypes.Structure):
+    """ymt3_metrics_params of include/ymt3.h"""
+    _fields_ = [("onset_tol", ctypes.c_double), ("offset_min_tol", ctypes.c_double), ("offset_ratio", ctypes.c_double),
+                ("n_programs", ctypes.c_int32), ("drum_program", ctypes.c_int32)]
 
 
 class YMT3Error(RuntimeError):
@@ -151,6 +158,12 @@ def load() -> ctypes.CDLL:
     lib.ymt3_tok_destroy.restype = None
     lib.ymt3_tokenize.argtypes = [vp, vp, vp, ctypes.c_longlong, vp, i32, ctypes.c_double, i32, vp, vp, vp]
     lib.ymt3_tokenize.restype = i32
+    lib.ymt3_metrics_create.argtypes = [vp, ctypes.POINTER(MetricsParams), ctypes.c_longlong, ctypes.c_longlong, ctypes.POINTER(vp)]
+    lib.ymt3_metrics_create.restype = i32
+    lib.ymt3_metrics_destroy.argtypes = [vp]
+    lib.ymt3_metrics_destroy.restype = None
+    lib.ymt3_note_metrics.argtypes = [vp, vp, vp, ctypes.c_longlong, vp, vp, ctypes.c_longlong, vp, vp, vp]
+    lib.ymt3_note_metrics.restype = i32
     for n in ("ymt3_logmel", "ymt3_encode", "ymt3_decode_greedy", "ymt3_transcribe_segments", "ymt3_test_gemm"):
         getattr(lib, n).restype = i32
     if lib.ymt3_abi_version() != 3:

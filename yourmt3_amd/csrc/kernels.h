@@ -83,6 +83,32 @@ struct TokArgs {
 };
 int launch_tok(const TokArgs& a, hipStream_t stream);
 
+// ---------------------------------------------------------------- device note metrics (metrics.hip; include/ymt3.h, note metrics)
+constexpr int METRICS_PITCHES = 128;               // a key is row * 128 + pitch; row n_programs holds the instrument-agnostic keys
+constexpr int METRICS_MAX_PROGRAMS = 256;
+constexpr long long METRICS_MAX_NOTES = 1LL << 24; // per side; a counted note fills at most two bucket slots
+struct MetricsArgs {
+    double onset_tol, offset_min_tol, offset_ratio;
+    int n_programs, drum_program;
+    const DetokNote* ref;                 // [n_ref] the detokeniser's record; `score` is not read
+    const DetokNote* est;                 // [n_est]
+    long long n_ref, n_est;               // the launches' sizes
+    const int32_t* ref_count;             // device counts (or null): the side has min(n, max(*count, 0)) records
+    const int32_t* est_count;
+    long long max_ref, max_est;           // what the scratch below was sized for
+    unsigned* hist;                       // [2][n_keys] records per key and side; zeroed by launch_metrics
+    unsigned* off;                        // [2][n_keys + 1] first bucket slot of every key, then the total
+    unsigned* cursor;                     // [2][n_keys] next free slot of every bucket
+    double2* t_ref;                       // [2 * max_ref] (onset, offset) bucketed by key
+    double2* t_est;                       // [2 * max_est]
+    int2* win;                            // [2 * max_ref] per reference slot: the interval of estimates it can hit by onset
+    int2* stack;                          // [2 * max_ref] the search's frames: (reference, next candidate)
+    int* match;                           // [2 * max_est] per estimate slot: the reference it is matched to, or -1
+    int* visit;                           // [2 * max_est] the root of the last search that visited it
+    int32_t* counts;                      // [(n_programs + 1) * 6 + 2]; zeroed by launch_metrics
+};
+int launch_metrics(const MetricsArgs& a, hipStream_t stream);
+
 // ---------------------------------------------------------------- dense GEMM (gemm.hip)
 // C[M][N] (+)= A[M][K] (bf16, row stride lda) * W[N][K]^T (bf16, row stride ldw), fp32 accumulate.
 enum GemmEpilogue {

@@ -826,6 +826,86 @@ extern "C" int ymt3_tokenize(ymt3_handle h, ymt3_tok t, const void* notes_dev, l
     return YMT3_OK;
 }
 
+// ---------------------------------------------------------------- device note metrics (include/ymt3.h)
+struct ymt3_metrics_s {
+    ymt3_ctx* owner;
+    int device;
+    ymt3_metrics_params p;
+    long long max_ref, max_est;
+    unsigned* hist = nullptr;               // [2][n_keys], then off [2][n_keys + 1] and cursor [2][n_keys]: one allocation
+    double2* t_ref = nullptr;               // [2 * max_ref]
+    double2* t_est = nullptr;               // [2 * max_est]
+    int2* win = nullptr;                    // [2 * max_ref], then stack [2 * max_ref]: one allocation
+    int* match = nullptr;                   // [2 * max_est], then visit [2 * max_est]: one allocation
+};
+
+extern "C" void ymt3_metrics_destroy(ymt3_metrics m) {
+    if (!m) return;
+    (void)hipSetDevice(m->device);
+    for (void* p : {(void*)m->hist, (void*)m->t_ref, (void*)m->t_est, (void*)m->win, (void*)m->match})
+        if (p) (void)hipFree(p);
+    delete m;
+}
+
+extern "C" int ymt3_metrics_create(ymt3_handle h, const ymt3_metrics_params* params, long long max_ref, long long max_est, ymt3_metrics* out) {
+    if (!out) FAIL(YMT3_ERR_ARG, "null output pointer");
+    *out = nullptr;
+    if (!h) FAIL(YMT3_ERR_ARG, "null handle");
+    if (!params) FAIL(YMT3_ERR_ARG, "params is NULL");
+    const ymt3_metrics_params& p = *params;
+    if (!std::isfinite(p.onset_tol) || p.onset_tol < 0) FAIL(YMT3_ERR_ARG, "onset_tol=%g must be finite and >= 0", p.onset_tol);
+    if (!std::isfinite(p.offset_min_tol) || p.offset_min_tol < 0) FAIL(YMT3_ERR_ARG, "offset_min_tol=%g must be finite and >= 0", p.offset_min_tol);
+    if (!std::isfinite(p.offset_ratio) || p.offset_ratio < 0) FAIL(YMT3_ERR_ARG, "offset_ratio=%g must be finite and >= 0", p.offset_ratio);
+    if (p.n_programs < 1) FAIL(YMT3_ERR_ARG, "n_programs=%d must be >= 1", p.n_programs);
+    if (p.n_programs > METRICS_MAX_PROGRAMS) FAIL(YMT3_ERR_UNSUPPORTED, "n_programs=%d: at most %d programs", p.n_programs, METRICS_MAX_PROGRAMS);
+    if (p.drum_program < 0 || p.drum_program >= p.n_programs) FAIL(YMT3_ERR_ARG, "drum_program=%d outside [0, n_programs=%d)", p.drum_program, p.n_programs);
+    if (max_ref < 1 || max_ref > METRICS_MAX_NOTES) FAIL(YMT3_ERR_ARG, "max_ref=%lld outside [1, %lld]", max_ref, METRICS_MAX_NOTES);
+    if (max_est < 1 || max_est > METRICS_MAX_NOTES) FAIL(YMT3_ERR_ARG, "max_est=%lld outside [1, %lld]", max_est, METRICS_MAX_NOTES);
+    HIP_TRY(hipSetDevice(h->device));
+    ymt3_metrics m = new ymt3_metrics_s{h, h->device, p, max_ref, max_est};
+    const size_t nk = (size_t)(p.n_programs + 1) * METRICS_PITCHES, keys_bytes = (2 * nk + 2 * (nk + 1) + 2 * nk) * sizeof(unsigned);
+    const size_t rs = 2 * (size_t)max_ref, es = 2 * (size_t)max_est;       // bucket slots: a counted note fills at most two
+    if (hipMalloc(reinterpret_cast<void**>(&m->hist), keys_bytes) != hipSuccess ||
+        hipMalloc(reinterpret_cast<void**>(&m->t_ref), rs * sizeof(double2)) != hipSuccess ||
+        hipMalloc(reinterpret_cast<void**>(&m->t_est), es * sizeof(double2)) != hipSuccess ||
+        hipMalloc(reinterpret_cast<void**>(&m->win), 2 * rs * sizeof(int2)) != hipSuccess ||
+        hipMalloc(reinterpret_cast<void**>(&m->match), 2 * es * sizeof(int)) != hipSuccess) {
+        ymt3_metrics_destroy(m);
+        FAIL(YMT3_ERR_HIP, "note metrics scratch (%zu bytes) could not be allocated", keys_bytes + rs * 32 + es * 24);
+    }
+    *out = m;
+    return YMT3_OK;
+}
+
+extern "C" int ymt3_note_metrics(ymt3_handle h, ymt3_metrics m, const void* ref_notes_dev, long long n_ref, const int32_t* ref_count_dev,
+                                 const void* est_notes_dev, long long n_est, const int32_t* est_count_dev, int32_t* counts_dev, void* stream) {
+    if (!h) FAIL(YMT3_ERR_ARG, "null handle");
+    if (!m) FAIL(YMT3_ERR_ARG, "null metrics object");
+    if (m->owner != h) FAIL(YMT3_ERR_ARG, "the metrics object belongs to another handle");
+    if (n_ref < 0 || n_ref > m->max_ref) FAIL(YMT3_ERR_ARG, "n_ref=%lld outside [0, max_ref=%lld]", n_ref, m->max_ref);
+    if (n_est < 0 || n_est > m->max_est) FAIL(YMT3_ERR_ARG, "n_est=%lld outside [0, max_est=%lld]", n_est, m->max_est);
+    if (!counts_dev) FAIL(YMT3_ERR_ARG, "counts_dev is NULL");
+    if (n_ref && !ref_notes_dev) FAIL(YMT3_ERR_ARG, "ref_notes_dev is NULL");
+    if (n_ref && reinterpret_cast<uintptr_t>(ref_notes_dev) % 8) FAIL(YMT3_ERR_ARG, "ref_notes_dev is not aligned to 8 bytes");
+    if (n_est && !est_notes_dev) FAIL(YMT3_ERR_ARG, "est_notes_dev is NULL");
+    if (n_est && reinterpret_cast<uintptr_t>(est_notes_dev) % 8) FAIL(YMT3_ERR_ARG, "est_notes_dev is not aligned to 8 bytes");
+    HIP_TRY(hipSetDevice(h->device));
+    const size_t nk = (size_t)(m->p.n_programs + 1) * METRICS_PITCHES;
+    MetricsArgs a{};
+    a.onset_tol = m->p.onset_tol; a.offset_min_tol = m->p.offset_min_tol; a.offset_ratio = m->p.offset_ratio;
+    a.n_programs = m->p.n_programs; a.drum_program = m->p.drum_program;
+    a.ref = static_cast<const DetokNote*>(ref_notes_dev); a.est = static_cast<const DetokNote*>(est_notes_dev);
+    a.n_ref = n_ref; a.n_est = n_est; a.ref_count = n_ref ? ref_count_dev : nullptr; a.est_count = n_est ? est_count_dev : nullptr;
+    a.max_ref = m->max_ref; a.max_est = m->max_est;
+    a.hist = m->hist; a.off = m->hist + 2 * nk; a.cursor = a.off + 2 * (nk + 1);
+    a.t_ref = m->t_ref; a.t_est = m->t_est;
+    a.win = m->win; a.stack = m->win + 2 * (size_t)m->max_ref;
+    a.match = m->match; a.visit = m->match + 2 * (size_t)m->max_est;
+    a.counts = counts_dev;
+    LAUNCH(launch_metrics(a, static_cast<hipStream_t>(stream)));
+    return YMT3_OK;
+}
+
 // the kernels' view of a call's constraint (all null without one)
 static int constraint_view(ymt3_handle h, ymt3_constraint c, const int32_t* start_state_dev, ConstraintView* cv) {
     *cv = ConstraintView{};

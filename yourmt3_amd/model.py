@@ -19,7 +19,7 @@ from . import _lib
 from .config import YMT3Config, to_c
 from .constraint import TokenAutomaton
 from .tables import derived_tables
-from .task_manager import DRUM_PROGRAM
+from .task_manager import DRUM_PROGRAM, NOTE_RECORD
 from .weights import make_weights, pack_blob
 
 
@@ -59,9 +59,6 @@ class DecodeConstraint:
             pass
 
 
-NOTE_RECORD = np.dtype([("onset", "<f8"), ("offset", "<f8"), ("program", "<i4"), ("pitch", "<i4"), ("is_drum", "<i4"), ("score", "<f4")])
-
-
 class Detokenizer:
     """The device detokeniser of one model for one TaskManager (YourMT3.compile_detokenizer; include/ymt3.h, device detokeniser): the
     token table and all scratch for up to `max_segments` segments of `max_steps` columns.  Freed by close(), or by the model's close()."""
@@ -87,6 +84,15 @@ class Detokenizer:
 
     def run(self, tokens: torch.Tensor, scores: Optional[torch.Tensor], start_secs: torch.Tensor, end_sec: float):
         """(n, K, L) ids (+ scores) on the device, (n,) f64 strictly increasing start times -> (records: NOTE_RECORD array, n_invalid)."""
+        notes, counts = self.run_device(tokens, scores, start_secs, end_sec)
+        n_notes, n_invalid = (int(v) for v in counts.cpu().tolist())
+        rec = notes[:n_notes * NOTE_RECORD.itemsize].cpu().numpy().view(NOTE_RECORD)
+        return rec, n_invalid
+
+    def run_device(self, tokens: torch.Tensor, scores: Optional[torch.Tensor], start_secs: torch.Tensor, end_sec: float):
+        """run() without the copy back -> (records: uint8 tensor of `capacity` NOTE_RECORDs, counts: int32 tensor [n_notes, n_invalid]),
+        both on the device and both the detokeniser's own buffers: the next call overwrites them.  Asynchronous; the first n_notes records
+        are valid, which NoteMetrics.run reads from `counts` on the device."""
         model = self._model()
         if model is None:
             raise ValueError("the detokenizer's model is gone")
@@ -104,9 +110,7 @@ class Detokenizer:
         _lib.check(self._lib.ymt3_detokenize(model._handle, self.ptr, _ptr(tokens), _ptr(scores), n, L, tokens.stride(0), tokens.stride(1),
                                              _ptr(starts), float(end_sec), _ptr(self._notes), self.capacity, _ptr(self._counts),
                                              model._stream()))
-        n_notes, n_invalid = (int(v) for v in self._counts.cpu().tolist())
-        rec = self._notes[:n_notes * NOTE_RECORD.itemsize].cpu().numpy().view(NOTE_RECORD)
-        return rec, n_invalid
+        return self._notes, self._counts
 
     def close(self):
         if getattr(self, "_c", None) is not None and self._c.value:
@@ -168,6 +172,66 @@ class Tokenizer:
     def close(self):
         if getattr(self, "_c", None) is not None and self._c.value:
             self._lib.ymt3_tok_destroy(self._c)
+            self._c = ctypes.c_void_p()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+class NoteMetrics:
+    """The device note metrics of one model (YourMT3.compile_note_metrics; include/ymt3.h, note metrics; the rules and the host
+    specification: yourmt3_amd/metrics.py): the parameters and all scratch for up to `max_ref` reference and `max_est` estimated notes.
+    Freed by close(), or by the model's close()."""
+
+    def __init__(self, model: "YourMT3", n_programs: int, max_ref: int, max_est: int, drum_program: int = DRUM_PROGRAM, onset_tol: float = 0.05,
+                 offset_min_tol: float = 0.05, offset_ratio: float = 0.2):
+        self.n_programs, self.drum_program = int(n_programs), int(drum_program)
+        self.max_ref, self.max_est = int(max_ref), int(max_est)
+        self._model = weakref.ref(model)
+        self._lib = model._lib
+        self._c = ctypes.c_void_p()
+        params = _lib.MetricsParams(float(onset_tol), float(offset_min_tol), float(offset_ratio), self.n_programs, self.drum_program)
+        _lib.check(self._lib.ymt3_metrics_create(model._handle, ctypes.byref(params), self.max_ref, self.max_est, ctypes.byref(self._c)))
+
+    @property
+    def ptr(self):
+        if not self._c.value:
+            raise ValueError("the note metrics object has been closed")
+        return self._c
+
+    def run(self, ref_records: torch.Tensor, est_records: torch.Tensor, ref_count: Optional[torch.Tensor] = None,
+            est_count: Optional[torch.Tensor] = None) -> torch.Tensor:
+        """NOTE_RECORD bytes on the device (uint8, a multiple of 32) for both sides -> the ((n_programs + 1) * 6 + 2,) int32 counts tensor on
+        the device (metrics.NoteMetricCounts.from_flat reads it).  `ref_count` / `est_count`: int32 device tensors whose FIRST element is
+        the side's number of records, read on the device (a Detokenizer.run_device counts tensor as it is); the tensor's size is then only the
+        buffer's capacity.  Asynchronous: nothing is copied back."""
+        model = self._model()
+        if model is None:
+            raise ValueError("the note metrics object's model is gone")
+        sides = []
+        for name, rec, cnt in (("ref", ref_records, ref_count), ("est", est_records, est_count)):
+            if rec.dtype != torch.uint8 or rec.dim() != 1 or rec.numel() % NOTE_RECORD.itemsize:
+                raise ValueError(f"{name}_records must be a 1-D uint8 tensor of {NOTE_RECORD.itemsize}-byte NOTE_RECORDs")
+            rec = rec.to(model.device).contiguous()
+            if rec.numel() and rec.data_ptr() % 8:
+                rec = rec.clone()
+            if cnt is not None:
+                if cnt.dtype != torch.int32 or not cnt.numel():
+                    raise ValueError(f"{name}_count must be an int32 tensor")
+                cnt = cnt.to(model.device)
+            sides.append((rec, rec.numel() // NOTE_RECORD.itemsize, cnt))
+        counts = torch.empty((self.n_programs + 1) * 6 + 2, device=model.device, dtype=torch.int32)
+        (r, nr, rc), (e, ne, ec) = sides
+        _lib.check(self._lib.ymt3_note_metrics(model._handle, self.ptr, _ptr(r) if nr else None, nr, _ptr(rc), _ptr(e) if ne else None, ne, _ptr(ec),
+                                               _ptr(counts), model._stream()))
+        return counts
+
+    def close(self):
+        if getattr(self, "_c", None) is not None and self._c.value:
+            self._lib.ymt3_metrics_destroy(self._c)
             self._c = ctypes.c_void_p()
 
     def __del__(self):
@@ -319,6 +383,14 @@ class YourMT3:
         t = Tokenizer(self, task_manager, max_segments, max_steps)
         self._constraints.add(t)
         return t
+
+    def compile_note_metrics(self, n_programs: int, max_ref: int, max_est: int, **tolerances) -> NoteMetrics:
+        """The device note metrics (include/ymt3.h, note metrics) for records of `n_programs` programs, with scratch for up to `max_ref`
+        reference and `max_est` estimated notes.  `tolerances`: drum_program, onset_tol, offset_min_tol, offset_ratio (metrics.note_metrics'
+        defaults)."""
+        m = NoteMetrics(self, n_programs, max_ref, max_est, **tolerances)
+        self._constraints.add(m)
+        return m
 
     def _start_states(self, constraint: Optional[DecodeConstraint], start_states, B: int) -> Optional[torch.Tensor]:
         """start_states -> (B, K) int32 device tensor, or None (state 0).  (K,) is every segment's; (B, K) per segment."""

@@ -41,6 +41,8 @@ from .vocab import Codec, Event, EOS, NUM_SPECIAL, PAD, UNK
 
 DRUM_PROGRAM = 128
 DRUM_NOTE_SEC = 0.01          # drums carry no offset: fixed nominal duration
+# the 32-byte note record of the device codec and the device metrics (include/ymt3.h)
+NOTE_RECORD = np.dtype([("onset", "<f8"), ("offset", "<f8"), ("program", "<i4"), ("pitch", "<i4"), ("is_drum", "<i4"), ("score", "<f4")])
 
 # token classes of TaskManager.token_table() (include/ymt3.h, device detokeniser): class << 12 | event value
 TOKEN_CLASSES = {"invalid": 0, "stop": 1, "skip": 2, "shift": 3, "pitch": 4, "velocity": 5, "tie": 6, "program": 7, "drum": 8}

@@ -11,6 +11,7 @@ import torch
 
 from .audio import load_wav_pcm
 from .midi import read_midi_notes, write_midi
+from .metrics import NoteMetricCounts, to_records
 from .task_manager import TaskManager, drop_low_confidence
 
 
@@ -171,3 +172,70 @@ def score_notes(model, audio_info: Union[str, dict, np.ndarray], notes, task_man
     lls = [model.score(segments[i:i + step], tokens[i:i + step], task_tokens=prompt, lengths=lengths[i:i + step])[1] for i in range(0, n, step)]
     seg_ll = torch.cat(lls, 0).cpu().numpy() if lls else np.zeros((0, cfg.n_channels), np.float64)
     return {"log_likelihood": float(seg_ll.sum()), "segment_log_likelihood": seg_ll, "n_tokens": int(lengths.sum()), "tokens": tokens}
+
+
+def evaluate(model, audio_info: Union[str, dict, np.ndarray], reference, task_manager: Optional[TaskManager] = None, bsz: int = 8,
+             continuous: bool = False, subtask: Optional[str] = None, constrained: bool = False, programs=None, num_beams: int = 1,
+             length_penalty: float = 1.0, **tolerances) -> dict:
+    """How right is the transcription of this audio: note-level onset, onset+offset and drum F1 against `reference` (a list of Note, or the
+    path of a .mid file), by the rules of yourmt3_amd/metrics.py.  The audio is decoded as transcribe(device_detok=True) decodes it
+    (`continuous`, `subtask`, `constrained`, `programs`, `num_beams`, `length_penalty` as there); the ids become note records on the device
+    (Detokenizer.run_device) and are matched against the uploaded reference there (NoteMetrics.run, reading the number of transcribed notes
+    from the detokeniser's counter on the device): one copy back, of the counts.  `tolerances`: onset_tol, offset_min_tol, offset_ratio.
+    -> NoteMetricCounts.summary(): onset_f / offset_f (instrument-agnostic, with _p and _r), drum_onset_f, multi_f, per_program, skipped and
+    "counts" (the (n_programs + 1, 2, 3) integers)."""
+    num_beams = int(num_beams)
+    if num_beams < 1:
+        raise ValueError(f"num_beams={num_beams} must be >= 1")
+    if num_beams > 1 and continuous:
+        raise ValueError("beam search (num_beams > 1) does not run with continuous batching (continuous=True)")
+    cfg = model.cfg
+    if task_manager is None:
+        task_manager = TaskManager("mc13_full_plus_256" if cfg.n_channels == 13 else "mt3_full_plus")
+    if task_manager.num_decoding_channels != cfg.n_channels:
+        raise ValueError("TaskManager channel count does not match the model's decoder")
+    if isinstance(audio_info, dict):
+        x, sr = load_wav_pcm(audio_info["filepath"])
+    elif isinstance(audio_info, str):
+        x, sr = load_wav_pcm(audio_info)
+    else:
+        x, sr = np.asarray(audio_info, dtype=np.float32), cfg.sample_rate
+    if isinstance(reference, (str, os.PathLike)):
+        with open(reference, "rb") as f:
+            reference = read_midi_notes(f.read())
+    ref = to_records(reference)
+    lo, hi = task_manager.codec.range_of("program")
+    n_programs = hi - lo
+    segments = model.ingest(torch.from_numpy(np.ascontiguousarray(x)), sr)
+    n = int(segments.shape[0])
+    start_secs = [i * cfg.segment_samples / cfg.sample_rate for i in range(n)]
+    prompt = None
+    if task_manager.subtasks:
+        prompt = torch.tensor(task_manager.task_prompt(subtask, 1)[0, 0])
+    elif subtask is not None:
+        raise ValueError(f"task {task_manager.task_name!r} has no sub-tasks (asked for {subtask!r})")
+    L = min(task_manager.max_note_token_length, cfg.max_decode_len - (0 if prompt is None else int(prompt.numel())))
+    kw = {} if prompt is None else {"task_tokens": prompt}
+    constraint = None
+    if constrained or programs is not None:
+        aut, starts = task_manager.event_automaton(programs)
+        constraint = model.compile_constraint(aut)
+        kw["constraint"] = constraint
+        kw["start_states"] = starts
+    if num_beams > 1:
+        kw.update(num_beams=num_beams, num_return_sequences=1, length_penalty=length_penalty)
+    try:
+        tokens, _ = _decode_device(model, segments, bsz, L, continuous, False, kw)
+    finally:
+        if constraint is not None:
+            constraint.close()
+    detok = model.compile_detokenizer(task_manager, max(n, 1), L)
+    metrics = model.compile_note_metrics(n_programs, max(len(ref), 1), detok.capacity, **tolerances)
+    try:
+        est, est_counts = detok.run_device(tokens, None, torch.tensor(start_secs, dtype=torch.float64), model.last_ingest_samples / cfg.sample_rate)
+        counts = metrics.run(torch.from_numpy(ref.view(np.uint8).reshape(-1).copy()), est, est_count=est_counts)
+        flat = counts.cpu().numpy()
+    finally:
+        metrics.close()
+        detok.close()
+    return NoteMetricCounts.from_flat(flat, n_programs, metrics.drum_program).summary()
