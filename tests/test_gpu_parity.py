@@ -1163,6 +1163,16 @@ def test_bad_blob_and_config_are_rejected():
     assert rc == 4 and "n_frames" in msg
 
 
+def test_short_decoder_tensor_is_refused_at_create():
+    """The decoder's weights are bound at create with their dtype and minimum size (runtime.hip: bind_dec_weights): a tensor that is present
+    but holds too few bytes is a blob error of ymt3_create, naming the tensor -- not a failure of the first decode inside a stream capture."""
+    from yourmt3_amd import _lib
+    W = make_weights(SMALL, seed=1234)
+    W["dec.0.wo"] = W["dec.0.wo"][: W["dec.0.wo"].shape[0] // 2].contiguous()
+    with pytest.raises(_lib.YMT3Error, match=r"ymt3 error 2: .*'dec\.0\.wo' holds"):          # 2 = YMT3_ERR_BLOB
+        _model(SMALL, weights=W)
+
+
 def test_bad_arguments_raise(small):
     from yourmt3_amd._lib import YMT3Error
     e = torch.zeros(1, SMALL.n_frames, SMALL.d_model, dtype=torch.bfloat16).cuda()

@@ -15,6 +15,7 @@
 #include <atomic>
 #include <string>
 #include <thread>
+#include <tuple>
 #include <vector>
 
 #include "../../include/ymt3.h"
@@ -51,6 +52,31 @@ struct StepGraph {
     hipGraphExec_t exec = nullptr;
     bool merged = false;            // the captured steps contain merged kernels (GEMM chain / attention pair): their abort word must be looked at
 };
+// What a cached step graph was captured for: everything that changes a captured launch and is not read from device memory.
+enum StepMode { SM_LOCKSTEP = 0, SM_BEAM, SM_SLOT, SM_SLOT_BEAM };
+struct StepKey {
+    StepMode mode = SM_LOCKSTEP;
+    int B = 0;                      // segments of the call (lock-step, beam) or slots (slot modes)
+    int n_chains = 1, chain = 0;    // chains the call used, and which of them this graph serves
+    int beams = 0;                  // W of a beam call, 0 otherwise
+    int steps = 1;                  // decode steps in the graph (set by step_graph)
+    bool operator<(const StepKey& o) const {
+        return std::tie(mode, B, n_chains, chain, beams, steps) < std::tie(o.mode, o.B, o.n_chains, o.chain, o.beams, o.steps);
+    }
+};
+
+// The decoder's weights, looked up in the blob once (create_impl: bind_dec_weights) with the dtype and minimum size the kernels rely on.
+struct LayerW {
+    const float *ln1 = nullptr, *ln2 = nullptr, *ln3 = nullptr;
+    const bf16_t *wqkv = nullptr, *wo = nullptr, *wq_c = nullptr, *wo_c = nullptr, *wi = nullptr, *wo2 = nullptr, *router = nullptr;
+    const uint8_t *wi_q8 = nullptr, *wo_q8 = nullptr;      // MoE experts in fp8 (then wi / wo2 are null) and their scales
+    const float *wi_s = nullptr, *wo_s = nullptr;
+};
+struct DecWeights {
+    std::vector<LayerW> layer;
+    const bf16_t *embed = nullptr, *chan_embed = nullptr, *lm_head = nullptr;      // chan_embed: null with one channel
+    const float *ln_f = nullptr, *bias_dist = nullptr;
+};
 
 struct ymt3_ctx {
     ymt3_config cfg{};
@@ -59,6 +85,7 @@ struct ymt3_ctx {
     char* blob_dev = nullptr;
     size_t blob_bytes = 0;
     std::map<std::string, Tensor> tensors;
+    DecWeights dec;
     std::vector<void*> allocs;
     size_t dev_bytes = 0;
     FrontendTables fe{};
@@ -106,10 +133,9 @@ struct ymt3_ctx {
     // attention, 16-row-tile GEMMs, no folded O-projection), so the ids do not depend on the choice (tested).
     bool auto_chains = true;
     int last_chains = 1;
-    bool chain_threads = true;              // one launcher thread per chain (YMT3_CHAIN_THREADS=0: the caller's thread feeds all)
     hipStream_t chain_stream[8] = {};
     hipEvent_t fork_ev = nullptr, join_ev[8] = {};
-    std::map<long, StepGraph> step_graphs;  // keyed by (B, n_chains_used, chain)
+    std::map<StepKey, StepGraph> step_graphs;
     bool use_graph = true;
     int graph_steps = 16;                   // decode steps per replayed graph (YMT3_GRAPH_STEPS): a graph launch costs ~7 us of stream time on top of its kernels
     bool fuse_q = true;                     // cross-attention computes its own query projection
@@ -255,6 +281,14 @@ static int parse_blob(ymt3_ctx* c, const void* blob, size_t nbytes) {
     return 0;
 }
 
+static void clear_step_graphs(ymt3_ctx* h) {
+    for (auto& kv : h->step_graphs) {
+        if (kv.second.exec) (void)hipGraphExecDestroy(kv.second.exec);
+        if (kv.second.graph) (void)hipGraphDestroy(kv.second.graph);
+    }
+    h->step_graphs.clear();
+}
+
 // ------------------------------------------------------------------------------------------------
 extern "C" int ymt3_abi_version(void) { return YMT3_ABI_VERSION; }
 extern "C" const char* ymt3_last_error(void) { return g_err; }
@@ -262,10 +296,7 @@ extern "C" const char* ymt3_last_error(void) { return g_err; }
 extern "C" void ymt3_destroy(ymt3_handle h) {
     if (!h) return;
     (void)hipSetDevice(h->device);
-    for (auto& kv : h->step_graphs) {
-        if (kv.second.exec) (void)hipGraphExecDestroy(kv.second.exec);
-        if (kv.second.graph) (void)hipGraphDestroy(kv.second.graph);
-    }
+    clear_step_graphs(h);
     if (h->cap_stream) (void)hipStreamDestroy(h->cap_stream);
     if (h->host_flag) (void)hipHostFree(h->host_flag);
     if (h->chain_host_abort) (void)hipHostFree(h->chain_host_abort);
@@ -296,13 +327,12 @@ static int build_qkv0_table(ymt3_ctx* c) {
     HIP_TRY(hipMalloc(reinterpret_cast<void**>(&ssq), (size_t)SSQ_TILES * CH * 4));
     ArgmaxArgs e{};
     e.h = hs; e.ssq = ssq; e.ssq_stride = CH; e.V = V; e.d = d; e.n_channels = 1;
-    GET(c, "dec.embed", 1u, const_cast<bf16_t**>(&e.embed), (size_t)V * d);
+    e.embed = c->dec.embed;
     DecGemmArgs a{};
     a.x_f32 = hs; a.ssq = ssq; a.ssq_stride = CH; a.N = N; a.K = d; a.eps = k.ln_eps; a.H = k.n_heads; a.L = k.max_decode_len;
     a.shared = c->shared;                     // (the kernel requests the cache position with its operands; the table path does not use it)
     a.mid_rows = 0;
-    GET(c, "dec.0.ln1", 0u, const_cast<float**>(&a.gain), (size_t)d);
-    GET(c, "dec.0.wqkv", 1u, const_cast<bf16_t**>(&a.W), (size_t)N * d);
+    a.gain = c->dec.layer[0].ln1; a.W = c->dec.layer[0].wqkv;
     for (int v0 = 0; v0 < V; v0 += CH) {
         const int n = std::min(CH, V - v0);
         hipStream_t s = nullptr;
@@ -311,6 +341,43 @@ static int build_qkv0_table(ymt3_ctx* c) {
         LAUNCH(launch_dec_gemm(DG_NORM_QKV_CACHE, a, s));
     }
     HIP_TRY(hipDeviceSynchronize());
+    return YMT3_OK;
+}
+
+// create_impl's helper: every decoder tensor the step kernels, the qkv0 table and the scoring pass read, with its dtype and minimum size
+static int bind_dec_weights(ymt3_ctx* c) {
+    const ymt3_config& k = c->cfg;
+    const size_t d = k.d_model, inner = c->inner, V = k.vocab;
+    const bool moe = k.dec_ffn == YMT3_FFN_MOE;
+    const size_t ne = moe ? (size_t)k.n_experts : 1;
+    DecWeights& D = c->dec;
+    D.layer.assign((size_t)k.n_dec_layers, LayerW{});
+    for (int l = 0; l < k.n_dec_layers; ++l) {
+        const std::string p = "dec." + std::to_string(l) + ".";
+        LayerW& W = D.layer[(size_t)l];
+        GET(c, p + "ln1", 0u, &W.ln1, d);
+        GET(c, p + "ln2", 0u, &W.ln2, d);
+        GET(c, p + "ln3", 0u, &W.ln3, d);
+        GET(c, p + "wqkv", 1u, &W.wqkv, 3 * inner * d);
+        GET(c, p + "wo", 1u, &W.wo, d * inner);
+        GET(c, p + "wq_c", 1u, &W.wq_c, inner * d);
+        GET(c, p + "wo_c", 1u, &W.wo_c, d * inner);
+        if (moe && k.moe_fp8) {
+            GET(c, p + "wi_q8", 3u, &W.wi_q8, ne * k.d_ff * d);
+            GET(c, p + "wo2_q8", 3u, &W.wo_q8, ne * d * k.d_ff);
+            GET(c, p + "wi_s", 0u, &W.wi_s, ne);
+            GET(c, p + "wo2_s", 0u, &W.wo_s, ne);
+        } else {
+            GET(c, p + "wi", 1u, &W.wi, ne * k.d_ff * d);
+            GET(c, p + "wo2", 1u, &W.wo2, ne * d * k.d_ff);
+        }
+        if (moe) GET(c, p + "router", 1u, &W.router, (size_t)k.n_experts * d);
+    }
+    GET(c, "dec.embed", 1u, &D.embed, V * d);
+    if (k.n_channels > 1) GET(c, "dec.chan_embed", 1u, &D.chan_embed, (size_t)k.n_channels * d);
+    GET(c, "dec.ln_f", 0u, &D.ln_f, d);
+    GET(c, "dec.lm_head", 1u, &D.lm_head, V * d);
+    GET(c, "dec.bias_dist", 0u, &D.bias_dist, (size_t)k.n_heads * k.max_decode_len);
     return YMT3_OK;
 }
 
@@ -513,8 +580,6 @@ static int create_impl(ymt3_ctx* c, const ymt3_config* cfg, const void* blob, si
     if (const char* ar = getenv("YMT3_ABORT_RECOVERY")) c->abort_recovery = ar[0] == '0' ? 0 : 1;
     const char* nc = getenv("YMT3_CHAINS");
     if (nc && atoi(nc) >= 1) { c->n_chains = atoi(nc) > 8 ? 8 : atoi(nc); c->auto_chains = false; }
-    const char* ct = getenv("YMT3_CHAIN_THREADS");
-    c->chain_threads = !(ct && ct[0] == '0');
     for (int i = 0; i < std::max(c->n_chains, 2); ++i) {
         HIP_TRY(hipStreamCreateWithFlags(&c->chain_stream[i], hipStreamNonBlocking));
         HIP_TRY(hipEventCreateWithFlags(&c->join_ev[i], hipEventDisableTiming));
@@ -526,14 +591,8 @@ static int create_impl(ymt3_ctx* c, const ymt3_config* cfg, const void* blob, si
     for (int l = 0; l < k.n_enc_layers; ++l)
         for (const char* n : enc_names)
             if (!c->tensors.count("enc." + std::to_string(l) + "." + n)) FAIL(YMT3_ERR_BLOB, "missing enc.%d.%s", l, n);
-    const bool fp8_experts = k.dec_ffn == YMT3_FFN_MOE && k.moe_fp8;
-    std::vector<const char*> dec_names = {"ln1", "wqkv", "wo", "ln2", "wq_c", "wo_c", "ln3"};
-    if (fp8_experts) { dec_names.push_back("wi_q8"); dec_names.push_back("wo2_q8"); dec_names.push_back("wi_s"); dec_names.push_back("wo2_s"); }
-    else { dec_names.push_back("wi"); dec_names.push_back("wo2"); }
-    if (k.dec_ffn == YMT3_FFN_MOE) dec_names.push_back("router");
-    for (int l = 0; l < nd; ++l)
-        for (const char* n : dec_names)
-            if (!c->tensors.count("dec." + std::to_string(l) + "." + n)) FAIL(YMT3_ERR_BLOB, "missing dec.%d.%s", l, n);
+    rc = bind_dec_weights(c);                // (the decoder's are bound with dtype and size: wrong ones are refused here, not inside a stream capture)
+    if (rc) return rc;
     {
         const char* nt = getenv("YMT3_NO_QKV0_TABLE");       // A/B: keep layer 0's QKV projection launch
         if (!(nt && nt[0] == '1') && k.n_channels == 1 && !c->step_kernel && !c->stamp_buf && 3 * c->inner == QKV0_COLS) {
@@ -570,11 +629,7 @@ static int merged_fallback(ymt3_ctx* h) {
     h->gemm_chain = h->attn_pair = h->step_kernel = h->moe_chain = false;
     ++h->fallback_count;
     h->forced_abort = false;
-    for (auto& kv : h->step_graphs) {
-        if (kv.second.exec) (void)hipGraphExecDestroy(kv.second.exec);
-        if (kv.second.graph) (void)hipGraphDestroy(kv.second.graph);
-    }
-    h->step_graphs.clear();
+    clear_step_graphs(h);
     if (h->chain_sync) HIP_TRY(hipMemset(h->chain_sync, 0, CHAIN_SYNC_WORDS * sizeof(unsigned)));
     if (h->pair_rows) HIP_TRY(hipMemset(h->pair_rows, 0, (size_t)16 * CHAIN_TILES_MAX * 2 * CHAIN_LINE * sizeof(unsigned)));
     if (h->step_sync) HIP_TRY(hipMemset(h->step_sync, 0, (size_t)STEP_SYNC_LINES * CHAIN_LINE * sizeof(unsigned)));
@@ -1075,25 +1130,37 @@ extern "C" int ymt3_encode(ymt3_handle h, const float* mel_dev, int B, void* enc
 }
 
 // the beam kernels' arguments for R rows of W beams: the handle's scratch, the step's buffers, the embedding tables
-static int beam_args(ymt3_handle h, int R, int W, DecodeShared* shared, BeamArgs* out) {
+static BeamArgs beam_args(ymt3_handle h, int R, int W, DecodeShared* shared) {
     const ymt3_config& k = h->cfg;
-    const int d = k.d_model;
     BeamArgs b = h->beam;
     b.logits = h->logits; b.h = h->h_dec; b.shared = shared; b.beam = h->beam_shared; b.finished = h->finished; b.ssq = h->ssq; b.ssq_stride = h->maxR;
-    b.R = R; b.V = k.vocab; b.d = d; b.n_channels = k.n_channels; b.eos_id = k.eos_id; b.pad_id = k.pad_id; b.W = W; b.row_state = h->row_state;
+    b.R = R; b.V = k.vocab; b.d = k.d_model; b.n_channels = k.n_channels; b.eos_id = k.eos_id; b.pad_id = k.pad_id; b.W = W; b.row_state = h->row_state;
     if (h->slot_mode) { b.row_pos = h->row_pos; b.row_out = h->row_out; b.row_prompt = h->row_prompt; }
-    GET(h, "dec.embed", 1u, const_cast<bf16_t**>(&b.embed), (size_t)k.vocab * d);
-    if (k.n_channels > 1) GET(h, "dec.chan_embed", 1u, const_cast<bf16_t**>(&b.chan_embed), (size_t)k.n_channels * d);
-    *out = b;
-    return 0;
+    b.embed = h->dec.embed; b.chan_embed = h->dec.chan_embed;
+    return b;
 }
+
+// what every user of ArgmaxArgs fills alike for R rows (the step's feeding kernel, decode_init, the slot kernels): loop state, the
+// embedding tables, the automaton states and, in slot mode, the per-row positions and offsets
+static ArgmaxArgs argmax_base(ymt3_handle h, int R) {
+    const ymt3_config& k = h->cfg;
+    ArgmaxArgs a{};
+    a.h = h->h_dec; a.shared = h->shared; a.finished = h->finished; a.ssq = h->ssq; a.ssq_stride = h->maxR;
+    a.R = R; a.V = k.vocab; a.d = k.d_model; a.n_channels = k.n_channels; a.eos_id = k.eos_id; a.pad_id = k.pad_id;
+    a.embed = h->dec.embed; a.chan_embed = h->dec.chan_embed; a.row_state = h->row_state;
+    if (h->slot_mode) { a.row_pos = h->row_pos; a.row_out = h->row_out; a.row_prompt = h->row_prompt; }
+    return a;
+}
+
+// From how many rows on the decode GEMMs take the mid-size tiles (DecGemmArgs::mid_rows).  The qkv0 table's gate and the step's regime ask
+// here, so that the table and the launch it replaces agree on the tile kernel.
+static int mid_threshold(ymt3_handle h) { return h->mid_rows > 0 ? h->mid_rows : (h->mid_rows < 0 ? DEC_GEMM_MID_ROWS : 1 << 30); }
 
 // Does a decode call whose largest step has `rows` rows take layer 0's q / k / v from the table?  Only where the launch it replaces is the
 // 16-row-tile kernel, whose bits the table holds (the mid-size tiles accumulate K differently); never a beam call (its selection kernels
 // do not gather) and never the profiled call (ymt3_profile_decode keeps the launch sequence its classes are defined by).
 static void qkv0_decide(ymt3_handle h, int rows, bool beam, bool profiled) {
-    const int mid = h->mid_rows > 0 ? h->mid_rows : (h->mid_rows < 0 ? DEC_GEMM_MID_ROWS : 1 << 30);
-    h->qkv0_call = h->qkv0_table && !beam && !profiled && h->cfg.n_channels == 1 && rows < mid;
+    h->qkv0_call = h->qkv0_table && !beam && !profiled && h->cfg.n_channels == 1 && rows < mid_threshold(h);
 }
 // the feeding kernels' side of it: where the fed id's table row goes
 static void qkv0_wire(ymt3_handle h, ArgmaxArgs* a) {
@@ -1101,59 +1168,24 @@ static void qkv0_wire(ymt3_handle h, ArgmaxArgs* a) {
     a->qkv0 = h->qkv0_table; a->q0 = h->dq; a->kcache0 = h->kcache; a->vcache0 = h->vcache; a->H = h->cfg.n_heads; a->L = h->cfg.max_decode_len;
 }
 
-// one decoder step of rows [row0, row0 + R) = 8 kernels per layer + lm_head + argmax, all reading the
-// position from the chain's DecodeShared
-static int launch_step(ymt3_handle h, int B, int row0, int R, DecodeShared* shared, hipStream_t s, bool solo = true) {
+// Which kernels a step of rows [row0, row0 + R) takes.  Every choice gives the same bits; they differ in launches and time.
+struct StepPlan {
+    int rows_kv;            // decoder rows per segment's cross-attention K/V: n_channels, times W in a beam call
+    bool fold_combine, mc, fold, merged_regime, chain, pair_ok, moe_chain, stepk;
+};
+static StepPlan plan_step(ymt3_handle h, int row0, int R, bool solo) {
     const ymt3_config& k = h->cfg;
-    const int d = k.d_model, inner = h->inner, H = k.n_heads, L = k.max_decode_len;
-    const size_t layer_cache = (size_t)h->maxR * H * L * 64;
-    const size_t slab = (size_t)B * H * h->T * 64;
-    const float* bias_dist;
-    GET(h, "dec.bias_dist", 0u, const_cast<float**>(&bias_dist), (size_t)H * L);
-    bf16_t* w;
-    float* f;
-    // every weight of the step up front
-    struct LayerW { float *ln1, *ln2, *ln3; bf16_t *wqkv, *wo, *wq_c, *wo_c, *wi, *wo2, *router; uint8_t *wi_q8, *wo_q8; float *wi_s, *wo_s; };
-    std::vector<LayerW> LW(k.n_dec_layers);
-    for (int l = 0; l < k.n_dec_layers; ++l) {
-        const std::string p = "dec." + std::to_string(l) + ".";
-        GET(h, p + "ln1", 0u, &LW[l].ln1, (size_t)d);
-        GET(h, p + "ln2", 0u, &LW[l].ln2, (size_t)d);
-        GET(h, p + "ln3", 0u, &LW[l].ln3, (size_t)d);
-        GET(h, p + "wqkv", 1u, &LW[l].wqkv, (size_t)3 * inner * d);
-        GET(h, p + "wo", 1u, &LW[l].wo, (size_t)d * inner);
-        GET(h, p + "wq_c", 1u, &LW[l].wq_c, (size_t)inner * d);
-        GET(h, p + "wo_c", 1u, &LW[l].wo_c, (size_t)d * inner);
-        const size_t ne = k.dec_ffn == YMT3_FFN_MOE ? (size_t)k.n_experts : 1;
-        LW[l].wi = LW[l].wo2 = nullptr; LW[l].wi_q8 = LW[l].wo_q8 = nullptr; LW[l].wi_s = LW[l].wo_s = nullptr;
-        if (k.dec_ffn == YMT3_FFN_MOE && k.moe_fp8) {
-            GET(h, p + "wi_q8", 3u, &LW[l].wi_q8, ne * k.d_ff * d);
-            GET(h, p + "wo2_q8", 3u, &LW[l].wo_q8, ne * d * k.d_ff);
-            GET(h, p + "wi_s", 0u, &LW[l].wi_s, ne);
-            GET(h, p + "wo2_s", 0u, &LW[l].wo_s, ne);
-        } else {
-            GET(h, p + "wi", 1u, &LW[l].wi, ne * k.d_ff * d);
-            GET(h, p + "wo2", 1u, &LW[l].wo2, ne * d * k.d_ff);
-        }
-        LW[l].router = nullptr;
-        if (k.dec_ffn == YMT3_FFN_MOE) GET(h, p + "router", 1u, &LW[l].router, (size_t)k.n_experts * d);
-    }
-    bf16_t* lm_head;
-    GET(h, "dec.lm_head", 1u, &lm_head, (size_t)k.vocab * d);
-    (void)w;
-    h->stamp_n = 0;
-    const int mtiles = (R + 15) / 16;
+    const int d = k.d_model, inner = h->inner, H = k.n_heads, bW = h->beam_W;
+    StepPlan p{};
     // MoE with the combine folded away: after an MoE FFN the residual stream is hcur + (y[2r] + y[2r+1]) until the next norm GEMM
     // (the next layer's QKV projection, or lm_head) has formed it; that QKV kernel stores it to the other buffer, which the rest of
     // its layer then uses.  Needs the 16-row decode GEMMs (below the mid-size tile threshold).
-    const bool fold_combine = k.dec_ffn == YMT3_FFN_MOE && h->moe_fold_combine && R < (h->mid_rows > 0 ? h->mid_rows : (h->mid_rows < 0 ? DEC_GEMM_MID_ROWS : 1 << 30));
-    float* hcur = h->h_dec;
-    const float* pend = nullptr;
+    p.fold_combine = k.dec_ffn == YMT3_FFN_MOE && h->moe_fold_combine && R < mid_threshold(h);
     // all channels of a segment share its cross-attention K/V: one workgroup per (segment, head) serves them together (mc_cross_attn.hip)
     // (a beam call: the W beams of a group share their segment's K/V exactly as channels do -- rows_kv = n_channels * W rows per segment)
-    const int bW = h->beam_W, rows_kv = k.n_channels * (bW > 0 ? bW : 1);
-    const bool mc = h->fuse_q && rows_kv >= 2 && rows_kv <= 16 && (h->T == 128 || h->T == 256 || h->T == 512) &&
-                    row0 % rows_kv == 0 && R % rows_kv == 0;
+    p.rows_kv = k.n_channels * (bW > 0 ? bW : 1);
+    p.mc = h->fuse_q && p.rows_kv >= 2 && p.rows_kv <= 16 && (h->T == 128 || h->T == 256 || h->T == 512) &&
+           row0 % p.rows_kv == 0 && R % p.rows_kv == 0;
     // fold_o: the self-attention kernel leaves per-head O-projection partials; the fused cross-attention and the cross
     // O-projection's residual read sum them (one launch less per layer, same bits).  Needs the 8-wave attention kernels
     // and the per-row fused cross-attention
@@ -1163,26 +1195,55 @@ static int launch_step(ymt3_handle h, int B, int row0, int R, DecodeShared* shar
     // (not for one of several concurrent chains: its 64 KB weight pulls per (row, head) share the chip badly -- two 96-row halves with it are no
     // faster than one 192-row chain, without it 6 % faster: profiles/r03_chains_many_rows.txt)
     // (a beam call runs the separate launches: its self-attention follows the ancestry table and has no folded form)
-    const bool fold = bW == 0 && h->fold_o && h->fuse_q && !mc && !h->force_2wave && H == 8 && d == 512 && ((R <= 96 && solo) || merged_rows);
+    p.fold = bW == 0 && h->fold_o && h->fuse_q && !p.mc && !h->force_2wave && H == 8 && d == 512 && ((R <= 96 && solo) || merged_rows);
     // The merged kernels' regime: one channel, up to 64 rows, and this step the only decode stream of the handle (`solo`: with YMT3_CHAINS > 1
     // other row ranges replay on other streams, and the merged kernels need every CU for their own workgroups while they run).
-    const bool merged_regime = fold && solo && k.n_channels == 1 && R <= h->merged_max_rows && row0 == 0;
+    p.merged_regime = p.fold && solo && k.n_channels == 1 && R <= h->merged_max_rows && row0 == 0;
     // GEMM chain (dec_chain.hip): after a layer's cross-attention, ONE launch does the cross O-projection, the FFN and the NEXT
     // layer's QKV projection (or lm_head) -- decided per step shape, same bits as the four launches.
-    const bool chain = h->gemm_chain && h->chain_sync && merged_regime && k.dec_ffn != YMT3_FFN_MOE && inner == 512 && k.d_ff == 2048 &&
-                       k.vocab % 32 == 0 && k.vocab / 32 >= 32 && k.vocab / 32 <= 64;
+    p.chain = h->gemm_chain && h->chain_sync && p.merged_regime && k.dec_ffn != YMT3_FFN_MOE && inner == 512 && k.d_ff == 2048 &&
+              k.vocab % 32 == 0 && k.vocab / 32 >= 32 && k.vocab / 32 <= 64;
     // attention pair (decode.hip: dec_attn_pair_kernel): a layer's two attention kernels as one launch wherever the folded
     // O-projection and the fused query projection apply to one channel of up to 64 rows (dense or MoE FFN alike)
-    const bool pair_ok = h->attn_pair && h->pair_rows && merged_regime;
-    // the per-step kernel (dec_step.hip): layer 0's QKV projection, then ALL layers' attention pairs and GEMM chains as one launch
+    p.pair_ok = h->attn_pair && h->pair_rows && p.merged_regime;
     // MoE chain (moe_chain.hip): cross O-projection -> router -> expert FFN-in -> expert FFN-out -> the next QKV projection / lm_head as one launch
-    const bool moe_chain = h->moe_chain && h->chain_sync && pair_ok && fold_combine && k.dec_ffn == YMT3_FFN_MOE && k.n_experts == 8 && inner == 512 && k.d_ff == 2048 &&
-                           k.vocab % 32 == 0 && k.vocab / 32 >= 32 && k.vocab / 32 <= 64 && h->h_dec2;
-    const bool stepk = h->step_kernel && h->step_sync && chain && pair_ok && R <= 64 && k.n_dec_layers <= 8 && h->T <= 0xfff;
-    h->step_merged = chain || pair_ok || moe_chain;
+    p.moe_chain = h->moe_chain && h->chain_sync && p.pair_ok && p.fold_combine && k.dec_ffn == YMT3_FFN_MOE && k.n_experts == 8 && inner == 512 && k.d_ff == 2048 &&
+                  k.vocab % 32 == 0 && k.vocab / 32 >= 32 && k.vocab / 32 <= 64 && h->h_dec2;
+    // the per-step kernel (dec_step.hip): layer 0's QKV projection, then ALL layers' attention pairs and GEMM chains as one launch
+    p.stepk = h->step_kernel && h->step_sync && p.chain && p.pair_ok && R <= 64 && k.n_dec_layers <= 8 && h->T <= 0xfff;
+    return p;
+}
+
+// What layer l's merged launch (GEMM chain, MoE chain, a layer of the step kernel) ends with: the NEXT layer's QKV projection into that
+// layer's cache slabs, or after the last layer the lm_head (no cache).
+struct NextStage { bool last; const bf16_t* w3; const float* gain3; int mode3, N3; bf16_t *kcache, *vcache; };
+static NextStage next_stage(ymt3_handle h, int l) {
+    const ymt3_config& k = h->cfg;
+    if (l + 1 == k.n_dec_layers) return {true, h->dec.lm_head, h->dec.ln_f, DG_NORM_LOGITS, k.vocab, nullptr, nullptr};
+    const size_t next_cache = (size_t)(l + 1) * h->maxR * k.n_heads * k.max_decode_len * 64;
+    const LayerW& N = h->dec.layer[(size_t)l + 1];
+    return {false, N.wqkv, N.ln1, DG_NORM_QKV_CACHE, 3 * h->inner, h->kcache + next_cache, h->vcache + next_cache};
+}
+
+// one decoder step of rows [row0, row0 + R) = 8 kernels per layer + lm_head + argmax, all reading the
+// position from the chain's DecodeShared
+static int launch_step(ymt3_handle h, int B, int row0, int R, DecodeShared* shared, hipStream_t s, bool solo = true) {
+    const ymt3_config& k = h->cfg;
+    const int d = k.d_model, inner = h->inner, H = k.n_heads, L = k.max_decode_len;
+    const size_t layer_cache = (size_t)h->maxR * H * L * 64;
+    const size_t slab = (size_t)B * H * h->T * 64;
+    const DecWeights& D = h->dec;
+    h->stamp_n = 0;
+    const int mtiles = (R + 15) / 16;
+    const StepPlan P = plan_step(h, row0, R, solo);
+    const bool fold = P.fold, mc = P.mc, chain = P.chain, moe_chain = P.moe_chain;
+    const int bW = h->beam_W;
+    float* hcur = h->h_dec;
+    const float* pend = nullptr;
+    h->step_merged = chain || P.pair_ok || moe_chain;
     bool qkv_done = false, lm_done = false;         // the previous layer's chain launch already did this layer's QKV / the lm_head
     for (int l = 0; l < k.n_dec_layers; ++l) {
-        const LayerW& W = LW[l];
+        const LayerW& W = D.layer[(size_t)l];
         DecGemmArgs a{};
         a.row0 = row0; a.R = R; a.eps = k.ln_eps; a.H = H; a.L = L; a.shared = shared; a.ssq = h->ssq; a.ssq_stride = h->maxR;
         a.row_pos = h->slot_mode ? h->row_pos : nullptr;
@@ -1201,25 +1262,23 @@ static int launch_step(ymt3_handle h, int B, int row0, int R, DecodeShared* shar
         }
         qkv_done = false;
         if (pend) { hcur = a.h_out; pend = nullptr; a.pend_y = nullptr; a.h_out = nullptr; }
-        if (stepk) {
+        if (P.stepk) {
             StepArgs sa{};
             sa.n_layers = k.n_dec_layers; sa.R = R; sa.T = h->T; sa.L = L; sa.ssq_stride = h->maxR; sa.eps = k.ln_eps;
             sa.tiles_free = h->step_tiles_free ? 1 : 0;
             sa.q = h->dq; sa.attn = h->dattn; sa.opart = h->opart; sa.h = hcur; sa.ssq = h->ssq; sa.dff = h->dff; sa.logits = h->logits;
-            sa.bias = bias_dist; sa.shared = shared; sa.row_pos = a.row_pos;
+            sa.bias = D.bias_dist; sa.shared = shared; sa.row_pos = a.row_pos;
             sa.sync = h->step_sync; sa.pair_rows = h->pair_rows; sa.abort_word = h->chain_sync + CHAIN_ABORT_WORD; sa.host_abort = h->chain_host_abort;
-            const float* ln_f;
-            GET(h, "dec.ln_f", 0u, const_cast<float**>(&ln_f), (size_t)d);
             for (int j = 0; j < k.n_dec_layers; ++j) {
-                const bool last = j + 1 == k.n_dec_layers;
+                const LayerW& J = D.layer[(size_t)j];
+                const NextStage ns = next_stage(h, j);
                 StepLayer& SL = sa.layer[j];
-                SL.wo = LW[j].wo; SL.wq_c = LW[j].wq_c; SL.wo_c = LW[j].wo_c; SL.wi = LW[j].wi; SL.wo2 = LW[j].wo2;
-                SL.w3 = last ? lm_head : LW[j + 1].wqkv;
-                SL.ln2 = LW[j].ln2; SL.ln3 = LW[j].ln3; SL.gain3 = last ? ln_f : LW[j + 1].ln1;
+                SL.wo = J.wo; SL.wq_c = J.wq_c; SL.wo_c = J.wo_c; SL.wi = J.wi; SL.wo2 = J.wo2; SL.w3 = ns.w3;
+                SL.ln2 = J.ln2; SL.ln3 = J.ln3; SL.gain3 = ns.gain3;
                 SL.kself = h->kcache + (size_t)j * layer_cache; SL.vself = h->vcache + (size_t)j * layer_cache;
                 SL.kcross = h->ckv + (size_t)(2 * j) * slab; SL.vcross = h->ckv + (size_t)(2 * j + 1) * slab;
-                SL.knext = last ? nullptr : h->kcache + (size_t)(j + 1) * layer_cache; SL.vnext = last ? nullptr : h->vcache + (size_t)(j + 1) * layer_cache;
-                SL.N3 = last ? k.vocab : 3 * inner; SL.last = last ? 1 : 0;
+                SL.knext = ns.kcache; SL.vnext = ns.vcache;
+                SL.N3 = ns.N3; SL.last = ns.last ? 1 : 0;
             }
             sa.stamp = next_stamp(h, PC_STEP, ((R + 15) / 16) * 128);
             PLAUNCH(PC_STEP, launch_dec_step(sa, s));
@@ -1227,11 +1286,11 @@ static int launch_step(ymt3_handle h, int B, int row0, int R, DecodeShared* shar
             break;
         }
         DecAttnArgs t{};
-        t.q = h->dq; t.k = a.kcache; t.v = a.vcache; t.out = h->dattn; t.bias = bias_dist; t.shared = shared; t.row0 = row0;
+        t.q = h->dq; t.k = a.kcache; t.v = a.vcache; t.out = h->dattn; t.bias = D.bias_dist; t.shared = shared; t.row0 = row0;
         t.n_keys_const = 0; t.slab_keys = L; t.rows_per_kv = 1; t.R = R; t.H = H; t.bias_stride = L;
         t.row_pos = a.row_pos; t.force_many = h->force_2wave ? 1 : 0;
         if (fold) { t.wo = W.wo; t.opart = h->opart; }
-        const bool pair = pair_ok && fold;
+        const bool pair = P.pair_ok && fold;
         DecAttnArgs ts = t;                          // the self-attention half
         if (bW > 0) {
             const BeamAttn ba{h->beam.anc, h->beam.anc_rows, h->beam.anc_pitch, bW};
@@ -1250,14 +1309,14 @@ static int launch_step(ymt3_handle h, int B, int row0, int R, DecodeShared* shar
         // cross-attention block: the query projection is fused into the attention kernel (YMT3_NO_FUSEQ=1 keeps
         // the separate skinny GEMM, for A/B measurements)
         t.k = h->ckv + (size_t)(2 * l) * slab; t.v = h->ckv + (size_t)(2 * l + 1) * slab; t.bias = nullptr;
-        t.n_keys_const = h->T; t.slab_keys = h->T; t.rows_per_kv = rows_kv;
+        t.n_keys_const = h->T; t.slab_keys = h->T; t.rows_per_kv = P.rows_kv;
         if (fold) t.ipart = h->opart;
         if (mc) {
             // all channels of a segment share its K/V: one workgroup per (segment, head) serves them together
             McCrossArgs mcx{};
             mcx.x_f32 = hcur; mcx.gain = W.ln2; mcx.ssq = h->ssq; mcx.ssq_stride = h->maxR; mcx.eps = k.ln_eps;
-            mcx.wq = W.wq_c; mcx.k = t.k + (size_t)(row0 / rows_kv) * H * h->T * 64; mcx.v = t.v + (size_t)(row0 / rows_kv) * H * h->T * 64;
-            mcx.out = h->dattn; mcx.row0 = row0; mcx.n_seg = R / rows_kv; mcx.n_channels = rows_kv; mcx.H = H; mcx.T = h->T;
+            mcx.wq = W.wq_c; mcx.k = t.k + (size_t)(row0 / P.rows_kv) * H * h->T * 64; mcx.v = t.v + (size_t)(row0 / P.rows_kv) * H * h->T * 64;
+            mcx.out = h->dattn; mcx.row0 = row0; mcx.n_seg = R / P.rows_kv; mcx.n_channels = P.rows_kv; mcx.H = H; mcx.T = h->T;
             PLAUNCH(PC_CROSS_ATTN, launch_mc_cross_attention(mcx, s));
         } else if (h->fuse_q) {
             t.wq = W.wq_c; t.x_f32 = hcur; t.gain = W.ln2; t.ssq = h->ssq; t.ssq_stride = h->maxR; t.eps = k.ln_eps;
@@ -1276,37 +1335,33 @@ static int launch_step(ymt3_handle h, int B, int row0, int R, DecodeShared* shar
             PLAUNCH(PC_CROSS_ATTN, launch_dec_attention(false, t, s));
         }
         if (chain) {
-            const bool last = l + 1 == k.n_dec_layers;
+            const NextStage ns = next_stage(h, l);
             ChainArgs cg{};
-            cg.w0 = W.wo_c; cg.w1 = W.wi; cg.w2 = W.wo2; cg.w3 = last ? lm_head : LW[l + 1].wqkv;
+            cg.w0 = W.wo_c; cg.w1 = W.wi; cg.w2 = W.wo2; cg.w3 = ns.w3;
             cg.attn = h->dattn; cg.part = h->opart; cg.h = hcur; cg.ssq = h->ssq; cg.ssq_stride = h->maxR;
-            cg.gain1 = W.ln3;
-            if (last) GET(h, "dec.ln_f", 0u, const_cast<float**>(&cg.gain3), (size_t)d);
-            else cg.gain3 = LW[l + 1].ln1;
+            cg.gain1 = W.ln3; cg.gain3 = ns.gain3;
             cg.dff = h->dff; cg.d_ff = k.d_ff;
-            cg.mode3 = last ? DG_NORM_LOGITS : DG_NORM_QKV_CACHE; cg.N3 = last ? k.vocab : 3 * inner;
-            cg.out_q = h->dq; cg.kcache = h->kcache + (size_t)(l + 1) * layer_cache; cg.vcache = h->vcache + (size_t)(l + 1) * layer_cache;
+            cg.mode3 = ns.mode3; cg.N3 = ns.N3;
+            cg.out_q = h->dq; cg.kcache = ns.kcache; cg.vcache = ns.vcache;
             cg.logits = h->logits; cg.H = H; cg.L = L; cg.shared = shared; cg.row_pos = a.row_pos; cg.row0 = row0; cg.R = R; cg.eps = k.ln_eps;
             cg.sync = h->chain_sync; cg.host_abort = h->chain_host_abort;
             { static const int nsub_env = [] { const char* e = getenv("YMT3_CHAIN_NSUB"); return e ? (int)strtol(e, nullptr, 16) : 0; }(); cg.nsub = nsub_env; }
             cg.stamp = next_stamp(h, PC_CHAIN, 256);
             PLAUNCH(PC_CHAIN, launch_dec_chain(cg, s));
-            if (last) lm_done = true; else qkv_done = true;
+            if (ns.last) lm_done = true; else qkv_done = true;
             continue;
         }
         if (moe_chain) {
-            const bool last = l + 1 == k.n_dec_layers;
+            const NextStage ns = next_stage(h, l);
             MoeChainArgs mc2{};
-            mc2.wo_c = W.wo_c; mc2.w3 = last ? lm_head : LW[l + 1].wqkv;
+            mc2.wo_c = W.wo_c; mc2.w3 = ns.w3;
             if (k.moe_fp8) { mc2.wi = W.wi_q8; mc2.wo = W.wo_q8; mc2.wi_s = W.wi_s; mc2.wo_s = W.wo_s; }
             else { mc2.wi = W.wi; mc2.wo = W.wo2; }
             mc2.attn = h->dattn; mc2.h = hcur; mc2.part = h->opart; mc2.ssq = h->ssq; mc2.ssq_stride = h->maxR;
             mc2.gain_r = W.ln3; mc2.router = W.router; mc2.xn = h->moe.xn; mc2.sel = h->moe.sel; mc2.gate = h->moe.gate; mc2.hidden = h->moe.hidden; mc2.y = h->moe.y;
-            if (last) GET(h, "dec.ln_f", 0u, const_cast<float**>(&mc2.gain3), (size_t)d);
-            else mc2.gain3 = LW[l + 1].ln1;
-            mc2.mode3 = last ? DG_NORM_LOGITS : DG_NORM_QKV_CACHE; mc2.N3 = last ? k.vocab : 3 * inner;
-            mc2.h_out = last ? nullptr : (hcur == h->h_dec ? h->h_dec2 : h->h_dec);
-            mc2.out_q = h->dq; mc2.kcache = h->kcache + (size_t)(l + 1) * layer_cache; mc2.vcache = h->vcache + (size_t)(l + 1) * layer_cache;
+            mc2.gain3 = ns.gain3; mc2.mode3 = ns.mode3; mc2.N3 = ns.N3;
+            mc2.h_out = ns.last ? nullptr : (hcur == h->h_dec ? h->h_dec2 : h->h_dec);
+            mc2.out_q = h->dq; mc2.kcache = ns.kcache; mc2.vcache = ns.vcache;
             mc2.logits = h->logits; mc2.H = H; mc2.L = L; mc2.shared = shared; mc2.row_pos = a.row_pos;
             mc2.R = R; mc2.E = k.n_experts; mc2.fp8 = k.moe_fp8; mc2.eps = k.ln_eps;
             mc2.sync = h->chain_sync; mc2.host_abort = h->chain_host_abort;
@@ -1314,7 +1369,7 @@ static int launch_step(ymt3_handle h, int B, int row0, int R, DecodeShared* shar
             mc2.trace_rows = h->moe_trace_rows; mc2.trace_steps = h->moe_trace_steps;
             mc2.stamp = next_stamp(h, PC_CHAIN, 256);
             PLAUNCH(PC_CHAIN, launch_moe_chain(mc2, s));
-            if (last) lm_done = true;
+            if (ns.last) lm_done = true;
             else { qkv_done = true; hcur = mc2.h_out; }
             continue;
         }
@@ -1332,8 +1387,8 @@ static int launch_step(ymt3_handle h, int B, int row0, int R, DecodeShared* shar
             mo.sel_trace = h->slot_mode ? nullptr : h->moe_trace; mo.shared = shared; mo.layer = l; mo.n_layers = k.n_dec_layers;
             mo.trace_rows = h->moe_trace_rows; mo.trace_steps = h->moe_trace_steps;
             { ProfScope _ps(h, PC_FFN_WI, s); LAUNCH(launch_moe_stage(0, mo, s)); LAUNCH(launch_moe_stage(1, mo, s)); }
-            { ProfScope _ps(h, PC_FFN_WO, s); LAUNCH(launch_moe_stage(2, mo, s)); if (!fold_combine) LAUNCH(launch_moe_stage(3, mo, s)); }
-            if (fold_combine) pend = mo.y;
+            { ProfScope _ps(h, PC_FFN_WO, s); LAUNCH(launch_moe_stage(2, mo, s)); if (!P.fold_combine) LAUNCH(launch_moe_stage(3, mo, s)); }
+            if (P.fold_combine) pend = mo.y;
         } else {
             a.gain = W.ln3; a.W = W.wi; a.N = k.d_ff; a.K = d; a.out_bf16 = h->dff;
             a.stamp = next_stamp(h, PC_FFN_WI, a.N / 16 * mtiles);
@@ -1346,33 +1401,100 @@ static int launch_step(ymt3_handle h, int B, int row0, int R, DecodeShared* shar
     DecGemmArgs a{};
     a.row0 = row0; a.R = R; a.eps = k.ln_eps; a.H = H; a.L = L; a.shared = shared; a.ssq = h->ssq; a.ssq_stride = h->maxR;
     a.mid_rows = h->mid_rows;
-    GET(h, "dec.ln_f", 0u, &f, (size_t)d);
-    a.x_f32 = hcur; a.gain = f; a.W = lm_head; a.N = k.vocab; a.K = d; a.out_f32 = h->logits;
+    a.x_f32 = hcur; a.gain = D.ln_f; a.W = D.lm_head; a.N = k.vocab; a.K = d; a.out_f32 = h->logits;
     a.pend_y = pend;                                 // the last layer's expert outputs, if their combine was folded away
     if (!lm_done) {
         a.stamp = next_stamp(h, PC_LM_HEAD, a.N / 16 * mtiles);
         PLAUNCH(PC_LM_HEAD, launch_dec_gemm(DG_NORM_LOGITS, a, s));
     }
     if (bW > 0) {
-        BeamArgs b{};
-        int rcb = beam_args(h, R, bW, shared, &b);
-        if (rcb) return rcb;
+        BeamArgs b = beam_args(h, R, bW, shared);
         b.stamp = next_stamp(h, PC_ARGMAX, R / bW);
         PLAUNCH(PC_ARGMAX, launch_beam_select(b, s));
         return YMT3_OK;
     }
-    ArgmaxArgs g{};
-    g.logits = h->logits; g.h = h->h_dec; g.shared = shared; g.finished = h->finished; g.ssq = h->ssq; g.ssq_stride = h->maxR; g.row0 = row0;
-    g.R = R; g.V = k.vocab; g.d = d; g.n_channels = k.n_channels; g.eos_id = k.eos_id; g.pad_id = k.pad_id;
-    GET(h, "dec.embed", 1u, const_cast<bf16_t**>(&g.embed), (size_t)k.vocab * d);
-    if (k.n_channels > 1) GET(h, "dec.chan_embed", 1u, const_cast<bf16_t**>(&g.chan_embed), (size_t)k.n_channels * d);
-    if (h->slot_mode) { g.row_pos = h->row_pos; g.row_out = h->row_out; g.row_prompt = h->row_prompt; }
-    g.row_state = h->row_state;
+    ArgmaxArgs g = argmax_base(h, R);
+    g.logits = h->logits; g.shared = shared; g.row0 = row0;
     qkv0_wire(h, &g);
     if (solo) g.ticket = h->ticket;                  // (row ranges of several chains would share groups)
-    if (stepk) { g.zero_sync = h->step_sync; g.zero_lines = k.n_dec_layers * STEP_SYNC_LINES_PER_LAYER; }
+    if (P.stepk) { g.zero_sync = h->step_sync; g.zero_lines = k.n_dec_layers * STEP_SYNC_LINES_PER_LAYER; }
     g.stamp = next_stamp(h, PC_ARGMAX, R);
     PLAUNCH(PC_ARGMAX, launch_argmax_embed(g, s));
+    return YMT3_OK;
+}
+
+// The cached graph of G consecutive steps of rows [row0, row0 + R) under `key`, captured on first use.  A capture that fails leaves
+// nothing behind: the capture is ended, what it recorded destroyed and the cache left without the entry.  *merged is raised when the
+// graph holds merged kernels.
+static int step_graph(ymt3_handle h, StepKey key, int B, int row0, int R, DecodeShared* shared, bool solo, int G, hipGraphExec_t* out,
+                      bool* merged = nullptr) {
+    key.steps = G;
+    auto it = h->step_graphs.find(key);
+    if (it == h->step_graphs.end()) {
+        StepGraph sg;
+        HIP_TRY(hipStreamBeginCapture(h->cap_stream, hipStreamCaptureModeThreadLocal));
+        int rc = 0;
+        for (int i = 0; i < G && !rc; ++i) rc = launch_step(h, B, row0, R, shared, h->cap_stream, solo);
+        hipError_t e = hipStreamEndCapture(h->cap_stream, &sg.graph);
+        if (!rc && e != hipSuccess) { ymt3_set_error("hipStreamEndCapture: %s", hipGetErrorString(e)); rc = YMT3_ERR_HIP; }
+        if (!rc && (e = hipGraphInstantiate(&sg.exec, sg.graph, nullptr, nullptr, 0)) != hipSuccess) {
+            ymt3_set_error("instantiating the step graph: %s", hipGetErrorString(e));
+            rc = YMT3_ERR_HIP;
+        }
+        if (rc) {
+            if (sg.graph) (void)hipGraphDestroy(sg.graph);
+            return rc;
+        }
+        sg.merged = h->step_merged;
+        it = h->step_graphs.emplace(key, sg).first;
+    }
+    *out = it->second.exec;
+    if (merged && it->second.merged) *merged = true;
+    return YMT3_OK;
+}
+
+// n_total steps on `s`: whole G-step graphs (`many`, or null: none), then the tail step by step.  G consecutive steps are ONE replayed
+// graph (every kernel reads the position from device memory, so a graph of G steps is the step's kernels G times): the boundary between
+// two graph launches costs ~7 us of stream time that a kernel boundary inside a graph does not (eager launches ran 2.9 % faster than
+// one-step graphs, profiles/r02_graph_steps.txt)
+static int replay(hipGraphExec_t many, int G, hipGraphExec_t one, int n_total, hipStream_t s) {
+    int t = 0;
+    if (many)
+        for (; t + G <= n_total; t += G) HIP_TRY(hipGraphLaunch(many, s));
+    for (; t < n_total; ++t) HIP_TRY(hipGraphLaunch(one, s));
+    return YMT3_OK;
+}
+
+// opt-in (ymt3_set_early_stop): every `interval` steps the host reads how many rows (beam call: groups) are still decoding and
+// stops launching once none is; the rest of every row is PAD by the EOS fill rule (a beam call's finished slots are complete by
+// then).  This path synchronises the stream (the only one that does).  Only emitted steps count: the prompt's steps go first, then
+// the host checks every `interval` emitted steps.  *emitted: the emitted steps launched.
+static int replay_early_stop(ymt3_handle h, hipGraphExec_t one, int n_prompt, int n_steps, hipStream_t s, int* emitted) {
+    int rc = replay(nullptr, 1, one, n_prompt, s);
+    if (rc) return rc;
+    int t = 0;
+    while (t < n_steps) {
+        const int chunk = std::min(h->early_stop_interval, n_steps - t);
+        rc = replay(nullptr, 1, one, chunk, s);
+        if (rc) return rc;
+        t += chunk;
+        if (t >= n_steps) break;
+        HIP_TRY(hipMemcpyAsync(h->host_flag, &h->shared->n_unfinished, sizeof(int), hipMemcpyDeviceToHost, s));
+        HIP_TRY(hipStreamSynchronize(s));
+        if (*h->host_flag == 0) break;
+    }
+    h->last_steps = n_prompt + t;
+    *emitted = t;
+    return YMT3_OK;
+}
+
+// The step range of a decode call: n_prompt fed steps, then n_steps emitted ones, from position step0 (ymt3_debug_decode_start, else 0).
+static int check_steps(ymt3_handle h, int n_steps, const int32_t* prompt, int n_prompt, int step0) {
+    if (n_prompt < 0) FAIL(YMT3_ERR_ARG, "n_prompt=%d < 0", n_prompt);
+    if (n_prompt > 0 && !prompt) FAIL(YMT3_ERR_ARG, "n_prompt=%d with a null prompt", n_prompt);
+    if (n_prompt > 0 && step0 > 0) FAIL(YMT3_ERR_ARG, "ymt3_debug_decode_start does not combine with a prompt (n_prompt=%d)", n_prompt);
+    if (n_steps <= 0 || step0 + n_prompt + n_steps > h->cfg.max_decode_len)
+        FAIL(YMT3_ERR_ARG, "n_steps=%d outside [1, max_decode_len - n_prompt=%d]", n_steps, h->cfg.max_decode_len - step0 - n_prompt);
     return YMT3_OK;
 }
 
@@ -1389,9 +1511,8 @@ static int decode_impl(ymt3_handle h, const bf16_t* enc, int B, int n_steps, con
                        int prof_stride = 0) {
     const int step0 = h->prof_step0;          // one shot (debug hook): consumed by this call whatever its outcome
     h->prof_step0 = 0;
-    if (n_prompt < 0) FAIL(YMT3_ERR_ARG, "n_prompt=%d < 0", n_prompt);
-    if (n_prompt > 0 && !prompt) FAIL(YMT3_ERR_ARG, "n_prompt=%d with a null prompt", n_prompt);
-    if (n_prompt > 0 && step0 > 0) FAIL(YMT3_ERR_ARG, "ymt3_debug_decode_start does not combine with a prompt (n_prompt=%d)", n_prompt);
+    int rc = check_steps(h, n_steps, prompt, n_prompt, step0);
+    if (rc) return rc;
     return decode_run(h, enc, B, n_steps, prompt, n_prompt, tokens, scores, forced, logits_out, cv, s, prof_stride, step0);
 }
 
@@ -1400,30 +1521,25 @@ static int decode_run(ymt3_handle h, const bf16_t* enc, int B, int n_steps, cons
                       int step0) {
     const ymt3_config& k = h->cfg;
     bool merged = false;                      // some step of this call ran merged kernels
-    if (n_steps <= 0 || step0 + n_prompt + n_steps > k.max_decode_len)
-        FAIL(YMT3_ERR_ARG, "n_steps=%d outside [1, max_decode_len - n_prompt=%d]", n_steps, k.max_decode_len - step0 - n_prompt);
     const int n_total = n_prompt + n_steps;   // steps launched
     const int d = k.d_model, R = B * k.n_channels;
     // a6: cross-attention K/V of every decoder layer in one GEMM, stored as per-(segment, head) slabs
     GemmArgs g{enc, h->wkv_all, h->ckv, nullptr, B * h->T, k.n_dec_layers * 2 * h->inner, d, d, d, 0, h->T, k.n_heads, B};
     LAUNCH(launch_gemm(EPI_KV_HEADMAJOR, g, s));
 
-    ArgmaxArgs a{};
-    a.h = h->h_dec; a.shared = h->shared; a.finished = h->finished; a.ssq = h->ssq; a.ssq_stride = h->maxR;
-    a.R = R; a.V = k.vocab; a.d = d; a.n_channels = k.n_channels; a.eos_id = k.eos_id; a.pad_id = k.pad_id;
-    GET(h, "dec.embed", 1u, const_cast<bf16_t**>(&a.embed), (size_t)k.vocab * d);
-    if (k.n_channels > 1) GET(h, "dec.chan_embed", 1u, const_cast<bf16_t**>(&a.chan_embed), (size_t)k.n_channels * d);
+    ArgmaxArgs a = argmax_base(h, R);
     // chains: contiguous, near-equal row ranges
     int n_chains = (!h->use_graph || prof_stride > 0 || k.dec_ffn == YMT3_FFN_MOE) ? 1 : h->n_chains;   // MoE pair tables are per handle
+    // the early-stop loop (replay_early_stop) runs one chain; with forced tokens the trajectory is fixed, so it is not used
+    const bool early = h->early_stop_interval > 0 && k.eos_id >= 0 && !forced;
     if (h->auto_chains && n_chains == 1 && h->use_graph && prof_stride == 0 && k.dec_ffn != YMT3_FFN_MOE && k.n_channels == 1 && R >= 168 && R <= 256 &&
-        !(h->early_stop_interval > 0 && k.eos_id >= 0 && !forced))
+        !early)
         n_chains = 2;
     if (n_chains > R) n_chains = R;
     h->last_chains = n_chains;
     qkv0_decide(h, (R + n_chains - 1) / n_chains, false, prof_stride > 0);      // (the largest chain's rows)
     qkv0_wire(h, &a);
     if (h->step_kernel && h->step_sync) HIP_TRY(hipMemsetAsync(h->step_sync, 0, (size_t)STEP_SYNC_LINES * CHAIN_LINE * sizeof(unsigned), s));
-    a.row_state = h->row_state;
     LAUNCH(launch_decode_init(a, n_chains, n_steps, step0, tokens, forced, logits_out, prompt, n_prompt, scores, cv, s));
     h->last_steps = n_total;
     int row0[9];
@@ -1459,112 +1575,46 @@ static int decode_run(ymt3_handle h, const bf16_t* enc, int B, int n_steps, cons
             h->prof_span_open = false;
         }
     } else {
-        hipGraphExec_t exec[8];
-        for (int c = 0; c < n_chains; ++c) {
-            StepGraph& sg = h->step_graphs[((long)B * 16 + n_chains) * 16 + c];
-            if (!sg.exec) {
-                HIP_TRY(hipStreamBeginCapture(h->cap_stream, hipStreamCaptureModeThreadLocal));
-                int rc = launch_step(h, B, row0[c], row0[c + 1] - row0[c], h->shared + c, h->cap_stream, n_chains == 1);
-                hipError_t e = hipStreamEndCapture(h->cap_stream, &sg.graph);
+        // every chain's one-step graph, and its G-step graph where the call has G steps to replay at once
+        const int G = h->graph_steps;
+        const bool stop_early = early && n_chains == 1;
+        StepKey key;
+        key.B = B; key.n_chains = n_chains;
+        hipGraphExec_t one[8], many[8] = {};
+        auto chain_graphs = [&](int steps, hipGraphExec_t* out) -> int {
+            for (int c = 0; c < n_chains; ++c) {
+                key.chain = c;
+                int rc = step_graph(h, key, B, row0[c], row0[c + 1] - row0[c], h->shared + c, n_chains == 1, steps, &out[c], &merged);
                 if (rc) return rc;
-                if (e != hipSuccess) FAIL(YMT3_ERR_HIP, "hipStreamEndCapture: %s", hipGetErrorString(e));
-                HIP_TRY(hipGraphInstantiate(&sg.exec, sg.graph, nullptr, nullptr, 0));
-                sg.merged = h->step_merged;
             }
-            exec[c] = sg.exec;
-            merged = merged || sg.merged;
-        }
-        if (n_chains == 1 && h->early_stop_interval > 0 && k.eos_id >= 0 && !forced) {
-            // opt-in (ymt3_set_early_stop): every `interval` steps the host reads how many rows are still decoding and
-            // stops launching once none is; the rest of every row is PAD by the EOS fill rule.  This path synchronises
-            // the stream (the only one that does); with forced tokens the trajectory is fixed, so it is not used.  Only emitted
-            // steps count: the prompt's steps go first, then the host checks every `interval` emitted steps.
-            for (int i = 0; i < n_prompt; ++i) HIP_TRY(hipGraphLaunch(exec[0], s));
+            return YMT3_OK;
+        };
+        int rc = chain_graphs(1, one);
+        if (!rc && !stop_early && G > 1 && n_total >= G) rc = chain_graphs(G, many);
+        if (rc) return rc;
+        if (stop_early) {
             int t = 0;
-            while (t < n_steps) {
-                const int chunk = std::min(h->early_stop_interval, n_steps - t);
-                for (int i = 0; i < chunk; ++i) HIP_TRY(hipGraphLaunch(exec[0], s));
-                t += chunk;
-                if (t >= n_steps) break;
-                HIP_TRY(hipMemcpyAsync(h->host_flag, &h->shared->n_unfinished, sizeof(int), hipMemcpyDeviceToHost, s));
-                HIP_TRY(hipStreamSynchronize(s));
-                if (*h->host_flag == 0) break;
-            }
-            h->last_steps = n_prompt + t;
+            rc = replay_early_stop(h, one[0], n_prompt, n_steps, s, &t);
+            if (rc) return rc;
             LAUNCH(launch_pad_tail(tokens, scores, 0, R, n_steps, t, k.pad_id, s));
         } else if (n_chains == 1) {
-            // graph_steps consecutive steps are ONE replayed graph (every kernel reads the position from device memory, so a graph of G
-            // steps is the step's kernels G times): the boundary between two graph launches costs ~7 us of stream time that a kernel
-            // boundary inside a graph does not (eager launches ran 2.9 % faster than one-step graphs, profiles/r02_graph_steps.txt)
-            const int G = h->graph_steps;
-            int t = 0;
-            if (G > 1 && n_total >= G) {
-                StepGraph& mg = h->step_graphs[(((long)B * 16 + 1) * 16) | (1L << 40) | ((long)G << 32)];
-                if (!mg.exec) {
-                    HIP_TRY(hipStreamBeginCapture(h->cap_stream, hipStreamCaptureModeThreadLocal));
-                    int rc = 0;
-                    for (int i = 0; i < G && !rc; ++i) rc = launch_step(h, B, 0, R, h->shared, h->cap_stream);
-                    hipError_t e = hipStreamEndCapture(h->cap_stream, &mg.graph);
-                    if (rc) return rc;
-                    if (e != hipSuccess) FAIL(YMT3_ERR_HIP, "hipStreamEndCapture: %s", hipGetErrorString(e));
-                    HIP_TRY(hipGraphInstantiate(&mg.exec, mg.graph, nullptr, nullptr, 0));
-                    mg.merged = h->step_merged;
-                }
-                merged = merged || mg.merged;
-                for (; t + G <= n_total; t += G) HIP_TRY(hipGraphLaunch(mg.exec, s));
-            }
-            for (; t < n_total; ++t) HIP_TRY(hipGraphLaunch(exec[0], s));
+            rc = replay(many[0], G, one[0], n_total, s);
+            if (rc) return rc;
         } else {
             // fork: every chain stream waits for the cross-KV GEMM + init on the caller's stream
             HIP_TRY(hipEventRecord(h->fork_ev, s));
             for (int c = 0; c < n_chains; ++c) HIP_TRY(hipStreamWaitEvent(h->chain_stream[c], h->fork_ev, 0));
-            // as for one chain: graph_steps consecutive steps of a chain are ONE replayed graph (the boundary between two graph launches costs ~7 us
-            // of stream time that a kernel boundary inside a graph does not)
-            const int G = h->graph_steps;
-            hipGraphExec_t mexec[8] = {};
-            if (G > 1 && n_total >= G) {
-                for (int c = 0; c < n_chains; ++c) {
-                    StepGraph& mg = h->step_graphs[((((long)B * 16 + n_chains) * 16 + c)) | (1L << 40) | ((long)G << 32)];
-                    if (!mg.exec) {
-                        HIP_TRY(hipStreamBeginCapture(h->cap_stream, hipStreamCaptureModeThreadLocal));
-                        int rc = 0;
-                        for (int i = 0; i < G && !rc; ++i) rc = launch_step(h, B, row0[c], row0[c + 1] - row0[c], h->shared + c, h->cap_stream, false);
-                        hipError_t e = hipStreamEndCapture(h->cap_stream, &mg.graph);
-                        if (rc) return rc;
-                        if (e != hipSuccess) FAIL(YMT3_ERR_HIP, "hipStreamEndCapture: %s", hipGetErrorString(e));
-                        HIP_TRY(hipGraphInstantiate(&mg.exec, mg.graph, nullptr, nullptr, 0));
-                        mg.merged = h->step_merged;
-                    }
-                    mexec[c] = mg.exec;
-                }
-            }
-            auto feed = [&](int c) -> bool {
-                int t = 0;
-                if (mexec[c])
-                    for (; t + G <= n_total; t += G)
-                        if (hipGraphLaunch(mexec[c], h->chain_stream[c]) != hipSuccess) return false;
-                for (; t < n_total; ++t)
-                    if (hipGraphLaunch(exec[c], h->chain_stream[c]) != hipSuccess) return false;
-                return true;
-            };
-            if (h->chain_threads) {
-                // one host thread per chain: a hipGraphLaunch of the ~44-node step costs the host 60-150 us, so ONE thread
-                // feeding n chains is host-bound as soon as a chain's step is shorter than n launches
-                std::atomic<int> bad{0};
-                std::vector<std::thread> th;
-                for (int c = 1; c < n_chains; ++c)
-                    th.emplace_back([&, c] {
-                        if (hipSetDevice(h->device) != hipSuccess) { bad = 1; return; }
-                        if (!feed(c)) bad = 1;
-                    });
-                if (!feed(0)) bad = 1;
-                for (auto& t : th) t.join();
-                if (bad) FAIL(YMT3_ERR_HIP, "hipGraphLaunch failed on a decode chain: %s", hipGetErrorString(hipGetLastError()));
-            } else {
-                // (the caller's thread feeds all chains: step by step, so that no chain runs ahead of the others' launches)
-                for (int t = 0; t < n_total; ++t)
-                    for (int c = 0; c < n_chains; ++c) HIP_TRY(hipGraphLaunch(exec[c], h->chain_stream[c]));
-            }
+            // one host thread per chain: a hipGraphLaunch of the ~44-node step costs the host 60-150 us, so ONE thread
+            // feeding n chains is host-bound as soon as a chain's step is shorter than n launches
+            std::atomic<int> bad{0};
+            std::vector<std::thread> th;
+            for (int c = 1; c < n_chains; ++c)
+                th.emplace_back([&, c] {
+                    if (hipSetDevice(h->device) != hipSuccess || replay(many[c], G, one[c], n_total, h->chain_stream[c])) bad = 1;
+                });
+            if (replay(many[0], G, one[0], n_total, h->chain_stream[0])) bad = 1;
+            for (auto& t : th) t.join();
+            if (bad) FAIL(YMT3_ERR_HIP, "hipGraphLaunch failed on a decode chain: %s", hipGetErrorString(hipGetLastError()));
             // join: the caller's stream continues only after every chain has emitted its last token
             for (int c = 0; c < n_chains; ++c) {
                 HIP_TRY(hipEventRecord(h->join_ev[c], h->chain_stream[c]));
@@ -1636,10 +1686,8 @@ extern "C" int ymt3_transcribe_segments_constrained(ymt3_handle h, const float* 
     if (rc) return rc;
     if (B == 0) return YMT3_OK;
     if (!audio_dev || !tokens_dev) FAIL(YMT3_ERR_ARG, "null buffer");
-    // the prompt is checked before any work is queued (decode_impl checks it again)
-    if (n_prompt < 0 || (n_prompt > 0 && !prompt_dev)) FAIL(YMT3_ERR_ARG, "n_prompt=%d with prompt %s", n_prompt, prompt_dev ? "set" : "null");
-    if (n_steps <= 0 || n_prompt + n_steps > h->cfg.max_decode_len)
-        FAIL(YMT3_ERR_ARG, "n_steps=%d outside [1, max_decode_len - n_prompt=%d]", n_steps, h->cfg.max_decode_len - n_prompt);
+    rc = check_steps(h, n_steps, prompt_dev, n_prompt, 0);      // before any work is queued (decode_impl checks again, with the debug start)
+    if (rc) return rc;
     hipStream_t s = (hipStream_t)stream;
     LAUNCH(launch_logmel(h->fe, audio_dev, h->mel, B, s));
     rc = encode_impl(h, h->mel, B, h->enc_out, s);
@@ -1691,14 +1739,7 @@ static int score_impl(ymt3_handle h, const bf16_t* enc, int B, int n_steps, cons
     SeqEmbedArgs e{};
     e.h = h->h_enc; e.prompt = prompt; e.tokens = tokens; e.L = L; e.n_prompt = n_prompt; e.n_steps = n_steps; e.V = k.vocab; e.d = d;
     e.n_channels = k.n_channels; e.pad_id = k.pad_id;
-    GET(h, "dec.embed", 1u, const_cast<bf16_t**>(&e.embed), (size_t)k.vocab * d);
-    if (k.n_channels > 1) GET(h, "dec.chan_embed", 1u, const_cast<bf16_t**>(&e.chan_embed), (size_t)k.n_channels * d);
-    const float* bias_dist;
-    GET(h, "dec.bias_dist", 0u, const_cast<float**>(&bias_dist), (size_t)H * k.max_decode_len);
-    bf16_t* lm_head;
-    float* ln_f;
-    GET(h, "dec.lm_head", 1u, &lm_head, (size_t)k.vocab * d);
-    GET(h, "dec.ln_f", 0u, &ln_f, (size_t)d);
+    e.embed = h->dec.embed; e.chan_embed = h->dec.chan_embed;
     const size_t slab = (size_t)B * H * T * 64;                    // one layer's K (or V) slabs of this call
     // >= 1: act_rows >= max_decode_len >= L; at most 65535 rows, the attention grid's z extent
     const int rows_per_chunk = (int)std::min<size_t>(std::min<size_t>(h->act_rows / (size_t)L, (size_t)R), 65535);
@@ -1707,43 +1748,32 @@ static int score_impl(ymt3_handle h, const bf16_t* enc, int B, int n_steps, cons
         e.row0 = row0; e.n_rows = nr;
         LAUNCH(launch_seq_embed(e, s));
         for (int l = 0; l < k.n_dec_layers; ++l) {
-            const std::string p = "dec." + std::to_string(l) + ".";
-            bf16_t* w;
-            float* f;
-            GET(h, p + "ln1", 0u, &f, (size_t)d);
-            LAUNCH(launch_rmsnorm(h->h_enc, f, h->xn, M, d, k.ln_eps, s));
-            GET(h, p + "wqkv", 1u, &w, (size_t)3 * inner * d);
-            { GemmArgs q{h->xn, w, h->qkv, nullptr, M, 3 * inner, d, d, d, 3 * inner, 0, 0, 0}; LAUNCH(launch_gemm(EPI_BF16, q, s)); }
+            const LayerW& W = h->dec.layer[(size_t)l];
+            LAUNCH(launch_rmsnorm(h->h_enc, W.ln1, h->xn, M, d, k.ln_eps, s));
+            { GemmArgs q{h->xn, W.wqkv, h->qkv, nullptr, M, 3 * inner, d, d, d, 3 * inner, 0, 0, 0}; LAUNCH(launch_gemm(EPI_BF16, q, s)); }
             SeqAttnDecArgs sa{};
-            sa.q = h->qkv; sa.k = h->qkv + inner; sa.v = h->qkv + 2 * inner; sa.out = h->attn; sa.bias = bias_dist;
+            sa.q = h->qkv; sa.k = h->qkv + inner; sa.v = h->qkv + 2 * inner; sa.out = h->attn; sa.bias = h->dec.bias_dist;
             sa.q_seq = sa.kv_seq = (long long)L * 3 * inner; sa.o_seq = (long long)L * inner;
             sa.ldq = sa.ldkv = 3 * inner; sa.ldo = inner; sa.kv_head = 64;
             sa.row0 = 0; sa.n_rows = nr; sa.L = L; sa.n_keys = L; sa.rows_per_kv = 1; sa.H = H; sa.bias_stride = k.max_decode_len;
             LAUNCH(launch_dec_seq_attention(true, sa, s));
-            GET(h, p + "wo", 1u, &w, (size_t)d * inner);
-            { GemmArgs q{h->attn, w, h->h_enc, nullptr, M, d, inner, inner, inner, d, 0, 0, 0}; LAUNCH(launch_gemm(EPI_RESID, q, s)); }
-            GET(h, p + "ln2", 0u, &f, (size_t)d);
-            LAUNCH(launch_rmsnorm(h->h_enc, f, h->xn, M, d, k.ln_eps, s));
-            GET(h, p + "wq_c", 1u, &w, (size_t)inner * d);
-            { GemmArgs q{h->xn, w, h->qkv, nullptr, M, inner, d, d, d, inner, 0, 0, 0}; LAUNCH(launch_gemm(EPI_BF16, q, s)); }
+            { GemmArgs q{h->attn, W.wo, h->h_enc, nullptr, M, d, inner, inner, inner, d, 0, 0, 0}; LAUNCH(launch_gemm(EPI_RESID, q, s)); }
+            LAUNCH(launch_rmsnorm(h->h_enc, W.ln2, h->xn, M, d, k.ln_eps, s));
+            { GemmArgs q{h->xn, W.wq_c, h->qkv, nullptr, M, inner, d, d, d, inner, 0, 0, 0}; LAUNCH(launch_gemm(EPI_BF16, q, s)); }
             SeqAttnDecArgs ca{};
             ca.q = h->qkv; ca.k = h->ckv + (size_t)(2 * l) * slab; ca.v = h->ckv + (size_t)(2 * l + 1) * slab; ca.out = h->attn;
             ca.q_seq = ca.o_seq = (long long)L * inner; ca.kv_seq = (long long)H * T * 64;
             ca.ldq = ca.ldo = inner; ca.ldkv = 64; ca.kv_head = T * 64;
             ca.row0 = row0; ca.n_rows = nr; ca.L = L; ca.n_keys = T; ca.rows_per_kv = k.n_channels; ca.H = H;
             LAUNCH(launch_dec_seq_attention(false, ca, s));
-            GET(h, p + "wo_c", 1u, &w, (size_t)d * inner);
-            { GemmArgs q{h->attn, w, h->h_enc, nullptr, M, d, inner, inner, inner, d, 0, 0, 0}; LAUNCH(launch_gemm(EPI_RESID, q, s)); }
-            GET(h, p + "ln3", 0u, &f, (size_t)d);
-            LAUNCH(launch_rmsnorm(h->h_enc, f, h->xn, M, d, k.ln_eps, s));
-            GET(h, p + "wi", 1u, &w, (size_t)k.d_ff * d);
-            { GemmArgs q{h->xn, w, h->ff, nullptr, M, k.d_ff, d, d, d, k.d_ff, 0, 0, 0}; LAUNCH(launch_gemm(EPI_BF16_RELU, q, s)); }
-            GET(h, p + "wo2", 1u, &w, (size_t)d * k.d_ff);
-            { GemmArgs q{h->ff, w, h->h_enc, nullptr, M, d, k.d_ff, k.d_ff, k.d_ff, d, 0, 0, 0}; LAUNCH(launch_gemm(EPI_RESID, q, s)); }
+            { GemmArgs q{h->attn, W.wo_c, h->h_enc, nullptr, M, d, inner, inner, inner, d, 0, 0, 0}; LAUNCH(launch_gemm(EPI_RESID, q, s)); }
+            LAUNCH(launch_rmsnorm(h->h_enc, W.ln3, h->xn, M, d, k.ln_eps, s));
+            { GemmArgs q{h->xn, W.wi, h->ff, nullptr, M, k.d_ff, d, d, d, k.d_ff, 0, 0, 0}; LAUNCH(launch_gemm(EPI_BF16_RELU, q, s)); }
+            { GemmArgs q{h->ff, W.wo2, h->h_enc, nullptr, M, d, k.d_ff, k.d_ff, k.d_ff, d, 0, 0, 0}; LAUNCH(launch_gemm(EPI_RESID, q, s)); }
         }
-        LAUNCH(launch_rmsnorm(h->h_enc, ln_f, h->xn, M, d, k.ln_eps, s));
+        LAUNCH(launch_rmsnorm(h->h_enc, h->dec.ln_f, h->xn, M, d, k.ln_eps, s));
         SeqLmHeadArgs lm{};
-        lm.xn = h->xn; lm.W = lm_head; lm.tokens = tokens; lm.lengths = lengths; lm.scores = scores; lm.logits = logits_out;
+        lm.xn = h->xn; lm.W = h->dec.lm_head; lm.tokens = tokens; lm.lengths = lengths; lm.scores = scores; lm.logits = logits_out;
         lm.M = M; lm.L = L; lm.n_prompt = n_prompt; lm.n_steps = n_steps; lm.V = k.vocab; lm.d = d; lm.row0 = row0;
         LAUNCH(launch_seq_lm_head_score(lm, s));
     }
@@ -1790,24 +1820,20 @@ static int beam_check(ymt3_handle h, int B, int n_steps, const int32_t* prompt, 
              (long long)B * k.n_channels * p->num_beams, h->maxR);
     if (k.n_channels * p->num_beams > 255) FAIL(YMT3_ERR_ARG, "n_channels * num_beams = %d exceeds 255 rows per segment", k.n_channels * p->num_beams);
     if (h->beam.anc_pitch > 48 * 1024) FAIL(YMT3_ERR_ARG, "beam search needs max_decode_len < %d (the staged ancestry table)", 48 * 1024 - 16);
-    if (n_prompt < 0 || (n_prompt > 0 && !prompt)) FAIL(YMT3_ERR_ARG, "n_prompt=%d with prompt %s", n_prompt, prompt ? "set" : "null");
-    if (n_steps <= 0 || n_prompt + n_steps > k.max_decode_len)
-        FAIL(YMT3_ERR_ARG, "n_steps=%d outside [1, max_decode_len - n_prompt=%d]", n_steps, k.max_decode_len - n_prompt);
+    if (int rc = check_steps(h, n_steps, prompt, n_prompt, 0)) return rc;
     if (h->prof_step0) FAIL(YMT3_ERR_ARG, "ymt3_debug_decode_start is pending: it does not combine with beams");
     if (B > 0 && !tokens) FAIL(YMT3_ERR_ARG, "null buffer");
     return 0;
 }
 
-// One chain, lock-step, the separate launches (launch_step with beam_W set); the step graphs are cached under a key of their own (B, W).
+// One chain, lock-step, the separate launches (launch_step with beam_W set); the step graphs are cached under a mode of their own (SM_BEAM: B, W).
 static int decode_beam_impl(ymt3_handle h, const bf16_t* enc, int B, int n_steps, const int32_t* prompt, int n_prompt, const ymt3_beam_params* p,
                             int32_t* tokens, float* seq_scores, float* token_scores, const ConstraintView& cv, hipStream_t s) {
     const ymt3_config& k = h->cfg;
     const int W = p->num_beams, d = k.d_model, R = B * k.n_channels * W, n_total = n_prompt + n_steps;
     GemmArgs g{enc, h->wkv_all, h->ckv, nullptr, B * h->T, k.n_dec_layers * 2 * h->inner, d, d, d, 0, h->T, k.n_heads, B};
     LAUNCH(launch_gemm(EPI_KV_HEADMAJOR, g, s));
-    BeamArgs b{};
-    int rcb = beam_args(h, R, W, h->shared, &b);
-    if (rcb) return rcb;
+    const BeamArgs b = beam_args(h, R, W, h->shared);
     BeamShared params = h->beam_trace;
     params.alpha = p->length_penalty; params.tokens_out = tokens; params.seq_out = seq_scores; params.tok_out = token_scores;
     h->last_chains = 1;
@@ -1816,55 +1842,24 @@ static int decode_beam_impl(ymt3_handle h, const bf16_t* enc, int B, int n_steps
     h->last_steps = n_total;
     struct BeamGuard { ymt3_ctx* c; ~BeamGuard() { c->beam_W = 0; } } guard{h};
     h->beam_W = W;
-    auto graph_of = [&](int G, hipGraphExec_t* out) -> int {
-        StepGraph& sg = h->step_graphs[(((long)B * 16 + 14) * 16 + W) | (1L << 41) | ((long)G << 32)];      // 14: beam graphs of B segments, W beams
-        if (!sg.exec) {
-            HIP_TRY(hipStreamBeginCapture(h->cap_stream, hipStreamCaptureModeThreadLocal));
-            int rc = 0;
-            for (int i = 0; i < G && !rc; ++i) rc = launch_step(h, B, 0, R, h->shared, h->cap_stream);
-            hipError_t e = hipStreamEndCapture(h->cap_stream, &sg.graph);
-            if (rc) return rc;
-            if (e != hipSuccess) FAIL(YMT3_ERR_HIP, "hipStreamEndCapture: %s", hipGetErrorString(e));
-            HIP_TRY(hipGraphInstantiate(&sg.exec, sg.graph, nullptr, nullptr, 0));
-        }
-        *out = sg.exec;
-        return 0;
-    };
+    StepKey key;
+    key.mode = SM_BEAM; key.B = B; key.beams = W;
+    const int G = h->graph_steps;
+    hipGraphExec_t many = nullptr, one = nullptr;
+    int rc = YMT3_OK;
     if (!h->use_graph) {
-        for (int t = 0; t < n_total; ++t) { int rc = launch_step(h, B, 0, R, h->shared, s); if (rc) return rc; }
+        for (int t = 0; t < n_total && !rc; ++t) rc = launch_step(h, B, 0, R, h->shared, s);
     } else if (h->early_stop_interval > 0) {
-        // opt-in (ymt3_set_early_stop): stop launching once every group is done; the finished slots are complete by then
-        hipGraphExec_t one;
-        int rc = graph_of(1, &one);
-        if (rc) return rc;
-        for (int i = 0; i < n_prompt; ++i) HIP_TRY(hipGraphLaunch(one, s));
-        int t = 0;
-        while (t < n_steps) {
-            const int chunk = std::min(h->early_stop_interval, n_steps - t);
-            for (int i = 0; i < chunk; ++i) HIP_TRY(hipGraphLaunch(one, s));
-            t += chunk;
-            if (t >= n_steps) break;
-            HIP_TRY(hipMemcpyAsync(h->host_flag, &h->shared->n_unfinished, sizeof(int), hipMemcpyDeviceToHost, s));
-            HIP_TRY(hipStreamSynchronize(s));
-            if (*h->host_flag == 0) break;
-        }
-        h->last_steps = n_prompt + t;
+        int emitted = 0;
+        rc = step_graph(h, key, B, 0, R, h->shared, true, 1, &one);
+        if (!rc) rc = replay_early_stop(h, one, n_prompt, n_steps, s, &emitted);
     } else {
-        const int G = h->graph_steps;
-        int t = 0;
-        if (G > 1 && n_total >= G) {
-            hipGraphExec_t many;
-            int rc = graph_of(G, &many);
-            if (rc) return rc;
-            for (; t + G <= n_total; t += G) HIP_TRY(hipGraphLaunch(many, s));
-        }
-        if (t < n_total) {
-            hipGraphExec_t one;
-            int rc = graph_of(1, &one);
-            if (rc) return rc;
-            for (; t < n_total; ++t) HIP_TRY(hipGraphLaunch(one, s));
-        }
+        // (the one-step graph is captured only by a call with a tail)
+        if (G > 1 && n_total >= G) rc = step_graph(h, key, B, 0, R, h->shared, true, G, &many);
+        if (!rc && (!many || n_total % G)) rc = step_graph(h, key, B, 0, R, h->shared, true, 1, &one);
+        if (!rc) rc = replay(many, G, one, n_total, s);
     }
+    if (rc) return rc;
     LAUNCH(launch_beam_finalize(b, p->num_return, s));
     HIP_TRY(hipGetLastError());
     return YMT3_OK;
@@ -1925,9 +1920,9 @@ extern "C" int ymt3_debug_beam_trace(ymt3_handle h, int32_t* trace_dev, float* r
 // reads the per-row `finished` flags, retires the segments whose rows have all stopped and admits the next pending ones into the freed
 // slots: log-mel + encoder batched over the admissions, cross-K/V written into each slot's slabs, then start(slot, segment).
 // retire(slot) launches whatever leaves the slot's results in the caller's buffers.  The caller has set the handle's mode (slot_mode,
-// beam_W) and reset the loop state with every row stopped.  watch_abort: the steps may hold merged kernels; restart() runs when one gave up.
+// beam_W) and launched its init kernel.  watch_abort: the steps may hold merged kernels; restart() runs when one gave up.
 template <class Start, class Retire, class Restart>
-static int run_slot_queue(ymt3_handle h, const float* audio_dev, int n_segments, int slots, int rows, int interval, int n_total, long key,
+static int run_slot_queue(ymt3_handle h, const float* audio_dev, int n_segments, int slots, int rows, int interval, int n_total, const StepKey& key,
                           bool watch_abort, Start start, Retire retire, Restart restart, hipStream_t s) {
     const ymt3_config& k = h->cfg;
     const int R = slots * rows, d = k.d_model, T = h->T, H = k.n_heads;
@@ -1935,21 +1930,17 @@ static int run_slot_queue(ymt3_handle h, const float* audio_dev, int n_segments,
     int rc;
     hipGraphExec_t exec = nullptr;
     // one replayed graph per round of `interval` steps when that is at most 64 steps (a graph launch costs ~7 us of stream time on
-    // top of its kernels, see decode_impl); else one per step
+    // top of its kernels, see replay); else one per step
     const int per_graph = interval <= 64 ? interval : 1;
+    if (!h->host_rows) HIP_TRY(hipHostMalloc(reinterpret_cast<void**>(&h->host_rows), (size_t)h->maxR * sizeof(int), hipHostMallocDefault));
+    // loop state (after the caller's init kernel): every row starts stopped; admissions start them
+    HIP_TRY(hipMemsetD32Async(reinterpret_cast<hipDeviceptr_t>(h->finished), 1, (size_t)R, s));
+    HIP_TRY(hipMemsetAsync(h->row_pos, 0, (size_t)R * sizeof(int), s));
+    HIP_TRY(hipMemsetAsync(h->row_out, 0, (size_t)R * sizeof(long long), s));
+    HIP_TRY(hipMemsetAsync(h->row_prompt, 0, (size_t)R * sizeof(long long), s));
     if (h->use_graph) {
-        StepGraph& sg = h->step_graphs[key | ((long)per_graph << 32)];
-        if (!sg.exec) {
-            HIP_TRY(hipStreamBeginCapture(h->cap_stream, hipStreamCaptureModeThreadLocal));
-            int rcs = 0;
-            for (int i = 0; i < per_graph && !rcs; ++i) rcs = launch_step(h, slots, 0, R, h->shared, h->cap_stream);
-            hipError_t e = hipStreamEndCapture(h->cap_stream, &sg.graph);
-            if (rcs) return rcs;
-            if (e != hipSuccess) FAIL(YMT3_ERR_HIP, "hipStreamEndCapture: %s", hipGetErrorString(e));
-            HIP_TRY(hipGraphInstantiate(&sg.exec, sg.graph, nullptr, nullptr, 0));
-            sg.merged = h->step_merged;
-        }
-        exec = sg.exec;
+        rc = step_graph(h, key, slots, 0, R, h->shared, true, per_graph, &exec);
+        if (rc) return rc;
     }
 
     std::vector<int> slot_seg((size_t)slots, -1), free_slots;
@@ -2029,40 +2020,28 @@ extern "C" int ymt3_transcribe_stream_constrained(ymt3_handle h, const float* au
     if (n_segments == 0) return YMT3_OK;
     if (!audio_dev || !tokens_dev) FAIL(YMT3_ERR_ARG, "null buffer");
     const ymt3_config& k = h->cfg;
-    if (n_prompt < 0 || (n_prompt > 0 && !prompt_dev)) FAIL(YMT3_ERR_ARG, "n_prompt=%d with prompt %s", n_prompt, prompt_dev ? "set" : "null");
-    if (n_steps <= 0 || n_prompt + n_steps > k.max_decode_len)
-        FAIL(YMT3_ERR_ARG, "n_steps=%d outside [1, max_decode_len - n_prompt=%d]", n_steps, k.max_decode_len - n_prompt);
+    rc = check_steps(h, n_steps, prompt_dev, n_prompt, 0);
+    if (rc) return rc;
     if (interval < 0) FAIL(YMT3_ERR_ARG, "interval=%d", interval);
     if (h->prof_step0) FAIL(YMT3_ERR_UNSUPPORTED, "ymt3_debug_decode_start is pending: it applies to lock-step decode calls only");
     if (interval == 0) interval = 8;
     if (slots <= 0 || slots > h->maxB) slots = h->maxB;
     if (slots > n_segments) slots = n_segments;
     hipStream_t s = (hipStream_t)stream;
-    if (!h->host_rows) HIP_TRY(hipHostMalloc(reinterpret_cast<void**>(&h->host_rows), (size_t)h->maxR * sizeof(int), hipHostMallocDefault));
-    const int K = k.n_channels, R = slots * K, d = k.d_model;
-
-    ArgmaxArgs a{};
-    a.h = h->h_dec; a.shared = h->shared; a.finished = h->finished; a.ssq = h->ssq; a.ssq_stride = h->maxR;
-    a.R = R; a.V = k.vocab; a.d = d; a.n_channels = K; a.eos_id = k.eos_id; a.pad_id = k.pad_id;
-    a.row_pos = h->row_pos; a.row_out = h->row_out; a.row_prompt = h->row_prompt; a.row_state = h->row_state;
-    GET(h, "dec.embed", 1u, const_cast<bf16_t**>(&a.embed), (size_t)k.vocab * d);
-    if (K > 1) GET(h, "dec.chan_embed", 1u, const_cast<bf16_t**>(&a.chan_embed), (size_t)K * d);
+    const int K = k.n_channels, R = slots * K;
 
     struct ModeGuard { ymt3_ctx* c; ~ModeGuard() { c->slot_mode = false; } } guard{h};
     h->slot_mode = true;
+    ArgmaxArgs a = argmax_base(h, R);        // (slot mode: with the per-row positions and offsets)
     qkv0_decide(h, R, false, false);
     qkv0_wire(h, &a);
-    // loop state: every row starts stopped; admissions start them
     if (h->step_kernel && h->step_sync) HIP_TRY(hipMemsetAsync(h->step_sync, 0, (size_t)STEP_SYNC_LINES * CHAIN_LINE * sizeof(unsigned), s));
     ConstraintView cv_init = cv;
     cv_init.start = nullptr;                  // (the rows' states are seeded at admission, from their segment's start states)
     LAUNCH(launch_decode_init(a, 1, n_steps, 0, tokens_dev, nullptr, nullptr, prompt_dev, n_prompt, scores_dev, cv_init, s));
-    HIP_TRY(hipMemsetD32Async(reinterpret_cast<hipDeviceptr_t>(h->finished), 1, (size_t)R, s));
-    HIP_TRY(hipMemsetAsync(h->row_pos, 0, (size_t)R * sizeof(int), s));
-    HIP_TRY(hipMemsetAsync(h->row_out, 0, (size_t)R * sizeof(long long), s));
-    HIP_TRY(hipMemsetAsync(h->row_prompt, 0, (size_t)R * sizeof(long long), s));
 
-    const long key = ((long)slots * 16 + 15) * 16;      // 15: slot-mode graph of `slots` segments
+    StepKey key;
+    key.mode = SM_SLOT; key.B = slots;
     auto start = [&](int slot, int seg) -> int {
         ConstraintView cv_seg = cv;
         if (cv.start) cv_seg.start = cv.start + (size_t)seg * K;
@@ -2126,29 +2105,22 @@ extern "C" int ymt3_transcribe_stream_beam(ymt3_handle h, const float* audio_dev
     if (slots <= 0 || slots > h->maxB / W) slots = h->maxB / W;
     if (slots > n_segments) slots = n_segments;
     hipStream_t s = (hipStream_t)stream;
-    if (!h->host_rows) HIP_TRY(hipHostMalloc(reinterpret_cast<void**>(&h->host_rows), (size_t)h->maxR * sizeof(int), hipHostMallocDefault));
     const int rows = K * W, R = slots * rows;
 
     struct ModeGuard { ymt3_ctx* c; ~ModeGuard() { c->slot_mode = false; c->beam_W = 0; } } guard{h};
     h->slot_mode = true;
     h->beam_W = W;
-    BeamArgs b{};
-    rc = beam_args(h, R, W, h->shared, &b);
-    if (rc) return rc;
+    const BeamArgs b = beam_args(h, R, W, h->shared);
     BeamShared bp = h->beam_trace;
     bp.alpha = params->length_penalty; bp.tokens_out = tokens_dev; bp.seq_out = seq_scores_dev; bp.tok_out = token_scores_dev;
     h->last_chains = 1;
     qkv0_decide(h, R, true, false);
-    // loop state: every row starts stopped; admissions start them
     ConstraintView cv_init = cv;
     cv_init.start = nullptr;                  // (the groups' states are seeded at admission, from their segment's start states)
     LAUNCH(launch_beam_init(b, n_steps, prompt_dev, n_prompt, cv_init, bp, s));
-    HIP_TRY(hipMemsetD32Async(reinterpret_cast<hipDeviceptr_t>(h->finished), 1, (size_t)R, s));
-    HIP_TRY(hipMemsetAsync(h->row_pos, 0, (size_t)R * sizeof(int), s));
-    HIP_TRY(hipMemsetAsync(h->row_out, 0, (size_t)R * sizeof(long long), s));
-    HIP_TRY(hipMemsetAsync(h->row_prompt, 0, (size_t)R * sizeof(long long), s));
 
-    const long key = (((long)slots * 16 + 13) * 16 + W) | (1L << 42);      // 13: slot-mode beam graph of `slots` segments, W beams
+    StepKey key;
+    key.mode = SM_SLOT_BEAM; key.B = slots; key.beams = W;
     const int N = params->num_return;
     auto start = [&](int slot, int seg) -> int {
         ConstraintView cv_seg = cv;
@@ -2258,11 +2230,7 @@ extern "C" int ymt3_debug_moe_trace(ymt3_handle h, int32_t* trace_dev, int n_ste
     if (trace_dev && (n_steps <= 0 || n_rows <= 0)) FAIL(YMT3_ERR_ARG, "n_steps=%d n_rows=%d", n_steps, n_rows);
     HIP_TRY(hipSetDevice(h->device));
     HIP_TRY(hipDeviceSynchronize());
-    for (auto& kv : h->step_graphs) {        // cached step graphs carry the old pointer in their kernel arguments
-        if (kv.second.exec) (void)hipGraphExecDestroy(kv.second.exec);
-        if (kv.second.graph) (void)hipGraphDestroy(kv.second.graph);
-    }
-    h->step_graphs.clear();
+    clear_step_graphs(h);                    // cached step graphs carry the old pointer in their kernel arguments
     h->moe_trace = trace_dev;
     h->moe_trace_steps = trace_dev ? n_steps : 0;
     h->moe_trace_rows = trace_dev ? n_rows : 0;
