@@ -31,7 +31,7 @@
  *   - the library owns weights, KV caches and scratch inside the handle; nothing is
  *     allocated after ymt3_create() except by ymt3_constraint_create() (the caller's automaton tables) and
  *     ymt3_detok_create() (the device detokeniser's scratch), ymt3_tok_create() (the device tokeniser's) and
- *     ymt3_metrics_create() (the note metrics');
+ *     ymt3_metrics_create() (the note metrics') and ymt3_roll_create() (the piano roll's);
  *   - return value: 0 = ok, non-zero = error; the message is in ymt3_last_error()
  *     (thread local).  No exception ever crosses this boundary;
  *   - one handle per device per host thread.  No internal host threads.
@@ -471,6 +471,55 @@ int  ymt3_note_metrics(ymt3_handle h, ymt3_metrics m,
                        const void* ref_notes_dev, long long n_ref, const int32_t* ref_count_dev /* may be NULL */,
                        const void* est_notes_dev, long long n_est, const int32_t* est_count_dev /* may be NULL */,
                        int32_t* counts_dev /* [(n_programs + 1) * 6 + 2] */, void* stream);
+
+/* Device piano roll and frame metrics: a note set as a 0/1 roll, and frame-level F1 of an estimate against a reference -- how much of the
+ * sounding (frame, pitch) area is right -- as integers (YourMT3.compile_piano_roll, piano_roll(), evaluate(frames=True); the
+ * specification is the host path, piano_roll and frame_metrics of yourmt3_amd/metrics.py, which it reproduces exactly: every byte and
+ * every integer).  The rules are this repository's own, shaped after the usual multi-pitch frame metric.  Records are the 32 bytes
+ * { f64 onset, f64 offset, i32 program, i32 pitch, i32 is_drum, f32 score } of the device detokeniser, 8-byte aligned, in any order;
+ * `score` is not read.
+ *   - counted records: exactly the rule of the note metrics above (p = drum_program if is_drum != 0, else program; a record with
+ *     p == drum_program is a drum note and counts even with a NaN offset); the others are skipped and appear in skipped[] only.
+ *   - frame of a time: F(t) = rint(t * frames_per_second) in f64, that one multiply, round half to even (the tokeniser's step rule: at
+ *     100 frames per second 0.57 * 100 = 56.99999999999999 lands on frame 57).
+ *   - cells of a note: a pitched note sounds in frames [F(on), max(F(off), F(on) + 1)) clipped to [0, n_frames): it always shows in its
+ *     onset frame, even when it is shorter than a frame or its offset lies before its onset.  A drum note sounds in [F(on), F(on) + 1),
+ *     clipped; its offset is not read.  The clipping is done in f64 before any conversion to an integer: an onset of +inf gives no
+ *     cell, an onset of -inf starts at frame 0, an offset of +inf ends at n_frames.
+ *   - rows: those of the note metrics.  Row p < n_programs holds the notes of effective program p; row n_programs holds all pitched
+ *     notes whatever their program (drums have only their own row).  A cell is a set member, not a count: overlapping or duplicate
+ *     notes of one (row, pitch) sound once.
+ *   - roll_dev: (n_rows, n_frames, 128) uint8 of 0 / 1 for the rows [first_row, first_row + n_rows), 16-byte aligned; every byte is
+ *     written.
+ *   - counts_dev: [(n_programs + 1) * 6 + 2] int64 = counts[row][6] then skipped[2].  With nr / ne the sounding pitches of reference /
+ *     estimate in a frame and tp those sounding in both, the six are sums over the row's frames: TP = sum tp, N_REF = sum nr, N_EST =
+ *     sum ne, SUB = sum (min(nr, ne) - tp), MISS = sum max(0, nr - ne), FA = sum max(0, ne - nr); skipped = (ref, est) records not counted.
+ *   - count pointers: count_dev / ref_count_dev / est_count_dev (each may be NULL) are read ON THE DEVICE: the side then has
+ *     min(n, max(*count, 0)) records, and n only sizes the launches (notes_dev and counts_dev[0] of ymt3_detokenize in place).
+ *   - layout and kernels (yourmt3_amd/csrc/roll.hip): frame-major bit sets, one 16-byte word of 128 pitch bits per (side, row, frame).  A
+ *     clear kernel zeroes the words in use; one wave per record sets its pitch bit in every frame of its interval with atomicOr; the
+ *     metrics reduce one (row, frame) per lane with popc and one 64-bit atomicAdd per wave and non-zero counter; the roll call expands
+ *     bits to bytes with 16-byte stores.  No kernel waits on another workgroup.
+ * ymt3_roll_create: synchronous, like ymt3_metrics_create; allocates all scratch, 2 x (n_programs + 1) x max_frames x 16 bytes (about
+ * 126 MB per side for 131 rows x 10 minutes at 100 frames per second).  Checks (YMT3_ERR_ARG naming the argument): params not NULL,
+ * frames_per_second finite and > 0, n_programs >= 1, drum_program in [0, n_programs), max_frames in [1, 2^24]; n_programs above 256
+ * is YMT3_ERR_UNSUPPORTED; a failed allocation is YMT3_ERR_HIP with nothing leaked and no object returned.  The object belongs to h;
+ * ymt3_roll_destroy frees it (NULL is a no-op), before or after the handle's destruction.
+ * ymt3_piano_roll / ymt3_frame_metrics: asynchronous on `stream`, allocate nothing, zero their output first, leave the handle's decode
+ * state alone.  YMT3_ERR_ARG, with handle and object still usable, for n_frames outside [0, max_frames], a note count outside
+ * [0, 2^29], NULL or misaligned roll_dev / counts_dev, a NULL or misaligned record pointer of a side with n > 0, or a row range outside
+ * [0, n_programs] (n_rows >= 1).  n_frames = 0 gives zero counts, with skipped still counted, or an empty roll.  One object serves one
+ * call at a time. */
+typedef struct ymt3_roll_params { double frames_per_second; int32_t n_programs, drum_program; } ymt3_roll_params;
+typedef struct ymt3_roll_s* ymt3_roll;
+int  ymt3_roll_create(ymt3_handle h, const ymt3_roll_params* p, long long max_frames, ymt3_roll* out);
+void ymt3_roll_destroy(ymt3_roll r);
+int  ymt3_piano_roll(ymt3_handle h, ymt3_roll r, const void* notes_dev, long long n_notes, const int32_t* count_dev /* may be NULL */,
+                     long long n_frames, int first_row, int n_rows, uint8_t* roll_dev /* (n_rows, n_frames, 128) */, void* stream);
+int  ymt3_frame_metrics(ymt3_handle h, ymt3_roll r,
+                        const void* ref_notes_dev, long long n_ref, const int32_t* ref_count_dev /* may be NULL */,
+                        const void* est_notes_dev, long long n_est, const int32_t* est_count_dev /* may be NULL */,
+                        long long n_frames, long long* counts_dev /* [(n_programs + 1) * 6 + 2] */, void* stream);
 
 /* Measurement hook (bench.py `roofline`): decode eagerly (no graph) and bracket every kernel launch of
  * every `stride`-th step (positions stride/2, 3*stride/2, ...) with HIP events on `stream`; synchronises the stream before returning.

@@ -1,7 +1,8 @@
 """MI355X-native audio -> MIDI-token transcription path (see README.md / DESIGN.md).  Heavy imports are lazy so that
 `import yourmt3_amd` works without a GPU or the built library."""
 
-__all__ = ["YMT3Config", "YourMT3", "TaskManager", "transcribe", "score_notes", "evaluate", "note_metrics", "NoteMetrics", "baseline_config"]
+__all__ = ["YMT3Config", "YourMT3", "TaskManager", "transcribe", "score_notes", "evaluate", "note_metrics", "NoteMetrics", "piano_roll", "frame_metrics",
+           "FrameMetricCounts", "PianoRoll", "baseline_config"]
 
 
 def __getattr__(name):
@@ -29,4 +30,13 @@ def __getattr__(name):
     if name == "NoteMetrics":
         from .model import NoteMetrics
         return NoteMetrics
+    if name == "piano_roll":
+        from .transcribe import piano_roll
+        return piano_roll
+    if name in ("frame_metrics", "FrameMetricCounts"):
+        from . import metrics
+        return getattr(metrics, name)
+    if name == "PianoRoll":
+        from .model import PianoRoll
+        return PianoRoll
     raise AttributeError(name)

@@ -27,6 +27,7 @@ SYMBOLS = [
     "ymt3_detok_create", "ymt3_detok_destroy", "ymt3_detokenize",
     "ymt3_tok_create", "ymt3_tok_destroy", "ymt3_tokenize",
     "ymt3_metrics_create", "ymt3_metrics_destroy", "ymt3_note_metrics",
+    "ymt3_roll_create", "ymt3_roll_destroy", "ymt3_piano_roll", "ymt3_frame_metrics",
 ]
 
 _lib = None
@@ -47,6 +48,11 @@ class MetricsParams(ctypes.Structure):
     """ymt3_metrics_params of include/ymt3.h"""
     _fields_ = [("onset_tol", ctypes.c_double), ("offset_min_tol", ctypes.c_double), ("offset_ratio", ctypes.c_double),
                 ("n_programs", ctypes.c_int32), ("drum_program", ctypes.c_int32)]
+
+
+class RollParams(ctypes.Structure):
+    """ymt3_roll_params of include/ymt3.h"""
+    _fields_ = [("frames_per_second", ctypes.c_double), ("n_programs", ctypes.c_int32), ("drum_program", ctypes.c_int32)]
 
 
 class YMT3Error(RuntimeError):
@@ -164,6 +170,14 @@ def load() -> ctypes.CDLL:
     lib.ymt3_metrics_destroy.restype = None
     lib.ymt3_note_metrics.argtypes = [vp, vp, vp, ctypes.c_longlong, vp, vp, ctypes.c_longlong, vp, vp, vp]
     lib.ymt3_note_metrics.restype = i32
+    lib.ymt3_roll_create.argtypes = [vp, ctypes.POINTER(RollParams), ctypes.c_longlong, ctypes.POINTER(vp)]
+    lib.ymt3_roll_create.restype = i32
+    lib.ymt3_roll_destroy.argtypes = [vp]
+    lib.ymt3_roll_destroy.restype = None
+    lib.ymt3_piano_roll.argtypes = [vp, vp, vp, ctypes.c_longlong, vp, ctypes.c_longlong, i32, i32, vp, vp]
+    lib.ymt3_piano_roll.restype = i32
+    lib.ymt3_frame_metrics.argtypes = [vp, vp, vp, ctypes.c_longlong, vp, vp, ctypes.c_longlong, vp, ctypes.c_longlong, vp, vp]
+    lib.ymt3_frame_metrics.restype = i32
     for n in ("ymt3_logmel", "ymt3_encode", "ymt3_decode_greedy", "ymt3_transcribe_segments", "ymt3_test_gemm"):
         getattr(lib, n).restype = i32
     if lib.ymt3_abi_version() != 3:

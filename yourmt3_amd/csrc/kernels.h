@@ -109,6 +109,27 @@ struct MetricsArgs {
 };
 int launch_metrics(const MetricsArgs& a, hipStream_t stream);
 
+// ---------------------------------------------------------------- device piano roll and frame metrics (roll.hip; include/ymt3.h, piano roll)
+constexpr int ROLL_PITCHES = 128;                  // one 16-byte word of pitch bits per (side, row, frame)
+constexpr int ROLL_MAX_PROGRAMS = 256;
+constexpr long long ROLL_MAX_FRAMES = 1LL << 24;
+constexpr long long ROLL_MAX_NOTES = 1LL << 29;    // per side
+struct RollArgs {
+    double frames_per_second;
+    int n_programs, drum_program;
+    int n_sides;                          // 2: reference and estimate (frame metrics); 1: the notes of a roll
+    const DetokNote* notes[2];            // [n[side]] the detokeniser's record; `score` is not read
+    long long n[2];                       // the launches' sizes
+    const int32_t* count[2];              // device counts (or null): the side has min(n, max(*count, 0)) records
+    long long n_frames, max_frames;       // frames of this call; what the scratch below was sized for
+    int row0, row_n;                      // the rows the call works on: all n_programs + 1 (metrics), or the roll's row range
+    uint4* bits;                          // [n_sides][row_n][n_frames] 128 pitch bits each, inside 2 * (n_programs + 1) * max_frames words; zeroed by the launch
+    long long* counts;                    // metrics: [(n_programs + 1) * 6 + 2], zeroed by the launch; null for a roll
+    uint8_t* roll;                        // roll: [row_n][n_frames][128] bytes of 0 / 1, every byte written; null for the metrics
+};
+int launch_frame_metrics(const RollArgs& a, hipStream_t stream);
+int launch_piano_roll(const RollArgs& a, hipStream_t stream);
+
 // ---------------------------------------------------------------- dense GEMM (gemm.hip)
 // C[M][N] (+)= A[M][K] (bf16, row stride lda) * W[N][K]^T (bf16, row stride ldw), fp32 accumulate.
 enum GemmEpilogue {

@@ -961,6 +961,95 @@ extern "C" int ymt3_note_metrics(ymt3_handle h, ymt3_metrics m, const void* ref_
     return YMT3_OK;
 }
 
+// ---------------------------------------------------------------- device piano roll and frame metrics (include/ymt3.h)
+struct ymt3_roll_s {
+    ymt3_ctx* owner;
+    int device;
+    ymt3_roll_params p;
+    long long max_frames;
+    uint4* bits = nullptr;                  // [2][n_programs + 1][max_frames] 128 pitch bits each
+};
+
+extern "C" void ymt3_roll_destroy(ymt3_roll r) {
+    if (!r) return;
+    (void)hipSetDevice(r->device);
+    if (r->bits) (void)hipFree(r->bits);
+    delete r;
+}
+
+extern "C" int ymt3_roll_create(ymt3_handle h, const ymt3_roll_params* params, long long max_frames, ymt3_roll* out) {
+    if (!out) FAIL(YMT3_ERR_ARG, "null output pointer");
+    *out = nullptr;
+    if (!h) FAIL(YMT3_ERR_ARG, "null handle");
+    if (!params) FAIL(YMT3_ERR_ARG, "params is NULL");
+    const ymt3_roll_params& p = *params;
+    if (!std::isfinite(p.frames_per_second) || p.frames_per_second <= 0) FAIL(YMT3_ERR_ARG, "frames_per_second=%g must be finite and > 0", p.frames_per_second);
+    if (p.n_programs < 1) FAIL(YMT3_ERR_ARG, "n_programs=%d must be >= 1", p.n_programs);
+    if (p.n_programs > ROLL_MAX_PROGRAMS) FAIL(YMT3_ERR_UNSUPPORTED, "n_programs=%d: at most %d programs", p.n_programs, ROLL_MAX_PROGRAMS);
+    if (p.drum_program < 0 || p.drum_program >= p.n_programs) FAIL(YMT3_ERR_ARG, "drum_program=%d outside [0, n_programs=%d)", p.drum_program, p.n_programs);
+    if (max_frames < 1 || max_frames > ROLL_MAX_FRAMES) FAIL(YMT3_ERR_ARG, "max_frames=%lld outside [1, %lld]", max_frames, ROLL_MAX_FRAMES);
+    HIP_TRY(hipSetDevice(h->device));
+    ymt3_roll r = new ymt3_roll_s{h, h->device, p, max_frames};
+    const size_t bytes = (size_t)2 * (p.n_programs + 1) * (size_t)max_frames * sizeof(uint4);
+    if (hipMalloc(reinterpret_cast<void**>(&r->bits), bytes) != hipSuccess) {
+        (void)hipGetLastError();
+        ymt3_roll_destroy(r);
+        FAIL(YMT3_ERR_HIP, "piano roll scratch (%zu bytes) could not be allocated", bytes);
+    }
+    *out = r;
+    return YMT3_OK;
+}
+
+// the checks the two roll calls share, and the arguments they share
+static int roll_args(ymt3_handle h, ymt3_roll r, long long n_frames, RollArgs* a) {
+    if (!h) FAIL(YMT3_ERR_ARG, "null handle");
+    if (!r) FAIL(YMT3_ERR_ARG, "null roll object");
+    if (r->owner != h) FAIL(YMT3_ERR_ARG, "the roll object belongs to another handle");
+    if (n_frames < 0 || n_frames > r->max_frames) FAIL(YMT3_ERR_ARG, "n_frames=%lld outside [0, max_frames=%lld]", n_frames, r->max_frames);
+    *a = RollArgs{};
+    a->frames_per_second = r->p.frames_per_second; a->n_programs = r->p.n_programs; a->drum_program = r->p.drum_program;
+    a->n_frames = n_frames; a->max_frames = r->max_frames; a->bits = r->bits;
+    return YMT3_OK;
+}
+
+static int roll_side(RollArgs* a, int side, const char* n_name, const char* ptr_name, const void* notes_dev, long long n, const int32_t* count_dev) {
+    if (n < 0 || n > ROLL_MAX_NOTES) FAIL(YMT3_ERR_ARG, "%s=%lld outside [0, %lld]", n_name, n, ROLL_MAX_NOTES);
+    if (n && !notes_dev) FAIL(YMT3_ERR_ARG, "%s is NULL", ptr_name);
+    if (n && reinterpret_cast<uintptr_t>(notes_dev) % 8) FAIL(YMT3_ERR_ARG, "%s is not aligned to 8 bytes", ptr_name);
+    a->notes[side] = static_cast<const DetokNote*>(notes_dev); a->n[side] = n; a->count[side] = n ? count_dev : nullptr;
+    return YMT3_OK;
+}
+
+extern "C" int ymt3_piano_roll(ymt3_handle h, ymt3_roll r, const void* notes_dev, long long n_notes, const int32_t* count_dev, long long n_frames,
+                               int first_row, int n_rows, uint8_t* roll_dev, void* stream) {
+    RollArgs a;
+    if (const int rc = roll_args(h, r, n_frames, &a)) return rc;
+    if (const int rc = roll_side(&a, 0, "n_notes", "notes_dev", notes_dev, n_notes, count_dev)) return rc;
+    if (first_row < 0 || n_rows < 1 || (long long)first_row + n_rows > r->p.n_programs + 1)
+        FAIL(YMT3_ERR_ARG, "rows [first_row=%d, first_row + n_rows=%lld) outside [0, n_programs + 1=%d]", first_row, (long long)first_row + n_rows, r->p.n_programs + 1);
+    if (!roll_dev) FAIL(YMT3_ERR_ARG, "roll_dev is NULL");
+    if (reinterpret_cast<uintptr_t>(roll_dev) % 16) FAIL(YMT3_ERR_ARG, "roll_dev is not aligned to 16 bytes");
+    HIP_TRY(hipSetDevice(h->device));
+    a.n_sides = 1; a.row0 = first_row; a.row_n = n_rows; a.roll = roll_dev;
+    LAUNCH(launch_piano_roll(a, static_cast<hipStream_t>(stream)));
+    return YMT3_OK;
+}
+
+extern "C" int ymt3_frame_metrics(ymt3_handle h, ymt3_roll r, const void* ref_notes_dev, long long n_ref, const int32_t* ref_count_dev,
+                                  const void* est_notes_dev, long long n_est, const int32_t* est_count_dev, long long n_frames, long long* counts_dev,
+                                  void* stream) {
+    RollArgs a;
+    if (const int rc = roll_args(h, r, n_frames, &a)) return rc;
+    if (const int rc = roll_side(&a, 0, "n_ref", "ref_notes_dev", ref_notes_dev, n_ref, ref_count_dev)) return rc;
+    if (const int rc = roll_side(&a, 1, "n_est", "est_notes_dev", est_notes_dev, n_est, est_count_dev)) return rc;
+    if (!counts_dev) FAIL(YMT3_ERR_ARG, "counts_dev is NULL");
+    if (reinterpret_cast<uintptr_t>(counts_dev) % 8) FAIL(YMT3_ERR_ARG, "counts_dev is not aligned to 8 bytes");
+    HIP_TRY(hipSetDevice(h->device));
+    a.n_sides = 2; a.row0 = 0; a.row_n = r->p.n_programs + 1; a.counts = counts_dev;
+    LAUNCH(launch_frame_metrics(a, static_cast<hipStream_t>(stream)));
+    return YMT3_OK;
+}
+
 // the kernels' view of a call's constraint (all null without one)
 static int constraint_view(ymt3_handle h, ymt3_constraint c, const int32_t* start_state_dev, ConstraintView* cv) {
     *cv = ConstraintView{};

@@ -21,7 +21,32 @@ minimum).  Drum notes never look at offsets: their offset metric equals their on
 Rows.  counts[n_programs + 1][2][3] int32: row x metric (0 onset, 1 onset+offset) x (TP, n_ref, n_est).  Row p < n_programs is
 instrument-aware: the notes of effective program p, matched only under the same pitch.  Row n_programs is instrument-agnostic: all pitched
 notes, keyed by pitch alone; drums have only their own row.  TP is the size of a MAXIMUM matching of the hit graph, which is unique
-whatever matching attains it."""
+whatever matching attains it.
+
+FRAME METRICS AND THE PIANO ROLL (piano_roll, frame_metrics below; the device path: include/ymt3.h, piano roll and frame metrics;
+yourmt3_amd/csrc/roll.hip).  How much of the sounding (frame, pitch) area is right.  These rules too are this repository's own, shaped after
+the usual multi-pitch frame metric (precision, recall, accuracy and the substitution / miss / false-alarm error of frame-wise pitch
+sets), written from memory: UNVERIFIED against the package they resemble, which is not available here.
+
+Counted records.  Exactly the rule above (classify): skipped[2] keeps its meaning, and a drum record counts even with a NaN offset.
+
+Frame of a time.  F(t) = rint(t * frames_per_second) in f64: that one multiply, round half to even -- the tokeniser's step rule.  At 100
+frames per second a time on the 10 ms grid lands on its own step despite f64 noise: 0.57 * 100 = 56.99999999999999 -> 57 and 1.1 * 100 = 110.00000000000001 -> 110.
+
+Cells of a note.  A counted pitched note sounds in frames [F(on), max(F(off), F(on) + 1)) clipped to [0, n_frames): it always shows in its
+onset frame, even when it is shorter than a frame or its offset lies before its onset.  A counted drum note sounds in [F(on), F(on) + 1),
+clipped; its offset is not read.  The clipping is done in f64 before any conversion to an integer, so +-inf and huge times are defined:
+an onset of +inf gives no cell, an onset of -inf starts at frame 0, an offset of +inf ends at n_frames.
+
+Rows.  Those of the note metrics: row p < n_programs holds the notes of effective program p, row n_programs all pitched notes whatever
+their program; drums have only their own row.  A cell is a set member, not a count: overlapping or duplicate notes of one (row, pitch)
+sound once.  roll[row][frame][pitch] in {0, 1}, shape (n_programs + 1, n_frames, 128).
+
+Frame counts.  For each row and frame, nr and ne are the numbers of sounding pitches of reference and estimate and tp the number sounding
+in both.  Per row, summed over frames, six int64: TP = sum tp, N_REF = sum nr, N_EST = sum ne, SUB = sum (min(nr, ne) - tp), MISS = sum
+max(0, nr - ne), FA = sum max(0, ne - nr).  The flat result is counts[n_programs + 1][6] then skipped[2], all int64.  Derived (0 where a
+denominator is 0): precision TP / N_EST, recall TP / N_REF, F, accuracy TP / (N_REF + N_EST - TP), and the error rates SUB / N_REF,
+MISS / N_REF, FA / N_REF and their sum."""
 from __future__ import annotations
 
 from typing import Dict, Optional, Sequence
@@ -33,6 +58,7 @@ from .task_manager import DRUM_PROGRAM, NOTE_RECORD, Note
 PITCHES = 128
 ONSET, OFFSET = 0, 1
 TP, N_REF, N_EST = 0, 1, 2
+SUB, MISS, FA = 3, 4, 5               # frame counts only: a row of FrameMetricCounts is TP, N_REF, N_EST, SUB, MISS, FA
 
 
 def to_records(notes) -> np.ndarray:
@@ -230,3 +256,142 @@ def note_metrics(ref, est, n_programs: int, drum_program: int = DRUM_PROGRAM, on
             counts[row, ONSET, TP] += tp
             counts[row, OFFSET, TP] += tp if row == drum_program else max_matching(both)
     return NoteMetricCounts(counts, skipped, drum_program)
+
+
+class FrameMetricCounts:
+    """The integers of one frame-level comparison and the values derived from them.  `counts`: (n_programs + 1, 6) int64, a row being TP,
+    N_REF, N_EST, SUB, MISS, FA; `skipped`: (2,) int64.  flat() is the device layout, counts then skipped: (n_programs + 1) * 6 + 2 integers."""
+
+    def __init__(self, counts, skipped, drum_program: int = DRUM_PROGRAM):
+        self.counts = np.asarray(counts, np.int64)
+        self.skipped = np.asarray(skipped, np.int64)
+        if self.counts.ndim != 2 or self.counts.shape[1] != 6 or self.counts.shape[0] < 2 or self.skipped.shape != (2,):
+            raise ValueError(f"counts {self.counts.shape} / skipped {self.skipped.shape} are not (n_programs + 1, 6) / (2,)")
+        self.n_programs = self.counts.shape[0] - 1
+        self.drum_program = int(drum_program)
+
+    @classmethod
+    def from_flat(cls, flat, n_programs: int, drum_program: int = DRUM_PROGRAM) -> "FrameMetricCounts":
+        flat = np.asarray(flat, np.int64).reshape(-1)
+        if flat.size != (n_programs + 1) * 6 + 2:
+            raise ValueError(f"{flat.size} integers, expected {(n_programs + 1) * 6 + 2}")
+        return cls(flat[:-2].reshape(n_programs + 1, 6), flat[-2:], drum_program)
+
+    def flat(self) -> np.ndarray:
+        return np.concatenate([self.counts.reshape(-1), self.skipped]).astype(np.int64)
+
+    def _six(self, row):
+        c = self.counts[row]
+        if c.ndim == 2:
+            c = c.sum(0)
+        return [int(v) for v in c]
+
+    def precision(self, row) -> float:
+        c = self._six(row)
+        return _ratio(c[TP], c[N_EST])
+
+    def recall(self, row) -> float:
+        c = self._six(row)
+        return _ratio(c[TP], c[N_REF])
+
+    def f_measure(self, row) -> float:
+        """F = 2PR / (P + R) of a row, or of several rows summed (a slice or a list of rows); 0 where a denominator is 0"""
+        p, r = self.precision(row), self.recall(row)
+        return 2.0 * p * r / (p + r) if p + r else 0.0
+
+    def accuracy(self, row) -> float:
+        c = self._six(row)
+        return _ratio(c[TP], c[N_REF] + c[N_EST] - c[TP])
+
+    def error(self, row) -> Dict[str, float]:
+        """the error rates of a row (or of several rows summed): substitutions, misses and false alarms over N_REF, and their sum"""
+        c = self._six(row)
+        return {"sub": _ratio(c[SUB], c[N_REF]), "miss": _ratio(c[MISS], c[N_REF]), "fa": _ratio(c[FA], c[N_REF]),
+                "total": _ratio(c[SUB] + c[MISS] + c[FA], c[N_REF])}
+
+    @property
+    def frame_f(self) -> float:
+        return self.f_measure(self.n_programs)
+
+    @property
+    def multi_frame_f(self) -> float:
+        """frame F over the instrument-aware rows summed (drums enter with their one-frame hits)"""
+        return self.f_measure(slice(0, self.n_programs))
+
+    def per_program(self) -> Dict[int, Dict[str, float]]:
+        """program -> derived values, for the programs that sound on either side"""
+        out = {}
+        for p in range(self.n_programs):
+            if self.counts[p, N_REF] or self.counts[p, N_EST]:
+                out[p] = {"frame_p": self.precision(p), "frame_r": self.recall(p), "frame_f": self.f_measure(p), "frame_acc": self.accuracy(p),
+                          "n_ref": int(self.counts[p, N_REF]), "n_est": int(self.counts[p, N_EST])}
+        return out
+
+    def summary(self) -> Dict[str, object]:
+        a = self.n_programs
+        return {"frame_f": self.frame_f, "frame_p": self.precision(a), "frame_r": self.recall(a), "frame_acc": self.accuracy(a),
+                "frame_err": self.error(a), "multi_frame_f": self.multi_frame_f, "frame_counts": self.counts}
+
+    def __eq__(self, other):
+        return isinstance(other, FrameMetricCounts) and np.array_equal(self.flat(), other.flat()) and self.drum_program == other.drum_program
+
+    def __repr__(self):
+        return f"FrameMetricCounts(frame_f={self.frame_f:.4f}, frame_acc={self.accuracy(self.n_programs):.4f}, multi_frame_f={self.multi_frame_f:.4f})"
+
+
+def frame_of(t, fps: float):
+    """F(t) of the rules, elementwise in f64 (not yet an integer: +-inf stay what they are)"""
+    with np.errstate(invalid="ignore"):
+        return np.rint(np.asarray(t, np.float64) * np.float64(fps))
+
+
+def _check_frames(n_frames: int, n_programs: int, drum_program: int, frames_per_second: float):
+    if not (np.isfinite(frames_per_second) and frames_per_second > 0):
+        raise ValueError(f"frames_per_second={frames_per_second} must be finite and > 0")
+    if n_frames < 0:
+        raise ValueError(f"n_frames={n_frames} must be >= 0")
+    if n_programs < 1 or not 0 <= drum_program < n_programs:
+        raise ValueError(f"n_programs={n_programs} must be >= 1 and drum_program={drum_program} inside [0, n_programs)")
+
+
+def _cells(notes, n_frames: int, n_programs: int, drum_program: int, fps: float):
+    """-> (the sorted, unique cells of a note set as keys (row * n_frames + frame) * 128 + pitch, the number of skipped records)"""
+    rec = to_records(notes)
+    counted, prog, drum = classify(rec, n_programs, drum_program)
+    rec, prog, drum = rec[counted], prog[counted], drum[counted]
+    f0 = frame_of(rec["onset"], fps)
+    f1 = np.where(drum, f0 + 1.0, np.maximum(frame_of(np.where(drum, 0.0, rec["offset"]), fps), f0 + 1.0))
+    lo, hi = np.maximum(f0, 0.0), np.minimum(f1, np.float64(n_frames))        # the clipping, still in f64
+    some = lo < hi
+    lo, hi = lo[some].astype(np.int64), hi[some].astype(np.int64)
+    prog, drum, pitch = prog[some], drum[some], rec["pitch"][some].astype(np.int64)
+    # every note once under its own row, every pitched note once more under the agnostic row
+    lo, hi = np.concatenate([lo, lo[~drum]]), np.concatenate([hi, hi[~drum]])
+    row = np.concatenate([prog, np.full(int((~drum).sum()), n_programs, np.int64)])
+    pitch = np.concatenate([pitch, pitch[~drum]])
+    length = hi - lo
+    first = np.cumsum(length) - length
+    frame = np.repeat(lo - first, length) + np.arange(int(length.sum()), dtype=np.int64)
+    keys = (np.repeat(row, length) * n_frames + frame) * PITCHES + np.repeat(pitch, length)
+    return np.unique(keys), int((~counted).sum())
+
+
+def piano_roll(notes, n_frames: int, n_programs: int, drum_program: int = DRUM_PROGRAM, frames_per_second: float = 100.0) -> np.ndarray:
+    """The roll of a note set (a list of Note, or a NOTE_RECORD array) by the rules of this module -> (n_programs + 1, n_frames, 128) uint8."""
+    _check_frames(n_frames, n_programs, drum_program, frames_per_second)
+    keys, _ = _cells(notes, int(n_frames), n_programs, drum_program, float(frames_per_second))
+    roll = np.zeros((n_programs + 1) * int(n_frames) * PITCHES, np.uint8)
+    roll[keys] = 1
+    return roll.reshape(n_programs + 1, int(n_frames), PITCHES)
+
+
+def frame_metrics(ref, est, n_frames: int, n_programs: int, drum_program: int = DRUM_PROGRAM, frames_per_second: float = 100.0) -> FrameMetricCounts:
+    """Compare the estimate `est` with the reference `ref` (lists of Note, or NOTE_RECORD arrays) frame by frame, by the rules of this module."""
+    _check_frames(n_frames, n_programs, drum_program, frames_per_second)
+    n_frames, rows = int(n_frames), n_programs + 1
+    (kr, skipped_r), (ke, skipped_e) = (_cells(s, n_frames, n_programs, drum_program, float(frames_per_second)) for s in (ref, est))
+    both = np.intersect1d(kr, ke, assume_unique=True)
+    nr, ne, tp = (np.bincount(k // PITCHES, minlength=rows * n_frames).reshape(rows, n_frames) for k in (kr, ke, both))
+    counts = np.stack([tp.sum(1), nr.sum(1), ne.sum(1), (np.minimum(nr, ne) - tp).sum(1), np.maximum(0, nr - ne).sum(1),
+                       np.maximum(0, ne - nr).sum(1)], 1)
+    return FrameMetricCounts(counts, (skipped_r, skipped_e), drum_program)

@@ -241,6 +241,89 @@ class NoteMetrics:
             pass
 
 
+class PianoRoll:
+    """The device piano roll and frame metrics of one model (YourMT3.compile_piano_roll; include/ymt3.h, piano roll and frame metrics; the
+    rules and the host specification: piano_roll and frame_metrics of yourmt3_amd/metrics.py): the parameters and the bit-set scratch for up
+    to `max_frames` frames.  Freed by close(), or by the model's close()."""
+
+    def __init__(self, model: "YourMT3", n_programs: int, max_frames: int, frames_per_second: float = 100.0, drum_program: int = DRUM_PROGRAM):
+        self.n_programs, self.drum_program = int(n_programs), int(drum_program)
+        self.max_frames, self.frames_per_second = int(max_frames), float(frames_per_second)
+        self._model = weakref.ref(model)
+        self._lib = model._lib
+        self._c = ctypes.c_void_p()
+        params = _lib.RollParams(self.frames_per_second, self.n_programs, self.drum_program)
+        _lib.check(self._lib.ymt3_roll_create(model._handle, ctypes.byref(params), self.max_frames, ctypes.byref(self._c)))
+
+    @property
+    def ptr(self):
+        if not self._c.value:
+            raise ValueError("the piano roll object has been closed")
+        return self._c
+
+    def _side(self, model, name: str, rec: torch.Tensor, cnt: Optional[torch.Tensor]):
+        """-> (records on the device, their number, the count tensor on the device or None)"""
+        if rec.dtype != torch.uint8 or rec.dim() != 1 or rec.numel() % NOTE_RECORD.itemsize:
+            raise ValueError(f"{name} must be a 1-D uint8 tensor of {NOTE_RECORD.itemsize}-byte NOTE_RECORDs")
+        rec = rec.to(model.device).contiguous()
+        if rec.numel() and rec.data_ptr() % 8:
+            rec = rec.clone()
+        if cnt is not None:
+            if cnt.dtype != torch.int32 or not cnt.numel():
+                raise ValueError(f"the count of {name} must be an int32 tensor")
+            cnt = cnt.to(model.device)
+        return rec, rec.numel() // NOTE_RECORD.itemsize, cnt
+
+    def roll(self, records: torch.Tensor, n_frames: int, count: Optional[torch.Tensor] = None, rows=None) -> torch.Tensor:
+        """NOTE_RECORD bytes (uint8, a multiple of 32; on the host: uploaded) -> the (n_rows, n_frames, 128) uint8 roll on the device.
+        `rows`: None for all n_programs + 1 rows, "agnostic" for the last row only, or (first_row, n_rows).  `count`: an int32 device
+        tensor whose FIRST element is the number of records, read on the device (a Detokenizer.run_device counts tensor as it is).
+        Asynchronous: nothing is copied back."""
+        model = self._model()
+        if model is None:
+            raise ValueError("the piano roll object's model is gone")
+        if rows is None:
+            first, n_rows = 0, self.n_programs + 1
+        elif isinstance(rows, str):
+            if rows != "agnostic":
+                raise ValueError(f"rows={rows!r}: None, \"agnostic\" or (first_row, n_rows)")
+            first, n_rows = self.n_programs, 1
+        else:
+            first, n_rows = (int(v) for v in rows)
+        rec, n, cnt = self._side(model, "records", records, count)
+        out = torch.empty(max(n_rows, 0), max(int(n_frames), 0), 128, device=model.device, dtype=torch.uint8)
+        if int(n_frames) == 0 and n_rows > 0:                            # an empty roll has no buffer to hand over
+            return out
+        _lib.check(self._lib.ymt3_piano_roll(model._handle, self.ptr, _ptr(rec) if n else None, n, _ptr(cnt), int(n_frames), first, n_rows,
+                                             _ptr(out) if out.numel() else None, model._stream()))
+        return out
+
+    def metrics(self, ref_records: torch.Tensor, est_records: torch.Tensor, n_frames: int, ref_count: Optional[torch.Tensor] = None,
+                est_count: Optional[torch.Tensor] = None) -> torch.Tensor:
+        """NOTE_RECORD bytes for both sides -> the ((n_programs + 1) * 6 + 2,) int64 counts tensor on the device
+        (metrics.FrameMetricCounts.from_flat reads it).  Records and counts as roll() takes them.  Asynchronous: nothing is copied back."""
+        model = self._model()
+        if model is None:
+            raise ValueError("the piano roll object's model is gone")
+        (r, nr, rc), (e, ne, ec) = (self._side(model, name, rec, cnt) for name, rec, cnt in (("ref_records", ref_records, ref_count),
+                                                                                            ("est_records", est_records, est_count)))
+        counts = torch.empty((self.n_programs + 1) * 6 + 2, device=model.device, dtype=torch.int64)
+        _lib.check(self._lib.ymt3_frame_metrics(model._handle, self.ptr, _ptr(r) if nr else None, nr, _ptr(rc), _ptr(e) if ne else None, ne,
+                                                _ptr(ec), int(n_frames), _ptr(counts), model._stream()))
+        return counts
+
+    def close(self):
+        if getattr(self, "_c", None) is not None and self._c.value:
+            self._lib.ymt3_roll_destroy(self._c)
+            self._c = ctypes.c_void_p()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
 class YourMT3:
     def __init__(self, cfg: YMT3Config, weights: Optional[Dict[str, torch.Tensor]] = None, *, seed: int = 1234,
                  device: int = 0, max_batch: int = 64):
@@ -391,6 +474,13 @@ class YourMT3:
         m = NoteMetrics(self, n_programs, max_ref, max_est, **tolerances)
         self._constraints.add(m)
         return m
+
+    def compile_piano_roll(self, n_programs: int, max_frames: int, frames_per_second: float = 100.0, drum_program: int = DRUM_PROGRAM) -> PianoRoll:
+        """The device piano roll and frame metrics (include/ymt3.h, piano roll and frame metrics) for records of `n_programs` programs,
+        with bit-set scratch for up to `max_frames` frames: 32 * (n_programs + 1) bytes per frame."""
+        r = PianoRoll(self, n_programs, max_frames, frames_per_second, drum_program)
+        self._constraints.add(r)
+        return r
 
     def _start_states(self, constraint: Optional[DecodeConstraint], start_states, B: int) -> Optional[torch.Tensor]:
         """start_states -> (B, K) int32 device tensor, or None (state 0).  (K,) is every segment's; (B, K) per segment."""

@@ -3,6 +3,7 @@
 (n_seg, 1, 32767) -> model.inference_file(bsz, segments) -> TaskManager detokenise per channel -> notes -> MIDI."""
 from __future__ import annotations
 
+import math
 import os
 from typing import Optional, Union
 
@@ -11,7 +12,7 @@ import torch
 
 from .audio import load_wav_pcm
 from .midi import read_midi_notes, write_midi
-from .metrics import NoteMetricCounts, to_records
+from .metrics import FrameMetricCounts, NoteMetricCounts, to_records
 from .task_manager import TaskManager, drop_low_confidence
 
 
@@ -176,14 +177,19 @@ def score_notes(model, audio_info: Union[str, dict, np.ndarray], notes, task_man
 
 def evaluate(model, audio_info: Union[str, dict, np.ndarray], reference, task_manager: Optional[TaskManager] = None, bsz: int = 8,
              continuous: bool = False, subtask: Optional[str] = None, constrained: bool = False, programs=None, num_beams: int = 1,
-             length_penalty: float = 1.0, **tolerances) -> dict:
+             length_penalty: float = 1.0, frames: bool = False, frames_per_second: float = 100.0, **tolerances) -> dict:
     """How right is the transcription of this audio: note-level onset, onset+offset and drum F1 against `reference` (a list of Note, or the
     path of a .mid file), by the rules of yourmt3_amd/metrics.py.  The audio is decoded as transcribe(device_detok=True) decodes it
     (`continuous`, `subtask`, `constrained`, `programs`, `num_beams`, `length_penalty` as there); the ids become note records on the device
     (Detokenizer.run_device) and are matched against the uploaded reference there (NoteMetrics.run, reading the number of transcribed notes
     from the detokeniser's counter on the device): one copy back, of the counts.  `tolerances`: onset_tol, offset_min_tol, offset_ratio.
     -> NoteMetricCounts.summary(): onset_f / offset_f (instrument-agnostic, with _p and _r), drum_onset_f, multi_f, per_program, skipped and
-    "counts" (the (n_programs + 1, 2, 3) integers)."""
+    "counts" (the (n_programs + 1, 2, 3) integers).
+    `frames=True` adds frame-level F1 (PianoRoll.metrics; the rules: yourmt3_amd/metrics.py, frame metrics) over n_frames = max(1,
+    ceil(end_sec * frames_per_second)) frames, end_sec being the audio's length as the detokeniser gets it.  It runs on the same records
+    and counter on the device, after the note metrics, and the copy back is still one.  The summary gains frame_f, frame_p, frame_r,
+    frame_acc (instrument-agnostic), frame_err ({"sub", "miss", "fa", "total"}), multi_frame_f, frame_counts (the (n_programs + 1, 6)
+    integers) and n_frames."""
     num_beams = int(num_beams)
     if num_beams < 1:
         raise ValueError(f"num_beams={num_beams} must be >= 1")
@@ -231,11 +237,47 @@ def evaluate(model, audio_info: Union[str, dict, np.ndarray], reference, task_ma
             constraint.close()
     detok = model.compile_detokenizer(task_manager, max(n, 1), L)
     metrics = model.compile_note_metrics(n_programs, max(len(ref), 1), detok.capacity, **tolerances)
+    end_sec = model.last_ingest_samples / cfg.sample_rate
+    roll = None
     try:
-        est, est_counts = detok.run_device(tokens, None, torch.tensor(start_secs, dtype=torch.float64), model.last_ingest_samples / cfg.sample_rate)
-        counts = metrics.run(torch.from_numpy(ref.view(np.uint8).reshape(-1).copy()), est, est_count=est_counts)
+        if frames:
+            n_frames = max(1, math.ceil(end_sec * float(frames_per_second)))
+            roll = model.compile_piano_roll(n_programs, n_frames, frames_per_second, metrics.drum_program)
+        est, est_counts = detok.run_device(tokens, None, torch.tensor(start_secs, dtype=torch.float64), end_sec)
+        ref_dev = torch.from_numpy(ref.view(np.uint8).reshape(-1).copy()).to(model.device)
+        counts = metrics.run(ref_dev, est, est_count=est_counts)
+        if frames:                                                       # int32 and int64 counts leave in one copy
+            counts = torch.cat([counts.to(torch.int64), roll.metrics(ref_dev, est, n_frames, est_count=est_counts)])
         flat = counts.cpu().numpy()
     finally:
+        if roll is not None:
+            roll.close()
         metrics.close()
         detok.close()
-    return NoteMetricCounts.from_flat(flat, n_programs, metrics.drum_program).summary()
+    n_note = (n_programs + 1) * 6 + 2
+    out = NoteMetricCounts.from_flat(flat[:n_note], n_programs, metrics.drum_program).summary()
+    if frames:
+        out.update(FrameMetricCounts.from_flat(flat[n_note:], n_programs, metrics.drum_program).summary(), n_frames=n_frames)
+    return out
+
+
+def piano_roll(model, notes, end_sec: float, frames_per_second: float = 100.0, per_program: bool = False,
+               task_manager: Optional[TaskManager] = None) -> torch.Tensor:
+    """The piano roll of `notes` (a list of Note, a NOTE_RECORD array, or the path of a .mid file) over n_frames = max(1, ceil(end_sec *
+    frames_per_second)) frames, rasterised on the device (PianoRoll.roll; the rules: yourmt3_amd/metrics.py, frame metrics).
+    -> the (n_frames, 128) uint8 instrument-agnostic roll (all pitched notes; drums are not in it), or with `per_program=True` all
+    (n_programs + 1, n_frames, 128) rows, the agnostic one last; a device tensor.  The programs are the TaskManager's."""
+    if task_manager is None:
+        task_manager = TaskManager("mc13_full_plus_256" if model.cfg.n_channels == 13 else "mt3_full_plus")
+    if isinstance(notes, (str, os.PathLike)):
+        with open(notes, "rb") as f:
+            notes = read_midi_notes(f.read())
+    rec = to_records(notes)
+    lo, hi = task_manager.codec.range_of("program")
+    n_frames = max(1, math.ceil(float(end_sec) * float(frames_per_second)))
+    roll = model.compile_piano_roll(hi - lo, n_frames, frames_per_second)
+    try:
+        out = roll.roll(torch.from_numpy(rec.view(np.uint8).reshape(-1).copy()), n_frames, rows=None if per_program else "agnostic")
+    finally:
+        roll.close()
+    return out if per_program else out[0]
