@@ -31,7 +31,8 @@
  *   - the library owns weights, KV caches and scratch inside the handle; nothing is
  *     allocated after ymt3_create() except by ymt3_constraint_create() (the caller's automaton tables) and
  *     ymt3_detok_create() (the device detokeniser's scratch), ymt3_tok_create() (the device tokeniser's) and
- *     ymt3_metrics_create() (the note metrics') and ymt3_roll_create() (the piano roll's);
+ *     ymt3_metrics_create() (the note metrics') and ymt3_roll_create() (the piano roll's) and ymt3_ingest_stream_create() (the
+ *     streaming ingest's history) and ymt3_detok_state_create() (the incremental detokeniser's state);
  *   - return value: 0 = ok, non-zero = error; the message is in ymt3_last_error()
  *     (thread local).  No exception ever crosses this boundary;
  *   - one handle per device per host thread.  No internal host threads.
@@ -97,6 +98,47 @@ size_t ymt3_device_bytes(ymt3_handle h);
 int ymt3_ingest_plan(ymt3_handle h, int64_t n_frames, int sample_rate_in, int64_t* n_samples_out, int* n_segments);
 int ymt3_ingest(ymt3_handle h, const void* pcm_dev, int pcm_format, int64_t n_frames, int n_channels,
                 int sample_rate_in, float* segments_dev, int n_segments, void* stream);
+
+/* Streaming ingest: ymt3_ingest for PCM that arrives in chunks (YourMT3.compile_ingest_stream).  Take the rows that every
+ * ymt3_ingest_stream_push and then ymt3_ingest_stream_finish write to segments_dev, in order: concatenated they are the (n_segments,
+ * segment_samples) buffer ymt3_ingest writes for the concatenated PCM, BIT FOR BIT for finite PCM and for every way of cutting the PCM
+ * into chunks (both forms mix a frame and sum a tap row with the same device functions of yourmt3_amd/csrc/ingest.hip).
+ *   - finality: output sample n reads input frames k0(n) - J + 1 .. k0(n) with k0(n) = floor((n + r) * down / up) (up / down the reduced
+ *     rate ratio, J the taps per phase, r the alignment of resample_poly), so once N frames have arrived exactly
+ *     F(N) = max(0, ceil(N * up / down) - r) samples are final.  A push computes the samples that became final, keeps them in a partial
+ *     segment inside the object, and writes to the caller only WHOLE segments: floor(F(N) / segment_samples) minus those already
+ *     written.  The last r samples, and the zero padding of the last segment, come from ymt3_ingest_stream_finish, which takes the
+ *     frames that never arrived as zeros: what ymt3_ingest computes.  A stream of zero frames finishes with one all-zero segment.
+ *   - n_ready (may be NULL) is the number of rows the call wrote; it is host arithmetic on the frame counts (ymt3_ingest_stream_plan
+ *     gives it for a push of n_frames without doing anything), so nothing is synchronised to learn it.  n_samples_total (may be NULL)
+ *     is ymt3_ingest_plan's n_samples_out for all the frames pushed.
+ *   - state: a ring of mono frames (every frame is mixed once, when it arrives; J - 1 + max_chunk_frames frames rounded up to a power
+ *     of two) and two partial-segment buffers.  Allocated by ymt3_ingest_stream_create, which is synchronous and, for a new rate pair,
+ *     designs the filter as the first ymt3_ingest call does.  The ring costs 4 bytes per frame of J - 1 + max_chunk_frames rounded up to a
+ *     power of two -- up to twice that, 128 MB at the cap of 2^24 frames -- so size max_chunk_frames by the chunks that really arrive
+ *     (100 ms at 48 kHz: 4800 frames, a 32 KB ring); rate pairs ymt3_ingest refuses are refused here with the same code.
+ *     push / finish / reset allocate nothing and are asynchronous on `stream`: a push is two launches (mix, resample), a finish one.
+ *     The calls of one object must be ordered on the device as they are on the host (one stream, or the caller's own events).
+ *   - non-finite PCM: a zero-padding tap is multiplied by a clamped window sample in both forms, so a non-finite frame can reach
+ *     a different few outputs in the neighbourhood of its own under a different workgroup alignment.  Guaranteed: every output
+ *     whose input frames k0(n) - J + 1 .. k0(n) all lie more than W = floor(255 * down / up) + J + 2 frames (the kernels' LDS window) from
+ *     every non-finite frame equals ymt3_ingest's, bit for bit.
+ *   - YMT3_ERR_ARG, with object and handle still usable and the stream's state unchanged: n_frames < 0 or > max_chunk_frames,
+ *     max_segments below the rows the call writes, a push, plan or finish after ymt3_ingest_stream_finish without a
+ *     ymt3_ingest_stream_reset, a NULL pcm_dev with n_frames > 0, a NULL segments_dev when the call writes a row; at create
+ *     max_chunk_frames outside [1, 2^24], n_channels outside [1, 64], an unknown pcm_format.
+ * The object belongs to h; ymt3_ingest_stream_destroy frees it (NULL is a no-op), before or after the handle's destruction.
+ * ymt3_ingest_stream_reset starts a new stream on the same object.  The handle's decode state is left alone. */
+typedef struct ymt3_ingest_stream_s* ymt3_ingest_stream;
+int  ymt3_ingest_stream_create(ymt3_handle h, int sample_rate_in, int n_channels, int pcm_format, int64_t max_chunk_frames,
+                               ymt3_ingest_stream* out);
+void ymt3_ingest_stream_destroy(ymt3_ingest_stream s);
+int  ymt3_ingest_stream_reset(ymt3_handle h, ymt3_ingest_stream s, void* stream);
+int  ymt3_ingest_stream_plan(ymt3_ingest_stream s, int64_t n_frames, int* n_ready);
+int  ymt3_ingest_stream_push(ymt3_handle h, ymt3_ingest_stream s, const void* pcm_dev, int64_t n_frames, float* segments_dev,
+                             int max_segments, int* n_ready, void* stream);
+int  ymt3_ingest_stream_finish(ymt3_handle h, ymt3_ingest_stream s, float* segments_dev, int max_segments, int* n_ready,
+                               int64_t* n_samples_total, void* stream);
 
 /* a1+a2: audio (B, segment_samples) f32 -> log-mel (B, n_frames, n_mels) f32. */
 int ymt3_logmel(ymt3_handle h, const float* audio_dev, int B, float* mel_dev, void* stream);
@@ -387,6 +429,55 @@ int  ymt3_detokenize(ymt3_handle h, ymt3_detok d, const int32_t* tokens_dev, con
                      int n_segments, int n_steps, long long seg_stride, long long chan_stride,
                      const double* start_sec_dev, double end_sec,
                      void* notes_dev, long long capacity, int32_t* counts_dev /* [2]: n_notes, n_invalid */, void* stream);
+
+/* Incremental detokeniser: ymt3_detokenize for segments that arrive over time (Detokenizer.new_state / push_device / finish_device,
+ * TaskManager.tokens_to_notes_stream).  The specification is the host's NoteStream (yourmt3_amd/task_manager.py), the incremental form of
+ * note_events_to_notes: take the records that every ymt3_detokenize_push and then ymt3_detokenize_finish write, and they are, as a set,
+ * the records ymt3_detokenize writes for all the segments at once with the same end_sec -- the same f64 times bit for bit, the same
+ * scores -- for every way of cutting the segments into pushes, as long as no call reports n_forced != 0.  Per call the records are
+ * exactly those NoteStream returns for the call.
+ *   - records, token table, strides, scores and the time arithmetic are those of ymt3_detokenize; kernel (a) is the same kernel, the
+ *     merge kernel is its form (c) (yourmt3_amd/csrc/detok.hip), which starts every key's walk from the carried state and stores it back.
+ *   - a push: n_segments >= 0 segments, LATER than every segment pushed before; start_sec_dev (n_segments,) f64 strictly increasing
+ *     (not checked on the device, as for ymt3_detokenize).  horizon_sec is the start time of the next segment not yet pushed; +inf means
+ *     that no further segment can arrive before the finish.  n_segments = 0 only moves the horizon.
+ *   - what a call writes: every pitched note that ended -- by an offset, a re-trigger, or a missing tie at a segment start.  A note still
+ *     sounding after the push's last segment stays in the state (its onset, its score, a valid bit per (channel, program, pitch)) and is
+ *     continued by a tie in the next push's first segment, else closed at that segment's start.  A pitched record never changes once
+ *     written.  A drum hit can: a hit of a later segment at the same f64 time and pitch is merged into it and may raise its score, and
+ *     every event of a later segment lies at or after that segment's start.  So a push writes the hits with time < horizon_sec and HOLDS
+ *     the others in the state, still open to de-duplication; a later push whose horizon exceeds their time, or the finish, writes them.
+ *   - the bound on held hits: every (channel, drum pitch) holds at most max_held.  When a push would leave more, the earliest surplus hits
+ *     are written at once, earliest time first, and counted in n_forced: a non-zero n_forced tells the caller that exactness may have
+ *     been lost (a later duplicate of a forced hit becomes a second record).
+ *   - ymt3_detokenize_finish writes every held hit and closes every sounding note at end_sec (dropped if end_sec is not after its onset),
+ *     the rule of the one-shot call's tail.  After it the state takes no call until ymt3_detok_state_reset.
+ *   - counts_dev: [3] int32 = { n_notes, n_invalid, n_forced } of THIS call; the call zeroes it first.
+ *   - capacity bound, exactly: capacity >= n_segments * n_channels * n_steps + ymt3_detok_state_carry(st), else YMT3_ERR_ARG (the finish:
+ *     n_segments = 0).  ymt3_detok_state_carry = n_channels * 128 * (n_programs - 1 + max_held), n_programs being one more than the largest
+ *     program of the token table (and of drum_program): a call can close one carried note per pitched key and write max_held held hits per
+ *     drum pitch on top of the one record per token of ymt3_detokenize.
+ *   - YMT3_ERR_ARG, with handle, detokeniser and state still usable and the state unchanged: the argument errors of ymt3_detokenize, a
+ *     NULL notes_dev, a capacity below the bound, a state created for another detokeniser, a call after the finish without a reset, and a
+ *     horizon_sec that is -inf, NaN or below the previous push's horizon (the start times are device memory and are not read: what the
+ *     host can check of "before the last pushed start" is the previous horizon, which no later start may precede; the Python wrapper
+ *     checks the start times themselves).
+ * ymt3_detok_state_create: synchronous; allocates the state, 16 bytes per (channel, program, pitch) and 2 x 16 x max_held bytes per
+ * (channel, drum pitch); max_held in [1, 4096].  The state belongs to h and to d; ymt3_detok_state_destroy frees it (NULL is a no-op),
+ * before or after the handle's destruction.  ymt3_detok_state_reset empties it, asynchronously on `stream`.  push and finish are
+ * asynchronous on `stream`, allocate nothing, use the detokeniser's scratch (one call at a time per detokeniser, whatever the state)
+ * and leave the handle's decode state alone. */
+typedef struct ymt3_detok_state_s* ymt3_detok_state;
+int  ymt3_detok_state_create(ymt3_handle h, ymt3_detok d, int max_held, ymt3_detok_state* out);
+void ymt3_detok_state_destroy(ymt3_detok_state st);
+int  ymt3_detok_state_reset(ymt3_handle h, ymt3_detok_state st, void* stream);
+long long ymt3_detok_state_carry(ymt3_detok_state st);
+int  ymt3_detokenize_push(ymt3_handle h, ymt3_detok d, ymt3_detok_state st, const int32_t* tokens_dev, const float* scores_dev /* may be NULL */,
+                          int n_segments, int n_steps, long long seg_stride, long long chan_stride,
+                          const double* start_sec_dev, double horizon_sec,
+                          void* notes_dev, long long capacity, int32_t* counts_dev /* [3]: n_notes, n_invalid, n_forced */, void* stream);
+int  ymt3_detokenize_finish(ymt3_handle h, ymt3_detok d, ymt3_detok_state st, double end_sec,
+                            void* notes_dev, long long capacity, int32_t* counts_dev /* [3] */, void* stream);
 
 /* Device tokeniser: notes -> token ids without a host loop, the inverse of the device detokeniser (TaskManager.notes_to_tokens_device;
  * the specification is the host path, TaskManager.notes_to_tokens of yourmt3_amd/task_manager.py, which it reproduces exactly: the same

@@ -2,7 +2,7 @@
 `import yourmt3_amd` works without a GPU or the built library."""
 
 __all__ = ["YMT3Config", "YourMT3", "TaskManager", "transcribe", "score_notes", "evaluate", "note_metrics", "NoteMetrics", "piano_roll", "frame_metrics",
-           "FrameMetricCounts", "PianoRoll", "baseline_config"]
+           "FrameMetricCounts", "PianoRoll", "baseline_config", "LiveTranscriber", "NoteStream"]
 
 
 def __getattr__(name):
@@ -36,6 +36,12 @@ def __getattr__(name):
     if name in ("frame_metrics", "FrameMetricCounts"):
         from . import metrics
         return getattr(metrics, name)
+    if name == "LiveTranscriber":
+        from .transcribe import LiveTranscriber
+        return LiveTranscriber
+    if name == "NoteStream":
+        from .task_manager import NoteStream
+        return NoteStream
     if name == "PianoRoll":
         from .model import PianoRoll
         return PianoRoll

@@ -28,6 +28,10 @@ SYMBOLS = [
     "ymt3_tok_create", "ymt3_tok_destroy", "ymt3_tokenize",
     "ymt3_metrics_create", "ymt3_metrics_destroy", "ymt3_note_metrics",
     "ymt3_roll_create", "ymt3_roll_destroy", "ymt3_piano_roll", "ymt3_frame_metrics",
+    "ymt3_ingest_stream_create", "ymt3_ingest_stream_destroy", "ymt3_ingest_stream_reset", "ymt3_ingest_stream_plan",
+    "ymt3_ingest_stream_push", "ymt3_ingest_stream_finish",
+    "ymt3_detok_state_create", "ymt3_detok_state_destroy", "ymt3_detok_state_reset", "ymt3_detok_state_carry",
+    "ymt3_detokenize_push", "ymt3_detokenize_finish",
 ]
 
 _lib = None
@@ -178,6 +182,32 @@ def load() -> ctypes.CDLL:
     lib.ymt3_piano_roll.restype = i32
     lib.ymt3_frame_metrics.argtypes = [vp, vp, vp, ctypes.c_longlong, vp, vp, ctypes.c_longlong, vp, ctypes.c_longlong, vp, vp]
     lib.ymt3_frame_metrics.restype = i32
+    i64 = ctypes.c_int64
+    lib.ymt3_ingest_stream_create.argtypes = [vp, i32, i32, i32, i64, ctypes.POINTER(vp)]
+    lib.ymt3_ingest_stream_create.restype = i32
+    lib.ymt3_ingest_stream_destroy.argtypes = [vp]
+    lib.ymt3_ingest_stream_destroy.restype = None
+    lib.ymt3_ingest_stream_reset.argtypes = [vp, vp, vp]
+    lib.ymt3_ingest_stream_reset.restype = i32
+    lib.ymt3_ingest_stream_plan.argtypes = [vp, i64, ctypes.POINTER(ctypes.c_int)]
+    lib.ymt3_ingest_stream_plan.restype = i32
+    lib.ymt3_ingest_stream_push.argtypes = [vp, vp, vp, i64, vp, i32, ctypes.POINTER(ctypes.c_int), vp]
+    lib.ymt3_ingest_stream_push.restype = i32
+    lib.ymt3_ingest_stream_finish.argtypes = [vp, vp, vp, i32, ctypes.POINTER(ctypes.c_int), ctypes.POINTER(i64), vp]
+    lib.ymt3_ingest_stream_finish.restype = i32
+    ll, f64 = ctypes.c_longlong, ctypes.c_double
+    lib.ymt3_detok_state_create.argtypes = [vp, vp, i32, ctypes.POINTER(vp)]
+    lib.ymt3_detok_state_create.restype = i32
+    lib.ymt3_detok_state_destroy.argtypes = [vp]
+    lib.ymt3_detok_state_destroy.restype = None
+    lib.ymt3_detok_state_reset.argtypes = [vp, vp, vp]
+    lib.ymt3_detok_state_reset.restype = i32
+    lib.ymt3_detok_state_carry.argtypes = [vp]
+    lib.ymt3_detok_state_carry.restype = ll
+    lib.ymt3_detokenize_push.argtypes = [vp, vp, vp, vp, vp, i32, i32, ll, ll, vp, f64, vp, ll, vp, vp]
+    lib.ymt3_detokenize_push.restype = i32
+    lib.ymt3_detokenize_finish.argtypes = [vp, vp, vp, f64, vp, ll, vp, vp]
+    lib.ymt3_detokenize_finish.restype = i32
     for n in ("ymt3_logmel", "ymt3_encode", "ymt3_decode_greedy", "ymt3_transcribe_segments", "ymt3_test_gemm"):
         getattr(lib, n).restype = i32
     if lib.ymt3_abi_version() != 3:

@@ -12,6 +12,8 @@
 //     do not interact: a counting sort over the n_programs * 128 keys (32-bit LDS counters) buckets the channel's items, scattered
 //     segment by segment so that a bucket is in segment order; one lane per key then orders its bucket (an insertion pass that
 //     only ever moves items inside one segment's group) and walks it with the host's rules.
+// (c) detok_notes_carry_kernel, the incremental form of (b): the same bucketing, and per-key walks that start from the state an
+//     earlier call left (the sounding note of a pitched key, the held hits of a drum pitch) and store it back.
 #include "common.h"
 #include "kernels.h"
 
@@ -212,9 +214,10 @@ __device__ void walk_drum(const DetokArgs& a, int ch, int prog, int pitch, unsig
     }
 }
 
-__global__ __launch_bounds__(NOTES_THREADS) void detok_notes_kernel(DetokArgs a) {
-    extern __shared__ unsigned hist[];                                  // [n_keys] counters, then [16] wave sums
-    const int ch = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+// Bucket one channel's items by key (the counting sort of (b)): on return S is the channel's bucketed copy, the bucket of key k is
+// S[koff[k], hist[k]) with its segments in order.  Every thread of the workgroup calls it.
+__device__ __forceinline__ void bucket_channel(const DetokArgs& a, int ch, unsigned* hist, unsigned*& koff, unsigned long long*& S) {
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int n_keys = a.n_programs * DETOK_PITCHES;
     unsigned* wsum = hist + n_keys;
     const long long cbase = (long long)ch * a.n_seg * a.L;              // the channel's slots in items / keys / sorted
@@ -242,7 +245,7 @@ __global__ __launch_bounds__(NOTES_THREADS) void detok_notes_kernel(DetokArgs a)
     __syncthreads();
     unsigned off = incl - mine;
     for (int w = 0; w < wave; ++w) off += wsum[w];
-    unsigned* koff = a.key_off + (long long)ch * n_keys;
+    koff = a.key_off + (long long)ch * n_keys;
     for (int k = k0; k < k1; ++k) {
         const unsigned c = hist[k];
         hist[k] = off;
@@ -251,7 +254,7 @@ __global__ __launch_bounds__(NOTES_THREADS) void detok_notes_kernel(DetokArgs a)
     }
     __syncthreads();
     // scatter, one segment at a time: a bucket then holds its segments in order (within a segment the order is the atomics')
-    unsigned long long* S = a.sorted + cbase;
+    S = a.sorted + cbase;
     for (int s = 0; s < a.n_seg; ++s) {
         const int cnt = rc[s];
         const long long rbase = cbase + (long long)s * a.L;
@@ -261,21 +264,165 @@ __global__ __launch_bounds__(NOTES_THREADS) void detok_notes_kernel(DetokArgs a)
         }
         __syncthreads();
     }
+}
+
+// order a bucket by the packed item (an insertion pass that only ever moves items inside one segment's group)
+__device__ __forceinline__ void order_bucket(unsigned long long* S, long long b, long long e) {
+    unsigned long long prev = S[b];
+    for (long long i = b + 1; i < e; ++i) {
+        const unsigned long long x = S[i];
+        if (x >= prev) { prev = x; continue; }
+        long long j = i;
+        while (j > b && S[j - 1] > x) { S[j] = S[j - 1]; --j; }
+        S[j] = x;
+    }
+}
+
+__global__ __launch_bounds__(NOTES_THREADS) void detok_notes_kernel(DetokArgs a) {
+    extern __shared__ unsigned hist[];                                  // [n_keys] counters, then [16] wave sums
+    const int ch = blockIdx.x, tid = threadIdx.x;
+    const int n_keys = a.n_programs * DETOK_PITCHES;
+    unsigned* koff;
+    unsigned long long* S;
+    bucket_channel(a, ch, hist, koff, S);
     // one lane per key: order the bucket, then merge.  hist[k] is now the bucket's end.
     for (int k = tid; k < n_keys; k += NOTES_THREADS) {
         const long long b = koff[k], e = hist[k];
         if (b == e) continue;
-        unsigned long long prev = S[b];
-        for (long long i = b + 1; i < e; ++i) {
-            const unsigned long long x = S[i];
-            if (x >= prev) { prev = x; continue; }
-            long long j = i;
-            while (j > b && S[j - 1] > x) { S[j] = S[j - 1]; --j; }
-            S[j] = x;
-        }
+        order_bucket(S, b, e);
         const int prog = k / DETOK_PITCHES, pitch = k % DETOK_PITCHES;
         if (prog == a.drum_program) walk_drum(a, ch, prog, pitch, S, b, e);
         else walk_pitched(a, ch, prog, pitch, S, b, e);
+    }
+}
+
+// ---------------------------------------------------------------- incremental form (include/ymt3.h, incremental detokeniser)
+// The per-key walks of (b) with their state carried between calls (tests/live_model.py states them in plain Python).  Segment indices
+// are those of the push: the last segment of the previous push is segment -1.
+
+// pitched key: walk_pitched starting from the carried note and storing back what still sounds after the push's last segment
+__device__ void walk_pitched_carry(const DetokArgs& a, const DetokCarryArgs& c, int ch, int k, const unsigned long long* S, long long b, long long e) {
+    const int prog = k / DETOK_PITCHES, pitch = k % DETOK_PITCHES;
+    DetokSounding& st = c.sounding[(long long)ch * a.n_programs * DETOK_PITCHES + k];
+    bool active = st.valid != 0;
+    double on = st.onset;
+    float score = st.score;
+    if (a.n_seg > 0) {
+        int q = -1;                                                     // the last segment that confirmed the note
+        for (long long i = b; i < e; ++i) {
+            const unsigned long long x = S[i];
+            const int s = item_seg(x);
+            const bool tie = !(x & NOT_TIE);
+            if (active && s > q) {
+                if (tie && s == q + 1) { q = s; continue; }
+                const double end = a.start[q + 1];                      // no tie in segment q + 1: the note ends at its start
+                if (end > on) emit_note(a, on, end, prog, pitch, 0, score);
+                active = false;
+            }
+            if (tie) continue;
+            const double t = event_time(a, s, item_step(x));
+            if (item_vel(x)) {
+                if (active && t > on) emit_note(a, on, t, prog, pitch, 0, score);
+                active = true; on = t; score = item_score(a, ch, x); q = s;
+            } else if (active) {
+                if (t > on) emit_note(a, on, t, prog, pitch, 0, score);
+                active = false;
+            }
+        }
+        if (active && q != a.n_seg - 1) {                               // a later segment of this push did not tie it
+            const double end = a.start[q + 1];
+            if (end > on) emit_note(a, on, end, prog, pitch, 0, score);
+            active = false;
+        }
+    }
+    if (active && c.finish) {
+        if (a.end_sec > on) emit_note(a, on, a.end_sec, prog, pitch, 0, score);
+        active = false;
+    }
+    st.onset = on; st.score = score; st.valid = active ? 1 : 0;
+}
+
+// drum key: the held hits (distinct times, ascending; earlier in processing order than anything new) merged with the push's bucket.
+// Hits below the horizon leave; the others are held again, at most max_held of them: the earliest surplus ones leave too and count as
+// forced.  Pass 0 counts, pass 1 emits and stores.
+__device__ void walk_drum_carry(const DetokArgs& a, const DetokCarryArgs& c, int ch, int prog, int pitch, unsigned long long* S, long long b, long long e) {
+    if (e > b) {
+        double tprev = event_time(a, item_seg(S[b]), item_step(S[b]));
+        for (long long i = b + 1; i < e; ++i) {
+            const unsigned long long x = S[i];
+            const double t = event_time(a, item_seg(x), item_step(x));
+            if (t >= tprev) { tprev = t; continue; }
+            long long j = i;
+            while (j > b) {
+                const unsigned long long y = S[j - 1];
+                if (!(event_time(a, item_seg(y), item_step(y)) > t)) break;
+                S[j] = y;
+                --j;
+            }
+            S[j] = x;
+        }
+    }
+    const long long slot = (long long)ch * DETOK_PITCHES + pitch;
+    const DetokHeld* Hin = c.held_in + slot * c.max_held;
+    DetokHeld* Hout = c.held_out + slot * c.max_held;
+    const int nh = min(max(c.held_count_in[slot], 0), c.max_held);
+    int total = 0, below = 0, n_emit = 0;
+    for (int pass = 0; pass < 2; ++pass) {
+        int i = 0, idx = 0;
+        long long j = b;
+        while (i < nh || j < e) {
+            const double tj = j < e ? event_time(a, item_seg(S[j]), item_step(S[j])) : 0.0;
+            const bool take_held = i < nh && (j >= e || Hin[i].time <= tj);
+            const bool take_new = j < e && (!take_held || tj == Hin[i].time);
+            const double t = take_held ? Hin[i].time : tj;
+            float score = 0.f;
+            if (pass) score = take_held ? Hin[i].score : item_score(a, ch, S[j]);
+            if (take_held) ++i;
+            if (take_new) {
+                if (pass && take_held) { const float sc = item_score(a, ch, S[j]); if (sc > score) score = sc; }
+                for (++j; j < e; ++j) {
+                    const unsigned long long y = S[j];
+                    if (event_time(a, item_seg(y), item_step(y)) != t) break;
+                    if (pass) { const float sc = item_score(a, ch, y); if (sc > score) score = sc; }
+                }
+            }
+            if (!pass) {
+                ++total;
+                if (t < c.horizon) ++below;
+            } else if (idx < n_emit) {
+                double off;
+                {
+#pragma clang fp contract(off)
+                    off = t + 0.01;                                     // DRUM_NOTE_SEC
+                }
+                emit_note(a, t, off, prog, pitch, 1, score);
+            } else {
+                Hout[idx - n_emit] = DetokHeld{t, score, 0};
+            }
+            ++idx;
+        }
+        if (!pass) {
+            const int forced = max(0, total - below - c.max_held);
+            n_emit = below + forced;
+            if (forced) atomicAdd(&a.counts[2], forced);
+        }
+    }
+    c.held_count_out[slot] = total - n_emit;
+}
+
+__global__ __launch_bounds__(NOTES_THREADS) void detok_notes_carry_kernel(DetokArgs a, DetokCarryArgs c) {
+    extern __shared__ unsigned hist[];                                  // [n_keys] counters, then [16] wave sums
+    const int ch = blockIdx.x, tid = threadIdx.x;
+    const int n_keys = a.n_programs * DETOK_PITCHES;
+    unsigned* koff = nullptr;
+    unsigned long long* S = nullptr;
+    if (a.n_seg > 0) bucket_channel(a, ch, hist, koff, S);             // (uniform over the grid)
+    for (int k = tid; k < n_keys; k += NOTES_THREADS) {
+        const long long b = a.n_seg > 0 ? koff[k] : 0, e = a.n_seg > 0 ? hist[k] : 0;
+        if (e > b) order_bucket(S, b, e);
+        const int prog = k / DETOK_PITCHES, pitch = k % DETOK_PITCHES;
+        if (prog == a.drum_program) walk_drum_carry(a, c, ch, prog, pitch, S, b, e);
+        else walk_pitched_carry(a, c, ch, k, S, b, e);
     }
 }
 
@@ -285,7 +432,20 @@ constexpr size_t NOTES_LDS_MAX = (size_t)DETOK_MAX_PROGRAMS * DETOK_PITCHES * si
 
 int init_detok_kernels() {
     return hipFuncSetAttribute(reinterpret_cast<const void*>(detok_notes_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)NOTES_LDS_MAX) !=
-           hipSuccess;
+               hipSuccess ||
+           hipFuncSetAttribute(reinterpret_cast<const void*>(detok_notes_carry_kernel), hipFuncAttributeMaxDynamicSharedMemorySize,
+                               (int)NOTES_LDS_MAX) != hipSuccess;
+}
+
+int launch_detok_carry(const DetokArgs& a, const DetokCarryArgs& c, hipStream_t stream) {
+    if (a.n_seg < 0 || a.n_chan <= 0) return 0;
+    if (a.n_seg > 0 && (a.L <= 0 || a.L > DETOK_MAX_STEPS || a.n_seg > DETOK_MAX_SEGMENTS)) return -1;
+    if (a.n_programs <= 0 || a.n_programs > DETOK_MAX_PROGRAMS || a.drum_program >= a.n_programs || c.max_held < 1) return -2;
+    if ((long long)a.n_seg * a.n_chan > 0x7fffffffLL || (long long)a.n_seg * a.L > 0xffffffffLL) return -3;
+    const size_t lds = (size_t)a.n_programs * DETOK_PITCHES * sizeof(unsigned) + (NOTES_THREADS / WAVE) * sizeof(unsigned);
+    if (a.n_seg > 0) detok_rows_kernel<<<a.n_seg * a.n_chan, WAVE, (size_t)a.L * sizeof(uint16_t), stream>>>(a);
+    detok_notes_carry_kernel<<<a.n_chan, NOTES_THREADS, lds, stream>>>(a, c);
+    return 0;
 }
 
 int launch_detok(const DetokArgs& a, hipStream_t stream) {

@@ -27,6 +27,20 @@ struct IngestArgs {
     int up, down, J, Jp, n_channels, s16, window;   // window: LDS floats per workgroup
 };
 int launch_ingest(const IngestArgs& a, hipStream_t stream);
+// streaming form: one push (or the finish) of a ymt3_ingest_stream.  Output sample n of the whole stream is addressed by its number.
+struct IngestStreamArgs {
+    const void* pcm;          // [n_new][n_channels] the frames of this push
+    float* hist;              // [hist_mask + 1] mono ring: frame k at k & hist_mask
+    const float* taps;        // as IngestArgs
+    float* out;               // the caller's rows: sample n at out[n - n_row0] for n < n_row_end
+    const float* part_old;    // partial segment kept by earlier pushes: sample n at part_old[n - n_row0] for n < n_done
+    float* part_new;          // partial segment this call leaves: sample n at part_new[n - n_row_end] for n >= n_row_end
+    long long hist_mask, n_new, n_in;      // n_in: frames arrived, these n_new included
+    long long g0, n_done, n_end, n_total;  // the launch covers [g0, n_total): copy below n_done, compute below n_end, then zero
+    long long n_row0, n_row_end, r;
+    int up, down, J, Jp, n_channels, s16, window;
+};
+int launch_ingest_stream(const IngestStreamArgs& a, hipStream_t stream);
 
 // ---------------------------------------------------------------- device detokeniser (detok.hip; include/ymt3.h, device detokeniser)
 constexpr int DETOK_PITCHES = 128;        // pitch / drum values per program: a merge key is program * 128 + pitch
@@ -58,6 +72,20 @@ struct DetokArgs {
 };
 int init_detok_kernels();
 int launch_detok(const DetokArgs& a, hipStream_t stream);
+// incremental form (ymt3_detokenize_push / ymt3_detokenize_finish): the state a ymt3_detok_state carries between calls
+struct DetokSounding { double onset; float score; int32_t valid; };     // per (channel, key): the note still sounding after the last pushed segment
+struct DetokHeld { double time; float score; int32_t pad; };            // a drum hit not yet below the horizon
+struct DetokCarryArgs {
+    DetokSounding* sounding;              // [n_chan][n_programs * 128]
+    const DetokHeld* held_in;             // [n_chan][128][max_held] ascending times, the first held_count_in valid
+    DetokHeld* held_out;                  // the other copy: what this call leaves
+    const int* held_count_in;             // [n_chan][128]
+    int* held_count_out;
+    int max_held, finish;                 // finish: close every sounding note at end_sec
+    double horizon;                       // hits with time < horizon leave the state
+};
+// DetokArgs as for launch_detok (n_seg may be 0: nothing is decoded, the state alone is walked); counts is [3], n_forced last
+int launch_detok_carry(const DetokArgs& a, const DetokCarryArgs& c, hipStream_t stream);
 
 // ---------------------------------------------------------------- device tokeniser (tok.hip; include/ymt3.h, device tokeniser)
 constexpr int TOK_PITCHES = 128;          // pitch values per program: a tie key is program * 128 + pitch

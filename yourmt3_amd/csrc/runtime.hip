@@ -790,6 +790,125 @@ extern "C" int ymt3_detokenize(ymt3_handle h, ymt3_detok d, const int32_t* token
     return YMT3_OK;
 }
 
+// ---------------------------------------------------------------- incremental detokeniser (include/ymt3.h)
+struct ymt3_detok_state_s {
+    ymt3_ctx* owner;
+    ymt3_detok detok;                       // the detokeniser it was created for (compared by address only)
+    int device, n_chan, n_programs, max_held;
+    DetokSounding* sounding = nullptr;      // [n_chan][n_programs * 128]
+    DetokHeld* held[2] = {nullptr, nullptr};   // [n_chan][128][max_held], read from [cur], written to [cur ^ 1]
+    int* held_count[2] = {nullptr, nullptr};   // [n_chan][128]
+    int cur = 0;
+    double horizon = -INFINITY;             // of the last push
+    bool finished = false;
+};
+
+extern "C" void ymt3_detok_state_destroy(ymt3_detok_state st) {
+    if (!st) return;
+    (void)hipSetDevice(st->device);
+    for (void* p : {(void*)st->sounding, (void*)st->held[0], (void*)st->held[1], (void*)st->held_count[0], (void*)st->held_count[1]})
+        if (p) (void)hipFree(p);
+    delete st;
+}
+
+static size_t detok_state_sounding_bytes(const ymt3_detok_state_s* st) { return (size_t)st->n_chan * st->n_programs * DETOK_PITCHES * sizeof(DetokSounding); }
+static size_t detok_state_count_bytes(const ymt3_detok_state_s* st) { return (size_t)st->n_chan * DETOK_PITCHES * sizeof(int); }
+
+extern "C" long long ymt3_detok_state_carry(ymt3_detok_state st) {
+    if (!st) return 0;
+    return (long long)st->n_chan * DETOK_PITCHES * ((long long)st->n_programs - 1 + st->max_held);
+}
+
+extern "C" int ymt3_detok_state_create(ymt3_handle h, ymt3_detok d, int max_held, ymt3_detok_state* out) {
+    if (!out) FAIL(YMT3_ERR_ARG, "null output pointer");
+    *out = nullptr;
+    if (!h) FAIL(YMT3_ERR_ARG, "null handle");
+    if (!d) FAIL(YMT3_ERR_ARG, "null detokeniser");
+    if (d->owner != h) FAIL(YMT3_ERR_ARG, "the detokeniser belongs to another handle");
+    if (max_held < 1 || max_held > 4096) FAIL(YMT3_ERR_ARG, "max_held=%d outside [1, 4096]", max_held);
+    HIP_TRY(hipSetDevice(h->device));
+    ymt3_detok_state st = new ymt3_detok_state_s{h, d, h->device, h->cfg.n_channels, d->n_programs, max_held};
+    const size_t hb = (size_t)st->n_chan * DETOK_PITCHES * max_held * sizeof(DetokHeld), cb = detok_state_count_bytes(st);
+    if (hipMalloc(reinterpret_cast<void**>(&st->sounding), detok_state_sounding_bytes(st)) != hipSuccess ||
+        hipMalloc(reinterpret_cast<void**>(&st->held[0]), hb) != hipSuccess || hipMalloc(reinterpret_cast<void**>(&st->held[1]), hb) != hipSuccess ||
+        hipMalloc(reinterpret_cast<void**>(&st->held_count[0]), cb) != hipSuccess || hipMalloc(reinterpret_cast<void**>(&st->held_count[1]), cb) != hipSuccess ||
+        hipMemset(st->sounding, 0, detok_state_sounding_bytes(st)) != hipSuccess || hipMemset(st->held_count[0], 0, cb) != hipSuccess ||
+        hipMemset(st->held_count[1], 0, cb) != hipSuccess) {
+        ymt3_detok_state_destroy(st);
+        FAIL(YMT3_ERR_HIP, "detokeniser state (%zu bytes) could not be allocated", detok_state_sounding_bytes(st) + 2 * (hb + cb));
+    }
+    *out = st;
+    return YMT3_OK;
+}
+
+extern "C" int ymt3_detok_state_reset(ymt3_handle h, ymt3_detok_state st, void* stream) {
+    if (!h) FAIL(YMT3_ERR_ARG, "null handle");
+    if (!st) FAIL(YMT3_ERR_ARG, "null detokeniser state");
+    if (st->owner != h) FAIL(YMT3_ERR_ARG, "the detokeniser state belongs to another handle");
+    HIP_TRY(hipSetDevice(h->device));
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    HIP_TRY(hipMemsetAsync(st->sounding, 0, detok_state_sounding_bytes(st), s));
+    HIP_TRY(hipMemsetAsync(st->held_count[st->cur], 0, detok_state_count_bytes(st), s));
+    st->horizon = -INFINITY;
+    st->finished = false;
+    return YMT3_OK;
+}
+
+// the shared tail of push and finish: n_segments = 0 walks the state alone
+static int detok_carry(ymt3_handle h, ymt3_detok d, ymt3_detok_state st, const int32_t* tokens_dev, const float* scores_dev, int n_segments,
+                       int n_steps, long long seg_stride, long long chan_stride, const double* start_sec_dev, double horizon, double end_sec,
+                       int finish, void* notes_dev, long long capacity, int32_t* counts_dev, void* stream) {
+    if (!h) FAIL(YMT3_ERR_ARG, "null handle");
+    if (!d) FAIL(YMT3_ERR_ARG, "null detokeniser");
+    if (!st) FAIL(YMT3_ERR_ARG, "null detokeniser state");
+    if (d->owner != h) FAIL(YMT3_ERR_ARG, "the detokeniser belongs to another handle");
+    if (st->owner != h || st->detok != d) FAIL(YMT3_ERR_ARG, "the detokeniser state was created for another detokeniser");
+    if (st->finished) FAIL(YMT3_ERR_ARG, "the state has been finished: reset it first");
+    if (n_segments < 0 || n_segments > d->max_segments) FAIL(YMT3_ERR_ARG, "n_segments=%d outside [0, max_segments=%d]", n_segments, d->max_segments);
+    if (n_segments && (n_steps < 1 || n_steps > d->max_steps)) FAIL(YMT3_ERR_ARG, "n_steps=%d outside [1, max_steps=%d]", n_steps, d->max_steps);
+    if (!counts_dev) FAIL(YMT3_ERR_ARG, "counts_dev is NULL");
+    if (!notes_dev) FAIL(YMT3_ERR_ARG, "notes_dev is NULL");
+    if (n_segments && !tokens_dev) FAIL(YMT3_ERR_ARG, "tokens_dev is NULL");
+    if (n_segments && !start_sec_dev) FAIL(YMT3_ERR_ARG, "start_sec_dev is NULL");
+    if (!finish && !(horizon >= st->horizon && horizon > -INFINITY))
+        FAIL(YMT3_ERR_ARG, "horizon_sec=%g is -inf, NaN or below the previous push's horizon %g", horizon, st->horizon);
+    const long long bound = (long long)n_segments * h->cfg.n_channels * (n_segments ? n_steps : 0) + ymt3_detok_state_carry(st);
+    if (capacity < bound)
+        FAIL(YMT3_ERR_ARG, "capacity=%lld below n_segments * n_channels * n_steps + ymt3_detok_state_carry = %lld records", capacity, bound);
+    HIP_TRY(hipSetDevice(h->device));
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    HIP_TRY(hipMemsetAsync(counts_dev, 0, 3 * sizeof(int32_t), s));
+    DetokArgs a{};
+    a.table = d->table; a.vocab = d->vocab; a.steps_per_second = d->steps_per_second; a.drum_program = d->drum_program; a.n_programs = d->n_programs;
+    a.tokens = tokens_dev; a.scores = scores_dev; a.seg_stride = seg_stride; a.chan_stride = chan_stride;
+    a.n_seg = n_segments; a.n_chan = h->cfg.n_channels; a.L = n_segments ? n_steps : 1;
+    a.start = start_sec_dev; a.end_sec = end_sec;
+    a.items = d->items; a.keys = d->keys; a.row_count = d->row_count; a.sorted = d->sorted; a.key_off = d->key_off;
+    a.notes = static_cast<DetokNote*>(notes_dev); a.capacity = capacity; a.counts = counts_dev;
+    DetokCarryArgs c{};
+    c.sounding = st->sounding; c.held_in = st->held[st->cur]; c.held_out = st->held[st->cur ^ 1];
+    c.held_count_in = st->held_count[st->cur]; c.held_count_out = st->held_count[st->cur ^ 1];
+    c.max_held = st->max_held; c.finish = finish; c.horizon = horizon;
+    LAUNCH(launch_detok_carry(a, c, s));
+    HIP_TRY(hipGetLastError());
+    st->cur ^= 1;
+    if (finish) st->finished = true;
+    else st->horizon = horizon;
+    return YMT3_OK;
+}
+
+extern "C" int ymt3_detokenize_push(ymt3_handle h, ymt3_detok d, ymt3_detok_state st, const int32_t* tokens_dev, const float* scores_dev,
+                                    int n_segments, int n_steps, long long seg_stride, long long chan_stride, const double* start_sec_dev,
+                                    double horizon_sec, void* notes_dev, long long capacity, int32_t* counts_dev, void* stream) {
+    return detok_carry(h, d, st, tokens_dev, scores_dev, n_segments, n_steps, seg_stride, chan_stride, start_sec_dev, horizon_sec, 0.0, 0,
+                       notes_dev, capacity, counts_dev, stream);
+}
+
+extern "C" int ymt3_detokenize_finish(ymt3_handle h, ymt3_detok d, ymt3_detok_state st, double end_sec, void* notes_dev, long long capacity,
+                                      int32_t* counts_dev, void* stream) {
+    return detok_carry(h, d, st, nullptr, nullptr, 0, 0, 0, 0, nullptr, INFINITY, end_sec, 1, notes_dev, capacity, counts_dev, stream);
+}
+
 // ---------------------------------------------------------------- device tokeniser (include/ymt3.h)
 struct ymt3_tok_s {
     ymt3_ctx* owner;
@@ -2440,6 +2559,139 @@ extern "C" int ymt3_ingest(ymt3_handle h, const void* pcm_dev, int pcm_format, i
     a.up = rs->up; a.down = rs->down; a.J = rs->J; a.Jp = rs->Jp; a.n_channels = n_channels; a.s16 = pcm_format == YMT3_PCM_S16; a.window = rs->window;
     LAUNCH(launch_ingest(a, (hipStream_t)stream));
     HIP_TRY(hipGetLastError());
+    return YMT3_OK;
+}
+
+// ---------------------------------------------------------------- streaming ingest (include/ymt3.h)
+// Output sample n reads input frames k0(n) - J + 1 .. k0(n), k0(n) = (n + r) * down / up, so with N frames arrived the samples with
+// k0(n) <= N - 1 are final: n + r < ceil(N * up / down), i.e. the first max(0, ceil(N * up / down) - r) of them.
+struct ymt3_ingest_stream_s {
+    ymt3_ctx* owner;
+    int device, sample_rate_in, n_channels, s16;
+    long long max_chunk;
+    ymt3_ctx::Resampler rs;                 // the taps belong to the handle
+    float* hist = nullptr;                  // [hist_mask + 1] mono ring
+    long long hist_mask = 0;
+    float* part[2] = {nullptr, nullptr};    // [segment_samples] each: the partial segment, and the one the next completing push starts
+    int cur = 0;
+    long long n_in = 0, n_done = 0, delivered = 0;   // frames arrived, samples computed, segments handed to the caller
+    bool finished = false;
+};
+
+static long long ingest_final(const ymt3_ingest_stream_s* s, long long n_in) {
+    return std::max(0LL, (n_in * s->rs.up + s->rs.down - 1) / s->rs.down - s->rs.r);
+}
+
+extern "C" void ymt3_ingest_stream_destroy(ymt3_ingest_stream s) {
+    if (!s) return;
+    (void)hipSetDevice(s->device);
+    for (void* p : {(void*)s->hist, (void*)s->part[0], (void*)s->part[1]})
+        if (p) (void)hipFree(p);
+    delete s;
+}
+
+extern "C" int ymt3_ingest_stream_create(ymt3_handle h, int sample_rate_in, int n_channels, int pcm_format, int64_t max_chunk_frames,
+                                         ymt3_ingest_stream* out) {
+    if (!out) FAIL(YMT3_ERR_ARG, "null output pointer");
+    *out = nullptr;
+    if (!h) FAIL(YMT3_ERR_ARG, "null handle");
+    if (pcm_format != YMT3_PCM_S16 && pcm_format != YMT3_PCM_F32) FAIL(YMT3_ERR_ARG, "pcm_format=%d", pcm_format);
+    if (n_channels < 1 || n_channels > 64 || sample_rate_in <= 0) FAIL(YMT3_ERR_ARG, "n_channels=%d sample_rate_in=%d", n_channels, sample_rate_in);
+    if (max_chunk_frames < 1 || max_chunk_frames > (1LL << 24)) FAIL(YMT3_ERR_ARG, "max_chunk_frames=%lld outside [1, 2^24]", (long long)max_chunk_frames);
+    HIP_TRY(hipSetDevice(h->device));
+    const ymt3_ctx::Resampler* rs = nullptr;
+    int rc = get_resampler(h, sample_rate_in, &rs);
+    if (rc) return rc;
+    ymt3_ingest_stream s = new ymt3_ingest_stream_s{h, h->device, sample_rate_in, n_channels, pcm_format == YMT3_PCM_S16, (long long)max_chunk_frames, *rs};
+    long long ring = 1;
+    while (ring < rs->J - 1 + max_chunk_frames) ring <<= 1;
+    s->hist_mask = ring - 1;
+    const size_t seg = (size_t)h->cfg.segment_samples * sizeof(float);
+    if (hipMalloc(reinterpret_cast<void**>(&s->hist), (size_t)ring * sizeof(float)) != hipSuccess ||
+        hipMalloc(reinterpret_cast<void**>(&s->part[0]), seg) != hipSuccess || hipMalloc(reinterpret_cast<void**>(&s->part[1]), seg) != hipSuccess) {
+        ymt3_ingest_stream_destroy(s);
+        FAIL(YMT3_ERR_HIP, "ingest stream buffers (%zu bytes) could not be allocated", (size_t)ring * sizeof(float) + 2 * seg);
+    }
+    *out = s;
+    return YMT3_OK;
+}
+
+extern "C" int ymt3_ingest_stream_reset(ymt3_handle h, ymt3_ingest_stream s, void* stream) {
+    if (!h) FAIL(YMT3_ERR_ARG, "null handle");
+    if (!s) FAIL(YMT3_ERR_ARG, "null ingest stream");
+    if (s->owner != h) FAIL(YMT3_ERR_ARG, "the ingest stream belongs to another handle");
+    (void)stream;   // nothing on the device carries over: frames outside [0, n_in) are never read from the ring
+    s->n_in = s->n_done = s->delivered = 0;
+    s->cur = 0;
+    s->finished = false;
+    return YMT3_OK;
+}
+
+extern "C" int ymt3_ingest_stream_plan(ymt3_ingest_stream s, int64_t n_frames, int* n_ready) {
+    if (!s) FAIL(YMT3_ERR_ARG, "null ingest stream");
+    if (s->finished) FAIL(YMT3_ERR_ARG, "the stream has been finished: reset it first");
+    if (n_frames < 0 || n_frames > s->max_chunk) FAIL(YMT3_ERR_ARG, "n_frames=%lld outside [0, max_chunk_frames=%lld]", (long long)n_frames, s->max_chunk);
+    const long long ready = ingest_final(s, s->n_in + n_frames) / s->owner->cfg.segment_samples - s->delivered;
+    if (ready > 0x7fffffffLL) FAIL(YMT3_ERR_ARG, "too many segments");
+    if (n_ready) *n_ready = (int)ready;
+    return YMT3_OK;
+}
+
+static IngestStreamArgs ingest_stream_args(const ymt3_ingest_stream_s* s) {
+    IngestStreamArgs a{};
+    a.hist = s->hist; a.hist_mask = s->hist_mask; a.taps = s->rs.taps; a.part_old = s->part[s->cur];
+    a.n_done = s->n_done; a.n_row0 = s->delivered * s->owner->cfg.segment_samples; a.r = s->rs.r;
+    a.up = s->rs.up; a.down = s->rs.down; a.J = s->rs.J; a.Jp = s->rs.Jp; a.n_channels = s->n_channels; a.s16 = s->s16; a.window = s->rs.window;
+    return a;
+}
+
+extern "C" int ymt3_ingest_stream_push(ymt3_handle h, ymt3_ingest_stream s, const void* pcm_dev, int64_t n_frames, float* segments_dev,
+                                       int max_segments, int* n_ready, void* stream) {
+    if (!h) FAIL(YMT3_ERR_ARG, "null handle");
+    if (!s) FAIL(YMT3_ERR_ARG, "null ingest stream");
+    if (s->owner != h) FAIL(YMT3_ERR_ARG, "the ingest stream belongs to another handle");
+    int ready = 0;
+    int rc = ymt3_ingest_stream_plan(s, n_frames, &ready);
+    if (rc) return rc;
+    if (max_segments < ready) FAIL(YMT3_ERR_ARG, "max_segments=%d but this push completes %d segments", max_segments, ready);
+    if ((n_frames > 0 && !pcm_dev) || (ready > 0 && !segments_dev)) FAIL(YMT3_ERR_ARG, "null buffer");
+    HIP_TRY(hipSetDevice(h->device));
+    const long long S = h->cfg.segment_samples, n_in = s->n_in + n_frames, n_final = ingest_final(s, n_in);
+    IngestStreamArgs a = ingest_stream_args(s);
+    a.pcm = pcm_dev; a.out = segments_dev; a.n_new = n_frames; a.n_in = n_in;
+    a.n_end = a.n_total = n_final;
+    a.n_row_end = a.n_row0 + ready * S;
+    a.g0 = ready > 0 ? a.n_row0 : s->n_done;                 // a completed segment takes its first part from the partial buffer
+    a.part_new = s->part[ready > 0 ? s->cur ^ 1 : s->cur];   // and the next partial segment starts in the other one
+    LAUNCH(launch_ingest_stream(a, (hipStream_t)stream));
+    HIP_TRY(hipGetLastError());
+    s->n_in = n_in; s->n_done = n_final; s->delivered += ready;
+    if (ready > 0) s->cur ^= 1;
+    if (n_ready) *n_ready = ready;
+    return YMT3_OK;
+}
+
+extern "C" int ymt3_ingest_stream_finish(ymt3_handle h, ymt3_ingest_stream s, float* segments_dev, int max_segments, int* n_ready,
+                                         int64_t* n_samples_total, void* stream) {
+    if (!h) FAIL(YMT3_ERR_ARG, "null handle");
+    if (!s) FAIL(YMT3_ERR_ARG, "null ingest stream");
+    if (s->owner != h) FAIL(YMT3_ERR_ARG, "the ingest stream belongs to another handle");
+    if (s->finished) FAIL(YMT3_ERR_ARG, "the stream has been finished: reset it first");
+    const long long S = h->cfg.segment_samples, n_out = (s->n_in * s->rs.up + s->rs.down - 1) / s->rs.down;
+    const long long n_seg = std::max(1LL, (n_out + S - 1) / S), ready = n_seg - s->delivered;
+    if (max_segments < ready) FAIL(YMT3_ERR_ARG, "max_segments=%d but the finish completes %lld segments", max_segments, ready);
+    if (ready > 0 && !segments_dev) FAIL(YMT3_ERR_ARG, "null buffer");
+    HIP_TRY(hipSetDevice(h->device));
+    IngestStreamArgs a = ingest_stream_args(s);
+    a.out = segments_dev; a.n_new = 0; a.n_in = s->n_in;
+    a.n_end = n_out; a.n_total = a.n_row_end = n_seg * S;    // frames that never came are zeros, as the one-shot call pads
+    a.g0 = a.n_row0;
+    a.part_new = s->part[s->cur];                            // not written: every sample lies in the caller's rows
+    LAUNCH(launch_ingest_stream(a, (hipStream_t)stream));
+    HIP_TRY(hipGetLastError());
+    s->n_done = n_out; s->delivered = n_seg; s->finished = true;
+    if (n_ready) *n_ready = (int)ready;
+    if (n_samples_total) *n_samples_total = n_out;
     return YMT3_OK;
 }
 

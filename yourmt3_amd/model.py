@@ -75,6 +75,7 @@ class Detokenizer:
         self.capacity = self.max_segments * self.n_channels * self.max_steps
         self._notes = torch.empty(self.capacity * NOTE_RECORD.itemsize, device=model.device, dtype=torch.uint8)
         self._counts = torch.zeros(2, device=model.device, dtype=torch.int32)
+        self._states = weakref.WeakSet()
 
     @property
     def ptr(self):
@@ -112,9 +113,96 @@ class Detokenizer:
                                              model._stream()))
         return self._notes, self._counts
 
+    # ------------------------------------------------------------------ incremental form (include/ymt3.h, incremental detokeniser)
+    def new_state(self, max_held: int = 16) -> "DetokState":
+        """The carried state of one stream of segments for push_device / finish_device: the notes still sounding and the drum hits not
+        yet final, at most `max_held` per (channel, drum pitch).  Freed by its close(), or with this detokeniser."""
+        model = self._model()
+        if model is None:
+            raise ValueError("the detokenizer's model is gone")
+        st = DetokState(self, model, max_held)
+        self._states.add(st)
+        return st
+
+    def push_device(self, state: "DetokState", tokens: torch.Tensor, scores: Optional[torch.Tensor], start_secs: torch.Tensor, horizon_sec: float):
+        """One push of (n, K, L) ids (+ scores) with their (n,) f64 start times; `horizon_sec` is the start of the next segment not yet
+        pushed.  -> (records: uint8 tensor of `state.capacity` NOTE_RECORDs, counts: int32 tensor [n_notes, n_invalid, n_forced]), the
+        state's own device buffers, overwritten by its next call.  Asynchronous; nothing is checked against the start times here."""
+        model = self._model()
+        if model is None:
+            raise ValueError("the detokenizer's model is gone")
+        n, K, L = (int(v) for v in tokens.shape)
+        if tokens.dtype != torch.int32:
+            tokens = tokens.to(torch.int32)
+        tokens = tokens.to(model.device)
+        if L > 1 and tokens.stride(2) != 1:
+            tokens = tokens.contiguous()
+        if scores is not None:
+            scores = scores.to(model.device, torch.float32)
+            if tuple(scores.stride()) != tuple(tokens.stride()):
+                tokens, scores = tokens.contiguous(), scores.contiguous()
+        starts = start_secs.to(model.device, torch.float64).contiguous()
+        _lib.check(self._lib.ymt3_detokenize_push(model._handle, self.ptr, state.ptr, _ptr(tokens) if n else None, _ptr(scores) if n else None,
+                                                  n, L, tokens.stride(0), tokens.stride(1), _ptr(starts) if n else None, float(horizon_sec),
+                                                  _ptr(state._notes), state.capacity, _ptr(state._counts), model._stream()))
+        return state._notes, state._counts
+
+    def finish_device(self, state: "DetokState", end_sec: float):
+        """The end of the stream: every held hit, and every sounding note closed at `end_sec` -> (records, counts) as push_device."""
+        model = self._model()
+        if model is None:
+            raise ValueError("the detokenizer's model is gone")
+        _lib.check(self._lib.ymt3_detokenize_finish(model._handle, self.ptr, state.ptr, float(end_sec), _ptr(state._notes), state.capacity,
+                                                    _ptr(state._counts), model._stream()))
+        return state._notes, state._counts
+
     def close(self):
+        for st in list(getattr(self, "_states", ())):
+            st.close()
         if getattr(self, "_c", None) is not None and self._c.value:
             self._lib.ymt3_detok_destroy(self._c)
+            self._c = ctypes.c_void_p()
+            self._notes = self._counts = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+class DetokState:
+    """What one stream of segments carries between Detokenizer.push_device calls (Detokenizer.new_state; include/ymt3.h, incremental
+    detokeniser), with the record and counter buffers its calls write."""
+
+    def __init__(self, detok: Detokenizer, model: "YourMT3", max_held: int):
+        self.max_held = int(max_held)
+        self._model = weakref.ref(model)
+        self._lib = model._lib
+        self._c = ctypes.c_void_p()
+        _lib.check(self._lib.ymt3_detok_state_create(model._handle, detok.ptr, self.max_held, ctypes.byref(self._c)))
+        self.carry = int(self._lib.ymt3_detok_state_carry(self._c))
+        self.capacity = detok.capacity + self.carry
+        self._notes = torch.empty(self.capacity * NOTE_RECORD.itemsize, device=model.device, dtype=torch.uint8)
+        self._counts = torch.zeros(3, device=model.device, dtype=torch.int32)
+        self.last_start = float("-inf")              # start of the last pushed segment (TaskManager.tokens_to_notes_stream checks against it)
+
+    @property
+    def ptr(self):
+        if not self._c.value:
+            raise ValueError("the detokenizer state has been closed")
+        return self._c
+
+    def reset(self) -> None:
+        model = self._model()
+        if model is None:
+            raise ValueError("the state's model is gone")
+        _lib.check(self._lib.ymt3_detok_state_reset(model._handle, self.ptr, model._stream()))
+        self.last_start = float("-inf")
+
+    def close(self):
+        if getattr(self, "_c", None) is not None and self._c.value:
+            self._lib.ymt3_detok_state_destroy(self._c)
             self._c = ctypes.c_void_p()
             self._notes = self._counts = None
 
@@ -324,6 +412,99 @@ class PianoRoll:
             pass
 
 
+class IngestStream:
+    """Streaming ingest of one model for one PCM format (YourMT3.compile_ingest_stream; include/ymt3.h, streaming ingest): PCM arrives
+    in chunks of at most `max_chunk_frames` frames, whole segments come out as soon as their last sample is final, and all of them
+    together are model.ingest() of the concatenated PCM bit for bit.  Freed by close(), or by the model's close()."""
+
+    def __init__(self, model: "YourMT3", sample_rate: int, n_channels: int, dtype, max_chunk_frames: int):
+        if dtype in (torch.int16, np.int16, "int16"):
+            self.dtype, fmt = torch.int16, 0
+        elif dtype in (torch.float32, np.float32, "float32"):
+            self.dtype, fmt = torch.float32, 1
+        else:
+            raise ValueError("pcm must be int16 or float32")
+        self.sample_rate, self.n_channels, self.max_chunk_frames = int(sample_rate), int(n_channels), int(max_chunk_frames)
+        self.segment_samples = model.cfg.segment_samples
+        self._model = weakref.ref(model)
+        self._lib = model._lib
+        self._c = ctypes.c_void_p()
+        self._frames = self._delivered = 0          # frames pushed, segments returned: what finish() sizes its result from
+        _lib.check(self._lib.ymt3_ingest_stream_create(model._handle, self.sample_rate, self.n_channels, fmt, self.max_chunk_frames,
+                                                       ctypes.byref(self._c)))
+
+    @property
+    def ptr(self):
+        if not self._c.value:
+            raise ValueError("the ingest stream has been closed")
+        return self._c
+
+    def _live_model(self):
+        model = self._model()
+        if model is None:
+            raise ValueError("the ingest stream's model is gone")
+        return model
+
+    def plan(self, n_frames: int) -> int:
+        """How many whole segments a push of `n_frames` frames would complete now (host arithmetic only)."""
+        k = ctypes.c_int(0)
+        _lib.check(self._lib.ymt3_ingest_stream_plan(self.ptr, int(n_frames), ctypes.byref(k)))
+        return k.value
+
+    def push(self, pcm: torch.Tensor) -> torch.Tensor:
+        """(n_frames, n_channels) or (n_frames,) PCM of the stream's dtype -> (k, 1, S) float32: the k >= 0 segments this chunk
+        completed, on the device.  Asynchronous; k is known without a synchronisation."""
+        model = self._live_model()
+        if pcm.dim() == 1:
+            pcm = pcm[:, None]
+        if pcm.dim() != 2 or int(pcm.shape[1]) != self.n_channels:
+            raise ValueError(f"pcm must be (n_frames, {self.n_channels})")
+        if pcm.dtype != self.dtype:
+            raise ValueError(f"pcm must be {self.dtype}, got {pcm.dtype}")
+        n_frames = int(pcm.shape[0])
+        k = self.plan(n_frames)
+        pcm = pcm.to(model.device).contiguous()
+        segs = torch.empty(k, 1, self.segment_samples, device=model.device, dtype=torch.float32)
+        got = ctypes.c_int(0)
+        _lib.check(self._lib.ymt3_ingest_stream_push(model._handle, self.ptr, _ptr(pcm) if n_frames else None, n_frames,
+                                                     _ptr(segs) if k else None, k, ctypes.byref(got), model._stream()))
+        assert got.value == k
+        self._frames += n_frames
+        self._delivered += k
+        return segs
+
+    def finish(self):
+        """-> ((k, 1, S) float32: the remaining segments, the last one zero padded; the stream's total resampled samples)."""
+        model = self._live_model()
+        S = self.segment_samples
+        n_out, n_seg, k = ctypes.c_int64(0), ctypes.c_int(0), ctypes.c_int(0)
+        _lib.check(self._lib.ymt3_ingest_plan(model._handle, self._frames, self.sample_rate, ctypes.byref(n_out), ctypes.byref(n_seg)))
+        rows = n_seg.value - self._delivered
+        segs = torch.empty(rows, 1, S, device=model.device, dtype=torch.float32)
+        _lib.check(self._lib.ymt3_ingest_stream_finish(model._handle, self.ptr, _ptr(segs) if rows else None, rows, ctypes.byref(k),
+                                                       ctypes.byref(n_out), model._stream()))
+        assert k.value == rows
+        self._delivered += rows
+        return segs, int(n_out.value)
+
+    def reset(self) -> None:
+        """Forget the stream so far; the next push starts a new one."""
+        model = self._live_model()
+        _lib.check(self._lib.ymt3_ingest_stream_reset(model._handle, self.ptr, model._stream()))
+        self._frames = self._delivered = 0
+
+    def close(self):
+        if getattr(self, "_c", None) is not None and self._c.value:
+            self._lib.ymt3_ingest_stream_destroy(self._c)
+            self._c = ctypes.c_void_p()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
 class YourMT3:
     def __init__(self, cfg: YMT3Config, weights: Optional[Dict[str, torch.Tensor]] = None, *, seed: int = 1234,
                  device: int = 0, max_batch: int = 64):
@@ -339,6 +520,8 @@ class YourMT3:
         ccfg = to_c(cfg, self.max_batch)
         # `blob` is immutable bytes: c_char_p points at its buffer (no second ~91 MB host copy); ymt3_create only reads it
         _lib.check(self._lib.ymt3_create(ctypes.byref(ccfg), ctypes.c_char_p(blob), len(blob), device, ctypes.byref(self._handle)))
+        # every object created for this handle that close() must free with it: constraints first, since then detokenisers, tokenisers,
+        # metrics, piano rolls and ingest streams as well (the name is the first tenant's)
         self._constraints = weakref.WeakSet()
 
     def close(self):
@@ -481,6 +664,13 @@ class YourMT3:
         r = PianoRoll(self, n_programs, max_frames, frames_per_second, drum_program)
         self._constraints.add(r)
         return r
+
+    def compile_ingest_stream(self, sample_rate: int, n_channels: int = 1, dtype=torch.int16, max_chunk_frames: int = 1 << 16) -> IngestStream:
+        """Streaming form of ingest() (include/ymt3.h, streaming ingest) for `n_channels`-channel PCM of `dtype` (int16 or float32) at
+        `sample_rate`, pushed in chunks of at most `max_chunk_frames` frames."""
+        s = IngestStream(self, sample_rate, n_channels, dtype, max_chunk_frames)
+        self._constraints.add(s)
+        return s
 
     def _start_states(self, constraint: Optional[DecodeConstraint], start_states, B: int) -> Optional[torch.Tensor]:
         """start_states -> (B, K) int32 device tensor, or None (state 0).  (K,) is every segment's; (B, K) per segment."""

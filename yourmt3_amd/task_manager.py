@@ -229,6 +229,88 @@ def note_events_to_notes(segments: Sequence[Tuple[float, List[NoteEvent], List[T
     return sorted(notes)
 
 
+class NoteStream:
+    """note_events_to_notes for ONE channel whose segments arrive over time: the same merge with its state carried from call to call,
+    and the specification of the incremental device detokeniser (include/ymt3.h).
+
+    push(segments, horizon_sec): `segments` are (start_sec, events, tie_notes) as for note_events_to_notes, later than everything pushed
+    before; `horizon_sec` is the start time of the next segment not yet pushed (+inf: none will come before finish).  The call returns
+    every note the one-shot merge appends while it processes these segments, except drum hits with time >= horizon_sec: a hit of a
+    later segment at the same f64 time and pitch is merged into them and may raise their confidence, and every event of a later segment
+    lies at or after that segment's start, so those hits -- and only those -- can still change.  They are held, and returned by the
+    first later push whose horizon exceeds their time, or by finish.  finish(end_sec) also closes what is still sounding, by the rule of
+    the one-shot loop's tail.  A returned note never changes and is never returned again:
+    sorted(everything returned) == note_events_to_notes(all the segments, end_sec), confidences included, for every split."""
+
+    def __init__(self):
+        self.reset()
+
+    def reset(self) -> None:
+        self._active: Dict[Tuple[int, int], Tuple[float, Optional[float]]] = {}   # (program, pitch) -> (onset, confidence)
+        self._held: Dict[Tuple[float, int], Note] = {}                              # (time, pitch) -> the hit, still open
+        self._last_start = -math.inf
+        self._finished = False
+
+    @property
+    def n_held(self) -> int:
+        return len(self._held)
+
+    def _release(self, horizon_sec: float) -> List[Note]:
+        out = [n for hit, n in self._held.items() if hit[0] < horizon_sec]
+        self._held = {hit: n for hit, n in self._held.items() if not hit[0] < horizon_sec}
+        return out
+
+    def push(self, segments: Sequence[Tuple[float, List[NoteEvent], List[Tuple[int, int]]]], horizon_sec: float) -> List[Note]:
+        if self._finished:
+            raise ValueError("the stream has been finished: reset it first")
+        segments = sorted(segments, key=lambda s: s[0])
+        starts = [self._last_start] + [float(s[0]) for s in segments]
+        if any(b <= a for a, b in zip(starts, starts[1:])):
+            raise ValueError("segment start times must be strictly increasing over the whole stream")
+        if not horizon_sec >= starts[-1] or horizon_sec == -math.inf:
+            raise ValueError(f"horizon_sec={horizon_sec} lies before the last pushed segment's start {starts[-1]}")
+        active, held = self._active, self._held
+        notes: List[Note] = []
+        for start, events, ties in segments:
+            tie_set = set(ties)
+            for key in [k for k in active if k not in tie_set]:
+                on, conf = active.pop(key)
+                if start > on:
+                    notes.append(Note(on, start, False, key[0], key[1], confidence=conf))
+            for ev in sorted(events):
+                conf = None if ev.score is None else math.exp(ev.score)
+                if ev.is_drum:
+                    hit = (ev.time, ev.pitch)
+                    if hit not in held:
+                        held[hit] = Note(ev.time, ev.time + DRUM_NOTE_SEC, True, DRUM_PROGRAM, ev.pitch, confidence=conf)
+                    elif conf is not None:
+                        old = held[hit]
+                        if old.confidence is None or conf > old.confidence:
+                            held[hit] = replace(old, confidence=conf)
+                    continue
+                key = (ev.program, ev.pitch)
+                if ev.velocity:
+                    if key in active and ev.time > active[key][0]:
+                        notes.append(Note(active[key][0], ev.time, False, key[0], key[1], confidence=active[key][1]))
+                    active[key] = (ev.time, conf)
+                elif key in active:
+                    on, oconf = active.pop(key)
+                    if ev.time > on:
+                        notes.append(Note(on, ev.time, False, key[0], key[1], confidence=oconf))
+        self._last_start = starts[-1]
+        return sorted(notes + self._release(horizon_sec))
+
+    def finish(self, end_sec: float) -> List[Note]:
+        if self._finished:
+            raise ValueError("the stream has been finished: reset it first")
+        notes = list(self._held.values())
+        for key, (on, conf) in self._active.items():
+            if end_sec > on:
+                notes.append(Note(on, end_sec, False, key[0], key[1], confidence=conf))
+        self._held, self._active, self._finished = {}, {}, True
+        return sorted(notes)
+
+
 def drop_low_confidence(notes: Sequence[Note], min_confidence: float) -> List[Note]:
     """The notes whose confidence is at least `min_confidence`, in their order.  A note without a confidence (decoded without
     scores) has nothing to be judged by and is kept."""
@@ -507,6 +589,48 @@ class TaskManager:
                  for on, off, pg, pt, dr, sc in zip(rec["onset"].tolist(), rec["offset"].tolist(), rec["program"].tolist(),
                                                     rec["pitch"].tolist(), rec["is_drum"].tolist(), rec["score"].astype(np.float64).tolist())]
         return sorted(notes), n_invalid
+
+    def tokens_to_notes_stream(self, model, detokenizer, state, tokens=None, start_secs: Sequence[float] = (), horizon_sec: float = math.inf,
+                               scores=None, end_sec: Optional[float] = None, scored: Optional[bool] = None) -> Tuple[List[Note], int, int]:
+        """One call of the incremental device detokeniser (include/ymt3.h; the specification is NoteStream, per channel) ->
+        (notes that became final, n_invalid, n_forced).  `detokenizer` / `state`: YourMT3.compile_detokenizer and its new_state().
+        A push: `tokens` (n, K, L) ids on the GPU, later than everything pushed before, `start_secs` their strictly increasing start
+        times, `horizon_sec` the start of the next segment not yet pushed (+inf: none before the end).  The finish: `end_sec` and no
+        tokens.  Notes carry confidence = exp(score) iff scores are in use (`scored`; by default whether `scores` is given -- pass it
+        at the finish).  One copy back of the counters and the new records.  n_forced != 0: the state's max_held was reached and the
+        result may differ from the one-shot one."""
+        import torch
+
+        if end_sec is not None:
+            if tokens is not None:
+                raise ValueError("the finish takes no tokens")
+            rec_dev, counts = detokenizer.finish_device(state, float(end_sec))
+        else:
+            starts = np.asarray(list(start_secs), np.float64)
+            if tokens is None or tokens.dim() != 3 or tokens.shape[1] != self.num_decoding_channels:
+                raise ValueError(f"tokens must be (n, {self.num_decoding_channels}, L)")
+            n = int(tokens.shape[0])
+            if starts.shape != (n,):
+                raise ValueError(f"{n} segments but {starts.size} start times")
+            last = getattr(state, "last_start", -math.inf)
+            if n and not (bool(np.all(np.diff(starts) > 0)) and starts[0] > last):
+                raise ValueError("start_secs must be strictly increasing over the whole stream")
+            if not float(horizon_sec) >= (starts[-1] if n else last) or float(horizon_sec) == -math.inf:
+                raise ValueError(f"horizon_sec={horizon_sec} lies before the last pushed segment's start")
+            if scores is not None and tuple(scores.shape) != tuple(tokens.shape):
+                raise ValueError(f"scores {tuple(scores.shape)} do not match tokens {tuple(tokens.shape)}")
+            rec_dev, counts = detokenizer.push_device(state, tokens, scores, torch.from_numpy(starts), float(horizon_sec))
+            if n:
+                state.last_start = float(starts[-1])
+        n_notes, n_invalid, n_forced = (int(v) for v in counts.cpu().tolist())
+        from .model import NOTE_RECORD
+        rec = rec_dev[:n_notes * NOTE_RECORD.itemsize].cpu().numpy().view(NOTE_RECORD)
+        if scored is None:
+            scored = scores is not None
+        notes = [Note(on, off, bool(dr), pg, pt, confidence=math.exp(sc) if scored else None)
+                 for on, off, pg, pt, dr, sc in zip(rec["onset"].tolist(), rec["offset"].tolist(), rec["program"].tolist(),
+                                                    rec["pitch"].tolist(), rec["is_drum"].tolist(), rec["score"].astype(np.float64).tolist())]
+        return sorted(notes), n_invalid, n_forced
 
     def notes_to_tokens_device(self, model, notes, start_secs: Sequence[float], end_sec: float, max_len: Optional[int] = None,
                                tokenizer=None):

@@ -5,7 +5,7 @@ from __future__ import annotations
 
 import math
 import os
-from typing import Optional, Union
+from typing import List, Optional, Union
 
 import numpy as np
 import torch
@@ -134,6 +134,156 @@ def _decode_device(model, segments, bsz, L, continuous, scored, kw):
         tokens = tokens[:, :, 0]
         scores = scores[:, :, 0] if scored else None
     return tokens, scores
+
+
+class LiveTranscriber:
+    """transcribe() for audio that arrives in chunks: a microphone, a network stream, a long recording read in blocks.
+
+        live = LiveTranscriber(model, 44100, n_channels=2, dtype=torch.int16)
+        for chunk in source:                    # (n_frames, n_channels) PCM, at most max_chunk_frames frames
+            new_notes = live.push(chunk)        # the notes that became final
+        new_notes = live.finish()
+        live.write_midi("out.mid"); live.close()
+
+    A push (1) ingests the chunk (IngestStream; include/ymt3.h, streaming ingest), (2) decodes the segments it completed, one
+    model.inference call per at most `bsz` of them (None: as many as the model's max_batch allows), (3) pushes the ids, and the scores when
+    confidences are asked for, to the incremental detokeniser on the device (include/ymt3.h, incremental detokeniser) and (4) copies back
+    only the counters and the new records.  A note is returned once, when nothing later can change it: a pitched note when it ends, a
+    drum hit when the next segment's start has passed it.  `finish()` pads the tail as the one-shot ingest does and closes what still
+    sounds at the end of the audio.  The latency is one segment: the model decodes whole segments.
+
+    Decode options are transcribe()'s except `continuous`: `subtask`, `confidence` / `min_confidence`, `constrained` / `programs`,
+    `num_beams` / `length_penalty`, `max_token_length`.  `min_confidence` filters what push / finish return (and `notes`, and the MIDI
+    file); the state on the device keeps every note.  `max_held` bounds the drum hits the state holds per (channel, pitch); `forced`
+    counts the hits that had to leave early because of it (0 in any sane stream: a hit is held only while it lies past the start of a
+    segment that has not come yet).
+
+    The invariant: sorted(everything returned) and the MIDI bytes are those of transcribe(model, the whole PCM, device_detok=True, ...) with
+    the same options -- both ends are exact, so this holds whenever the decode gives a segment the same ids here and there.  Rows are
+    independent of batch composition only within a kernel regime (DESIGN, "Rows are independent of batch composition"): the two boundaries are 2048
+    (row, head) pairs, beyond which self-attention sums with 2 waves per pair, and 512 rows, from which the decode GEMMs take mid-size tiles.
+    A live session decodes a few segments per call and a file transcription up to `bsz`; the ids agree bit for bit as long as both stay on
+    the same side of both boundaries."""
+
+    def __init__(self, model, sample_rate: int, n_channels: int = 1, dtype=torch.int16, task_manager: Optional[TaskManager] = None,
+                 max_chunk_frames: int = 1 << 16, bsz: Optional[int] = None, max_token_length: Optional[int] = None,
+                 subtask: Optional[str] = None, confidence: bool = False, min_confidence: Optional[float] = None, constrained: bool = False,
+                 programs=None, num_beams: int = 1, length_penalty: float = 1.0, max_held: int = 16, name: str = "audio"):
+        cfg = model.cfg
+        self.model, self.name = model, name
+        self.num_beams = int(num_beams)
+        if self.num_beams < 1:
+            raise ValueError(f"num_beams={num_beams} must be >= 1")
+        room = model.max_batch // self.num_beams
+        if room < 1:
+            raise ValueError(f"num_beams={self.num_beams} needs max_batch >= {self.num_beams}, the model was created with max_batch={model.max_batch}")
+        self.bsz = room if bsz is None else max(1, min(int(bsz), room))
+        if task_manager is None:
+            task_manager = TaskManager("mc13_full_plus_256" if cfg.n_channels == 13 else "mt3_full_plus")
+        if task_manager.num_decoding_channels != cfg.n_channels:
+            raise ValueError("TaskManager channel count does not match the model's decoder")
+        self.task_manager = task_manager
+        prompt = None
+        if task_manager.subtasks:
+            prompt = torch.tensor(task_manager.task_prompt(subtask, 1)[0, 0])
+        elif subtask is not None:
+            raise ValueError(f"task {task_manager.task_name!r} has no sub-tasks (asked for {subtask!r})")
+        n_prompt = 0 if prompt is None else int(prompt.numel())
+        self.L = min(max_token_length or task_manager.max_note_token_length, cfg.max_decode_len - n_prompt)
+        self.scored = bool(confidence) or min_confidence is not None
+        self.min_confidence = None if min_confidence is None else float(min_confidence)
+        self._kw = {} if prompt is None else {"task_tokens": prompt}
+        if self.scored:
+            self._kw["return_scores"] = True
+        if self.num_beams > 1:
+            self._kw.update(num_beams=self.num_beams, num_return_sequences=1, length_penalty=length_penalty)
+        self._constraint = self._ingest = self._detok = self._state = None
+        try:
+            if constrained or programs is not None:
+                aut, starts = task_manager.event_automaton(programs)
+                self._constraint = model.compile_constraint(aut)
+                self._kw["constraint"] = self._constraint
+                self._kw["start_states"] = starts
+            self._ingest = model.compile_ingest_stream(sample_rate, n_channels, dtype, max_chunk_frames)
+            # the most segments one call can complete: a chunk's resampled samples on top of an almost whole partial segment
+            per_chunk = -(-int(max_chunk_frames) * cfg.sample_rate // int(sample_rate)) // cfg.segment_samples + 2
+            self._detok = model.compile_detokenizer(task_manager, per_chunk, self.L)
+            self._state = self._detok.new_state(max_held=max_held)
+        except Exception:
+            self.close()
+            raise
+        self.notes: List = []               # everything returned so far, in the order it became final
+        self.n_segments = 0                 # segments decoded so far
+        self.n_invalid = self.forced = 0
+        self.finished = False
+
+    def _decode(self, segments):
+        """(k, 1, S) segments -> ((k, K, L) ids, (k, K, L) scores or None) on the device, `bsz` segments per inference call"""
+        outs = [self.model.inference(segments[i:i + self.bsz], max_token_length=self.L, **self._kw) for i in range(0, segments.shape[0], self.bsz)]
+        tokens = torch.cat([o[0] if self.scored else o for o in outs], 0)
+        scores = torch.cat([o[1] for o in outs], 0) if self.scored else None
+        if self.num_beams > 1:              # (k, K, 1, L): hypothesis 0, read in place
+            tokens = tokens[:, :, 0]
+            scores = scores[:, :, 0] if self.scored else None
+        return tokens, scores
+
+    def _segments(self, segments, last: bool):
+        cfg = self.model.cfg
+        k = int(segments.shape[0])
+        if k == 0 and not last:
+            return []
+        starts = [(self.n_segments + i) * cfg.segment_samples / cfg.sample_rate for i in range(k)]
+        horizon = math.inf if last else (self.n_segments + k) * cfg.segment_samples / cfg.sample_rate
+        tokens, scores = self._decode(segments) if k else (torch.zeros(0, cfg.n_channels, self.L, dtype=torch.int32, device=self.model.device), None)
+        notes, bad, forced = self.task_manager.tokens_to_notes_stream(self.model, self._detok, self._state, tokens, starts, horizon, scores=scores,
+                                                                      scored=self.scored)
+        self.n_segments += k
+        self.n_invalid += bad
+        self.forced += forced
+        return notes
+
+    def _out(self, notes):
+        if self.min_confidence is not None:
+            notes = drop_low_confidence(notes, self.min_confidence)
+        self.notes += notes
+        return notes
+
+    def push(self, pcm) -> list:
+        """One chunk of (n_frames, n_channels) or (n_frames,) PCM -> the notes that became final, sorted."""
+        if self.finished:
+            raise ValueError("the session has been finished")
+        pcm = torch.as_tensor(pcm) if not isinstance(pcm, torch.Tensor) else pcm
+        return self._out(self._segments(self._ingest.push(pcm), last=False))
+
+    def finish(self) -> list:
+        """The end of the audio -> the remaining notes: the tail segments, every held hit, and what still sounds, closed at the end."""
+        if self.finished:
+            raise ValueError("the session has been finished")
+        segments, n_samples = self._ingest.finish()
+        notes = self._segments(segments, last=True)
+        last, _, _ = self.task_manager.tokens_to_notes_stream(self.model, self._detok, self._state, end_sec=n_samples / self.model.cfg.sample_rate,
+                                                              scored=self.scored)
+        self.finished = True
+        return self._out(sorted(notes + last))
+
+    def write_midi(self, path: Optional[str] = None, output_dir: str = ".") -> str:
+        """Write everything returned so far as a MIDI file -> its path (default: output_dir/name.mid, as transcribe())."""
+        if path is None:
+            os.makedirs(output_dir, exist_ok=True)
+            path = os.path.join(output_dir, self.name + ".mid")
+        return write_midi(sorted(self.notes), path)
+
+    def close(self):
+        for o in (getattr(self, "_state", None), getattr(self, "_detok", None), getattr(self, "_ingest", None), getattr(self, "_constraint", None)):
+            if o is not None:
+                o.close()
+        self._state = self._detok = self._ingest = self._constraint = None
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
 
 
 def score_notes(model, audio_info: Union[str, dict, np.ndarray], notes, task_manager: Optional[TaskManager] = None, bsz: int = 8,
