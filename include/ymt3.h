@@ -612,6 +612,61 @@ int  ymt3_frame_metrics(ymt3_handle h, ymt3_roll r,
                         const void* est_notes_dev, long long n_est, const int32_t* est_count_dev /* may be NULL */,
                         long long n_frames, long long* counts_dev /* [(n_programs + 1) * 6 + 2] */, void* stream);
 
+/* Device alignment: the monotone time map between a reference note set and an estimate, by banded dynamic time warping over frame-wise
+ * pitch sets, and the reference carried onto the estimate's time axis (YourMT3.compile_aligner, align(), evaluate(align=True); the
+ * specification is the host path, dtw_align and warp_notes of yourmt3_amd/metrics.py, which it reproduces exactly: every integer, and
+ * every byte of the warped records, NaN payloads aside).  The rules are this repository's own.  Records are the 32 bytes of the device
+ * detokeniser, 8-byte aligned, in any order; `score` is not read.
+ *   - features: a side with n frames has 256 bits per frame: the instrument-agnostic row of the piano roll above (all pitched counted
+ *     notes), then the drum row (row drum_program).  Counted records, F(t) = rint(t * frames_per_second), the one-frame rule, the
+ *     clipping in f64 before any conversion to an integer and skipped[2] are the piano roll's rules, word for word.  The two sides have
+ *     their OWN frame counts, n_ref_frames = Na and n_est_frames = Nb, each in [1, max_frames], max_frames <= 2^20.
+ *   - cost: c(i, j) = popc(ref_i XOR est_j) over the 256 bits, the size of the symmetric difference: 0 ... 256.
+ *   - band: with q = Na - 1, p = Nb - 1 and m = max(p, q, 1), cell (i, j) is in the band iff |i * p - j * q| <= band_frames * m, in
+ *     int64; band_frames >= 1.  The rule is symmetric in the two sides; (0, 0) and (q, p) are always in the band.
+ *   - recurrence: INF = 2^30.  D(0, 0) = c(0, 0); for every other in-band cell best = min(D(i-1, j-1), D(i-1, j), D(i, j-1)), a
+ *     predecessor outside the rectangle or the band counting as INF, and D = min(best + c, INF).  The cell's step is the FIRST of
+ *     (diagonal, (i-1, j), (i, j-1)) whose D equals best.  Out-of-band cells are INF.  A true cost stays below 2^29: int32 suffices.
+ *   - path: the steps followed from (q, p) back to (0, 0), reported in forward order as (i, j) int32 pairs, path_len <= Na + Nb - 1;
+ *     total = D(q, p); warp[i] = min { j : (i, j) on the path }, int32, non-decreasing, warp[0] = 0.  The path's last cell is (q, p), but
+ *     warp[q] is the LOWEST j of the path in row q: warp[q] <= p, and < p whenever the path ends along the last row (any 1 x N call gives
+ *     warp[0] = 0).  W therefore maps the reference's end to warp[q] / frames_per_second, not to the estimate's end.  If D(q, p) = INF
+ *     (not known to occur) path_len = 0, every warp[i] = -1 and total = INF.
+ *   - result_dev: [4] int64 = total, path_len, skipped ref, skipped est.  path_dev (may be NULL) is 8-byte aligned.
+ *   - warping a time: W(t) in f64, each operation rounded once, nothing contracted: x = t * frames_per_second; k = floor(x) clamped to
+ *     [0, q] in f64 before any conversion to an integer; f = x - k clamped to [0, 1]; a = warp[k], b = warp[min(k + 1, q)];
+ *     W = (a + f * (b - a)) / frames_per_second.  A NaN stays NaN, -inf gives 0, a time at or past the end gives warp[q] /
+ *     frames_per_second.  ymt3_warp_notes applies W to onset and offset of every record and copies program, pitch, is_drum and score: it
+ *     filters nothing.  notes_out_dev may equal notes_dev.
+ *   - count pointers (each may be NULL) are read ON THE DEVICE: the side then has min(n, max(*count, 0)) records.
+ *   - layout and kernels (yourmt3_amd/csrc/align.hip): the dynamic programme is a tiled, skewed wavefront with the longer side on the
+ *     lanes: one wave per tile of 256 x 64 cells, one launch per tile anti-diagonal, tiles wholly outside the band not run; a cell's
+ *     three predecessors come from the lane's own register, one cross-lane move and the value moved the step before; tiles hand their
+ *     last row, last column and last cell on through edge arrays in global memory.  Steps are 2 bits per cell, 16 consecutive cells of
+ *     a column of the longer side per dword; one workgroup walks the path back tile by tile from LDS.  No kernel waits on another
+ *     workgroup; the number of launches follows from the shapes alone.
+ * ymt3_aligner_create: synchronous; allocates all scratch.  With B = min(band_frames, max_frames) (a wider band changes no cell) and
+ * M = max_frames, in bytes: features 64 x M, step bits 4 x M x (B / 8 + 2), reversed path 8 x (2 x M - 1), edges about 8 x M + M / 12:
+ * 60 000 frames under a band of 3000 take about 95 MB.  Checks (YMT3_ERR_ARG naming the argument): params not NULL, frames_per_second
+ * finite and > 0, n_programs >= 1, drum_program in [0, n_programs), band_frames >= 1, max_frames in [1, 2^20]; n_programs above 256 is
+ * YMT3_ERR_UNSUPPORTED; a failed allocation is YMT3_ERR_HIP with nothing leaked and no object returned.  The object belongs to h;
+ * ymt3_aligner_destroy frees it (NULL is a no-op), before or after the handle's destruction.
+ * ymt3_align_notes / ymt3_warp_notes: asynchronous on `stream`, allocate nothing, leave the handle's decode state alone.  YMT3_ERR_ARG,
+ * with handle and object still usable, for a frame count outside [1, max_frames], a note count outside [0, 2^29], NULL or misaligned
+ * warp_dev / result_dev, a misaligned path_dev, or a NULL or misaligned record pointer with n > 0.  One object serves one call at a
+ * time. */
+typedef struct ymt3_align_params { double frames_per_second; int32_t n_programs, drum_program, band_frames; } ymt3_align_params;
+typedef struct ymt3_aligner_s* ymt3_aligner;
+int  ymt3_aligner_create(ymt3_handle h, const ymt3_align_params* p, long long max_frames, ymt3_aligner* out);
+void ymt3_aligner_destroy(ymt3_aligner a);
+int  ymt3_align_notes(ymt3_handle h, ymt3_aligner a,
+                      const void* ref_notes_dev, long long n_ref, const int32_t* ref_count_dev /* may be NULL */, long long n_ref_frames,
+                      const void* est_notes_dev, long long n_est, const int32_t* est_count_dev /* may be NULL */, long long n_est_frames,
+                      int32_t* warp_dev /* [n_ref_frames] */, int32_t* path_dev /* may be NULL; [(n_ref_frames + n_est_frames - 1) * 2] */,
+                      long long* result_dev /* [4]: total, path_len, skipped ref, skipped est */, void* stream);
+int  ymt3_warp_notes(ymt3_handle h, ymt3_aligner a, const void* notes_dev, long long n_notes, const int32_t* count_dev /* may be NULL */,
+                     const int32_t* warp_dev, long long n_ref_frames, void* notes_out_dev, void* stream);
+
 /* Measurement hook (bench.py `roofline`): decode eagerly (no graph) and bracket every kernel launch of
  * every `stride`-th step (positions stride/2, 3*stride/2, ...) with HIP events on `stream`; synchronises the stream before returning.
  * Classes: 0 qkv+cache GEMM, 1 self-attention, 2 self O-proj, 3 cross Q GEMM, 4 cross-attention,

@@ -2,7 +2,8 @@
 `import yourmt3_amd` works without a GPU or the built library."""
 
 __all__ = ["YMT3Config", "YourMT3", "TaskManager", "transcribe", "score_notes", "evaluate", "note_metrics", "NoteMetrics", "piano_roll", "frame_metrics",
-           "FrameMetricCounts", "PianoRoll", "baseline_config", "LiveTranscriber", "NoteStream"]
+           "FrameMetricCounts", "PianoRoll", "baseline_config", "LiveTranscriber", "NoteStream", "dtw_align", "warp_notes", "Alignment", "Aligner",
+           "align"]
 
 
 def __getattr__(name):
@@ -33,7 +34,7 @@ def __getattr__(name):
     if name == "piano_roll":
         from .transcribe import piano_roll
         return piano_roll
-    if name in ("frame_metrics", "FrameMetricCounts"):
+    if name in ("frame_metrics", "FrameMetricCounts", "dtw_align", "warp_notes", "Alignment"):
         from . import metrics
         return getattr(metrics, name)
     if name == "LiveTranscriber":
@@ -45,4 +46,10 @@ def __getattr__(name):
     if name == "PianoRoll":
         from .model import PianoRoll
         return PianoRoll
+    if name == "Aligner":
+        from .model import Aligner
+        return Aligner
+    if name == "align":
+        from .transcribe import align
+        return align
     raise AttributeError(name)

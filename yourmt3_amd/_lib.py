@@ -28,6 +28,7 @@ SYMBOLS = [
     "ymt3_tok_create", "ymt3_tok_destroy", "ymt3_tokenize",
     "ymt3_metrics_create", "ymt3_metrics_destroy", "ymt3_note_metrics",
     "ymt3_roll_create", "ymt3_roll_destroy", "ymt3_piano_roll", "ymt3_frame_metrics",
+    "ymt3_aligner_create", "ymt3_aligner_destroy", "ymt3_align_notes", "ymt3_warp_notes",
     "ymt3_ingest_stream_create", "ymt3_ingest_stream_destroy", "ymt3_ingest_stream_reset", "ymt3_ingest_stream_plan",
     "ymt3_ingest_stream_push", "ymt3_ingest_stream_finish",
     "ymt3_detok_state_create", "ymt3_detok_state_destroy", "ymt3_detok_state_reset", "ymt3_detok_state_carry",
@@ -57,6 +58,12 @@ class MetricsParams(ctypes.Structure):
 class RollParams(ctypes.Structure):
     """ymt3_roll_params of include/ymt3.h"""
     _fields_ = [("frames_per_second", ctypes.c_double), ("n_programs", ctypes.c_int32), ("drum_program", ctypes.c_int32)]
+
+
+class AlignParams(ctypes.Structure):
+    """ymt3_align_params of include/ymt3.h"""
+    _fields_ = [("frames_per_second", ctypes.c_double), ("n_programs", ctypes.c_int32), ("drum_program", ctypes.c_int32),
+                ("band_frames", ctypes.c_int32)]
 
 
 class YMT3Error(RuntimeError):
@@ -182,6 +189,14 @@ def load() -> ctypes.CDLL:
     lib.ymt3_piano_roll.restype = i32
     lib.ymt3_frame_metrics.argtypes = [vp, vp, vp, ctypes.c_longlong, vp, vp, ctypes.c_longlong, vp, ctypes.c_longlong, vp, vp]
     lib.ymt3_frame_metrics.restype = i32
+    lib.ymt3_aligner_create.argtypes = [vp, ctypes.POINTER(AlignParams), ctypes.c_longlong, ctypes.POINTER(vp)]
+    lib.ymt3_aligner_create.restype = i32
+    lib.ymt3_aligner_destroy.argtypes = [vp]
+    lib.ymt3_aligner_destroy.restype = None
+    lib.ymt3_align_notes.argtypes = [vp, vp, vp, ctypes.c_longlong, vp, ctypes.c_longlong, vp, ctypes.c_longlong, vp, ctypes.c_longlong, vp, vp, vp, vp]
+    lib.ymt3_align_notes.restype = i32
+    lib.ymt3_warp_notes.argtypes = [vp, vp, vp, ctypes.c_longlong, vp, vp, ctypes.c_longlong, vp, vp]
+    lib.ymt3_warp_notes.restype = i32
     i64 = ctypes.c_int64
     lib.ymt3_ingest_stream_create.argtypes = [vp, i32, i32, i32, i64, ctypes.POINTER(vp)]
     lib.ymt3_ingest_stream_create.restype = i32

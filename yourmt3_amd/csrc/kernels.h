@@ -158,6 +158,45 @@ struct RollArgs {
 int launch_frame_metrics(const RollArgs& a, hipStream_t stream);
 int launch_piano_roll(const RollArgs& a, hipStream_t stream);
 
+// ---------------------------------------------------------------- device alignment: banded DTW over pitch sets (align.hip; include/ymt3.h, alignment)
+constexpr int ALIGN_INF = 1 << 30;
+constexpr long long ALIGN_MAX_FRAMES = 1LL << 20;
+constexpr int ALIGN_TILE_ROWS = 256, ALIGN_TILE_COLS = 64;               // a tile of the dynamic programme: one wave, one lane per column
+// scratch sizing, shared by ymt3_aligner_create and the launches (band = min(band_frames, max_frames): a wider band changes no cell)
+inline long long align_step_words(long long band) { return band / 8 + 2; }                       // dwords per column: 2 bits x (2 * band + 1) rows, 16-row groups
+inline long long align_padded(long long frames, int tile) { return (frames + tile - 1) / tile * tile; }
+inline long long align_corners(long long max_frames) { return align_padded(max_frames, ALIGN_TILE_ROWS) / ALIGN_TILE_ROWS + align_padded(max_frames, ALIGN_TILE_COLS) / ALIGN_TILE_COLS; }
+inline long long align_edge_ints(long long max_frames) {                                          // bottom, right, corners, total
+    return align_padded(max_frames, ALIGN_TILE_COLS) + align_padded(max_frames, ALIGN_TILE_ROWS) + align_corners(max_frames) + 1;
+}
+struct AlignArgs {
+    double frames_per_second;
+    int n_programs, drum_program;
+    long long band_frames;                // min(the object's band_frames, max_frames)
+    const DetokNote* notes[2];            // reference, estimate: [n[side]]
+    long long n[2];
+    const int32_t* count[2];              // device counts (or null): the side has min(n, max(*count, 0)) records
+    long long n_frames[2], max_frames;    // each in [1, max_frames]
+    uint4* feat;                          // [2][max_frames][2] 128 pitch bits each: the agnostic word, then the drum word
+    int* edges;                           // [align_edge_ints(max_frames)]
+    unsigned* steps;                      // [max_frames][align_step_words(band_frames)]
+    int2* rpath;                          // [2 * max_frames - 1] the path, last cell first
+    int32_t* warp;                        // [n_frames[0]]
+    int32_t* path;                        // [(n_frames[0] + n_frames[1] - 1) * 2] or null
+    long long* result;                    // [4]: total, path_len, skipped ref, skipped est
+};
+int launch_align(const AlignArgs& a, hipStream_t stream);
+struct WarpNotesArgs {
+    double frames_per_second;
+    const DetokNote* notes;               // [n]
+    DetokNote* out;                       // [n]; may be `notes`
+    long long n;
+    const int32_t* count;                 // device count (or null)
+    const int32_t* warp;                  // [n_ref_frames]
+    long long n_ref_frames;
+};
+int launch_warp_notes(const WarpNotesArgs& a, hipStream_t stream);
+
 // ---------------------------------------------------------------- dense GEMM (gemm.hip)
 // C[M][N] (+)= A[M][K] (bf16, row stride lda) * W[N][K]^T (bf16, row stride ldw), fp32 accumulate.
 enum GemmEpilogue {

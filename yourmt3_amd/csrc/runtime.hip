@@ -1169,6 +1169,107 @@ extern "C" int ymt3_frame_metrics(ymt3_handle h, ymt3_roll r, const void* ref_no
     return YMT3_OK;
 }
 
+// ---------------------------------------------------------------- device alignment (include/ymt3.h)
+struct ymt3_aligner_s {
+    ymt3_ctx* owner;
+    int device;
+    ymt3_align_params p;
+    long long max_frames, band;             // band = min(p.band_frames, max_frames)
+    uint4* feat = nullptr;                  // [2][max_frames][2]
+    int* edges = nullptr;                   // [align_edge_ints(max_frames)]
+    unsigned* steps = nullptr;              // [max_frames][align_step_words(band)]
+    int2* rpath = nullptr;                  // [2 * max_frames - 1]
+};
+
+extern "C" void ymt3_aligner_destroy(ymt3_aligner a) {
+    if (!a) return;
+    (void)hipSetDevice(a->device);
+    for (void* p : {(void*)a->feat, (void*)a->edges, (void*)a->steps, (void*)a->rpath})
+        if (p) (void)hipFree(p);
+    delete a;
+}
+
+extern "C" int ymt3_aligner_create(ymt3_handle h, const ymt3_align_params* params, long long max_frames, ymt3_aligner* out) {
+    if (!out) FAIL(YMT3_ERR_ARG, "null output pointer");
+    *out = nullptr;
+    if (!h) FAIL(YMT3_ERR_ARG, "null handle");
+    if (!params) FAIL(YMT3_ERR_ARG, "params is NULL");
+    const ymt3_align_params& p = *params;
+    if (!std::isfinite(p.frames_per_second) || p.frames_per_second <= 0) FAIL(YMT3_ERR_ARG, "frames_per_second=%g must be finite and > 0", p.frames_per_second);
+    if (p.n_programs < 1) FAIL(YMT3_ERR_ARG, "n_programs=%d must be >= 1", p.n_programs);
+    if (p.n_programs > ROLL_MAX_PROGRAMS) FAIL(YMT3_ERR_UNSUPPORTED, "n_programs=%d: at most %d programs", p.n_programs, ROLL_MAX_PROGRAMS);
+    if (p.drum_program < 0 || p.drum_program >= p.n_programs) FAIL(YMT3_ERR_ARG, "drum_program=%d outside [0, n_programs=%d)", p.drum_program, p.n_programs);
+    if (p.band_frames < 1) FAIL(YMT3_ERR_ARG, "band_frames=%d must be >= 1", p.band_frames);
+    if (max_frames < 1 || max_frames > ALIGN_MAX_FRAMES) FAIL(YMT3_ERR_ARG, "max_frames=%lld outside [1, %lld]", max_frames, ALIGN_MAX_FRAMES);
+    HIP_TRY(hipSetDevice(h->device));
+    ymt3_aligner a = new ymt3_aligner_s{h, h->device, p, max_frames, std::min<long long>(p.band_frames, max_frames)};
+    const size_t feat_bytes = (size_t)2 * max_frames * 2 * sizeof(uint4), edge_bytes = (size_t)align_edge_ints(max_frames) * sizeof(int);
+    const size_t step_bytes = (size_t)max_frames * align_step_words(a->band) * sizeof(unsigned), path_bytes = (size_t)(2 * max_frames - 1) * sizeof(int2);
+    if (hipMalloc(reinterpret_cast<void**>(&a->feat), feat_bytes) != hipSuccess ||
+        hipMalloc(reinterpret_cast<void**>(&a->edges), edge_bytes) != hipSuccess ||
+        hipMalloc(reinterpret_cast<void**>(&a->steps), step_bytes) != hipSuccess ||
+        hipMalloc(reinterpret_cast<void**>(&a->rpath), path_bytes) != hipSuccess) {
+        (void)hipGetLastError();
+        ymt3_aligner_destroy(a);
+        FAIL(YMT3_ERR_HIP, "alignment scratch (%zu bytes) could not be allocated", feat_bytes + edge_bytes + step_bytes + path_bytes);
+    }
+    *out = a;
+    return YMT3_OK;
+}
+
+static int align_side(AlignArgs* a, int side, const char* n_name, const char* ptr_name, const char* frames_name, const void* notes_dev, long long n,
+                      const int32_t* count_dev, long long n_frames) {
+    if (n_frames < 1 || n_frames > a->max_frames) FAIL(YMT3_ERR_ARG, "%s=%lld outside [1, max_frames=%lld]", frames_name, n_frames, a->max_frames);
+    if (n < 0 || n > ROLL_MAX_NOTES) FAIL(YMT3_ERR_ARG, "%s=%lld outside [0, %lld]", n_name, n, ROLL_MAX_NOTES);
+    if (n && !notes_dev) FAIL(YMT3_ERR_ARG, "%s is NULL", ptr_name);
+    if (n && reinterpret_cast<uintptr_t>(notes_dev) % 8) FAIL(YMT3_ERR_ARG, "%s is not aligned to 8 bytes", ptr_name);
+    a->notes[side] = static_cast<const DetokNote*>(notes_dev); a->n[side] = n; a->count[side] = n ? count_dev : nullptr; a->n_frames[side] = n_frames;
+    return YMT3_OK;
+}
+
+extern "C" int ymt3_align_notes(ymt3_handle h, ymt3_aligner al, const void* ref_notes_dev, long long n_ref, const int32_t* ref_count_dev,
+                                long long n_ref_frames, const void* est_notes_dev, long long n_est, const int32_t* est_count_dev,
+                                long long n_est_frames, int32_t* warp_dev, int32_t* path_dev, long long* result_dev, void* stream) {
+    if (!h) FAIL(YMT3_ERR_ARG, "null handle");
+    if (!al) FAIL(YMT3_ERR_ARG, "null aligner object");
+    if (al->owner != h) FAIL(YMT3_ERR_ARG, "the aligner object belongs to another handle");
+    AlignArgs a{};
+    a.frames_per_second = al->p.frames_per_second; a.n_programs = al->p.n_programs; a.drum_program = al->p.drum_program;
+    a.band_frames = al->band; a.max_frames = al->max_frames;
+    if (const int rc = align_side(&a, 0, "n_ref", "ref_notes_dev", "n_ref_frames", ref_notes_dev, n_ref, ref_count_dev, n_ref_frames)) return rc;
+    if (const int rc = align_side(&a, 1, "n_est", "est_notes_dev", "n_est_frames", est_notes_dev, n_est, est_count_dev, n_est_frames)) return rc;
+    if (!warp_dev) FAIL(YMT3_ERR_ARG, "warp_dev is NULL");
+    if (reinterpret_cast<uintptr_t>(warp_dev) % 4) FAIL(YMT3_ERR_ARG, "warp_dev is not aligned to 4 bytes");
+    if (reinterpret_cast<uintptr_t>(path_dev) % 8) FAIL(YMT3_ERR_ARG, "path_dev is not aligned to 8 bytes");
+    if (!result_dev) FAIL(YMT3_ERR_ARG, "result_dev is NULL");
+    if (reinterpret_cast<uintptr_t>(result_dev) % 8) FAIL(YMT3_ERR_ARG, "result_dev is not aligned to 8 bytes");
+    HIP_TRY(hipSetDevice(h->device));
+    a.feat = al->feat; a.edges = al->edges; a.steps = al->steps; a.rpath = al->rpath;
+    a.warp = warp_dev; a.path = path_dev; a.result = result_dev;
+    LAUNCH(launch_align(a, static_cast<hipStream_t>(stream)));
+    return YMT3_OK;
+}
+
+extern "C" int ymt3_warp_notes(ymt3_handle h, ymt3_aligner al, const void* notes_dev, long long n_notes, const int32_t* count_dev,
+                               const int32_t* warp_dev, long long n_ref_frames, void* notes_out_dev, void* stream) {
+    if (!h) FAIL(YMT3_ERR_ARG, "null handle");
+    if (!al) FAIL(YMT3_ERR_ARG, "null aligner object");
+    if (al->owner != h) FAIL(YMT3_ERR_ARG, "the aligner object belongs to another handle");
+    if (n_ref_frames < 1 || n_ref_frames > al->max_frames) FAIL(YMT3_ERR_ARG, "n_ref_frames=%lld outside [1, max_frames=%lld]", n_ref_frames, al->max_frames);
+    if (n_notes < 0 || n_notes > ROLL_MAX_NOTES) FAIL(YMT3_ERR_ARG, "n_notes=%lld outside [0, %lld]", n_notes, ROLL_MAX_NOTES);
+    if (!warp_dev) FAIL(YMT3_ERR_ARG, "warp_dev is NULL");
+    if (reinterpret_cast<uintptr_t>(warp_dev) % 4) FAIL(YMT3_ERR_ARG, "warp_dev is not aligned to 4 bytes");
+    if (n_notes && !notes_dev) FAIL(YMT3_ERR_ARG, "notes_dev is NULL");
+    if (n_notes && reinterpret_cast<uintptr_t>(notes_dev) % 8) FAIL(YMT3_ERR_ARG, "notes_dev is not aligned to 8 bytes");
+    if (n_notes && !notes_out_dev) FAIL(YMT3_ERR_ARG, "notes_out_dev is NULL");
+    if (n_notes && reinterpret_cast<uintptr_t>(notes_out_dev) % 8) FAIL(YMT3_ERR_ARG, "notes_out_dev is not aligned to 8 bytes");
+    HIP_TRY(hipSetDevice(h->device));
+    WarpNotesArgs a{al->p.frames_per_second, static_cast<const DetokNote*>(notes_dev), static_cast<DetokNote*>(notes_out_dev), n_notes,
+                    n_notes ? count_dev : nullptr, warp_dev, n_ref_frames};
+    LAUNCH(launch_warp_notes(a, static_cast<hipStream_t>(stream)));
+    return YMT3_OK;
+}
+
 // the kernels' view of a call's constraint (all null without one)
 static int constraint_view(ymt3_handle h, ymt3_constraint c, const int32_t* start_state_dev, ConstraintView* cv) {
     *cv = ConstraintView{};

@@ -395,3 +395,177 @@ def frame_metrics(ref, est, n_frames: int, n_programs: int, drum_program: int = 
     counts = np.stack([tp.sum(1), nr.sum(1), ne.sum(1), (np.minimum(nr, ne) - tp).sum(1), np.maximum(0, nr - ne).sum(1),
                        np.maximum(0, ne - nr).sum(1)], 1)
     return FrameMetricCounts(counts, (skipped_r, skipped_e), drum_program)
+
+
+# ---------------------------------------------------------------- alignment: banded DTW over pitch sets (the rules: DESIGN.md section 20)
+# The device path (include/ymt3.h, alignment; yourmt3_amd/csrc/align.hip) reproduces every integer of dtw_align and every byte of
+# warp_notes.  Features: per side and frame 256 bits, the instrument-agnostic row of the frame metrics (all pitched counted notes) and
+# the drum row, each side at its OWN frame count.  Cost c(i, j) = popc(ref_i XOR est_j), 0 ... 256.  Band: with q = Na - 1, p = Nb - 1,
+# m = max(p, q, 1), cell (i, j) is in the band iff |i * p - j * q| <= band_frames * m (int64).  D(0, 0) = c(0, 0); every other in-band
+# cell: best = min(D(i-1, j-1), D(i-1, j), D(i, j-1)), a predecessor outside the rectangle or the band being INF = 2^30, D = min(best + c,
+# INF), and the cell's step is the FIRST of (diagonal, (i-1, j), (i, j-1)) whose D equals best.  The path follows the steps from (q, p)
+# back to (0, 0); warp[i] is the lowest j of the path in row i: warp[0] = 0, and warp[q] <= p, below p when the path ends along row q.
+ALIGN_INF = 1 << 30
+ALIGN_MAX_FRAMES = 1 << 20
+_POPC8 = np.array([bin(v).count("1") for v in range(256)], np.int32)
+
+
+class Alignment:
+    """One alignment: `total` = D(q, p); `path`: (n, 2) int32, the cells (i, j) from (0, 0) to (q, p); `warp`: (Na,) int32, the lowest j of
+    the path per i; `skipped`: (2,) int64 (ref, est) records not counted.  flat() is total, path_len, skipped[2], warp[Na], path[n][2] as
+    int64; from_flat reads it back."""
+
+    def __init__(self, total, path, warp, skipped):
+        self.total = int(total)
+        self.path = np.asarray(path, np.int32).reshape(-1, 2)
+        self.warp = np.asarray(warp, np.int32).reshape(-1)
+        self.skipped = np.asarray(skipped, np.int64)
+        if self.skipped.shape != (2,) or self.warp.size < 1:
+            raise ValueError(f"warp {self.warp.shape} / skipped {self.skipped.shape} are not (Na >= 1,) / (2,)")
+
+    @property
+    def path_len(self) -> int:
+        return int(self.path.shape[0])
+
+    def flat(self) -> np.ndarray:
+        return np.concatenate([[self.total, self.path_len], self.skipped, self.warp.astype(np.int64), self.path.reshape(-1).astype(np.int64)]).astype(np.int64)
+
+    @classmethod
+    def from_flat(cls, flat, n_ref_frames: int) -> "Alignment":
+        flat = np.asarray(flat, np.int64).reshape(-1)
+        if flat.size < 4 + n_ref_frames or flat.size != 4 + n_ref_frames + 2 * int(flat[1]):
+            raise ValueError(f"{flat.size} integers do not hold 4 + {n_ref_frames} + 2 * path_len")
+        return cls(flat[0], flat[4 + n_ref_frames:], flat[4:4 + n_ref_frames], flat[2:4])
+
+    def __eq__(self, other):
+        return isinstance(other, Alignment) and np.array_equal(self.flat(), other.flat())
+
+    def __repr__(self):
+        return f"Alignment(total={self.total}, path_len={self.path_len}, n_ref_frames={self.warp.size})"
+
+
+def _check_align(n_ref_frames, n_est_frames, n_programs, drum_program, frames_per_second, band_frames):
+    if not (np.isfinite(frames_per_second) and frames_per_second > 0):
+        raise ValueError(f"frames_per_second={frames_per_second} must be finite and > 0")
+    for name, v in (("n_ref_frames", n_ref_frames), ("n_est_frames", n_est_frames)):
+        if v < 1 or v > ALIGN_MAX_FRAMES:
+            raise ValueError(f"{name}={v} outside [1, {ALIGN_MAX_FRAMES}]")
+    if band_frames < 1:
+        raise ValueError(f"band_frames={band_frames} must be >= 1")
+    if n_programs < 1 or not 0 <= drum_program < n_programs:
+        raise ValueError(f"n_programs={n_programs} must be >= 1 and drum_program={drum_program} inside [0, n_programs)")
+
+
+def align_features(notes, n_frames: int, n_programs: int, drum_program: int = DRUM_PROGRAM, frames_per_second: float = 100.0):
+    """-> ((n_frames, 4) uint64: the 256 bits of every frame, agnostic row then drum row, bit `pitch` of each; skipped records)"""
+    keys, skipped = _cells(notes, int(n_frames), n_programs, drum_program, float(frames_per_second))
+    row, rest = np.divmod(keys, int(n_frames) * PITCHES)
+    frame, pitch = np.divmod(rest, PITCHES)
+    feat = np.zeros((int(n_frames), 4), np.uint64)
+    for r, half in ((n_programs, 0), (drum_program, 2)):
+        sel = row == r
+        np.bitwise_or.at(feat, (frame[sel], half + pitch[sel] // 64), np.uint64(1) << (pitch[sel] % 64).astype(np.uint64))
+    return feat, skipped
+
+
+def _popc_rows(x: np.ndarray) -> np.ndarray:
+    """(n, 4) uint64 -> (n,) int32 set bits"""
+    if hasattr(np, "bitwise_count"):
+        return np.bitwise_count(x).sum(1, dtype=np.int32)
+    return _POPC8[np.ascontiguousarray(x).view(np.uint8)].sum(1, dtype=np.int32)
+
+
+def _diag_range(d: int, p: int, q: int, bm: int):
+    """the in-band i of anti-diagonal d = i + j: i * p - (d - i) * q in [-bm, bm], inside the rectangle"""
+    lo, hi = max(0, d - p), min(d, q)
+    if p + q:
+        lo, hi = max(lo, -((bm - d * q) // (p + q))), min(hi, (d * q + bm) // (p + q))
+    return lo, hi
+
+
+def _take(prev, lo: int, n: int) -> np.ndarray:
+    """D of a stored anti-diagonal (its first i, its values) at i = lo ... lo + n - 1; INF outside"""
+    out = np.full(n, ALIGN_INF, np.int32)
+    if prev is not None:
+        plo, vals = prev
+        a, b = max(lo, plo), min(lo + n, plo + vals.size)
+        if a < b:
+            out[a - lo:b - lo] = vals[a - plo:b - plo]
+    return out
+
+
+def dtw_align(ref, est, n_ref_frames: int, n_est_frames: int, n_programs: int, drum_program: int = DRUM_PROGRAM, frames_per_second: float = 100.0,
+              band_frames: int = 1000) -> Alignment:
+    """Align the reference `ref` (n_ref_frames frames) to the estimate `est` (n_est_frames frames) by the rules above, one anti-diagonal
+    of the band at a time."""
+    _check_align(n_ref_frames, n_est_frames, n_programs, drum_program, frames_per_second, band_frames)
+    na, nb = int(n_ref_frames), int(n_est_frames)
+    fr, skipped_r = align_features(ref, na, n_programs, drum_program, frames_per_second)
+    fe, skipped_e = align_features(est, nb, n_programs, drum_program, frames_per_second)
+    q, p = na - 1, nb - 1
+    bm = int(band_frames) * max(p, q, 1)
+    prev1 = prev2 = None
+    steps = []                                                           # per anti-diagonal: (first i, uint8 steps) or None
+    for d in range(q + p + 1):
+        lo, hi = _diag_range(d, p, q, bm)
+        if lo > hi:
+            prev2, prev1 = prev1, None
+            steps.append(None)
+            continue
+        n = hi - lo + 1
+        i = np.arange(lo, hi + 1)
+        cost = _popc_rows(fr[i] ^ fe[d - i])
+        diag, up, left = _take(prev2, lo - 1, n), _take(prev1, lo - 1, n), _take(prev1, lo, n)
+        best = np.minimum(np.minimum(diag, up), left)
+        step = np.where(diag == best, 0, np.where(up == best, 1, 2)).astype(np.uint8)
+        if d == 0:
+            best = np.zeros(1, np.int32)
+        val = np.minimum(best.astype(np.int64) + cost, ALIGN_INF).astype(np.int32)
+        prev2, prev1 = prev1, (lo, val)
+        steps.append((lo, step))
+    total = int(prev1[1][0]) if prev1 is not None else ALIGN_INF
+    if total >= ALIGN_INF:
+        return Alignment(ALIGN_INF, np.zeros((0, 2), np.int32), np.full(na, -1, np.int32), (skipped_r, skipped_e))
+    path = []
+    i, j = q, p
+    while True:
+        path.append((i, j))
+        if i == 0 and j == 0:
+            break
+        lo, step = steps[i + j]
+        s = int(step[i - lo])
+        i, j = i - (s != 2), j - (s != 1)
+    path = np.array(path[::-1], np.int32)
+    warp = np.zeros(na, np.int32)
+    first = np.concatenate([[True], path[1:, 0] != path[:-1, 0]])
+    warp[path[first, 0]] = path[first, 1]
+    return Alignment(total, path, warp, (skipped_r, skipped_e))
+
+
+def warp_times(t, warp, frames_per_second: float) -> np.ndarray:
+    """W(t) of the rules in f64, elementwise: x = t * fps; k = floor(x) clamped to [0, q]; f = x - k clamped to [0, 1];
+    W = (warp[k] + f * (warp[min(k + 1, q)] - warp[k])) / fps.  NaN stays NaN, -inf gives 0, a time at or past the end warp[q] / fps."""
+    warp = np.asarray(warp, np.int32).reshape(-1)
+    if warp.size < 1:
+        raise ValueError("warp must hold at least one frame")
+    if not (np.isfinite(frames_per_second) and frames_per_second > 0):
+        raise ValueError(f"frames_per_second={frames_per_second} must be finite and > 0")
+    fps, q = np.float64(frames_per_second), warp.size - 1
+    with np.errstate(invalid="ignore"):
+        x = np.asarray(t, np.float64) * fps
+        nan = np.isnan(x)
+        k = np.minimum(np.maximum(np.floor(np.where(nan, 0.0, x)), 0.0), np.float64(q))
+        f = np.minimum(np.maximum(np.where(nan, 0.0, x) - k, 0.0), 1.0)
+        ki = k.astype(np.int64)
+        a, b = warp[ki].astype(np.float64), warp[np.minimum(ki + 1, q)].astype(np.float64)
+        w = (a + f * (b - a)) / fps
+    return np.where(nan, np.float64("nan"), w)
+
+
+def warp_notes(records, warp, frames_per_second: float = 100.0) -> np.ndarray:
+    """Carry a note set (a list of Note, or a NOTE_RECORD array) onto the estimate's time axis: W applied to onset and offset of every
+    record, everything else copied, nothing filtered -> a new NOTE_RECORD array."""
+    out = to_records(records).copy()
+    out["onset"] = warp_times(out["onset"], warp, frames_per_second)
+    out["offset"] = warp_times(out["offset"], warp, frames_per_second)
+    return out

@@ -412,6 +412,81 @@ class PianoRoll:
             pass
 
 
+class Aligner:
+    """The device alignment of one model (YourMT3.compile_aligner; include/ymt3.h, alignment; the rules and the host specification: dtw_align
+    and warp_notes of yourmt3_amd/metrics.py): the parameters and all scratch for sides of up to `max_frames` frames under a band of
+    `band_frames`.  Freed by close(), by leaving a `with` block, or by the model's close()."""
+
+    def __init__(self, model: "YourMT3", n_programs: int, max_frames: int, frames_per_second: float = 100.0, band_frames: int = 1000,
+                 drum_program: int = DRUM_PROGRAM):
+        self.n_programs, self.drum_program = int(n_programs), int(drum_program)
+        self.max_frames, self.frames_per_second, self.band_frames = int(max_frames), float(frames_per_second), int(band_frames)
+        self._model = weakref.ref(model)
+        self._lib = model._lib
+        self._c = ctypes.c_void_p()
+        params = _lib.AlignParams(self.frames_per_second, self.n_programs, self.drum_program, max(min(self.band_frames, 2 ** 31 - 1), -1))
+        _lib.check(self._lib.ymt3_aligner_create(model._handle, ctypes.byref(params), self.max_frames, ctypes.byref(self._c)))
+
+    @property
+    def ptr(self):
+        if not self._c.value:
+            raise ValueError("the aligner object has been closed")
+        return self._c
+
+    _side = PianoRoll._side
+
+    def align(self, ref_records: torch.Tensor, est_records: torch.Tensor, n_ref_frames: int, n_est_frames: int,
+              ref_count: Optional[torch.Tensor] = None, est_count: Optional[torch.Tensor] = None, path: bool = False):
+        """NOTE_RECORD bytes for both sides (uint8, a multiple of 32; on the host: uploaded) -> (warp, result) or, with `path=True`,
+        (warp, result, path), device tensors: warp (n_ref_frames,) int32; result (4,) int64 = total, path_len, skipped ref, skipped est;
+        path (n_ref_frames + n_est_frames - 1, 2) int32, of which the first path_len rows are written.  Counts as PianoRoll.metrics takes
+        them.  Asynchronous: nothing is copied back."""
+        model = self._model()
+        if model is None:
+            raise ValueError("the aligner object's model is gone")
+        (r, nr, rc), (e, ne, ec) = (self._side(model, name, rec, cnt) for name, rec, cnt in (("ref_records", ref_records, ref_count),
+                                                                                            ("est_records", est_records, est_count)))
+        na, nb = int(n_ref_frames), int(n_est_frames)
+        warp = torch.empty(max(na, 1), device=model.device, dtype=torch.int32)
+        result = torch.empty(4, device=model.device, dtype=torch.int64)
+        cells = torch.empty((max(na + nb - 1, 1), 2), device=model.device, dtype=torch.int32) if path else None
+        _lib.check(self._lib.ymt3_align_notes(model._handle, self.ptr, _ptr(r) if nr else None, nr, _ptr(rc), na, _ptr(e) if ne else None, ne,
+                                              _ptr(ec), nb, _ptr(warp), _ptr(cells), _ptr(result), model._stream()))
+        return (warp, result, cells) if path else (warp, result)
+
+    def warp(self, records: torch.Tensor, warp: torch.Tensor, count: Optional[torch.Tensor] = None) -> torch.Tensor:
+        """NOTE_RECORD bytes and the warp of align() -> the records with W applied to onset and offset (metrics.warp_notes), a new uint8
+        tensor on the device; with `count`, records past it are copied as they are.  Asynchronous."""
+        model = self._model()
+        if model is None:
+            raise ValueError("the aligner object's model is gone")
+        rec, n, cnt = self._side(model, "records", records, count)
+        if warp.dtype != torch.int32 or warp.dim() != 1 or not warp.numel():
+            raise ValueError("warp must be a 1-D int32 tensor of n_ref_frames elements")
+        warp = warp.to(model.device).contiguous()
+        out = rec.clone()
+        _lib.check(self._lib.ymt3_warp_notes(model._handle, self.ptr, _ptr(out) if n else None, n, _ptr(cnt), _ptr(warp), int(warp.numel()),
+                                             _ptr(out) if n else None, model._stream()))
+        return out
+
+    def close(self):
+        if getattr(self, "_c", None) is not None and self._c.value:
+            self._lib.ymt3_aligner_destroy(self._c)
+            self._c = ctypes.c_void_p()
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
 class IngestStream:
     """Streaming ingest of one model for one PCM format (YourMT3.compile_ingest_stream; include/ymt3.h, streaming ingest): PCM arrives
     in chunks of at most `max_chunk_frames` frames, whole segments come out as soon as their last sample is final, and all of them
@@ -664,6 +739,15 @@ class YourMT3:
         r = PianoRoll(self, n_programs, max_frames, frames_per_second, drum_program)
         self._constraints.add(r)
         return r
+
+    def compile_aligner(self, n_programs: int, max_frames: int, frames_per_second: float = 100.0, band_frames: int = 1000,
+                        drum_program: int = DRUM_PROGRAM) -> Aligner:
+        """The device alignment (include/ymt3.h, alignment) for records of `n_programs` programs: banded DTW of a reference onto an
+        estimate, each of up to `max_frames` frames, under a band of `band_frames`; the step bits take max_frames * (band_frames / 8 + 2)
+        * 4 bytes."""
+        a = Aligner(self, n_programs, max_frames, frames_per_second, band_frames, drum_program)
+        self._constraints.add(a)
+        return a
 
     def compile_ingest_stream(self, sample_rate: int, n_channels: int = 1, dtype=torch.int16, max_chunk_frames: int = 1 << 16) -> IngestStream:
         """Streaming form of ingest() (include/ymt3.h, streaming ingest) for `n_channels`-channel PCM of `dtype` (int16 or float32) at

@@ -13,7 +13,7 @@ import torch
 from .audio import load_wav_pcm
 from .midi import read_midi_notes, write_midi
 from .metrics import FrameMetricCounts, NoteMetricCounts, to_records
-from .task_manager import TaskManager, drop_low_confidence
+from .task_manager import DRUM_PROGRAM, NOTE_RECORD as NOTE_RECORD_DTYPE, Note, TaskManager, drop_low_confidence
 
 
 def transcribe(model, audio_info: Union[str, dict, np.ndarray], task_manager: Optional[TaskManager] = None, bsz: int = 8,
@@ -325,21 +325,10 @@ def score_notes(model, audio_info: Union[str, dict, np.ndarray], notes, task_man
     return {"log_likelihood": float(seg_ll.sum()), "segment_log_likelihood": seg_ll, "n_tokens": int(lengths.sum()), "tokens": tokens}
 
 
-def evaluate(model, audio_info: Union[str, dict, np.ndarray], reference, task_manager: Optional[TaskManager] = None, bsz: int = 8,
-             continuous: bool = False, subtask: Optional[str] = None, constrained: bool = False, programs=None, num_beams: int = 1,
-             length_penalty: float = 1.0, frames: bool = False, frames_per_second: float = 100.0, **tolerances) -> dict:
-    """How right is the transcription of this audio: note-level onset, onset+offset and drum F1 against `reference` (a list of Note, or the
-    path of a .mid file), by the rules of yourmt3_amd/metrics.py.  The audio is decoded as transcribe(device_detok=True) decodes it
-    (`continuous`, `subtask`, `constrained`, `programs`, `num_beams`, `length_penalty` as there); the ids become note records on the device
-    (Detokenizer.run_device) and are matched against the uploaded reference there (NoteMetrics.run, reading the number of transcribed notes
-    from the detokeniser's counter on the device): one copy back, of the counts.  `tolerances`: onset_tol, offset_min_tol, offset_ratio.
-    -> NoteMetricCounts.summary(): onset_f / offset_f (instrument-agnostic, with _p and _r), drum_onset_f, multi_f, per_program, skipped and
-    "counts" (the (n_programs + 1, 2, 3) integers).
-    `frames=True` adds frame-level F1 (PianoRoll.metrics; the rules: yourmt3_amd/metrics.py, frame metrics) over n_frames = max(1,
-    ceil(end_sec * frames_per_second)) frames, end_sec being the audio's length as the detokeniser gets it.  It runs on the same records
-    and counter on the device, after the note metrics, and the copy back is still one.  The summary gains frame_f, frame_p, frame_r,
-    frame_acc (instrument-agnostic), frame_err ({"sub", "miss", "fa", "total"}), multi_frame_f, frame_counts (the (n_programs + 1, 6)
-    integers) and n_frames."""
+def _decode_against(model, audio_info, reference, task_manager, bsz, continuous, subtask, constrained, programs, num_beams, length_penalty):
+    """What evaluate() and align() share: load the audio and the reference (a list of Note, a NOTE_RECORD array or the path of a .mid
+    file), and decode the audio as transcribe(device_detok=True) does, the ids staying on the device.
+    -> (task_manager, the audio's name, the reference as given or read, its records, n_programs, tokens, start_secs, L, end_sec)"""
     num_beams = int(num_beams)
     if num_beams < 1:
         raise ValueError(f"num_beams={num_beams} must be >= 1")
@@ -350,9 +339,12 @@ def evaluate(model, audio_info: Union[str, dict, np.ndarray], reference, task_ma
         task_manager = TaskManager("mc13_full_plus_256" if cfg.n_channels == 13 else "mt3_full_plus")
     if task_manager.num_decoding_channels != cfg.n_channels:
         raise ValueError("TaskManager channel count does not match the model's decoder")
+    name = "audio"
     if isinstance(audio_info, dict):
+        name = audio_info.get("track_name") or os.path.splitext(os.path.basename(audio_info["filepath"]))[0]
         x, sr = load_wav_pcm(audio_info["filepath"])
     elif isinstance(audio_info, str):
+        name = os.path.splitext(os.path.basename(audio_info))[0]
         x, sr = load_wav_pcm(audio_info)
     else:
         x, sr = np.asarray(audio_info, dtype=np.float32), cfg.sample_rate
@@ -385,21 +377,57 @@ def evaluate(model, audio_info: Union[str, dict, np.ndarray], reference, task_ma
     finally:
         if constraint is not None:
             constraint.close()
+    return task_manager, name, reference, ref, n_programs, tokens, start_secs, L, model.last_ingest_samples / cfg.sample_rate
+
+
+def evaluate(model, audio_info: Union[str, dict, np.ndarray], reference, task_manager: Optional[TaskManager] = None, bsz: int = 8,
+             continuous: bool = False, subtask: Optional[str] = None, constrained: bool = False, programs=None, num_beams: int = 1,
+             length_penalty: float = 1.0, frames: bool = False, frames_per_second: float = 100.0, align: bool = False, band_sec: float = 10.0,
+             **tolerances) -> dict:
+    """How right is the transcription of this audio: note-level onset, onset+offset and drum F1 against `reference` (a list of Note, or the
+    path of a .mid file), by the rules of yourmt3_amd/metrics.py.  The audio is decoded as transcribe(device_detok=True) decodes it
+    (`continuous`, `subtask`, `constrained`, `programs`, `num_beams`, `length_penalty` as there); the ids become note records on the device
+    (Detokenizer.run_device) and are matched against the uploaded reference there (NoteMetrics.run, reading the number of transcribed notes
+    from the detokeniser's counter on the device): one copy back, of the counts.  `tolerances`: onset_tol, offset_min_tol, offset_ratio.
+    -> NoteMetricCounts.summary(): onset_f / offset_f (instrument-agnostic, with _p and _r), drum_onset_f, multi_f, per_program, skipped and
+    "counts" (the (n_programs + 1, 2, 3) integers).
+    `frames=True` adds frame-level F1 (PianoRoll.metrics; the rules: yourmt3_amd/metrics.py, frame metrics) over n_frames = max(1,
+    ceil(end_sec * frames_per_second)) frames, end_sec being the audio's length as the detokeniser gets it.  It runs on the same records
+    and counter on the device, after the note metrics, and the copy back is still one.  The summary gains frame_f, frame_p, frame_r,
+    frame_acc (instrument-agnostic), frame_err ({"sub", "miss", "fa", "total"}), multi_frame_f, frame_counts (the (n_programs + 1, 6)
+    integers) and n_frames.
+    `align=True` first aligns the reference to the transcription (Aligner.align; the rules: yourmt3_amd/metrics.py, alignment: banded DTW
+    over frame-wise pitch sets at frames_per_second under a band of band_sec seconds) and warps the uploaded reference records onto the
+    audio's time axis on the device (Aligner.warp) before the metrics read them: for a reference that is a score, another performance
+    or carries a lead-in.  n_est_frames = max(1, ceil(end_sec * frames_per_second)), n_ref_frames the same of the largest finite time of
+    the reference.  The copy back is still one; the summary gains align_total and align_path_len."""
+    task_manager, _, _, ref, n_programs, tokens, start_secs, L, end_sec = _decode_against(
+        model, audio_info, reference, task_manager, bsz, continuous, subtask, constrained, programs, num_beams, length_penalty)
+    n = len(start_secs)
     detok = model.compile_detokenizer(task_manager, max(n, 1), L)
     metrics = model.compile_note_metrics(n_programs, max(len(ref), 1), detok.capacity, **tolerances)
-    end_sec = model.last_ingest_samples / cfg.sample_rate
-    roll = None
+    roll = aligner = None
     try:
         if frames:
             n_frames = max(1, math.ceil(end_sec * float(frames_per_second)))
             roll = model.compile_piano_roll(n_programs, n_frames, frames_per_second, metrics.drum_program)
+        if align:
+            n_ref_frames, n_est_frames, band = _align_frames(ref, end_sec, frames_per_second, band_sec)
+            aligner = model.compile_aligner(n_programs, max(n_ref_frames, n_est_frames), frames_per_second, band, metrics.drum_program)
         est, est_counts = detok.run_device(tokens, None, torch.tensor(start_secs, dtype=torch.float64), end_sec)
         ref_dev = torch.from_numpy(ref.view(np.uint8).reshape(-1).copy()).to(model.device)
+        if align:
+            warp, aligned = aligner.align(ref_dev, est, n_ref_frames, n_est_frames, est_count=est_counts)
+            ref_dev = aligner.warp(ref_dev, warp)
         counts = metrics.run(ref_dev, est, est_count=est_counts)
         if frames:                                                       # int32 and int64 counts leave in one copy
             counts = torch.cat([counts.to(torch.int64), roll.metrics(ref_dev, est, n_frames, est_count=est_counts)])
+        if align:
+            counts = torch.cat([counts.to(torch.int64), aligned[:2]])
         flat = counts.cpu().numpy()
     finally:
+        if aligner is not None:
+            aligner.close()
         if roll is not None:
             roll.close()
         metrics.close()
@@ -407,7 +435,61 @@ def evaluate(model, audio_info: Union[str, dict, np.ndarray], reference, task_ma
     n_note = (n_programs + 1) * 6 + 2
     out = NoteMetricCounts.from_flat(flat[:n_note], n_programs, metrics.drum_program).summary()
     if frames:
-        out.update(FrameMetricCounts.from_flat(flat[n_note:], n_programs, metrics.drum_program).summary(), n_frames=n_frames)
+        out.update(FrameMetricCounts.from_flat(flat[n_note:n_note + n_note], n_programs, metrics.drum_program).summary(), n_frames=n_frames)
+    if align:
+        out.update(align_total=int(flat[-2]), align_path_len=int(flat[-1]))
+    return out
+
+
+def _align_frames(ref: np.ndarray, end_sec: float, frames_per_second: float, band_sec: float):
+    """-> (n_ref_frames, n_est_frames, band_frames) of an alignment of the reference records `ref` to audio of end_sec seconds"""
+    fps = float(frames_per_second)
+    if not (np.isfinite(fps) and fps > 0):
+        raise ValueError(f"frames_per_second={frames_per_second} must be finite and > 0")
+    if not (np.isfinite(band_sec) and band_sec > 0):
+        raise ValueError(f"band_sec={band_sec} must be finite and > 0")
+    times = np.concatenate([ref["onset"], ref["offset"]])
+    times = times[np.isfinite(times)]
+    ref_end = max(float(times.max()), 0.0) if times.size else 0.0
+    return max(1, math.ceil(ref_end * fps)), max(1, math.ceil(float(end_sec) * fps)), max(1, math.ceil(float(band_sec) * fps))
+
+
+def align(model, audio_info: Union[str, dict, np.ndarray], reference, task_manager: Optional[TaskManager] = None, bsz: int = 8,
+          frames_per_second: float = 100.0, band_sec: float = 10.0, output_dir: Optional[str] = None, continuous: bool = False,
+          subtask: Optional[str] = None, constrained: bool = False, programs=None, num_beams: int = 1, length_penalty: float = 1.0,
+          drum_program: int = DRUM_PROGRAM) -> dict:
+    """Carry `reference` (a list of Note, or the path of a .mid file: a score, another performance, a file with a lead-in) onto the time
+    axis of this audio.  The audio is transcribed as evaluate() transcribes it, the records staying on the device; the reference is
+    aligned to them there by banded DTW over frame-wise pitch sets (Aligner.align; the rules: yourmt3_amd/metrics.py, alignment) with
+    n_est_frames = max(1, ceil(end_sec * frames_per_second)), n_ref_frames the same of the largest finite onset or offset of the reference
+    and a band of band_sec seconds, and warped along the path (Aligner.warp).  `drum_program` is evaluate()'s: the row of the drums.
+    -> {"notes": the reference on the audio's time axis (a list of Note), "total", "path_len", "n_ref_frames", "n_est_frames", "warp"
+    (the (n_ref_frames,) int32 array)}.  With `output_dir` the notes are also written to <name>.aligned.mid."""
+    task_manager, name, reference, ref, n_programs, tokens, start_secs, L, end_sec = _decode_against(
+        model, audio_info, reference, task_manager, bsz, continuous, subtask, constrained, programs, num_beams, length_penalty)
+    n = len(start_secs)
+    notes_in = reference if not isinstance(reference, np.ndarray) else None
+    n_ref_frames, n_est_frames, band = _align_frames(ref, end_sec, frames_per_second, band_sec)
+    detok = model.compile_detokenizer(task_manager, max(n, 1), L)
+    aligner = None
+    try:
+        aligner = model.compile_aligner(n_programs, max(n_ref_frames, n_est_frames), frames_per_second, band, drum_program)
+        est, est_counts = detok.run_device(tokens, None, torch.tensor(start_secs, dtype=torch.float64), end_sec)
+        ref_dev = torch.from_numpy(ref.view(np.uint8).reshape(-1).copy()).to(model.device)
+        warp, result = aligner.align(ref_dev, est, n_ref_frames, n_est_frames, est_count=est_counts)
+        warped = aligner.warp(ref_dev, warp).cpu().numpy().view(NOTE_RECORD_DTYPE)
+        warp, result = warp.cpu().numpy(), result.cpu().numpy()
+    finally:
+        if aligner is not None:
+            aligner.close()
+        detok.close()
+    notes = [Note(float(r["onset"]), float(r["offset"]), bool(r["is_drum"]), int(r["program"]), int(r["pitch"]),
+                  **({} if notes_in is None else {"velocity": notes_in[i].velocity})) for i, r in enumerate(warped)]
+    out = {"notes": notes, "total": int(result[0]), "path_len": int(result[1]), "n_ref_frames": n_ref_frames, "n_est_frames": n_est_frames,
+           "warp": warp}
+    if output_dir is not None:
+        os.makedirs(output_dir, exist_ok=True)
+        out["midi_path"] = write_midi(notes, os.path.join(output_dir, name + ".aligned.mid"))
     return out
 
 
