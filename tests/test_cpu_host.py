@@ -325,3 +325,55 @@ def test_header_is_plain_c(tmp_path):
     r = subprocess.run([gcc, "-std=c99", "-pedantic", "-Wall", "-Werror", "-fsyntax-only", "-I", os.path.join(root, "include"), str(src)],
                        capture_output=True, text=True)
     assert r.returncode == 0, r.stderr
+
+
+def test_closed_and_orphaned_objects_say_so_and_free_once():
+    """Every device object of a model shares one lifecycle (yourmt3_amd/model.py: _Owned).  Without a GPU: an object that was never given a
+    C pointer is closed, says so under its own name, says when its model is gone, and close() calls the class's destroy function once."""
+    from yourmt3_amd import model as M
+    classes = {M.DecodeConstraint: ("constraint", "constraint", "ymt3_constraint_destroy"),
+               M.Detokenizer: ("detokenizer", "detokenizer", "ymt3_detok_destroy"),
+               M.DetokState: ("detokenizer state", "state", "ymt3_detok_state_destroy"),
+               M.Tokenizer: ("tokenizer", "tokenizer", "ymt3_tok_destroy"),
+               M.NoteMetrics: ("note metrics object", "note metrics object", "ymt3_metrics_destroy"),
+               M.PianoRoll: ("piano roll object", "piano roll object", "ymt3_roll_destroy"),
+               M.Aligner: ("aligner object", "aligner object", "ymt3_aligner_destroy"),
+               M.IngestStream: ("ingest stream", "ingest stream", "ymt3_ingest_stream_destroy")}
+    assert set(classes) == {c for c in vars(M).values() if isinstance(c, type) and issubclass(c, M._Owned) and c is not M._Owned}
+
+    class Lib:
+        def __init__(self):
+            self.freed = []
+
+        def __getattr__(self, name):
+            if not name.startswith("ymt3_"):
+                raise AttributeError(name)
+            return lambda c: self.freed.append((name, c.value))
+
+    class Model:                                     # what _own asks of a model
+        def __init__(self):
+            self._lib = Lib()
+            self._owned = __import__("weakref").WeakSet()
+
+    for cls, (noun, gone, destroy) in classes.items():
+        obj = cls.__new__(cls)
+        obj.close()                                  # before _own: nothing to free
+        model = Model()
+        obj._own(model)
+        assert obj in model._owned
+        with pytest.raises(ValueError, match=f"^the {noun} has been closed$"):
+            obj.ptr
+        assert obj._live_model() is model
+        obj._c = ctypes.c_void_p(0x1000)
+        assert obj.ptr.value == 0x1000
+        with obj as same:                            # every class leaves a `with` block closed
+            assert same is obj
+        obj.close()
+        assert model._lib.freed == [(destroy, 0x1000)]
+        with pytest.raises(ValueError, match=f"^the {noun} has been closed$"):
+            obj.ptr
+        freed = model._lib.freed
+        del model
+        with pytest.raises(ValueError, match=f"^the {gone}'s model is gone$"):
+            obj._live_model()
+        assert freed == [(destroy, 0x1000)]

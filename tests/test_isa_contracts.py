@@ -148,3 +148,27 @@ def test_moe_chain_kernels_fit_one_workgroup_per_cu_without_scratch(tmp_path_fac
     # the dynamic LDS block is set by the launcher from these constants: stage 3's two 16-row strips per wave behind the reduction space
     src = open(os.path.join(ROOT, "yourmt3_amd", "csrc", "moe_chain.hip")).read()
     assert "static_assert(MOE_CHAIN_LDS_BF16 <= 160 * 1024 && MOE_CHAIN_LDS_FP8 <= 160 * 1024" in src
+
+
+def _f64_opcodes(asm: str, name: str) -> dict:
+    """the f64 instructions of a kernel, by opcode (encoding suffixes dropped), over the whole function: a kernel may end in several places"""
+    m = re.search(r"^(_Z\w*" + name + r"\w*):[^\n]*\n(.*?)\n\.Lfunc_end", asm, re.S | re.M)
+    assert m, f"kernel {name} not found in the assembly"
+    ops = {}
+    for line in m.group(2).splitlines():
+        op = line.split()[0] if line.split() else ""
+        if re.match(r"v_\w+_f64", op):
+            op = re.sub(r"_(e32|e64|dpp|sdwa)$", "", op)
+            ops[op] = ops.get(op, 0) + 1
+    return ops
+
+
+def test_the_two_rasterisers_share_one_frame_arithmetic(tmp_path_factory):
+    """roll_raster_kernel and align_raster_kernel take a record's frames from one helper (note_rule.h): the same f64 instructions in both, and
+    of the rule's own exactly two multiplies (onset and offset times frames_per_second) and two round-half-even, with no fused multiply-add
+    made of them."""
+    roll = _f64_opcodes(_asm(tmp_path_factory, "roll"), "roll_raster_kernel")
+    align = _f64_opcodes(_asm(tmp_path_factory, "align"), "align_raster_kernel")
+    assert roll == align, (roll, align)
+    for ops in (roll, align):
+        assert ops.get("v_mul_f64") == 2 and ops.get("v_rndne_f64") == 2, ops

@@ -4,7 +4,7 @@
 // contraction off: every output equals the host's.
 //
 // Features: feat[side][frame][2], two 16-byte words per frame (the instrument-agnostic pitch set, then the drum row's), each side packed at
-// its own frame count.  The rasteriser's arithmetic is roll_raster_kernel's (roll.hip), restated here.
+// its own frame count.  The rasteriser classifies a record and clips its frames by the rule roll.hip and metrics.hip use (note_rule.h).
 //
 // The dynamic programme runs on (r, c): c is the LONGER side (the lanes' axis), r the other; for n_ref_frames > n_est_frames that is the
 // transposed problem, and only the tie order between the two non-diagonal steps and the step codes (always those of the untransposed
@@ -28,6 +28,7 @@
 
 #include "common.h"
 #include "kernels.h"
+#include "note_rule.h"
 
 namespace {
 
@@ -76,39 +77,17 @@ __global__ __launch_bounds__(ALIGN_THREADS) void align_clear_kernel(AlignArgs a,
 __global__ __launch_bounds__(ALIGN_THREADS) void align_raster_kernel(AlignArgs a) {
     const int side = blockIdx.y, lane = threadIdx.x & (WAVE - 1);
     const long long i = (long long)blockIdx.x * (ALIGN_THREADS / WAVE) + (threadIdx.x >> 6);
-    const int32_t* cp = a.count[side];
-    long long n = a.n[side];
-    if (cp) {
-        const long long c = max(*cp, 0);
-        n = min(n, c);
-    }
-    if (i >= n) return;
+    if (i >= note_live_count(a.n[side], a.count[side])) return;
     const DetokNote r = a.notes[side][i];
-    const int prog = r.is_drum != 0 ? a.drum_program : r.program;
-    const bool drum = prog == a.drum_program;
-    const bool counted = r.onset == r.onset && r.pitch >= 0 && r.pitch < ROLL_PITCHES && prog >= 0 && prog < a.n_programs &&
-                         (drum || r.offset == r.offset);
-    if (!counted) {
+    const NoteClass c = note_classify(r, a.n_programs, a.drum_program);
+    if (!c.counted) {
         if (lane == 0) atomicAdd(reinterpret_cast<unsigned long long*>(&a.result[2 + side]), 1ull);
         return;
     }
-    const long long n_frames = a.n_frames[side];
-    double lo, hi;
-    {
-#pragma clang fp contract(off)
-        const double f0 = rint(r.onset * a.frames_per_second);
-        double f1 = f0 + 1.0;
-        if (!drum) {
-            const double fo = rint(r.offset * a.frames_per_second);
-            f1 = fo > f1 ? fo : f1;
-        }
-        lo = f0 > 0.0 ? f0 : 0.0;
-        hi = f1 < (double)n_frames ? f1 : (double)n_frames;
-    }
-    if (!(lo < hi)) return;
-    const long long f_lo = (long long)lo, f_hi = (long long)hi;         // 0 <= f_lo < f_hi <= n_frames
+    long long f_lo, f_hi;
+    if (!note_frame_span(r, c.drum, a.frames_per_second, a.n_frames[side], &f_lo, &f_hi)) return;
     const unsigned bit = 1u << (r.pitch & 31);
-    unsigned* w = reinterpret_cast<unsigned*>(a.feat + (long long)side * a.max_frames * 2) + (drum ? 4 : 0) + (r.pitch >> 5);
+    unsigned* w = reinterpret_cast<unsigned*>(a.feat + (long long)side * a.max_frames * 2) + (c.drum ? 4 : 0) + (r.pitch >> 5);
     for (long long f = f_lo + lane; f < f_hi; f += WAVE) atomicOr(&w[f * 8], bit);
 }
 
@@ -255,12 +234,7 @@ __device__ __forceinline__ double warp_time(double t, const int32_t* warp, doubl
 
 __global__ __launch_bounds__(ALIGN_THREADS) void warp_notes_kernel(WarpNotesArgs a) {
     const long long i = (long long)blockIdx.x * ALIGN_THREADS + threadIdx.x;
-    long long n = a.n;
-    if (a.count) {
-        const long long c = max(*a.count, 0);
-        n = min(n, c);
-    }
-    if (i >= n) return;
+    if (i >= note_live_count(a.n, a.count)) return;
     DetokNote r = a.notes[i];
     const double q = (double)(a.n_ref_frames - 1);
     r.onset = warp_time(r.onset, a.warp, q, a.frames_per_second);

@@ -1,4 +1,4 @@
-// Launcher declarations shared between the kernel translation units and runtime.hip.
+// Launcher declarations shared between the kernel translation units and the host code (runtime.hip, note_objects.hip).
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -47,6 +47,7 @@ constexpr int DETOK_PITCHES = 128;        // pitch / drum values per program: a 
 constexpr int DETOK_MAX_PROGRAMS = 256;   // 256 * 128 32-bit counters = 128 KB of the 160 KB of LDS
 constexpr int DETOK_MAX_STEPS = 32768;    // an item's column has 15 bits, its step 27 (32768 * 4095 < 2^27), its segment 20
 constexpr int DETOK_MAX_SEGMENTS = 1 << 20;
+constexpr int NOTE_PITCHES = 128;         // the pitch range of a counted record (note_rule.h)
 struct DetokNote {                        // the 32-byte record of include/ymt3.h
     double onset, offset;
     int32_t program, pitch, is_drum;
@@ -112,7 +113,7 @@ struct TokArgs {
 int launch_tok(const TokArgs& a, hipStream_t stream);
 
 // ---------------------------------------------------------------- device note metrics (metrics.hip; include/ymt3.h, note metrics)
-constexpr int METRICS_PITCHES = 128;               // a key is row * 128 + pitch; row n_programs holds the instrument-agnostic keys
+constexpr int METRICS_PITCHES = NOTE_PITCHES;      // a key is row * 128 + pitch; row n_programs holds the instrument-agnostic keys
 constexpr int METRICS_MAX_PROGRAMS = 256;
 constexpr long long METRICS_MAX_NOTES = 1LL << 24; // per side; a counted note fills at most two bucket slots
 struct MetricsArgs {
@@ -138,7 +139,7 @@ struct MetricsArgs {
 int launch_metrics(const MetricsArgs& a, hipStream_t stream);
 
 // ---------------------------------------------------------------- device piano roll and frame metrics (roll.hip; include/ymt3.h, piano roll)
-constexpr int ROLL_PITCHES = 128;                  // one 16-byte word of pitch bits per (side, row, frame)
+constexpr int ROLL_PITCHES = NOTE_PITCHES;         // one 16-byte word of pitch bits per (side, row, frame)
 constexpr int ROLL_MAX_PROGRAMS = 256;
 constexpr long long ROLL_MAX_FRAMES = 1LL << 24;
 constexpr long long ROLL_MAX_NOTES = 1LL << 29;    // per side

@@ -5,7 +5,7 @@
 //
 // A counted record enters the bucket of its instrument-aware key, program * 128 + pitch, and, if pitched, of its agnostic key,
 // n_programs * 128 + pitch: (n_programs + 1) * 128 keys per side, most of them empty.
-// (a) metrics_notes_kernel<false>, one lane per record and side: validity, the two keys, a per-key histogram; skipped records are counted.
+// (a) metrics_notes_kernel<false>, one lane per record and side: validity (note_rule.h), the two keys, a per-key histogram; skipped records are counted.
 // (b) metrics_scan_kernel, one workgroup per side: exclusive scan of the histogram into bucket offsets, and n_ref / n_est of every row
 //     (the sum of the row's 128 counters) stored into the result.
 // (c) metrics_notes_kernel<true>: the same lanes scatter their (onset, offset) into the buckets through a per-key cursor.
@@ -22,6 +22,7 @@
 // Worst case: the searches are cubic in the notes of ONE key that lie within one onset window of each other; the sort is n log^2 n.
 #include "common.h"
 #include "kernels.h"
+#include "note_rule.h"
 
 namespace {
 
@@ -52,35 +53,26 @@ template <bool SCATTER>
 __global__ __launch_bounds__(NOTE_THREADS) void metrics_notes_kernel(MetricsArgs a) {
     const int side = blockIdx.y;
     const long long i = (long long)blockIdx.x * NOTE_THREADS + threadIdx.x;
-    const int32_t* cp = side ? a.est_count : a.ref_count;
-    long long n = side ? a.n_est : a.n_ref;
-    if (cp) {
-        const long long c = max(*cp, 0);
-        n = min(n, c);
-    }
-    if (i >= n) return;
+    if (i >= note_live_count(side ? a.n_est : a.n_ref, side ? a.est_count : a.ref_count)) return;
     const DetokNote r = (side ? a.est : a.ref)[i];
-    const int prog = r.is_drum != 0 ? a.drum_program : r.program;
-    const bool drum = prog == a.drum_program;
-    const bool counted = r.onset == r.onset && r.pitch >= 0 && r.pitch < METRICS_PITCHES && prog >= 0 && prog < a.n_programs &&
-                         (drum || r.offset == r.offset);
-    if (!counted) {
+    const NoteClass c = note_classify(r, a.n_programs, a.drum_program);
+    if (!c.counted) {
         if (!SCATTER) atomicAdd(&a.counts[(a.n_programs + 1) * 6 + side], 1);
         return;
     }
     const int NK = n_keys(a);
-    const int aware = prog * METRICS_PITCHES + r.pitch, agnostic = a.n_programs * METRICS_PITCHES + r.pitch;
+    const int aware = c.prog * METRICS_PITCHES + r.pitch, agnostic = a.n_programs * METRICS_PITCHES + r.pitch;
     if (!SCATTER) {
         unsigned* h = a.hist + (long long)side * NK;
         atomicAdd(&h[aware], 1u);
-        if (!drum) atomicAdd(&h[agnostic], 1u);
+        if (!c.drum) atomicAdd(&h[agnostic], 1u);
     } else {
         unsigned* cur = a.cursor + (long long)side * NK;
         double2* T = side ? a.t_est : a.t_ref;
         const long long cap = 2 * (side ? a.max_est : a.max_ref);
         const unsigned p0 = atomicAdd(&cur[aware], 1u);
         if (p0 < cap) T[p0] = make_double2(r.onset, r.offset);
-        if (!drum) {
+        if (!c.drum) {
             const unsigned p1 = atomicAdd(&cur[agnostic], 1u);
             if (p1 < cap) T[p1] = make_double2(r.onset, r.offset);
         }

@@ -1,0 +1,517 @@
+// The note-side objects of the C ABI (include/ymt3.h): detokeniser and its incremental state, tokeniser, note metrics, piano roll / frame
+// metrics, aligner.  Host logic only: argument checks, scratch, and the launches of detok.hip, tok.hip, metrics.hip, roll.hip and align.hip.
+// Of the handle they need the device and the configuration (runtime.h).  What the six have in common is written once, at the top: the
+// create prologue, the owner check, the program and record-array checks, and the scratch list that both *_create and *_destroy walk.
+#include <algorithm>
+#include <cmath>
+#include <vector>
+
+#include "kernels.h"
+#include "runtime.h"
+
+// ---------------------------------------------------------------- shared checks
+// name: the argument every create but the state's needs besides the handle (NULL: none)
+static int create_prologue(void** out, ymt3_handle h, const void* arg, const char* name) {
+    if (!out) FAIL(YMT3_ERR_ARG, "null output pointer");
+    *out = nullptr;
+    if (!h) FAIL(YMT3_ERR_ARG, "null handle");
+    if (name && !arg) FAIL(YMT3_ERR_ARG, "%s is NULL", name);
+    return YMT3_OK;
+}
+
+template <class T> static int check_owner(ymt3_handle h, const T* o, const char* noun) {
+    if (!h) FAIL(YMT3_ERR_ARG, "null handle");
+    if (!o) FAIL(YMT3_ERR_ARG, "null %s", noun);
+    if (o->owner != h) FAIL(YMT3_ERR_ARG, "the %s belongs to another handle", noun);
+    return YMT3_OK;
+}
+
+// why: what the object's limit comes from, ending in ", " (or empty)
+static int check_programs(int n_programs, int drum_program, int max_programs, const char* why) {
+    if (n_programs < 1) FAIL(YMT3_ERR_ARG, "n_programs=%d must be >= 1", n_programs);
+    if (n_programs > max_programs) FAIL(YMT3_ERR_UNSUPPORTED, "n_programs=%d: %sat most %d programs", n_programs, why, max_programs);
+    if (drum_program < 0 || drum_program >= n_programs) FAIL(YMT3_ERR_ARG, "drum_program=%d outside [0, n_programs=%d)", drum_program, n_programs);
+    return YMT3_OK;
+}
+
+// A record array of a call: its count is in [0, max] (max_name: the object's limit of that name, or NULL for a constant of the kernels) ...
+static int check_count(const char* n_name, long long n, long long max, const char* max_name) {
+    if (n < 0 || n > max) FAIL(YMT3_ERR_ARG, "%s=%lld outside [0, %s%s%lld]", n_name, n, max_name ? max_name : "", max_name ? "=" : "", max);
+    return YMT3_OK;
+}
+// ... and where it has records (always: without them too) its pointer is there and aligned for the records' doubles
+static int check_record_ptr(const char* ptr_name, const void* p, long long n, bool always = false) {
+    if (n && !p) FAIL(YMT3_ERR_ARG, "%s is NULL", ptr_name);
+    if ((n || always) && reinterpret_cast<uintptr_t>(p) % 8) FAIL(YMT3_ERR_ARG, "%s is not aligned to 8 bytes", ptr_name);
+    return YMT3_OK;
+}
+
+// ---------------------------------------------------------------- scratch
+// One device allocation of an object (src: host data to upload, or NULL; zero: zero-filled at create).  Every object type has a slots() that
+// lists its allocations: *_create allocates and fills them in that order, *_destroy frees them.
+struct Slot { void** p; size_t bytes; const void* src; bool zero; };
+template <class T> static Slot slot(T** p, size_t bytes, const void* src = nullptr, bool zero = false) { return Slot{reinterpret_cast<void**>(p), bytes, src, zero}; }
+
+template <class T> static void destroy_object(T* o) {
+    if (!o) return;
+    (void)hipSetDevice(o->device);
+    for (const Slot& s : slots(o))
+        if (*s.p) (void)hipFree(*s.p);
+    delete o;
+}
+
+// the tail of every create: on failure nothing is leaked, no object is returned and HIP's sticky error is cleared (unnamed: bytes of the
+// list that the message's total leaves out)
+template <class T> static int allocate_object(T* o, const std::vector<Slot>& list, const char* what, T** out, size_t unnamed = 0) {
+    size_t total = 0;
+    bool ok = true;
+    for (const Slot& s : list) {
+        total += s.bytes;
+        ok = ok && hipMalloc(s.p, s.bytes) == hipSuccess && (!s.src || hipMemcpy(*s.p, s.src, s.bytes, hipMemcpyHostToDevice) == hipSuccess) &&
+             (!s.zero || hipMemset(*s.p, 0, s.bytes) == hipSuccess);
+    }
+    if (ok) { *out = o; return YMT3_OK; }
+    (void)hipGetLastError();
+    destroy_object(o);
+    FAIL(YMT3_ERR_HIP, "%s (%zu bytes) could not be allocated", what, total - unnamed);
+}
+
+// ---------------------------------------------------------------- device detokeniser (include/ymt3.h)
+struct ymt3_detok_s {
+    ymt3_handle owner;
+    int device, n_chan, vocab, steps_per_second, drum_program, n_programs, max_segments, max_steps;
+    uint16_t* table = nullptr;              // [vocab]
+    unsigned long long* items = nullptr;    // [n_channels * max_segments * max_steps]
+    unsigned long long* sorted = nullptr;   // the same
+    uint16_t* keys = nullptr;               // the same
+    int* row_count = nullptr;               // [n_channels * max_segments]
+    unsigned* key_off = nullptr;            // [n_channels][n_programs * 128]
+};
+
+static std::vector<Slot> slots(ymt3_detok d, const uint16_t* table_host = nullptr) {
+    const size_t rows = (size_t)d->max_segments * d->n_chan, n = rows * d->max_steps;
+    return {slot(&d->table, (size_t)d->vocab * 2, table_host), slot(&d->items, n * 8), slot(&d->sorted, n * 8), slot(&d->keys, n * 2),
+            slot(&d->row_count, rows * sizeof(int)), slot(&d->key_off, (size_t)d->n_chan * d->n_programs * DETOK_PITCHES * sizeof(unsigned))};
+}
+extern "C" void ymt3_detok_destroy(ymt3_detok d) { destroy_object(d); }
+
+extern "C" int ymt3_detok_create(ymt3_handle h, const uint16_t* token_table_host, int vocab, int steps_per_second, int drum_program,
+                                 int max_segments, int max_steps, ymt3_detok* out) {
+    if (const int rc = create_prologue(reinterpret_cast<void**>(out), h, token_table_host, "token_table_host")) return rc;
+    const ymt3_config& cfg = handle_config(h);
+    if (vocab != cfg.vocab) FAIL(YMT3_ERR_ARG, "detokeniser vocab=%d != the model's vocab=%d", vocab, cfg.vocab);
+    if (steps_per_second < 1) FAIL(YMT3_ERR_ARG, "steps_per_second=%d must be >= 1", steps_per_second);
+    if (drum_program < 0 || drum_program > 4095) FAIL(YMT3_ERR_ARG, "drum_program=%d outside [0, 4095]", drum_program);
+    if (max_segments < 1 || max_segments > DETOK_MAX_SEGMENTS) FAIL(YMT3_ERR_ARG, "max_segments=%d outside [1, %d]", max_segments, DETOK_MAX_SEGMENTS);
+    if (max_steps < 1 || max_steps > cfg.max_decode_len || max_steps > DETOK_MAX_STEPS)
+        FAIL(YMT3_ERR_ARG, "max_steps=%d outside [1, max_decode_len=%d]", max_steps, std::min(cfg.max_decode_len, DETOK_MAX_STEPS));
+    int n_programs = drum_program + 1;
+    for (int i = 0; i < vocab; ++i) {
+        const int cls = token_table_host[i] >> 12, v = token_table_host[i] & 0xfff;
+        if (cls > 8) FAIL(YMT3_ERR_ARG, "token_table_host[%d] has class %d (0..8 are defined)", i, cls);
+        if ((cls == 4 || cls == 8) && v >= DETOK_PITCHES) FAIL(YMT3_ERR_ARG, "token_table_host[%d]: pitch %d outside [0, %d)", i, v, DETOK_PITCHES);
+        if (cls == 5 && v > 1) FAIL(YMT3_ERR_ARG, "token_table_host[%d]: velocity %d is neither 0 (offsets) nor 1 (onsets)", i, v);
+        if (cls == 7) n_programs = std::max(n_programs, v + 1);
+    }
+    if (n_programs > DETOK_MAX_PROGRAMS)
+        FAIL(YMT3_ERR_UNSUPPORTED, "programs up to %d: the merge keeps one LDS counter per (program, pitch), at most %d programs", n_programs - 1, DETOK_MAX_PROGRAMS);
+    HIP_TRY(hipSetDevice(handle_device(h)));
+    if (init_detok_kernels()) FAIL(YMT3_ERR_HIP, "hipFuncSetAttribute(max dynamic LDS) failed");
+    ymt3_detok d = new ymt3_detok_s{h, handle_device(h), cfg.n_channels, vocab, steps_per_second, drum_program, n_programs, max_segments, max_steps};
+    return allocate_object(d, slots(d, token_table_host), "detokeniser scratch", out, (size_t)vocab * 2);     // (the message never counted the table)
+}
+
+// what ymt3_detokenize and the incremental calls tell the kernels about the tokens and the output
+static DetokArgs detok_args(ymt3_detok d, const int32_t* tokens_dev, const float* scores_dev, int n_segments, int L, long long seg_stride, long long chan_stride,
+                            const double* start_sec_dev, double end_sec, void* notes_dev, long long capacity, int32_t* counts_dev) {
+    DetokArgs a{};
+    a.table = d->table; a.vocab = d->vocab; a.steps_per_second = d->steps_per_second; a.drum_program = d->drum_program; a.n_programs = d->n_programs;
+    a.tokens = tokens_dev; a.scores = scores_dev; a.seg_stride = seg_stride; a.chan_stride = chan_stride;
+    a.n_seg = n_segments; a.n_chan = d->n_chan; a.L = L;
+    a.start = start_sec_dev; a.end_sec = end_sec;
+    a.items = d->items; a.keys = d->keys; a.row_count = d->row_count; a.sorted = d->sorted; a.key_off = d->key_off;
+    a.notes = static_cast<DetokNote*>(notes_dev); a.capacity = capacity; a.counts = counts_dev;
+    return a;
+}
+
+extern "C" int ymt3_detokenize(ymt3_handle h, ymt3_detok d, const int32_t* tokens_dev, const float* scores_dev, int n_segments, int n_steps,
+                               long long seg_stride, long long chan_stride, const double* start_sec_dev, double end_sec, void* notes_dev,
+                               long long capacity, int32_t* counts_dev, void* stream) {
+    if (const int rc = check_owner(h, d, "detokeniser")) return rc;
+    if (n_segments < 0 || n_segments > d->max_segments) FAIL(YMT3_ERR_ARG, "n_segments=%d outside [0, max_segments=%d]", n_segments, d->max_segments);
+    if (n_steps < 1 || n_steps > d->max_steps) FAIL(YMT3_ERR_ARG, "n_steps=%d outside [1, max_steps=%d]", n_steps, d->max_steps);
+    if (!counts_dev) FAIL(YMT3_ERR_ARG, "counts_dev is NULL");
+    if (n_segments && !tokens_dev) FAIL(YMT3_ERR_ARG, "tokens_dev is NULL");
+    if (n_segments && !start_sec_dev) FAIL(YMT3_ERR_ARG, "start_sec_dev is NULL");
+    if (n_segments && !notes_dev) FAIL(YMT3_ERR_ARG, "notes_dev is NULL");
+    const long long bound = (long long)n_segments * d->n_chan * n_steps;
+    if (capacity < bound) FAIL(YMT3_ERR_ARG, "capacity=%lld below n_segments * n_channels * n_steps = %lld records", capacity, bound);
+    HIP_TRY(hipSetDevice(d->device));
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    HIP_TRY(hipMemsetAsync(counts_dev, 0, 2 * sizeof(int32_t), s));
+    if (!n_segments) return YMT3_OK;
+    const DetokArgs a = detok_args(d, tokens_dev, scores_dev, n_segments, n_steps, seg_stride, chan_stride, start_sec_dev, end_sec, notes_dev, capacity, counts_dev);
+    LAUNCH(launch_detok(a, s));
+    return YMT3_OK;
+}
+
+// ---------------------------------------------------------------- incremental detokeniser (include/ymt3.h)
+struct ymt3_detok_state_s {
+    ymt3_handle owner;
+    ymt3_detok detok;                       // the detokeniser it was created for (compared by address only)
+    int device, n_chan, n_programs, max_held;
+    DetokSounding* sounding = nullptr;      // [n_chan][n_programs * 128]
+    DetokHeld* held[2] = {nullptr, nullptr};   // [n_chan][128][max_held], read from [cur], written to [cur ^ 1]
+    int* held_count[2] = {nullptr, nullptr};   // [n_chan][128]
+    int cur = 0;
+    double horizon = -INFINITY;             // of the last push
+    bool finished = false;
+};
+
+static size_t detok_state_sounding_bytes(const ymt3_detok_state_s* st) { return (size_t)st->n_chan * st->n_programs * DETOK_PITCHES * sizeof(DetokSounding); }
+static size_t detok_state_count_bytes(const ymt3_detok_state_s* st) { return (size_t)st->n_chan * DETOK_PITCHES * sizeof(int); }
+static std::vector<Slot> slots(ymt3_detok_state st) {
+    const size_t hb = (size_t)st->n_chan * DETOK_PITCHES * st->max_held * sizeof(DetokHeld), cb = detok_state_count_bytes(st);
+    return {slot(&st->sounding, detok_state_sounding_bytes(st), nullptr, true), slot(&st->held[0], hb), slot(&st->held[1], hb),
+            slot(&st->held_count[0], cb, nullptr, true), slot(&st->held_count[1], cb, nullptr, true)};
+}
+extern "C" void ymt3_detok_state_destroy(ymt3_detok_state st) { destroy_object(st); }
+
+extern "C" long long ymt3_detok_state_carry(ymt3_detok_state st) {
+    return st ? (long long)st->n_chan * DETOK_PITCHES * ((long long)st->n_programs - 1 + st->max_held) : 0;
+}
+
+extern "C" int ymt3_detok_state_create(ymt3_handle h, ymt3_detok d, int max_held, ymt3_detok_state* out) {
+    if (const int rc = create_prologue(reinterpret_cast<void**>(out), h, nullptr, nullptr)) return rc;
+    if (const int rc = check_owner(h, d, "detokeniser")) return rc;
+    if (max_held < 1 || max_held > 4096) FAIL(YMT3_ERR_ARG, "max_held=%d outside [1, 4096]", max_held);
+    HIP_TRY(hipSetDevice(d->device));
+    ymt3_detok_state st = new ymt3_detok_state_s{h, d, d->device, d->n_chan, d->n_programs, max_held};
+    return allocate_object(st, slots(st), "detokeniser state", out);
+}
+
+extern "C" int ymt3_detok_state_reset(ymt3_handle h, ymt3_detok_state st, void* stream) {
+    if (const int rc = check_owner(h, st, "detokeniser state")) return rc;
+    HIP_TRY(hipSetDevice(st->device));
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    HIP_TRY(hipMemsetAsync(st->sounding, 0, detok_state_sounding_bytes(st), s));
+    HIP_TRY(hipMemsetAsync(st->held_count[st->cur], 0, detok_state_count_bytes(st), s));
+    st->horizon = -INFINITY;
+    st->finished = false;
+    return YMT3_OK;
+}
+
+// the shared tail of push and finish: n_segments = 0 walks the state alone
+static int detok_carry(ymt3_handle h, ymt3_detok d, ymt3_detok_state st, const int32_t* tokens_dev, const float* scores_dev, int n_segments,
+                       int n_steps, long long seg_stride, long long chan_stride, const double* start_sec_dev, double horizon, double end_sec,
+                       int finish, void* notes_dev, long long capacity, int32_t* counts_dev, void* stream) {
+    if (h && d && !st) FAIL(YMT3_ERR_ARG, "null detokeniser state");
+    if (const int rc = check_owner(h, d, "detokeniser")) return rc;
+    if (st->owner != h || st->detok != d) FAIL(YMT3_ERR_ARG, "the detokeniser state was created for another detokeniser");
+    if (st->finished) FAIL(YMT3_ERR_ARG, "the state has been finished: reset it first");
+    if (n_segments < 0 || n_segments > d->max_segments) FAIL(YMT3_ERR_ARG, "n_segments=%d outside [0, max_segments=%d]", n_segments, d->max_segments);
+    if (n_segments && (n_steps < 1 || n_steps > d->max_steps)) FAIL(YMT3_ERR_ARG, "n_steps=%d outside [1, max_steps=%d]", n_steps, d->max_steps);
+    if (!counts_dev) FAIL(YMT3_ERR_ARG, "counts_dev is NULL");
+    if (!notes_dev) FAIL(YMT3_ERR_ARG, "notes_dev is NULL");
+    if (n_segments && !tokens_dev) FAIL(YMT3_ERR_ARG, "tokens_dev is NULL");
+    if (n_segments && !start_sec_dev) FAIL(YMT3_ERR_ARG, "start_sec_dev is NULL");
+    if (!finish && !(horizon >= st->horizon && horizon > -INFINITY))
+        FAIL(YMT3_ERR_ARG, "horizon_sec=%g is -inf, NaN or below the previous push's horizon %g", horizon, st->horizon);
+    const long long bound = (long long)n_segments * d->n_chan * (n_segments ? n_steps : 0) + ymt3_detok_state_carry(st);
+    if (capacity < bound)
+        FAIL(YMT3_ERR_ARG, "capacity=%lld below n_segments * n_channels * n_steps + ymt3_detok_state_carry = %lld records", capacity, bound);
+    HIP_TRY(hipSetDevice(d->device));
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    HIP_TRY(hipMemsetAsync(counts_dev, 0, 3 * sizeof(int32_t), s));
+    const DetokArgs a = detok_args(d, tokens_dev, scores_dev, n_segments, n_segments ? n_steps : 1, seg_stride, chan_stride, start_sec_dev, end_sec,
+                                   notes_dev, capacity, counts_dev);
+    DetokCarryArgs c{};
+    c.sounding = st->sounding; c.held_in = st->held[st->cur]; c.held_out = st->held[st->cur ^ 1];
+    c.held_count_in = st->held_count[st->cur]; c.held_count_out = st->held_count[st->cur ^ 1];
+    c.max_held = st->max_held; c.finish = finish; c.horizon = horizon;
+    LAUNCH(launch_detok_carry(a, c, s));
+    HIP_TRY(hipGetLastError());
+    st->cur ^= 1;
+    if (finish) st->finished = true;
+    else st->horizon = horizon;
+    return YMT3_OK;
+}
+
+extern "C" int ymt3_detokenize_push(ymt3_handle h, ymt3_detok d, ymt3_detok_state st, const int32_t* tokens_dev, const float* scores_dev,
+                                    int n_segments, int n_steps, long long seg_stride, long long chan_stride, const double* start_sec_dev,
+                                    double horizon_sec, void* notes_dev, long long capacity, int32_t* counts_dev, void* stream) {
+    return detok_carry(h, d, st, tokens_dev, scores_dev, n_segments, n_steps, seg_stride, chan_stride, start_sec_dev, horizon_sec, 0.0, 0,
+                       notes_dev, capacity, counts_dev, stream);
+}
+
+extern "C" int ymt3_detokenize_finish(ymt3_handle h, ymt3_detok d, ymt3_detok_state st, double end_sec, void* notes_dev, long long capacity,
+                                      int32_t* counts_dev, void* stream) {
+    return detok_carry(h, d, st, nullptr, nullptr, 0, 0, 0, 0, nullptr, INFINITY, end_sec, 1, notes_dev, capacity, counts_dev, stream);
+}
+
+// ---------------------------------------------------------------- device tokeniser (include/ymt3.h)
+struct ymt3_tok_s {
+    ymt3_handle owner;
+    int device, n_chan;
+    ymt3_tok_params p;
+    int n_programs, max_segments, max_steps;
+    uint8_t* program_channel = nullptr;     // [n_programs]
+    unsigned long long* items = nullptr;    // [max_segments * n_channels * max_steps]
+    int* row_count = nullptr;               // [max_segments * n_channels]
+    unsigned* tie_seen = nullptr;           // [max_segments][n_programs * 4]
+};
+
+static std::vector<Slot> slots(ymt3_tok t, const uint8_t* program_channel_host = nullptr) {
+    const size_t rows = (size_t)t->max_segments * t->n_chan;
+    return {slot(&t->program_channel, (size_t)t->n_programs, program_channel_host), slot(&t->items, rows * t->max_steps * 8),
+            slot(&t->row_count, rows * sizeof(int)), slot(&t->tie_seen, (size_t)t->max_segments * t->n_programs * (TOK_PITCHES / 8))};
+}
+extern "C" void ymt3_tok_destroy(ymt3_tok t) { destroy_object(t); }
+
+extern "C" int ymt3_tok_create(ymt3_handle h, const ymt3_tok_params* params, const uint8_t* program_channel_host, int n_programs, int max_segments,
+                               int max_steps, ymt3_tok* out) {
+    if (const int rc = create_prologue(reinterpret_cast<void**>(out), h, params, "params")) return rc;
+    if (!program_channel_host) FAIL(YMT3_ERR_ARG, "program_channel_host is NULL");
+    const ymt3_tok_params& p = *params;
+    const ymt3_config& cfg = handle_config(h);
+    if (const int rc = check_programs(n_programs, 0, TOK_MAX_PROGRAMS, "an item gives the program 8 bits, ")) return rc;     // n_programs only (0 is always a valid drum)
+    if (p.steps_per_second < 1) FAIL(YMT3_ERR_ARG, "steps_per_second=%d must be >= 1", p.steps_per_second);
+    if (p.max_shift_steps < 1) FAIL(YMT3_ERR_ARG, "max_shift_steps=%d must be >= 1", p.max_shift_steps);
+    if (const int rc = check_programs(n_programs, p.drum_program, TOK_MAX_PROGRAMS, "")) return rc;     // n_programs passed above: this tests drum_program, where it always was
+    const struct { const char* name; int base, size; } ranges[] = {
+        {"shift_base", p.shift_base, p.max_shift_steps}, {"pitch_base", p.pitch_base, TOK_PITCHES}, {"velocity_base", p.velocity_base, 2},
+        {"tie_base", p.tie_base, 1}, {"program_base", p.program_base, n_programs}, {"drum_base", p.drum_base, TOK_PITCHES},
+        {"eos_id", p.eos_id, 1}, {"pad_id", p.pad_id, 1}};
+    for (const auto& r : ranges)
+        if (r.base < 0 || (long long)r.base + r.size > cfg.vocab) FAIL(YMT3_ERR_ARG, "%s=%d: its %d ids do not fit the model's vocab=%d", r.name, r.base, r.size, cfg.vocab);
+    for (int i = 0; i < n_programs; ++i)
+        if (program_channel_host[i] >= cfg.n_channels) FAIL(YMT3_ERR_ARG, "program_channel_host[%d]=%d outside [0, n_channels=%d)", i, (int)program_channel_host[i], cfg.n_channels);
+    if (max_segments < 1 || max_segments > TOK_MAX_SEGMENTS) FAIL(YMT3_ERR_ARG, "max_segments=%d outside [1, %d]", max_segments, TOK_MAX_SEGMENTS);
+    if (max_steps < 1 || max_steps > cfg.max_decode_len || max_steps > TOK_MAX_STEPS)
+        FAIL(YMT3_ERR_ARG, "max_steps=%d outside [1, max_decode_len=%d]", max_steps, std::min(cfg.max_decode_len, TOK_MAX_STEPS));
+    HIP_TRY(hipSetDevice(handle_device(h)));
+    ymt3_tok t = new ymt3_tok_s{h, handle_device(h), cfg.n_channels, p, n_programs, max_segments, max_steps};
+    return allocate_object(t, slots(t, program_channel_host), "tokeniser scratch", out);
+}
+
+extern "C" int ymt3_tokenize(ymt3_handle h, ymt3_tok t, const void* notes_dev, long long n_notes, const double* start_sec_dev, int n_segments,
+                             double end_sec, int n_steps, int32_t* tokens_dev, int32_t* lengths_dev, void* stream) {
+    if (const int rc = check_owner(h, t, "tokeniser")) return rc;
+    if (n_segments < 0 || n_segments > t->max_segments) FAIL(YMT3_ERR_ARG, "n_segments=%d outside [0, max_segments=%d]", n_segments, t->max_segments);
+    if (n_steps < 1 || n_steps > t->max_steps) FAIL(YMT3_ERR_ARG, "n_steps=%d outside [1, max_steps=%d]", n_steps, t->max_steps);
+    if (const int rc = check_count("n_notes", n_notes, TOK_MAX_NOTES, nullptr)) return rc;
+    if (!n_segments) return YMT3_OK;
+    if (const int rc = check_record_ptr("notes_dev", notes_dev, n_notes, true)) return rc;
+    if (!start_sec_dev) FAIL(YMT3_ERR_ARG, "start_sec_dev is NULL");
+    if (!tokens_dev) FAIL(YMT3_ERR_ARG, "tokens_dev is NULL");
+    if (!lengths_dev) FAIL(YMT3_ERR_ARG, "lengths_dev is NULL");
+    HIP_TRY(hipSetDevice(t->device));
+    const ymt3_tok_params& p = t->p;
+    TokArgs a{};
+    a.shift_base = p.shift_base; a.pitch_base = p.pitch_base; a.velocity_base = p.velocity_base; a.tie_base = p.tie_base;
+    a.program_base = p.program_base; a.drum_base = p.drum_base; a.max_shift_steps = p.max_shift_steps; a.steps_per_second = p.steps_per_second;
+    a.drum_program = p.drum_program; a.eos_id = p.eos_id; a.pad_id = p.pad_id;
+    a.notes = static_cast<const DetokNote*>(notes_dev); a.n_notes = n_notes;
+    a.start = start_sec_dev; a.end_sec = end_sec; a.n_seg = n_segments; a.n_chan = t->n_chan; a.L = n_steps;
+    a.items = t->items; a.row_count = t->row_count; a.tie_seen = t->tie_seen;
+    a.n_programs = t->n_programs; a.program_channel = t->program_channel; a.tokens = tokens_dev; a.lengths = lengths_dev;
+    LAUNCH(launch_tok(a, static_cast<hipStream_t>(stream)));
+    return YMT3_OK;
+}
+
+// ---------------------------------------------------------------- device note metrics (include/ymt3.h)
+struct ymt3_metrics_s {
+    ymt3_handle owner;
+    int device;
+    ymt3_metrics_params p;
+    long long max_ref, max_est;
+    unsigned* hist = nullptr;               // [2][n_keys], then off [2][n_keys + 1] and cursor [2][n_keys]: one allocation
+    double2* t_ref = nullptr;               // [2 * max_ref]
+    double2* t_est = nullptr;               // [2 * max_est]
+    int2* win = nullptr;                    // [2 * max_ref], then stack [2 * max_ref]: one allocation
+    int* match = nullptr;                   // [2 * max_est], then visit [2 * max_est]: one allocation
+};
+
+static std::vector<Slot> slots(ymt3_metrics m) {
+    const size_t nk = (size_t)(m->p.n_programs + 1) * METRICS_PITCHES;
+    const size_t rs = 2 * (size_t)m->max_ref, es = 2 * (size_t)m->max_est;       // bucket slots: a counted note fills at most two
+    return {slot(&m->hist, (2 * nk + 2 * (nk + 1) + 2 * nk) * sizeof(unsigned)), slot(&m->t_ref, rs * sizeof(double2)), slot(&m->t_est, es * sizeof(double2)),
+            slot(&m->win, 2 * rs * sizeof(int2)), slot(&m->match, 2 * es * sizeof(int))};
+}
+extern "C" void ymt3_metrics_destroy(ymt3_metrics m) { destroy_object(m); }
+
+extern "C" int ymt3_metrics_create(ymt3_handle h, const ymt3_metrics_params* params, long long max_ref, long long max_est, ymt3_metrics* out) {
+    if (const int rc = create_prologue(reinterpret_cast<void**>(out), h, params, "params")) return rc;
+    const ymt3_metrics_params& p = *params;
+    if (!std::isfinite(p.onset_tol) || p.onset_tol < 0) FAIL(YMT3_ERR_ARG, "onset_tol=%g must be finite and >= 0", p.onset_tol);
+    if (!std::isfinite(p.offset_min_tol) || p.offset_min_tol < 0) FAIL(YMT3_ERR_ARG, "offset_min_tol=%g must be finite and >= 0", p.offset_min_tol);
+    if (!std::isfinite(p.offset_ratio) || p.offset_ratio < 0) FAIL(YMT3_ERR_ARG, "offset_ratio=%g must be finite and >= 0", p.offset_ratio);
+    if (const int rc = check_programs(p.n_programs, p.drum_program, METRICS_MAX_PROGRAMS, "")) return rc;
+    if (max_ref < 1 || max_ref > METRICS_MAX_NOTES) FAIL(YMT3_ERR_ARG, "max_ref=%lld outside [1, %lld]", max_ref, METRICS_MAX_NOTES);
+    if (max_est < 1 || max_est > METRICS_MAX_NOTES) FAIL(YMT3_ERR_ARG, "max_est=%lld outside [1, %lld]", max_est, METRICS_MAX_NOTES);
+    HIP_TRY(hipSetDevice(handle_device(h)));
+    ymt3_metrics m = new ymt3_metrics_s{h, handle_device(h), p, max_ref, max_est};
+    return allocate_object(m, slots(m), "note metrics scratch", out);
+}
+
+extern "C" int ymt3_note_metrics(ymt3_handle h, ymt3_metrics m, const void* ref_notes_dev, long long n_ref, const int32_t* ref_count_dev,
+                                 const void* est_notes_dev, long long n_est, const int32_t* est_count_dev, int32_t* counts_dev, void* stream) {
+    if (const int rc = check_owner(h, m, "metrics object")) return rc;
+    if (const int rc = check_count("n_ref", n_ref, m->max_ref, "max_ref")) return rc;
+    if (const int rc = check_count("n_est", n_est, m->max_est, "max_est")) return rc;
+    if (!counts_dev) FAIL(YMT3_ERR_ARG, "counts_dev is NULL");
+    if (const int rc = check_record_ptr("ref_notes_dev", ref_notes_dev, n_ref)) return rc;
+    if (const int rc = check_record_ptr("est_notes_dev", est_notes_dev, n_est)) return rc;
+    HIP_TRY(hipSetDevice(m->device));
+    const size_t nk = (size_t)(m->p.n_programs + 1) * METRICS_PITCHES;
+    MetricsArgs a{};
+    a.onset_tol = m->p.onset_tol; a.offset_min_tol = m->p.offset_min_tol; a.offset_ratio = m->p.offset_ratio;
+    a.ref = static_cast<const DetokNote*>(ref_notes_dev); a.est = static_cast<const DetokNote*>(est_notes_dev);
+    a.n_ref = n_ref; a.n_est = n_est; a.ref_count = n_ref ? ref_count_dev : nullptr; a.est_count = n_est ? est_count_dev : nullptr;
+    a.max_ref = m->max_ref; a.max_est = m->max_est; a.t_ref = m->t_ref; a.t_est = m->t_est;
+    a.hist = m->hist; a.off = m->hist + 2 * nk; a.cursor = a.off + 2 * (nk + 1);
+    a.n_programs = m->p.n_programs; a.drum_program = m->p.drum_program; a.win = m->win; a.stack = m->win + 2 * (size_t)m->max_ref;
+    a.match = m->match; a.visit = m->match + 2 * (size_t)m->max_est; a.counts = counts_dev;
+    LAUNCH(launch_metrics(a, static_cast<hipStream_t>(stream)));
+    return YMT3_OK;
+}
+
+// ---------------------------------------------------------------- device piano roll and frame metrics (include/ymt3.h)
+struct ymt3_roll_s {
+    ymt3_handle owner;
+    int device;
+    ymt3_roll_params p;
+    long long max_frames;
+    uint4* bits = nullptr;                  // [2][n_programs + 1][max_frames] 128 pitch bits each
+};
+
+static std::vector<Slot> slots(ymt3_roll r) { return {slot(&r->bits, (size_t)2 * (r->p.n_programs + 1) * (size_t)r->max_frames * sizeof(uint4))}; }
+extern "C" void ymt3_roll_destroy(ymt3_roll r) { destroy_object(r); }
+
+extern "C" int ymt3_roll_create(ymt3_handle h, const ymt3_roll_params* params, long long max_frames, ymt3_roll* out) {
+    if (const int rc = create_prologue(reinterpret_cast<void**>(out), h, params, "params")) return rc;
+    const ymt3_roll_params& p = *params;
+    if (!std::isfinite(p.frames_per_second) || p.frames_per_second <= 0) FAIL(YMT3_ERR_ARG, "frames_per_second=%g must be finite and > 0", p.frames_per_second);
+    if (const int rc = check_programs(p.n_programs, p.drum_program, ROLL_MAX_PROGRAMS, "")) return rc;
+    if (max_frames < 1 || max_frames > ROLL_MAX_FRAMES) FAIL(YMT3_ERR_ARG, "max_frames=%lld outside [1, %lld]", max_frames, ROLL_MAX_FRAMES);
+    HIP_TRY(hipSetDevice(handle_device(h)));
+    ymt3_roll r = new ymt3_roll_s{h, handle_device(h), p, max_frames};
+    return allocate_object(r, slots(r), "piano roll scratch", out);
+}
+
+// the checks the two roll calls share, and the arguments they share
+static int roll_args(ymt3_handle h, ymt3_roll r, long long n_frames, RollArgs* a) {
+    if (const int rc = check_owner(h, r, "roll object")) return rc;
+    if (n_frames < 0 || n_frames > r->max_frames) FAIL(YMT3_ERR_ARG, "n_frames=%lld outside [0, max_frames=%lld]", n_frames, r->max_frames);
+    *a = RollArgs{};
+    a->frames_per_second = r->p.frames_per_second; a->n_programs = r->p.n_programs; a->drum_program = r->p.drum_program;
+    a->n_frames = n_frames; a->max_frames = r->max_frames; a->bits = r->bits;
+    return YMT3_OK;
+}
+
+// one side of a roll or alignment call (RollArgs and AlignArgs name these three fields alike)
+template <class Args>
+static int set_side(Args* a, int side, const char* n_name, const char* ptr_name, const void* notes_dev, long long n, const int32_t* count_dev) {
+    if (const int rc = check_count(n_name, n, ROLL_MAX_NOTES, nullptr)) return rc;
+    if (const int rc = check_record_ptr(ptr_name, notes_dev, n)) return rc;
+    a->notes[side] = static_cast<const DetokNote*>(notes_dev); a->n[side] = n; a->count[side] = n ? count_dev : nullptr;
+    return YMT3_OK;
+}
+
+extern "C" int ymt3_piano_roll(ymt3_handle h, ymt3_roll r, const void* notes_dev, long long n_notes, const int32_t* count_dev, long long n_frames,
+                               int first_row, int n_rows, uint8_t* roll_dev, void* stream) {
+    RollArgs a;
+    if (const int rc = roll_args(h, r, n_frames, &a)) return rc;
+    if (const int rc = set_side(&a, 0, "n_notes", "notes_dev", notes_dev, n_notes, count_dev)) return rc;
+    if (first_row < 0 || n_rows < 1 || (long long)first_row + n_rows > r->p.n_programs + 1)
+        FAIL(YMT3_ERR_ARG, "rows [first_row=%d, first_row + n_rows=%lld) outside [0, n_programs + 1=%d]", first_row, (long long)first_row + n_rows, r->p.n_programs + 1);
+    if (!roll_dev) FAIL(YMT3_ERR_ARG, "roll_dev is NULL");
+    if (reinterpret_cast<uintptr_t>(roll_dev) % 16) FAIL(YMT3_ERR_ARG, "roll_dev is not aligned to 16 bytes");
+    HIP_TRY(hipSetDevice(r->device));
+    a.n_sides = 1; a.row0 = first_row; a.row_n = n_rows; a.roll = roll_dev;
+    LAUNCH(launch_piano_roll(a, static_cast<hipStream_t>(stream)));
+    return YMT3_OK;
+}
+
+extern "C" int ymt3_frame_metrics(ymt3_handle h, ymt3_roll r, const void* ref_notes_dev, long long n_ref, const int32_t* ref_count_dev,
+                                  const void* est_notes_dev, long long n_est, const int32_t* est_count_dev, long long n_frames, long long* counts_dev,
+                                  void* stream) {
+    RollArgs a;
+    if (const int rc = roll_args(h, r, n_frames, &a)) return rc;
+    if (const int rc = set_side(&a, 0, "n_ref", "ref_notes_dev", ref_notes_dev, n_ref, ref_count_dev)) return rc;
+    if (const int rc = set_side(&a, 1, "n_est", "est_notes_dev", est_notes_dev, n_est, est_count_dev)) return rc;
+    if (!counts_dev) FAIL(YMT3_ERR_ARG, "counts_dev is NULL");
+    if (reinterpret_cast<uintptr_t>(counts_dev) % 8) FAIL(YMT3_ERR_ARG, "counts_dev is not aligned to 8 bytes");
+    HIP_TRY(hipSetDevice(r->device));
+    a.n_sides = 2; a.row0 = 0; a.row_n = r->p.n_programs + 1; a.counts = counts_dev;
+    LAUNCH(launch_frame_metrics(a, static_cast<hipStream_t>(stream)));
+    return YMT3_OK;
+}
+
+// ---------------------------------------------------------------- device alignment (include/ymt3.h)
+struct ymt3_aligner_s {
+    ymt3_handle owner;
+    int device;
+    ymt3_align_params p;
+    long long max_frames, band;             // band = min(p.band_frames, max_frames)
+    uint4* feat = nullptr;                  // [2][max_frames][2]
+    int* edges = nullptr;                   // [align_edge_ints(max_frames)]
+    unsigned* steps = nullptr;              // [max_frames][align_step_words(band)]
+    int2* rpath = nullptr;                  // [2 * max_frames - 1]
+};
+
+static std::vector<Slot> slots(ymt3_aligner a) {
+    return {slot(&a->feat, (size_t)2 * a->max_frames * 2 * sizeof(uint4)), slot(&a->edges, (size_t)align_edge_ints(a->max_frames) * sizeof(int)),
+            slot(&a->steps, (size_t)a->max_frames * align_step_words(a->band) * sizeof(unsigned)), slot(&a->rpath, (size_t)(2 * a->max_frames - 1) * sizeof(int2))};
+}
+extern "C" void ymt3_aligner_destroy(ymt3_aligner a) { destroy_object(a); }
+
+extern "C" int ymt3_aligner_create(ymt3_handle h, const ymt3_align_params* params, long long max_frames, ymt3_aligner* out) {
+    if (const int rc = create_prologue(reinterpret_cast<void**>(out), h, params, "params")) return rc;
+    const ymt3_align_params& p = *params;
+    if (!std::isfinite(p.frames_per_second) || p.frames_per_second <= 0) FAIL(YMT3_ERR_ARG, "frames_per_second=%g must be finite and > 0", p.frames_per_second);
+    if (const int rc = check_programs(p.n_programs, p.drum_program, ROLL_MAX_PROGRAMS, "")) return rc;
+    if (p.band_frames < 1) FAIL(YMT3_ERR_ARG, "band_frames=%d must be >= 1", p.band_frames);
+    if (max_frames < 1 || max_frames > ALIGN_MAX_FRAMES) FAIL(YMT3_ERR_ARG, "max_frames=%lld outside [1, %lld]", max_frames, ALIGN_MAX_FRAMES);
+    HIP_TRY(hipSetDevice(handle_device(h)));
+    ymt3_aligner a = new ymt3_aligner_s{h, handle_device(h), p, max_frames, std::min<long long>(p.band_frames, max_frames)};
+    return allocate_object(a, slots(a), "alignment scratch", out);
+}
+
+extern "C" int ymt3_align_notes(ymt3_handle h, ymt3_aligner al, const void* ref_notes_dev, long long n_ref, const int32_t* ref_count_dev,
+                                long long n_ref_frames, const void* est_notes_dev, long long n_est, const int32_t* est_count_dev,
+                                long long n_est_frames, int32_t* warp_dev, int32_t* path_dev, long long* result_dev, void* stream) {
+    if (const int rc = check_owner(h, al, "aligner object")) return rc;
+    AlignArgs a{};
+    a.frames_per_second = al->p.frames_per_second; a.n_programs = al->p.n_programs; a.drum_program = al->p.drum_program;
+    a.band_frames = al->band; a.max_frames = al->max_frames; a.n_frames[0] = n_ref_frames; a.n_frames[1] = n_est_frames;
+    if (n_ref_frames < 1 || n_ref_frames > a.max_frames) FAIL(YMT3_ERR_ARG, "n_ref_frames=%lld outside [1, max_frames=%lld]", n_ref_frames, a.max_frames);
+    if (const int rc = set_side(&a, 0, "n_ref", "ref_notes_dev", ref_notes_dev, n_ref, ref_count_dev)) return rc;
+    if (n_est_frames < 1 || n_est_frames > a.max_frames) FAIL(YMT3_ERR_ARG, "n_est_frames=%lld outside [1, max_frames=%lld]", n_est_frames, a.max_frames);
+    if (const int rc = set_side(&a, 1, "n_est", "est_notes_dev", est_notes_dev, n_est, est_count_dev)) return rc;
+    if (!warp_dev) FAIL(YMT3_ERR_ARG, "warp_dev is NULL");
+    if (reinterpret_cast<uintptr_t>(warp_dev) % 4) FAIL(YMT3_ERR_ARG, "warp_dev is not aligned to 4 bytes");
+    if (reinterpret_cast<uintptr_t>(path_dev) % 8) FAIL(YMT3_ERR_ARG, "path_dev is not aligned to 8 bytes");
+    if (!result_dev) FAIL(YMT3_ERR_ARG, "result_dev is NULL");
+    if (reinterpret_cast<uintptr_t>(result_dev) % 8) FAIL(YMT3_ERR_ARG, "result_dev is not aligned to 8 bytes");
+    HIP_TRY(hipSetDevice(al->device));
+    a.feat = al->feat; a.edges = al->edges; a.steps = al->steps; a.rpath = al->rpath; a.warp = warp_dev; a.path = path_dev; a.result = result_dev;
+    LAUNCH(launch_align(a, static_cast<hipStream_t>(stream)));
+    return YMT3_OK;
+}
+
+extern "C" int ymt3_warp_notes(ymt3_handle h, ymt3_aligner al, const void* notes_dev, long long n_notes, const int32_t* count_dev,
+                               const int32_t* warp_dev, long long n_ref_frames, void* notes_out_dev, void* stream) {
+    if (const int rc = check_owner(h, al, "aligner object")) return rc;
+    if (n_ref_frames < 1 || n_ref_frames > al->max_frames) FAIL(YMT3_ERR_ARG, "n_ref_frames=%lld outside [1, max_frames=%lld]", n_ref_frames, al->max_frames);
+    if (const int rc = check_count("n_notes", n_notes, ROLL_MAX_NOTES, nullptr)) return rc;
+    if (!warp_dev) FAIL(YMT3_ERR_ARG, "warp_dev is NULL");
+    if (reinterpret_cast<uintptr_t>(warp_dev) % 4) FAIL(YMT3_ERR_ARG, "warp_dev is not aligned to 4 bytes");
+    if (const int rc = check_record_ptr("notes_dev", notes_dev, n_notes)) return rc;
+    if (const int rc = check_record_ptr("notes_out_dev", notes_out_dev, n_notes)) return rc;
+    HIP_TRY(hipSetDevice(al->device));
+    WarpNotesArgs a{al->p.frames_per_second, static_cast<const DetokNote*>(notes_dev), static_cast<DetokNote*>(notes_out_dev), n_notes,
+                    n_notes ? count_dev : nullptr, warp_dev, n_ref_frames};
+    LAUNCH(launch_warp_notes(a, static_cast<hipStream_t>(stream)));
+    return YMT3_OK;
+}

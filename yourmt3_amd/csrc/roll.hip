@@ -9,8 +9,8 @@
 // a call are packed at the call's n_frames, so the frames in use are one contiguous range of words.  The object's scratch holds
 // 2 x (n_programs + 1) x max_frames words: about 126 MB per side for 131 rows x 10 minutes at 100 frames per second.
 // (a) roll_clear_kernel: zeroes the words in use (n_frames of every row and side of the call) and, for the metrics, counts_dev.
-// (b) roll_raster_kernel, one wave per record and side: every lane classifies the record (the note metrics' rule) and computes the
-//     clipped frame interval; the lanes stride over its frames and set the pitch bit with atomicOr on the dword, in the record's
+// (b) roll_raster_kernel, one wave per record and side: every lane classifies the record and computes the clipped frame
+//     interval (note_rule.h); the lanes stride over its frames and set the pitch bit with atomicOr on the dword, in the record's
 //     aware row and, if it is pitched, in the agnostic row.  A skipped record adds one to skipped[side].
 // (c) roll_reduce_kernel (metrics), one lane per (row, frame) and REDUCE_FRAMES frames per lane: nr, ne, tp and the three error terms;
 //     the wave sums the six values with shuffles and lane 0 adds those that are not zero to the row's six 64-bit integers.  Integer
@@ -20,6 +20,7 @@
 // No kernel waits on another workgroup and nothing spins.
 #include "common.h"
 #include "kernels.h"
+#include "note_rule.h"
 
 namespace {
 
@@ -38,41 +39,19 @@ __global__ __launch_bounds__(ROLL_THREADS) void roll_clear_kernel(RollArgs a) {
 __global__ __launch_bounds__(ROLL_THREADS) void roll_raster_kernel(RollArgs a) {
     const int side = blockIdx.y, lane = threadIdx.x & (WAVE - 1);
     const long long i = (long long)blockIdx.x * (ROLL_THREADS / WAVE) + (threadIdx.x >> 6);
-    const int32_t* cp = a.count[side];
-    long long n = a.n[side];
-    if (cp) {
-        const long long c = max(*cp, 0);
-        n = min(n, c);
-    }
-    if (i >= n) return;
+    if (i >= note_live_count(a.n[side], a.count[side])) return;
     const DetokNote r = a.notes[side][i];
-    const int prog = r.is_drum != 0 ? a.drum_program : r.program;
-    const bool drum = prog == a.drum_program;
-    const bool counted = r.onset == r.onset && r.pitch >= 0 && r.pitch < ROLL_PITCHES && prog >= 0 && prog < a.n_programs &&
-                         (drum || r.offset == r.offset);
-    if (!counted) {
+    const NoteClass c = note_classify(r, a.n_programs, a.drum_program);
+    if (!c.counted) {
         if (a.counts && lane == 0) atomicAdd(reinterpret_cast<unsigned long long*>(&a.counts[(a.n_programs + 1) * 6 + side]), 1ull);
         return;
     }
-    // [F(on), max(F(off), F(on) + 1)) clipped to [0, n_frames) in f64: +-inf and huge times never reach an integer conversion
-    double lo, hi;
-    {
-#pragma clang fp contract(off)
-        const double f0 = rint(r.onset * a.frames_per_second);
-        double f1 = f0 + 1.0;
-        if (!drum) {
-            const double fo = rint(r.offset * a.frames_per_second);
-            f1 = fo > f1 ? fo : f1;
-        }
-        lo = f0 > 0.0 ? f0 : 0.0;
-        hi = f1 < (double)a.n_frames ? f1 : (double)a.n_frames;
-    }
-    if (!(lo < hi)) return;
-    const long long f_lo = (long long)lo, f_hi = (long long)hi;         // 0 <= f_lo < f_hi <= n_frames
+    long long f_lo, f_hi;
+    if (!note_frame_span(r, c.drum, a.frames_per_second, a.n_frames, &f_lo, &f_hi)) return;
     const int dword = r.pitch >> 5;
     const unsigned bit = 1u << (r.pitch & 31);
     unsigned* words = reinterpret_cast<unsigned*>(a.bits);
-    const int rows[2] = {prog, drum ? -1 : a.n_programs};
+    const int rows[2] = {c.prog, c.drum ? -1 : a.n_programs};
 #pragma unroll
     for (int k = 0; k < 2; ++k) {
         const int row = rows[k] - a.row0;

@@ -2,7 +2,8 @@
 // replay of the decode step.  Declarations and ownership rules: include/ymt3.h.
 //
 // Host logic only -- every FLOP is in frontend.hip / gemm.hip / norm.hip / enc_attn.hip /
-// decode.hip.  There is no CPU fallback: a missing device, tensor or unsupported shape is an error.
+// decode.hip; the note-side objects are in note_objects.hip.  There is no CPU fallback: a missing
+// device, tensor or unsupported shape is an error.
 #include <hip/hip_runtime.h>
 
 #include <cmath>
@@ -21,6 +22,7 @@
 #include "../../include/ymt3.h"
 #include "common.h"
 #include "kernels.h"
+#include "runtime.h"
 
 // ------------------------------------------------------------------------------------------------
 static thread_local char g_err[512] = "";
@@ -30,17 +32,6 @@ void ymt3_set_error(const char* fmt, ...) {
     vsnprintf(g_err, sizeof(g_err), fmt, ap);
     va_end(ap);
 }
-#define FAIL(code, ...)              \
-    do {                             \
-        ymt3_set_error(__VA_ARGS__); \
-        return (code);               \
-    } while (0)
-#define LAUNCH(expr)                                                             \
-    do {                                                                         \
-        int _rc = (expr);                                                        \
-        if (_rc != 0) FAIL(YMT3_ERR_UNSUPPORTED, "%s rejected its shape (rc=%d)", #expr, _rc); \
-    } while (0)
-
 struct Tensor {
     void* dev = nullptr;
     uint32_t dtype = 0, ndim = 0, shape[4] = {1, 1, 1, 1};
@@ -290,6 +281,9 @@ static void clear_step_graphs(ymt3_ctx* h) {
 }
 
 // ------------------------------------------------------------------------------------------------
+int handle_device(ymt3_handle h) { return h->device; }
+const ymt3_config& handle_config(ymt3_handle h) { return h->cfg; }
+
 extern "C" int ymt3_abi_version(void) { return YMT3_ABI_VERSION; }
 extern "C" const char* ymt3_last_error(void) { return g_err; }
 
@@ -697,576 +691,6 @@ extern "C" int ymt3_constraint_create(ymt3_handle h, int n_states, int vocab, co
         FAIL(YMT3_ERR_HIP, "constraint upload (%zu bytes) failed", ab + nb);
     }
     *out = c;
-    return YMT3_OK;
-}
-
-// ---------------------------------------------------------------- device detokeniser (include/ymt3.h)
-struct ymt3_detok_s {
-    ymt3_ctx* owner;
-    int device, vocab, steps_per_second, drum_program, n_programs, max_segments, max_steps;
-    uint16_t* table = nullptr;              // [vocab]
-    unsigned long long* items = nullptr;    // [n_channels * max_segments * max_steps]
-    unsigned long long* sorted = nullptr;   // the same
-    uint16_t* keys = nullptr;               // the same
-    int* row_count = nullptr;               // [n_channels * max_segments]
-    unsigned* key_off = nullptr;            // [n_channels][n_programs * 128]
-};
-
-extern "C" void ymt3_detok_destroy(ymt3_detok d) {
-    if (!d) return;
-    (void)hipSetDevice(d->device);
-    for (void* p : {(void*)d->table, (void*)d->items, (void*)d->sorted, (void*)d->keys, (void*)d->row_count, (void*)d->key_off})
-        if (p) (void)hipFree(p);
-    delete d;
-}
-
-extern "C" int ymt3_detok_create(ymt3_handle h, const uint16_t* token_table_host, int vocab, int steps_per_second, int drum_program,
-                                 int max_segments, int max_steps, ymt3_detok* out) {
-    if (!out) FAIL(YMT3_ERR_ARG, "null output pointer");
-    *out = nullptr;
-    if (!h) FAIL(YMT3_ERR_ARG, "null handle");
-    if (!token_table_host) FAIL(YMT3_ERR_ARG, "token_table_host is NULL");
-    if (vocab != h->cfg.vocab) FAIL(YMT3_ERR_ARG, "detokeniser vocab=%d != the model's vocab=%d", vocab, h->cfg.vocab);
-    if (steps_per_second < 1) FAIL(YMT3_ERR_ARG, "steps_per_second=%d must be >= 1", steps_per_second);
-    if (drum_program < 0 || drum_program > 4095) FAIL(YMT3_ERR_ARG, "drum_program=%d outside [0, 4095]", drum_program);
-    if (max_segments < 1 || max_segments > DETOK_MAX_SEGMENTS) FAIL(YMT3_ERR_ARG, "max_segments=%d outside [1, %d]", max_segments, DETOK_MAX_SEGMENTS);
-    if (max_steps < 1 || max_steps > h->cfg.max_decode_len || max_steps > DETOK_MAX_STEPS)
-        FAIL(YMT3_ERR_ARG, "max_steps=%d outside [1, max_decode_len=%d]", max_steps, std::min(h->cfg.max_decode_len, DETOK_MAX_STEPS));
-    int n_programs = drum_program + 1;
-    for (int i = 0; i < vocab; ++i) {
-        const int cls = token_table_host[i] >> 12, v = token_table_host[i] & 0xfff;
-        if (cls > 8) FAIL(YMT3_ERR_ARG, "token_table_host[%d] has class %d (0..8 are defined)", i, cls);
-        if ((cls == 4 || cls == 8) && v >= DETOK_PITCHES) FAIL(YMT3_ERR_ARG, "token_table_host[%d]: pitch %d outside [0, %d)", i, v, DETOK_PITCHES);
-        if (cls == 5 && v > 1) FAIL(YMT3_ERR_ARG, "token_table_host[%d]: velocity %d is neither 0 (offsets) nor 1 (onsets)", i, v);
-        if (cls == 7) n_programs = std::max(n_programs, v + 1);
-    }
-    if (n_programs > DETOK_MAX_PROGRAMS)
-        FAIL(YMT3_ERR_UNSUPPORTED, "programs up to %d: the merge keeps one LDS counter per (program, pitch), at most %d programs", n_programs - 1, DETOK_MAX_PROGRAMS);
-    HIP_TRY(hipSetDevice(h->device));
-    if (init_detok_kernels()) FAIL(YMT3_ERR_HIP, "hipFuncSetAttribute(max dynamic LDS) failed");
-    ymt3_detok d = new ymt3_detok_s{h, h->device, vocab, steps_per_second, drum_program, n_programs, max_segments, max_steps};
-    const size_t rows = (size_t)max_segments * h->cfg.n_channels, slots = rows * max_steps;
-    const size_t koff = (size_t)h->cfg.n_channels * n_programs * DETOK_PITCHES * sizeof(unsigned);
-    if (hipMalloc(reinterpret_cast<void**>(&d->table), (size_t)vocab * 2) != hipSuccess ||
-        hipMalloc(reinterpret_cast<void**>(&d->items), slots * 8) != hipSuccess ||
-        hipMalloc(reinterpret_cast<void**>(&d->sorted), slots * 8) != hipSuccess ||
-        hipMalloc(reinterpret_cast<void**>(&d->keys), slots * 2) != hipSuccess ||
-        hipMalloc(reinterpret_cast<void**>(&d->row_count), rows * sizeof(int)) != hipSuccess ||
-        hipMalloc(reinterpret_cast<void**>(&d->key_off), koff) != hipSuccess ||
-        hipMemcpy(d->table, token_table_host, (size_t)vocab * 2, hipMemcpyHostToDevice) != hipSuccess) {
-        ymt3_detok_destroy(d);
-        FAIL(YMT3_ERR_HIP, "detokeniser scratch (%zu bytes) could not be allocated", slots * 18 + rows * sizeof(int) + koff);
-    }
-    *out = d;
-    return YMT3_OK;
-}
-
-extern "C" int ymt3_detokenize(ymt3_handle h, ymt3_detok d, const int32_t* tokens_dev, const float* scores_dev, int n_segments, int n_steps,
-                               long long seg_stride, long long chan_stride, const double* start_sec_dev, double end_sec, void* notes_dev,
-                               long long capacity, int32_t* counts_dev, void* stream) {
-    if (!h) FAIL(YMT3_ERR_ARG, "null handle");
-    if (!d) FAIL(YMT3_ERR_ARG, "null detokeniser");
-    if (d->owner != h) FAIL(YMT3_ERR_ARG, "the detokeniser belongs to another handle");
-    if (n_segments < 0 || n_segments > d->max_segments) FAIL(YMT3_ERR_ARG, "n_segments=%d outside [0, max_segments=%d]", n_segments, d->max_segments);
-    if (n_steps < 1 || n_steps > d->max_steps) FAIL(YMT3_ERR_ARG, "n_steps=%d outside [1, max_steps=%d]", n_steps, d->max_steps);
-    if (!counts_dev) FAIL(YMT3_ERR_ARG, "counts_dev is NULL");
-    if (n_segments && !tokens_dev) FAIL(YMT3_ERR_ARG, "tokens_dev is NULL");
-    if (n_segments && !start_sec_dev) FAIL(YMT3_ERR_ARG, "start_sec_dev is NULL");
-    if (n_segments && !notes_dev) FAIL(YMT3_ERR_ARG, "notes_dev is NULL");
-    const long long bound = (long long)n_segments * h->cfg.n_channels * n_steps;
-    if (capacity < bound) FAIL(YMT3_ERR_ARG, "capacity=%lld below n_segments * n_channels * n_steps = %lld records", capacity, bound);
-    HIP_TRY(hipSetDevice(h->device));
-    hipStream_t s = static_cast<hipStream_t>(stream);
-    HIP_TRY(hipMemsetAsync(counts_dev, 0, 2 * sizeof(int32_t), s));
-    if (!n_segments) return YMT3_OK;
-    DetokArgs a{};
-    a.table = d->table; a.vocab = d->vocab; a.steps_per_second = d->steps_per_second; a.drum_program = d->drum_program; a.n_programs = d->n_programs;
-    a.tokens = tokens_dev; a.scores = scores_dev; a.seg_stride = seg_stride; a.chan_stride = chan_stride;
-    a.n_seg = n_segments; a.n_chan = h->cfg.n_channels; a.L = n_steps;
-    a.start = start_sec_dev; a.end_sec = end_sec;
-    a.items = d->items; a.keys = d->keys; a.row_count = d->row_count; a.sorted = d->sorted; a.key_off = d->key_off;
-    a.notes = static_cast<DetokNote*>(notes_dev); a.capacity = capacity; a.counts = counts_dev;
-    LAUNCH(launch_detok(a, s));
-    return YMT3_OK;
-}
-
-// ---------------------------------------------------------------- incremental detokeniser (include/ymt3.h)
-struct ymt3_detok_state_s {
-    ymt3_ctx* owner;
-    ymt3_detok detok;                       // the detokeniser it was created for (compared by address only)
-    int device, n_chan, n_programs, max_held;
-    DetokSounding* sounding = nullptr;      // [n_chan][n_programs * 128]
-    DetokHeld* held[2] = {nullptr, nullptr};   // [n_chan][128][max_held], read from [cur], written to [cur ^ 1]
-    int* held_count[2] = {nullptr, nullptr};   // [n_chan][128]
-    int cur = 0;
-    double horizon = -INFINITY;             // of the last push
-    bool finished = false;
-};
-
-extern "C" void ymt3_detok_state_destroy(ymt3_detok_state st) {
-    if (!st) return;
-    (void)hipSetDevice(st->device);
-    for (void* p : {(void*)st->sounding, (void*)st->held[0], (void*)st->held[1], (void*)st->held_count[0], (void*)st->held_count[1]})
-        if (p) (void)hipFree(p);
-    delete st;
-}
-
-static size_t detok_state_sounding_bytes(const ymt3_detok_state_s* st) { return (size_t)st->n_chan * st->n_programs * DETOK_PITCHES * sizeof(DetokSounding); }
-static size_t detok_state_count_bytes(const ymt3_detok_state_s* st) { return (size_t)st->n_chan * DETOK_PITCHES * sizeof(int); }
-
-extern "C" long long ymt3_detok_state_carry(ymt3_detok_state st) {
-    if (!st) return 0;
-    return (long long)st->n_chan * DETOK_PITCHES * ((long long)st->n_programs - 1 + st->max_held);
-}
-
-extern "C" int ymt3_detok_state_create(ymt3_handle h, ymt3_detok d, int max_held, ymt3_detok_state* out) {
-    if (!out) FAIL(YMT3_ERR_ARG, "null output pointer");
-    *out = nullptr;
-    if (!h) FAIL(YMT3_ERR_ARG, "null handle");
-    if (!d) FAIL(YMT3_ERR_ARG, "null detokeniser");
-    if (d->owner != h) FAIL(YMT3_ERR_ARG, "the detokeniser belongs to another handle");
-    if (max_held < 1 || max_held > 4096) FAIL(YMT3_ERR_ARG, "max_held=%d outside [1, 4096]", max_held);
-    HIP_TRY(hipSetDevice(h->device));
-    ymt3_detok_state st = new ymt3_detok_state_s{h, d, h->device, h->cfg.n_channels, d->n_programs, max_held};
-    const size_t hb = (size_t)st->n_chan * DETOK_PITCHES * max_held * sizeof(DetokHeld), cb = detok_state_count_bytes(st);
-    if (hipMalloc(reinterpret_cast<void**>(&st->sounding), detok_state_sounding_bytes(st)) != hipSuccess ||
-        hipMalloc(reinterpret_cast<void**>(&st->held[0]), hb) != hipSuccess || hipMalloc(reinterpret_cast<void**>(&st->held[1]), hb) != hipSuccess ||
-        hipMalloc(reinterpret_cast<void**>(&st->held_count[0]), cb) != hipSuccess || hipMalloc(reinterpret_cast<void**>(&st->held_count[1]), cb) != hipSuccess ||
-        hipMemset(st->sounding, 0, detok_state_sounding_bytes(st)) != hipSuccess || hipMemset(st->held_count[0], 0, cb) != hipSuccess ||
-        hipMemset(st->held_count[1], 0, cb) != hipSuccess) {
-        ymt3_detok_state_destroy(st);
-        FAIL(YMT3_ERR_HIP, "detokeniser state (%zu bytes) could not be allocated", detok_state_sounding_bytes(st) + 2 * (hb + cb));
-    }
-    *out = st;
-    return YMT3_OK;
-}
-
-extern "C" int ymt3_detok_state_reset(ymt3_handle h, ymt3_detok_state st, void* stream) {
-    if (!h) FAIL(YMT3_ERR_ARG, "null handle");
-    if (!st) FAIL(YMT3_ERR_ARG, "null detokeniser state");
-    if (st->owner != h) FAIL(YMT3_ERR_ARG, "the detokeniser state belongs to another handle");
-    HIP_TRY(hipSetDevice(h->device));
-    hipStream_t s = static_cast<hipStream_t>(stream);
-    HIP_TRY(hipMemsetAsync(st->sounding, 0, detok_state_sounding_bytes(st), s));
-    HIP_TRY(hipMemsetAsync(st->held_count[st->cur], 0, detok_state_count_bytes(st), s));
-    st->horizon = -INFINITY;
-    st->finished = false;
-    return YMT3_OK;
-}
-
-// the shared tail of push and finish: n_segments = 0 walks the state alone
-static int detok_carry(ymt3_handle h, ymt3_detok d, ymt3_detok_state st, const int32_t* tokens_dev, const float* scores_dev, int n_segments,
-                       int n_steps, long long seg_stride, long long chan_stride, const double* start_sec_dev, double horizon, double end_sec,
-                       int finish, void* notes_dev, long long capacity, int32_t* counts_dev, void* stream) {
-    if (!h) FAIL(YMT3_ERR_ARG, "null handle");
-    if (!d) FAIL(YMT3_ERR_ARG, "null detokeniser");
-    if (!st) FAIL(YMT3_ERR_ARG, "null detokeniser state");
-    if (d->owner != h) FAIL(YMT3_ERR_ARG, "the detokeniser belongs to another handle");
-    if (st->owner != h || st->detok != d) FAIL(YMT3_ERR_ARG, "the detokeniser state was created for another detokeniser");
-    if (st->finished) FAIL(YMT3_ERR_ARG, "the state has been finished: reset it first");
-    if (n_segments < 0 || n_segments > d->max_segments) FAIL(YMT3_ERR_ARG, "n_segments=%d outside [0, max_segments=%d]", n_segments, d->max_segments);
-    if (n_segments && (n_steps < 1 || n_steps > d->max_steps)) FAIL(YMT3_ERR_ARG, "n_steps=%d outside [1, max_steps=%d]", n_steps, d->max_steps);
-    if (!counts_dev) FAIL(YMT3_ERR_ARG, "counts_dev is NULL");
-    if (!notes_dev) FAIL(YMT3_ERR_ARG, "notes_dev is NULL");
-    if (n_segments && !tokens_dev) FAIL(YMT3_ERR_ARG, "tokens_dev is NULL");
-    if (n_segments && !start_sec_dev) FAIL(YMT3_ERR_ARG, "start_sec_dev is NULL");
-    if (!finish && !(horizon >= st->horizon && horizon > -INFINITY))
-        FAIL(YMT3_ERR_ARG, "horizon_sec=%g is -inf, NaN or below the previous push's horizon %g", horizon, st->horizon);
-    const long long bound = (long long)n_segments * h->cfg.n_channels * (n_segments ? n_steps : 0) + ymt3_detok_state_carry(st);
-    if (capacity < bound)
-        FAIL(YMT3_ERR_ARG, "capacity=%lld below n_segments * n_channels * n_steps + ymt3_detok_state_carry = %lld records", capacity, bound);
-    HIP_TRY(hipSetDevice(h->device));
-    hipStream_t s = static_cast<hipStream_t>(stream);
-    HIP_TRY(hipMemsetAsync(counts_dev, 0, 3 * sizeof(int32_t), s));
-    DetokArgs a{};
-    a.table = d->table; a.vocab = d->vocab; a.steps_per_second = d->steps_per_second; a.drum_program = d->drum_program; a.n_programs = d->n_programs;
-    a.tokens = tokens_dev; a.scores = scores_dev; a.seg_stride = seg_stride; a.chan_stride = chan_stride;
-    a.n_seg = n_segments; a.n_chan = h->cfg.n_channels; a.L = n_segments ? n_steps : 1;
-    a.start = start_sec_dev; a.end_sec = end_sec;
-    a.items = d->items; a.keys = d->keys; a.row_count = d->row_count; a.sorted = d->sorted; a.key_off = d->key_off;
-    a.notes = static_cast<DetokNote*>(notes_dev); a.capacity = capacity; a.counts = counts_dev;
-    DetokCarryArgs c{};
-    c.sounding = st->sounding; c.held_in = st->held[st->cur]; c.held_out = st->held[st->cur ^ 1];
-    c.held_count_in = st->held_count[st->cur]; c.held_count_out = st->held_count[st->cur ^ 1];
-    c.max_held = st->max_held; c.finish = finish; c.horizon = horizon;
-    LAUNCH(launch_detok_carry(a, c, s));
-    HIP_TRY(hipGetLastError());
-    st->cur ^= 1;
-    if (finish) st->finished = true;
-    else st->horizon = horizon;
-    return YMT3_OK;
-}
-
-extern "C" int ymt3_detokenize_push(ymt3_handle h, ymt3_detok d, ymt3_detok_state st, const int32_t* tokens_dev, const float* scores_dev,
-                                    int n_segments, int n_steps, long long seg_stride, long long chan_stride, const double* start_sec_dev,
-                                    double horizon_sec, void* notes_dev, long long capacity, int32_t* counts_dev, void* stream) {
-    return detok_carry(h, d, st, tokens_dev, scores_dev, n_segments, n_steps, seg_stride, chan_stride, start_sec_dev, horizon_sec, 0.0, 0,
-                       notes_dev, capacity, counts_dev, stream);
-}
-
-extern "C" int ymt3_detokenize_finish(ymt3_handle h, ymt3_detok d, ymt3_detok_state st, double end_sec, void* notes_dev, long long capacity,
-                                      int32_t* counts_dev, void* stream) {
-    return detok_carry(h, d, st, nullptr, nullptr, 0, 0, 0, 0, nullptr, INFINITY, end_sec, 1, notes_dev, capacity, counts_dev, stream);
-}
-
-// ---------------------------------------------------------------- device tokeniser (include/ymt3.h)
-struct ymt3_tok_s {
-    ymt3_ctx* owner;
-    int device;
-    ymt3_tok_params p;
-    int n_programs, max_segments, max_steps;
-    uint8_t* program_channel = nullptr;     // [n_programs]
-    unsigned long long* items = nullptr;    // [max_segments * n_channels * max_steps]
-    int* row_count = nullptr;               // [max_segments * n_channels]
-    unsigned* tie_seen = nullptr;           // [max_segments][n_programs * 4]
-};
-
-extern "C" void ymt3_tok_destroy(ymt3_tok t) {
-    if (!t) return;
-    (void)hipSetDevice(t->device);
-    for (void* p : {(void*)t->program_channel, (void*)t->items, (void*)t->row_count, (void*)t->tie_seen})
-        if (p) (void)hipFree(p);
-    delete t;
-}
-
-extern "C" int ymt3_tok_create(ymt3_handle h, const ymt3_tok_params* params, const uint8_t* program_channel_host, int n_programs, int max_segments,
-                               int max_steps, ymt3_tok* out) {
-    if (!out) FAIL(YMT3_ERR_ARG, "null output pointer");
-    *out = nullptr;
-    if (!h) FAIL(YMT3_ERR_ARG, "null handle");
-    if (!params) FAIL(YMT3_ERR_ARG, "params is NULL");
-    if (!program_channel_host) FAIL(YMT3_ERR_ARG, "program_channel_host is NULL");
-    const ymt3_tok_params& p = *params;
-    const int V = h->cfg.vocab;
-    if (n_programs < 1) FAIL(YMT3_ERR_ARG, "n_programs=%d must be >= 1", n_programs);
-    if (n_programs > TOK_MAX_PROGRAMS) FAIL(YMT3_ERR_UNSUPPORTED, "n_programs=%d: an item gives the program 8 bits, at most %d programs", n_programs, TOK_MAX_PROGRAMS);
-    if (p.steps_per_second < 1) FAIL(YMT3_ERR_ARG, "steps_per_second=%d must be >= 1", p.steps_per_second);
-    if (p.max_shift_steps < 1) FAIL(YMT3_ERR_ARG, "max_shift_steps=%d must be >= 1", p.max_shift_steps);
-    if (p.drum_program < 0 || p.drum_program >= n_programs) FAIL(YMT3_ERR_ARG, "drum_program=%d outside [0, n_programs=%d)", p.drum_program, n_programs);
-    const struct { const char* name; int base, size; } ranges[] = {
-        {"shift_base", p.shift_base, p.max_shift_steps}, {"pitch_base", p.pitch_base, TOK_PITCHES}, {"velocity_base", p.velocity_base, 2},
-        {"tie_base", p.tie_base, 1}, {"program_base", p.program_base, n_programs}, {"drum_base", p.drum_base, TOK_PITCHES},
-        {"eos_id", p.eos_id, 1}, {"pad_id", p.pad_id, 1}};
-    for (const auto& r : ranges)
-        if (r.base < 0 || (long long)r.base + r.size > V) FAIL(YMT3_ERR_ARG, "%s=%d: its %d ids do not fit the model's vocab=%d", r.name, r.base, r.size, V);
-    for (int i = 0; i < n_programs; ++i)
-        if (program_channel_host[i] >= h->cfg.n_channels)
-            FAIL(YMT3_ERR_ARG, "program_channel_host[%d]=%d outside [0, n_channels=%d)", i, (int)program_channel_host[i], h->cfg.n_channels);
-    if (max_segments < 1 || max_segments > TOK_MAX_SEGMENTS) FAIL(YMT3_ERR_ARG, "max_segments=%d outside [1, %d]", max_segments, TOK_MAX_SEGMENTS);
-    if (max_steps < 1 || max_steps > h->cfg.max_decode_len || max_steps > TOK_MAX_STEPS)
-        FAIL(YMT3_ERR_ARG, "max_steps=%d outside [1, max_decode_len=%d]", max_steps, std::min(h->cfg.max_decode_len, TOK_MAX_STEPS));
-    HIP_TRY(hipSetDevice(h->device));
-    ymt3_tok t = new ymt3_tok_s{h, h->device, p, n_programs, max_segments, max_steps};
-    const size_t rows = (size_t)max_segments * h->cfg.n_channels, slots = rows * max_steps;
-    const size_t seen = (size_t)max_segments * n_programs * (TOK_PITCHES / 8);
-    if (hipMalloc(reinterpret_cast<void**>(&t->program_channel), (size_t)n_programs) != hipSuccess ||
-        hipMalloc(reinterpret_cast<void**>(&t->items), slots * 8) != hipSuccess ||
-        hipMalloc(reinterpret_cast<void**>(&t->row_count), rows * sizeof(int)) != hipSuccess ||
-        hipMalloc(reinterpret_cast<void**>(&t->tie_seen), seen) != hipSuccess ||
-        hipMemcpy(t->program_channel, program_channel_host, (size_t)n_programs, hipMemcpyHostToDevice) != hipSuccess) {
-        ymt3_tok_destroy(t);
-        FAIL(YMT3_ERR_HIP, "tokeniser scratch (%zu bytes) could not be allocated", slots * 8 + rows * sizeof(int) + seen + n_programs);
-    }
-    *out = t;
-    return YMT3_OK;
-}
-
-extern "C" int ymt3_tokenize(ymt3_handle h, ymt3_tok t, const void* notes_dev, long long n_notes, const double* start_sec_dev, int n_segments,
-                             double end_sec, int n_steps, int32_t* tokens_dev, int32_t* lengths_dev, void* stream) {
-    if (!h) FAIL(YMT3_ERR_ARG, "null handle");
-    if (!t) FAIL(YMT3_ERR_ARG, "null tokeniser");
-    if (t->owner != h) FAIL(YMT3_ERR_ARG, "the tokeniser belongs to another handle");
-    if (n_segments < 0 || n_segments > t->max_segments) FAIL(YMT3_ERR_ARG, "n_segments=%d outside [0, max_segments=%d]", n_segments, t->max_segments);
-    if (n_steps < 1 || n_steps > t->max_steps) FAIL(YMT3_ERR_ARG, "n_steps=%d outside [1, max_steps=%d]", n_steps, t->max_steps);
-    if (n_notes < 0 || n_notes > TOK_MAX_NOTES) FAIL(YMT3_ERR_ARG, "n_notes=%lld outside [0, %lld]", n_notes, TOK_MAX_NOTES);
-    if (!n_segments) return YMT3_OK;
-    if (n_notes && !notes_dev) FAIL(YMT3_ERR_ARG, "notes_dev is NULL");
-    if (reinterpret_cast<uintptr_t>(notes_dev) % 8) FAIL(YMT3_ERR_ARG, "notes_dev is not aligned to 8 bytes");
-    if (!start_sec_dev) FAIL(YMT3_ERR_ARG, "start_sec_dev is NULL");
-    if (!tokens_dev) FAIL(YMT3_ERR_ARG, "tokens_dev is NULL");
-    if (!lengths_dev) FAIL(YMT3_ERR_ARG, "lengths_dev is NULL");
-    HIP_TRY(hipSetDevice(h->device));
-    const ymt3_tok_params& p = t->p;
-    TokArgs a{};
-    a.shift_base = p.shift_base; a.pitch_base = p.pitch_base; a.velocity_base = p.velocity_base; a.tie_base = p.tie_base;
-    a.program_base = p.program_base; a.drum_base = p.drum_base; a.max_shift_steps = p.max_shift_steps; a.steps_per_second = p.steps_per_second;
-    a.drum_program = p.drum_program; a.eos_id = p.eos_id; a.pad_id = p.pad_id;
-    a.n_programs = t->n_programs; a.program_channel = t->program_channel;
-    a.notes = static_cast<const DetokNote*>(notes_dev); a.n_notes = n_notes;
-    a.start = start_sec_dev; a.end_sec = end_sec; a.n_seg = n_segments; a.n_chan = h->cfg.n_channels; a.L = n_steps;
-    a.items = t->items; a.row_count = t->row_count; a.tie_seen = t->tie_seen;
-    a.tokens = tokens_dev; a.lengths = lengths_dev;
-    LAUNCH(launch_tok(a, static_cast<hipStream_t>(stream)));
-    return YMT3_OK;
-}
-
-// ---------------------------------------------------------------- device note metrics (include/ymt3.h)
-struct ymt3_metrics_s {
-    ymt3_ctx* owner;
-    int device;
-    ymt3_metrics_params p;
-    long long max_ref, max_est;
-    unsigned* hist = nullptr;               // [2][n_keys], then off [2][n_keys + 1] and cursor [2][n_keys]: one allocation
-    double2* t_ref = nullptr;               // [2 * max_ref]
-    double2* t_est = nullptr;               // [2 * max_est]
-    int2* win = nullptr;                    // [2 * max_ref], then stack [2 * max_ref]: one allocation
-    int* match = nullptr;                   // [2 * max_est], then visit [2 * max_est]: one allocation
-};
-
-extern "C" void ymt3_metrics_destroy(ymt3_metrics m) {
-    if (!m) return;
-    (void)hipSetDevice(m->device);
-    for (void* p : {(void*)m->hist, (void*)m->t_ref, (void*)m->t_est, (void*)m->win, (void*)m->match})
-        if (p) (void)hipFree(p);
-    delete m;
-}
-
-extern "C" int ymt3_metrics_create(ymt3_handle h, const ymt3_metrics_params* params, long long max_ref, long long max_est, ymt3_metrics* out) {
-    if (!out) FAIL(YMT3_ERR_ARG, "null output pointer");
-    *out = nullptr;
-    if (!h) FAIL(YMT3_ERR_ARG, "null handle");
-    if (!params) FAIL(YMT3_ERR_ARG, "params is NULL");
-    const ymt3_metrics_params& p = *params;
-    if (!std::isfinite(p.onset_tol) || p.onset_tol < 0) FAIL(YMT3_ERR_ARG, "onset_tol=%g must be finite and >= 0", p.onset_tol);
-    if (!std::isfinite(p.offset_min_tol) || p.offset_min_tol < 0) FAIL(YMT3_ERR_ARG, "offset_min_tol=%g must be finite and >= 0", p.offset_min_tol);
-    if (!std::isfinite(p.offset_ratio) || p.offset_ratio < 0) FAIL(YMT3_ERR_ARG, "offset_ratio=%g must be finite and >= 0", p.offset_ratio);
-    if (p.n_programs < 1) FAIL(YMT3_ERR_ARG, "n_programs=%d must be >= 1", p.n_programs);
-    if (p.n_programs > METRICS_MAX_PROGRAMS) FAIL(YMT3_ERR_UNSUPPORTED, "n_programs=%d: at most %d programs", p.n_programs, METRICS_MAX_PROGRAMS);
-    if (p.drum_program < 0 || p.drum_program >= p.n_programs) FAIL(YMT3_ERR_ARG, "drum_program=%d outside [0, n_programs=%d)", p.drum_program, p.n_programs);
-    if (max_ref < 1 || max_ref > METRICS_MAX_NOTES) FAIL(YMT3_ERR_ARG, "max_ref=%lld outside [1, %lld]", max_ref, METRICS_MAX_NOTES);
-    if (max_est < 1 || max_est > METRICS_MAX_NOTES) FAIL(YMT3_ERR_ARG, "max_est=%lld outside [1, %lld]", max_est, METRICS_MAX_NOTES);
-    HIP_TRY(hipSetDevice(h->device));
-    ymt3_metrics m = new ymt3_metrics_s{h, h->device, p, max_ref, max_est};
-    const size_t nk = (size_t)(p.n_programs + 1) * METRICS_PITCHES, keys_bytes = (2 * nk + 2 * (nk + 1) + 2 * nk) * sizeof(unsigned);
-    const size_t rs = 2 * (size_t)max_ref, es = 2 * (size_t)max_est;       // bucket slots: a counted note fills at most two
-    if (hipMalloc(reinterpret_cast<void**>(&m->hist), keys_bytes) != hipSuccess ||
-        hipMalloc(reinterpret_cast<void**>(&m->t_ref), rs * sizeof(double2)) != hipSuccess ||
-        hipMalloc(reinterpret_cast<void**>(&m->t_est), es * sizeof(double2)) != hipSuccess ||
-        hipMalloc(reinterpret_cast<void**>(&m->win), 2 * rs * sizeof(int2)) != hipSuccess ||
-        hipMalloc(reinterpret_cast<void**>(&m->match), 2 * es * sizeof(int)) != hipSuccess) {
-        ymt3_metrics_destroy(m);
-        FAIL(YMT3_ERR_HIP, "note metrics scratch (%zu bytes) could not be allocated", keys_bytes + rs * 32 + es * 24);
-    }
-    *out = m;
-    return YMT3_OK;
-}
-
-extern "C" int ymt3_note_metrics(ymt3_handle h, ymt3_metrics m, const void* ref_notes_dev, long long n_ref, const int32_t* ref_count_dev,
-                                 const void* est_notes_dev, long long n_est, const int32_t* est_count_dev, int32_t* counts_dev, void* stream) {
-    if (!h) FAIL(YMT3_ERR_ARG, "null handle");
-    if (!m) FAIL(YMT3_ERR_ARG, "null metrics object");
-    if (m->owner != h) FAIL(YMT3_ERR_ARG, "the metrics object belongs to another handle");
-    if (n_ref < 0 || n_ref > m->max_ref) FAIL(YMT3_ERR_ARG, "n_ref=%lld outside [0, max_ref=%lld]", n_ref, m->max_ref);
-    if (n_est < 0 || n_est > m->max_est) FAIL(YMT3_ERR_ARG, "n_est=%lld outside [0, max_est=%lld]", n_est, m->max_est);
-    if (!counts_dev) FAIL(YMT3_ERR_ARG, "counts_dev is NULL");
-    if (n_ref && !ref_notes_dev) FAIL(YMT3_ERR_ARG, "ref_notes_dev is NULL");
-    if (n_ref && reinterpret_cast<uintptr_t>(ref_notes_dev) % 8) FAIL(YMT3_ERR_ARG, "ref_notes_dev is not aligned to 8 bytes");
-    if (n_est && !est_notes_dev) FAIL(YMT3_ERR_ARG, "est_notes_dev is NULL");
-    if (n_est && reinterpret_cast<uintptr_t>(est_notes_dev) % 8) FAIL(YMT3_ERR_ARG, "est_notes_dev is not aligned to 8 bytes");
-    HIP_TRY(hipSetDevice(h->device));
-    const size_t nk = (size_t)(m->p.n_programs + 1) * METRICS_PITCHES;
-    MetricsArgs a{};
-    a.onset_tol = m->p.onset_tol; a.offset_min_tol = m->p.offset_min_tol; a.offset_ratio = m->p.offset_ratio;
-    a.n_programs = m->p.n_programs; a.drum_program = m->p.drum_program;
-    a.ref = static_cast<const DetokNote*>(ref_notes_dev); a.est = static_cast<const DetokNote*>(est_notes_dev);
-    a.n_ref = n_ref; a.n_est = n_est; a.ref_count = n_ref ? ref_count_dev : nullptr; a.est_count = n_est ? est_count_dev : nullptr;
-    a.max_ref = m->max_ref; a.max_est = m->max_est;
-    a.hist = m->hist; a.off = m->hist + 2 * nk; a.cursor = a.off + 2 * (nk + 1);
-    a.t_ref = m->t_ref; a.t_est = m->t_est;
-    a.win = m->win; a.stack = m->win + 2 * (size_t)m->max_ref;
-    a.match = m->match; a.visit = m->match + 2 * (size_t)m->max_est;
-    a.counts = counts_dev;
-    LAUNCH(launch_metrics(a, static_cast<hipStream_t>(stream)));
-    return YMT3_OK;
-}
-
-// ---------------------------------------------------------------- device piano roll and frame metrics (include/ymt3.h)
-struct ymt3_roll_s {
-    ymt3_ctx* owner;
-    int device;
-    ymt3_roll_params p;
-    long long max_frames;
-    uint4* bits = nullptr;                  // [2][n_programs + 1][max_frames] 128 pitch bits each
-};
-
-extern "C" void ymt3_roll_destroy(ymt3_roll r) {
-    if (!r) return;
-    (void)hipSetDevice(r->device);
-    if (r->bits) (void)hipFree(r->bits);
-    delete r;
-}
-
-extern "C" int ymt3_roll_create(ymt3_handle h, const ymt3_roll_params* params, long long max_frames, ymt3_roll* out) {
-    if (!out) FAIL(YMT3_ERR_ARG, "null output pointer");
-    *out = nullptr;
-    if (!h) FAIL(YMT3_ERR_ARG, "null handle");
-    if (!params) FAIL(YMT3_ERR_ARG, "params is NULL");
-    const ymt3_roll_params& p = *params;
-    if (!std::isfinite(p.frames_per_second) || p.frames_per_second <= 0) FAIL(YMT3_ERR_ARG, "frames_per_second=%g must be finite and > 0", p.frames_per_second);
-    if (p.n_programs < 1) FAIL(YMT3_ERR_ARG, "n_programs=%d must be >= 1", p.n_programs);
-    if (p.n_programs > ROLL_MAX_PROGRAMS) FAIL(YMT3_ERR_UNSUPPORTED, "n_programs=%d: at most %d programs", p.n_programs, ROLL_MAX_PROGRAMS);
-    if (p.drum_program < 0 || p.drum_program >= p.n_programs) FAIL(YMT3_ERR_ARG, "drum_program=%d outside [0, n_programs=%d)", p.drum_program, p.n_programs);
-    if (max_frames < 1 || max_frames > ROLL_MAX_FRAMES) FAIL(YMT3_ERR_ARG, "max_frames=%lld outside [1, %lld]", max_frames, ROLL_MAX_FRAMES);
-    HIP_TRY(hipSetDevice(h->device));
-    ymt3_roll r = new ymt3_roll_s{h, h->device, p, max_frames};
-    const size_t bytes = (size_t)2 * (p.n_programs + 1) * (size_t)max_frames * sizeof(uint4);
-    if (hipMalloc(reinterpret_cast<void**>(&r->bits), bytes) != hipSuccess) {
-        (void)hipGetLastError();
-        ymt3_roll_destroy(r);
-        FAIL(YMT3_ERR_HIP, "piano roll scratch (%zu bytes) could not be allocated", bytes);
-    }
-    *out = r;
-    return YMT3_OK;
-}
-
-// the checks the two roll calls share, and the arguments they share
-static int roll_args(ymt3_handle h, ymt3_roll r, long long n_frames, RollArgs* a) {
-    if (!h) FAIL(YMT3_ERR_ARG, "null handle");
-    if (!r) FAIL(YMT3_ERR_ARG, "null roll object");
-    if (r->owner != h) FAIL(YMT3_ERR_ARG, "the roll object belongs to another handle");
-    if (n_frames < 0 || n_frames > r->max_frames) FAIL(YMT3_ERR_ARG, "n_frames=%lld outside [0, max_frames=%lld]", n_frames, r->max_frames);
-    *a = RollArgs{};
-    a->frames_per_second = r->p.frames_per_second; a->n_programs = r->p.n_programs; a->drum_program = r->p.drum_program;
-    a->n_frames = n_frames; a->max_frames = r->max_frames; a->bits = r->bits;
-    return YMT3_OK;
-}
-
-static int roll_side(RollArgs* a, int side, const char* n_name, const char* ptr_name, const void* notes_dev, long long n, const int32_t* count_dev) {
-    if (n < 0 || n > ROLL_MAX_NOTES) FAIL(YMT3_ERR_ARG, "%s=%lld outside [0, %lld]", n_name, n, ROLL_MAX_NOTES);
-    if (n && !notes_dev) FAIL(YMT3_ERR_ARG, "%s is NULL", ptr_name);
-    if (n && reinterpret_cast<uintptr_t>(notes_dev) % 8) FAIL(YMT3_ERR_ARG, "%s is not aligned to 8 bytes", ptr_name);
-    a->notes[side] = static_cast<const DetokNote*>(notes_dev); a->n[side] = n; a->count[side] = n ? count_dev : nullptr;
-    return YMT3_OK;
-}
-
-extern "C" int ymt3_piano_roll(ymt3_handle h, ymt3_roll r, const void* notes_dev, long long n_notes, const int32_t* count_dev, long long n_frames,
-                               int first_row, int n_rows, uint8_t* roll_dev, void* stream) {
-    RollArgs a;
-    if (const int rc = roll_args(h, r, n_frames, &a)) return rc;
-    if (const int rc = roll_side(&a, 0, "n_notes", "notes_dev", notes_dev, n_notes, count_dev)) return rc;
-    if (first_row < 0 || n_rows < 1 || (long long)first_row + n_rows > r->p.n_programs + 1)
-        FAIL(YMT3_ERR_ARG, "rows [first_row=%d, first_row + n_rows=%lld) outside [0, n_programs + 1=%d]", first_row, (long long)first_row + n_rows, r->p.n_programs + 1);
-    if (!roll_dev) FAIL(YMT3_ERR_ARG, "roll_dev is NULL");
-    if (reinterpret_cast<uintptr_t>(roll_dev) % 16) FAIL(YMT3_ERR_ARG, "roll_dev is not aligned to 16 bytes");
-    HIP_TRY(hipSetDevice(h->device));
-    a.n_sides = 1; a.row0 = first_row; a.row_n = n_rows; a.roll = roll_dev;
-    LAUNCH(launch_piano_roll(a, static_cast<hipStream_t>(stream)));
-    return YMT3_OK;
-}
-
-extern "C" int ymt3_frame_metrics(ymt3_handle h, ymt3_roll r, const void* ref_notes_dev, long long n_ref, const int32_t* ref_count_dev,
-                                  const void* est_notes_dev, long long n_est, const int32_t* est_count_dev, long long n_frames, long long* counts_dev,
-                                  void* stream) {
-    RollArgs a;
-    if (const int rc = roll_args(h, r, n_frames, &a)) return rc;
-    if (const int rc = roll_side(&a, 0, "n_ref", "ref_notes_dev", ref_notes_dev, n_ref, ref_count_dev)) return rc;
-    if (const int rc = roll_side(&a, 1, "n_est", "est_notes_dev", est_notes_dev, n_est, est_count_dev)) return rc;
-    if (!counts_dev) FAIL(YMT3_ERR_ARG, "counts_dev is NULL");
-    if (reinterpret_cast<uintptr_t>(counts_dev) % 8) FAIL(YMT3_ERR_ARG, "counts_dev is not aligned to 8 bytes");
-    HIP_TRY(hipSetDevice(h->device));
-    a.n_sides = 2; a.row0 = 0; a.row_n = r->p.n_programs + 1; a.counts = counts_dev;
-    LAUNCH(launch_frame_metrics(a, static_cast<hipStream_t>(stream)));
-    return YMT3_OK;
-}
-
-// ---------------------------------------------------------------- device alignment (include/ymt3.h)
-struct ymt3_aligner_s {
-    ymt3_ctx* owner;
-    int device;
-    ymt3_align_params p;
-    long long max_frames, band;             // band = min(p.band_frames, max_frames)
-    uint4* feat = nullptr;                  // [2][max_frames][2]
-    int* edges = nullptr;                   // [align_edge_ints(max_frames)]
-    unsigned* steps = nullptr;              // [max_frames][align_step_words(band)]
-    int2* rpath = nullptr;                  // [2 * max_frames - 1]
-};
-
-extern "C" void ymt3_aligner_destroy(ymt3_aligner a) {
-    if (!a) return;
-    (void)hipSetDevice(a->device);
-    for (void* p : {(void*)a->feat, (void*)a->edges, (void*)a->steps, (void*)a->rpath})
-        if (p) (void)hipFree(p);
-    delete a;
-}
-
-extern "C" int ymt3_aligner_create(ymt3_handle h, const ymt3_align_params* params, long long max_frames, ymt3_aligner* out) {
-    if (!out) FAIL(YMT3_ERR_ARG, "null output pointer");
-    *out = nullptr;
-    if (!h) FAIL(YMT3_ERR_ARG, "null handle");
-    if (!params) FAIL(YMT3_ERR_ARG, "params is NULL");
-    const ymt3_align_params& p = *params;
-    if (!std::isfinite(p.frames_per_second) || p.frames_per_second <= 0) FAIL(YMT3_ERR_ARG, "frames_per_second=%g must be finite and > 0", p.frames_per_second);
-    if (p.n_programs < 1) FAIL(YMT3_ERR_ARG, "n_programs=%d must be >= 1", p.n_programs);
-    if (p.n_programs > ROLL_MAX_PROGRAMS) FAIL(YMT3_ERR_UNSUPPORTED, "n_programs=%d: at most %d programs", p.n_programs, ROLL_MAX_PROGRAMS);
-    if (p.drum_program < 0 || p.drum_program >= p.n_programs) FAIL(YMT3_ERR_ARG, "drum_program=%d outside [0, n_programs=%d)", p.drum_program, p.n_programs);
-    if (p.band_frames < 1) FAIL(YMT3_ERR_ARG, "band_frames=%d must be >= 1", p.band_frames);
-    if (max_frames < 1 || max_frames > ALIGN_MAX_FRAMES) FAIL(YMT3_ERR_ARG, "max_frames=%lld outside [1, %lld]", max_frames, ALIGN_MAX_FRAMES);
-    HIP_TRY(hipSetDevice(h->device));
-    ymt3_aligner a = new ymt3_aligner_s{h, h->device, p, max_frames, std::min<long long>(p.band_frames, max_frames)};
-    const size_t feat_bytes = (size_t)2 * max_frames * 2 * sizeof(uint4), edge_bytes = (size_t)align_edge_ints(max_frames) * sizeof(int);
-    const size_t step_bytes = (size_t)max_frames * align_step_words(a->band) * sizeof(unsigned), path_bytes = (size_t)(2 * max_frames - 1) * sizeof(int2);
-    if (hipMalloc(reinterpret_cast<void**>(&a->feat), feat_bytes) != hipSuccess ||
-        hipMalloc(reinterpret_cast<void**>(&a->edges), edge_bytes) != hipSuccess ||
-        hipMalloc(reinterpret_cast<void**>(&a->steps), step_bytes) != hipSuccess ||
-        hipMalloc(reinterpret_cast<void**>(&a->rpath), path_bytes) != hipSuccess) {
-        (void)hipGetLastError();
-        ymt3_aligner_destroy(a);
-        FAIL(YMT3_ERR_HIP, "alignment scratch (%zu bytes) could not be allocated", feat_bytes + edge_bytes + step_bytes + path_bytes);
-    }
-    *out = a;
-    return YMT3_OK;
-}
-
-static int align_side(AlignArgs* a, int side, const char* n_name, const char* ptr_name, const char* frames_name, const void* notes_dev, long long n,
-                      const int32_t* count_dev, long long n_frames) {
-    if (n_frames < 1 || n_frames > a->max_frames) FAIL(YMT3_ERR_ARG, "%s=%lld outside [1, max_frames=%lld]", frames_name, n_frames, a->max_frames);
-    if (n < 0 || n > ROLL_MAX_NOTES) FAIL(YMT3_ERR_ARG, "%s=%lld outside [0, %lld]", n_name, n, ROLL_MAX_NOTES);
-    if (n && !notes_dev) FAIL(YMT3_ERR_ARG, "%s is NULL", ptr_name);
-    if (n && reinterpret_cast<uintptr_t>(notes_dev) % 8) FAIL(YMT3_ERR_ARG, "%s is not aligned to 8 bytes", ptr_name);
-    a->notes[side] = static_cast<const DetokNote*>(notes_dev); a->n[side] = n; a->count[side] = n ? count_dev : nullptr; a->n_frames[side] = n_frames;
-    return YMT3_OK;
-}
-
-extern "C" int ymt3_align_notes(ymt3_handle h, ymt3_aligner al, const void* ref_notes_dev, long long n_ref, const int32_t* ref_count_dev,
-                                long long n_ref_frames, const void* est_notes_dev, long long n_est, const int32_t* est_count_dev,
-                                long long n_est_frames, int32_t* warp_dev, int32_t* path_dev, long long* result_dev, void* stream) {
-    if (!h) FAIL(YMT3_ERR_ARG, "null handle");
-    if (!al) FAIL(YMT3_ERR_ARG, "null aligner object");
-    if (al->owner != h) FAIL(YMT3_ERR_ARG, "the aligner object belongs to another handle");
-    AlignArgs a{};
-    a.frames_per_second = al->p.frames_per_second; a.n_programs = al->p.n_programs; a.drum_program = al->p.drum_program;
-    a.band_frames = al->band; a.max_frames = al->max_frames;
-    if (const int rc = align_side(&a, 0, "n_ref", "ref_notes_dev", "n_ref_frames", ref_notes_dev, n_ref, ref_count_dev, n_ref_frames)) return rc;
-    if (const int rc = align_side(&a, 1, "n_est", "est_notes_dev", "n_est_frames", est_notes_dev, n_est, est_count_dev, n_est_frames)) return rc;
-    if (!warp_dev) FAIL(YMT3_ERR_ARG, "warp_dev is NULL");
-    if (reinterpret_cast<uintptr_t>(warp_dev) % 4) FAIL(YMT3_ERR_ARG, "warp_dev is not aligned to 4 bytes");
-    if (reinterpret_cast<uintptr_t>(path_dev) % 8) FAIL(YMT3_ERR_ARG, "path_dev is not aligned to 8 bytes");
-    if (!result_dev) FAIL(YMT3_ERR_ARG, "result_dev is NULL");
-    if (reinterpret_cast<uintptr_t>(result_dev) % 8) FAIL(YMT3_ERR_ARG, "result_dev is not aligned to 8 bytes");
-    HIP_TRY(hipSetDevice(h->device));
-    a.feat = al->feat; a.edges = al->edges; a.steps = al->steps; a.rpath = al->rpath;
-    a.warp = warp_dev; a.path = path_dev; a.result = result_dev;
-    LAUNCH(launch_align(a, static_cast<hipStream_t>(stream)));
-    return YMT3_OK;
-}
-
-extern "C" int ymt3_warp_notes(ymt3_handle h, ymt3_aligner al, const void* notes_dev, long long n_notes, const int32_t* count_dev,
-                               const int32_t* warp_dev, long long n_ref_frames, void* notes_out_dev, void* stream) {
-    if (!h) FAIL(YMT3_ERR_ARG, "null handle");
-    if (!al) FAIL(YMT3_ERR_ARG, "null aligner object");
-    if (al->owner != h) FAIL(YMT3_ERR_ARG, "the aligner object belongs to another handle");
-    if (n_ref_frames < 1 || n_ref_frames > al->max_frames) FAIL(YMT3_ERR_ARG, "n_ref_frames=%lld outside [1, max_frames=%lld]", n_ref_frames, al->max_frames);
-    if (n_notes < 0 || n_notes > ROLL_MAX_NOTES) FAIL(YMT3_ERR_ARG, "n_notes=%lld outside [0, %lld]", n_notes, ROLL_MAX_NOTES);
-    if (!warp_dev) FAIL(YMT3_ERR_ARG, "warp_dev is NULL");
-    if (reinterpret_cast<uintptr_t>(warp_dev) % 4) FAIL(YMT3_ERR_ARG, "warp_dev is not aligned to 4 bytes");
-    if (n_notes && !notes_dev) FAIL(YMT3_ERR_ARG, "notes_dev is NULL");
-    if (n_notes && reinterpret_cast<uintptr_t>(notes_dev) % 8) FAIL(YMT3_ERR_ARG, "notes_dev is not aligned to 8 bytes");
-    if (n_notes && !notes_out_dev) FAIL(YMT3_ERR_ARG, "notes_out_dev is NULL");
-    if (n_notes && reinterpret_cast<uintptr_t>(notes_out_dev) % 8) FAIL(YMT3_ERR_ARG, "notes_out_dev is not aligned to 8 bytes");
-    HIP_TRY(hipSetDevice(h->device));
-    WarpNotesArgs a{al->p.frames_per_second, static_cast<const DetokNote*>(notes_dev), static_cast<DetokNote*>(notes_out_dev), n_notes,
-                    n_notes ? count_dev : nullptr, warp_dev, n_ref_frames};
-    LAUNCH(launch_warp_notes(a, static_cast<hipStream_t>(stream)));
     return YMT3_OK;
 }
 

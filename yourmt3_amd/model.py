@@ -27,451 +27,55 @@ def _ptr(t: Optional[torch.Tensor]):
     return ctypes.c_void_p(t.data_ptr()) if t is not None else None
 
 
-class DecodeConstraint:
-    """A token automaton uploaded to one model's device (YourMT3.compile_constraint; include/ymt3.h, constraints).  Freed by
-    close(), or by the model's close()."""
-
-    def __init__(self, model: "YourMT3", automaton: TokenAutomaton):
-        self.automaton = automaton
-        self.n_states = automaton.n_states
-        self._lib = model._lib
-        self._c = ctypes.c_void_p()
-        bits = np.ascontiguousarray(automaton.bits())
-        nxt = np.ascontiguousarray(automaton.next, dtype=np.int32)
-        _lib.check(self._lib.ymt3_constraint_create(model._handle, automaton.n_states, automaton.vocab, bits.ctypes.data,
-                                                    nxt.ctypes.data, ctypes.byref(self._c)))
-
-    @property
-    def ptr(self):
-        if not self._c.value:
-            raise ValueError("the constraint has been closed")
-        return self._c
-
-    def close(self):
-        if getattr(self, "_c", None) is not None and self._c.value:
-            self._lib.ymt3_constraint_destroy(self._c)
-            self._c = ctypes.c_void_p()
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
+def _records_side(device, label: str, rec: torch.Tensor, cnt: Optional[torch.Tensor] = None, count_label: str = ""):
+    """One side of a call that reads NOTE_RECORDs -> (records on the device, their number, the count tensor on the device or None)."""
+    if rec.dtype != torch.uint8 or rec.dim() != 1 or rec.numel() % NOTE_RECORD.itemsize:
+        raise ValueError(f"{label} must be a 1-D uint8 tensor of {NOTE_RECORD.itemsize}-byte NOTE_RECORDs")
+    rec = rec.to(device).contiguous()
+    if rec.numel() and rec.data_ptr() % 8:
+        rec = rec.clone()
+    if cnt is not None:
+        if cnt.dtype != torch.int32 or not cnt.numel():
+            raise ValueError(f"{count_label} must be an int32 tensor")
+        cnt = cnt.to(device)
+    return rec, rec.numel() // NOTE_RECORD.itemsize, cnt
 
 
-class Detokenizer:
-    """The device detokeniser of one model for one TaskManager (YourMT3.compile_detokenizer; include/ymt3.h, device detokeniser): the
-    token table and all scratch for up to `max_segments` segments of `max_steps` columns.  Freed by close(), or by the model's close()."""
+def _two_sides(device, ref_records, est_records, ref_count, est_count):
+    """The reference and the estimate of PianoRoll.metrics and Aligner.align."""
+    return (_records_side(device, "ref_records", ref_records, ref_count, "the count of ref_records"),
+            _records_side(device, "est_records", est_records, est_count, "the count of est_records"))
 
-    def __init__(self, model: "YourMT3", task_manager, max_segments: int, max_steps: int):
-        self.max_segments, self.max_steps = int(max_segments), int(max_steps)
-        self.n_channels = model.cfg.n_channels
+
+class _Owned:
+    """What every device object of a model shares: the C pointer, the library, a weak reference to the model, and one way to end.  A
+    subclass names its C destroy function and itself; YourMT3.close() closes every object the model created (YourMT3._owned)."""
+    _destroy = ""
+    _noun = ""                 # "the <noun> has been closed"
+    _gone = None               # "the <_gone>'s model is gone": the noun, unless the class says otherwise
+
+    def _own(self, model: "YourMT3") -> None:
+        """In every __init__, before the C create call: close() and __del__ are safe whether or not that call succeeds."""
         self._model = weakref.ref(model)
         self._lib = model._lib
         self._c = ctypes.c_void_p()
-        table = np.ascontiguousarray(task_manager.token_table(), dtype=np.uint16)
-        _lib.check(self._lib.ymt3_detok_create(model._handle, table.ctypes.data, int(table.size), int(task_manager.codec.steps_per_second),
-                                               DRUM_PROGRAM, self.max_segments, self.max_steps, ctypes.byref(self._c)))
-        self.capacity = self.max_segments * self.n_channels * self.max_steps
-        self._notes = torch.empty(self.capacity * NOTE_RECORD.itemsize, device=model.device, dtype=torch.uint8)
-        self._counts = torch.zeros(2, device=model.device, dtype=torch.int32)
-        self._states = weakref.WeakSet()
+        model._owned.add(self)
 
     @property
     def ptr(self):
         if not self._c.value:
-            raise ValueError("the detokenizer has been closed")
+            raise ValueError(f"the {self._noun} has been closed")
         return self._c
 
-    def run(self, tokens: torch.Tensor, scores: Optional[torch.Tensor], start_secs: torch.Tensor, end_sec: float):
-        """(n, K, L) ids (+ scores) on the device, (n,) f64 strictly increasing start times -> (records: NOTE_RECORD array, n_invalid)."""
-        notes, counts = self.run_device(tokens, scores, start_secs, end_sec)
-        n_notes, n_invalid = (int(v) for v in counts.cpu().tolist())
-        rec = notes[:n_notes * NOTE_RECORD.itemsize].cpu().numpy().view(NOTE_RECORD)
-        return rec, n_invalid
-
-    def run_device(self, tokens: torch.Tensor, scores: Optional[torch.Tensor], start_secs: torch.Tensor, end_sec: float):
-        """run() without the copy back -> (records: uint8 tensor of `capacity` NOTE_RECORDs, counts: int32 tensor [n_notes, n_invalid]),
-        both on the device and both the detokeniser's own buffers: the next call overwrites them.  Asynchronous; the first n_notes records
-        are valid, which NoteMetrics.run reads from `counts` on the device."""
+    def _live_model(self) -> "YourMT3":
         model = self._model()
         if model is None:
-            raise ValueError("the detokenizer's model is gone")
-        n, K, L = (int(v) for v in tokens.shape)
-        if tokens.dtype != torch.int32:
-            tokens = tokens.to(torch.int32)
-        tokens = tokens.to(model.device)
-        if L > 1 and tokens.stride(2) != 1:
-            tokens = tokens.contiguous()
-        if scores is not None:
-            scores = scores.to(model.device, torch.float32)
-            if tuple(scores.stride()) != tuple(tokens.stride()):         # one pair of strides serves both
-                tokens, scores = tokens.contiguous(), scores.contiguous()
-        starts = start_secs.to(model.device, torch.float64).contiguous()
-        _lib.check(self._lib.ymt3_detokenize(model._handle, self.ptr, _ptr(tokens), _ptr(scores), n, L, tokens.stride(0), tokens.stride(1),
-                                             _ptr(starts), float(end_sec), _ptr(self._notes), self.capacity, _ptr(self._counts),
-                                             model._stream()))
-        return self._notes, self._counts
-
-    # ------------------------------------------------------------------ incremental form (include/ymt3.h, incremental detokeniser)
-    def new_state(self, max_held: int = 16) -> "DetokState":
-        """The carried state of one stream of segments for push_device / finish_device: the notes still sounding and the drum hits not
-        yet final, at most `max_held` per (channel, drum pitch).  Freed by its close(), or with this detokeniser."""
-        model = self._model()
-        if model is None:
-            raise ValueError("the detokenizer's model is gone")
-        st = DetokState(self, model, max_held)
-        self._states.add(st)
-        return st
-
-    def push_device(self, state: "DetokState", tokens: torch.Tensor, scores: Optional[torch.Tensor], start_secs: torch.Tensor, horizon_sec: float):
-        """One push of (n, K, L) ids (+ scores) with their (n,) f64 start times; `horizon_sec` is the start of the next segment not yet
-        pushed.  -> (records: uint8 tensor of `state.capacity` NOTE_RECORDs, counts: int32 tensor [n_notes, n_invalid, n_forced]), the
-        state's own device buffers, overwritten by its next call.  Asynchronous; nothing is checked against the start times here."""
-        model = self._model()
-        if model is None:
-            raise ValueError("the detokenizer's model is gone")
-        n, K, L = (int(v) for v in tokens.shape)
-        if tokens.dtype != torch.int32:
-            tokens = tokens.to(torch.int32)
-        tokens = tokens.to(model.device)
-        if L > 1 and tokens.stride(2) != 1:
-            tokens = tokens.contiguous()
-        if scores is not None:
-            scores = scores.to(model.device, torch.float32)
-            if tuple(scores.stride()) != tuple(tokens.stride()):
-                tokens, scores = tokens.contiguous(), scores.contiguous()
-        starts = start_secs.to(model.device, torch.float64).contiguous()
-        _lib.check(self._lib.ymt3_detokenize_push(model._handle, self.ptr, state.ptr, _ptr(tokens) if n else None, _ptr(scores) if n else None,
-                                                  n, L, tokens.stride(0), tokens.stride(1), _ptr(starts) if n else None, float(horizon_sec),
-                                                  _ptr(state._notes), state.capacity, _ptr(state._counts), model._stream()))
-        return state._notes, state._counts
-
-    def finish_device(self, state: "DetokState", end_sec: float):
-        """The end of the stream: every held hit, and every sounding note closed at `end_sec` -> (records, counts) as push_device."""
-        model = self._model()
-        if model is None:
-            raise ValueError("the detokenizer's model is gone")
-        _lib.check(self._lib.ymt3_detokenize_finish(model._handle, self.ptr, state.ptr, float(end_sec), _ptr(state._notes), state.capacity,
-                                                    _ptr(state._counts), model._stream()))
-        return state._notes, state._counts
-
-    def close(self):
-        for st in list(getattr(self, "_states", ())):
-            st.close()
-        if getattr(self, "_c", None) is not None and self._c.value:
-            self._lib.ymt3_detok_destroy(self._c)
-            self._c = ctypes.c_void_p()
-            self._notes = self._counts = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
-
-
-class DetokState:
-    """What one stream of segments carries between Detokenizer.push_device calls (Detokenizer.new_state; include/ymt3.h, incremental
-    detokeniser), with the record and counter buffers its calls write."""
-
-    def __init__(self, detok: Detokenizer, model: "YourMT3", max_held: int):
-        self.max_held = int(max_held)
-        self._model = weakref.ref(model)
-        self._lib = model._lib
-        self._c = ctypes.c_void_p()
-        _lib.check(self._lib.ymt3_detok_state_create(model._handle, detok.ptr, self.max_held, ctypes.byref(self._c)))
-        self.carry = int(self._lib.ymt3_detok_state_carry(self._c))
-        self.capacity = detok.capacity + self.carry
-        self._notes = torch.empty(self.capacity * NOTE_RECORD.itemsize, device=model.device, dtype=torch.uint8)
-        self._counts = torch.zeros(3, device=model.device, dtype=torch.int32)
-        self.last_start = float("-inf")              # start of the last pushed segment (TaskManager.tokens_to_notes_stream checks against it)
-
-    @property
-    def ptr(self):
-        if not self._c.value:
-            raise ValueError("the detokenizer state has been closed")
-        return self._c
-
-    def reset(self) -> None:
-        model = self._model()
-        if model is None:
-            raise ValueError("the state's model is gone")
-        _lib.check(self._lib.ymt3_detok_state_reset(model._handle, self.ptr, model._stream()))
-        self.last_start = float("-inf")
+            raise ValueError(f"the {self._gone or self._noun}'s model is gone")
+        return model
 
     def close(self):
         if getattr(self, "_c", None) is not None and self._c.value:
-            self._lib.ymt3_detok_state_destroy(self._c)
-            self._c = ctypes.c_void_p()
-            self._notes = self._counts = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
-
-
-class Tokenizer:
-    """The device tokeniser of one model for one TaskManager (YourMT3.compile_tokenizer; include/ymt3.h, device tokeniser): the codec's
-    parameter block, the program -> channel table and all scratch for up to `max_segments` segments of `max_steps` columns.  Freed by
-    close(), or by the model's close()."""
-
-    def __init__(self, model: "YourMT3", task_manager, max_segments: int, max_steps: int):
-        self.max_segments, self.max_steps = int(max_segments), int(max_steps)
-        self.n_channels = model.cfg.n_channels
-        self._model = weakref.ref(model)
-        self._lib = model._lib
-        self._c = ctypes.c_void_p()
-        fields, chan = task_manager.tok_params()
-        self.n_programs = int(chan.size)
-        params = _lib.TokParams(**fields)
-        chan = np.ascontiguousarray(chan, dtype=np.uint8)
-        _lib.check(self._lib.ymt3_tok_create(model._handle, ctypes.byref(params), chan.ctypes.data, self.n_programs, self.max_segments,
-                                             self.max_steps, ctypes.byref(self._c)))
-
-    @property
-    def ptr(self):
-        if not self._c.value:
-            raise ValueError("the tokenizer has been closed")
-        return self._c
-
-    def run(self, records: torch.Tensor, start_secs: torch.Tensor, end_sec: float, n_steps: Optional[int] = None):
-        """NOTE_RECORD bytes on the device (uint8, a multiple of 32), (n,) f64 strictly increasing start times -> (tokens (n, K, L)
-        int32, lengths (n, K) int32) on the device, L = n_steps or max_steps.  Asynchronous: nothing is copied back."""
-        model = self._model()
-        if model is None:
-            raise ValueError("the tokenizer's model is gone")
-        if records.dtype != torch.uint8 or records.dim() != 1 or records.numel() % NOTE_RECORD.itemsize:
-            raise ValueError(f"records must be a 1-D uint8 tensor of {NOTE_RECORD.itemsize}-byte NOTE_RECORDs")
-        records = records.to(model.device).contiguous()
-        if records.numel() and records.data_ptr() % 8:
-            records = records.clone()
-        starts = start_secs.to(model.device, torch.float64).contiguous()
-        n, L = int(starts.shape[0]), int(n_steps or self.max_steps)
-        tokens = torch.empty(n, self.n_channels, L, device=model.device, dtype=torch.int32)
-        lengths = torch.empty(n, self.n_channels, device=model.device, dtype=torch.int32)
-        n_notes = records.numel() // NOTE_RECORD.itemsize
-        _lib.check(self._lib.ymt3_tokenize(model._handle, self.ptr, _ptr(records) if n_notes else None, n_notes, _ptr(starts) if n else None, n,
-                                           float(end_sec), L, _ptr(tokens) if n else None, _ptr(lengths) if n else None, model._stream()))
-        return tokens, lengths
-
-    def close(self):
-        if getattr(self, "_c", None) is not None and self._c.value:
-            self._lib.ymt3_tok_destroy(self._c)
-            self._c = ctypes.c_void_p()
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
-
-
-class NoteMetrics:
-    """The device note metrics of one model (YourMT3.compile_note_metrics; include/ymt3.h, note metrics; the rules and the host
-    specification: yourmt3_amd/metrics.py): the parameters and all scratch for up to `max_ref` reference and `max_est` estimated notes.
-    Freed by close(), or by the model's close()."""
-
-    def __init__(self, model: "YourMT3", n_programs: int, max_ref: int, max_est: int, drum_program: int = DRUM_PROGRAM, onset_tol: float = 0.05,
-                 offset_min_tol: float = 0.05, offset_ratio: float = 0.2):
-        self.n_programs, self.drum_program = int(n_programs), int(drum_program)
-        self.max_ref, self.max_est = int(max_ref), int(max_est)
-        self._model = weakref.ref(model)
-        self._lib = model._lib
-        self._c = ctypes.c_void_p()
-        params = _lib.MetricsParams(float(onset_tol), float(offset_min_tol), float(offset_ratio), self.n_programs, self.drum_program)
-        _lib.check(self._lib.ymt3_metrics_create(model._handle, ctypes.byref(params), self.max_ref, self.max_est, ctypes.byref(self._c)))
-
-    @property
-    def ptr(self):
-        if not self._c.value:
-            raise ValueError("the note metrics object has been closed")
-        return self._c
-
-    def run(self, ref_records: torch.Tensor, est_records: torch.Tensor, ref_count: Optional[torch.Tensor] = None,
-            est_count: Optional[torch.Tensor] = None) -> torch.Tensor:
-        """NOTE_RECORD bytes on the device (uint8, a multiple of 32) for both sides -> the ((n_programs + 1) * 6 + 2,) int32 counts tensor on
-        the device (metrics.NoteMetricCounts.from_flat reads it).  `ref_count` / `est_count`: int32 device tensors whose FIRST element is
-        the side's number of records, read on the device (a Detokenizer.run_device counts tensor as it is); the tensor's size is then only the
-        buffer's capacity.  Asynchronous: nothing is copied back."""
-        model = self._model()
-        if model is None:
-            raise ValueError("the note metrics object's model is gone")
-        sides = []
-        for name, rec, cnt in (("ref", ref_records, ref_count), ("est", est_records, est_count)):
-            if rec.dtype != torch.uint8 or rec.dim() != 1 or rec.numel() % NOTE_RECORD.itemsize:
-                raise ValueError(f"{name}_records must be a 1-D uint8 tensor of {NOTE_RECORD.itemsize}-byte NOTE_RECORDs")
-            rec = rec.to(model.device).contiguous()
-            if rec.numel() and rec.data_ptr() % 8:
-                rec = rec.clone()
-            if cnt is not None:
-                if cnt.dtype != torch.int32 or not cnt.numel():
-                    raise ValueError(f"{name}_count must be an int32 tensor")
-                cnt = cnt.to(model.device)
-            sides.append((rec, rec.numel() // NOTE_RECORD.itemsize, cnt))
-        counts = torch.empty((self.n_programs + 1) * 6 + 2, device=model.device, dtype=torch.int32)
-        (r, nr, rc), (e, ne, ec) = sides
-        _lib.check(self._lib.ymt3_note_metrics(model._handle, self.ptr, _ptr(r) if nr else None, nr, _ptr(rc), _ptr(e) if ne else None, ne, _ptr(ec),
-                                               _ptr(counts), model._stream()))
-        return counts
-
-    def close(self):
-        if getattr(self, "_c", None) is not None and self._c.value:
-            self._lib.ymt3_metrics_destroy(self._c)
-            self._c = ctypes.c_void_p()
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
-
-
-class PianoRoll:
-    """The device piano roll and frame metrics of one model (YourMT3.compile_piano_roll; include/ymt3.h, piano roll and frame metrics; the
-    rules and the host specification: piano_roll and frame_metrics of yourmt3_amd/metrics.py): the parameters and the bit-set scratch for up
-    to `max_frames` frames.  Freed by close(), or by the model's close()."""
-
-    def __init__(self, model: "YourMT3", n_programs: int, max_frames: int, frames_per_second: float = 100.0, drum_program: int = DRUM_PROGRAM):
-        self.n_programs, self.drum_program = int(n_programs), int(drum_program)
-        self.max_frames, self.frames_per_second = int(max_frames), float(frames_per_second)
-        self._model = weakref.ref(model)
-        self._lib = model._lib
-        self._c = ctypes.c_void_p()
-        params = _lib.RollParams(self.frames_per_second, self.n_programs, self.drum_program)
-        _lib.check(self._lib.ymt3_roll_create(model._handle, ctypes.byref(params), self.max_frames, ctypes.byref(self._c)))
-
-    @property
-    def ptr(self):
-        if not self._c.value:
-            raise ValueError("the piano roll object has been closed")
-        return self._c
-
-    def _side(self, model, name: str, rec: torch.Tensor, cnt: Optional[torch.Tensor]):
-        """-> (records on the device, their number, the count tensor on the device or None)"""
-        if rec.dtype != torch.uint8 or rec.dim() != 1 or rec.numel() % NOTE_RECORD.itemsize:
-            raise ValueError(f"{name} must be a 1-D uint8 tensor of {NOTE_RECORD.itemsize}-byte NOTE_RECORDs")
-        rec = rec.to(model.device).contiguous()
-        if rec.numel() and rec.data_ptr() % 8:
-            rec = rec.clone()
-        if cnt is not None:
-            if cnt.dtype != torch.int32 or not cnt.numel():
-                raise ValueError(f"the count of {name} must be an int32 tensor")
-            cnt = cnt.to(model.device)
-        return rec, rec.numel() // NOTE_RECORD.itemsize, cnt
-
-    def roll(self, records: torch.Tensor, n_frames: int, count: Optional[torch.Tensor] = None, rows=None) -> torch.Tensor:
-        """NOTE_RECORD bytes (uint8, a multiple of 32; on the host: uploaded) -> the (n_rows, n_frames, 128) uint8 roll on the device.
-        `rows`: None for all n_programs + 1 rows, "agnostic" for the last row only, or (first_row, n_rows).  `count`: an int32 device
-        tensor whose FIRST element is the number of records, read on the device (a Detokenizer.run_device counts tensor as it is).
-        Asynchronous: nothing is copied back."""
-        model = self._model()
-        if model is None:
-            raise ValueError("the piano roll object's model is gone")
-        if rows is None:
-            first, n_rows = 0, self.n_programs + 1
-        elif isinstance(rows, str):
-            if rows != "agnostic":
-                raise ValueError(f"rows={rows!r}: None, \"agnostic\" or (first_row, n_rows)")
-            first, n_rows = self.n_programs, 1
-        else:
-            first, n_rows = (int(v) for v in rows)
-        rec, n, cnt = self._side(model, "records", records, count)
-        out = torch.empty(max(n_rows, 0), max(int(n_frames), 0), 128, device=model.device, dtype=torch.uint8)
-        if int(n_frames) == 0 and n_rows > 0:                            # an empty roll has no buffer to hand over
-            return out
-        _lib.check(self._lib.ymt3_piano_roll(model._handle, self.ptr, _ptr(rec) if n else None, n, _ptr(cnt), int(n_frames), first, n_rows,
-                                             _ptr(out) if out.numel() else None, model._stream()))
-        return out
-
-    def metrics(self, ref_records: torch.Tensor, est_records: torch.Tensor, n_frames: int, ref_count: Optional[torch.Tensor] = None,
-                est_count: Optional[torch.Tensor] = None) -> torch.Tensor:
-        """NOTE_RECORD bytes for both sides -> the ((n_programs + 1) * 6 + 2,) int64 counts tensor on the device
-        (metrics.FrameMetricCounts.from_flat reads it).  Records and counts as roll() takes them.  Asynchronous: nothing is copied back."""
-        model = self._model()
-        if model is None:
-            raise ValueError("the piano roll object's model is gone")
-        (r, nr, rc), (e, ne, ec) = (self._side(model, name, rec, cnt) for name, rec, cnt in (("ref_records", ref_records, ref_count),
-                                                                                            ("est_records", est_records, est_count)))
-        counts = torch.empty((self.n_programs + 1) * 6 + 2, device=model.device, dtype=torch.int64)
-        _lib.check(self._lib.ymt3_frame_metrics(model._handle, self.ptr, _ptr(r) if nr else None, nr, _ptr(rc), _ptr(e) if ne else None, ne,
-                                                _ptr(ec), int(n_frames), _ptr(counts), model._stream()))
-        return counts
-
-    def close(self):
-        if getattr(self, "_c", None) is not None and self._c.value:
-            self._lib.ymt3_roll_destroy(self._c)
-            self._c = ctypes.c_void_p()
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
-
-
-class Aligner:
-    """The device alignment of one model (YourMT3.compile_aligner; include/ymt3.h, alignment; the rules and the host specification: dtw_align
-    and warp_notes of yourmt3_amd/metrics.py): the parameters and all scratch for sides of up to `max_frames` frames under a band of
-    `band_frames`.  Freed by close(), by leaving a `with` block, or by the model's close()."""
-
-    def __init__(self, model: "YourMT3", n_programs: int, max_frames: int, frames_per_second: float = 100.0, band_frames: int = 1000,
-                 drum_program: int = DRUM_PROGRAM):
-        self.n_programs, self.drum_program = int(n_programs), int(drum_program)
-        self.max_frames, self.frames_per_second, self.band_frames = int(max_frames), float(frames_per_second), int(band_frames)
-        self._model = weakref.ref(model)
-        self._lib = model._lib
-        self._c = ctypes.c_void_p()
-        params = _lib.AlignParams(self.frames_per_second, self.n_programs, self.drum_program, max(min(self.band_frames, 2 ** 31 - 1), -1))
-        _lib.check(self._lib.ymt3_aligner_create(model._handle, ctypes.byref(params), self.max_frames, ctypes.byref(self._c)))
-
-    @property
-    def ptr(self):
-        if not self._c.value:
-            raise ValueError("the aligner object has been closed")
-        return self._c
-
-    _side = PianoRoll._side
-
-    def align(self, ref_records: torch.Tensor, est_records: torch.Tensor, n_ref_frames: int, n_est_frames: int,
-              ref_count: Optional[torch.Tensor] = None, est_count: Optional[torch.Tensor] = None, path: bool = False):
-        """NOTE_RECORD bytes for both sides (uint8, a multiple of 32; on the host: uploaded) -> (warp, result) or, with `path=True`,
-        (warp, result, path), device tensors: warp (n_ref_frames,) int32; result (4,) int64 = total, path_len, skipped ref, skipped est;
-        path (n_ref_frames + n_est_frames - 1, 2) int32, of which the first path_len rows are written.  Counts as PianoRoll.metrics takes
-        them.  Asynchronous: nothing is copied back."""
-        model = self._model()
-        if model is None:
-            raise ValueError("the aligner object's model is gone")
-        (r, nr, rc), (e, ne, ec) = (self._side(model, name, rec, cnt) for name, rec, cnt in (("ref_records", ref_records, ref_count),
-                                                                                            ("est_records", est_records, est_count)))
-        na, nb = int(n_ref_frames), int(n_est_frames)
-        warp = torch.empty(max(na, 1), device=model.device, dtype=torch.int32)
-        result = torch.empty(4, device=model.device, dtype=torch.int64)
-        cells = torch.empty((max(na + nb - 1, 1), 2), device=model.device, dtype=torch.int32) if path else None
-        _lib.check(self._lib.ymt3_align_notes(model._handle, self.ptr, _ptr(r) if nr else None, nr, _ptr(rc), na, _ptr(e) if ne else None, ne,
-                                              _ptr(ec), nb, _ptr(warp), _ptr(cells), _ptr(result), model._stream()))
-        return (warp, result, cells) if path else (warp, result)
-
-    def warp(self, records: torch.Tensor, warp: torch.Tensor, count: Optional[torch.Tensor] = None) -> torch.Tensor:
-        """NOTE_RECORD bytes and the warp of align() -> the records with W applied to onset and offset (metrics.warp_notes), a new uint8
-        tensor on the device; with `count`, records past it are copied as they are.  Asynchronous."""
-        model = self._model()
-        if model is None:
-            raise ValueError("the aligner object's model is gone")
-        rec, n, cnt = self._side(model, "records", records, count)
-        if warp.dtype != torch.int32 or warp.dim() != 1 or not warp.numel():
-            raise ValueError("warp must be a 1-D int32 tensor of n_ref_frames elements")
-        warp = warp.to(model.device).contiguous()
-        out = rec.clone()
-        _lib.check(self._lib.ymt3_warp_notes(model._handle, self.ptr, _ptr(out) if n else None, n, _ptr(cnt), _ptr(warp), int(warp.numel()),
-                                             _ptr(out) if n else None, model._stream()))
-        return out
-
-    def close(self):
-        if getattr(self, "_c", None) is not None and self._c.value:
-            self._lib.ymt3_aligner_destroy(self._c)
+            getattr(self._lib, self._destroy)(self._c)
             self._c = ctypes.c_void_p()
 
     def __enter__(self):
@@ -487,10 +91,286 @@ class Aligner:
             pass
 
 
-class IngestStream:
+class DecodeConstraint(_Owned):
+    """A token automaton uploaded to one model's device (YourMT3.compile_constraint; include/ymt3.h, constraints).  Freed by
+    close(), or by the model's close()."""
+    _destroy, _noun = "ymt3_constraint_destroy", "constraint"
+
+    def __init__(self, model: "YourMT3", automaton: TokenAutomaton):
+        self.automaton = automaton
+        self.n_states = automaton.n_states
+        self._own(model)
+        bits = np.ascontiguousarray(automaton.bits())
+        nxt = np.ascontiguousarray(automaton.next, dtype=np.int32)
+        _lib.check(self._lib.ymt3_constraint_create(model._handle, automaton.n_states, automaton.vocab, bits.ctypes.data,
+                                                    nxt.ctypes.data, ctypes.byref(self._c)))
+
+
+class Detokenizer(_Owned):
+    """The device detokeniser of one model for one TaskManager (YourMT3.compile_detokenizer; include/ymt3.h, device detokeniser): the
+    token table and all scratch for up to `max_segments` segments of `max_steps` columns.  Freed by close(), or by the model's close()."""
+    _destroy, _noun = "ymt3_detok_destroy", "detokenizer"
+
+    def __init__(self, model: "YourMT3", task_manager, max_segments: int, max_steps: int):
+        self.max_segments, self.max_steps = int(max_segments), int(max_steps)
+        self.n_channels = model.cfg.n_channels
+        self._own(model)
+        table = np.ascontiguousarray(task_manager.token_table(), dtype=np.uint16)
+        _lib.check(self._lib.ymt3_detok_create(model._handle, table.ctypes.data, int(table.size), int(task_manager.codec.steps_per_second),
+                                               DRUM_PROGRAM, self.max_segments, self.max_steps, ctypes.byref(self._c)))
+        self.capacity = self.max_segments * self.n_channels * self.max_steps
+        self._notes = torch.empty(self.capacity * NOTE_RECORD.itemsize, device=model.device, dtype=torch.uint8)
+        self._counts = torch.zeros(2, device=model.device, dtype=torch.int32)
+        self._states = weakref.WeakSet()
+
+    def run(self, tokens: torch.Tensor, scores: Optional[torch.Tensor], start_secs: torch.Tensor, end_sec: float):
+        """(n, K, L) ids (+ scores) on the device, (n,) f64 strictly increasing start times -> (records: NOTE_RECORD array, n_invalid)."""
+        notes, counts = self.run_device(tokens, scores, start_secs, end_sec)
+        n_notes, n_invalid = (int(v) for v in counts.cpu().tolist())
+        rec = notes[:n_notes * NOTE_RECORD.itemsize].cpu().numpy().view(NOTE_RECORD)
+        return rec, n_invalid
+
+    @staticmethod
+    def _inputs(model, tokens: torch.Tensor, scores: Optional[torch.Tensor], start_secs: torch.Tensor):
+        """-> (tokens, scores, start times) as the C calls read them, on the device, and the tokens' n and L"""
+        n, K, L = (int(v) for v in tokens.shape)
+        if tokens.dtype != torch.int32:
+            tokens = tokens.to(torch.int32)
+        tokens = tokens.to(model.device)
+        if L > 1 and tokens.stride(2) != 1:
+            tokens = tokens.contiguous()
+        if scores is not None:
+            scores = scores.to(model.device, torch.float32)
+            if tuple(scores.stride()) != tuple(tokens.stride()):         # one pair of strides serves both
+                tokens, scores = tokens.contiguous(), scores.contiguous()
+        return tokens, scores, start_secs.to(model.device, torch.float64).contiguous(), n, L
+
+    def run_device(self, tokens: torch.Tensor, scores: Optional[torch.Tensor], start_secs: torch.Tensor, end_sec: float):
+        """run() without the copy back -> (records: uint8 tensor of `capacity` NOTE_RECORDs, counts: int32 tensor [n_notes, n_invalid]),
+        both on the device and both the detokeniser's own buffers: the next call overwrites them.  Asynchronous; the first n_notes records
+        are valid, which NoteMetrics.run reads from `counts` on the device."""
+        model = self._live_model()
+        tokens, scores, starts, n, L = self._inputs(model, tokens, scores, start_secs)
+        _lib.check(self._lib.ymt3_detokenize(model._handle, self.ptr, _ptr(tokens), _ptr(scores), n, L, tokens.stride(0), tokens.stride(1),
+                                             _ptr(starts), float(end_sec), _ptr(self._notes), self.capacity, _ptr(self._counts),
+                                             model._stream()))
+        return self._notes, self._counts
+
+    # ------------------------------------------------------------------ incremental form (include/ymt3.h, incremental detokeniser)
+    def new_state(self, max_held: int = 16) -> "DetokState":
+        """The carried state of one stream of segments for push_device / finish_device: the notes still sounding and the drum hits not
+        yet final, at most `max_held` per (channel, drum pitch).  Freed by its close(), or with this detokeniser."""
+        model = self._live_model()
+        st = DetokState(self, model, max_held)
+        self._states.add(st)
+        return st
+
+    def push_device(self, state: "DetokState", tokens: torch.Tensor, scores: Optional[torch.Tensor], start_secs: torch.Tensor, horizon_sec: float):
+        """One push of (n, K, L) ids (+ scores) with their (n,) f64 start times; `horizon_sec` is the start of the next segment not yet
+        pushed.  -> (records: uint8 tensor of `state.capacity` NOTE_RECORDs, counts: int32 tensor [n_notes, n_invalid, n_forced]), the
+        state's own device buffers, overwritten by its next call.  Asynchronous; nothing is checked against the start times here."""
+        model = self._live_model()
+        tokens, scores, starts, n, L = self._inputs(model, tokens, scores, start_secs)
+        _lib.check(self._lib.ymt3_detokenize_push(model._handle, self.ptr, state.ptr, _ptr(tokens) if n else None, _ptr(scores) if n else None,
+                                                  n, L, tokens.stride(0), tokens.stride(1), _ptr(starts) if n else None, float(horizon_sec),
+                                                  _ptr(state._notes), state.capacity, _ptr(state._counts), model._stream()))
+        return state._notes, state._counts
+
+    def finish_device(self, state: "DetokState", end_sec: float):
+        """The end of the stream: every held hit, and every sounding note closed at `end_sec` -> (records, counts) as push_device."""
+        model = self._live_model()
+        _lib.check(self._lib.ymt3_detokenize_finish(model._handle, self.ptr, state.ptr, float(end_sec), _ptr(state._notes), state.capacity,
+                                                    _ptr(state._counts), model._stream()))
+        return state._notes, state._counts
+
+    def close(self):
+        for st in list(getattr(self, "_states", ())):
+            st.close()
+        super().close()
+        self._notes = self._counts = None
+
+
+class DetokState(_Owned):
+    """What one stream of segments carries between Detokenizer.push_device calls (Detokenizer.new_state; include/ymt3.h, incremental
+    detokeniser), with the record and counter buffers its calls write."""
+    _destroy, _noun, _gone = "ymt3_detok_state_destroy", "detokenizer state", "state"
+
+    def __init__(self, detok: Detokenizer, model: "YourMT3", max_held: int):
+        self.max_held = int(max_held)
+        self._own(model)
+        _lib.check(self._lib.ymt3_detok_state_create(model._handle, detok.ptr, self.max_held, ctypes.byref(self._c)))
+        self.carry = int(self._lib.ymt3_detok_state_carry(self._c))
+        self.capacity = detok.capacity + self.carry
+        self._notes = torch.empty(self.capacity * NOTE_RECORD.itemsize, device=model.device, dtype=torch.uint8)
+        self._counts = torch.zeros(3, device=model.device, dtype=torch.int32)
+        self.last_start = float("-inf")              # start of the last pushed segment (TaskManager.tokens_to_notes_stream checks against it)
+
+    def reset(self) -> None:
+        model = self._live_model()
+        _lib.check(self._lib.ymt3_detok_state_reset(model._handle, self.ptr, model._stream()))
+        self.last_start = float("-inf")
+
+    def close(self):
+        super().close()
+        self._notes = self._counts = None
+
+
+class Tokenizer(_Owned):
+    """The device tokeniser of one model for one TaskManager (YourMT3.compile_tokenizer; include/ymt3.h, device tokeniser): the codec's
+    parameter block, the program -> channel table and all scratch for up to `max_segments` segments of `max_steps` columns.  Freed by
+    close(), or by the model's close()."""
+    _destroy, _noun = "ymt3_tok_destroy", "tokenizer"
+
+    def __init__(self, model: "YourMT3", task_manager, max_segments: int, max_steps: int):
+        self.max_segments, self.max_steps = int(max_segments), int(max_steps)
+        self.n_channels = model.cfg.n_channels
+        self._own(model)
+        fields, chan = task_manager.tok_params()
+        self.n_programs = int(chan.size)
+        params = _lib.TokParams(**fields)
+        chan = np.ascontiguousarray(chan, dtype=np.uint8)
+        _lib.check(self._lib.ymt3_tok_create(model._handle, ctypes.byref(params), chan.ctypes.data, self.n_programs, self.max_segments,
+                                             self.max_steps, ctypes.byref(self._c)))
+
+    def run(self, records: torch.Tensor, start_secs: torch.Tensor, end_sec: float, n_steps: Optional[int] = None):
+        """NOTE_RECORD bytes on the device (uint8, a multiple of 32), (n,) f64 strictly increasing start times -> (tokens (n, K, L)
+        int32, lengths (n, K) int32) on the device, L = n_steps or max_steps.  Asynchronous: nothing is copied back."""
+        model = self._live_model()
+        records, n_notes, _ = _records_side(model.device, "records", records)
+        starts = start_secs.to(model.device, torch.float64).contiguous()
+        n, L = int(starts.shape[0]), int(n_steps or self.max_steps)
+        tokens = torch.empty(n, self.n_channels, L, device=model.device, dtype=torch.int32)
+        lengths = torch.empty(n, self.n_channels, device=model.device, dtype=torch.int32)
+        _lib.check(self._lib.ymt3_tokenize(model._handle, self.ptr, _ptr(records) if n_notes else None, n_notes, _ptr(starts) if n else None, n,
+                                           float(end_sec), L, _ptr(tokens) if n else None, _ptr(lengths) if n else None, model._stream()))
+        return tokens, lengths
+
+
+class NoteMetrics(_Owned):
+    """The device note metrics of one model (YourMT3.compile_note_metrics; include/ymt3.h, note metrics; the rules and the host
+    specification: yourmt3_amd/metrics.py): the parameters and all scratch for up to `max_ref` reference and `max_est` estimated notes.
+    Freed by close(), or by the model's close()."""
+    _destroy, _noun = "ymt3_metrics_destroy", "note metrics object"
+
+    def __init__(self, model: "YourMT3", n_programs: int, max_ref: int, max_est: int, drum_program: int = DRUM_PROGRAM, onset_tol: float = 0.05,
+                 offset_min_tol: float = 0.05, offset_ratio: float = 0.2):
+        self.n_programs, self.drum_program = int(n_programs), int(drum_program)
+        self.max_ref, self.max_est = int(max_ref), int(max_est)
+        self._own(model)
+        params = _lib.MetricsParams(float(onset_tol), float(offset_min_tol), float(offset_ratio), self.n_programs, self.drum_program)
+        _lib.check(self._lib.ymt3_metrics_create(model._handle, ctypes.byref(params), self.max_ref, self.max_est, ctypes.byref(self._c)))
+
+    def run(self, ref_records: torch.Tensor, est_records: torch.Tensor, ref_count: Optional[torch.Tensor] = None,
+            est_count: Optional[torch.Tensor] = None) -> torch.Tensor:
+        """NOTE_RECORD bytes on the device (uint8, a multiple of 32) for both sides -> the ((n_programs + 1) * 6 + 2,) int32 counts tensor on
+        the device (metrics.NoteMetricCounts.from_flat reads it).  `ref_count` / `est_count`: int32 device tensors whose FIRST element is
+        the side's number of records, read on the device (a Detokenizer.run_device counts tensor as it is); the tensor's size is then only the
+        buffer's capacity.  Asynchronous: nothing is copied back."""
+        model = self._live_model()
+        r, nr, rc = _records_side(model.device, "ref_records", ref_records, ref_count, "ref_count")
+        e, ne, ec = _records_side(model.device, "est_records", est_records, est_count, "est_count")
+        counts = torch.empty((self.n_programs + 1) * 6 + 2, device=model.device, dtype=torch.int32)
+        _lib.check(self._lib.ymt3_note_metrics(model._handle, self.ptr, _ptr(r) if nr else None, nr, _ptr(rc), _ptr(e) if ne else None, ne, _ptr(ec),
+                                               _ptr(counts), model._stream()))
+        return counts
+
+
+class PianoRoll(_Owned):
+    """The device piano roll and frame metrics of one model (YourMT3.compile_piano_roll; include/ymt3.h, piano roll and frame metrics; the
+    rules and the host specification: piano_roll and frame_metrics of yourmt3_amd/metrics.py): the parameters and the bit-set scratch for up
+    to `max_frames` frames.  Freed by close(), or by the model's close()."""
+    _destroy, _noun = "ymt3_roll_destroy", "piano roll object"
+
+    def __init__(self, model: "YourMT3", n_programs: int, max_frames: int, frames_per_second: float = 100.0, drum_program: int = DRUM_PROGRAM):
+        self.n_programs, self.drum_program = int(n_programs), int(drum_program)
+        self.max_frames, self.frames_per_second = int(max_frames), float(frames_per_second)
+        self._own(model)
+        params = _lib.RollParams(self.frames_per_second, self.n_programs, self.drum_program)
+        _lib.check(self._lib.ymt3_roll_create(model._handle, ctypes.byref(params), self.max_frames, ctypes.byref(self._c)))
+
+    def roll(self, records: torch.Tensor, n_frames: int, count: Optional[torch.Tensor] = None, rows=None) -> torch.Tensor:
+        """NOTE_RECORD bytes (uint8, a multiple of 32; on the host: uploaded) -> the (n_rows, n_frames, 128) uint8 roll on the device.
+        `rows`: None for all n_programs + 1 rows, "agnostic" for the last row only, or (first_row, n_rows).  `count`: an int32 device
+        tensor whose FIRST element is the number of records, read on the device (a Detokenizer.run_device counts tensor as it is).
+        Asynchronous: nothing is copied back."""
+        model = self._live_model()
+        if rows is None:
+            first, n_rows = 0, self.n_programs + 1
+        elif isinstance(rows, str):
+            if rows != "agnostic":
+                raise ValueError(f"rows={rows!r}: None, \"agnostic\" or (first_row, n_rows)")
+            first, n_rows = self.n_programs, 1
+        else:
+            first, n_rows = (int(v) for v in rows)
+        rec, n, cnt = _records_side(model.device, "records", records, count, "the count of records")
+        out = torch.empty(max(n_rows, 0), max(int(n_frames), 0), 128, device=model.device, dtype=torch.uint8)
+        if int(n_frames) == 0 and n_rows > 0:                            # an empty roll has no buffer to hand over
+            return out
+        _lib.check(self._lib.ymt3_piano_roll(model._handle, self.ptr, _ptr(rec) if n else None, n, _ptr(cnt), int(n_frames), first, n_rows,
+                                             _ptr(out) if out.numel() else None, model._stream()))
+        return out
+
+    def metrics(self, ref_records: torch.Tensor, est_records: torch.Tensor, n_frames: int, ref_count: Optional[torch.Tensor] = None,
+                est_count: Optional[torch.Tensor] = None) -> torch.Tensor:
+        """NOTE_RECORD bytes for both sides -> the ((n_programs + 1) * 6 + 2,) int64 counts tensor on the device
+        (metrics.FrameMetricCounts.from_flat reads it).  Records and counts as roll() takes them.  Asynchronous: nothing is copied back."""
+        model = self._live_model()
+        (r, nr, rc), (e, ne, ec) = _two_sides(model.device, ref_records, est_records, ref_count, est_count)
+        counts = torch.empty((self.n_programs + 1) * 6 + 2, device=model.device, dtype=torch.int64)
+        _lib.check(self._lib.ymt3_frame_metrics(model._handle, self.ptr, _ptr(r) if nr else None, nr, _ptr(rc), _ptr(e) if ne else None, ne,
+                                                _ptr(ec), int(n_frames), _ptr(counts), model._stream()))
+        return counts
+
+
+class Aligner(_Owned):
+    """The device alignment of one model (YourMT3.compile_aligner; include/ymt3.h, alignment; the rules and the host specification: dtw_align
+    and warp_notes of yourmt3_amd/metrics.py): the parameters and all scratch for sides of up to `max_frames` frames under a band of
+    `band_frames`.  Freed by close(), by leaving a `with` block, or by the model's close()."""
+    _destroy, _noun = "ymt3_aligner_destroy", "aligner object"
+
+    def __init__(self, model: "YourMT3", n_programs: int, max_frames: int, frames_per_second: float = 100.0, band_frames: int = 1000,
+                 drum_program: int = DRUM_PROGRAM):
+        self.n_programs, self.drum_program = int(n_programs), int(drum_program)
+        self.max_frames, self.frames_per_second, self.band_frames = int(max_frames), float(frames_per_second), int(band_frames)
+        self._own(model)
+        params = _lib.AlignParams(self.frames_per_second, self.n_programs, self.drum_program, max(min(self.band_frames, 2 ** 31 - 1), -1))
+        _lib.check(self._lib.ymt3_aligner_create(model._handle, ctypes.byref(params), self.max_frames, ctypes.byref(self._c)))
+
+    def align(self, ref_records: torch.Tensor, est_records: torch.Tensor, n_ref_frames: int, n_est_frames: int,
+              ref_count: Optional[torch.Tensor] = None, est_count: Optional[torch.Tensor] = None, path: bool = False):
+        """NOTE_RECORD bytes for both sides (uint8, a multiple of 32; on the host: uploaded) -> (warp, result) or, with `path=True`,
+        (warp, result, path), device tensors: warp (n_ref_frames,) int32; result (4,) int64 = total, path_len, skipped ref, skipped est;
+        path (n_ref_frames + n_est_frames - 1, 2) int32, of which the first path_len rows are written.  Counts as PianoRoll.metrics takes
+        them.  Asynchronous: nothing is copied back."""
+        model = self._live_model()
+        (r, nr, rc), (e, ne, ec) = _two_sides(model.device, ref_records, est_records, ref_count, est_count)
+        na, nb = int(n_ref_frames), int(n_est_frames)
+        warp = torch.empty(max(na, 1), device=model.device, dtype=torch.int32)
+        result = torch.empty(4, device=model.device, dtype=torch.int64)
+        cells = torch.empty((max(na + nb - 1, 1), 2), device=model.device, dtype=torch.int32) if path else None
+        _lib.check(self._lib.ymt3_align_notes(model._handle, self.ptr, _ptr(r) if nr else None, nr, _ptr(rc), na, _ptr(e) if ne else None, ne,
+                                              _ptr(ec), nb, _ptr(warp), _ptr(cells), _ptr(result), model._stream()))
+        return (warp, result, cells) if path else (warp, result)
+
+    def warp(self, records: torch.Tensor, warp: torch.Tensor, count: Optional[torch.Tensor] = None) -> torch.Tensor:
+        """NOTE_RECORD bytes and the warp of align() -> the records with W applied to onset and offset (metrics.warp_notes), a new uint8
+        tensor on the device; with `count`, records past it are copied as they are.  Asynchronous."""
+        model = self._live_model()
+        rec, n, cnt = _records_side(model.device, "records", records, count, "the count of records")
+        if warp.dtype != torch.int32 or warp.dim() != 1 or not warp.numel():
+            raise ValueError("warp must be a 1-D int32 tensor of n_ref_frames elements")
+        warp = warp.to(model.device).contiguous()
+        out = rec.clone()
+        _lib.check(self._lib.ymt3_warp_notes(model._handle, self.ptr, _ptr(out) if n else None, n, _ptr(cnt), _ptr(warp), int(warp.numel()),
+                                             _ptr(out) if n else None, model._stream()))
+        return out
+
+
+class IngestStream(_Owned):
     """Streaming ingest of one model for one PCM format (YourMT3.compile_ingest_stream; include/ymt3.h, streaming ingest): PCM arrives
     in chunks of at most `max_chunk_frames` frames, whole segments come out as soon as their last sample is final, and all of them
     together are model.ingest() of the concatenated PCM bit for bit.  Freed by close(), or by the model's close()."""
+    _destroy, _noun = "ymt3_ingest_stream_destroy", "ingest stream"
 
     def __init__(self, model: "YourMT3", sample_rate: int, n_channels: int, dtype, max_chunk_frames: int):
         if dtype in (torch.int16, np.int16, "int16"):
@@ -501,24 +381,10 @@ class IngestStream:
             raise ValueError("pcm must be int16 or float32")
         self.sample_rate, self.n_channels, self.max_chunk_frames = int(sample_rate), int(n_channels), int(max_chunk_frames)
         self.segment_samples = model.cfg.segment_samples
-        self._model = weakref.ref(model)
-        self._lib = model._lib
-        self._c = ctypes.c_void_p()
+        self._own(model)
         self._frames = self._delivered = 0          # frames pushed, segments returned: what finish() sizes its result from
         _lib.check(self._lib.ymt3_ingest_stream_create(model._handle, self.sample_rate, self.n_channels, fmt, self.max_chunk_frames,
                                                        ctypes.byref(self._c)))
-
-    @property
-    def ptr(self):
-        if not self._c.value:
-            raise ValueError("the ingest stream has been closed")
-        return self._c
-
-    def _live_model(self):
-        model = self._model()
-        if model is None:
-            raise ValueError("the ingest stream's model is gone")
-        return model
 
     def plan(self, n_frames: int) -> int:
         """How many whole segments a push of `n_frames` frames would complete now (host arithmetic only)."""
@@ -568,17 +434,6 @@ class IngestStream:
         _lib.check(self._lib.ymt3_ingest_stream_reset(model._handle, self.ptr, model._stream()))
         self._frames = self._delivered = 0
 
-    def close(self):
-        if getattr(self, "_c", None) is not None and self._c.value:
-            self._lib.ymt3_ingest_stream_destroy(self._c)
-            self._c = ctypes.c_void_p()
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
-
 
 class YourMT3:
     def __init__(self, cfg: YMT3Config, weights: Optional[Dict[str, torch.Tensor]] = None, *, seed: int = 1234,
@@ -595,13 +450,12 @@ class YourMT3:
         ccfg = to_c(cfg, self.max_batch)
         # `blob` is immutable bytes: c_char_p points at its buffer (no second ~91 MB host copy); ymt3_create only reads it
         _lib.check(self._lib.ymt3_create(ctypes.byref(ccfg), ctypes.c_char_p(blob), len(blob), device, ctypes.byref(self._handle)))
-        # every object created for this handle that close() must free with it: constraints first, since then detokenisers, tokenisers,
-        # metrics, piano rolls and ingest streams as well (the name is the first tenant's)
-        self._constraints = weakref.WeakSet()
+        # every object created for this handle, which close() must free with it (_Owned._own adds them)
+        self._owned = weakref.WeakSet()
 
     def close(self):
-        for c in list(getattr(self, "_constraints", ())):
-            c.close()
+        for o in list(getattr(self, "_owned", ())):
+            o.close()
         if getattr(self, "_handle", None) and self._handle.value:
             self._lib.ymt3_destroy(self._handle)
             self._handle = ctypes.c_void_p()
@@ -695,66 +549,48 @@ class YourMT3:
         """Validate and upload a token automaton (yourmt3_amd/constraint.py) for decode / inference(constraint=...)."""
         if automaton.vocab != self.cfg.vocab:
             raise ValueError(f"automaton vocab {automaton.vocab} != the model's {self.cfg.vocab}")
-        c = DecodeConstraint(self, automaton)
-        self._constraints.add(c)
-        return c
+        return DecodeConstraint(self, automaton)
+
+    def _task_steps(self, task_manager, max_steps: Optional[int]) -> int:
+        """What compile_detokenizer and compile_tokenizer ask of a TaskManager -> max_steps, or its default."""
+        if task_manager.num_decoding_channels != self.cfg.n_channels:
+            raise ValueError("TaskManager channel count does not match the model's decoder")
+        if task_manager.vocab_size != self.cfg.vocab:
+            raise ValueError(f"TaskManager vocab {task_manager.vocab_size} != the model's {self.cfg.vocab}")
+        return min(task_manager.max_note_token_length, self.cfg.max_decode_len) if max_steps is None else max_steps
 
     def compile_detokenizer(self, task_manager, max_segments: int, max_steps: Optional[int] = None) -> Detokenizer:
         """The device detokeniser for `task_manager`'s vocabulary (TaskManager.tokens_to_notes_device), with scratch for `max_segments`
         segments of up to `max_steps` columns (None: the task's max_note_token_length, at most max_decode_len)."""
-        if task_manager.num_decoding_channels != self.cfg.n_channels:
-            raise ValueError("TaskManager channel count does not match the model's decoder")
-        if task_manager.vocab_size != self.cfg.vocab:
-            raise ValueError(f"TaskManager vocab {task_manager.vocab_size} != the model's {self.cfg.vocab}")
-        if max_steps is None:
-            max_steps = min(task_manager.max_note_token_length, self.cfg.max_decode_len)
-        d = Detokenizer(self, task_manager, max_segments, max_steps)
-        self._constraints.add(d)
-        return d
+        return Detokenizer(self, task_manager, max_segments, self._task_steps(task_manager, max_steps))
 
     def compile_tokenizer(self, task_manager, max_segments: int, max_steps: Optional[int] = None) -> Tokenizer:
         """The device tokeniser for `task_manager`'s vocabulary (TaskManager.notes_to_tokens_device), with scratch for `max_segments`
         segments of up to `max_steps` columns (None: the task's max_note_token_length, at most max_decode_len)."""
-        if task_manager.num_decoding_channels != self.cfg.n_channels:
-            raise ValueError("TaskManager channel count does not match the model's decoder")
-        if task_manager.vocab_size != self.cfg.vocab:
-            raise ValueError(f"TaskManager vocab {task_manager.vocab_size} != the model's {self.cfg.vocab}")
-        if max_steps is None:
-            max_steps = min(task_manager.max_note_token_length, self.cfg.max_decode_len)
-        t = Tokenizer(self, task_manager, max_segments, max_steps)
-        self._constraints.add(t)
-        return t
+        return Tokenizer(self, task_manager, max_segments, self._task_steps(task_manager, max_steps))
 
     def compile_note_metrics(self, n_programs: int, max_ref: int, max_est: int, **tolerances) -> NoteMetrics:
         """The device note metrics (include/ymt3.h, note metrics) for records of `n_programs` programs, with scratch for up to `max_ref`
         reference and `max_est` estimated notes.  `tolerances`: drum_program, onset_tol, offset_min_tol, offset_ratio (metrics.note_metrics'
         defaults)."""
-        m = NoteMetrics(self, n_programs, max_ref, max_est, **tolerances)
-        self._constraints.add(m)
-        return m
+        return NoteMetrics(self, n_programs, max_ref, max_est, **tolerances)
 
     def compile_piano_roll(self, n_programs: int, max_frames: int, frames_per_second: float = 100.0, drum_program: int = DRUM_PROGRAM) -> PianoRoll:
         """The device piano roll and frame metrics (include/ymt3.h, piano roll and frame metrics) for records of `n_programs` programs,
         with bit-set scratch for up to `max_frames` frames: 32 * (n_programs + 1) bytes per frame."""
-        r = PianoRoll(self, n_programs, max_frames, frames_per_second, drum_program)
-        self._constraints.add(r)
-        return r
+        return PianoRoll(self, n_programs, max_frames, frames_per_second, drum_program)
 
     def compile_aligner(self, n_programs: int, max_frames: int, frames_per_second: float = 100.0, band_frames: int = 1000,
                         drum_program: int = DRUM_PROGRAM) -> Aligner:
         """The device alignment (include/ymt3.h, alignment) for records of `n_programs` programs: banded DTW of a reference onto an
         estimate, each of up to `max_frames` frames, under a band of `band_frames`; the step bits take max_frames * (band_frames / 8 + 2)
         * 4 bytes."""
-        a = Aligner(self, n_programs, max_frames, frames_per_second, band_frames, drum_program)
-        self._constraints.add(a)
-        return a
+        return Aligner(self, n_programs, max_frames, frames_per_second, band_frames, drum_program)
 
     def compile_ingest_stream(self, sample_rate: int, n_channels: int = 1, dtype=torch.int16, max_chunk_frames: int = 1 << 16) -> IngestStream:
         """Streaming form of ingest() (include/ymt3.h, streaming ingest) for `n_channels`-channel PCM of `dtype` (int16 or float32) at
         `sample_rate`, pushed in chunks of at most `max_chunk_frames` frames."""
-        s = IngestStream(self, sample_rate, n_channels, dtype, max_chunk_frames)
-        self._constraints.add(s)
-        return s
+        return IngestStream(self, sample_rate, n_channels, dtype, max_chunk_frames)
 
     def _start_states(self, constraint: Optional[DecodeConstraint], start_states, B: int) -> Optional[torch.Tensor]:
         """start_states -> (B, K) int32 device tensor, or None (state 0).  (K,) is every segment's; (B, K) per segment."""
