@@ -32,7 +32,8 @@
  *     allocated after ymt3_create() except by ymt3_constraint_create() (the caller's automaton tables) and
  *     ymt3_detok_create() (the device detokeniser's scratch), ymt3_tok_create() (the device tokeniser's) and
  *     ymt3_metrics_create() (the note metrics') and ymt3_roll_create() (the piano roll's) and ymt3_ingest_stream_create() (the
- *     streaming ingest's history) and ymt3_detok_state_create() (the incremental detokeniser's state);
+ *     streaming ingest's history) and ymt3_detok_state_create() (the incremental detokeniser's state) and ymt3_velocity_create() (the note
+ *     velocities' two tables);
  *   - return value: 0 = ok, non-zero = error; the message is in ymt3_last_error()
  *     (thread local).  No exception ever crosses this boundary;
  *   - one handle per device per host thread.  No internal host threads.
@@ -666,6 +667,63 @@ int  ymt3_align_notes(ymt3_handle h, ymt3_aligner a,
                       long long* result_dev /* [4]: total, path_len, skipped ref, skipped est */, void* stream);
 int  ymt3_warp_notes(ymt3_handle h, ymt3_aligner a, const void* notes_dev, long long n_notes, const int32_t* count_dev /* may be NULL */,
                      const int32_t* warp_dev, long long n_ref_frames, void* notes_out_dev, void* stream);
+
+/* Note velocities from the audio: how loud is each note at its onset, as a MIDI velocity (YourMT3.compile_note_velocity,
+ * transcribe(velocity=True), estimate_velocities(); the specification is the host path, note_velocities of yourmt3_amd/velocity.py, in
+ * f64).  The vocabulary carries no dynamics, so the level is measured where it is: in the audio ymt3_ingest left on the device, under
+ * each record of the device detokeniser.  The rules are this repository's own.  Records are the 32 bytes { f64 onset, f64 offset, i32
+ * program, i32 pitch, i32 is_drum, f32 score } of the device detokeniser, 8-byte aligned, in any order; offset and score are not read.
+ *   - audio: audio_dev[0 .. n_audio) f32 mono at params.sample_rate, which must be cfg.sample_rate (the (n_segments, segment_samples)
+ *     buffer of ymt3_ingest, read flat).  Samples outside the range read as 0.
+ *   - tables, built in f64 by ymt3_velocity_create: the window w[k] = f32(0.5 - 0.5 cos(2 pi (k + 0.5) / W)), W = window_samples, and the
+ *     phase steps step[p][h - 1] = uint32(rint(h f(p) / sr * 2^32)), f(p) = 440 * 2^((p - 69) / 12), h = 1 .. n_harmonics, kept only where
+ *     h f(p) < sr / 2 and 0 ("absent") elsewhere.
+ *   - measured records: the onset is finite, the pitch lies in [0, 128), and the record is a drum (is_drum != 0 or program ==
+ *     drum_program) or f(pitch) < sr / 2.  Every other record gets default_velocity and the energy NaN and is counted in counts[1];
+ *     measured records are counted in counts[0].
+ *   - window position: n0 = rint(onset * sr) in f64, that one multiply, round half to even (the roll's frame rule).  The window is
+ *     always the W samples from n0, whatever the note's offset.  The clamp is done in f64 before any conversion to an integer: a window
+ *     wholly outside the audio (an onset of 1e300) is all zeros, one that crosses an end reads zeros beyond it.
+ *   - energy, with a[k] = w[k] x[n0 + k]: the window power P = 2 sum a^2 / sum w^2; a drum has E = P; a pitched note has E = 4 sum_h
+ *     |sum_k a[k] e^(-i theta)|^2 / (sum w)^2 over the harmonics present, theta = phi 2 pi / 2^32 with the exact integer phase word phi =
+ *     (step * k) mod 2^32, relative to the window start.  A steady sinusoid of amplitude A at f(p) gives E ~ A^2.  A non-finite E (a NaN
+ *     or infinite sample under the window) makes the record unmeasured after all: default_velocity, counts[1], kept out of the peak.
+ *   - peaks_dev: [2] f32 = the largest E over the measured pitched records, and over the measured drums; 0 for an empty class.
+ *   - velocity: u = peak_velocity + velocity_per_db * (10 log10(max(E, 1e-12)) - 10 log10(max(ref, 1e-12))) in f64, ref being the peak of
+ *     the record's class or, with a finite peak_db (an absolute level in dB re full scale; NaN: relative to the loudest measured note
+ *     of this call), 10^(peak_db / 10) for both classes; velocity = clamp(rint(u), min_velocity, 127).
+ *   - precision: the device sums in f32 and in another order than the specification, and takes sine and cosine from the integer phase
+ *     word in f32.  Exact: counts, the measured / unmeasured split, the bytes of unmeasured records and of records beyond the count.
+ *     Energies and peaks agree with the f64 specification within tau * max(P, 1e-12), tau as measured in DESIGN section 21; a velocity
+ *     is the specification's wherever that interval rounds to one value.  Samples so large that sum a^2 leaves the f32 range count
+ *     as non-finite.
+ *   - count pointer: count_dev (may be NULL) is read ON THE DEVICE: min(n_notes, max(*count, 0)) records are live and n_notes only sizes
+ *     the launches (notes_dev and counts_dev[0] of ymt3_detokenize in place).  Every byte of velocity_dev[0 .. n_notes) is written;
+ *     records at or beyond the count get velocity 0 (and energy NaN).
+ *   - kernels (yourmt3_amd/csrc/velocity.hip): one wave per record strides the window (coalesced rows of audio; overlapping notes meet
+ *     in L2), keeps per lane the f32 power and the real and imaginary sums of each harmonic, finishes them with a shuffle butterfly in a
+ *     fixed order, raises its class's peak with atomicMax on the bits of the non-negative finite f32 and bumps a counter; then one lane
+ *     per record maps E to the velocity in f64.  With energy_dev = NULL there is nowhere to keep E, and the second kernel measures again
+ *     (the same bits) before it maps.  No kernel waits on another workgroup.
+ * ymt3_velocity_create: synchronous; builds and uploads the two tables (4 * window_samples + 4 KB).  Checks (YMT3_ERR_ARG naming the
+ * argument): params not NULL, sample_rate == cfg.sample_rate, window_samples in [64, 4096], n_harmonics in [1, 8], velocity_per_db finite
+ * and > 0, peak_velocity in [1, 127], min_velocity in [1, peak_velocity], default_velocity in [1, 127], peak_db finite or NaN,
+ * drum_program >= 0.  The object belongs to h; ymt3_velocity_destroy frees it (NULL is a no-op), before or after the handle's destruction.
+ * ymt3_note_velocities: asynchronous on `stream`, allocates nothing, zeroes peaks_dev and counts_dev first, leaves the handle's decode state
+ * alone.  YMT3_ERR_ARG, with handle and object still usable, for n_audio < 0, a NULL audio_dev with n_audio > 0, n_notes outside
+ * [0, 2^29], a NULL notes_dev or velocity_dev with n_notes > 0, NULL peaks_dev or counts_dev, a notes_dev not aligned to 8 bytes or an
+ * audio_dev, count_dev, energy_dev, peaks_dev or counts_dev not aligned to 4.  n_notes = 0 only zeroes the outputs.  The object keeps no
+ * state between calls: several calls may be in flight on one object. */
+typedef struct ymt3_velocity_params {
+    double  velocity_per_db, peak_db;
+    int32_t sample_rate, window_samples, n_harmonics, peak_velocity, min_velocity, default_velocity, drum_program;
+} ymt3_velocity_params;
+typedef struct ymt3_velocity_s* ymt3_velocity;
+int  ymt3_velocity_create(ymt3_handle h, const ymt3_velocity_params* params, ymt3_velocity* out);
+void ymt3_velocity_destroy(ymt3_velocity v);
+int  ymt3_note_velocities(ymt3_handle h, ymt3_velocity v, const float* audio_dev, long long n_audio, const void* notes_dev, long long n_notes,
+                          const int32_t* count_dev /* may be NULL */, uint8_t* velocity_dev, float* energy_dev /* may be NULL */,
+                          float* peaks_dev /* [2] */, int32_t* counts_dev /* [2] */, void* stream);
 
 /* Measurement hook (bench.py `roofline`): decode eagerly (no graph) and bracket every kernel launch of
  * every `stride`-th step (positions stride/2, 3*stride/2, ...) with HIP events on `stream`; synchronises the stream before returning.

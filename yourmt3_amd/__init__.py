@@ -3,7 +3,7 @@
 
 __all__ = ["YMT3Config", "YourMT3", "TaskManager", "transcribe", "score_notes", "evaluate", "note_metrics", "NoteMetrics", "piano_roll", "frame_metrics",
            "FrameMetricCounts", "PianoRoll", "baseline_config", "LiveTranscriber", "NoteStream", "dtw_align", "warp_notes", "Alignment", "Aligner",
-           "align"]
+           "align", "note_velocities", "NoteVelocity", "estimate_velocities"]
 
 
 def __getattr__(name):
@@ -52,4 +52,7 @@ def __getattr__(name):
     if name == "align":
         from .transcribe import align
         return align
+    if name in ("note_velocities", "NoteVelocity", "estimate_velocities"):
+        from . import velocity
+        return getattr(velocity, name)
     raise AttributeError(name)

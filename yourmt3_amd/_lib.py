@@ -33,6 +33,7 @@ SYMBOLS = [
     "ymt3_ingest_stream_push", "ymt3_ingest_stream_finish",
     "ymt3_detok_state_create", "ymt3_detok_state_destroy", "ymt3_detok_state_reset", "ymt3_detok_state_carry",
     "ymt3_detokenize_push", "ymt3_detokenize_finish",
+    "ymt3_velocity_create", "ymt3_velocity_destroy", "ymt3_note_velocities",
 ]
 
 _lib = None
@@ -64,6 +65,12 @@ class AlignParams(ctypes.Structure):
     """ymt3_align_params of include/ymt3.h"""
     _fields_ = [("frames_per_second", ctypes.c_double), ("n_programs", ctypes.c_int32), ("drum_program", ctypes.c_int32),
                 ("band_frames", ctypes.c_int32)]
+
+
+class VelocityParams(ctypes.Structure):
+    """ymt3_velocity_params of include/ymt3.h"""
+    _fields_ = [("velocity_per_db", ctypes.c_double), ("peak_db", ctypes.c_double)] + [(n, ctypes.c_int32) for n in (
+        "sample_rate", "window_samples", "n_harmonics", "peak_velocity", "min_velocity", "default_velocity", "drum_program")]
 
 
 class YMT3Error(RuntimeError):
@@ -223,6 +230,12 @@ def load() -> ctypes.CDLL:
     lib.ymt3_detokenize_push.restype = i32
     lib.ymt3_detokenize_finish.argtypes = [vp, vp, vp, f64, vp, ll, vp, vp]
     lib.ymt3_detokenize_finish.restype = i32
+    lib.ymt3_velocity_create.argtypes = [vp, ctypes.POINTER(VelocityParams), ctypes.POINTER(vp)]
+    lib.ymt3_velocity_create.restype = i32
+    lib.ymt3_velocity_destroy.argtypes = [vp]
+    lib.ymt3_velocity_destroy.restype = None
+    lib.ymt3_note_velocities.argtypes = [vp, vp, vp, ll, vp, ll, vp, vp, vp, vp, vp, vp]
+    lib.ymt3_note_velocities.restype = i32
     for n in ("ymt3_logmel", "ymt3_encode", "ymt3_decode_greedy", "ymt3_transcribe_segments", "ymt3_test_gemm"):
         getattr(lib, n).restype = i32
     if lib.ymt3_abi_version() != 3:

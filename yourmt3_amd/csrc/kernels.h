@@ -198,6 +198,30 @@ struct WarpNotesArgs {
 };
 int launch_warp_notes(const WarpNotesArgs& a, hipStream_t stream);
 
+// ---------------------------------------------------------------- note velocities from the audio (velocity.hip; include/ymt3.h, note velocities)
+constexpr int VELOCITY_MIN_WINDOW = 64, VELOCITY_MAX_WINDOW = 4096;
+constexpr int VELOCITY_MAX_HARMONICS = 8;
+constexpr long long VELOCITY_MAX_NOTES = 1LL << 29;
+struct VelocityArgs {
+    const float* audio;                   // [n_audio] mono at the object's sample rate; samples outside read as 0
+    long long n_audio;
+    const DetokNote* notes;               // [n] the detokeniser's record; offset and score are not read
+    long long n;
+    const int32_t* count;                 // device count (or null): min(n, max(*count, 0)) records are live
+    const float* window;                  // [W]
+    const uint32_t* steps;                // [128][VELOCITY_MAX_HARMONICS] phase steps, 0 = absent
+    int W, H, drum_program;
+    double sample_rate;
+    float e_scale, p_scale;               // 4 / (sum w)^2 and 2 / sum w^2
+    double velocity_per_db, ref_energy;   // ref_energy: 10^(peak_db / 10), or NaN for the class's peak
+    int peak_velocity, min_velocity, default_velocity;
+    uint8_t* velocity;                    // [n] every byte written; 0 at or beyond the count
+    float* energy;                        // [n] or null: E, NaN where unmeasured or beyond the count
+    float* peaks;                         // [2] pitched, drums; zeroed by the caller before the launch
+    int32_t* counts;                      // [2] measured, unmeasured; zeroed by the caller before the launch
+};
+int launch_note_velocities(const VelocityArgs& a, hipStream_t stream);
+
 // ---------------------------------------------------------------- dense GEMM (gemm.hip)
 // C[M][N] (+)= A[M][K] (bf16, row stride lda) * W[N][K]^T (bf16, row stride ldw), fp32 accumulate.
 enum GemmEpilogue {

@@ -1,6 +1,6 @@
 // The note-side objects of the C ABI (include/ymt3.h): detokeniser and its incremental state, tokeniser, note metrics, piano roll / frame
-// metrics, aligner.  Host logic only: argument checks, scratch, and the launches of detok.hip, tok.hip, metrics.hip, roll.hip and align.hip.
-// Of the handle they need the device and the configuration (runtime.h).  What the six have in common is written once, at the top: the
+// metrics, aligner, note velocities.  Host logic only: argument checks, scratch, and the launches of detok.hip, tok.hip, metrics.hip, roll.hip,
+// align.hip and velocity.hip.  Of the handle they need the device and the configuration (runtime.h).  What they have in common is written once, at the top: the
 // create prologue, the owner check, the program and record-array checks, and the scratch list that both *_create and *_destroy walk.
 #include <algorithm>
 #include <cmath>
@@ -513,5 +513,89 @@ extern "C" int ymt3_warp_notes(ymt3_handle h, ymt3_aligner al, const void* notes
     WarpNotesArgs a{al->p.frames_per_second, static_cast<const DetokNote*>(notes_dev), static_cast<DetokNote*>(notes_out_dev), n_notes,
                     n_notes ? count_dev : nullptr, warp_dev, n_ref_frames};
     LAUNCH(launch_warp_notes(a, static_cast<hipStream_t>(stream)));
+    return YMT3_OK;
+}
+
+// ---------------------------------------------------------------- note velocities from the audio (include/ymt3.h)
+struct ymt3_velocity_s {
+    ymt3_handle owner;
+    int device;
+    ymt3_velocity_params p;
+    double ref_energy;                      // 10^(peak_db / 10), or NaN: the class's peak
+    float e_scale, p_scale;                 // 4 / (sum w)^2, 2 / sum w^2
+    float* window = nullptr;                // [window_samples]
+    uint32_t* steps = nullptr;              // [128][VELOCITY_MAX_HARMONICS]
+};
+
+static std::vector<Slot> slots(ymt3_velocity v, const float* window_host = nullptr, const uint32_t* steps_host = nullptr) {
+    return {slot(&v->window, (size_t)v->p.window_samples * sizeof(float), window_host),
+            slot(&v->steps, (size_t)NOTE_PITCHES * VELOCITY_MAX_HARMONICS * sizeof(uint32_t), steps_host)};
+}
+extern "C" void ymt3_velocity_destroy(ymt3_velocity v) { destroy_object(v); }
+
+extern "C" int ymt3_velocity_create(ymt3_handle h, const ymt3_velocity_params* params, ymt3_velocity* out) {
+    if (const int rc = create_prologue(reinterpret_cast<void**>(out), h, params, "params")) return rc;
+    const ymt3_velocity_params& p = *params;
+    const ymt3_config& cfg = handle_config(h);
+    if (p.sample_rate != cfg.sample_rate) FAIL(YMT3_ERR_ARG, "sample_rate=%d != the model's sample_rate=%d", p.sample_rate, cfg.sample_rate);
+    if (p.window_samples < VELOCITY_MIN_WINDOW || p.window_samples > VELOCITY_MAX_WINDOW)
+        FAIL(YMT3_ERR_ARG, "window_samples=%d outside [%d, %d]", p.window_samples, VELOCITY_MIN_WINDOW, VELOCITY_MAX_WINDOW);
+    if (p.n_harmonics < 1 || p.n_harmonics > VELOCITY_MAX_HARMONICS) FAIL(YMT3_ERR_ARG, "n_harmonics=%d outside [1, %d]", p.n_harmonics, VELOCITY_MAX_HARMONICS);
+    if (!std::isfinite(p.velocity_per_db) || p.velocity_per_db <= 0) FAIL(YMT3_ERR_ARG, "velocity_per_db=%g must be finite and > 0", p.velocity_per_db);
+    if (p.peak_velocity < 1 || p.peak_velocity > 127) FAIL(YMT3_ERR_ARG, "peak_velocity=%d outside [1, 127]", p.peak_velocity);
+    if (p.min_velocity < 1 || p.min_velocity > p.peak_velocity) FAIL(YMT3_ERR_ARG, "min_velocity=%d outside [1, peak_velocity=%d]", p.min_velocity, p.peak_velocity);
+    if (p.default_velocity < 1 || p.default_velocity > 127) FAIL(YMT3_ERR_ARG, "default_velocity=%d outside [1, 127]", p.default_velocity);
+    if (std::isinf(p.peak_db)) FAIL(YMT3_ERR_ARG, "peak_db=%g must be finite, or NaN for the loudest measured note", p.peak_db);
+    if (p.drum_program < 0) FAIL(YMT3_ERR_ARG, "drum_program=%d must be >= 0", p.drum_program);
+    // the two tables, in f64 as velocity_tables of yourmt3_amd/velocity.py builds them: the same libm calls, the sums in index order
+    const int W = p.window_samples;
+    const double sr = (double)p.sample_rate;
+    std::vector<float> window(W);
+    double sw = 0.0, sw2 = 0.0;
+    for (int k = 0; k < W; ++k) {
+        window[k] = (float)(0.5 - 0.5 * std::cos(2.0 * M_PI * (k + 0.5) / W));
+        sw += (double)window[k];
+        sw2 += (double)window[k] * (double)window[k];
+    }
+    std::vector<uint32_t> steps((size_t)NOTE_PITCHES * VELOCITY_MAX_HARMONICS, 0u);
+    for (int pitch = 0; pitch < NOTE_PITCHES; ++pitch) {
+        const double f = 440.0 * std::pow(2.0, (pitch - 69) / 12.0);
+        for (int k = 1; k <= p.n_harmonics; ++k)
+            if (k * f < sr / 2.0) steps[(size_t)pitch * VELOCITY_MAX_HARMONICS + k - 1] = (uint32_t)std::rint(k * f / sr * 4294967296.0);
+    }
+    HIP_TRY(hipSetDevice(handle_device(h)));
+    ymt3_velocity v = new ymt3_velocity_s{h, handle_device(h), p, std::isnan(p.peak_db) ? (double)NAN : std::pow(10.0, p.peak_db / 10.0),
+                                          (float)(4.0 / (sw * sw)), (float)(2.0 / sw2)};
+    return allocate_object(v, slots(v, window.data(), steps.data()), "note velocity tables", out);
+}
+
+extern "C" int ymt3_note_velocities(ymt3_handle h, ymt3_velocity v, const float* audio_dev, long long n_audio, const void* notes_dev, long long n_notes,
+                                    const int32_t* count_dev, uint8_t* velocity_dev, float* energy_dev, float* peaks_dev, int32_t* counts_dev, void* stream) {
+    if (const int rc = check_owner(h, v, "note velocity object")) return rc;
+    if (n_audio < 0) FAIL(YMT3_ERR_ARG, "n_audio=%lld must be >= 0", n_audio);
+    if (n_audio && !audio_dev) FAIL(YMT3_ERR_ARG, "audio_dev is NULL");
+    if (reinterpret_cast<uintptr_t>(audio_dev) % 4) FAIL(YMT3_ERR_ARG, "audio_dev is not aligned to 4 bytes");
+    if (const int rc = check_count("n_notes", n_notes, VELOCITY_MAX_NOTES, nullptr)) return rc;
+    if (const int rc = check_record_ptr("notes_dev", notes_dev, n_notes)) return rc;
+    if (reinterpret_cast<uintptr_t>(count_dev) % 4) FAIL(YMT3_ERR_ARG, "count_dev is not aligned to 4 bytes");
+    if (n_notes && !velocity_dev) FAIL(YMT3_ERR_ARG, "velocity_dev is NULL");
+    if (reinterpret_cast<uintptr_t>(energy_dev) % 4) FAIL(YMT3_ERR_ARG, "energy_dev is not aligned to 4 bytes");
+    if (!peaks_dev) FAIL(YMT3_ERR_ARG, "peaks_dev is NULL");
+    if (reinterpret_cast<uintptr_t>(peaks_dev) % 4) FAIL(YMT3_ERR_ARG, "peaks_dev is not aligned to 4 bytes");
+    if (!counts_dev) FAIL(YMT3_ERR_ARG, "counts_dev is NULL");
+    if (reinterpret_cast<uintptr_t>(counts_dev) % 4) FAIL(YMT3_ERR_ARG, "counts_dev is not aligned to 4 bytes");
+    HIP_TRY(hipSetDevice(v->device));
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    HIP_TRY(hipMemsetAsync(peaks_dev, 0, 2 * sizeof(float), s));
+    HIP_TRY(hipMemsetAsync(counts_dev, 0, 2 * sizeof(int32_t), s));
+    if (!n_notes) return YMT3_OK;
+    VelocityArgs a{};
+    a.audio = audio_dev; a.n_audio = n_audio; a.notes = static_cast<const DetokNote*>(notes_dev); a.n = n_notes; a.count = count_dev;
+    a.window = v->window; a.steps = v->steps; a.W = v->p.window_samples; a.H = v->p.n_harmonics; a.drum_program = v->p.drum_program;
+    a.sample_rate = (double)v->p.sample_rate; a.e_scale = v->e_scale; a.p_scale = v->p_scale;
+    a.velocity_per_db = v->p.velocity_per_db; a.ref_energy = v->ref_energy;
+    a.peak_velocity = v->p.peak_velocity; a.min_velocity = v->p.min_velocity; a.default_velocity = v->p.default_velocity;
+    a.velocity = velocity_dev; a.energy = energy_dev; a.peaks = peaks_dev; a.counts = counts_dev;
+    LAUNCH(launch_note_velocities(a, s));
     return YMT3_OK;
 }

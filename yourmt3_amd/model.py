@@ -587,6 +587,14 @@ class YourMT3:
         * 4 bytes."""
         return Aligner(self, n_programs, max_frames, frames_per_second, band_frames, drum_program)
 
+    def compile_note_velocity(self, **params):
+        """The device note velocities (include/ymt3.h, note velocities; the rules and the host specification: yourmt3_amd/velocity.py)
+        at the model's sample rate.  `params`: window_samples, n_harmonics, velocity_per_db, peak_velocity, min_velocity,
+        default_velocity, peak_db, drum_program (velocity.DEFAULTS).  -> a velocity.NoteVelocity, closed with the model like every
+        other device object."""
+        from .velocity import NoteVelocity                              # (not a name of this module: velocity.py builds on it)
+        return NoteVelocity(self, **params)
+
     def compile_ingest_stream(self, sample_rate: int, n_channels: int = 1, dtype=torch.int16, max_chunk_frames: int = 1 << 16) -> IngestStream:
         """Streaming form of ingest() (include/ymt3.h, streaming ingest) for `n_channels`-channel PCM of `dtype` (int16 or float32) at
         `sample_rate`, pushed in chunks of at most `max_chunk_frames` frames."""

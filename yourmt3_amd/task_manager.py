@@ -557,11 +557,14 @@ class TaskManager:
         return table
 
     def tokens_to_notes_device(self, model, tokens, start_secs: Sequence[float], end_sec: float, scores=None,
-                               detokenizer=None) -> Tuple[List[Note], int]:
+                               detokenizer=None, velocity=None, audio=None) -> Tuple[List[Note], int]:
         """tokens_to_notes on the device -> (notes, n_invalid).  `tokens`: (n, K, L) integer ids on `model`'s GPU (any strides whose
         last dimension is contiguous, e.g. hypothesis 0 of a beam call's (n, K, N, L)); `scores`: the matching (n, K, L) f32 token scores
         or None; `start_secs` must be strictly increasing.  `detokenizer`: a YourMT3.compile_detokenizer object to reuse (None: one is
-        made for this call and closed).  One copy back of the counters and the notes' records; confidence = exp(score) on the host."""
+        made for this call and closed).  One copy back of the counters and the notes' records; confidence = exp(score) on the host.
+        `velocity`: a YourMT3.compile_note_velocity object, with `audio` the flat f32 samples the segments were cut from, on the GPU
+        (YourMT3.ingest's buffer as it is): every note's velocity is measured on the records where they lie, their number read from the
+        detokeniser's counter on the device, and the bytes come back in the records' copy."""
         import torch
 
         starts = np.asarray(list(start_secs), np.float64)
@@ -574,13 +577,23 @@ class TaskManager:
             raise ValueError("start_secs must be strictly increasing")
         if scores is not None and tuple(scores.shape) != tuple(tokens.shape):
             raise ValueError(f"scores {tuple(scores.shape)} do not match tokens {tuple(tokens.shape)}")
+        if (velocity is None) != (audio is None):
+            raise ValueError("velocity and audio go together")
         if n == 0 or L == 0:
             return [], 0
         own = detokenizer is None
         if own:
             detokenizer = model.compile_detokenizer(self, n, L)
         try:
-            rec, n_invalid = detokenizer.run(tokens, scores, torch.from_numpy(starts), float(end_sec))
+            if velocity is None:
+                rec, n_invalid = detokenizer.run(tokens, scores, torch.from_numpy(starts), float(end_sec))
+                vel = None
+            else:
+                rec_dev, counts = detokenizer.run_device(tokens, scores, torch.from_numpy(starts), float(end_sec))
+                vel_dev = velocity.run(audio, rec_dev, count=counts)[0]
+                n_notes, n_invalid = (int(v) for v in counts.cpu().tolist())
+                both = torch.cat([rec_dev[:n_notes * NOTE_RECORD.itemsize], vel_dev[:n_notes]]).cpu().numpy()
+                rec, vel = both[:n_notes * NOTE_RECORD.itemsize].view(NOTE_RECORD), both[n_notes * NOTE_RECORD.itemsize:].tolist()
         finally:
             if own:
                 detokenizer.close()
@@ -588,6 +601,8 @@ class TaskManager:
         notes = [Note(on, off, bool(dr), pg, pt, confidence=math.exp(sc) if scored else None)
                  for on, off, pg, pt, dr, sc in zip(rec["onset"].tolist(), rec["offset"].tolist(), rec["program"].tolist(),
                                                     rec["pitch"].tolist(), rec["is_drum"].tolist(), rec["score"].astype(np.float64).tolist())]
+        if vel is not None:
+            notes = [replace(x, velocity=v) for x, v in zip(notes, vel)]
         return sorted(notes), n_invalid
 
     def tokens_to_notes_stream(self, model, detokenizer, state, tokens=None, start_secs: Sequence[float] = (), horizon_sec: float = math.inf,

@@ -14,13 +14,14 @@ from .audio import load_wav_pcm
 from .midi import read_midi_notes, write_midi
 from .metrics import FrameMetricCounts, NoteMetricCounts, to_records
 from .task_manager import DRUM_PROGRAM, NOTE_RECORD as NOTE_RECORD_DTYPE, Note, TaskManager, drop_low_confidence
+from .velocity import estimate_velocities  # noqa: F401  (its home is velocity.py; it belongs with transcribe, evaluate and align)
 
 
 def transcribe(model, audio_info: Union[str, dict, np.ndarray], task_manager: Optional[TaskManager] = None, bsz: int = 8,
                output_dir: str = ".", max_token_length: Optional[int] = None, return_notes: bool = False,
                continuous: bool = False, subtask: Optional[str] = None, confidence: bool = False,
                min_confidence: Optional[float] = None, constrained: bool = False, programs=None, num_beams: int = 1,
-               length_penalty: float = 1.0, device_detok: bool = False):
+               length_penalty: float = 1.0, device_detok: bool = False, velocity: bool = False, velocity_params: Optional[dict] = None):
     """`continuous=True` decodes the file's segments through `bsz` slots with continuous batching
     (YourMT3.inference_stream: segments leave at EOS and the next ones enter) instead of fixed batches; same ids.
     `subtask`: for a task-conditioned TaskManager (e.g. "singing_drum_v1"), the sub-task whose task tokens prompt every
@@ -36,7 +37,13 @@ def transcribe(model, audio_info: Union[str, dict, np.ndarray], task_manager: Op
     max_batch >= bsz * num_beams.  Beams do not combine with `continuous=True` here yet: YourMT3.inference_stream(num_beams=...) is the
     beam search under continuous batching, and routing this call to it is a two-line follow-up (existing tests pin the refusal).
     `device_detok=True` keeps the ids (and scores) on the GPU and turns them into notes there (TaskManager.tokens_to_notes_device;
-    include/ymt3.h, device detokeniser) in every mode above: the same notes and the same MIDI bytes, without the host's loop over every token."""
+    include/ymt3.h, device detokeniser) in every mode above: the same notes and the same MIDI bytes, without the host's loop over every token.
+    `velocity=True` fills every note's `velocity` from the audio under its onset (YourMT3.compile_note_velocity; include/ymt3.h, note
+    velocities; the rules: yourmt3_amd/velocity.py) instead of the flat 100, in every mode above and with both detokenisers: the ingested
+    buffer, still on the device, is the audio.  `velocity_params`: velocity.DEFAULTS' keys.  The notes `min_confidence` drops are gone
+    before the measurement, so the loudest KEPT note gets peak_velocity.  Off, nothing changes by a byte."""
+    if velocity_params is not None and not velocity:
+        raise ValueError("velocity_params without velocity=True")
     num_beams = int(num_beams)
     if num_beams < 1:
         raise ValueError(f"num_beams={num_beams} must be >= 1")
@@ -90,12 +97,21 @@ def transcribe(model, audio_info: Union[str, dict, np.ndarray], task_manager: Op
     finally:
         if constraint is not None:
             constraint.close()
-    if device_detok:
-        notes, _ = task_manager.tokens_to_notes_device(model, tokens, start_secs, n_samples / cfg.sample_rate, scores=scores)
-    else:
-        notes = task_manager.tokens_to_notes(batches, start_secs, end_sec=n_samples / cfg.sample_rate, score_batches=score_batches)
-    if min_confidence is not None:
-        notes = drop_low_confidence(notes, float(min_confidence))
+    measurer = model.compile_note_velocity(**(velocity_params or {})) if velocity else None
+    try:
+        in_place = measurer is not None and device_detok and min_confidence is None      # measured on the detokeniser's records where they lie
+        if device_detok:
+            notes, _ = task_manager.tokens_to_notes_device(model, tokens, start_secs, n_samples / cfg.sample_rate, scores=scores,
+                                                           **({"velocity": measurer, "audio": segments.view(-1)} if in_place else {}))
+        else:
+            notes = task_manager.tokens_to_notes(batches, start_secs, end_sec=n_samples / cfg.sample_rate, score_batches=score_batches)
+        if min_confidence is not None:
+            notes = drop_low_confidence(notes, float(min_confidence))
+        if measurer is not None and not in_place:                           # the host's notes: one upload of their records, the same kernel
+            notes = measurer.apply(segments.view(-1), notes)
+    finally:
+        if measurer is not None:
+            measurer.close()
     os.makedirs(output_dir, exist_ok=True)
     midi_path = write_midi(notes, os.path.join(output_dir, name + ".mid"))
     return (midi_path, notes) if return_notes else midi_path
@@ -163,7 +179,10 @@ class LiveTranscriber:
     independent of batch composition only within a kernel regime (DESIGN, "Rows are independent of batch composition"): the two boundaries are 2048
     (row, head) pairs, beyond which self-attention sums with 2 waves per pair, and 512 rows, from which the decode GEMMs take mid-size tiles.
     A live session decodes a few segments per call and a file transcription up to `bsz`; the ids agree bit for bit as long as both stay on
-    the same side of both boundaries."""
+    the same side of both boundaries.
+
+    Note velocities (transcribe(velocity=True)) are not part of a live session: a pitched note becomes final when it ends, long after the
+    audio of its onset has left the device.  estimate_velocities() on the recording puts them onto the session's MIDI file afterwards."""
 
     def __init__(self, model, sample_rate: int, n_channels: int = 1, dtype=torch.int16, task_manager: Optional[TaskManager] = None,
                  max_chunk_frames: int = 1 << 16, bsz: Optional[int] = None, max_token_length: Optional[int] = None,
