@@ -725,6 +725,56 @@ int  ymt3_note_velocities(ymt3_handle h, ymt3_velocity v, const float* audio_dev
                           const int32_t* count_dev /* may be NULL */, uint8_t* velocity_dev, float* energy_dev /* may be NULL */,
                           float* peaks_dev /* [2] */, int32_t* counts_dev /* [2] */, void* stream);
 
+/* ---- beat tracking over note records ------------------------------------------------------------------------------------------
+ * The vocabulary carries no metre; the notes do: their onsets are an onset-strength signal.  A ymt3_beats object finds a tempo per
+ * window and the beats' frames from records on the device, and gives every record its position in beats, as MIDI ticks.  The rules are
+ * this project's own (an autocorrelation tempogram and a dynamic-programming beat tracker); the host specification is
+ * track_beats / beat_positions of yourmt3_amd/beats.py, and every output equals it bit for bit: everything is an integer, the two tables
+ * are built on the host in f64, and the position is one f64 expression without contraction.  Integer divisions below are floor divisions.
+ *
+ * Parameters (ymt3_beats_create refuses, YMT3_ERR_ARG, what is outside): frames_per_second, bpm_min <= bpm_max, bpm_prior, prior_octaves,
+ * tightness (<= 10000): finite and > 0; lag_min = ceil(60 fps / bpm_max) and lag_max = floor(60 fps / bpm_min) with
+ * 4 <= lag_min <= lag_max <= 512; 2 lag_max <= window_frames (Wn) <= 2048; 1 <= hop_frames (Hn) <= Wn; 0 <= lag_step_max (D) <= 512;
+ * 1 <= onset_cap <= 255; 1 <= n_programs <= 256, drum_program in [0, n_programs); 1 <= max_frames <= 2^20, and
+ * ceil(max_frames / Hn) Wn (4 onset_cap)^2 65535 <= 2^62, which bounds every int64 sum below.
+ *   tables    prior[L] = rint(65535 exp(-0.5 (log2(L / L0) / prior_octaves)^2)), L0 = 60 fps / bpm_prior;
+ *             pen[t][d] = rint(tightness 1024 ln(d / t)^2) for t in [lag_min, lag_max], d in [ceil(t / 2), 2 t].
+ *   envelope  a record counts by the rule of the note metrics (NaN onset, pitch outside [0, 128), program outside [0, n_programs), a
+ *             pitched note with a NaN offset: skipped).  A counted record adds 1 to e[F], F = rint(onset fps) in f64, if 0 <= F < n_frames.
+ *             e[f] = min(e[f], onset_cap); s[f] = e[f-1] + 2 e[f] + e[f+1], zeros outside [0, n_frames).
+ *   tempogram nW = max(1, ceil(n_frames / Hn)); window w: c = w Hn + Hn / 2, f in [c - Wn / 2, c + Wn / 2) within [0, n_frames);
+ *             A[w][L] = sum of s[f] s[f+L] over the window's f with f + L < n_frames; T[w][L] = A[w][L] prior[L].
+ *   tempo     V[0] = T[0]; V[w][L] = T[w][L] + max of V[w-1][L'] over |L' - L| <= D inside the lag range, ties to the nearest L', then
+ *             the smaller.  The end is the smallest L with V[nW-1][L] maximal; tempo[w] is the lag followed back from it.
+ *   beats     t(f) = tempo[min(f / Hn, nW - 1)]; best(f) = max of C[p] - pen[t][f-p] over p in [max(0, f - 2 t), f - ceil(t / 2)]; with
+ *             best > 0 back[f] is the LARGEST such p, else best = 0 and back[f] = -1; C[f] = 1024 s[f] + best.  The last beat is the
+ *             SMALLEST f with C[f] maximal; the beats are the chain of back[] from it, ascending; max C = 0: no beats.
+ * ymt3_track_beats: notes_dev / n_notes / count_dev as in the note metrics.  beats_dev[0 .. n_beats) are written, the rest is left alone;
+ * max_beats >= n_frames / ceil(lag_min / 2) + 1 is required.  tempo_dev (may be NULL): nW lags, frames per beat.  result_dev[4]: n_beats,
+ * max C, the maximum of V's last row, skipped records.
+ * ymt3_beat_positions: ticks_dev[i] = {onset tick, offset tick} of record i at 480 ticks per beat; the number of beats K is read from
+ * result_dev[0] on the device.  With K >= 2: x = t fps, i the largest index with b[i] <= x clamped to [0, K-2],
+ * n0 = ceil(b[0] / (b[1] - b[0])), pos = (n0 + i) + (x - b[i]) / (b[i+1] - b[i]); Q = divisions, or 480 for divisions = 0 (divisions
+ * divides 480); tick = clamp(rint(pos Q), 0, 2^20) (480 / Q), rint half to even.  With K < 2: tick = clamp(rint(t 960), 0, 2^29) and Q = 480.
+ * A counted pitched record's offset tick is at least its onset tick + 480 / Q.  A NaN time, an uncounted record, a record at or beyond
+ * the count: -1.  Every entry of ticks_dev is written.
+ * Both calls are asynchronous on `stream`, allocate nothing, read nothing back and leave the handle's decode state alone.  The object's
+ * scratch is used by ymt3_track_beats: calls on one object are ordered by their stream.  Only beats are estimated: no bars, no time
+ * signature, no downbeats. */
+typedef struct ymt3_beat_params {
+    double  frames_per_second, bpm_min, bpm_max, bpm_prior, prior_octaves, tightness;
+    int32_t window_frames, hop_frames, lag_step_max, onset_cap, n_programs, drum_program;
+} ymt3_beat_params;
+typedef struct ymt3_beats_s* ymt3_beats;
+int  ymt3_beats_create(ymt3_handle h, const ymt3_beat_params* params, long long max_frames, ymt3_beats* out);
+void ymt3_beats_destroy(ymt3_beats b);
+int  ymt3_track_beats(ymt3_handle h, ymt3_beats b, const void* notes_dev, long long n_notes, const int32_t* count_dev /* may be NULL */,
+                      long long n_frames, int32_t* beats_dev, long long max_beats, int32_t* tempo_dev /* may be NULL */,
+                      long long* result_dev /* [4] */, void* stream);
+int  ymt3_beat_positions(ymt3_handle h, ymt3_beats b, const int32_t* beats_dev, const long long* result_dev, const void* notes_dev,
+                         long long n_notes, const int32_t* count_dev /* may be NULL */, int divisions, int32_t* ticks_dev /* [n_notes][2] */,
+                         void* stream);
+
 /* Measurement hook (bench.py `roofline`): decode eagerly (no graph) and bracket every kernel launch of
  * every `stride`-th step (positions stride/2, 3*stride/2, ...) with HIP events on `stream`; synchronises the stream before returning.
  * Classes: 0 qkv+cache GEMM, 1 self-attention, 2 self O-proj, 3 cross Q GEMM, 4 cross-attention,

@@ -3,7 +3,7 @@
 
 __all__ = ["YMT3Config", "YourMT3", "TaskManager", "transcribe", "score_notes", "evaluate", "note_metrics", "NoteMetrics", "piano_roll", "frame_metrics",
            "FrameMetricCounts", "PianoRoll", "baseline_config", "LiveTranscriber", "NoteStream", "dtw_align", "warp_notes", "Alignment", "Aligner",
-           "align", "note_velocities", "NoteVelocity", "estimate_velocities"]
+           "align", "note_velocities", "NoteVelocity", "estimate_velocities", "track_beats", "beat_positions", "BeatTracker", "estimate_beats"]
 
 
 def __getattr__(name):
@@ -55,4 +55,7 @@ def __getattr__(name):
     if name in ("note_velocities", "NoteVelocity", "estimate_velocities"):
         from . import velocity
         return getattr(velocity, name)
+    if name in ("track_beats", "beat_positions", "BeatTracker", "estimate_beats"):
+        from . import beats
+        return getattr(beats, name)
     raise AttributeError(name)

@@ -34,6 +34,7 @@ SYMBOLS = [
     "ymt3_detok_state_create", "ymt3_detok_state_destroy", "ymt3_detok_state_reset", "ymt3_detok_state_carry",
     "ymt3_detokenize_push", "ymt3_detokenize_finish",
     "ymt3_velocity_create", "ymt3_velocity_destroy", "ymt3_note_velocities",
+    "ymt3_beats_create", "ymt3_beats_destroy", "ymt3_track_beats", "ymt3_beat_positions",
 ]
 
 _lib = None
@@ -71,6 +72,12 @@ class VelocityParams(ctypes.Structure):
     """ymt3_velocity_params of include/ymt3.h"""
     _fields_ = [("velocity_per_db", ctypes.c_double), ("peak_db", ctypes.c_double)] + [(n, ctypes.c_int32) for n in (
         "sample_rate", "window_samples", "n_harmonics", "peak_velocity", "min_velocity", "default_velocity", "drum_program")]
+
+
+class BeatParams(ctypes.Structure):
+    """ymt3_beat_params of include/ymt3.h"""
+    _fields_ = [(n, ctypes.c_double) for n in ("frames_per_second", "bpm_min", "bpm_max", "bpm_prior", "prior_octaves", "tightness")] + [
+        (n, ctypes.c_int32) for n in ("window_frames", "hop_frames", "lag_step_max", "onset_cap", "n_programs", "drum_program")]
 
 
 class YMT3Error(RuntimeError):
@@ -236,6 +243,14 @@ def load() -> ctypes.CDLL:
     lib.ymt3_velocity_destroy.restype = None
     lib.ymt3_note_velocities.argtypes = [vp, vp, vp, ll, vp, ll, vp, vp, vp, vp, vp, vp]
     lib.ymt3_note_velocities.restype = i32
+    lib.ymt3_beats_create.argtypes = [vp, ctypes.POINTER(BeatParams), ll, ctypes.POINTER(vp)]
+    lib.ymt3_beats_create.restype = i32
+    lib.ymt3_beats_destroy.argtypes = [vp]
+    lib.ymt3_beats_destroy.restype = None
+    lib.ymt3_track_beats.argtypes = [vp, vp, vp, ll, vp, ll, vp, ll, vp, vp, vp]
+    lib.ymt3_track_beats.restype = i32
+    lib.ymt3_beat_positions.argtypes = [vp, vp, vp, vp, vp, ll, vp, i32, vp, vp]
+    lib.ymt3_beat_positions.restype = i32
     for n in ("ymt3_logmel", "ymt3_encode", "ymt3_decode_greedy", "ymt3_transcribe_segments", "ymt3_test_gemm"):
         getattr(lib, n).restype = i32
     if lib.ymt3_abi_version() != 3:

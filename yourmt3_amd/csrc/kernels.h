@@ -222,6 +222,50 @@ struct VelocityArgs {
 };
 int launch_note_velocities(const VelocityArgs& a, hipStream_t stream);
 
+// ---------------------------------------------------------------- beat tracking over note records (beats.hip; include/ymt3.h, beat tracking)
+constexpr long long BEAT_MAX_FRAMES = 1LL << 20;
+constexpr long long BEAT_MAX_NOTES = 1LL << 29;
+constexpr int BEAT_MIN_LAG = 4, BEAT_MAX_LAG = 512, BEAT_MAX_WINDOW = 2048, BEAT_MAX_PROGRAMS = 256;
+constexpr int BEAT_TICKS_PER_BEAT = 480;
+constexpr int BEAT_RING = 2048;                                        // the power of two >= 2 * BEAT_MAX_LAG + BEAT_MAX_LAG / 2
+__host__ __device__ inline long long beat_windows(long long n_frames, int hop) { const long long w = (n_frames + hop - 1) / hop; return w > 1 ? w : 1; }
+__host__ __device__ inline long long beat_max_beats(long long n_frames, int lag_min) { return n_frames / ((lag_min + 1) / 2) + 1; }
+struct BeatArgs {
+    double frames_per_second;
+    int n_programs, drum_program;
+    int lag_min, lag_max, window, hop, lag_step, onset_cap;
+    const DetokNote* notes;               // [n] the detokeniser's record; offset is read only by the counting rule
+    long long n;
+    const int32_t* count;                 // device count (or null): min(n, max(*count, 0)) records are live
+    long long n_frames;                   // in [1, the object's max_frames]
+    const int32_t* prior;                 // [nL], nL = lag_max - lag_min + 1
+    const int32_t* pen;                   // [nL][2 * lag_max + 1]: row t - lag_min, column d
+    unsigned* env;                        // [max_frames] onsets per frame
+    unsigned short* smooth;               // [max_frames] s
+    long long* tgram;                     // [nW][nL] T
+    unsigned short* lag_back;             // [nW][nL] the tempo path's back-pointers, as lag indices
+    int32_t* lags;                        // [nW] the tempo path, read by the beat kernel
+    int32_t* back;                        // [max_frames]
+    int32_t* rbeats;                      // [beat_max_beats(max_frames)] the chain, last beat first
+    int32_t* beats;                       // [max_beats]: the first n_beats are written
+    long long max_beats;
+    int32_t* tempo;                       // [nW] or null
+    long long* result;                    // [4]: n_beats, max C, max V, skipped
+};
+int launch_track_beats(const BeatArgs& a, hipStream_t stream);
+struct BeatPositionArgs {
+    double frames_per_second;
+    int n_programs, drum_program, divisions;
+    const int32_t* beats;                 // [result[0]] ascending
+    const long long* result;              // track_beats' result: [0] is read
+    long long max_beats;                  // what [0] is clamped to: beat_max_beats(the object's max_frames)
+    const DetokNote* notes;               // [n]
+    long long n;
+    const int32_t* count;                 // device count (or null)
+    int32_t* ticks;                       // [n][2] every entry written; -1 at or beyond the count
+};
+int launch_beat_positions(const BeatPositionArgs& a, hipStream_t stream);
+
 // ---------------------------------------------------------------- dense GEMM (gemm.hip)
 // C[M][N] (+)= A[M][K] (bf16, row stride lda) * W[N][K]^T (bf16, row stride ldw), fp32 accumulate.
 enum GemmEpilogue {

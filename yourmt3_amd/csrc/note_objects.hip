@@ -1,6 +1,6 @@
 // The note-side objects of the C ABI (include/ymt3.h): detokeniser and its incremental state, tokeniser, note metrics, piano roll / frame
-// metrics, aligner, note velocities.  Host logic only: argument checks, scratch, and the launches of detok.hip, tok.hip, metrics.hip, roll.hip,
-// align.hip and velocity.hip.  Of the handle they need the device and the configuration (runtime.h).  What they have in common is written once, at the top: the
+// metrics, aligner, note velocities, beat tracker.  Host logic only: argument checks, scratch, and the launches of detok.hip, tok.hip, metrics.hip, roll.hip,
+// align.hip, velocity.hip and beats.hip.  Of the handle they need the device and the configuration (runtime.h).  What they have in common is written once, at the top: the
 // create prologue, the owner check, the program and record-array checks, and the scratch list that both *_create and *_destroy walk.
 #include <algorithm>
 #include <cmath>
@@ -597,5 +597,122 @@ extern "C" int ymt3_note_velocities(ymt3_handle h, ymt3_velocity v, const float*
     a.peak_velocity = v->p.peak_velocity; a.min_velocity = v->p.min_velocity; a.default_velocity = v->p.default_velocity;
     a.velocity = velocity_dev; a.energy = energy_dev; a.peaks = peaks_dev; a.counts = counts_dev;
     LAUNCH(launch_note_velocities(a, s));
+    return YMT3_OK;
+}
+
+// ---------------------------------------------------------------- beat tracking over note records (include/ymt3.h)
+struct ymt3_beats_s {
+    ymt3_handle owner;
+    int device;
+    ymt3_beat_params p;
+    long long max_frames;
+    int lag_min, lag_max;
+    int32_t* prior = nullptr;               // [nL]
+    int32_t* pen = nullptr;                 // [nL][2 * lag_max + 1]
+    unsigned* env = nullptr;                // [max_frames]
+    unsigned short* smooth = nullptr;       // [max_frames]
+    long long* tgram = nullptr;             // [beat_windows(max_frames)][nL]
+    unsigned short* lag_back = nullptr;     // the same
+    int32_t* lags = nullptr;                // [beat_windows(max_frames)]
+    int32_t* back = nullptr;                // [max_frames]
+    int32_t* rbeats = nullptr;              // [beat_max_beats(max_frames)]
+};
+
+static std::vector<Slot> slots(ymt3_beats b, const int32_t* prior_host = nullptr, const int32_t* pen_host = nullptr) {
+    const size_t nL = (size_t)(b->lag_max - b->lag_min + 1), F = (size_t)b->max_frames, nW = (size_t)beat_windows(b->max_frames, b->p.hop_frames);
+    return {slot(&b->prior, nL * sizeof(int32_t), prior_host), slot(&b->pen, nL * (2 * (size_t)b->lag_max + 1) * sizeof(int32_t), pen_host),
+            slot(&b->env, F * sizeof(unsigned)), slot(&b->smooth, F * sizeof(unsigned short)), slot(&b->tgram, nW * nL * sizeof(long long)),
+            slot(&b->lag_back, nW * nL * sizeof(unsigned short)), slot(&b->lags, nW * sizeof(int32_t)), slot(&b->back, F * sizeof(int32_t)),
+            slot(&b->rbeats, (size_t)beat_max_beats(b->max_frames, b->lag_min) * sizeof(int32_t))};
+}
+extern "C" void ymt3_beats_destroy(ymt3_beats b) { destroy_object(b); }
+
+extern "C" int ymt3_beats_create(ymt3_handle h, const ymt3_beat_params* params, long long max_frames, ymt3_beats* out) {
+    if (const int rc = create_prologue(reinterpret_cast<void**>(out), h, params, "params")) return rc;
+    const ymt3_beat_params& p = *params;
+    const struct { const char* name; double v; } positive[] = {{"frames_per_second", p.frames_per_second}, {"bpm_min", p.bpm_min}, {"bpm_max", p.bpm_max},
+                                                               {"bpm_prior", p.bpm_prior}, {"prior_octaves", p.prior_octaves}, {"tightness", p.tightness}};
+    for (const auto& q : positive)
+        if (!std::isfinite(q.v) || q.v <= 0) FAIL(YMT3_ERR_ARG, "%s=%g must be finite and > 0", q.name, q.v);
+    if (p.bpm_min > p.bpm_max) FAIL(YMT3_ERR_ARG, "bpm_min=%g above bpm_max=%g", p.bpm_min, p.bpm_max);
+    if (p.tightness > 10000) FAIL(YMT3_ERR_ARG, "tightness=%g above 10000", p.tightness);
+    const double lo = std::ceil(60.0 * p.frames_per_second / p.bpm_max), hi = std::floor(60.0 * p.frames_per_second / p.bpm_min);
+    if (!(lo >= BEAT_MIN_LAG && lo <= hi && hi <= BEAT_MAX_LAG))
+        FAIL(YMT3_ERR_ARG, "lag_min=%g, lag_max=%g (60 frames_per_second / bpm_max, / bpm_min) must satisfy %d <= lag_min <= lag_max <= %d", lo, hi, BEAT_MIN_LAG, BEAT_MAX_LAG);
+    const int lag_min = (int)lo, lag_max = (int)hi;
+    if (p.window_frames < 2 * lag_max || p.window_frames > BEAT_MAX_WINDOW)
+        FAIL(YMT3_ERR_ARG, "window_frames=%d outside [2 * lag_max=%d, %d]", p.window_frames, 2 * lag_max, BEAT_MAX_WINDOW);
+    if (p.hop_frames < 1 || p.hop_frames > p.window_frames) FAIL(YMT3_ERR_ARG, "hop_frames=%d outside [1, window_frames=%d]", p.hop_frames, p.window_frames);
+    if (p.lag_step_max < 0 || p.lag_step_max > BEAT_MAX_LAG) FAIL(YMT3_ERR_ARG, "lag_step_max=%d outside [0, %d]", p.lag_step_max, BEAT_MAX_LAG);
+    if (p.onset_cap < 1 || p.onset_cap > 255) FAIL(YMT3_ERR_ARG, "onset_cap=%d outside [1, 255]", p.onset_cap);
+    if (const int rc = check_programs(p.n_programs, p.drum_program, BEAT_MAX_PROGRAMS, "")) return rc;
+    if (max_frames < 1 || max_frames > BEAT_MAX_FRAMES) FAIL(YMT3_ERR_ARG, "max_frames=%lld outside [1, %lld]", max_frames, BEAT_MAX_FRAMES);
+    // the tempo path adds one T per window: nW * Wn * (4 cap)^2 * 65535 bounds every sum; in integers, as the
+    // specification checks it: the first three factors stay below 2^52
+    const unsigned long long s_max = 4ull * p.onset_cap, terms = (unsigned long long)beat_windows(max_frames, p.hop_frames) * p.window_frames * s_max * s_max;
+    if (terms > (1ull << 62) / 65535ull)
+        FAIL(YMT3_ERR_ARG, "max_frames=%lld with hop_frames=%d: the tempo path's sums could pass 2^62", max_frames, p.hop_frames);
+    // the two tables, in f64 as beat_tables of yourmt3_amd/beats.py builds them: the same libm calls, element by element
+    const int nL = lag_max - lag_min + 1, row = 2 * lag_max + 1;
+    const double l0 = 60.0 * p.frames_per_second / p.bpm_prior;
+    std::vector<int32_t> prior(nL), pen((size_t)nL * row, 0);
+    for (int lag = lag_min; lag <= lag_max; ++lag) {
+        const double z = std::log2(lag / l0) / p.prior_octaves;
+        prior[lag - lag_min] = (int32_t)std::rint(65535.0 * std::exp(-0.5 * (z * z)));
+        for (int d = (lag + 1) / 2; d <= 2 * lag; ++d) {
+            const double g = std::log((double)d / lag);
+            pen[(size_t)(lag - lag_min) * row + d] = (int32_t)std::rint(p.tightness * 1024.0 * (g * g));
+        }
+    }
+    HIP_TRY(hipSetDevice(handle_device(h)));
+    ymt3_beats b = new ymt3_beats_s{h, handle_device(h), p, max_frames, lag_min, lag_max};
+    return allocate_object(b, slots(b, prior.data(), pen.data()), "beat tracker scratch", out);
+}
+
+extern "C" int ymt3_track_beats(ymt3_handle h, ymt3_beats b, const void* notes_dev, long long n_notes, const int32_t* count_dev, long long n_frames,
+                                int32_t* beats_dev, long long max_beats, int32_t* tempo_dev, long long* result_dev, void* stream) {
+    if (const int rc = check_owner(h, b, "beat tracker")) return rc;
+    if (n_frames < 1 || n_frames > b->max_frames) FAIL(YMT3_ERR_ARG, "n_frames=%lld outside [1, max_frames=%lld]", n_frames, b->max_frames);
+    if (const int rc = check_count("n_notes", n_notes, BEAT_MAX_NOTES, nullptr)) return rc;
+    if (const int rc = check_record_ptr("notes_dev", notes_dev, n_notes)) return rc;
+    if (reinterpret_cast<uintptr_t>(count_dev) % 4) FAIL(YMT3_ERR_ARG, "count_dev is not aligned to 4 bytes");
+    if (!beats_dev) FAIL(YMT3_ERR_ARG, "beats_dev is NULL");
+    if (reinterpret_cast<uintptr_t>(beats_dev) % 4) FAIL(YMT3_ERR_ARG, "beats_dev is not aligned to 4 bytes");
+    const long long need = beat_max_beats(n_frames, b->lag_min);
+    if (max_beats < need) FAIL(YMT3_ERR_ARG, "max_beats=%lld below n_frames / ceil(lag_min / 2) + 1 = %lld", max_beats, need);
+    if (reinterpret_cast<uintptr_t>(tempo_dev) % 4) FAIL(YMT3_ERR_ARG, "tempo_dev is not aligned to 4 bytes");
+    if (!result_dev) FAIL(YMT3_ERR_ARG, "result_dev is NULL");
+    if (reinterpret_cast<uintptr_t>(result_dev) % 8) FAIL(YMT3_ERR_ARG, "result_dev is not aligned to 8 bytes");
+    HIP_TRY(hipSetDevice(b->device));
+    BeatArgs a{};
+    a.frames_per_second = b->p.frames_per_second; a.n_programs = b->p.n_programs; a.drum_program = b->p.drum_program;
+    a.lag_min = b->lag_min; a.lag_max = b->lag_max; a.window = b->p.window_frames; a.hop = b->p.hop_frames; a.lag_step = b->p.lag_step_max;
+    a.onset_cap = b->p.onset_cap;
+    a.notes = static_cast<const DetokNote*>(notes_dev); a.n = n_notes; a.count = n_notes ? count_dev : nullptr; a.n_frames = n_frames;
+    a.prior = b->prior; a.pen = b->pen; a.env = b->env; a.smooth = b->smooth; a.tgram = b->tgram; a.lag_back = b->lag_back; a.lags = b->lags;
+    a.back = b->back; a.rbeats = b->rbeats; a.beats = beats_dev; a.max_beats = max_beats; a.tempo = tempo_dev; a.result = result_dev;
+    LAUNCH(launch_track_beats(a, static_cast<hipStream_t>(stream)));
+    return YMT3_OK;
+}
+
+extern "C" int ymt3_beat_positions(ymt3_handle h, ymt3_beats b, const int32_t* beats_dev, const long long* result_dev, const void* notes_dev,
+                                   long long n_notes, const int32_t* count_dev, int divisions, int32_t* ticks_dev, void* stream) {
+    if (const int rc = check_owner(h, b, "beat tracker")) return rc;
+    if (divisions < 0 || (divisions && BEAT_TICKS_PER_BEAT % divisions)) FAIL(YMT3_ERR_ARG, "divisions=%d must be 0 or a divisor of %d", divisions, BEAT_TICKS_PER_BEAT);
+    if (const int rc = check_count("n_notes", n_notes, BEAT_MAX_NOTES, nullptr)) return rc;
+    if (const int rc = check_record_ptr("notes_dev", notes_dev, n_notes)) return rc;
+    if (reinterpret_cast<uintptr_t>(count_dev) % 4) FAIL(YMT3_ERR_ARG, "count_dev is not aligned to 4 bytes");
+    if (!beats_dev) FAIL(YMT3_ERR_ARG, "beats_dev is NULL");
+    if (reinterpret_cast<uintptr_t>(beats_dev) % 4) FAIL(YMT3_ERR_ARG, "beats_dev is not aligned to 4 bytes");
+    if (!result_dev) FAIL(YMT3_ERR_ARG, "result_dev is NULL");
+    if (reinterpret_cast<uintptr_t>(result_dev) % 8) FAIL(YMT3_ERR_ARG, "result_dev is not aligned to 8 bytes");
+    if (n_notes && !ticks_dev) FAIL(YMT3_ERR_ARG, "ticks_dev is NULL");
+    if (reinterpret_cast<uintptr_t>(ticks_dev) % 8) FAIL(YMT3_ERR_ARG, "ticks_dev is not aligned to 8 bytes");
+    HIP_TRY(hipSetDevice(b->device));
+    BeatPositionArgs a{};
+    a.frames_per_second = b->p.frames_per_second; a.n_programs = b->p.n_programs; a.drum_program = b->p.drum_program; a.divisions = divisions;
+    a.beats = beats_dev; a.result = result_dev; a.max_beats = beat_max_beats(b->max_frames, b->lag_min);
+    a.notes = static_cast<const DetokNote*>(notes_dev); a.n = n_notes; a.count = n_notes ? count_dev : nullptr; a.ticks = ticks_dev;
+    LAUNCH(launch_beat_positions(a, static_cast<hipStream_t>(stream)));
     return YMT3_OK;
 }

@@ -1,6 +1,7 @@
 """Minimal Standard MIDI File (format 1) writer/reader for Note lists (mido / pretty_midi are absent)."""
 from __future__ import annotations
 
+import bisect
 import struct
 from typing import Dict, List, Sequence
 
@@ -67,10 +68,21 @@ def _fit_melodic_channels(by_prog: Dict[int, List[Note]]) -> Dict[int, List[Note
 
 
 def notes_to_midi_bytes(notes: Sequence[Note]) -> bytes:
+    return _smf_bytes(notes, {id(n): (_ticks(n.onset), _ticks(n.offset)) for n in notes}, [(0, TEMPO_US)])
+
+
+def _smf_bytes(notes: Sequence[Note], ticks: Dict[int, tuple], tempos) -> bytes:
+    """The file of `notes`: ticks[id(note)] = (onset tick, offset tick); `tempos` = [(tick, microseconds per beat)], ascending.  The
+    ticks are keyed by the note objects' identity: everything below, _fit_melodic_channels included, regroups the SAME objects and never
+    copies a note (equal notes may carry different ticks, so the notes' values cannot be the key)."""
     by_prog: Dict[int, List[Note]] = {}
     for n in notes:
         by_prog.setdefault(DRUM_PROGRAM if n.is_drum else n.program, []).append(n)
-    tracks = [b"\x00\xff\x51\x03" + TEMPO_US.to_bytes(3, "big") + b"\x00\xff\x2f\x00"]
+    conductor, last = bytearray(), 0
+    for tick, us in tempos:
+        conductor += _vlq(tick - last) + b"\xff\x51\x03" + int(us).to_bytes(3, "big")
+        last = tick
+    tracks = [bytes(conductor) + b"\x00\xff\x2f\x00"]
     by_prog = _fit_melodic_channels(by_prog)
     melodic_channels = [c for c in range(16) if c != 9]
     melodic = [p for p in sorted(by_prog) if p != DRUM_PROGRAM]
@@ -81,7 +93,7 @@ def notes_to_midi_bytes(notes: Sequence[Note]) -> bytes:
         # second note starting on the same tick is dropped -- otherwise the note-ons and note-offs of the file do not pair up
         spans: Dict[int, List[List[int]]] = {}
         for n in sorted(ns, key=lambda x: (x.pitch, x.onset, x.offset)):
-            on, off = _ticks(n.onset), max(_ticks(n.offset), _ticks(n.onset) + 1)
+            on, off = ticks[id(n)][0], max(ticks[id(n)][1], ticks[id(n)][0] + 1)
             sp = spans.setdefault(n.pitch, [])
             if sp and sp[-1][0] == on:
                 sp[-1][1] = max(sp[-1][1], off)
@@ -107,6 +119,24 @@ def notes_to_midi_bytes(notes: Sequence[Note]) -> bytes:
     for t in tracks:
         out += b"MTrk" + struct.pack(">I", len(t)) + t
     return out
+
+
+def notes_to_midi_bytes_on_beats(notes: Sequence[Note], ticks, beats, frames_per_second: float = 100.0) -> bytes:
+    """notes_to_midi_bytes with a tempo map: `ticks` (n, 2), every note's onset and offset tick at 480 per beat (beats.beat_positions or
+    BeatTracker.positions, in the notes' order), `beats` the beats' frames at `frames_per_second`.  The tempo track starts with the first
+    interval's tempo at tick 0 and sets interval i's, rint((b[i+1] - b[i]) / fps 1e6) microseconds per beat, at tick (n0 + i) 480
+    (beats.tempo_map); played back, the file keeps the performance's timing, after a lead-in of beats.lead_sec.  A note without ticks
+    (-1: a NaN time) is left out.  With fewer than two beats there is no map: the bytes are notes_to_midi_bytes'."""
+    from .beats import tempo_map
+    notes = list(notes)
+    tempos = tempo_map(beats, frames_per_second)
+    if not tempos:
+        return notes_to_midi_bytes(notes)
+    pairs = [(int(a), int(b)) for a, b in ticks]
+    if len(pairs) != len(notes):
+        raise ValueError(f"{len(notes)} notes but {len(pairs)} tick pairs")
+    kept = [(n, t) for n, t in zip(notes, pairs) if t[0] >= 0 and (t[1] >= 0 or n.is_drum)]
+    return _smf_bytes([n for n, _ in kept], {id(n): t for n, t in kept}, tempos)
 
 
 def write_midi(notes: Sequence[Note], path: str) -> str:
@@ -148,3 +178,79 @@ def read_midi_notes(data: bytes) -> List[Note]:
                     notes.append(Note(sec(on), sec(tick), drum, DRUM_PROGRAM if drum else prog, pitch, v))
         pos = end
     return sorted(notes)
+
+
+def _track_events(data: bytes):
+    """The events of a Standard MIDI File as notes_to_midi_bytes and notes_to_midi_bytes_on_beats write it -> (ticks per beat, an
+    iterator of (track, absolute tick, status byte, payload bytes)); a meta event's payload starts with its type byte."""
+    assert data[:4] == b"MThd"
+    _, fmt, ntrk, tpb = struct.unpack(">IHHH", data[4:14])
+
+    def events():
+        pos = 14
+        for track in range(ntrk):
+            assert data[pos:pos + 4] == b"MTrk"
+            ln = struct.unpack(">I", data[pos + 4:pos + 8])[0]
+            p, end, tick = pos + 8, pos + 8 + ln, 0
+            while p < end:
+                d = 0
+                while True:
+                    b = data[p]; p += 1
+                    d = (d << 7) | (b & 0x7F)
+                    if not b & 0x80:
+                        break
+                tick += d
+                st = data[p]; p += 1
+                if st == 0xFF:
+                    n = 2 + data[p + 1]
+                    payload = data[p:p + 1] + data[p + 2:p + n]
+                else:
+                    n = 1 if st & 0xF0 == 0xC0 else 2
+                    payload = data[p:p + n]
+                p += n
+                yield track, tick, st, payload
+            pos = end
+
+    return tpb, events()
+
+
+def note_on_ticks(data: bytes) -> List[int]:
+    """the absolute tick of every note-on of a file, track by track"""
+    return [tick for _, tick, st, payload in _track_events(data)[1] if st & 0xF0 == 0x90 and payload[1] > 0]
+
+
+def read_midi_on_beats(data: bytes):
+    """Parse what notes_to_midi_bytes_on_beats writes -> (notes in seconds through the file's tempo map, the map as [(tick, microseconds
+    per beat)]).  A file without tempo events plays at 120 bpm."""
+    tpb, events = _track_events(data)
+    raw, tempos, prog, open_ = [], [], {}, {}
+    for track, tick, st, payload in events:
+        if st == 0xFF:
+            if payload[0] == 0x51:
+                tempos.append((tick, int.from_bytes(payload[1:], "big")))
+        elif st & 0xF0 == 0xC0:
+            prog[track] = payload[0]
+        elif st & 0xF0 in (0x90, 0x80):
+            pitch, vel = payload[0], payload[1]
+            drum = (st & 0x0F) == 9
+            if st & 0xF0 == 0x90 and vel > 0:
+                open_[track, pitch] = (tick, vel)
+            elif (track, pitch) in open_:
+                on, v = open_.pop((track, pitch))
+                raw.append((on, tick, drum, DRUM_PROGRAM if drum else prog.get(track, 0), pitch, v))
+    tempos = sorted(tempos) or [(0, TEMPO_US)]
+    if tempos[0][0] != 0:
+        tempos.insert(0, (0, TEMPO_US))
+    starts, t = [], 0.0                                 # the time at which every tempo event takes hold
+    for i, (tk, us) in enumerate(tempos):
+        if i:
+            t += (tk - tempos[i - 1][0]) * tempos[i - 1][1] / (tpb * 1e6)
+        starts.append(t)
+
+    at = [tk for tk, _ in tempos]
+
+    def sec(tick):
+        i = bisect.bisect_right(at, tick) - 1
+        return starts[i] + (tick - at[i]) * tempos[i][1] / (tpb * 1e6)
+
+    return sorted(Note(sec(on), sec(off), drum, prog, pitch, v) for on, off, drum, prog, pitch, v in raw), tempos

@@ -595,6 +595,14 @@ class YourMT3:
         from .velocity import NoteVelocity                              # (not a name of this module: velocity.py builds on it)
         return NoteVelocity(self, **params)
 
+    def compile_beat_tracker(self, max_frames: int, **params):
+        """The device beat tracker (include/ymt3.h, beat tracking; the rules and the host specification: yourmt3_amd/beats.py) with
+        scratch for up to `max_frames` frames.  `params`: frames_per_second, bpm_min, bpm_max, bpm_prior, prior_octaves, tightness,
+        window_frames, hop_frames, lag_step_max, onset_cap, n_programs, drum_program (beats.DEFAULTS).  -> a beats.BeatTracker, closed
+        with the model like every other device object."""
+        from .beats import BeatTracker                                  # (not a name of this module: beats.py builds on it)
+        return BeatTracker(self, max_frames, **params)
+
     def compile_ingest_stream(self, sample_rate: int, n_channels: int = 1, dtype=torch.int16, max_chunk_frames: int = 1 << 16) -> IngestStream:
         """Streaming form of ingest() (include/ymt3.h, streaming ingest) for `n_channels`-channel PCM of `dtype` (int16 or float32) at
         `sample_rate`, pushed in chunks of at most `max_chunk_frames` frames."""

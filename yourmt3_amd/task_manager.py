@@ -557,14 +557,18 @@ class TaskManager:
         return table
 
     def tokens_to_notes_device(self, model, tokens, start_secs: Sequence[float], end_sec: float, scores=None,
-                               detokenizer=None, velocity=None, audio=None) -> Tuple[List[Note], int]:
+                               detokenizer=None, velocity=None, audio=None, beats=None, quantize: int = 0):
         """tokens_to_notes on the device -> (notes, n_invalid).  `tokens`: (n, K, L) integer ids on `model`'s GPU (any strides whose
         last dimension is contiguous, e.g. hypothesis 0 of a beam call's (n, K, N, L)); `scores`: the matching (n, K, L) f32 token scores
         or None; `start_secs` must be strictly increasing.  `detokenizer`: a YourMT3.compile_detokenizer object to reuse (None: one is
         made for this call and closed).  One copy back of the counters and the notes' records; confidence = exp(score) on the host.
         `velocity`: a YourMT3.compile_note_velocity object, with `audio` the flat f32 samples the segments were cut from, on the GPU
         (YourMT3.ingest's buffer as it is): every note's velocity is measured on the records where they lie, their number read from the
-        detokeniser's counter on the device, and the bytes come back in the records' copy."""
+        detokeniser's counter on the device, and the bytes come back in the records' copy.
+        `beats`: a YourMT3.compile_beat_tracker object: the beats are tracked on the records where they lie (over the frames of `end_sec`,
+        beats.n_frames_of), every note gets its ticks (snapped to `quantize` steps per beat if that is not 0), and beats, tempo and ticks
+        come back in the same copy: the result gains a third element, {"beats" (frames), "tempo" (lags per window), "ticks" ((n, 2), in
+        the returned notes' order)}."""
         import torch
 
         starts = np.asarray(list(start_secs), np.float64)
@@ -580,20 +584,39 @@ class TaskManager:
         if (velocity is None) != (audio is None):
             raise ValueError("velocity and audio go together")
         if n == 0 or L == 0:
+            if beats is not None:
+                return [], 0, {"beats": np.zeros(0, np.int32), "tempo": np.zeros(0, np.int32), "ticks": np.zeros((0, 2), np.int32)}
             return [], 0
         own = detokenizer is None
         if own:
             detokenizer = model.compile_detokenizer(self, n, L)
         try:
-            if velocity is None:
+            tracked = None
+            if velocity is None and beats is None:
                 rec, n_invalid = detokenizer.run(tokens, scores, torch.from_numpy(starts), float(end_sec))
                 vel = None
             else:
                 rec_dev, counts = detokenizer.run_device(tokens, scores, torch.from_numpy(starts), float(end_sec))
-                vel_dev = velocity.run(audio, rec_dev, count=counts)[0]
+                vel_dev = velocity.run(audio, rec_dev, count=counts)[0] if velocity is not None else None
+                if beats is not None:
+                    from .beats import n_frames_of
+                    beats_dev, lags_dev, result_dev = beats.track(rec_dev, n_frames_of(end_sec, beats.params["frames_per_second"]), count=counts)
+                    ticks_dev = beats.positions(beats_dev, result_dev, rec_dev, counts, quantize)
                 n_notes, n_invalid = (int(v) for v in counts.cpu().tolist())
-                both = torch.cat([rec_dev[:n_notes * NOTE_RECORD.itemsize], vel_dev[:n_notes]]).cpu().numpy()
-                rec, vel = both[:n_notes * NOTE_RECORD.itemsize].view(NOTE_RECORD), both[n_notes * NOTE_RECORD.itemsize:].tolist()
+                nb = n_notes * NOTE_RECORD.itemsize
+                parts = [rec_dev[:nb]] + ([vel_dev[:n_notes]] if velocity is not None else [])
+                if beats is not None:
+                    parts += [t.reshape(-1).view(torch.uint8) for t in (ticks_dev[:n_notes], result_dev, lags_dev, beats_dev)]
+                both = torch.cat(parts).cpu().numpy()
+                rec, o = both[:nb].view(NOTE_RECORD), nb
+                vel = None
+                if velocity is not None:
+                    vel, o = both[o:o + n_notes].tolist(), o + n_notes
+                if beats is not None:
+                    ints = both[o:].view(np.int32)
+                    n_beats = int(ints[2 * n_notes:2 * n_notes + 8].view(np.int64)[0])
+                    o = 2 * n_notes + 8 + lags_dev.numel()
+                    tracked = {"beats": ints[o:o + n_beats].copy(), "tempo": ints[2 * n_notes + 8:o].copy(), "ticks": ints[:2 * n_notes].reshape(-1, 2).copy()}
         finally:
             if own:
                 detokenizer.close()
@@ -603,6 +626,10 @@ class TaskManager:
                                                     rec["pitch"].tolist(), rec["is_drum"].tolist(), rec["score"].astype(np.float64).tolist())]
         if vel is not None:
             notes = [replace(x, velocity=v) for x, v in zip(notes, vel)]
+        if tracked is not None:
+            order = sorted(range(len(notes)), key=notes.__getitem__)
+            tracked["ticks"] = tracked["ticks"][order]
+            return [notes[i] for i in order], n_invalid, tracked
         return sorted(notes), n_invalid
 
     def tokens_to_notes_stream(self, model, detokenizer, state, tokens=None, start_secs: Sequence[float] = (), horizon_sec: float = math.inf,

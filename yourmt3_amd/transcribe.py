@@ -15,13 +15,15 @@ from .midi import read_midi_notes, write_midi
 from .metrics import FrameMetricCounts, NoteMetricCounts, to_records
 from .task_manager import DRUM_PROGRAM, NOTE_RECORD as NOTE_RECORD_DTYPE, Note, TaskManager, drop_low_confidence
 from .velocity import estimate_velocities  # noqa: F401  (its home is velocity.py; it belongs with transcribe, evaluate and align)
+from .beats import estimate_beats  # noqa: F401  (the same for beats.py)
 
 
 def transcribe(model, audio_info: Union[str, dict, np.ndarray], task_manager: Optional[TaskManager] = None, bsz: int = 8,
                output_dir: str = ".", max_token_length: Optional[int] = None, return_notes: bool = False,
                continuous: bool = False, subtask: Optional[str] = None, confidence: bool = False,
                min_confidence: Optional[float] = None, constrained: bool = False, programs=None, num_beams: int = 1,
-               length_penalty: float = 1.0, device_detok: bool = False, velocity: bool = False, velocity_params: Optional[dict] = None):
+               length_penalty: float = 1.0, device_detok: bool = False, velocity: bool = False, velocity_params: Optional[dict] = None,
+               beats: bool = False, quantize: int = 0, beat_params: Optional[dict] = None):
     """`continuous=True` decodes the file's segments through `bsz` slots with continuous batching
     (YourMT3.inference_stream: segments leave at EOS and the next ones enter) instead of fixed batches; same ids.
     `subtask`: for a task-conditioned TaskManager (e.g. "singing_drum_v1"), the sub-task whose task tokens prompt every
@@ -41,9 +43,18 @@ def transcribe(model, audio_info: Union[str, dict, np.ndarray], task_manager: Op
     `velocity=True` fills every note's `velocity` from the audio under its onset (YourMT3.compile_note_velocity; include/ymt3.h, note
     velocities; the rules: yourmt3_amd/velocity.py) instead of the flat 100, in every mode above and with both detokenisers: the ingested
     buffer, still on the device, is the audio.  `velocity_params`: velocity.DEFAULTS' keys.  The notes `min_confidence` drops are gone
-    before the measurement, so the loudest KEPT note gets peak_velocity.  Off, nothing changes by a byte."""
+    before the measurement, so the loudest KEPT note gets peak_velocity.  Off, nothing changes by a byte.
+    `beats=True` tracks the beats of the notes on the device (YourMT3.compile_beat_tracker; include/ymt3.h, beat tracking; the rules:
+    yourmt3_amd/beats.py) and writes the .mid on them: its tempo track follows the music, a tick is a position in beats, and playback keeps
+    the performance's timing after a lead-in of less than a beat.  `quantize` (a divisor of 480; 0: none) snaps every note to that many
+    steps per beat.  `beat_params`: beats.DEFAULTS' keys.  With both detokenisers the same bytes: the device one is tracked on its records
+    where they lie, the host's notes go up once.  After `min_confidence` and `velocity`, on the kept notes.  The return value gains a last
+    element: {"beats_sec", "tempo_bpm" (one per window of hop_frames), "lead_sec", "ticks" ((n, 2), in the notes' order)}.  Off, nothing
+    changes by a byte."""
     if velocity_params is not None and not velocity:
         raise ValueError("velocity_params without velocity=True")
+    if (beat_params is not None or quantize) and not beats:
+        raise ValueError("beat_params or quantize without beats=True")
     num_beams = int(num_beams)
     if num_beams < 1:
         raise ValueError(f"num_beams={num_beams} must be >= 1")
@@ -97,24 +108,50 @@ def transcribe(model, audio_info: Union[str, dict, np.ndarray], task_manager: Op
     finally:
         if constraint is not None:
             constraint.close()
+    end_sec = n_samples / cfg.sample_rate
     measurer = model.compile_note_velocity(**(velocity_params or {})) if velocity else None
+    tracker = tracked = None
     try:
-        in_place = measurer is not None and device_detok and min_confidence is None      # measured on the detokeniser's records where they lie
+        if beats:
+            from .beats import DEFAULTS as BEAT_DEFAULTS, n_frames_of
+            fps = float((beat_params or {}).get("frames_per_second", BEAT_DEFAULTS["frames_per_second"]))
+            n_frames = n_frames_of(end_sec, fps)
+            tracker = model.compile_beat_tracker(n_frames, **(beat_params or {}))
+        in_place = device_detok and min_confidence is None                   # measured and tracked on the detokeniser's records where they lie
         if device_detok:
-            notes, _ = task_manager.tokens_to_notes_device(model, tokens, start_secs, n_samples / cfg.sample_rate, scores=scores,
-                                                           **({"velocity": measurer, "audio": segments.view(-1)} if in_place else {}))
+            extra = {}
+            if in_place and measurer is not None:
+                extra.update(velocity=measurer, audio=segments.view(-1))
+            if in_place and tracker is not None:
+                extra.update(beats=tracker, quantize=quantize)
+            out = task_manager.tokens_to_notes_device(model, tokens, start_secs, end_sec, scores=scores, **extra)
+            notes, tracked = out[0], (out[2] if len(out) > 2 else None)
         else:
-            notes = task_manager.tokens_to_notes(batches, start_secs, end_sec=n_samples / cfg.sample_rate, score_batches=score_batches)
+            notes = task_manager.tokens_to_notes(batches, start_secs, end_sec=end_sec, score_batches=score_batches)
         if min_confidence is not None:
             notes = drop_low_confidence(notes, float(min_confidence))
         if measurer is not None and not in_place:                           # the host's notes: one upload of their records, the same kernel
             notes = measurer.apply(segments.view(-1), notes)
+        if tracker is not None and tracked is None:                         # the same for the beats
+            b, t, _, ticks = tracker.run(torch.from_numpy(to_records(list(notes)).view(np.uint8).reshape(-1).copy()), n_frames, divisions=quantize)
+            tracked = {"beats": b, "tempo": t, "ticks": ticks}
     finally:
         if measurer is not None:
             measurer.close()
+        if tracker is not None:
+            tracker.close()
     os.makedirs(output_dir, exist_ok=True)
-    midi_path = write_midi(notes, os.path.join(output_dir, name + ".mid"))
-    return (midi_path, notes) if return_notes else midi_path
+    if tracked is None:
+        midi_path = write_midi(notes, os.path.join(output_dir, name + ".mid"))
+        return (midi_path, notes) if return_notes else midi_path
+    from .beats import beat_summary
+    from .midi import notes_to_midi_bytes_on_beats
+    midi_path = os.path.join(output_dir, name + ".mid")
+    with open(midi_path, "wb") as f:
+        f.write(notes_to_midi_bytes_on_beats(notes, tracked["ticks"], tracked["beats"], fps))
+    info = beat_summary(tracked["beats"], tracked["tempo"], fps)
+    info["ticks"] = tracked["ticks"]
+    return (midi_path, notes, info) if return_notes else (midi_path, info)
 
 
 def _decode(model, segments, bsz, L, continuous, scored, kw):
@@ -182,7 +219,9 @@ class LiveTranscriber:
     the same side of both boundaries.
 
     Note velocities (transcribe(velocity=True)) are not part of a live session: a pitched note becomes final when it ends, long after the
-    audio of its onset has left the device.  estimate_velocities() on the recording puts them onto the session's MIDI file afterwards."""
+    audio of its onset has left the device.  estimate_velocities() on the recording puts them onto the session's MIDI file afterwards.
+    Beats (transcribe(beats=True)) are not part of a live session either: the tempo path looks at the whole file.  estimate_beats() on the
+    session's notes tracks them afterwards."""
 
     def __init__(self, model, sample_rate: int, n_channels: int = 1, dtype=torch.int16, task_manager: Optional[TaskManager] = None,
                  max_chunk_frames: int = 1 << 16, bsz: Optional[int] = None, max_token_length: Optional[int] = None,
