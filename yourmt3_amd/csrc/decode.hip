@@ -678,21 +678,28 @@ __device__ __forceinline__ void attn_body(const bf16_t* __restrict__ pK, const b
     // clamped to the wave's first key and masked in the math: with the loads behind `if (u < nblk)` branches hipcc's
     // wait-count pass merges the paths and waits for the oldest load with the count of the path that issued the fewest
     // (vmcnt(1): the whole block), and each bias value became its own load + vmcnt(0) round trip in the score loop.
-    auto load_block = [&](u32x4 (&ku)[U], u32x4 (&vu)[U], bool (&ok)[U], float (&bv)[U], int kw, auto full_tag) {
+    // A partly filled block (FULL == false) comes in two forms.  nv_tag = 0: all U sub-blocks are loaded and run, each masked by key.
+    // nv_tag = NV in 1..U (the self-attention stream's last block, see `tail` below): only the NV sub-blocks that hold a key of this wave --
+    // the wave's first key of sub-block u is valid for u < NV and for no other u, so sub-blocks below NV - 1 are whole and only the
+    // last one keeps its per-lane mask.  A sub-block left out contributed p = 0 to l and to every accumulator and had no part in the
+    // maximum: the same bits (but for the sign of an accumulator that is exactly -0), and still one straight-line path per NV.
+    auto load_block = [&](u32x4 (&ku)[U], u32x4 (&vu)[U], bool (&ok)[U], float (&bv)[U], int kw, auto full_tag, auto nv_tag) {
         constexpr bool FULL = decltype(full_tag)::value;         // FULL: all U blocks valid, no masks
+        constexpr int NVT = decltype(nv_tag)::value, NV = NVT ? NVT : U;
+        static_assert(NVT >= 0 && NVT <= U && !(FULL && NVT), "sub-block count of a partly filled block");
         const int k0 = kw + kg;
         int holder[BEAM ? U : 1];                                // BEAM: the block's table entries, read together in front of its loads
         if constexpr (BEAM) {
 #pragma unroll
-            for (int u = 0; u < U; ++u) {
+            for (int u = 0; u < NV; ++u) {
                 const int key = k0 + 8 * NW * u;
                 holder[u] = anc_s[FULL || key < n_keys ? key : kw];
             }
         }
 #pragma unroll
-        for (int u = 0; u < U; ++u) {
+        for (int u = 0; u < NV; ++u) {
             const int key = k0 + 8 * NW * u;
-            ok[u] = FULL || key < n_keys;
+            ok[u] = FULL || (NVT && u < NV - 1) || key < n_keys;
             const int kc = ok[u] ? key : kw;
             if constexpr (BEAM) {
                 const size_t at = (size_t)min(holder[u], ba.W - 1) * row_pitch + (size_t)kc * DKV;
@@ -707,17 +714,18 @@ __device__ __forceinline__ void attn_body(const bf16_t* __restrict__ pK, const b
             }
         }
 #pragma unroll
-        for (int u = 0; u < U; ++u) {
+        for (int u = 0; u < NV; ++u) {
             if constexpr (SELF) bv[u] = bias[ok[u] ? n_keys - 1 - (k0 + 8 * NW * u) : 0];
             else bv[u] = 0.f;
         }
         __builtin_amdgcn_sched_barrier(0);                       // every load of the block is in flight before any math waits
     };
-    auto compute_block = [&](u32x4 (&ku)[U], u32x4 (&vu)[U], bool (&ok)[U], float (&bv)[U], auto full_tag) {
+    auto compute_block = [&](u32x4 (&ku)[U], u32x4 (&vu)[U], bool (&ok)[U], float (&bv)[U], auto full_tag, auto nv_tag) {
+        constexpr int NV = decltype(nv_tag)::value ? decltype(nv_tag)::value : U;
         float sc[U];
         float mn = m;
 #pragma unroll
-        for (int u = 0; u < U; ++u) {
+        for (int u = 0; u < NV; ++u) {
             {
                 float s = 0.f;
                 // plain fp32 FMAs on the unpacked halves: v_dot2c_f32_bf16 chains gave O(1) wrong scores on
@@ -738,7 +746,7 @@ __device__ __forceinline__ void attn_body(const bf16_t* __restrict__ pK, const b
 #pragma unroll
         for (int d = 0; d < 8; ++d) acc[d] *= rescale;
 #pragma unroll
-        for (int u = 0; u < U; ++u) {
+        for (int u = 0; u < NV; ++u) {
             {
                 const float p = ok[u] ? __expf(sc[u] - mn) : 0.f;
                 l += p;
@@ -755,38 +763,85 @@ __device__ __forceinline__ void attn_body(const bf16_t* __restrict__ pK, const b
     bool fok[FUSEQ ? U : 1];
     float fbv[FUSEQ ? U : 1];
     if constexpr (!FUSEQ) {
+        constexpr std::integral_constant<int, 0> every_sub{};
         auto block = [&](int kw, auto full_tag) {                // staging registers scoped to one block
             u32x4 ku[U], vu[U];
             bool ok[U];
             float bv[U];
-            load_block(ku, vu, ok, bv, kw, full_tag);
-            compute_block(ku, vu, ok, bv, full_tag);
+            load_block(ku, vu, ok, bv, kw, full_tag, every_sub);
+            compute_block(ku, vu, ok, bv, full_tag, every_sub);
         };
         int kw = wave * 8;
-        if constexpr (OP && SELF) {
-            // the first block's K/V requests, then the wo DMAs, then its math (the inline-asm DMAs are invisible to hipcc's wait counts: its waits
-            // for the block's loads, which are older, do not wait for them until the block's last load is needed)
-            if (kw < n_keys) {
-                u32x4 ku[U], vu[U];
-                bool ok[U];
-                float bv[U];
-                if (n_keys - kw >= 8 * NW * U) {
-                    load_block(ku, vu, ok, bv, kw, std::true_type{});
-                    issue_wo();
-                    compute_block(ku, vu, ok, bv, std::true_type{});
+#if defined(YMT3_PARENT_B)                      // A/B builds of one tree (build.py: flags / lib; selected with YMT3_LIB): the masked form everywhere
+        constexpr bool TAIL_NV = false;
+#else
+        constexpr bool TAIL_NV = SELF && !BEAM;      // (the beam kernels keep the masked form: their table reads sit in front of every sub-block's loads)
+#endif
+        if constexpr (!TAIL_NV) {
+            if constexpr (OP && SELF) {
+                // the first block's K/V requests, then the wo DMAs, then its math (the inline-asm DMAs are invisible to hipcc's wait counts: its waits
+                // for the block's loads, which are older, do not wait for them until the block's last load is needed)
+                if (kw < n_keys) {
+                    u32x4 ku[U], vu[U];
+                    bool ok[U];
+                    float bv[U];
+                    if (n_keys - kw >= 8 * NW * U) {
+                        load_block(ku, vu, ok, bv, kw, std::true_type{}, every_sub);
+                        issue_wo();
+                        compute_block(ku, vu, ok, bv, std::true_type{}, every_sub);
+                    } else {
+                        load_block(ku, vu, ok, bv, kw, std::false_type{}, every_sub);
+                        issue_wo();
+                        compute_block(ku, vu, ok, bv, std::false_type{}, every_sub);
+                    }
+                    kw += 8 * NW * U;
                 } else {
-                    load_block(ku, vu, ok, bv, kw, std::false_type{});
                     issue_wo();
-                    compute_block(ku, vu, ok, bv, std::false_type{});
                 }
-                kw += 8 * NW * U;
-            } else {
-                issue_wo();
             }
-        }
-        for (; kw < n_keys; kw += 8 * NW * U) {      // wave-uniform trip count: waves with no key skip everything
-            if (n_keys - kw >= 8 * NW * U) block(kw, std::true_type{});
-            else block(kw, std::false_type{});
+            for (; kw < n_keys; kw += 8 * NW * U) {      // wave-uniform trip count: waves with no key skip everything
+                if (n_keys - kw >= 8 * NW * U) block(kw, std::true_type{});
+                else block(kw, std::false_type{});
+            }
+        } else {
+            // Whole blocks, then ONE partly filled block that costs what its keys cost: nv = the sub-blocks in which this wave still has a
+            // key (wave-uniform, 1..U), one straight-line instantiation each.  OP: the wo DMAs go behind the wave's first block of K/V
+            // requests, whichever form that block takes (see above), or out at once for a wave without keys.
+            bool wo_pending = OP && SELF;
+            if constexpr (OP && SELF) {
+                if (n_keys - kw >= 8 * NW * U) {
+                    u32x4 ku[U], vu[U];
+                    bool ok[U];
+                    float bv[U];
+                    load_block(ku, vu, ok, bv, kw, std::true_type{}, every_sub);
+                    issue_wo();
+                    compute_block(ku, vu, ok, bv, std::true_type{}, every_sub);
+                    kw += 8 * NW * U;
+                    wo_pending = false;
+                }
+            }
+            for (; n_keys - kw >= 8 * NW * U; kw += 8 * NW * U) block(kw, std::true_type{});
+            if (kw < n_keys) {
+                auto tail = [&](auto nv_tag) {
+                    u32x4 ku[U], vu[U];
+                    bool ok[U];
+                    float bv[U];
+                    load_block(ku, vu, ok, bv, kw, std::false_type{}, nv_tag);
+                    if constexpr (OP && SELF) { if (wo_pending) issue_wo(); }
+                    compute_block(ku, vu, ok, bv, std::false_type{}, nv_tag);
+                };
+                static_assert(U == 6 || !TAIL_NV, "one case per sub-block count");
+                switch ((n_keys - kw + 8 * NW - 1) / (8 * NW)) {
+                    case 1: tail(std::integral_constant<int, 1>{}); break;
+                    case 2: tail(std::integral_constant<int, 2>{}); break;
+                    case 3: tail(std::integral_constant<int, 3>{}); break;
+                    case 4: tail(std::integral_constant<int, 4>{}); break;
+                    case 5: tail(std::integral_constant<int, 5>{}); break;
+                    default: tail(std::integral_constant<int, U < 6 ? U : 6>{}); break;
+                }
+            } else if constexpr (OP && SELF) {
+                if (wo_pending) issue_wo();
+            }
         }
     } else {
         // every wave's projection operands are requested before ANY wave's K/V: the CU returns vector-memory data in request
@@ -896,8 +951,8 @@ __device__ __forceinline__ void attn_body(const bf16_t* __restrict__ pK, const b
         qp = *reinterpret_cast<const u32x4*>(qs + sub * 8);
         // the block loaded above, then the remaining ones
         for (int kw = wave * 8; kw < n_keys; kw += 8 * NW * U) {
-            if (kw != wave * 8) load_block(fku, fvu, fok, fbv, kw, std::false_type{});
-            compute_block(fku, fvu, fok, fbv, std::false_type{});
+            if (kw != wave * 8) load_block(fku, fvu, fok, fbv, kw, std::false_type{}, std::integral_constant<int, 0>{});
+            compute_block(fku, fvu, fok, fbv, std::false_type{}, std::integral_constant<int, 0>{});
         }
     }
     if constexpr (PAIR == 1) PAIR_MARK(a, 1, wall_clock64());     // self-attention stream consumed
