@@ -821,6 +821,41 @@ int ymt3_debug_moe_trace(ymt3_handle h, int32_t* trace_dev, int n_steps, int n_r
 /* Unit-test hooks: C = A(bf16 MxK) * W^T(bf16 NxK), f32 out; runs the encoder GEMM kernel. */
 int ymt3_test_gemm(ymt3_handle h, const void* a_dev, const void* w_dev, float* c_dev, int M, int N, int K, void* stream);
 
+/* Per-kernel test doors of the encoder.  Each validates its arguments and calls ONE launcher of the production path (nothing on that
+ * path calls them).  They take raw device pointers, so what can be checked without knowing the allocations is checked here and refused
+ * with YMT3_ERR_ARG and a text: null pointers, pointers not aligned to 16 bytes, and every shape the launcher would refuse.  The
+ * EXTENTS behind the pointers are the caller's duty (yourmt3_amd/model.py computes them from the shape and the strides and refuses a
+ * smaller tensor before it calls).  All asynchronous on `stream`; a refused call leaves the door usable.
+ *
+ * ymt3_test_gemm_ex: out (+)= A[M][K] (bf16, row stride lda) * W[N][K]^T (bf16, ldw) with epilogue 0..4 =
+ *   0 f32 out[m * ldc + n] = acc (+ bias[n], bias may be NULL)      1 bf16 out = R(acc)      2 bf16 out = R(max(acc, 0))
+ *   3 f32 out += acc                                                 4 bf16 out[n / (H*64)][m / T][h][m % T][64], needs M == n_seg * T
+ * N % 128 == 0, K % 64 == 0, lda, ldw >= K and multiples of 8, ldc >= N and a multiple of 8 (epilogue 4 ignores ldc), bias with
+ * epilogue 0 only.  M * N elements are written (rows >= M and columns >= N never). */
+int ymt3_test_gemm_ex(ymt3_handle h, int epilogue, const void* a_dev, const void* w_dev, void* out_dev, const float* bias_dev, int M, int N,
+                      int K, int lda, int ldw, int ldc, int T, int H, int n_seg, void* stream);
+/* out bf16 [M][d] = R(x f32 [M][d] * rsqrt(mean(x^2) + eps) * gain f32 [d]);  d % 4 == 0 */
+int ymt3_test_rmsnorm(ymt3_handle h, const float* x_dev, const float* gain_dev, void* out_dev, int M, int d, float eps, void* stream);
+/* Encoder self-attention of B segments of T in {64, 128, 256, 512} positions, H heads of 64: query rows q + (b*T + t) * ldq + h*64,
+ * key / value rows k|v + (b*T + t) * ldkv + h*64 (bf16), bias_off f32 [H][2T-1] indexed by key - query + T - 1,
+ * out bf16 [B*T][H*64].  ldq, ldkv >= H*64 and multiples of 8. */
+int ymt3_test_enc_attention(ymt3_handle h, const void* q_dev, int ldq, const void* k_dev, const void* v_dev, int ldkv, const float* bias_off_dev,
+                            void* out_dev, int B, int T, int H, void* stream);
+/* Batched small-sequence attention: sequence s = so * inner_n + si (so = s / inner_n) starts at element so * outer + si * inner of its
+ * buffer, position t lies t * step further, head h at + h*64.  Tq % 16 == 0, Tk in {32, 64, 128, 256}; bias_off f32 [H][2*Tk-1] (needs
+ * Tq == Tk) or NULL.  Strides are multiples of 8 elements, steps positive. */
+typedef struct ymt3_seq_attn_args {
+    const void* q; const void* k; const void* v; void* out;
+    const float* bias_off;
+    int32_t n_seq, H, Tq, Tk, inner_n;
+    int64_t q_outer, q_inner, q_step, kv_outer, kv_inner, kv_step, o_outer, o_inner, o_step;
+} ymt3_seq_attn_args;
+int ymt3_test_seq_attention(ymt3_handle h, const ymt3_seq_attn_args* args, void* stream);
+/* out bf16 [n_rows][d] = R(rmsnorm(mel[row] * w + pos[row % F]) * gain): mel f32 [n_rows], w f32 [d], pos bf16 [F][d], gain f32 [d];
+ * d % 4 == 0, d <= 256 */
+int ymt3_test_spec_embed(ymt3_handle h, const float* mel_dev, const float* w_dev, const void* pos_dev, const float* gain_dev, void* out_dev,
+                         long long n_rows, int F, int d, float eps, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -35,6 +35,7 @@ SYMBOLS = [
     "ymt3_detokenize_push", "ymt3_detokenize_finish",
     "ymt3_velocity_create", "ymt3_velocity_destroy", "ymt3_note_velocities",
     "ymt3_beats_create", "ymt3_beats_destroy", "ymt3_track_beats", "ymt3_beat_positions",
+    "ymt3_test_gemm_ex", "ymt3_test_rmsnorm", "ymt3_test_enc_attention", "ymt3_test_seq_attention", "ymt3_test_spec_embed",
 ]
 
 _lib = None
@@ -78,6 +79,13 @@ class BeatParams(ctypes.Structure):
     """ymt3_beat_params of include/ymt3.h"""
     _fields_ = [(n, ctypes.c_double) for n in ("frames_per_second", "bpm_min", "bpm_max", "bpm_prior", "prior_octaves", "tightness")] + [
         (n, ctypes.c_int32) for n in ("window_frames", "hop_frames", "lag_step_max", "onset_cap", "n_programs", "drum_program")]
+
+
+class SeqAttnArgs(ctypes.Structure):
+    """ymt3_seq_attn_args of include/ymt3.h"""
+    _fields_ = [(n, ctypes.c_void_p) for n in ("q", "k", "v", "out", "bias_off")] + [
+        (n, ctypes.c_int32) for n in ("n_seq", "H", "Tq", "Tk", "inner_n")] + [
+        (n, ctypes.c_int64) for n in ("q_outer", "q_inner", "q_step", "kv_outer", "kv_inner", "kv_step", "o_outer", "o_inner", "o_step")]
 
 
 class YMT3Error(RuntimeError):
@@ -251,6 +259,17 @@ def load() -> ctypes.CDLL:
     lib.ymt3_track_beats.restype = i32
     lib.ymt3_beat_positions.argtypes = [vp, vp, vp, vp, vp, ll, vp, i32, vp, vp]
     lib.ymt3_beat_positions.restype = i32
+    f32 = ctypes.c_float
+    lib.ymt3_test_gemm_ex.argtypes = [vp, i32, vp, vp, vp, vp, i32, i32, i32, i32, i32, i32, i32, i32, i32, vp]
+    lib.ymt3_test_gemm_ex.restype = i32
+    lib.ymt3_test_rmsnorm.argtypes = [vp, vp, vp, vp, i32, i32, f32, vp]
+    lib.ymt3_test_rmsnorm.restype = i32
+    lib.ymt3_test_enc_attention.argtypes = [vp, vp, i32, vp, vp, i32, vp, vp, i32, i32, i32, vp]
+    lib.ymt3_test_enc_attention.restype = i32
+    lib.ymt3_test_seq_attention.argtypes = [vp, ctypes.POINTER(SeqAttnArgs), vp]
+    lib.ymt3_test_seq_attention.restype = i32
+    lib.ymt3_test_spec_embed.argtypes = [vp, vp, vp, vp, vp, vp, ll, i32, i32, f32, vp]
+    lib.ymt3_test_spec_embed.restype = i32
     for n in ("ymt3_logmel", "ymt3_encode", "ymt3_decode_greedy", "ymt3_transcribe_segments", "ymt3_test_gemm"):
         getattr(lib, n).restype = i32
     if lib.ymt3_abi_version() != 3:

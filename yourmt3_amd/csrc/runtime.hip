@@ -1878,6 +1878,98 @@ extern "C" int ymt3_test_gemm(ymt3_handle h, const void* a_dev, const void* w_de
     return YMT3_OK;
 }
 
+// ---------------------------------------------------------------- per-kernel test doors (include/ymt3.h)
+// What a raw pointer can be checked for; the extents behind it are the caller's (model.py).
+static bool door_ptr_ok(const void* p) { return p && (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
+#define DOOR_PTR(p) do { if (!door_ptr_ok(p)) FAIL(YMT3_ERR_ARG, "%s: %s is %s", __func__, #p, (p) ? "not aligned to 16 bytes" : "null"); } while (0)
+#define DOOR_REQUIRE(cond) do { if (!(cond)) FAIL(YMT3_ERR_ARG, "%s: needs %s", __func__, #cond); } while (0)
+
+extern "C" int ymt3_test_gemm_ex(ymt3_handle h, int epilogue, const void* a_dev, const void* w_dev, void* out_dev, const float* bias_dev, int M,
+                                 int N, int K, int lda, int ldw, int ldc, int T, int H, int n_seg, void* stream) {
+    int rc = check_call(h, 0);
+    if (rc) return rc;
+    DOOR_PTR(a_dev); DOOR_PTR(w_dev); DOOR_PTR(out_dev);
+    if (bias_dev) DOOR_PTR(bias_dev);
+    DOOR_REQUIRE(epilogue >= EPI_F32 && epilogue <= EPI_KV_HEADMAJOR);
+    DOOR_REQUIRE(bias_dev == nullptr || epilogue == EPI_F32);
+    DOOR_REQUIRE(M > 0 && N > 0 && K > 0 && N % 128 == 0 && K % 64 == 0);
+    DOOR_REQUIRE(lda >= K && ldw >= K && lda % 8 == 0 && ldw % 8 == 0);
+    if (epilogue == EPI_KV_HEADMAJOR) {
+        DOOR_REQUIRE(T > 0 && H > 0 && n_seg > 0 && N % (H * 64) == 0);
+        DOOR_REQUIRE((long long)n_seg * T == M);
+    } else {
+        DOOR_REQUIRE(ldc >= N && ldc % 8 == 0);
+    }
+    GemmArgs g{static_cast<const bf16_t*>(a_dev), static_cast<const bf16_t*>(w_dev), out_dev, bias_dev, M, N, K, lda, ldw, ldc, T, H, n_seg};
+    LAUNCH(launch_gemm(epilogue, g, (hipStream_t)stream));
+    HIP_TRY(hipGetLastError());
+    return YMT3_OK;
+}
+
+extern "C" int ymt3_test_rmsnorm(ymt3_handle h, const float* x_dev, const float* gain_dev, void* out_dev, int M, int d, float eps, void* stream) {
+    int rc = check_call(h, 0);
+    if (rc) return rc;
+    DOOR_PTR(x_dev); DOOR_PTR(gain_dev); DOOR_PTR(out_dev);
+    DOOR_REQUIRE(M > 0 && d > 0 && d % 4 == 0);
+    LAUNCH(launch_rmsnorm(x_dev, gain_dev, static_cast<bf16_t*>(out_dev), M, d, eps, (hipStream_t)stream));
+    HIP_TRY(hipGetLastError());
+    return YMT3_OK;
+}
+
+extern "C" int ymt3_test_enc_attention(ymt3_handle h, const void* q_dev, int ldq, const void* k_dev, const void* v_dev, int ldkv,
+                                       const float* bias_off_dev, void* out_dev, int B, int T, int H, void* stream) {
+    int rc = check_call(h, 0);
+    if (rc) return rc;
+    DOOR_PTR(q_dev); DOOR_PTR(k_dev); DOOR_PTR(v_dev); DOOR_PTR(bias_off_dev); DOOR_PTR(out_dev);
+    DOOR_REQUIRE(T == 64 || T == 128 || T == 256 || T == 512);
+    DOOR_REQUIRE(B > 0 && H > 0 && H <= 65535 && B <= 65535);
+    DOOR_REQUIRE(ldq >= H * 64 && ldkv >= H * 64 && ldq % 8 == 0 && ldkv % 8 == 0);
+    LAUNCH(launch_enc_attention_qkv(static_cast<const bf16_t*>(q_dev), ldq, static_cast<const bf16_t*>(k_dev), static_cast<const bf16_t*>(v_dev), ldkv,
+                                    bias_off_dev, static_cast<bf16_t*>(out_dev), B, T, H, (hipStream_t)stream));
+    HIP_TRY(hipGetLastError());
+    return YMT3_OK;
+}
+
+extern "C" int ymt3_test_seq_attention(ymt3_handle h, const ymt3_seq_attn_args* args, void* stream) {
+    int rc = check_call(h, 0);
+    if (rc) return rc;
+    if (!args) FAIL(YMT3_ERR_ARG, "%s: args is null", __func__);
+    const ymt3_seq_attn_args& c = *args;
+    DOOR_PTR(c.q); DOOR_PTR(c.k); DOOR_PTR(c.v); DOOR_PTR(c.out);
+    if (c.bias_off) DOOR_PTR(c.bias_off);
+    DOOR_REQUIRE(c.n_seq > 0 && c.H > 0 && c.inner_n > 0);
+    DOOR_REQUIRE(c.Tq > 0 && c.Tq % 16 == 0);
+    DOOR_REQUIRE(c.Tk == 32 || c.Tk == 64 || c.Tk == 128 || c.Tk == 256);
+    DOOR_REQUIRE(c.bias_off == nullptr || c.Tq == c.Tk);
+    DOOR_REQUIRE(c.q_step > 0 && c.kv_step > 0 && c.o_step > 0);
+    DOOR_REQUIRE(c.q_outer >= 0 && c.q_inner >= 0 && c.kv_outer >= 0 && c.kv_inner >= 0 && c.o_outer >= 0 && c.o_inner >= 0);
+    DOOR_REQUIRE((c.q_step | c.kv_step | c.o_step | c.q_outer | c.q_inner | c.kv_outer | c.kv_inner | c.o_outer | c.o_inner) % 8 == 0);
+    SeqAttnArgs a{};
+    a.q = static_cast<const bf16_t*>(c.q); a.k = static_cast<const bf16_t*>(c.k); a.v = static_cast<const bf16_t*>(c.v);
+    a.out = static_cast<bf16_t*>(c.out); a.bias_off = c.bias_off;
+    a.n_seq = c.n_seq; a.H = c.H; a.Tq = c.Tq; a.Tk = c.Tk; a.inner_n = c.inner_n;
+    a.q_outer = c.q_outer; a.q_inner = c.q_inner; a.q_step = c.q_step;
+    a.kv_outer = c.kv_outer; a.kv_inner = c.kv_inner; a.kv_step = c.kv_step;
+    a.o_outer = c.o_outer; a.o_inner = c.o_inner; a.o_step = c.o_step;
+    LAUNCH(launch_seq_attention(a, (hipStream_t)stream));
+    HIP_TRY(hipGetLastError());
+    return YMT3_OK;
+}
+
+extern "C" int ymt3_test_spec_embed(ymt3_handle h, const float* mel_dev, const float* w_dev, const void* pos_dev, const float* gain_dev,
+                                    void* out_dev, long long n_rows, int F, int d, float eps, void* stream) {
+    int rc = check_call(h, 0);
+    if (rc) return rc;
+    DOOR_PTR(mel_dev); DOOR_PTR(w_dev); DOOR_PTR(pos_dev); DOOR_PTR(gain_dev); DOOR_PTR(out_dev);
+    DOOR_REQUIRE(n_rows > 0 && F > 0 && d > 0 && d % 4 == 0 && d <= 256);
+    LAUNCH(launch_spec_embed(mel_dev, w_dev, static_cast<const bf16_t*>(pos_dev), gain_dev, static_cast<bf16_t*>(out_dev), n_rows, F, d, eps,
+                             (hipStream_t)stream));
+    HIP_TRY(hipGetLastError());
+    return YMT3_OK;
+}
+#undef DOOR_PTR
+#undef DOOR_REQUIRE
+
 extern "C" int ymt3_profile_decode(ymt3_handle h, const void* enc_dev, int B, int n_steps, int stride, int32_t* tokens_dev,
                                    float* ms_by_class, int32_t* launches_by_class, void* stream) {
     int rc = check_call(h, B);

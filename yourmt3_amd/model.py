@@ -1011,3 +1011,78 @@ class YourMT3:
         c = torch.empty(M, N, device=self.device, dtype=torch.float32)
         _lib.check(self._lib.ymt3_test_gemm(self._handle, _ptr(a_bf16.contiguous()), _ptr(w_bf16.contiguous()), _ptr(c), M, N, K, self._stream()))
         return c
+
+    # ------------------------------------------------------------------ per-kernel test doors (include/ymt3.h)
+    # Debug entry points: each runs ONE production launcher on caller-owned tensors.  The C side refuses what it can see from a raw pointer;
+    # the extent every tensor must have is computed HERE from the shape and the strides, and a smaller tensor is refused before the call.
+    def _door(self, name: str, t: torch.Tensor, dtype, need: int) -> torch.Tensor:
+        if t.device != self.device or t.dtype != dtype or not t.is_contiguous():
+            raise ValueError(f"{name}: needs a contiguous {dtype} tensor on {self.device}")
+        if need <= 0 or t.numel() < need:
+            raise ValueError(f"{name}: {t.numel()} elements, the shape and strides reach {need}")
+        return t
+
+    def test_gemm_ex(self, epilogue: int, a: torch.Tensor, w: torch.Tensor, out: torch.Tensor, M: int, N: int, K: int, lda: Optional[int] = None,
+                     ldw: Optional[int] = None, ldc: Optional[int] = None, bias: Optional[torch.Tensor] = None, T: int = 0, H: int = 0,
+                     n_seg: int = 0) -> torch.Tensor:
+        """out (+)= a[M][K] (row stride lda) w[N][K]^T with epilogue 0 f32 (+ bias), 1 bf16, 2 bf16 relu, 3 f32 +=, 4 bf16 head-major
+        [N / (H 64)][n_seg][H][T][64]; `out` is written in place (row stride ldc) and returned."""
+        lda, ldw, ldc = K if lda is None else lda, K if ldw is None else ldw, N if ldc is None else ldc
+        self._door("a", a, torch.bfloat16, (M - 1) * lda + K)
+        self._door("w", w, torch.bfloat16, (N - 1) * ldw + K)
+        self._door("out", out, torch.float32 if epilogue in (0, 3) else torch.bfloat16, M * N if epilogue == 4 else (M - 1) * ldc + N)
+        if bias is not None:
+            self._door("bias", bias, torch.float32, N)
+        _lib.check(self._lib.ymt3_test_gemm_ex(self._handle, int(epilogue), _ptr(a), _ptr(w), _ptr(out), _ptr(bias), M, N, K, lda, ldw, ldc, T, H,
+                                               n_seg, self._stream()))
+        return out
+
+    def test_rmsnorm(self, x: torch.Tensor, gain: torch.Tensor, out: torch.Tensor, M: int, d: int, eps: float) -> torch.Tensor:
+        self._door("x", x, torch.float32, M * d)
+        self._door("gain", gain, torch.float32, d)
+        self._door("out", out, torch.bfloat16, M * d)
+        _lib.check(self._lib.ymt3_test_rmsnorm(self._handle, _ptr(x), _ptr(gain), _ptr(out), M, d, float(eps), self._stream()))
+        return out
+
+    def test_enc_attention(self, q: torch.Tensor, ldq: int, k: torch.Tensor, v: torch.Tensor, ldkv: int, bias_off: torch.Tensor, out: torch.Tensor,
+                           B: int, T: int, H: int) -> torch.Tensor:
+        """rows q + (b T + t) ldq + 64 h, k|v + (b T + t) ldkv + 64 h; out [B T][64 H].  q, k, v may be views into one fused buffer."""
+        self._door("q", q, torch.bfloat16, (B * T - 1) * ldq + H * 64)
+        self._door("k", k, torch.bfloat16, (B * T - 1) * ldkv + H * 64)
+        self._door("v", v, torch.bfloat16, (B * T - 1) * ldkv + H * 64)
+        self._door("bias_off", bias_off, torch.float32, H * (2 * T - 1))
+        self._door("out", out, torch.bfloat16, B * T * H * 64)
+        _lib.check(self._lib.ymt3_test_enc_attention(self._handle, _ptr(q), ldq, _ptr(k), _ptr(v), ldkv, _ptr(bias_off), _ptr(out), B, T, H,
+                                                     self._stream()))
+        return out
+
+    def test_seq_attention(self, q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, out: torch.Tensor, bias_off: Optional[torch.Tensor], n_seq: int,
+                           H: int, Tq: int, Tk: int, inner_n: int, q_strides, kv_strides, o_strides) -> torch.Tensor:
+        """SeqAttnArgs of csrc/kernels.h; every *_strides is (outer, inner, step) in elements."""
+        def reach(st, n_pos):
+            last = n_seq - 1                                      # the furthest start: the last sequence, or the last of the row before it
+            starts = [(s // inner_n) * st[0] + (s % inner_n) * st[1] for s in (last, last - last % inner_n - 1) if s >= 0]
+            return max(starts) + (n_pos - 1) * st[2] + H * 64
+        if min(n_seq, H, Tq, Tk, inner_n) <= 0 or min(tuple(q_strides) + tuple(kv_strides) + tuple(o_strides)) < 0:
+            raise ValueError("counts must be positive and strides non-negative")
+        self._door("q", q, torch.bfloat16, reach(q_strides, Tq))
+        self._door("k", k, torch.bfloat16, reach(kv_strides, Tk))
+        self._door("v", v, torch.bfloat16, reach(kv_strides, Tk))
+        self._door("out", out, torch.bfloat16, reach(o_strides, Tq))
+        if bias_off is not None:
+            self._door("bias_off", bias_off, torch.float32, H * (2 * Tk - 1))
+        a = _lib.SeqAttnArgs(q.data_ptr(), k.data_ptr(), v.data_ptr(), out.data_ptr(), bias_off.data_ptr() if bias_off is not None else None,
+                             n_seq, H, Tq, Tk, inner_n, *[int(s) for s in tuple(q_strides) + tuple(kv_strides) + tuple(o_strides)])
+        _lib.check(self._lib.ymt3_test_seq_attention(self._handle, ctypes.byref(a), self._stream()))
+        return out
+
+    def test_spec_embed(self, mel: torch.Tensor, w: torch.Tensor, pos: torch.Tensor, gain: torch.Tensor, out: torch.Tensor, n_rows: int, F: int,
+                        d: int, eps: float) -> torch.Tensor:
+        self._door("mel", mel, torch.float32, n_rows)
+        self._door("w", w, torch.float32, d)
+        self._door("pos", pos, torch.bfloat16, F * d)
+        self._door("gain", gain, torch.float32, d)
+        self._door("out", out, torch.bfloat16, n_rows * d)
+        _lib.check(self._lib.ymt3_test_spec_embed(self._handle, _ptr(mel), _ptr(w), _ptr(pos), _ptr(gain), _ptr(out), n_rows, F, d, float(eps),
+                                                  self._stream()))
+        return out
