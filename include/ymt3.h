@@ -856,6 +856,56 @@ int ymt3_test_seq_attention(ymt3_handle h, const ymt3_seq_attn_args* args, void*
 int ymt3_test_spec_embed(ymt3_handle h, const float* mel_dev, const float* w_dev, const void* pos_dev, const float* gain_dev, void* out_dev,
                          long long n_rows, int F, int d, float eps, void* stream);
 
+/* Per-kernel test doors of the decoder step's SEPARATE-LAUNCH kernels (the merged, polling kernels -- attention pair, GEMM chain, step kernel,
+ * MoE chain -- need a resident grid and have no door; their bits are tied to these launches by the bit-identity tests).  Same rules as the
+ * encoder's doors: one production launcher each, nothing on the production path calls them, YMT3_ERR_ARG with a text for a null or
+ * misaligned pointer, for everything the launcher would refuse and for everything it silently assumes; extents are the caller's duty
+ * (yourmt3_amd/model.py).  The decode position: `row_pos` (int32 per row, indexed by the absolute row) or, when that is NULL, `step`, which
+ * the door places in a DecodeShared block of its own (allocated at first use, freed with the handle): the handle's loop state, caches,
+ * counters and graph cache are not touched, and a decode call gives the same bits after any door call.
+ *
+ * ymt3_test_dec_gemm: launch_dec_gemm.  mode 0 QKV + cache append, 1 bf16, 2 bf16 relu, 3 f32 logits (all four: x = x_f32[R][K] normed with
+ * gain and the 32 carried sum(h^2) partials ssq[t][row], K = 512), 4 residual: out_f32[r][n] += a_bf16[R][K] . W[n]^T (N = 512, K in {512,
+ * 1024, 2048}; + the eight `part` rows [R][8][512] when given) and ssq[n / 16][r] = this tile's share of sum(h_new^2).  Rows are
+ * [row0, row0 + R) of every row-indexed buffer; ssq_stride >= row0 + R.  Mode 0: N = 3 * H * 64; columns [0, H*64) go to out_bf16[r][.],
+ * the K and V thirds to cache[((r * H + h) * L + pos) * 64 + d]; `table` (not NULL) takes the packed row as table[r * N + n] instead.
+ * pend_y [2R][K] (modes 0 and 3): x = x_f32 + (y[2r] + y[2r + 1]), sum(x^2) taken by the kernel; mode 0 also stores x to h_out.
+ * mid_rows: row count from which the mid-size tile kernel runs (< 0: the built-in 512, 0: never); refused when it selects that kernel for a
+ * shape it has no instantiation for. */
+typedef struct ymt3_dec_gemm_args {
+    const float* x_f32; const void* a_bf16; const float* gain; const void* W;
+    void* out_bf16; float* out_f32; void* kcache; void* vcache;
+    float* ssq; const float* part; const float* pend_y; float* h_out; void* table;
+    const int32_t* row_pos;
+    int32_t row0, R, N, K, H, L, ssq_stride, mid_rows, step;
+    float eps;
+} ymt3_dec_gemm_args;
+int ymt3_test_dec_gemm(ymt3_handle h, int mode, const ymt3_dec_gemm_args* args, void* stream);
+/* ymt3_test_dec_attention: launch_dec_attention, or launch_dec_attention_beam when `anc` is given.  One (row, head) per workgroup, rows
+ * [row0, row0 + R), heads of 64; slab (r / rows_per_kv, h) of k / v starts at ((r / rows_per_kv) * H + h) * slab_keys * 64.
+ * self_attn != 0: keys 0 .. pos of the slab, bias f32 [H][bias_stride == slab_keys] by distance; wo bf16 [512][H*64] (H == 8): no `out`,
+ * opart f32 [R][8][512] instead.  self_attn == 0: n_keys_const in [1, slab_keys] keys, no bias; wq bf16 [H*64][512] (d == 512): the query
+ * is projected from the residual row x_f32[r] (gain, and ssq partials or ipart [R][8][512] with H == 8) instead of read from q.
+ * force_many: the 2-waves-per-(row, head) form.  anc u8 [2][anc_rows][anc_pitch], W: beam search (self-attention only). */
+typedef struct ymt3_dec_attn_args {
+    const void* q; const void* k; const void* v; void* out;
+    const float* bias; const int32_t* row_pos;
+    const void* wq; const float* x_f32; const float* gain; const float* ssq; const float* ipart;
+    const void* wo; float* opart;
+    const uint8_t* anc;
+    int32_t self_attn, step, n_keys_const, slab_keys, rows_per_kv, row0, R, H, bias_stride, ssq_stride, force_many, anc_rows, anc_pitch, W, d;
+    float eps;
+} ymt3_dec_attn_args;
+int ymt3_test_dec_attention(ymt3_handle h, const ymt3_dec_attn_args* args, void* stream);
+/* ymt3_test_mc_cross_attention: launch_mc_cross_attention.  Rows row0 + seg * n_channels + channel; k / v bf16 [n_seg][H][T][64];
+ * n_channels in [2, 16], T in {128, 256, 512}, d == 512, ssq_stride >= row0 + n_seg * n_channels. */
+typedef struct ymt3_mc_cross_args {
+    const float* x_f32; const float* gain; const float* ssq; const void* wq; const void* k; const void* v; void* out;
+    int32_t row0, n_seg, n_channels, H, T, ssq_stride, d;
+    float eps;
+} ymt3_mc_cross_args;
+int ymt3_test_mc_cross_attention(ymt3_handle h, const ymt3_mc_cross_args* args, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -47,11 +47,9 @@ def ulp_bf16(x):
     return torch.ldexp(torch.ones_like(x, dtype=torch.float64), ex.clamp(min=-125) - 8)
 
 
-def check_bf16(got, o, beta, relu=False):
-    """The criterion of the module docstring.  got: the device's bf16 values; o, beta: float64.  relu: o = max(ref, 0) was applied to a
-    reference `o` passed UNclamped: an element with |ref| <= beta may be 0 or within beta.  Returns the figures and `ok`; worst_err_over_allowance
-    is the largest |got - o| / (beta + ulp) over the unstable elements (a bf16 result hides the device's value before its rounding, so up to
-    half an ulp of every figure is that rounding and 0.5 is what a perfect device shows on an unstable element)."""
+def judge_bf16(got, o, beta, relu=False):
+    """The criterion of the module docstring, per element: (stable, bad_stable, bad_unstable, err, allow, rounds_to) as tensors of o's shape.
+    check_bf16 reduces them to figures; tests/dec_kernel_model.py reduces them per (row, head) for its candidate rule."""
     got, o, beta = got.double(), o.double(), beta.double()
     ref = o
     if relu:
@@ -66,9 +64,18 @@ def check_bf16(got, o, beta, relu=False):
     bad_unstable = ~stable & ~(err <= allow)
     if relu:
         bad_unstable &= ~((ref.abs() <= beta) & (got == 0))
+    return stable, bad_stable, bad_unstable, err, allow, rb(o)
+
+
+def check_bf16(got, o, beta, relu=False):
+    """The criterion of the module docstring.  got: the device's bf16 values; o, beta: float64.  relu: o = max(ref, 0) was applied to a
+    reference `o` passed UNclamped: an element with |ref| <= beta may be 0 or within beta.  Returns the figures and `ok`; worst_err_over_allowance
+    is the largest |got - o| / (beta + ulp) over the unstable elements (a bf16 result hides the device's value before its rounding, so up to
+    half an ulp of every figure is that rounding and 0.5 is what a perfect device shows on an unstable element)."""
+    stable, bad_stable, bad_unstable, err, allow, ro = judge_bf16(got, o, beta, relu)
     n_un = int((~stable).sum())
-    return dict(elements=int(o.numel()), stable_share=float(stable.double().mean()), stable_wrong=int(bad_stable.sum()),
-                unstable=n_un, unstable_differ=int((~stable & (got != rb(o))).sum()), unstable_wrong=int(bad_unstable.sum()),
+    return dict(elements=int(stable.numel()), stable_share=float(stable.double().mean()), stable_wrong=int(bad_stable.sum()),
+                unstable=n_un, unstable_differ=int((~stable & (got.double() != ro)).sum()), unstable_wrong=int(bad_unstable.sum()),
                 worst_err_over_allowance=float((err / allow)[~stable].max()) if n_un else 0.0,
                 ok=not bool(bad_stable.any() or bad_unstable.any()))
 

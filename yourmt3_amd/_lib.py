@@ -36,6 +36,7 @@ SYMBOLS = [
     "ymt3_velocity_create", "ymt3_velocity_destroy", "ymt3_note_velocities",
     "ymt3_beats_create", "ymt3_beats_destroy", "ymt3_track_beats", "ymt3_beat_positions",
     "ymt3_test_gemm_ex", "ymt3_test_rmsnorm", "ymt3_test_enc_attention", "ymt3_test_seq_attention", "ymt3_test_spec_embed",
+    "ymt3_test_dec_gemm", "ymt3_test_dec_attention", "ymt3_test_mc_cross_attention",
 ]
 
 _lib = None
@@ -86,6 +87,26 @@ class SeqAttnArgs(ctypes.Structure):
     _fields_ = [(n, ctypes.c_void_p) for n in ("q", "k", "v", "out", "bias_off")] + [
         (n, ctypes.c_int32) for n in ("n_seq", "H", "Tq", "Tk", "inner_n")] + [
         (n, ctypes.c_int64) for n in ("q_outer", "q_inner", "q_step", "kv_outer", "kv_inner", "kv_step", "o_outer", "o_inner", "o_step")]
+
+
+class DecGemmArgs(ctypes.Structure):
+    """ymt3_dec_gemm_args of include/ymt3.h"""
+    _fields_ = [(n, ctypes.c_void_p) for n in ("x_f32", "a_bf16", "gain", "W", "out_bf16", "out_f32", "kcache", "vcache", "ssq", "part", "pend_y",
+                                               "h_out", "table", "row_pos")] + [
+        (n, ctypes.c_int32) for n in ("row0", "R", "N", "K", "H", "L", "ssq_stride", "mid_rows", "step")] + [("eps", ctypes.c_float)]
+
+
+class DecAttnArgs(ctypes.Structure):
+    """ymt3_dec_attn_args of include/ymt3.h"""
+    _fields_ = [(n, ctypes.c_void_p) for n in ("q", "k", "v", "out", "bias", "row_pos", "wq", "x_f32", "gain", "ssq", "ipart", "wo", "opart", "anc")] + [
+        (n, ctypes.c_int32) for n in ("self_attn", "step", "n_keys_const", "slab_keys", "rows_per_kv", "row0", "R", "H", "bias_stride", "ssq_stride",
+                                      "force_many", "anc_rows", "anc_pitch", "W", "d")] + [("eps", ctypes.c_float)]
+
+
+class McCrossArgs(ctypes.Structure):
+    """ymt3_mc_cross_args of include/ymt3.h"""
+    _fields_ = [(n, ctypes.c_void_p) for n in ("x_f32", "gain", "ssq", "wq", "k", "v", "out")] + [
+        (n, ctypes.c_int32) for n in ("row0", "n_seg", "n_channels", "H", "T", "ssq_stride", "d")] + [("eps", ctypes.c_float)]
 
 
 class YMT3Error(RuntimeError):
@@ -270,6 +291,12 @@ def load() -> ctypes.CDLL:
     lib.ymt3_test_seq_attention.restype = i32
     lib.ymt3_test_spec_embed.argtypes = [vp, vp, vp, vp, vp, vp, ll, i32, i32, f32, vp]
     lib.ymt3_test_spec_embed.restype = i32
+    lib.ymt3_test_dec_gemm.argtypes = [vp, i32, ctypes.POINTER(DecGemmArgs), vp]
+    lib.ymt3_test_dec_gemm.restype = i32
+    lib.ymt3_test_dec_attention.argtypes = [vp, ctypes.POINTER(DecAttnArgs), vp]
+    lib.ymt3_test_dec_attention.restype = i32
+    lib.ymt3_test_mc_cross_attention.argtypes = [vp, ctypes.POINTER(McCrossArgs), vp]
+    lib.ymt3_test_mc_cross_attention.restype = i32
     for n in ("ymt3_logmel", "ymt3_encode", "ymt3_decode_greedy", "ymt3_transcribe_segments", "ymt3_test_gemm"):
         getattr(lib, n).restype = i32
     if lib.ymt3_abi_version() != 3:

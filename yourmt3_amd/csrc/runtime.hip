@@ -111,6 +111,7 @@ struct ymt3_ctx {
     int* host_rows = nullptr;           // pinned [maxR]: copy of `finished` for the host's retire/admit decisions
     bool slot_mode = false;
     DecodeShared* shared = nullptr;     // [MAX_CHAINS] per-chain loop state
+    DecodeShared* test_shared = nullptr;   // the decoder test doors' own block (ymt3_test_dec_gemm / _dec_attention), allocated at first use
     hipStream_t cap_stream = nullptr;
     // Decode rows are independent, so a batch CAN be cut into `n_chains` contiguous row ranges whose step graphs replay
     // concurrently on separate HIP streams.  Measured on MI355X in both rounds (profiles/r01_chain_sweep.txt with one host thread
@@ -1964,6 +1965,156 @@ extern "C" int ymt3_test_spec_embed(ymt3_handle h, const float* mel_dev, const f
     DOOR_REQUIRE(n_rows > 0 && F > 0 && d > 0 && d % 4 == 0 && d <= 256);
     LAUNCH(launch_spec_embed(mel_dev, w_dev, static_cast<const bf16_t*>(pos_dev), gain_dev, static_cast<bf16_t*>(out_dev), n_rows, F, d, eps,
                              (hipStream_t)stream));
+    HIP_TRY(hipGetLastError());
+    return YMT3_OK;
+}
+
+// The decoder doors' own DecodeShared (never the handle's h->shared, which the decode loop owns): zero but for `step`, set on the caller's stream
+// in front of the launch that reads it.
+static int door_shared(ymt3_ctx* c, int step, hipStream_t s, const DecodeShared** out) {
+    if (!c->test_shared) {
+        if (dev_alloc(c, (void**)&c->test_shared, sizeof(DecodeShared))) return YMT3_ERR_HIP;
+        HIP_TRY(hipMemset(c->test_shared, 0, sizeof(DecodeShared)));
+    }
+    static_assert(offsetof(DecodeShared, step) == 0, "the position is the block's first word");
+    HIP_TRY(hipMemsetD32Async(reinterpret_cast<hipDeviceptr_t>(c->test_shared), step, 1, s));
+    *out = c->test_shared;
+    return YMT3_OK;
+}
+
+extern "C" int ymt3_test_dec_gemm(ymt3_handle h, int mode, const ymt3_dec_gemm_args* args, void* stream) {
+    int rc = check_call(h, 0);
+    if (rc) return rc;
+    if (!args) FAIL(YMT3_ERR_ARG, "%s: args is null", __func__);
+    const ymt3_dec_gemm_args& c = *args;
+    DOOR_REQUIRE(mode >= DG_NORM_QKV_CACHE && mode <= DG_RESID);
+    const bool norm = mode != DG_RESID, qkv = mode == DG_NORM_QKV_CACHE;
+    DOOR_PTR(c.W);
+    DOOR_REQUIRE(c.R > 0 && c.row0 >= 0 && c.row0 <= 0xffff && c.R <= 0xffff && c.N > 0 && c.N % 16 == 0);
+    DOOR_REQUIRE(norm ? c.K == 512 : (c.K == 512 || c.K == 1024 || c.K == 2048));
+    DOOR_REQUIRE(c.pend_y == nullptr || qkv || mode == DG_NORM_LOGITS);
+    DOOR_REQUIRE(c.part == nullptr || !norm);
+    DOOR_REQUIRE(c.table == nullptr || (qkv && c.pend_y == nullptr));
+    DOOR_REQUIRE(c.h_out == nullptr || (qkv && c.pend_y != nullptr));
+    if (norm) {
+        DOOR_PTR(c.x_f32); DOOR_PTR(c.gain);
+        if (c.pend_y) DOOR_PTR(c.pend_y);
+        else { DOOR_PTR(c.ssq); DOOR_REQUIRE(c.ssq_stride >= c.row0 + c.R); }
+    } else {
+        DOOR_PTR(c.a_bf16); DOOR_PTR(c.out_f32); DOOR_PTR(c.ssq);
+        DOOR_REQUIRE(c.ssq_stride >= c.row0 + c.R);
+        DOOR_REQUIRE(c.N == 16 * SSQ_TILES);
+        if (c.part) DOOR_PTR(c.part);
+    }
+    if (qkv) {
+        DOOR_REQUIRE(c.H > 0 && c.H <= 0xff && c.L > 0 && c.L <= 0xfffff && c.N == 3 * c.H * 64);
+        if (c.table) DOOR_PTR(c.table);
+        else { DOOR_PTR(c.out_bf16); DOOR_PTR(c.kcache); DOOR_PTR(c.vcache); }
+        if (c.pend_y) { DOOR_PTR(c.h_out); DOOR_REQUIRE(c.h_out != c.x_f32); }
+        if (c.row_pos) DOOR_PTR(c.row_pos);
+        else DOOR_REQUIRE(c.step >= 0 && c.step < c.L);
+    } else if (mode == DG_NORM_LOGITS) {
+        DOOR_PTR(c.out_f32);
+    } else if (norm) {
+        DOOR_PTR(c.out_bf16);
+    }
+    const int mid = c.mid_rows >= 0 ? c.mid_rows : DEC_GEMM_MID_ROWS;
+    if (mid > 0 && c.R >= mid)      // the mid-size tile kernel: launch_dec_gemm falls back to the 16-row tiles where it has no instantiation
+        DOOR_REQUIRE(c.N % 64 == 0 && c.part == nullptr && c.pend_y == nullptr && c.table == nullptr && (c.K == 512 || (c.K == 2048 && !norm)));
+    DecGemmArgs a{};
+    a.x_f32 = c.x_f32; a.gain = c.gain; a.a_bf16 = static_cast<const bf16_t*>(c.a_bf16); a.W = static_cast<const bf16_t*>(c.W);
+    a.row0 = c.row0; a.R = c.R; a.N = c.N; a.K = c.K; a.eps = c.eps;
+    a.out_bf16 = static_cast<bf16_t*>(c.out_bf16); a.out_f32 = c.out_f32;
+    a.kcache = static_cast<bf16_t*>(c.kcache); a.vcache = static_cast<bf16_t*>(c.vcache); a.H = c.H; a.L = c.L;
+    a.row_pos = c.row_pos; a.ssq = c.ssq; a.ssq_stride = c.ssq_stride;
+    a.part = c.part; a.pend_y = c.pend_y; a.h_out = c.h_out; a.mid_rows = c.mid_rows; a.table = static_cast<bf16_t*>(c.table);
+    if (qkv) {                      // (the table build reads the position too, and ignores it)
+        rc = door_shared(h, c.row_pos || c.table ? 0 : c.step, (hipStream_t)stream, &a.shared);
+        if (rc) return rc;
+    }
+    LAUNCH(launch_dec_gemm(mode, a, (hipStream_t)stream));
+    HIP_TRY(hipGetLastError());
+    return YMT3_OK;
+}
+
+extern "C" int ymt3_test_dec_attention(ymt3_handle h, const ymt3_dec_attn_args* args, void* stream) {
+    int rc = check_call(h, 0);
+    if (rc) return rc;
+    if (!args) FAIL(YMT3_ERR_ARG, "%s: args is null", __func__);
+    const ymt3_dec_attn_args& c = *args;
+    const bool self = c.self_attn != 0;
+    DOOR_PTR(c.k); DOOR_PTR(c.v);
+    DOOR_REQUIRE(c.R > 0 && c.row0 >= 0 && c.row0 <= 0xffff && c.R <= 0xffff && c.H >= 1 && c.H <= 0xff);
+    DOOR_REQUIRE(c.slab_keys >= 1 && c.slab_keys <= 0xfffff && c.rows_per_kv >= 1 && c.rows_per_kv <= 0xff);
+    const bool many = c.force_many || c.R * c.H > 2048;
+    DecAttnArgs a{};
+    if (self) {
+        DOOR_PTR(c.q); DOOR_PTR(c.bias);
+        DOOR_REQUIRE(c.bias_stride == c.slab_keys && c.n_keys_const == 0);
+        DOOR_REQUIRE(c.wq == nullptr && c.x_f32 == nullptr && c.gain == nullptr && c.ssq == nullptr && c.ipart == nullptr);
+        if (c.row_pos) DOOR_PTR(c.row_pos);
+        else DOOR_REQUIRE(c.step >= 0 && c.step < c.slab_keys);
+        if (c.wo) {
+            DOOR_PTR(c.wo); DOOR_PTR(c.opart);
+            DOOR_REQUIRE(c.H == 8 && !many && c.anc == nullptr);
+        } else {
+            DOOR_PTR(c.out);
+            DOOR_REQUIRE(c.opart == nullptr);
+        }
+        if (c.anc) {
+            DOOR_PTR(c.anc);
+            DOOR_REQUIRE(c.W >= 1 && c.W <= BEAM_MAX && c.R % c.W == 0 && c.row0 % c.W == 0 && c.rows_per_kv == 1);
+            DOOR_REQUIRE(c.anc_pitch % 16 == 0 && c.anc_pitch > c.slab_keys && c.anc_pitch <= 48 * 1024 && c.row0 + c.R <= c.anc_rows);
+        }
+    } else {
+        DOOR_PTR(c.out);
+        DOOR_REQUIRE(c.bias == nullptr && c.row_pos == nullptr && c.anc == nullptr && c.wo == nullptr && c.opart == nullptr);
+        DOOR_REQUIRE(c.n_keys_const >= 1 && c.n_keys_const <= c.slab_keys && c.n_keys_const <= 0xfff);
+        if (c.wq) {
+            DOOR_PTR(c.wq); DOOR_PTR(c.x_f32); DOOR_PTR(c.gain);
+            DOOR_REQUIRE(c.d == 512 && !c.force_many);          // one thread per element of the residual row; 8 waves whatever the row count
+            if (c.ipart) { DOOR_PTR(c.ipart); DOOR_REQUIRE(c.H == 8 && c.ssq == nullptr && !many); }
+            else { DOOR_PTR(c.ssq); DOOR_REQUIRE(c.ssq_stride >= c.row0 + c.R); }
+        } else {
+            DOOR_PTR(c.q);
+            DOOR_REQUIRE(c.x_f32 == nullptr && c.gain == nullptr && c.ssq == nullptr && c.ipart == nullptr);
+        }
+    }
+    a.q = static_cast<const bf16_t*>(c.q); a.k = static_cast<const bf16_t*>(c.k); a.v = static_cast<const bf16_t*>(c.v);
+    a.out = static_cast<bf16_t*>(c.out); a.bias = c.bias; a.row_pos = c.row_pos;
+    a.n_keys_const = c.n_keys_const; a.slab_keys = c.slab_keys; a.rows_per_kv = c.rows_per_kv;
+    a.row0 = c.row0; a.R = c.R; a.H = c.H; a.bias_stride = c.bias_stride;
+    a.wq = static_cast<const bf16_t*>(c.wq); a.x_f32 = c.x_f32; a.gain = c.gain; a.ssq = c.ssq; a.ssq_stride = c.ssq_stride; a.eps = c.eps;
+    a.wo = static_cast<const bf16_t*>(c.wo); a.opart = c.opart; a.ipart = c.ipart; a.force_many = c.force_many ? 1 : 0;
+    if (self) {
+        rc = door_shared(h, c.row_pos ? 0 : c.step, (hipStream_t)stream, &a.shared);
+        if (rc) return rc;
+    }
+    if (c.anc) {
+        const BeamAttn ba{c.anc, c.anc_rows, c.anc_pitch, c.W};
+        LAUNCH(launch_dec_attention_beam(a, ba, (hipStream_t)stream));
+    } else {
+        LAUNCH(launch_dec_attention(self, a, (hipStream_t)stream));
+    }
+    HIP_TRY(hipGetLastError());
+    return YMT3_OK;
+}
+
+extern "C" int ymt3_test_mc_cross_attention(ymt3_handle h, const ymt3_mc_cross_args* args, void* stream) {
+    int rc = check_call(h, 0);
+    if (rc) return rc;
+    if (!args) FAIL(YMT3_ERR_ARG, "%s: args is null", __func__);
+    const ymt3_mc_cross_args& c = *args;
+    DOOR_PTR(c.x_f32); DOOR_PTR(c.gain); DOOR_PTR(c.ssq); DOOR_PTR(c.wq); DOOR_PTR(c.k); DOOR_PTR(c.v); DOOR_PTR(c.out);
+    DOOR_REQUIRE(c.n_seg > 0 && c.n_seg <= 65535 && c.H >= 1 && c.H <= 0xff && c.row0 >= 0 && c.row0 <= 0xffff);
+    DOOR_REQUIRE(c.n_channels >= 2 && c.n_channels <= 16);
+    DOOR_REQUIRE(c.T == 128 || c.T == 256 || c.T == 512);
+    DOOR_REQUIRE(c.d == 512 && c.ssq_stride >= c.row0 + c.n_seg * c.n_channels);
+    McCrossArgs a{};
+    a.x_f32 = c.x_f32; a.gain = c.gain; a.ssq = c.ssq; a.ssq_stride = c.ssq_stride; a.wq = static_cast<const bf16_t*>(c.wq);
+    a.k = static_cast<const bf16_t*>(c.k); a.v = static_cast<const bf16_t*>(c.v); a.out = static_cast<bf16_t*>(c.out);
+    a.row0 = c.row0; a.n_seg = c.n_seg; a.n_channels = c.n_channels; a.H = c.H; a.T = c.T; a.eps = c.eps;
+    LAUNCH(launch_mc_cross_attention(a, (hipStream_t)stream));
     HIP_TRY(hipGetLastError());
     return YMT3_OK;
 }

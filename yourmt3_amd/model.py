@@ -1086,3 +1086,161 @@ class YourMT3:
         _lib.check(self._lib.ymt3_test_spec_embed(self._handle, _ptr(mel), _ptr(w), _ptr(pos), _ptr(gain), _ptr(out), n_rows, F, d, float(eps),
                                                   self._stream()))
         return out
+
+    # ---- decoder step kernels (separate launches).  Everything is validated BEFORE the library is touched, so the refusals can be tested
+    # without a device: geometry first (ValueError), then every tensor's extent, then the position values.
+    @staticmethod
+    def _need(cond: bool, text: str) -> None:
+        if not cond:
+            raise ValueError("needs " + text)
+
+    def _positions(self, row_pos: Optional[torch.Tensor], step: int, row0: int, R: int, L: int) -> None:
+        if row_pos is None:
+            self._need(0 <= step < L, f"0 <= step < {L}")
+            return
+        self._door("row_pos", row_pos, torch.int32, row0 + R)
+        p = row_pos[row0:row0 + R]
+        self._need(bool(((p >= 0) & (p < L)).all()), f"every row_pos in [0, {L})")
+
+    def test_dec_gemm(self, mode: int, *, W: torch.Tensor, R: int, N: int, K: int, row0: int = 0, eps: float = 1e-6,
+                      x: Optional[torch.Tensor] = None, a: Optional[torch.Tensor] = None, gain: Optional[torch.Tensor] = None,
+                      out_bf16: Optional[torch.Tensor] = None, out_f32: Optional[torch.Tensor] = None, kcache: Optional[torch.Tensor] = None,
+                      vcache: Optional[torch.Tensor] = None, H: int = 0, L: int = 0, ssq: Optional[torch.Tensor] = None, ssq_stride: int = 0,
+                      part: Optional[torch.Tensor] = None, pend_y: Optional[torch.Tensor] = None, h_out: Optional[torch.Tensor] = None,
+                      table: Optional[torch.Tensor] = None, mid_rows: int = 0, step: int = 0, row_pos: Optional[torch.Tensor] = None) -> None:
+        """ymt3_test_dec_gemm (include/ymt3.h): mode 0 QKV + cache append, 1 bf16, 2 bf16 relu, 3 f32 logits, 4 residual.  Every row-indexed
+        tensor starts at row 0 and must reach row0 + R; outputs are written in place."""
+        need, rows = self._need, row0 + R
+        need(0 <= mode <= 4 and R > 0 and 0 <= row0 <= 0xffff and R <= 0xffff and N > 0 and N % 16 == 0, "a mode in 0..4, R > 0, 0 <= row0, N % 16 == 0")
+        need(K == 512 if mode != 4 else K in (512, 1024, 2048), "K = 512 (mode 4: 512, 1024 or 2048)")
+        need(pend_y is None or mode in (0, 3), "pend_y with modes 0 and 3 only")
+        need(part is None or mode == 4, "part with mode 4 only")
+        need(table is None or (mode == 0 and pend_y is None), "table with mode 0 and without pend_y only")
+        need(h_out is None or (mode == 0 and pend_y is not None), "h_out with mode 0 and pend_y only")
+        mid = mid_rows if mid_rows >= 0 else 512
+        if mid > 0 and R >= mid:
+            need(N % 64 == 0 and part is None and pend_y is None and table is None and (K == 512 or (K == 2048 and mode == 4)),
+                 "a shape the mid-size tile kernel is instantiated for")
+        self._door("W", W, torch.bfloat16, N * K)
+        if mode == 4:
+            need(N == 512, "N == 512 in mode 4")
+            need(a is not None and out_f32 is not None and ssq is not None, "a, out_f32 and ssq in mode 4")
+            self._door("a", a, torch.bfloat16, rows * K)
+            if part is not None:
+                self._door("part", part, torch.float32, rows * 8 * N)
+        else:
+            need(x is not None and gain is not None, "x and gain")
+            self._door("x", x, torch.float32, rows * K)
+            self._door("gain", gain, torch.float32, K)
+            if pend_y is not None:
+                self._door("pend_y", pend_y, torch.float32, 2 * rows * K)
+            else:
+                need(ssq is not None, "ssq")
+        if ssq is not None:
+            need(ssq_stride >= rows, "ssq_stride >= row0 + R")
+            self._door("ssq", ssq, torch.float32, 31 * ssq_stride + rows)
+        if mode == 0:
+            need(H > 0 and L > 0 and N == 3 * H * 64, "N == 3 * H * 64")
+            if table is not None:
+                self._door("table", table, torch.bfloat16, rows * N)
+            else:
+                need(out_bf16 is not None and kcache is not None and vcache is not None, "out_bf16, kcache and vcache")
+                self._door("out_bf16", out_bf16, torch.bfloat16, rows * H * 64)
+                self._door("kcache", kcache, torch.bfloat16, rows * H * L * 64)
+                self._door("vcache", vcache, torch.bfloat16, rows * H * L * 64)
+                self._positions(row_pos, step, row0, R, L)
+            if pend_y is not None:
+                need(h_out is not None and h_out.data_ptr() != x.data_ptr(), "h_out, another buffer than x")
+                self._door("h_out", h_out, torch.float32, rows * K)
+        elif mode in (3, 4):
+            need(out_f32 is not None, "out_f32")
+            self._door("out_f32", out_f32, torch.float32, rows * N)
+        else:
+            need(out_bf16 is not None, "out_bf16")
+            self._door("out_bf16", out_bf16, torch.bfloat16, rows * N)
+        p = lambda t: t.data_ptr() if t is not None else None
+        c = _lib.DecGemmArgs(p(x), p(a), p(gain), p(W), p(out_bf16), p(out_f32), p(kcache), p(vcache), p(ssq), p(part), p(pend_y), p(h_out),
+                             p(table), p(row_pos), row0, R, N, K, H, L, ssq_stride, mid_rows, step, float(eps))
+        _lib.check(self._lib.ymt3_test_dec_gemm(self._handle, int(mode), ctypes.byref(c), self._stream()))
+
+    def test_dec_attention(self, *, self_attn: bool, k: torch.Tensor, v: torch.Tensor, R: int, H: int, slab_keys: int, row0: int = 0,
+                           q: Optional[torch.Tensor] = None, out: Optional[torch.Tensor] = None, bias: Optional[torch.Tensor] = None,
+                           step: int = 0, row_pos: Optional[torch.Tensor] = None, n_keys_const: int = 0, rows_per_kv: int = 1,
+                           force_many: bool = False, wo: Optional[torch.Tensor] = None, opart: Optional[torch.Tensor] = None,
+                           wq: Optional[torch.Tensor] = None, x: Optional[torch.Tensor] = None, gain: Optional[torch.Tensor] = None,
+                           ssq: Optional[torch.Tensor] = None, ssq_stride: int = 0, ipart: Optional[torch.Tensor] = None, eps: float = 1e-6,
+                           anc: Optional[torch.Tensor] = None, anc_rows: int = 0, anc_pitch: int = 0, W: int = 0) -> None:
+        """ymt3_test_dec_attention (include/ymt3.h).  k / v hold the slabs of kv rows 0 .. (row0 + R - 1) / rows_per_kv (beam: of rows
+        0 .. row0 + R - 1, whole groups)."""
+        need, rows = self._need, row0 + R
+        need(R > 0 and 0 <= row0 <= 0xffff and R <= 0xffff and 1 <= H <= 255 and 1 <= slab_keys <= 0xfffff and 1 <= rows_per_kv <= 255,
+             "R > 0, 0 <= row0, 1 <= H <= 255, 1 <= slab_keys, 1 <= rows_per_kv <= 255")
+        many = force_many or R * H > 2048
+        kv_rows = rows if anc is not None else (rows - 1) // rows_per_kv + 1
+        self._door("k", k, torch.bfloat16, kv_rows * H * slab_keys * 64)
+        self._door("v", v, torch.bfloat16, kv_rows * H * slab_keys * 64)
+        if self_attn:
+            need(q is not None and bias is not None and n_keys_const == 0, "q and bias, n_keys_const == 0 (self-attention)")
+            need(wq is None and x is None and gain is None and ssq is None and ipart is None, "no fused query projection (self-attention)")
+            self._door("q", q, torch.bfloat16, rows * H * 64)
+            self._door("bias", bias, torch.float32, H * slab_keys)
+            self._positions(row_pos, step, row0, R, slab_keys)
+            if wo is not None:
+                need(H == 8 and not many and anc is None and opart is not None and out is None, "H == 8, the 8-wave form, opart and no out (wo)")
+                self._door("wo", wo, torch.bfloat16, 512 * H * 64)
+                self._door("opart", opart, torch.float32, rows * 8 * 512)
+            else:
+                need(out is not None and opart is None, "out")
+            if anc is not None:
+                need(1 <= W <= 8 and R % W == 0 and row0 % W == 0 and rows_per_kv == 1, "1 <= W <= 8 dividing R and row0, rows_per_kv == 1 (beam)")
+                need(anc_pitch % 16 == 0 and slab_keys < anc_pitch <= 48 * 1024 and rows <= anc_rows,
+                     "anc_pitch % 16 == 0, slab_keys < anc_pitch <= 48 KiB, row0 + R <= anc_rows (beam)")
+                self._door("anc", anc, torch.uint8, 2 * anc_rows * anc_pitch)
+        else:
+            need(bias is None and row_pos is None and anc is None and wo is None and opart is None and out is not None,
+                 "out and neither bias, row_pos, anc nor wo (cross-attention)")
+            need(1 <= n_keys_const <= min(slab_keys, 0xfff), "1 <= n_keys_const <= min(slab_keys, 4095)")
+            if wq is not None:
+                need(x is not None and gain is not None and not force_many, "x and gain, the 8-wave form (wq)")
+                need(x.numel() % 512 == 0 and gain.numel() == 512, "residual rows of 512 elements (wq)")
+                self._door("wq", wq, torch.bfloat16, H * 64 * 512)
+                self._door("x", x, torch.float32, rows * 512)
+                self._door("gain", gain, torch.float32, 512)
+                if ipart is not None:
+                    need(H == 8 and ssq is None and not many, "H == 8, no ssq, at most 2048 (row, head) pairs (ipart)")
+                    self._door("ipart", ipart, torch.float32, rows * 8 * 512)
+                else:
+                    need(ssq is not None and ssq_stride >= rows, "ssq with ssq_stride >= row0 + R")
+                    self._door("ssq", ssq, torch.float32, 31 * ssq_stride + rows)
+            else:
+                need(q is not None and x is None and gain is None and ssq is None and ipart is None, "q and no projection operands")
+                self._door("q", q, torch.bfloat16, rows * H * 64)
+        if out is not None:
+            self._door("out", out, torch.bfloat16, rows * H * 64)
+        p = lambda t: t.data_ptr() if t is not None else None
+        c = _lib.DecAttnArgs(p(q), p(k), p(v), p(out), p(bias), p(row_pos), p(wq), p(x), p(gain), p(ssq), p(ipart), p(wo), p(opart), p(anc),
+                             int(bool(self_attn)), step, n_keys_const, slab_keys, rows_per_kv, row0, R, H, slab_keys if self_attn else 0, ssq_stride,
+                             int(bool(force_many)), anc_rows, anc_pitch, W, 512 if wq is not None else 0, float(eps))
+        _lib.check(self._lib.ymt3_test_dec_attention(self._handle, ctypes.byref(c), self._stream()))
+
+    def test_mc_cross_attention(self, *, x: torch.Tensor, gain: torch.Tensor, ssq: torch.Tensor, ssq_stride: int, wq: torch.Tensor,
+                                k: torch.Tensor, v: torch.Tensor, out: torch.Tensor, n_seg: int, n_channels: int, H: int, T: int, row0: int = 0,
+                                eps: float = 1e-6) -> None:
+        """ymt3_test_mc_cross_attention (include/ymt3.h): rows row0 + seg * n_channels + channel; k / v [n_seg][H][T][64]."""
+        need = self._need
+        need(0 < n_seg <= 65535 and 1 <= H <= 255 and 0 <= row0 <= 0xffff, "0 < n_seg, 1 <= H <= 255, 0 <= row0")
+        need(2 <= n_channels <= 16, "2 <= n_channels <= 16")
+        need(T in (128, 256, 512), "T in {128, 256, 512}")
+        rows = row0 + n_seg * n_channels
+        need(ssq_stride >= rows, "ssq_stride >= row0 + n_seg * n_channels")
+        need(gain.numel() == 512 and x.numel() % 512 == 0, "residual rows of 512 elements")
+        self._door("x", x, torch.float32, rows * 512)
+        self._door("gain", gain, torch.float32, 512)
+        self._door("ssq", ssq, torch.float32, 31 * ssq_stride + rows)
+        self._door("wq", wq, torch.bfloat16, H * 64 * 512)
+        self._door("k", k, torch.bfloat16, n_seg * H * T * 64)
+        self._door("v", v, torch.bfloat16, n_seg * H * T * 64)
+        self._door("out", out, torch.bfloat16, rows * H * 64)
+        c = _lib.McCrossArgs(x.data_ptr(), gain.data_ptr(), ssq.data_ptr(), wq.data_ptr(), k.data_ptr(), v.data_ptr(), out.data_ptr(), row0, n_seg,
+                             n_channels, H, T, ssq_stride, 512, float(eps))
+        _lib.check(self._lib.ymt3_test_mc_cross_attention(self._handle, ctypes.byref(c), self._stream()))
