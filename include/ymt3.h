@@ -759,8 +759,8 @@ int  ymt3_note_velocities(ymt3_handle h, ymt3_velocity v, const float* audio_dev
  * A counted pitched record's offset tick is at least its onset tick + 480 / Q.  A NaN time, an uncounted record, a record at or beyond
  * the count: -1.  Every entry of ticks_dev is written.
  * Both calls are asynchronous on `stream`, allocate nothing, read nothing back and leave the handle's decode state alone.  The object's
- * scratch is used by ymt3_track_beats: calls on one object are ordered by their stream.  Only beats are estimated: no bars, no time
- * signature, no downbeats. */
+ * scratch is used by ymt3_track_beats: calls on one object are ordered by their stream.  Bars, the time signature, downbeats and the
+ * key are the next section's (ymt3_track_bars). */
 typedef struct ymt3_beat_params {
     double  frames_per_second, bpm_min, bpm_max, bpm_prior, prior_octaves, tightness;
     int32_t window_frames, hop_frames, lag_step_max, onset_cap, n_programs, drum_program;
@@ -774,6 +774,54 @@ int  ymt3_track_beats(ymt3_handle h, ymt3_beats b, const void* notes_dev, long l
 int  ymt3_beat_positions(ymt3_handle h, ymt3_beats b, const int32_t* beats_dev, const long long* result_dev, const void* notes_dev,
                          long long n_notes, const int32_t* count_dev /* may be NULL */, int divisions, int32_t* ticks_dev /* [n_notes][2] */,
                          void* stream);
+
+/* ---- bars and key over note records and tracked beats --------------------------------------------------------------------------
+ * The beats give a tick a position; a ymt3_bars object gives every beat its metre and its place in the bar (so: the downbeats and the
+ * time signatures) and the file one key, from the records and the beats where ymt3_track_beats left them.  The rules are this project's
+ * own; the host specification is track_bars of yourmt3_amd/bars.py, and every output equals it bit for bit:
+ * everything is an integer, and times stay f64 until they are known to lie inside the slots or the frames.  Integer divisions below are
+ * floor divisions.
+ *
+ * Parameters (ymt3_bars_create refuses, YMT3_ERR_ARG, what is outside): frames_per_second finite and > 0; metres[0 .. n_metres), 1 to 5
+ * distinct values in [2, 6], their order being the tie order; near_div (nd) in [2, 64]; accent_cap in [1, 255]; w_long, w_kick in
+ * [0, 15]; 0 <= kick_lo <= kick_hi <= 127; w_accent in [0, 1024]; switch_cost in [0, 4096]; 1 <= n_programs <= 256, drum_program in
+ * [0, n_programs); max_beats in [1, 2^20 + 1]; max_notes in [1, 2^20], which keeps a chroma cell inside 32 bits.
+ *   slots     K beats b (K is read from beat_result_dev[0] on the device, clamped to [0, max_beats]).  With K >= 2: D[i] = b[i+1] - b[i],
+ *             D[K-1] = D[K-2]; lo[0] = b[0] - D[0] / nd, lo[i] = b[i] - D[i-1] / nd; hi[i] = lo[i+1], hi[K-1] = b[K-1] + D[K-1] - D[K-1] / nd.
+ *   accent    a record counts by the rule of the note metrics; the others are skipped.  F = rint(onset fps) in f64.  A counted record
+ *             with F inside slot i and F <= b[i] + D[i] / nd adds to a[i]: 1, + w_kick for a drum with pitch in [kick_lo, kick_hi],
+ *             + w_long for a pitched record with F(offset) - F >= D[i] (f64).  a[i] = min(a[i], accent_cap).
+ *   chroma    a counted pitched record's span [F(on), max(F(off), F(on) + 1)) clipped to [0, n_frames) adds the frames it shares with
+ *             slot i to c[i][pitch mod 12], for every slot it overlaps.  sum[i] = sum of c[i]; n[i][pc] = c[i][pc] 1024 / sum[i];
+ *             h[0] = 0, h[i] = sum over pc of |n[i][pc] - n[i-1][pc]| if both sums are positive, else 0.
+ *   salience  d[i] = w_accent a[i] + h[i]; mean_d = (sum of d) / K.
+ *   bar path  states (m, k), m in metres' order, k = 0 .. m-1, k = 0 the downbeat; r(i, m, 0) = (60 / m) (m - 1) d[i],
+ *             r(i, m, k > 0) = -(60 / m) d[i].  V[0][(m, k)] = r(0, m, k); V[i][(m, k > 0)] = V[i-1][(m, k-1)] + r;
+ *             V[i][(m, 0)] = max(V[i-1][(m, m-1)], max over m' != m of V[i-1][(m', m'-1)] - switch_cost 60 mean_d) + r, ties to staying,
+ *             then to the earliest m'.  The end is the first state in state order with V[K-1] maximal; the path is followed back.
+ *   key       tot[pc] = sum over i of c[i][pc]; S[mode][t] = sum over pc of tot[pc] T_mode[(pc - t) mod 12] with the two tables of
+ *             yourmt3_amd/bars.py (KEY_MAJOR, KEY_MINOR); key = 12 mode + t of the maximum, major before minor, then the smaller t; -1
+ *             if the sum of tot is 0.
+ * ymt3_track_bars: beats_dev / beat_result_dev as ymt3_track_beats wrote them; notes_dev / n_notes / count_dev as there, n_notes at most
+ * the object's max_notes.  metre_dev[i] = 256 m + k for i < K, the rest is left alone; max_beats, its length, is at least the object's.
+ * result_dev[8]: n_downbeats, max V[K-1], mean_d, key, the best S, the second-best S, skipped records, 0.  With K < 2 nothing is written
+ * to metre_dev and result_dev = {0, 0, 0, -1, 0, 0, skipped, 0}.
+ * Asynchronous on `stream`, allocates nothing, reads nothing back and leaves the handle's decode state alone.  The object's scratch is
+ * used by the call: calls on one object are ordered by their stream.  YMT3_ERR_ARG, with handle and object still usable, for a NULL or
+ * misaligned beats_dev, beat_result_dev, metre_dev or result_dev, a NULL notes_dev with n_notes > 0, a misaligned notes_dev or count_dev,
+ * n_notes outside [0, max_notes], n_frames outside [1, 2^20], max_beats below the object's.  One key per file and the denominator 4:
+ * modulations and compound metres are out of scope. */
+typedef struct ymt3_bar_params {
+    double  frames_per_second;
+    int32_t n_metres, metres[5];
+    int32_t near_div, accent_cap, w_long, w_kick, kick_lo, kick_hi, w_accent, switch_cost, n_programs, drum_program;
+} ymt3_bar_params;
+typedef struct ymt3_bars_s* ymt3_bars;
+int  ymt3_bars_create(ymt3_handle h, const ymt3_bar_params* params, long long max_beats, long long max_notes, ymt3_bars* out);
+void ymt3_bars_destroy(ymt3_bars b);
+int  ymt3_track_bars(ymt3_handle h, ymt3_bars b, const int32_t* beats_dev, const long long* beat_result_dev, const void* notes_dev,
+                     long long n_notes, const int32_t* count_dev /* may be NULL */, long long n_frames, int32_t* metre_dev, long long max_beats,
+                     long long* result_dev /* [8] */, void* stream);
 
 /* Measurement hook (bench.py `roofline`): decode eagerly (no graph) and bracket every kernel launch of
  * every `stride`-th step (positions stride/2, 3*stride/2, ...) with HIP events on `stream`; synchronises the stream before returning.

@@ -3,7 +3,7 @@
 
 __all__ = ["YMT3Config", "YourMT3", "TaskManager", "transcribe", "score_notes", "evaluate", "note_metrics", "NoteMetrics", "piano_roll", "frame_metrics",
            "FrameMetricCounts", "PianoRoll", "baseline_config", "LiveTranscriber", "NoteStream", "dtw_align", "warp_notes", "Alignment", "Aligner",
-           "align", "note_velocities", "NoteVelocity", "estimate_velocities", "track_beats", "beat_positions", "BeatTracker", "estimate_beats"]
+           "align", "note_velocities", "NoteVelocity", "estimate_velocities", "track_beats", "beat_positions", "BeatTracker", "estimate_beats", "track_bars", "BarTracker", "estimate_bars"]
 
 
 def __getattr__(name):
@@ -58,4 +58,7 @@ def __getattr__(name):
     if name in ("track_beats", "beat_positions", "BeatTracker", "estimate_beats"):
         from . import beats
         return getattr(beats, name)
+    if name in ("track_bars", "BarTracker", "estimate_bars"):
+        from . import bars
+        return getattr(bars, name)
     raise AttributeError(name)

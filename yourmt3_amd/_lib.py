@@ -35,6 +35,7 @@ SYMBOLS = [
     "ymt3_detokenize_push", "ymt3_detokenize_finish",
     "ymt3_velocity_create", "ymt3_velocity_destroy", "ymt3_note_velocities",
     "ymt3_beats_create", "ymt3_beats_destroy", "ymt3_track_beats", "ymt3_beat_positions",
+    "ymt3_bars_create", "ymt3_bars_destroy", "ymt3_track_bars",
     "ymt3_test_gemm_ex", "ymt3_test_rmsnorm", "ymt3_test_enc_attention", "ymt3_test_seq_attention", "ymt3_test_spec_embed",
     "ymt3_test_dec_gemm", "ymt3_test_dec_attention", "ymt3_test_mc_cross_attention",
 ]
@@ -80,6 +81,13 @@ class BeatParams(ctypes.Structure):
     """ymt3_beat_params of include/ymt3.h"""
     _fields_ = [(n, ctypes.c_double) for n in ("frames_per_second", "bpm_min", "bpm_max", "bpm_prior", "prior_octaves", "tightness")] + [
         (n, ctypes.c_int32) for n in ("window_frames", "hop_frames", "lag_step_max", "onset_cap", "n_programs", "drum_program")]
+
+
+class BarParams(ctypes.Structure):
+    """ymt3_bar_params of include/ymt3.h"""
+    _fields_ = [("frames_per_second", ctypes.c_double), ("n_metres", ctypes.c_int32), ("metres", ctypes.c_int32 * 5)] + [
+        (n, ctypes.c_int32) for n in ("near_div", "accent_cap", "w_long", "w_kick", "kick_lo", "kick_hi", "w_accent", "switch_cost", "n_programs",
+                                      "drum_program")]
 
 
 class SeqAttnArgs(ctypes.Structure):
@@ -280,6 +288,12 @@ def load() -> ctypes.CDLL:
     lib.ymt3_track_beats.restype = i32
     lib.ymt3_beat_positions.argtypes = [vp, vp, vp, vp, vp, ll, vp, i32, vp, vp]
     lib.ymt3_beat_positions.restype = i32
+    lib.ymt3_bars_create.argtypes = [vp, ctypes.POINTER(BarParams), ll, ll, ctypes.POINTER(vp)]
+    lib.ymt3_bars_create.restype = i32
+    lib.ymt3_bars_destroy.argtypes = [vp]
+    lib.ymt3_bars_destroy.restype = None
+    lib.ymt3_track_bars.argtypes = [vp, vp, vp, vp, vp, ll, vp, ll, vp, ll, vp, vp]
+    lib.ymt3_track_bars.restype = i32
     f32 = ctypes.c_float
     lib.ymt3_test_gemm_ex.argtypes = [vp, i32, vp, vp, vp, vp, i32, i32, i32, i32, i32, i32, i32, i32, i32, vp]
     lib.ymt3_test_gemm_ex.restype = i32

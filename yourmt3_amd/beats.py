@@ -6,7 +6,7 @@ onsets are an onset-strength signal.  The rules below are this repository's own,
 dynamic-programming beat tracker, written from memory and UNVERIFIED against any package.  `track_beats` and `beat_positions` are their host
 specification: numpy, integers throughout except the two tables (f64 libm calls, rounded to integers once) and the position expression (f64,
 no contraction).  `BeatTracker` is the device object (YourMT3.compile_beat_tracker; yourmt3_amd/csrc/beats.hip), which equals them bit for
-bit.  Only beats are estimated: bars, the time signature and downbeats are out of scope.
+bit.  Bars, the time signature, downbeats and the key are found on top of these beats by yourmt3_amd/bars.py.
 
 The rules.  fps = frames_per_second, Wn = window_frames, Hn = hop_frames, D = lag_step_max; all divisions of integers below are floor
 divisions.

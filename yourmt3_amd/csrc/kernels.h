@@ -266,6 +266,33 @@ struct BeatPositionArgs {
 };
 int launch_beat_positions(const BeatPositionArgs& a, hipStream_t stream);
 
+// ---------------------------------------------------------------- bars and key over note records and beats (bars.hip; include/ymt3.h, bars and key)
+constexpr long long BAR_MAX_FRAMES = 1LL << 20;
+constexpr long long BAR_MAX_BEATS = (1LL << 20) + 1, BAR_MAX_NOTES = 1LL << 20;
+constexpr int BAR_MAX_METRES = 5, BAR_MIN_METRE = 2, BAR_MAX_METRE = 6, BAR_MAX_PROGRAMS = 256;
+constexpr int BAR_ACC_WORDS = 16;                                       // tot[12], the sum of d, three spare
+struct BarArgs {
+    double frames_per_second;
+    int n_programs, drum_program;
+    int n_metres, metres[BAR_MAX_METRES];
+    int near_div, accent_cap, w_long, w_kick, kick_lo, kick_hi, w_accent, switch_cost;
+    const int32_t* beats;                 // [K] frames, strictly ascending
+    const long long* beat_result;         // track_beats' result: [0] is K, clamped to [0, max_beats]
+    long long max_beats;                  // the object's: what the scratch below holds
+    const DetokNote* notes;               // [n]
+    long long n;
+    const int32_t* count;                 // device count (or null): min(n, max(*count, 0)) records are live
+    long long n_frames;
+    unsigned* accent;                     // [max_beats] a
+    unsigned* chroma;                     // [max_beats][12] c
+    int32_t* salience;                    // [max_beats] d
+    unsigned short* choice;               // [max_beats] the downbeat states' back-pointers, 3 bits per metre
+    unsigned long long* acc;              // [BAR_ACC_WORDS]
+    int32_t* metre;                       // [>= max_beats]: the first K are written
+    long long* result;                    // [8]: n_downbeats, max V, mean_d, key, best S, second S, skipped, 0
+};
+int launch_track_bars(const BarArgs& a, hipStream_t stream);
+
 // ---------------------------------------------------------------- dense GEMM (gemm.hip)
 // C[M][N] (+)= A[M][K] (bf16, row stride lda) * W[N][K]^T (bf16, row stride ldw), fp32 accumulate.
 enum GemmEpilogue {

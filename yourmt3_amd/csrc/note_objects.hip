@@ -1,6 +1,6 @@
 // The note-side objects of the C ABI (include/ymt3.h): detokeniser and its incremental state, tokeniser, note metrics, piano roll / frame
-// metrics, aligner, note velocities, beat tracker.  Host logic only: argument checks, scratch, and the launches of detok.hip, tok.hip, metrics.hip, roll.hip,
-// align.hip, velocity.hip and beats.hip.  Of the handle they need the device and the configuration (runtime.h).  What they have in common is written once, at the top: the
+// metrics, aligner, note velocities, beat tracker, bar tracker.  Host logic only: argument checks, scratch, and the launches of detok.hip, tok.hip, metrics.hip, roll.hip,
+// align.hip, velocity.hip, beats.hip and bars.hip.  Of the handle they need the device and the configuration (runtime.h).  What they have in common is written once, at the top: the
 // create prologue, the owner check, the program and record-array checks, and the scratch list that both *_create and *_destroy walk.
 #include <algorithm>
 #include <cmath>
@@ -714,5 +714,82 @@ extern "C" int ymt3_beat_positions(ymt3_handle h, ymt3_beats b, const int32_t* b
     a.beats = beats_dev; a.result = result_dev; a.max_beats = beat_max_beats(b->max_frames, b->lag_min);
     a.notes = static_cast<const DetokNote*>(notes_dev); a.n = n_notes; a.count = n_notes ? count_dev : nullptr; a.ticks = ticks_dev;
     LAUNCH(launch_beat_positions(a, static_cast<hipStream_t>(stream)));
+    return YMT3_OK;
+}
+
+// ---------------------------------------------------------------- bars and key over note records and beats (include/ymt3.h)
+struct ymt3_bars_s {
+    ymt3_handle owner;
+    int device;
+    ymt3_bar_params p;
+    long long max_beats, max_notes;
+    unsigned* accent = nullptr;             // [max_beats]
+    unsigned* chroma = nullptr;             // [max_beats][12]
+    int32_t* salience = nullptr;            // [max_beats]
+    unsigned short* choice = nullptr;       // [max_beats]
+    unsigned long long* acc = nullptr;      // [BAR_ACC_WORDS]
+};
+
+static std::vector<Slot> slots(ymt3_bars b) {
+    const size_t B = (size_t)b->max_beats;
+    return {slot(&b->accent, B * sizeof(unsigned)), slot(&b->chroma, B * 12 * sizeof(unsigned)), slot(&b->salience, B * sizeof(int32_t)),
+            slot(&b->choice, B * sizeof(unsigned short)), slot(&b->acc, BAR_ACC_WORDS * sizeof(unsigned long long))};
+}
+extern "C" void ymt3_bars_destroy(ymt3_bars b) { destroy_object(b); }
+
+extern "C" int ymt3_bars_create(ymt3_handle h, const ymt3_bar_params* params, long long max_beats, long long max_notes, ymt3_bars* out) {
+    if (const int rc = create_prologue(reinterpret_cast<void**>(out), h, params, "params")) return rc;
+    const ymt3_bar_params& p = *params;
+    if (!std::isfinite(p.frames_per_second) || p.frames_per_second <= 0) FAIL(YMT3_ERR_ARG, "frames_per_second=%g must be finite and > 0", p.frames_per_second);
+    if (p.n_metres < 1 || p.n_metres > BAR_MAX_METRES) FAIL(YMT3_ERR_ARG, "n_metres=%d outside [1, %d]", p.n_metres, BAR_MAX_METRES);
+    for (int q = 0; q < p.n_metres; ++q) {
+        if (p.metres[q] < BAR_MIN_METRE || p.metres[q] > BAR_MAX_METRE)
+            FAIL(YMT3_ERR_ARG, "metres[%d]=%d outside [%d, %d]", q, p.metres[q], BAR_MIN_METRE, BAR_MAX_METRE);
+        for (int r = 0; r < q; ++r)
+            if (p.metres[r] == p.metres[q]) FAIL(YMT3_ERR_ARG, "metres[%d]=%d is given twice", q, p.metres[q]);
+    }
+    const struct { const char* name; int v, lo, hi; } ranged[] = {{"near_div", p.near_div, 2, 64}, {"accent_cap", p.accent_cap, 1, 255}, {"w_long", p.w_long, 0, 15},
+                                                                  {"w_kick", p.w_kick, 0, 15}, {"w_accent", p.w_accent, 0, 1024}, {"switch_cost", p.switch_cost, 0, 4096}};
+    for (const auto& q : ranged)
+        if (q.v < q.lo || q.v > q.hi) FAIL(YMT3_ERR_ARG, "%s=%d outside [%d, %d]", q.name, q.v, q.lo, q.hi);
+    if (p.kick_lo < 0 || p.kick_lo > p.kick_hi || p.kick_hi > 127)
+        FAIL(YMT3_ERR_ARG, "kick_lo=%d, kick_hi=%d must satisfy 0 <= kick_lo <= kick_hi <= 127", p.kick_lo, p.kick_hi);
+    if (const int rc = check_programs(p.n_programs, p.drum_program, BAR_MAX_PROGRAMS, "")) return rc;
+    if (max_beats < 1 || max_beats > BAR_MAX_BEATS) FAIL(YMT3_ERR_ARG, "max_beats=%lld outside [1, %lld]", max_beats, BAR_MAX_BEATS);
+    if (max_notes < 1 || max_notes > BAR_MAX_NOTES) FAIL(YMT3_ERR_ARG, "max_notes=%lld outside [1, %lld]", max_notes, BAR_MAX_NOTES);
+    HIP_TRY(hipSetDevice(handle_device(h)));
+    ymt3_bars b = new ymt3_bars_s{h, handle_device(h), p, max_beats, max_notes};
+    return allocate_object(b, slots(b), "bar tracker scratch", out);
+}
+
+extern "C" int ymt3_track_bars(ymt3_handle h, ymt3_bars b, const int32_t* beats_dev, const long long* beat_result_dev, const void* notes_dev,
+                               long long n_notes, const int32_t* count_dev, long long n_frames, int32_t* metre_dev, long long max_beats,
+                               long long* result_dev, void* stream) {
+    if (const int rc = check_owner(h, b, "bar tracker")) return rc;
+    if (!beats_dev) FAIL(YMT3_ERR_ARG, "beats_dev is NULL");
+    if (reinterpret_cast<uintptr_t>(beats_dev) % 4) FAIL(YMT3_ERR_ARG, "beats_dev is not aligned to 4 bytes");
+    if (!beat_result_dev) FAIL(YMT3_ERR_ARG, "beat_result_dev is NULL");
+    if (reinterpret_cast<uintptr_t>(beat_result_dev) % 8) FAIL(YMT3_ERR_ARG, "beat_result_dev is not aligned to 8 bytes");
+    if (const int rc = check_count("n_notes", n_notes, b->max_notes, "max_notes")) return rc;
+    if (const int rc = check_record_ptr("notes_dev", notes_dev, n_notes)) return rc;
+    if (reinterpret_cast<uintptr_t>(count_dev) % 4) FAIL(YMT3_ERR_ARG, "count_dev is not aligned to 4 bytes");
+    if (n_frames < 1 || n_frames > BAR_MAX_FRAMES) FAIL(YMT3_ERR_ARG, "n_frames=%lld outside [1, %lld]", n_frames, BAR_MAX_FRAMES);
+    if (!metre_dev) FAIL(YMT3_ERR_ARG, "metre_dev is NULL");
+    if (reinterpret_cast<uintptr_t>(metre_dev) % 4) FAIL(YMT3_ERR_ARG, "metre_dev is not aligned to 4 bytes");
+    if (max_beats < b->max_beats) FAIL(YMT3_ERR_ARG, "max_beats=%lld below the bar tracker's max_beats=%lld", max_beats, b->max_beats);
+    if (!result_dev) FAIL(YMT3_ERR_ARG, "result_dev is NULL");
+    if (reinterpret_cast<uintptr_t>(result_dev) % 8) FAIL(YMT3_ERR_ARG, "result_dev is not aligned to 8 bytes");
+    HIP_TRY(hipSetDevice(b->device));
+    BarArgs a{};
+    a.frames_per_second = b->p.frames_per_second; a.n_programs = b->p.n_programs; a.drum_program = b->p.drum_program;
+    a.n_metres = b->p.n_metres;
+    for (int q = 0; q < BAR_MAX_METRES; ++q) a.metres[q] = q < b->p.n_metres ? b->p.metres[q] : 0;
+    a.near_div = b->p.near_div; a.accent_cap = b->p.accent_cap; a.w_long = b->p.w_long; a.w_kick = b->p.w_kick; a.kick_lo = b->p.kick_lo;
+    a.kick_hi = b->p.kick_hi; a.w_accent = b->p.w_accent; a.switch_cost = b->p.switch_cost;
+    a.beats = beats_dev; a.beat_result = beat_result_dev; a.max_beats = b->max_beats;
+    a.notes = static_cast<const DetokNote*>(notes_dev); a.n = n_notes; a.count = n_notes ? count_dev : nullptr; a.n_frames = n_frames;
+    a.accent = b->accent; a.chroma = b->chroma; a.salience = b->salience; a.choice = b->choice; a.acc = b->acc;
+    a.metre = metre_dev; a.result = result_dev;
+    LAUNCH(launch_track_bars(a, static_cast<hipStream_t>(stream)));
     return YMT3_OK;
 }

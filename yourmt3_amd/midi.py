@@ -71,16 +71,20 @@ def notes_to_midi_bytes(notes: Sequence[Note]) -> bytes:
     return _smf_bytes(notes, {id(n): (_ticks(n.onset), _ticks(n.offset)) for n in notes}, [(0, TEMPO_US)])
 
 
-def _smf_bytes(notes: Sequence[Note], ticks: Dict[int, tuple], tempos) -> bytes:
-    """The file of `notes`: ticks[id(note)] = (onset tick, offset tick); `tempos` = [(tick, microseconds per beat)], ascending.  The
+def _smf_bytes(notes: Sequence[Note], ticks: Dict[int, tuple], tempos, conductor_events=()) -> bytes:
+    """The file of `notes`: ticks[id(note)] = (onset tick, offset tick); `tempos` = [(tick, microseconds per beat)], ascending;
+    `conductor_events` = [(tick, the bytes of a meta event)], ascending, merged into the conductor track before the tempo of the same tick.  The
     ticks are keyed by the note objects' identity: everything below, _fit_melodic_channels included, regroups the SAME objects and never
     copies a note (equal notes may carry different ticks, so the notes' values cannot be the key)."""
     by_prog: Dict[int, List[Note]] = {}
     for n in notes:
         by_prog.setdefault(DRUM_PROGRAM if n.is_drum else n.program, []).append(n)
     conductor, last = bytearray(), 0
-    for tick, us in tempos:
-        conductor += _vlq(tick - last) + b"\xff\x51\x03" + int(us).to_bytes(3, "big")
+    events = [(tick, 1, b"\xff\x51\x03" + int(us).to_bytes(3, "big")) for tick, us in tempos]
+    if conductor_events:
+        events = sorted(events + [(int(tick), 0, bytes(ev)) for tick, ev in conductor_events], key=lambda e: (e[0], e[1]))   # (stable: the given order at one tick)
+    for tick, _, ev in events:
+        conductor += _vlq(tick - last) + ev
         last = tick
     tracks = [bytes(conductor) + b"\x00\xff\x2f\x00"]
     by_prog = _fit_melodic_channels(by_prog)
@@ -137,6 +141,29 @@ def notes_to_midi_bytes_on_beats(notes: Sequence[Note], ticks, beats, frames_per
         raise ValueError(f"{len(notes)} notes but {len(pairs)} tick pairs")
     kept = [(n, t) for n, t in zip(notes, pairs) if t[0] >= 0 and (t[1] >= 0 or n.is_drum)]
     return _smf_bytes([n for n, _ in kept], {id(n): t for n, t in kept}, tempos)
+
+
+def notes_to_midi_bytes_on_bars(notes: Sequence[Note], ticks, beats, metre, key: int = -1, frames_per_second: float = 100.0) -> bytes:
+    """notes_to_midi_bytes_on_beats with bar lines and a key: `metre` (256 m + k of every beat) and `key` as bars.track_bars or
+    BarTracker give them.  The conductor track gains one FF 58 04 nn 02 18 08 (nn/4) per entry of bars.time_signatures and one
+    FF 59 02 sf mi at tick 0 (bars.key_signature; none for key -1), in tick order with the tempo events.  Without downbeats (fewer
+    than two beats among them) the bytes are exactly notes_to_midi_bytes_on_beats'."""
+    from .bars import key_signature, time_signatures
+    from .beats import tempo_map
+    notes = list(notes)
+    signatures = time_signatures(metre, beats)
+    tempos = tempo_map(beats, frames_per_second)
+    if not signatures or not tempos:
+        return notes_to_midi_bytes_on_beats(notes, ticks, beats, frames_per_second)
+    pairs = [(int(a), int(b)) for a, b in ticks]
+    if len(pairs) != len(notes):
+        raise ValueError(f"{len(notes)} notes but {len(pairs)} tick pairs")
+    kept = [(n, t) for n, t in zip(notes, pairs) if t[0] >= 0 and (t[1] >= 0 or n.is_drum)]
+    events = [(tick, b"\xff\x58\x04" + bytes([nn, 2, 24, 8])) for tick, nn in signatures]
+    if int(key) >= 0:
+        sf, mi = key_signature(key)
+        events.insert(1 if events[0][0] == 0 else 0, (0, b"\xff\x59\x02" + bytes([sf & 0xFF, mi])))
+    return _smf_bytes([n for n, _ in kept], {id(n): t for n, t in kept}, tempos, events)
 
 
 def write_midi(notes: Sequence[Note], path: str) -> str:
@@ -254,3 +281,17 @@ def read_midi_on_beats(data: bytes):
         return starts[i] + (tick - at[i]) * tempos[i][1] / (tpb * 1e6)
 
     return sorted(Note(sec(on), sec(off), drum, prog, pitch, v) for on, off, drum, prog, pitch, v in raw), tempos
+
+
+def read_midi_on_bars(data: bytes):
+    """Parse what notes_to_midi_bytes_on_bars writes -> (notes, tempo map) as read_midi_on_beats, then the time signatures as [(tick,
+    numerator)] (denominator 4 is asserted) and the key signature as (sf, mi), or None if the file has none."""
+    notes, tempos = read_midi_on_beats(data)
+    signatures, key = [], None
+    for _, tick, st, payload in _track_events(data)[1]:
+        if st == 0xFF and payload[0] == 0x58:
+            assert payload[2] == 2, "a denominator other than 4"
+            signatures.append((tick, payload[1]))
+        elif st == 0xFF and payload[0] == 0x59:
+            key = (payload[1] - 256 if payload[1] > 127 else payload[1], payload[2])
+    return notes, tempos, signatures, key

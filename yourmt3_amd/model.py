@@ -603,6 +603,14 @@ class YourMT3:
         from .beats import BeatTracker                                  # (not a name of this module: beats.py builds on it)
         return BeatTracker(self, max_frames, **params)
 
+    def compile_bar_tracker(self, max_beats: int, max_notes: int, **params):
+        """The device bar tracker (include/ymt3.h, bars and key; the rules and the host specification: yourmt3_amd/bars.py) with scratch
+        for up to `max_beats` beats, for calls of up to `max_notes` records.  `params`: frames_per_second, metres, near_div, accent_cap,
+        w_long, w_kick, kick_lo, kick_hi, w_accent, switch_cost, n_programs, drum_program (bars.DEFAULTS).  -> a bars.BarTracker, closed
+        with the model like every other device object."""
+        from .bars import BarTracker                                    # (not a name of this module: bars.py builds on it)
+        return BarTracker(self, max_beats, max_notes, **params)
+
     def compile_ingest_stream(self, sample_rate: int, n_channels: int = 1, dtype=torch.int16, max_chunk_frames: int = 1 << 16) -> IngestStream:
         """Streaming form of ingest() (include/ymt3.h, streaming ingest) for `n_channels`-channel PCM of `dtype` (int16 or float32) at
         `sample_rate`, pushed in chunks of at most `max_chunk_frames` frames."""

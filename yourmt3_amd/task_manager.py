@@ -557,7 +557,7 @@ class TaskManager:
         return table
 
     def tokens_to_notes_device(self, model, tokens, start_secs: Sequence[float], end_sec: float, scores=None,
-                               detokenizer=None, velocity=None, audio=None, beats=None, quantize: int = 0):
+                               detokenizer=None, velocity=None, audio=None, beats=None, quantize: int = 0, bars=None):
         """tokens_to_notes on the device -> (notes, n_invalid).  `tokens`: (n, K, L) integer ids on `model`'s GPU (any strides whose
         last dimension is contiguous, e.g. hypothesis 0 of a beam call's (n, K, N, L)); `scores`: the matching (n, K, L) f32 token scores
         or None; `start_secs` must be strictly increasing.  `detokenizer`: a YourMT3.compile_detokenizer object to reuse (None: one is
@@ -568,9 +568,14 @@ class TaskManager:
         `beats`: a YourMT3.compile_beat_tracker object: the beats are tracked on the records where they lie (over the frames of `end_sec`,
         beats.n_frames_of), every note gets its ticks (snapped to `quantize` steps per beat if that is not 0), and beats, tempo and ticks
         come back in the same copy: the result gains a third element, {"beats" (frames), "tempo" (lags per window), "ticks" ((n, 2), in
-        the returned notes' order)}."""
+        the returned notes' order)}.
+        `bars`: a YourMT3.compile_bar_tracker object (it needs `beats`, and the beat tracker's frames_per_second): metres, downbeats and
+        key are tracked on the same records and beats where they lie, and ride back in the same copy: the third element gains "metre"
+        (int32 (n_beats,), 256 m + k) and "bar_result" (int64 (8,), bars.track_bars' result)."""
         import torch
 
+        if bars is not None and beats is None:
+            raise ValueError("bars without beats: the bar tracker works on the beat tracker's beats")
         starts = np.asarray(list(start_secs), np.float64)
         if tokens.dim() != 3 or tokens.shape[1] != self.num_decoding_channels:
             raise ValueError(f"tokens must be (n, {self.num_decoding_channels}, L), got {tuple(tokens.shape)}")
@@ -585,7 +590,10 @@ class TaskManager:
             raise ValueError("velocity and audio go together")
         if n == 0 or L == 0:
             if beats is not None:
-                return [], 0, {"beats": np.zeros(0, np.int32), "tempo": np.zeros(0, np.int32), "ticks": np.zeros((0, 2), np.int32)}
+                none = {"beats": np.zeros(0, np.int32), "tempo": np.zeros(0, np.int32), "ticks": np.zeros((0, 2), np.int32)}
+                if bars is not None:
+                    none.update(metre=np.zeros(0, np.int32), bar_result=np.array([0, 0, 0, -1, 0, 0, 0, 0], np.int64))
+                return [], 0, none
             return [], 0
         own = detokenizer is None
         if own:
@@ -607,6 +615,9 @@ class TaskManager:
                 parts = [rec_dev[:nb]] + ([vel_dev[:n_notes]] if velocity is not None else [])
                 if beats is not None:
                     parts += [t.reshape(-1).view(torch.uint8) for t in (ticks_dev[:n_notes], result_dev, lags_dev, beats_dev)]
+                if bars is not None:                                     # on the live records: their number is known by now, the beats' is not
+                    metre_dev, bar_result_dev = bars.track(beats_dev, result_dev, rec_dev[:nb], n_frames_of(end_sec, beats.params["frames_per_second"]))
+                    parts += [t.view(torch.uint8) for t in (bar_result_dev, metre_dev)]
                 both = torch.cat(parts).cpu().numpy()
                 rec, o = both[:nb].view(NOTE_RECORD), nb
                 vel = None
@@ -617,6 +628,9 @@ class TaskManager:
                     n_beats = int(ints[2 * n_notes:2 * n_notes + 8].view(np.int64)[0])
                     o = 2 * n_notes + 8 + lags_dev.numel()
                     tracked = {"beats": ints[o:o + n_beats].copy(), "tempo": ints[2 * n_notes + 8:o].copy(), "ticks": ints[:2 * n_notes].reshape(-1, 2).copy()}
+                    if bars is not None:
+                        o += beats_dev.numel()
+                        tracked.update(bar_result=ints[o:o + 16].view(np.int64).copy(), metre=ints[o + 16:o + 16 + (n_beats if n_beats >= 2 else 0)].copy())
         finally:
             if own:
                 detokenizer.close()
