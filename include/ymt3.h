@@ -823,6 +823,55 @@ int  ymt3_track_bars(ymt3_handle h, ymt3_bars b, const int32_t* beats_dev, const
                      long long n_notes, const int32_t* count_dev /* may be NULL */, long long n_frames, int32_t* metre_dev, long long max_beats,
                      long long* result_dev /* [8] */, void* stream);
 
+/* ---- chords over note records and tracked beats -----------------------------------------------------------------------------------
+ * A ymt3_chords object gives every beat one chord, (quality, root) or N, from the records and the beats where ymt3_track_beats left
+ * them, and optionally the metre ymt3_track_bars wrote.  The rules are this project's own, UNVERIFIED against any
+ * package; the host specification is track_chords of yourmt3_amd/chords.py, and every output equals it bit for bit: everything is an
+ * integer, and times stay f64 until they are known to lie inside the frames.  Integer divisions below are floor divisions.
+ *
+ * Parameters (ymt3_chords_create refuses, YMT3_ERR_ARG, what is outside): frames_per_second finite and > 0; qualities[0 .. n_qualities),
+ * 1 to 8 distinct indices of the fixed table, their order being the state order and so the tie order; near_div (nd) in [2, 64];
+ * bass_div in [1, 64]; w_bass, w_none in [0, 1024]; change_cost, change_cost_down in [0, 4096]; 1 <= n_programs <= 256, drum_program in
+ * [0, n_programs); reserved is ignored; max_beats in [1, 2^20 + 1]; max_notes in [1, 2^20].
+ *   table     q: 0 maj {0,4,7}, 1 min {0,3,7}, 2 dim {0,3,6}, 3 aug {0,4,8}, 4 sus4 {0,5,7}, 5 "7" {0,4,7,10}, 6 maj7 {0,4,7,11},
+ *             7 min7 {0,3,7,10}; W_q = 591 for three tones, 512 for four (1024 / sqrt(n)).
+ *   slots     the bars': K beats b (K is read from beat_result_dev[0] on the device, clamped to [0, max_beats]); with K >= 2:
+ *             D[i] = b[i+1] - b[i], D[K-1] = D[K-2]; lo[0] = b[0] - D[0] / nd, lo[i] = b[i] - D[i-1] / nd; hi[i] = lo[i+1],
+ *             hi[K-1] = b[K-1] + D[K-1] - D[K-1] / nd.
+ *   chroma    the bars': a counted pitched record's span [F(on), max(F(off), F(on) + 1)) clipped to [0, n_frames) adds the frames it
+ *             shares with slot i to c[i][pitch mod 12], for every slot it overlaps.  n[i][pc] = c[i][pc] 1024 / max(sum of c[i], 1) (64 bits).
+ *   bass      bass[i] = the smallest pitch among the counted pitched records whose share with slot i satisfies
+ *             bass_div share >= hi[i] - lo[i]; 255 with none.
+ *   states    (q, r), q in qualities' order, r = 0 .. 11, then N last: S = 12 n_qualities + 1 <= 97.
+ *   emission  e[i][(q, r)] = W_q (sum over s in the intervals of q of n[i][(r + s) mod 12]) + (1024 w_bass if bass[i] < 128 and
+ *             bass[i] mod 12 = r); e[i][N] = 1024 w_none; e < 2^21.
+ *   path      V[0] = e[0].  For i >= 1: j* = the first state with V[i-1] maximal; P_i = 1024 change_cost_down if metre_dev is given and
+ *             metre_dev[i] & 255 = 0, else 1024 change_cost; jump = V[i-1][j*] - P_i; state s stays if V[i-1][s] >= jump, else it comes
+ *             from j*; V[i][s] = max(V[i-1][s], jump) + e[i][s] (0 <= V < 2^42).  The end is the first state with V[K-1] maximal; the
+ *             path is followed back.
+ * ymt3_track_chords: beats_dev / beat_result_dev as ymt3_track_beats wrote them; metre_dev as ymt3_track_bars wrote it (at least K
+ * entries), or NULL; notes_dev / n_notes / count_dev as there, n_notes at most the object's max_notes.  chord_dev[i] = 256 bass[i] +
+ * label for i < K, the rest is left alone; label = 12 q + r with q the table's index, 255 for N; chord_cap, its length, is at least the
+ * object's max_beats.  result_dev[8]: the number of runs of equal label, max V[K-1], the number of N beats, skipped records, 0, 0, 0, 0.
+ * With K < 2 nothing is written to chord_dev and result_dev = {0, 0, 0, skipped, 0, 0, 0, 0}.
+ * Asynchronous on `stream`, allocates nothing, reads nothing back and leaves the handle's decode state alone.  The object's scratch
+ * (68 bytes per beat) is used by the call: calls on one object are ordered by their stream.  YMT3_ERR_ARG, with handle and object
+ * still usable, for a NULL or misaligned beats_dev, beat_result_dev, chord_dev or result_dev, a misaligned metre_dev, a NULL notes_dev
+ * with n_notes > 0, a misaligned notes_dev or count_dev, n_notes outside [0, max_notes], n_frames outside [1, 2^20], chord_cap below the
+ * object's max_beats.  One chord per beat at the finest; chords beyond the table are out of scope. */
+typedef struct ymt3_chord_params {
+    double  frames_per_second;
+    int32_t n_qualities, qualities[8];
+    int32_t near_div, bass_div, w_bass, w_none, change_cost, change_cost_down, n_programs, drum_program, reserved;
+} ymt3_chord_params;
+typedef struct ymt3_chords_s* ymt3_chords;
+int  ymt3_chords_create(ymt3_handle h, const ymt3_chord_params* params, long long max_beats, long long max_notes, ymt3_chords* out);
+void ymt3_chords_destroy(ymt3_chords c);
+int  ymt3_track_chords(ymt3_handle h, ymt3_chords c, const int32_t* beats_dev, const long long* beat_result_dev,
+                       const int32_t* metre_dev /* may be NULL */, const void* notes_dev, long long n_notes,
+                       const int32_t* count_dev /* may be NULL */, long long n_frames, int32_t* chord_dev, long long chord_cap,
+                       long long* result_dev /* [8] */, void* stream);
+
 /* Measurement hook (bench.py `roofline`): decode eagerly (no graph) and bracket every kernel launch of
  * every `stride`-th step (positions stride/2, 3*stride/2, ...) with HIP events on `stream`; synchronises the stream before returning.
  * Classes: 0 qkv+cache GEMM, 1 self-attention, 2 self O-proj, 3 cross Q GEMM, 4 cross-attention,

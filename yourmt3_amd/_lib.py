@@ -36,6 +36,7 @@ SYMBOLS = [
     "ymt3_velocity_create", "ymt3_velocity_destroy", "ymt3_note_velocities",
     "ymt3_beats_create", "ymt3_beats_destroy", "ymt3_track_beats", "ymt3_beat_positions",
     "ymt3_bars_create", "ymt3_bars_destroy", "ymt3_track_bars",
+    "ymt3_chords_create", "ymt3_chords_destroy", "ymt3_track_chords",
     "ymt3_test_gemm_ex", "ymt3_test_rmsnorm", "ymt3_test_enc_attention", "ymt3_test_seq_attention", "ymt3_test_spec_embed",
     "ymt3_test_dec_gemm", "ymt3_test_dec_attention", "ymt3_test_mc_cross_attention",
 ]
@@ -88,6 +89,13 @@ class BarParams(ctypes.Structure):
     _fields_ = [("frames_per_second", ctypes.c_double), ("n_metres", ctypes.c_int32), ("metres", ctypes.c_int32 * 5)] + [
         (n, ctypes.c_int32) for n in ("near_div", "accent_cap", "w_long", "w_kick", "kick_lo", "kick_hi", "w_accent", "switch_cost", "n_programs",
                                       "drum_program")]
+
+
+class ChordParams(ctypes.Structure):
+    """ymt3_chord_params of include/ymt3.h"""
+    _fields_ = [("frames_per_second", ctypes.c_double), ("n_qualities", ctypes.c_int32), ("qualities", ctypes.c_int32 * 8)] + [
+        (n, ctypes.c_int32) for n in ("near_div", "bass_div", "w_bass", "w_none", "change_cost", "change_cost_down", "n_programs", "drum_program",
+                                      "reserved")]
 
 
 class SeqAttnArgs(ctypes.Structure):
@@ -294,6 +302,12 @@ def load() -> ctypes.CDLL:
     lib.ymt3_bars_destroy.restype = None
     lib.ymt3_track_bars.argtypes = [vp, vp, vp, vp, vp, ll, vp, ll, vp, ll, vp, vp]
     lib.ymt3_track_bars.restype = i32
+    lib.ymt3_chords_create.argtypes = [vp, ctypes.POINTER(ChordParams), ll, ll, ctypes.POINTER(vp)]
+    lib.ymt3_chords_create.restype = i32
+    lib.ymt3_chords_destroy.argtypes = [vp]
+    lib.ymt3_chords_destroy.restype = None
+    lib.ymt3_track_chords.argtypes = [vp, vp, vp, vp, vp, vp, ll, vp, ll, vp, ll, vp, vp]
+    lib.ymt3_track_chords.restype = i32
     f32 = ctypes.c_float
     lib.ymt3_test_gemm_ex.argtypes = [vp, i32, vp, vp, vp, vp, i32, i32, i32, i32, i32, i32, i32, i32, i32, vp]
     lib.ymt3_test_gemm_ex.restype = i32

@@ -293,6 +293,31 @@ struct BarArgs {
 };
 int launch_track_bars(const BarArgs& a, hipStream_t stream);
 
+// ---------------------------------------------------------------- chords over note records and beats (chords.hip; include/ymt3.h, chords)
+constexpr int CHORD_QUALITIES = 8;                                      // the fixed table: maj, min, dim, aug, sus4, 7, maj7, min7
+constexpr int CHORD_MAX_STATES = 12 * CHORD_QUALITIES + 1;              // (q, r), then N
+constexpr int CHORD_BACK_WORDS = 4;                                     // per beat: a stay bit per state, then j* (7 bits)
+struct ChordArgs {
+    double frames_per_second;
+    int n_programs, drum_program;
+    int n_qualities, qualities[CHORD_QUALITIES];                         // indices into the fixed table, in state order
+    int near_div, bass_div, w_bass, w_none, change_cost, change_cost_down;
+    const int32_t* beats;                 // [K] frames, strictly ascending
+    const long long* beat_result;         // track_beats' result: [0] is K, clamped to [0, max_beats]
+    long long max_beats;                  // the object's: what the scratch below holds
+    const int32_t* metre;                 // [K] 256 m + k of every beat, or null
+    const DetokNote* notes;               // [n]
+    long long n;
+    const int32_t* count;                 // device count (or null): min(n, max(*count, 0)) records are live
+    long long n_frames;
+    unsigned* chroma;                     // [max_beats][12] c
+    unsigned* bass;                       // [max_beats] the lowest long pitch, 255 with none
+    unsigned* back;                       // [max_beats][CHORD_BACK_WORDS] the back-pointers
+    int32_t* chord;                       // [>= max_beats]: the first K are written
+    long long* result;                    // [8]: runs, max V, N beats, skipped, 0, 0, 0, 0
+};
+int launch_track_chords(const ChordArgs& a, hipStream_t stream);
+
 // ---------------------------------------------------------------- dense GEMM (gemm.hip)
 // C[M][N] (+)= A[M][K] (bf16, row stride lda) * W[N][K]^T (bf16, row stride ldw), fp32 accumulate.
 enum GemmEpilogue {

@@ -1,6 +1,6 @@
 // The note-side objects of the C ABI (include/ymt3.h): detokeniser and its incremental state, tokeniser, note metrics, piano roll / frame
-// metrics, aligner, note velocities, beat tracker, bar tracker.  Host logic only: argument checks, scratch, and the launches of detok.hip, tok.hip, metrics.hip, roll.hip,
-// align.hip, velocity.hip, beats.hip and bars.hip.  Of the handle they need the device and the configuration (runtime.h).  What they have in common is written once, at the top: the
+// metrics, aligner, note velocities, beat tracker, bar tracker, chord tracker.  Host logic only: argument checks, scratch, and the launches of detok.hip, tok.hip, metrics.hip, roll.hip,
+// align.hip, velocity.hip, beats.hip, bars.hip and chords.hip.  Of the handle they need the device and the configuration (runtime.h).  What they have in common is written once, at the top: the
 // create prologue, the owner check, the program and record-array checks, and the scratch list that both *_create and *_destroy walk.
 #include <algorithm>
 #include <cmath>
@@ -791,5 +791,78 @@ extern "C" int ymt3_track_bars(ymt3_handle h, ymt3_bars b, const int32_t* beats_
     a.accent = b->accent; a.chroma = b->chroma; a.salience = b->salience; a.choice = b->choice; a.acc = b->acc;
     a.metre = metre_dev; a.result = result_dev;
     LAUNCH(launch_track_bars(a, static_cast<hipStream_t>(stream)));
+    return YMT3_OK;
+}
+
+// ---------------------------------------------------------------- chords over note records and beats (include/ymt3.h)
+struct ymt3_chords_s {
+    ymt3_handle owner;
+    int device;
+    ymt3_chord_params p;
+    long long max_beats, max_notes;
+    unsigned* chroma = nullptr;             // [max_beats][12]
+    unsigned* bass = nullptr;               // [max_beats]
+    unsigned* back = nullptr;               // [max_beats][CHORD_BACK_WORDS]
+};
+
+static std::vector<Slot> slots(ymt3_chords c) {
+    const size_t B = (size_t)c->max_beats;
+    return {slot(&c->chroma, B * 12 * sizeof(unsigned)), slot(&c->bass, B * sizeof(unsigned)), slot(&c->back, B * CHORD_BACK_WORDS * sizeof(unsigned))};
+}
+extern "C" void ymt3_chords_destroy(ymt3_chords c) { destroy_object(c); }
+
+extern "C" int ymt3_chords_create(ymt3_handle h, const ymt3_chord_params* params, long long max_beats, long long max_notes, ymt3_chords* out) {
+    if (const int rc = create_prologue(reinterpret_cast<void**>(out), h, params, "params")) return rc;
+    const ymt3_chord_params& p = *params;
+    if (!std::isfinite(p.frames_per_second) || p.frames_per_second <= 0) FAIL(YMT3_ERR_ARG, "frames_per_second=%g must be finite and > 0", p.frames_per_second);
+    if (p.n_qualities < 1 || p.n_qualities > CHORD_QUALITIES) FAIL(YMT3_ERR_ARG, "n_qualities=%d outside [1, %d]", p.n_qualities, CHORD_QUALITIES);
+    for (int q = 0; q < p.n_qualities; ++q) {
+        if (p.qualities[q] < 0 || p.qualities[q] >= CHORD_QUALITIES) FAIL(YMT3_ERR_ARG, "qualities[%d]=%d outside [0, %d)", q, p.qualities[q], CHORD_QUALITIES);
+        for (int r = 0; r < q; ++r)
+            if (p.qualities[r] == p.qualities[q]) FAIL(YMT3_ERR_ARG, "qualities[%d]=%d is given twice", q, p.qualities[q]);
+    }
+    const struct { const char* name; int v, lo, hi; } ranged[] = {{"near_div", p.near_div, 2, 64}, {"bass_div", p.bass_div, 1, 64}, {"w_bass", p.w_bass, 0, 1024},
+                                                                  {"w_none", p.w_none, 0, 1024}, {"change_cost", p.change_cost, 0, 4096},
+                                                                  {"change_cost_down", p.change_cost_down, 0, 4096}};
+    for (const auto& q : ranged)
+        if (q.v < q.lo || q.v > q.hi) FAIL(YMT3_ERR_ARG, "%s=%d outside [%d, %d]", q.name, q.v, q.lo, q.hi);
+    if (const int rc = check_programs(p.n_programs, p.drum_program, BAR_MAX_PROGRAMS, "")) return rc;
+    if (max_beats < 1 || max_beats > BAR_MAX_BEATS) FAIL(YMT3_ERR_ARG, "max_beats=%lld outside [1, %lld]", max_beats, BAR_MAX_BEATS);
+    if (max_notes < 1 || max_notes > BAR_MAX_NOTES) FAIL(YMT3_ERR_ARG, "max_notes=%lld outside [1, %lld]", max_notes, BAR_MAX_NOTES);
+    HIP_TRY(hipSetDevice(handle_device(h)));
+    ymt3_chords c = new ymt3_chords_s{h, handle_device(h), p, max_beats, max_notes};
+    return allocate_object(c, slots(c), "chord tracker scratch", out);
+}
+
+extern "C" int ymt3_track_chords(ymt3_handle h, ymt3_chords c, const int32_t* beats_dev, const long long* beat_result_dev, const int32_t* metre_dev,
+                                 const void* notes_dev, long long n_notes, const int32_t* count_dev, long long n_frames, int32_t* chord_dev,
+                                 long long chord_cap, long long* result_dev, void* stream) {
+    if (const int rc = check_owner(h, c, "chord tracker")) return rc;
+    if (!beats_dev) FAIL(YMT3_ERR_ARG, "beats_dev is NULL");
+    if (reinterpret_cast<uintptr_t>(beats_dev) % 4) FAIL(YMT3_ERR_ARG, "beats_dev is not aligned to 4 bytes");
+    if (!beat_result_dev) FAIL(YMT3_ERR_ARG, "beat_result_dev is NULL");
+    if (reinterpret_cast<uintptr_t>(beat_result_dev) % 8) FAIL(YMT3_ERR_ARG, "beat_result_dev is not aligned to 8 bytes");
+    if (reinterpret_cast<uintptr_t>(metre_dev) % 4) FAIL(YMT3_ERR_ARG, "metre_dev is not aligned to 4 bytes");
+    if (const int rc = check_count("n_notes", n_notes, c->max_notes, "max_notes")) return rc;
+    if (const int rc = check_record_ptr("notes_dev", notes_dev, n_notes)) return rc;
+    if (reinterpret_cast<uintptr_t>(count_dev) % 4) FAIL(YMT3_ERR_ARG, "count_dev is not aligned to 4 bytes");
+    if (n_frames < 1 || n_frames > BAR_MAX_FRAMES) FAIL(YMT3_ERR_ARG, "n_frames=%lld outside [1, %lld]", n_frames, BAR_MAX_FRAMES);
+    if (!chord_dev) FAIL(YMT3_ERR_ARG, "chord_dev is NULL");
+    if (reinterpret_cast<uintptr_t>(chord_dev) % 4) FAIL(YMT3_ERR_ARG, "chord_dev is not aligned to 4 bytes");
+    if (chord_cap < c->max_beats) FAIL(YMT3_ERR_ARG, "chord_cap=%lld below the chord tracker's max_beats=%lld", chord_cap, c->max_beats);
+    if (!result_dev) FAIL(YMT3_ERR_ARG, "result_dev is NULL");
+    if (reinterpret_cast<uintptr_t>(result_dev) % 8) FAIL(YMT3_ERR_ARG, "result_dev is not aligned to 8 bytes");
+    HIP_TRY(hipSetDevice(c->device));
+    ChordArgs a{};
+    a.frames_per_second = c->p.frames_per_second; a.n_programs = c->p.n_programs; a.drum_program = c->p.drum_program;
+    a.n_qualities = c->p.n_qualities;
+    for (int q = 0; q < CHORD_QUALITIES; ++q) a.qualities[q] = q < c->p.n_qualities ? c->p.qualities[q] : -1;
+    a.near_div = c->p.near_div; a.bass_div = c->p.bass_div; a.w_bass = c->p.w_bass; a.w_none = c->p.w_none; a.change_cost = c->p.change_cost;
+    a.change_cost_down = c->p.change_cost_down;
+    a.beats = beats_dev; a.beat_result = beat_result_dev; a.max_beats = c->max_beats; a.metre = metre_dev;
+    a.notes = static_cast<const DetokNote*>(notes_dev); a.n = n_notes; a.count = n_notes ? count_dev : nullptr; a.n_frames = n_frames;
+    a.chroma = c->chroma; a.bass = c->bass; a.back = c->back;
+    a.chord = chord_dev; a.result = result_dev;
+    LAUNCH(launch_track_chords(a, static_cast<hipStream_t>(stream)));
     return YMT3_OK;
 }

@@ -125,12 +125,25 @@ def _smf_bytes(notes: Sequence[Note], ticks: Dict[int, tuple], tempos, conductor
     return out
 
 
-def notes_to_midi_bytes_on_beats(notes: Sequence[Note], ticks, beats, frames_per_second: float = 100.0) -> bytes:
+def _marker_events(markers):
+    """[(tick, text)] -> conductor events FF 06 (marker), in the given order"""
+    out = []
+    for tick, text in markers:
+        raw = str(text).encode("utf-8")
+        if not 0 < len(raw) < 128:
+            raise ValueError(f"marker {text!r}: 1 to 127 bytes")
+        out.append((int(tick), b"\xff\x06" + bytes([len(raw)]) + raw))
+    return out
+
+
+def notes_to_midi_bytes_on_beats(notes: Sequence[Note], ticks, beats, frames_per_second: float = 100.0, markers=()) -> bytes:
     """notes_to_midi_bytes with a tempo map: `ticks` (n, 2), every note's onset and offset tick at 480 per beat (beats.beat_positions or
     BeatTracker.positions, in the notes' order), `beats` the beats' frames at `frames_per_second`.  The tempo track starts with the first
     interval's tempo at tick 0 and sets interval i's, rint((b[i+1] - b[i]) / fps 1e6) microseconds per beat, at tick (n0 + i) 480
     (beats.tempo_map); played back, the file keeps the performance's timing, after a lead-in of beats.lead_sec.  A note without ticks
-    (-1: a NaN time) is left out.  With fewer than two beats there is no map: the bytes are notes_to_midi_bytes'."""
+    (-1: a NaN time) is left out.  With fewer than two beats there is no map: the bytes are notes_to_midi_bytes'.  `markers` = [(tick,
+    text)], ascending (chords.chord_markers: a chord symbol at its first beat), go into the conductor track as FF 06 events; without
+    them the bytes are the same as before."""
     from .beats import tempo_map
     notes = list(notes)
     tempos = tempo_map(beats, frames_per_second)
@@ -140,21 +153,22 @@ def notes_to_midi_bytes_on_beats(notes: Sequence[Note], ticks, beats, frames_per
     if len(pairs) != len(notes):
         raise ValueError(f"{len(notes)} notes but {len(pairs)} tick pairs")
     kept = [(n, t) for n, t in zip(notes, pairs) if t[0] >= 0 and (t[1] >= 0 or n.is_drum)]
-    return _smf_bytes([n for n, _ in kept], {id(n): t for n, t in kept}, tempos)
+    return _smf_bytes([n for n, _ in kept], {id(n): t for n, t in kept}, tempos, _marker_events(markers))
 
 
-def notes_to_midi_bytes_on_bars(notes: Sequence[Note], ticks, beats, metre, key: int = -1, frames_per_second: float = 100.0) -> bytes:
+def notes_to_midi_bytes_on_bars(notes: Sequence[Note], ticks, beats, metre, key: int = -1, frames_per_second: float = 100.0, markers=()) -> bytes:
     """notes_to_midi_bytes_on_beats with bar lines and a key: `metre` (256 m + k of every beat) and `key` as bars.track_bars or
     BarTracker give them.  The conductor track gains one FF 58 04 nn 02 18 08 (nn/4) per entry of bars.time_signatures and one
     FF 59 02 sf mi at tick 0 (bars.key_signature; none for key -1), in tick order with the tempo events.  Without downbeats (fewer
-    than two beats among them) the bytes are exactly notes_to_midi_bytes_on_beats'."""
+    than two beats among them) the bytes are exactly notes_to_midi_bytes_on_beats'.  `markers` as there: at one tick after the time and
+    key signatures and before the tempo."""
     from .bars import key_signature, time_signatures
     from .beats import tempo_map
     notes = list(notes)
     signatures = time_signatures(metre, beats)
     tempos = tempo_map(beats, frames_per_second)
     if not signatures or not tempos:
-        return notes_to_midi_bytes_on_beats(notes, ticks, beats, frames_per_second)
+        return notes_to_midi_bytes_on_beats(notes, ticks, beats, frames_per_second, markers)
     pairs = [(int(a), int(b)) for a, b in ticks]
     if len(pairs) != len(notes):
         raise ValueError(f"{len(notes)} notes but {len(pairs)} tick pairs")
@@ -163,7 +177,7 @@ def notes_to_midi_bytes_on_bars(notes: Sequence[Note], ticks, beats, metre, key:
     if int(key) >= 0:
         sf, mi = key_signature(key)
         events.insert(1 if events[0][0] == 0 else 0, (0, b"\xff\x59\x02" + bytes([sf & 0xFF, mi])))
-    return _smf_bytes([n for n, _ in kept], {id(n): t for n, t in kept}, tempos, events)
+    return _smf_bytes([n for n, _ in kept], {id(n): t for n, t in kept}, tempos, events + _marker_events(markers))
 
 
 def write_midi(notes: Sequence[Note], path: str) -> str:
@@ -295,3 +309,8 @@ def read_midi_on_bars(data: bytes):
         elif st == 0xFF and payload[0] == 0x59:
             key = (payload[1] - 256 if payload[1] > 127 else payload[1], payload[2])
     return notes, tempos, signatures, key
+
+
+def read_midi_markers(data: bytes):
+    """the markers (FF 06) of a file, as the writers on the beats and on the bars write them -> [(tick, text)]"""
+    return [(tick, bytes(payload[1:]).decode("utf-8")) for _, tick, st, payload in _track_events(data)[1] if st == 0xFF and payload[0] == 0x06]

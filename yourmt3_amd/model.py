@@ -611,6 +611,14 @@ class YourMT3:
         from .bars import BarTracker                                    # (not a name of this module: bars.py builds on it)
         return BarTracker(self, max_beats, max_notes, **params)
 
+    def compile_chord_tracker(self, max_beats: int, max_notes: int, **params):
+        """The device chord tracker (include/ymt3.h, chords; the rules and the host specification: yourmt3_amd/chords.py) with scratch
+        for `max_beats` beats, taking at most `max_notes` records a call.  `params`: frames_per_second, near_div, qualities, bass_div,
+        w_bass, w_none, change_cost, change_cost_down, n_programs, drum_program (chords.DEFAULTS).  -> a chords.ChordTracker, closed
+        with the model at the latest."""
+        from .chords import ChordTracker                                # (not a name of this module: chords.py builds on it)
+        return ChordTracker(self, max_beats, max_notes, **params)
+
     def compile_ingest_stream(self, sample_rate: int, n_channels: int = 1, dtype=torch.int16, max_chunk_frames: int = 1 << 16) -> IngestStream:
         """Streaming form of ingest() (include/ymt3.h, streaming ingest) for `n_channels`-channel PCM of `dtype` (int16 or float32) at
         `sample_rate`, pushed in chunks of at most `max_chunk_frames` frames."""

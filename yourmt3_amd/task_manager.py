@@ -557,7 +557,7 @@ class TaskManager:
         return table
 
     def tokens_to_notes_device(self, model, tokens, start_secs: Sequence[float], end_sec: float, scores=None,
-                               detokenizer=None, velocity=None, audio=None, beats=None, quantize: int = 0, bars=None):
+                               detokenizer=None, velocity=None, audio=None, beats=None, quantize: int = 0, bars=None, chords=None):
         """tokens_to_notes on the device -> (notes, n_invalid).  `tokens`: (n, K, L) integer ids on `model`'s GPU (any strides whose
         last dimension is contiguous, e.g. hypothesis 0 of a beam call's (n, K, N, L)); `scores`: the matching (n, K, L) f32 token scores
         or None; `start_secs` must be strictly increasing.  `detokenizer`: a YourMT3.compile_detokenizer object to reuse (None: one is
@@ -571,11 +571,16 @@ class TaskManager:
         the returned notes' order)}.
         `bars`: a YourMT3.compile_bar_tracker object (it needs `beats`, and the beat tracker's frames_per_second): metres, downbeats and
         key are tracked on the same records and beats where they lie, and ride back in the same copy: the third element gains "metre"
-        (int32 (n_beats,), 256 m + k) and "bar_result" (int64 (8,), bars.track_bars' result)."""
+        (int32 (n_beats,), 256 m + k) and "bar_result" (int64 (8,), bars.track_bars' result).
+        `chords`: a YourMT3.compile_chord_tracker object (it needs `beats`; with `bars` it uses their metre): a chord per beat, tracked on
+        the same records and beats where they lie, riding back in the same copy: the third element gains "chord" (int32 (n_beats,),
+        256 bass + label) and "chord_result" (int64 (8,), chords.track_chords' result)."""
         import torch
 
         if bars is not None and beats is None:
             raise ValueError("bars without beats: the bar tracker works on the beat tracker's beats")
+        if chords is not None and beats is None:
+            raise ValueError("chords without beats: the chord tracker works on the beat tracker's beats")
         starts = np.asarray(list(start_secs), np.float64)
         if tokens.dim() != 3 or tokens.shape[1] != self.num_decoding_channels:
             raise ValueError(f"tokens must be (n, {self.num_decoding_channels}, L), got {tuple(tokens.shape)}")
@@ -593,6 +598,8 @@ class TaskManager:
                 none = {"beats": np.zeros(0, np.int32), "tempo": np.zeros(0, np.int32), "ticks": np.zeros((0, 2), np.int32)}
                 if bars is not None:
                     none.update(metre=np.zeros(0, np.int32), bar_result=np.array([0, 0, 0, -1, 0, 0, 0, 0], np.int64))
+                if chords is not None:
+                    none.update(chord=np.zeros(0, np.int32), chord_result=np.zeros(8, np.int64))
                 return [], 0, none
             return [], 0
         own = detokenizer is None
@@ -618,6 +625,10 @@ class TaskManager:
                 if bars is not None:                                     # on the live records: their number is known by now, the beats' is not
                     metre_dev, bar_result_dev = bars.track(beats_dev, result_dev, rec_dev[:nb], n_frames_of(end_sec, beats.params["frames_per_second"]))
                     parts += [t.view(torch.uint8) for t in (bar_result_dev, metre_dev)]
+                if chords is not None:                                   # the same, with the bars' metre where there is one
+                    chord_dev, chord_result_dev = chords.track(beats_dev, result_dev, metre_dev if bars is not None else None, rec_dev[:nb],
+                                                               n_frames_of(end_sec, beats.params["frames_per_second"]))
+                    parts += [t.view(torch.uint8) for t in (chord_result_dev, chord_dev)]
                 both = torch.cat(parts).cpu().numpy()
                 rec, o = both[:nb].view(NOTE_RECORD), nb
                 vel = None
@@ -628,9 +639,12 @@ class TaskManager:
                     n_beats = int(ints[2 * n_notes:2 * n_notes + 8].view(np.int64)[0])
                     o = 2 * n_notes + 8 + lags_dev.numel()
                     tracked = {"beats": ints[o:o + n_beats].copy(), "tempo": ints[2 * n_notes + 8:o].copy(), "ticks": ints[:2 * n_notes].reshape(-1, 2).copy()}
+                    o += beats_dev.numel()
                     if bars is not None:
-                        o += beats_dev.numel()
                         tracked.update(bar_result=ints[o:o + 16].view(np.int64).copy(), metre=ints[o + 16:o + 16 + (n_beats if n_beats >= 2 else 0)].copy())
+                        o += 16 + metre_dev.numel()
+                    if chords is not None:
+                        tracked.update(chord_result=ints[o:o + 16].view(np.int64).copy(), chord=ints[o + 16:o + 16 + (n_beats if n_beats >= 2 else 0)].copy())
         finally:
             if own:
                 detokenizer.close()

@@ -17,6 +17,7 @@ from .task_manager import DRUM_PROGRAM, NOTE_RECORD as NOTE_RECORD_DTYPE, Note, 
 from .velocity import estimate_velocities  # noqa: F401  (its home is velocity.py; it belongs with transcribe, evaluate and align)
 from .beats import estimate_beats  # noqa: F401  (the same for beats.py)
 from .bars import estimate_bars  # noqa: F401  (and for bars.py)
+from .chords import estimate_chords  # noqa: F401  (and for chords.py)
 
 
 def transcribe(model, audio_info: Union[str, dict, np.ndarray], task_manager: Optional[TaskManager] = None, bsz: int = 8,
@@ -24,7 +25,8 @@ def transcribe(model, audio_info: Union[str, dict, np.ndarray], task_manager: Op
                continuous: bool = False, subtask: Optional[str] = None, confidence: bool = False,
                min_confidence: Optional[float] = None, constrained: bool = False, programs=None, num_beams: int = 1,
                length_penalty: float = 1.0, device_detok: bool = False, velocity: bool = False, velocity_params: Optional[dict] = None,
-               beats: bool = False, quantize: int = 0, beat_params: Optional[dict] = None, bars: bool = False, bar_params: Optional[dict] = None):
+               beats: bool = False, quantize: int = 0, beat_params: Optional[dict] = None, bars: bool = False, bar_params: Optional[dict] = None,
+               chords: bool = False, chord_params: Optional[dict] = None):
     """`continuous=True` decodes the file's segments through `bsz` slots with continuous batching
     (YourMT3.inference_stream: segments leave at EOS and the next ones enter) instead of fixed batches; same ids.
     `subtask`: for a task-conditioned TaskManager (e.g. "singing_drum_v1"), the sub-task whose task tokens prompt every
@@ -57,7 +59,13 @@ def transcribe(model, audio_info: Union[str, dict, np.ndarray], task_manager: Op
     tracked, and writes them into the .mid: time signatures at the bar lines where the metre changes, a key signature at tick 0.
     `bar_params`: bars.DEFAULTS' keys (frames_per_second is the beats').  In every decode mode and with both detokenisers the same bytes.
     The info dict gains "downbeats_sec", "time_signatures" ([(tick, numerator)] over 4), "key" (e.g. "F# minor", "none" without pitched
-    notes) and "key_margin" (the best key's score minus the second best's).  Off, nothing changes by a byte."""
+    notes) and "key_margin" (the best key's score minus the second best's).  Off, nothing changes by a byte.
+    `chords=True` (it needs `beats=True`) gives every beat a chord on the device (YourMT3.compile_chord_tracker; include/ymt3.h, chords;
+    the rules: yourmt3_amd/chords.py), on the same kept notes and beats, after the bars and with their metre when `bars=True`, and writes
+    one marker (FF 06) per run of equal chords into the .mid's conductor track, at the tick of the run's first beat.  `chord_params`:
+    chords.DEFAULTS' keys (frames_per_second is the beats').  In every decode mode and with both detokenisers the same bytes.  The info
+    dict gains "chords" ([(start_sec, end_sec, name)], e.g. "Am", "G7", "C/E", "N") and "chord_labels" (every beat's 12 q + r, 255 for
+    N).  Off, nothing changes by a byte."""
     if velocity_params is not None and not velocity:
         raise ValueError("velocity_params without velocity=True")
     if (beat_params is not None or quantize) and not beats:
@@ -66,6 +74,10 @@ def transcribe(model, audio_info: Union[str, dict, np.ndarray], task_manager: Op
         raise ValueError("bars=True without beats=True")
     if bar_params is not None and not bars:
         raise ValueError("bar_params without bars=True")
+    if chords and not beats:
+        raise ValueError("chords=True without beats=True")
+    if chord_params is not None and not chords:
+        raise ValueError("chord_params without chords=True")
     num_beams = int(num_beams)
     if num_beams < 1:
         raise ValueError(f"num_beams={num_beams} must be >= 1")
@@ -121,27 +133,33 @@ def transcribe(model, audio_info: Union[str, dict, np.ndarray], task_manager: Op
             constraint.close()
     end_sec = n_samples / cfg.sample_rate
     measurer = model.compile_note_velocity(**(velocity_params or {})) if velocity else None
-    tracker = tracked = bar_tracker = None
+    tracker = tracked = bar_tracker = chord_tracker = None
     try:
         if beats:
             from .beats import DEFAULTS as BEAT_DEFAULTS, n_frames_of
             fps = float((beat_params or {}).get("frames_per_second", BEAT_DEFAULTS["frames_per_second"]))
             n_frames = n_frames_of(end_sec, fps)
             tracker = model.compile_beat_tracker(n_frames, **(beat_params or {}))
-            if bars:
+            if bars or chords:
                 from .bars import MAX_NOTES as BAR_MAX_NOTES
                 from .beats import max_beats
+                most = min(BAR_MAX_NOTES, max(1, int(segments.shape[0]) * cfg.n_channels * L))
+            if bars:
                 if float((bar_params or {}).get("frames_per_second", fps)) != fps:
                     raise ValueError("bar_params' frames_per_second must be the beats'")
-                bar_tracker = model.compile_bar_tracker(max_beats(n_frames, tracker.lag_min), min(BAR_MAX_NOTES, max(1, int(segments.shape[0]) * cfg.n_channels * L)),
-                                                   **{**(bar_params or {}), "frames_per_second": fps})
+                bar_tracker = model.compile_bar_tracker(max_beats(n_frames, tracker.lag_min), most, **{**(bar_params or {}), "frames_per_second": fps})
+            if chords:
+                if float((chord_params or {}).get("frames_per_second", fps)) != fps:
+                    raise ValueError("chord_params' frames_per_second must be the beats'")
+                chord_tracker = model.compile_chord_tracker(max_beats(n_frames, tracker.lag_min), most, **{**(chord_params or {}), "frames_per_second": fps})
         in_place = device_detok and min_confidence is None                   # measured and tracked on the detokeniser's records where they lie
         if device_detok:
             extra = {}
             if in_place and measurer is not None:
                 extra.update(velocity=measurer, audio=segments.view(-1))
             if in_place and tracker is not None:
-                extra.update(beats=tracker, quantize=quantize, **({"bars": bar_tracker} if bar_tracker is not None else {}))
+                extra.update(beats=tracker, quantize=quantize, **({"bars": bar_tracker} if bar_tracker is not None else {}),
+                             **({"chords": chord_tracker} if chord_tracker is not None else {}))
             out = task_manager.tokens_to_notes_device(model, tokens, start_secs, end_sec, scores=scores, **extra)
             notes, tracked = out[0], (out[2] if len(out) > 2 else None)
         else:
@@ -156,9 +174,13 @@ def transcribe(model, audio_info: Union[str, dict, np.ndarray], task_manager: Op
             tracked = {"beats": b, "tempo": t, "ticks": ticks}
             if bar_tracker is not None:
                 tracked["metre"], tracked["bar_result"] = bar_tracker.run(b, rec_host, n_frames)
+            if chord_tracker is not None:
+                tracked["chord"], tracked["chord_result"] = chord_tracker.run(b, rec_host, n_frames, metre=tracked.get("metre"))
     finally:
         if measurer is not None:
             measurer.close()
+        if chord_tracker is not None:
+            chord_tracker.close()
         if bar_tracker is not None:
             bar_tracker.close()
         if tracker is not None:
@@ -170,17 +192,23 @@ def transcribe(model, audio_info: Union[str, dict, np.ndarray], task_manager: Op
     from .beats import beat_summary
     from .midi import notes_to_midi_bytes_on_beats
     midi_path = os.path.join(output_dir, name + ".mid")
+    markers = ()
+    if "chord" in tracked:
+        from .chords import chord_markers, chord_segments, chord_summary
+        markers = chord_markers(chord_segments(tracked["chord"], tracked["beats"]), tracked["beats"])
     with open(midi_path, "wb") as f:
         if "metre" in tracked:
             from .midi import notes_to_midi_bytes_on_bars
-            f.write(notes_to_midi_bytes_on_bars(notes, tracked["ticks"], tracked["beats"], tracked["metre"], int(tracked["bar_result"][3]), fps))
+            f.write(notes_to_midi_bytes_on_bars(notes, tracked["ticks"], tracked["beats"], tracked["metre"], int(tracked["bar_result"][3]), fps, markers))
         else:
-            f.write(notes_to_midi_bytes_on_beats(notes, tracked["ticks"], tracked["beats"], fps))
+            f.write(notes_to_midi_bytes_on_beats(notes, tracked["ticks"], tracked["beats"], fps, markers))
     info = beat_summary(tracked["beats"], tracked["tempo"], fps)
     info["ticks"] = tracked["ticks"]
     if "metre" in tracked:
         from .bars import bar_summary
         info.update(bar_summary(tracked["metre"], tracked["bar_result"], tracked["beats"], fps))
+    if "chord" in tracked:
+        info.update(chord_summary(tracked["chord"], tracked["chord_result"], tracked["beats"], fps))
     return (midi_path, notes, info) if return_notes else (midi_path, info)
 
 
@@ -252,7 +280,7 @@ class LiveTranscriber:
     audio of its onset has left the device.  estimate_velocities() on the recording puts them onto the session's MIDI file afterwards.
     Beats (transcribe(beats=True)) are not part of a live session either: the tempo path looks at the whole file.  estimate_beats() on the
     session's notes tracks them afterwards.  Bars and key (transcribe(bars=True)) build on the beats and are out of scope here for the same
-    reason: estimate_bars() on the session's notes finds them afterwards."""
+    reason: estimate_bars() on the session's notes finds them afterwards; chords (transcribe(chords=True)) likewise, by estimate_chords()."""
 
     def __init__(self, model, sample_rate: int, n_channels: int = 1, dtype=torch.int16, task_manager: Optional[TaskManager] = None,
                  max_chunk_frames: int = 1 << 16, bsz: Optional[int] = None, max_token_length: Optional[int] = None,
