@@ -40,12 +40,11 @@ from __future__ import annotations
 
 import ctypes
 import math
-import os
 from typing import List, Optional, Tuple
 
 import numpy as np
 
-from .beats import TICKS_PER_BEAT, lead_beats
+from .beats import TICKS_PER_BEAT, _records, lead_beats, with_defaults
 from .model import _Owned
 from .task_manager import DRUM_PROGRAM
 
@@ -61,14 +60,25 @@ _MAJOR_NAMES = ("C", "Db", "D", "Eb", "E", "F", "F#", "G", "Ab", "A", "Bb", "B")
 _MINOR_NAMES = ("C", "C#", "D", "D#", "E", "F", "F#", "G", "G#", "A", "Bb", "B")
 
 
-def check_params(**params) -> dict:
-    """the parameters with their defaults (`metres` as a tuple of ints), refused (ValueError naming the parameter) outside what the C ABI accepts"""
-    unknown = set(params) - set(DEFAULTS)
-    if unknown:
-        raise TypeError(f"unknown bar parameter(s): {sorted(unknown)}")
-    p = {**DEFAULTS, **params}
+def check_shared(params: dict, defaults: dict, ranges, noun: str) -> dict:
+    """what the bars' and the chords' check_params share -> the parameters with their defaults: the names known, frames_per_second
+    finite and positive, every integer of `ranges` inside its range, the programs as the note rule needs them"""
+    p = with_defaults(params, defaults, noun)
     if not (math.isfinite(p["frames_per_second"]) and p["frames_per_second"] > 0):
         raise ValueError(f"frames_per_second={p['frames_per_second']} must be finite and > 0")
+    for k, lo, hi in ranges:
+        if not lo <= int(p[k]) <= hi:
+            raise ValueError(f"{k}={p[k]} outside [{lo}, {hi}]")
+    if not 1 <= int(p["n_programs"]) <= MAX_PROGRAMS:
+        raise ValueError(f"n_programs={p['n_programs']} outside [1, {MAX_PROGRAMS}]")
+    if not 0 <= int(p["drum_program"]) < int(p["n_programs"]):
+        raise ValueError(f"drum_program={p['drum_program']} outside [0, n_programs={p['n_programs']})")
+    return p
+
+
+def check_params(**params) -> dict:
+    """the parameters with their defaults (`metres` as a tuple of ints), refused (ValueError naming the parameter) outside what the C ABI accepts"""
+    p = check_shared(params, DEFAULTS, _RANGES, "bar")
     try:
         metres = tuple(int(m) for m in p["metres"])
     except TypeError:
@@ -78,15 +88,8 @@ def check_params(**params) -> dict:
     if any(not 2 <= m <= 6 for m in metres) or len(set(metres)) != len(metres):
         raise ValueError(f"metres={metres} must be distinct integers in [2, 6]")
     p["metres"] = metres
-    for k, lo, hi in _RANGES:
-        if not lo <= int(p[k]) <= hi:
-            raise ValueError(f"{k}={p[k]} outside [{lo}, {hi}]")
     if not 0 <= int(p["kick_lo"]) <= int(p["kick_hi"]) <= 127:
         raise ValueError(f"kick_lo={p['kick_lo']}, kick_hi={p['kick_hi']} must satisfy 0 <= kick_lo <= kick_hi <= 127")
-    if not 1 <= int(p["n_programs"]) <= MAX_PROGRAMS:
-        raise ValueError(f"n_programs={p['n_programs']} outside [1, {MAX_PROGRAMS}]")
-    if not 0 <= int(p["drum_program"]) < int(p["n_programs"]):
-        raise ValueError(f"drum_program={p['drum_program']} outside [0, n_programs={p['n_programs']})")
     return p
 
 
@@ -95,11 +98,6 @@ def check_sizes(max_beats: int, max_notes: int) -> None:
         raise ValueError(f"max_beats={max_beats} outside [1, {MAX_BEATS}]")
     if not 1 <= int(max_notes) <= MAX_NOTES:
         raise ValueError(f"max_notes={max_notes} outside [1, {MAX_NOTES}]")
-
-
-def _records(notes) -> np.ndarray:
-    from .metrics import to_records
-    return to_records(notes)
 
 
 def slot_edges(beats, near_div: int) -> Tuple[np.ndarray, np.ndarray]:
@@ -113,6 +111,30 @@ def slot_edges(beats, near_div: int) -> Tuple[np.ndarray, np.ndarray]:
     e[1:-1] = b[1:] - d[:-1] // near_div
     e[-1] = b[-1] + d[-1] - d[-1] // near_div
     return d, e
+
+
+def pitched_spans(rec, drum, n_frames: int, fps: float) -> Tuple[np.ndarray, np.ndarray, np.ndarray]:
+    """the counted records `rec` (`drum`: which of them are drums) -> (lo, hi, pitch) int64 of the pitched ones whose span
+    [F(on), max(F(off), F(on) + 1)), clipped to [0, n_frames) in f64, is not empty"""
+    from .metrics import frame_of
+    rec = rec[~drum]
+    f_on, f_off = frame_of(rec["onset"], fps), frame_of(rec["offset"], fps)
+    lo, hi = np.maximum(f_on, 0.0), np.minimum(np.maximum(f_off, f_on + 1.0), np.float64(n_frames))
+    some = lo < hi
+    return lo[some].astype(np.int64), hi[some].astype(np.int64), rec["pitch"][some].astype(np.int64)
+
+
+def share_spans(lo, hi, pitch, e, each=None) -> np.ndarray:
+    """the spans [lo, hi) shared out among the slots of edges `e` -> c int64 (K, 12): the frames every span shares with slot s, added to
+    c[s][pitch mod 12].  `each(s, ok, share)`: called per slot with the spans that overlap it and every span's share."""
+    c = np.zeros((e.size - 1, 12), np.int64)
+    for s in range(e.size - 1):
+        share = np.minimum(hi, e[s + 1]) - np.maximum(lo, e[s])
+        ok = share > 0
+        c[s] += np.bincount(pitch[ok] % 12, weights=share[ok], minlength=12).astype(np.int64)
+        if each is not None:
+            each(s, ok, share)
+    return c
 
 
 def bar_features(notes, beats, n_frames: int, p: dict) -> Tuple[np.ndarray, np.ndarray, int]:
@@ -138,17 +160,8 @@ def bar_features(notes, beats, n_frames: int, p: dict) -> Tuple[np.ndarray, np.n
         long_ = ~dr & (f_off[inside][near] - fi.astype(np.float64) >= d[i].astype(np.float64))
     w = 1 + np.where(dr & (pt >= int(p["kick_lo"])) & (pt <= int(p["kick_hi"])), int(p["w_kick"]), 0) + np.where(long_, int(p["w_long"]), 0)
     a = np.bincount(i, weights=w, minlength=K).astype(np.int64)
-    # chroma: the pitched records' spans, clipped to the frames in f64, shared out among the slots
-    f1 = np.maximum(f_off, f_on + 1.0)
-    lo, hi = np.maximum(f_on, 0.0), np.minimum(f1, np.float64(n_frames))
-    some = ~drum & (lo < hi)
-    lo, hi, pc = lo[some].astype(np.int64), hi[some].astype(np.int64), pitch[some] % 12
-    c = np.zeros((K, 12), np.int64)
-    for s in range(K):
-        share = np.minimum(hi, e[s + 1]) - np.maximum(lo, e[s])
-        ok = share > 0
-        c[s] += np.bincount(pc[ok], weights=share[ok], minlength=12).astype(np.int64)
-    return a, c, int((~counted).sum())
+    # chroma: the pitched records' spans, shared out among the slots
+    return a, share_spans(*pitched_spans(rec, drum, n_frames, fps), e), int((~counted).sum())
 
 
 def salience(a: np.ndarray, c: np.ndarray, p: dict) -> np.ndarray:
@@ -208,12 +221,10 @@ def key_of(tot) -> Tuple[int, int, int]:
     return key, S[key], max(S[j] for j in range(24) if j != key)
 
 
-def track_bars(notes, beats, n_frames: int, **params) -> Tuple[np.ndarray, np.ndarray]:
-    """The host specification -> (metre int32 (K,): 256 m + k of every beat, result int64 (8,): n_downbeats, max V[K-1], mean_d, key,
-    the best S, the second-best S, skipped records, 0).  `notes`: a list of Note or a NOTE_RECORD array, in any order; `beats`: the
-    beats' frames, ascending (beats.track_beats); `params`: DEFAULTS' keys."""
+def check_inputs(notes, beats, n_frames: int, p: dict, metre=None) -> Tuple[np.ndarray, np.ndarray, Optional[int]]:
+    """what track_bars and track_chords ask of their inputs -> (the records, the beats int64, with fewer than two beats the number of
+    skipped records: all that is left to report then)"""
     from .metrics import classify
-    p = check_params(**params)
     if not 1 <= int(n_frames) <= MAX_FRAMES:
         raise ValueError(f"n_frames={n_frames} outside [1, {MAX_FRAMES}]")
     rec = _records(notes)
@@ -222,11 +233,23 @@ def track_bars(notes, beats, n_frames: int, **params) -> Tuple[np.ndarray, np.nd
         raise ValueError(f"{rec.size} notes: at most {MAX_NOTES}")
     if b.size > MAX_BEATS:
         raise ValueError(f"{b.size} beats: at most {MAX_BEATS}")
+    if metre is not None and len(metre) < b.size:
+        raise ValueError(f"{len(metre)} metre entries for {b.size} beats")
     if b.size < 2:
-        skipped = int((~classify(rec, int(p["n_programs"]), int(p["drum_program"]))[0]).sum())
-        return np.zeros(0, np.int32), np.array([0, 0, 0, -1, 0, 0, skipped, 0], np.int64)
+        return rec, b, int((~classify(rec, int(p["n_programs"]), int(p["drum_program"]))[0]).sum())
     if not bool(np.all(np.diff(b) > 0)):
         raise ValueError("beats must ascend strictly")
+    return rec, b, None
+
+
+def track_bars(notes, beats, n_frames: int, **params) -> Tuple[np.ndarray, np.ndarray]:
+    """The host specification -> (metre int32 (K,): 256 m + k of every beat, result int64 (8,): n_downbeats, max V[K-1], mean_d, key,
+    the best S, the second-best S, skipped records, 0).  `notes`: a list of Note or a NOTE_RECORD array, in any order; `beats`: the
+    beats' frames, ascending (beats.track_beats); `params`: DEFAULTS' keys."""
+    p = check_params(**params)
+    rec, b, skipped = check_inputs(notes, beats, n_frames, p)
+    if b.size < 2:
+        return np.zeros(0, np.int32), np.array([0, 0, 0, -1, 0, 0, skipped, 0], np.int64)
     a, c, skipped = bar_features(rec, b, int(n_frames), p)
     metre, top, mean_d = bar_path(salience(a, c, p), p)
     key, best, second = key_of(c.sum(0))
@@ -300,10 +323,7 @@ class BarTracker(_Owned):
 
     def __init__(self, model, max_beats: int, max_notes: int, **params):
         from . import _lib
-        unknown = set(params) - set(DEFAULTS)
-        if unknown:
-            raise TypeError(f"unknown bar parameter(s): {sorted(unknown)}")
-        self.params = p = {**DEFAULTS, **params}
+        self.params = p = with_defaults(params, DEFAULTS, "bar")
         metres = tuple(int(m) for m in p["metres"])
         if not 1 <= len(metres) <= MAX_METRES:
             raise ValueError(f"metres={metres} must hold 1 to {MAX_METRES} metres")
@@ -332,16 +352,27 @@ class BarTracker(_Owned):
     def run(self, beats, records, n_frames: int, count=None):
         """`beats`: the beats' frames (a sequence or an int32 tensor, uploaded if on the host), all of them live.  track(), then ONE copy
         back -> (metre int32 (n_beats,), result int64 (8,)) as numpy arrays"""
-        import torch
-        model = self._live_model()
-        b = torch.as_tensor(np.asarray(beats.cpu() if isinstance(beats, torch.Tensor) else beats, np.int32)).to(model.device)
-        k = int(b.numel())
-        if k > self.max_beats:
-            raise ValueError(f"{k} beats: the bar tracker was made for max_beats={self.max_beats}")
-        beat_result = torch.tensor([k, 0, 0, 0], dtype=torch.int64).to(model.device)
-        metre, result = self.track(b if k else torch.zeros(1, dtype=torch.int32, device=model.device), beat_result, records, n_frames, count)
-        flat = torch.cat([result.view(torch.int32), metre[:k]]).cpu().numpy()
-        return flat[16:16 + (k if k >= 2 else 0)].copy(), flat[:16].view(np.int64).copy()
+        return run_on_beats(self, beats, lambda b, beat_result, k: self.track(b, beat_result, records, n_frames, count))
+
+
+def _to_device(device, x):
+    import torch
+    return torch.as_tensor(np.asarray(x.cpu() if isinstance(x, torch.Tensor) else x, np.int32)).to(device)
+
+
+def run_on_beats(tracker, beats, track) -> Tuple[np.ndarray, np.ndarray]:
+    """What BarTracker.run and ChordTracker.run share: `beats` go up (one zero where there are none: the kernels take no null) with a
+    beat tracker's result that says their number k, `track(b, beat_result, k)` gives the per-beat output and the result on the device,
+    then ONE copy back -> (the per-beat output int32 (k,), none with fewer than two beats; result int64 (8,))"""
+    import torch
+    device = tracker._live_model().device
+    b = _to_device(device, beats)
+    k = int(b.numel())
+    if k > tracker.max_beats:
+        raise ValueError(f"{k} beats: the {tracker._noun} was made for max_beats={tracker.max_beats}")
+    per_beat, result = track(b if k else torch.zeros(1, dtype=torch.int32, device=device), torch.tensor([k, 0, 0, 0], dtype=torch.int64).to(device), k)
+    flat = torch.cat([result.view(torch.int32), per_beat[:k]]).cpu().numpy()
+    return flat[16:16 + (k if k >= 2 else 0)].copy(), flat[:16].view(np.int64).copy()
 
 
 def bar_summary(metre, result, beats, frames_per_second: float) -> dict:
@@ -359,39 +390,7 @@ def estimate_bars(model, notes_or_mid_path, end_sec: Optional[float] = None, div
     the last note's end); `beat_params`: beats.DEFAULTS' keys; `params`: DEFAULTS' keys.  -> estimate_beats' dict plus {"downbeats_sec",
     "time_signatures", "key", "key_margin", "metre" (int32 (n_beats,))}, "midi" being the bytes of the file on the bars; with `output_path`
     the bytes are written there too."""
-    import torch
-    from .beats import DEFAULTS as BEAT_DEFAULTS, beat_summary, max_beats, n_frames_of
-    from .midi import notes_to_midi_bytes_on_bars, read_midi_notes
-    notes = notes_or_mid_path
-    if isinstance(notes, (str, os.PathLike)):
-        with open(notes, "rb") as f:
-            notes = read_midi_notes(f.read())
-    notes = list(notes)
-    beat_params = dict(beat_params or {})
-    fps = float(beat_params.get("frames_per_second", BEAT_DEFAULTS["frames_per_second"]))
-    if float(params.get("frames_per_second", fps)) != fps:
-        raise ValueError("the bars' frames_per_second must be the beats'")
-    if end_sec is None:
-        end_sec = max([0.0] + [max(n.onset, n.offset) for n in notes if math.isfinite(n.onset) and math.isfinite(n.offset)])
-    n_frames = n_frames_of(end_sec, fps)
-    rec = torch.from_numpy(_records(notes).view(np.uint8).reshape(-1).copy()).to(model.device)
-    with model.compile_beat_tracker(max_frames=n_frames, **beat_params) as bt:
-        with model.compile_bar_tracker(max_beats(n_frames, bt.lag_min), max(1, len(notes)), **{**params, "frames_per_second": fps}) as br:
-            beats_dev, lags_dev, beat_result = bt.track(rec, n_frames)
-            ticks_dev = bt.positions(beats_dev, beat_result, rec, None, divisions)
-            metre_dev, result_dev = br.track(beats_dev, beat_result, rec, n_frames)
-            flat = torch.cat([beat_result.view(torch.int32), result_dev.view(torch.int32), lags_dev, beats_dev, metre_dev, ticks_dev.view(-1)]).cpu().numpy()
-    k = int(flat[:8].view(np.int64)[0])
-    result = flat[8:24].view(np.int64).copy()
-    o = 24 + lags_dev.numel()
-    tempo, beats = flat[24:o].copy(), flat[o:o + k].copy()
-    o += beats_dev.numel()
-    metre = flat[o:o + k].copy()
-    ticks = flat[o + metre_dev.numel():].reshape(-1, 2).copy()
-    out = beat_summary(beats, tempo, fps)
-    out.update(bar_summary(metre, result, beats, fps))
-    out.update(ticks=ticks, metre=metre, midi=notes_to_midi_bytes_on_bars(notes, ticks, beats, metre, int(result[3]), fps))
-    if output_path is not None:
-        with open(output_path, "wb") as f:
-            f.write(out["midi"])
+    from .tracking import estimate
+    out, tracked = estimate(model, notes_or_mid_path, end_sec, divisions, output_path, beat_params, params)
+    out["metre"] = tracked["metre"]
     return out

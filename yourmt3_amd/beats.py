@@ -32,7 +32,6 @@ from __future__ import annotations
 
 import ctypes
 import math
-import os
 from typing import List, Optional, Sequence, Tuple
 
 import numpy as np
@@ -50,12 +49,16 @@ SUM_LIMIT = 1 << 62                       # what the tempo path's sums may reach
 TICK_GRID_MAX, TICK_FLAT_MAX = 1 << 20, 1 << 29
 
 
+def with_defaults(params: dict, defaults: dict, noun: str) -> dict:
+    unknown = set(params) - set(defaults)
+    if unknown:
+        raise TypeError(f"unknown {noun} parameter(s): {sorted(unknown)}")
+    return {**defaults, **params}
+
+
 def check_params(**params) -> dict:
     """the parameters with their defaults and the two derived lags, refused (ValueError naming the parameter) outside what the C ABI accepts"""
-    unknown = set(params) - set(DEFAULTS)
-    if unknown:
-        raise TypeError(f"unknown beat parameter(s): {sorted(unknown)}")
-    p = {**DEFAULTS, **params}
+    p = with_defaults(params, DEFAULTS, "beat")
     for k in ("frames_per_second", "bpm_min", "bpm_max", "bpm_prior", "prior_octaves", "tightness"):
         if not (math.isfinite(p[k]) and p[k] > 0):
             raise ValueError(f"{k}={p[k]} must be finite and > 0")
@@ -285,10 +288,7 @@ class BeatTracker(_Owned):
 
     def __init__(self, model, max_frames: int, **params):
         from . import _lib
-        unknown = set(params) - set(DEFAULTS)
-        if unknown:
-            raise TypeError(f"unknown beat parameter(s): {sorted(unknown)}")
-        self.params = {**DEFAULTS, **params}
+        self.params = with_defaults(params, DEFAULTS, "beat")
         self.max_frames = int(max_frames)
         self._own(model)
         p = self.params
@@ -358,23 +358,5 @@ def estimate_beats(model, notes_or_mid_path, end_sec: Optional[float] = None, di
     (BeatTracker; the rules: this module's docstring).  `end_sec`: the length of the music (None: the last note's end); `params`:
     DEFAULTS' keys.  -> {"beats_sec", "tempo_bpm", "lead_sec", "ticks" (int32 (n, 2), in the notes' order), "midi" (the bytes of the file
     on the beats)}; with `output_path` the bytes are written there too."""
-    import torch
-    from .midi import notes_to_midi_bytes_on_beats, read_midi_notes
-    notes = notes_or_mid_path
-    if isinstance(notes, (str, os.PathLike)):
-        with open(notes, "rb") as f:
-            notes = read_midi_notes(f.read())
-    notes = list(notes)
-    fps = float(params.get("frames_per_second", DEFAULTS["frames_per_second"]))
-    if end_sec is None:
-        end_sec = max([0.0] + [max(n.onset, n.offset) for n in notes if math.isfinite(n.onset) and math.isfinite(n.offset)])
-    n_frames = n_frames_of(end_sec, fps)
-    rec = torch.from_numpy(_records(notes).view(np.uint8).reshape(-1).copy())
-    with model.compile_beat_tracker(max_frames=n_frames, **params) as bt:
-        beats, tempo, _, ticks = bt.run(rec, n_frames, divisions=divisions)
-    out = beat_summary(beats, tempo, fps)
-    out.update(ticks=ticks, midi=notes_to_midi_bytes_on_beats(notes, ticks, beats, fps))
-    if output_path is not None:
-        with open(output_path, "wb") as f:
-            f.write(out["midi"])
-    return out
+    from .tracking import estimate
+    return estimate(model, notes_or_mid_path, end_sec, divisions, output_path, params)[0]

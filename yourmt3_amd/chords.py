@@ -35,14 +35,13 @@ One chord per beat at the finest: changes inside a beat, chords beyond the eight
 from __future__ import annotations
 
 import ctypes
-import math
-import os
 from typing import List, Optional, Sequence, Tuple
 
 import numpy as np
 
-from .bars import MAX_BEATS, MAX_FRAMES, MAX_NOTES, MAX_PROGRAMS, _MAJOR_NAMES, _records, check_sizes, slot_edges  # noqa: F401  (the sizes are the bars')
-from .beats import TICKS_PER_BEAT, lead_beats
+from .bars import (MAX_BEATS, MAX_FRAMES, MAX_NOTES, MAX_PROGRAMS, _MAJOR_NAMES, _records, _to_device, check_inputs, check_shared,  # noqa: F401
+                   check_sizes, pitched_spans, run_on_beats, share_spans, slot_edges)  # (the sizes and the slot rule are the bars')
+from .beats import TICKS_PER_BEAT, lead_beats, with_defaults
 from .model import _Owned
 from .task_manager import DRUM_PROGRAM
 
@@ -58,12 +57,7 @@ _RANGES = (("near_div", 2, 64), ("bass_div", 1, 64), ("w_bass", 0, 1024), ("w_no
 
 def check_params(**params) -> dict:
     """the parameters with their defaults (`qualities` as a tuple of names), refused (ValueError naming the parameter) outside what the C ABI accepts"""
-    unknown = set(params) - set(DEFAULTS)
-    if unknown:
-        raise TypeError(f"unknown chord parameter(s): {sorted(unknown)}")
-    p = {**DEFAULTS, **params}
-    if not (math.isfinite(p["frames_per_second"]) and p["frames_per_second"] > 0):
-        raise ValueError(f"frames_per_second={p['frames_per_second']} must be finite and > 0")
+    p = check_shared(params, DEFAULTS, _RANGES, "chord")
     q = p["qualities"]
     if isinstance(q, str) or not isinstance(q, (tuple, list)):
         raise ValueError(f"qualities={q!r} must be a tuple of names")
@@ -73,38 +67,25 @@ def check_params(**params) -> dict:
     if any(name not in QUALITIES for name in q) or len(set(q)) != len(q):
         raise ValueError(f"qualities={q} must be distinct names of {QUALITIES}")
     p["qualities"] = q
-    for k, lo, hi in _RANGES:
-        if not lo <= int(p[k]) <= hi:
-            raise ValueError(f"{k}={p[k]} outside [{lo}, {hi}]")
-    if not 1 <= int(p["n_programs"]) <= MAX_PROGRAMS:
-        raise ValueError(f"n_programs={p['n_programs']} outside [1, {MAX_PROGRAMS}]")
-    if not 0 <= int(p["drum_program"]) < int(p["n_programs"]):
-        raise ValueError(f"drum_program={p['drum_program']} outside [0, n_programs={p['n_programs']})")
     return p
 
 
 def chord_features(notes, beats, n_frames: int, p: dict) -> Tuple[np.ndarray, np.ndarray, int]:
     """-> (c int64 (K, 12), bass int64 (K,), the number of skipped records); K >= 2"""
-    from .metrics import classify, frame_of
+    from .metrics import classify
     rec = _records(notes)
     b = np.asarray(beats, np.int64)
-    K, fps = b.size, float(p["frames_per_second"])
     _, e = slot_edges(b, int(p["near_div"]))
     counted, _, drum = classify(rec, int(p["n_programs"]), int(p["drum_program"]))
-    rec = rec[counted & ~drum]
-    f_on, f_off = frame_of(rec["onset"], fps), frame_of(rec["offset"], fps)
-    lo, hi = np.maximum(f_on, 0.0), np.minimum(np.maximum(f_off, f_on + 1.0), np.float64(n_frames))
-    some = lo < hi
-    lo, hi, pitch = lo[some].astype(np.int64), hi[some].astype(np.int64), rec["pitch"][some].astype(np.int64)
-    c, bass = np.zeros((K, 12), np.int64), np.full(K, NO_BASS, np.int64)
-    for s in range(K):
-        share = np.minimum(hi, e[s + 1]) - np.maximum(lo, e[s])
-        ok = share > 0
-        c[s] += np.bincount(pitch[ok] % 12, weights=share[ok], minlength=12).astype(np.int64)
+    lo, hi, pitch = pitched_spans(rec[counted], drum[counted], n_frames, float(p["frames_per_second"]))
+    bass = np.full(b.size, NO_BASS, np.int64)
+
+    def lowest_long(s, ok, share):
         long_ = ok & (int(p["bass_div"]) * share >= e[s + 1] - e[s])
         if long_.any():
             bass[s] = pitch[long_].min()
-    return c, bass, int((~counted).sum())
+
+    return share_spans(lo, hi, pitch, e, lowest_long), bass, int((~counted).sum())
 
 
 def chord_states(qualities) -> List[Tuple[int, int]]:
@@ -147,23 +128,10 @@ def track_chords(notes, beats, n_frames: int, metre=None, **params) -> Tuple[np.
     """The host specification -> (chord int32 (K,): 256 bass + label of every beat, result int64 (8,): runs, max V[K-1], N beats, skipped
     records, 0, 0, 0, 0).  `notes`: a list of Note or a NOTE_RECORD array, in any order; `beats`: the beats' frames, ascending
     (beats.track_beats); `metre`: bars.track_bars' metre of the same beats, or None; `params`: DEFAULTS' keys."""
-    from .metrics import classify
     p = check_params(**params)
-    if not 1 <= int(n_frames) <= MAX_FRAMES:
-        raise ValueError(f"n_frames={n_frames} outside [1, {MAX_FRAMES}]")
-    rec = _records(notes)
-    b = np.asarray(beats, np.int64)
-    if rec.size > MAX_NOTES:
-        raise ValueError(f"{rec.size} notes: at most {MAX_NOTES}")
-    if b.size > MAX_BEATS:
-        raise ValueError(f"{b.size} beats: at most {MAX_BEATS}")
-    if metre is not None and len(metre) < b.size:
-        raise ValueError(f"{len(metre)} metre entries for {b.size} beats")
+    rec, b, skipped = check_inputs(notes, beats, n_frames, p, metre)
     if b.size < 2:
-        skipped = int((~classify(rec, int(p["n_programs"]), int(p["drum_program"]))[0]).sum())
         return np.zeros(0, np.int32), np.array([0, 0, 0, skipped, 0, 0, 0, 0], np.int64)
-    if not bool(np.all(np.diff(b) > 0)):
-        raise ValueError("beats must ascend strictly")
     c, bass, skipped = chord_features(rec, b, int(n_frames), p)
     path, top = chord_path(emissions(c, bass, p), metre, p)
     states = chord_states(p["qualities"])
@@ -248,10 +216,7 @@ class ChordTracker(_Owned):
 
     def __init__(self, model, max_beats: int, max_notes: int, **params):
         from . import _lib
-        unknown = set(params) - set(DEFAULTS)
-        if unknown:
-            raise TypeError(f"unknown chord parameter(s): {sorted(unknown)}")
-        self.params = p = {**DEFAULTS, **params}
+        self.params = p = with_defaults(params, DEFAULTS, "chord")
         names = tuple(p["qualities"])
         if isinstance(p["qualities"], str) or not 1 <= len(names) <= len(QUALITIES) or any(n not in QUALITIES for n in names):
             raise ValueError(f"qualities={p['qualities']!r} must hold 1 to {len(QUALITIES)} names of {QUALITIES}")
@@ -279,22 +244,15 @@ class ChordTracker(_Owned):
     def run(self, beats, records, n_frames: int, metre=None, count=None):
         """`beats`: the beats' frames, `metre`: their metre or None (sequences or int32 tensors, uploaded if on the host), all of them
         live.  track(), then ONE copy back -> (chord int32 (n_beats,), result int64 (8,)) as numpy arrays"""
-        import torch
-        model = self._live_model()
-        up = lambda x: torch.as_tensor(np.asarray(x.cpu() if isinstance(x, torch.Tensor) else x, np.int32)).to(model.device)
-        b = up(beats)
-        k = int(b.numel())
-        if k > self.max_beats:
-            raise ValueError(f"{k} beats: the chord tracker was made for max_beats={self.max_beats}")
-        m = None
-        if metre is not None and k >= 2:
-            m = up(metre)
-            if int(m.numel()) < k:
-                raise ValueError(f"{int(m.numel())} metre entries for {k} beats")
-        beat_result = torch.tensor([k, 0, 0, 0], dtype=torch.int64).to(model.device)
-        chord, result = self.track(b if k else torch.zeros(1, dtype=torch.int32, device=model.device), beat_result, m, records, n_frames, count)
-        flat = torch.cat([result.view(torch.int32), chord[:k]]).cpu().numpy()
-        return flat[16:16 + (k if k >= 2 else 0)].copy(), flat[:16].view(np.int64).copy()
+        def track(b, beat_result, k):
+            m = None
+            if metre is not None and k >= 2:
+                m = _to_device(b.device, metre)
+                if int(m.numel()) < k:
+                    raise ValueError(f"{int(m.numel())} metre entries for {k} beats")
+            return self.track(b, beat_result, m, records, n_frames, count)
+
+        return run_on_beats(self, beats, track)
 
 
 def estimate_chords(model, notes_or_mid_path, end_sec: Optional[float] = None, divisions: int = 0, output_path: Optional[str] = None,
@@ -304,51 +262,10 @@ def estimate_chords(model, notes_or_mid_path, end_sec: Optional[float] = None, d
     `end_sec`, `divisions`, `beat_params` as estimate_bars; `bar_params`: bars.DEFAULTS' keys; `params`: DEFAULTS' keys.  -> estimate_bars'
     dict plus {"chords", "chord_labels", "chord" (int32 (n_beats,)), "lab" (the text of a .lab file)}, "midi" being the bytes of the file
     on the bars with one marker per chord; with `output_path` / `lab_path` the bytes and the text are written there too."""
-    import torch
-    from .bars import bar_summary
-    from .beats import DEFAULTS as BEAT_DEFAULTS, beat_summary, max_beats, n_frames_of
-    from .midi import notes_to_midi_bytes_on_bars, read_midi_notes
-    notes = notes_or_mid_path
-    if isinstance(notes, (str, os.PathLike)):
-        with open(notes, "rb") as f:
-            notes = read_midi_notes(f.read())
-    notes = list(notes)
-    beat_params, bar_params = dict(beat_params or {}), dict(bar_params or {})
-    fps = float(beat_params.get("frames_per_second", BEAT_DEFAULTS["frames_per_second"]))
-    if float(params.get("frames_per_second", fps)) != fps or float(bar_params.get("frames_per_second", fps)) != fps:
-        raise ValueError("the chords' and the bars' frames_per_second must be the beats'")
-    if end_sec is None:
-        end_sec = max([0.0] + [max(n.onset, n.offset) for n in notes if math.isfinite(n.onset) and math.isfinite(n.offset)])
-    n_frames = n_frames_of(end_sec, fps)
-    rec = torch.from_numpy(_records(notes).view(np.uint8).reshape(-1).copy()).to(model.device)
-    with model.compile_beat_tracker(max_frames=n_frames, **beat_params) as bt:
-        cap, most = max_beats(n_frames, bt.lag_min), max(1, len(notes))
-        with model.compile_bar_tracker(cap, most, **{**bar_params, "frames_per_second": fps}) as br, \
-                model.compile_chord_tracker(cap, most, **{**params, "frames_per_second": fps}) as ct:
-            beats_dev, lags_dev, beat_result = bt.track(rec, n_frames)
-            ticks_dev = bt.positions(beats_dev, beat_result, rec, None, divisions)
-            metre_dev, result_dev = br.track(beats_dev, beat_result, rec, n_frames)
-            chord_dev, chord_result = ct.track(beats_dev, beat_result, metre_dev, rec, n_frames)
-            flat = torch.cat([beat_result.view(torch.int32), result_dev.view(torch.int32), lags_dev, beats_dev, metre_dev, chord_dev,
-                              ticks_dev.view(-1)]).cpu().numpy()
-    k = int(flat[:8].view(np.int64)[0])
-    result = flat[8:24].view(np.int64).copy()
-    o = 24 + lags_dev.numel()
-    tempo, beats = flat[24:o].copy(), flat[o:o + k].copy()
-    o += beats_dev.numel()
-    metre = flat[o:o + k].copy()
-    o += metre_dev.numel()
-    chord = flat[o:o + (k if k >= 2 else 0)].copy()
-    ticks = flat[o + chord_dev.numel():].reshape(-1, 2).copy()
-    out = beat_summary(beats, tempo, fps)
-    out.update(bar_summary(metre, result, beats, fps))
-    out.update(chord_summary(chord, None, beats, fps))
-    seg = chord_segments(chord, beats)
-    out.update(ticks=ticks, metre=metre, chord=chord, lab=chord_lab(seg, beats, fps),
-               midi=notes_to_midi_bytes_on_bars(notes, ticks, beats, metre, int(result[3]), fps, markers=chord_markers(seg, beats)))
-    if output_path is not None:
-        with open(output_path, "wb") as f:
-            f.write(out["midi"])
+    from .tracking import beats_fps, estimate
+    out, tracked = estimate(model, notes_or_mid_path, end_sec, divisions, output_path, beat_params, dict(bar_params or {}), params)
+    out.update(metre=tracked["metre"], chord=tracked["chord"],
+               lab=chord_lab(chord_segments(tracked["chord"], tracked["beats"]), tracked["beats"], beats_fps(beat_params)))
     if lab_path is not None:
         with open(lab_path, "w") as f:
             f.write(out["lab"])

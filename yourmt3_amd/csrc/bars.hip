@@ -22,6 +22,7 @@
 
 #include "common.h"
 #include "kernels.h"
+#include "beat_slots.h"
 #include "note_rule.h"
 
 namespace {
@@ -32,36 +33,9 @@ constexpr int BAR_CLEAR_BLOCKS = 256;
 __device__ const int BAR_KEY_TABLE[2][12] = {{671, -293, -1, -270, 210, 142, -225, 400, -256, 42, -279, -141},
                                              {671, -263, -48, 428, -284, -46, -299, 266, 69, -261, -94, -138}};
 
-__device__ __forceinline__ int bar_beats(const BarArgs& a) {
-    const long long k = a.beat_result[0];
-    return (int)(k < 0 ? 0 : (k < a.max_beats ? k : a.max_beats));
-}
-
-// D[i], i in [0, K), K >= 2
-__device__ __forceinline__ int bar_delta(const int32_t* b, int K, int i) { return i < K - 1 ? b[i + 1] - b[i] : b[K - 1] - b[K - 2]; }
-
-// the slots' edges, i in [0, K]: lo[i] for i < K, hi[K-1] for i = K
-__device__ __forceinline__ long long bar_edge(const int32_t* b, int K, int nd, int i) {
-    if (i == 0) return (long long)b[0] - (b[1] - b[0]) / nd;
-    if (i < K) return (long long)b[i] - (b[i] - b[i - 1]) / nd;
-    const int d = b[K - 1] - b[K - 2];
-    return (long long)b[K - 1] + d - d / nd;
-}
-
-// the largest s in [0, K-1] with edge(s) <= f (0 if there is none)
-__device__ __forceinline__ int bar_slot(const int32_t* b, int K, int nd, long long f) {
-    int lo = 0, hi = K - 1;
-    while (lo < hi) {
-        const int mid = (lo + hi + 1) >> 1;
-        if (bar_edge(b, K, nd, mid) <= f) lo = mid;
-        else hi = mid - 1;
-    }
-    return lo;
-}
-
 __global__ __launch_bounds__(BAR_THREADS) void bar_clear_kernel(BarArgs a) {
     const long long stride = (long long)gridDim.x * BAR_THREADS, t0 = (long long)blockIdx.x * BAR_THREADS + threadIdx.x;
-    const long long K = bar_beats(a);
+    const long long K = beat_count(a.beat_result, a.max_beats);
     for (long long i = t0; i < K * 12; i += stride) a.chroma[i] = 0u;
     for (long long i = t0; i < K; i += stride) a.accent[i] = 0u;
     if (t0 < BAR_ACC_WORDS) a.acc[t0] = 0ull;
@@ -78,17 +52,16 @@ __global__ __launch_bounds__(BAR_THREADS) void bar_features_kernel(BarArgs a) {
         atomicAdd(reinterpret_cast<unsigned long long*>(&a.result[6]), 1ull);
         return;
     }
-    const int K = bar_beats(a);
+    const int K = beat_count(a.beat_result, a.max_beats);
     if (K < 2) return;
-    const int32_t* b = a.beats;
-    const int nd = a.near_div;
-    const long long e0 = bar_edge(b, K, nd, 0), eK = bar_edge(b, K, nd, K);
+    const BeatSlots sl = {a.beats, K, a.near_div};
+    const long long e0 = slot_edge(sl, 0), eK = slot_edge(sl, K);
     const double f0 = rint(r.onset * a.frames_per_second);
     if (f0 >= (double)e0 && f0 < (double)eK) {                             // finite, and inside the slots
         const long long F = (long long)f0;
-        const int s = bar_slot(b, K, nd, F);
-        const int D = bar_delta(b, K, s);
-        if (F <= (long long)b[s] + D / nd) {
+        const int s = slot_of(sl, F);
+        const int D = slot_delta(sl, s);
+        if (F <= (long long)sl.b[s] + D / sl.nd) {
             unsigned w = 1u;
             if (c.drum && r.pitch >= a.kick_lo && r.pitch <= a.kick_hi) w += (unsigned)a.w_kick;
             if (!c.drum && rint(r.offset * a.frames_per_second) - f0 >= (double)D) w += (unsigned)a.w_long;
@@ -100,15 +73,10 @@ __global__ __launch_bounds__(BAR_THREADS) void bar_features_kernel(BarArgs a) {
     if (hi <= e0 || lo >= eK) return;
     const int pc = r.pitch % 12;
     unsigned long long total = 0ull;
-    for (int s = bar_slot(b, K, nd, lo); s < K; ++s) {
-        const long long es = bar_edge(b, K, nd, s), en = bar_edge(b, K, nd, s + 1);
-        if (es >= hi) break;
-        const long long share = min(hi, en) - max(lo, es);
-        if (share > 0) {
-            atomicAdd(&a.chroma[(long long)s * 12 + pc], (unsigned)share);
-            total += (unsigned long long)share;
-        }
-    }
+    slot_walk(sl, lo, hi, [&](int s, long long share, long long) {
+        atomicAdd(&a.chroma[(long long)s * 12 + pc], (unsigned)share);
+        total += (unsigned long long)share;
+    });
     if (total) atomicAdd(&a.acc[pc], total);
 }
 
@@ -116,7 +84,7 @@ __global__ __launch_bounds__(BAR_THREADS) void bar_salience_kernel(BarArgs a) {
     __shared__ long long part[BAR_THREADS / WAVE];
     const int tid = threadIdx.x, lane = tid & (WAVE - 1), wave = tid >> 6;
     const long long s = (long long)blockIdx.x * BAR_THREADS + tid;
-    const int K = bar_beats(a);
+    const int K = beat_count(a.beat_result, a.max_beats);
     long long d = 0;
     if (K >= 2 && s < K) {
         const unsigned acc = min(a.accent[s], (unsigned)a.accent_cap);
@@ -190,7 +158,7 @@ __global__ __launch_bounds__(WAVE) void bar_key_kernel(BarArgs a) {
 
 __global__ __launch_bounds__(WAVE) void bar_path_kernel(BarArgs a) {
     const int lane = threadIdx.x;
-    const int K = bar_beats(a);
+    const int K = beat_count(a.beat_result, a.max_beats);
     if (K < 2) return;                                                     // result[0 .. 2] stay 0
     const int nM = a.n_metres;
     int m[BAR_MAX_METRES], first[BAR_MAX_METRES], last[BAR_MAX_METRES];
@@ -283,7 +251,7 @@ __global__ __launch_bounds__(WAVE) void bar_path_kernel(BarArgs a) {
 }  // namespace
 
 int launch_track_bars(const BarArgs& a, hipStream_t stream) {
-    if (a.n_programs < 1 || a.n_programs > BAR_MAX_PROGRAMS || a.drum_program < 0 || a.drum_program >= a.n_programs) return -1;
+    if (int e = slot_check_programs(a)) return e;
     if (a.n_metres < 1 || a.n_metres > BAR_MAX_METRES) return -2;
     int states = 0;
     for (int q = 0; q < a.n_metres; ++q) {
@@ -291,12 +259,9 @@ int launch_track_bars(const BarArgs& a, hipStream_t stream) {
         states += a.metres[q];
     }
     if (states > WAVE) return -2;
-    if (a.near_div < 2 || a.accent_cap < 1 || a.accent_cap > 255 || a.w_long < 0 || a.w_kick < 0 || a.w_accent < 0 || a.switch_cost < 0 ||
-        !(a.frames_per_second > 0.0))
-        return -3;
-    if (a.n_frames < 1 || a.n_frames > BAR_MAX_FRAMES || a.n < 0 || a.n > BAR_MAX_NOTES || (a.n && !a.notes)) return -4;
-    if (a.max_beats < 1 || a.max_beats > BAR_MAX_BEATS) return -5;
-    if (!a.beats || !a.beat_result || !a.accent || !a.chroma || !a.salience || !a.choice || !a.acc || !a.metre || !a.result) return -6;
+    if (a.accent_cap < 1 || a.accent_cap > 255 || a.w_long < 0 || a.w_kick < 0 || a.w_accent < 0 || a.switch_cost < 0) return -3;
+    if (int e = slot_check_call(a)) return e;
+    if (!a.accent || !a.salience || !a.choice || !a.acc || !a.metre) return -6;
     const unsigned beat_blocks = (unsigned)((a.max_beats + BAR_THREADS - 1) / BAR_THREADS);
     bar_clear_kernel<<<beat_blocks < (unsigned)BAR_CLEAR_BLOCKS ? beat_blocks : (unsigned)BAR_CLEAR_BLOCKS, BAR_THREADS, 0, stream>>>(a);
     if (a.n) bar_features_kernel<<<(unsigned)((a.n + BAR_THREADS - 1) / BAR_THREADS), BAR_THREADS, 0, stream>>>(a);

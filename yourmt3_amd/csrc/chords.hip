@@ -6,7 +6,7 @@
 // the number of records, and nothing is read back.
 // (a) chord_clear_kernel zeroes c[0, K)[12] and result[8] and sets bass[0, K) to 255.
 // (b) chord_features_kernel, one lane per record: classifies it by the rule every note consumer uses (note_rule.h), finds the first slot
-//     its span overlaps by a binary search over the slots' lower edges (computed on the fly from the beats, as bars.hip does), walks the
+//     its span overlaps by a binary search over the slots' lower edges (beat_slots.h, computed on the fly from the beats), walks the
 //     slots it overlaps, adds the shared frames to c[slot][pitch class] and, where the share is long enough, takes bass[slot] down to its
 //     pitch.  Integer atomicAdd and atomicMin: exact in any order.
 // (c) chord_path_kernel, one workgroup of four waves.  Wave 0 is the serial spine: the states two per lane (s = lane, lane + 64), V in
@@ -19,6 +19,7 @@
 // No kernel waits on another workgroup and nothing spins.
 #include "common.h"
 #include "kernels.h"
+#include "beat_slots.h"
 #include "note_rule.h"
 
 namespace {
@@ -29,33 +30,9 @@ constexpr int CHORD_ROW = 99;                                              // LD
 constexpr int CHORD_FLAG = 97;
 constexpr unsigned CHORD_NO_BASS = 255u, CHORD_NONE = 255u;
 
-__device__ __forceinline__ int chord_beats(const ChordArgs& a) {
-    const long long k = a.beat_result[0];
-    return (int)(k < 0 ? 0 : (k < a.max_beats ? k : a.max_beats));
-}
-
-// the slots' edges, i in [0, K]: lo[i] for i < K, hi[K-1] for i = K (bars.py, slot_edges)
-__device__ __forceinline__ long long chord_edge(const int32_t* b, int K, int nd, int i) {
-    if (i == 0) return (long long)b[0] - (b[1] - b[0]) / nd;
-    if (i < K) return (long long)b[i] - (b[i] - b[i - 1]) / nd;
-    const int d = b[K - 1] - b[K - 2];
-    return (long long)b[K - 1] + d - d / nd;
-}
-
-// the largest s in [0, K-1] with edge(s) <= f (0 if there is none)
-__device__ __forceinline__ int chord_slot(const int32_t* b, int K, int nd, long long f) {
-    int lo = 0, hi = K - 1;
-    while (lo < hi) {
-        const int mid = (lo + hi + 1) >> 1;
-        if (chord_edge(b, K, nd, mid) <= f) lo = mid;
-        else hi = mid - 1;
-    }
-    return lo;
-}
-
 __global__ __launch_bounds__(CHORD_THREADS) void chord_clear_kernel(ChordArgs a) {
     const long long stride = (long long)gridDim.x * CHORD_THREADS, t0 = (long long)blockIdx.x * CHORD_THREADS + threadIdx.x;
-    const long long K = chord_beats(a);
+    const long long K = beat_count(a.beat_result, a.max_beats);
     for (long long i = t0; i < K * 12; i += stride) a.chroma[i] = 0u;
     for (long long i = t0; i < K; i += stride) a.bass[i] = CHORD_NO_BASS;
     if (t0 < 8) a.result[t0] = 0;
@@ -70,23 +47,17 @@ __global__ __launch_bounds__(CHORD_THREADS) void chord_features_kernel(ChordArgs
         atomicAdd(reinterpret_cast<unsigned long long*>(&a.result[3]), 1ull);
         return;
     }
-    const int K = chord_beats(a);
+    const int K = beat_count(a.beat_result, a.max_beats);
     if (K < 2 || c.drum) return;
-    const int32_t* b = a.beats;
-    const int nd = a.near_div;
     long long lo, hi;
     if (!note_frame_span(r, false, a.frames_per_second, a.n_frames, &lo, &hi)) return;
-    if (hi <= chord_edge(b, K, nd, 0) || lo >= chord_edge(b, K, nd, K)) return;
+    const BeatSlots sl = {a.beats, K, a.near_div};
+    if (hi <= slot_edge(sl, 0) || lo >= slot_edge(sl, K)) return;
     const int pc = r.pitch % 12;
-    for (int s = chord_slot(b, K, nd, lo); s < K; ++s) {
-        const long long es = chord_edge(b, K, nd, s), en = chord_edge(b, K, nd, s + 1);
-        if (es >= hi) break;
-        const long long share = min(hi, en) - max(lo, es);
-        if (share > 0) {
-            atomicAdd(&a.chroma[(long long)s * 12 + pc], (unsigned)share);
-            if ((long long)a.bass_div * share >= en - es) atomicMin(&a.bass[s], (unsigned)r.pitch);
-        }
-    }
+    slot_walk(sl, lo, hi, [&](int s, long long share, long long length) {
+        atomicAdd(&a.chroma[(long long)s * 12 + pc], (unsigned)share);
+        if ((long long)a.bass_div * share >= length) atomicMin(&a.bass[s], (unsigned)r.pitch);
+    });
 }
 
 // where the states of the fixed table's quality q start in this object's state order; -1 if it is not among them
@@ -161,7 +132,7 @@ __device__ __forceinline__ unsigned long long chord_key(bool active, long long v
 __global__ __launch_bounds__(CHORD_THREADS) void chord_path_kernel(ChordArgs a) {
     __shared__ int em[2][WAVE * CHORD_ROW];
     const int tid = threadIdx.x, lane = tid & (WAVE - 1), wave = tid >> 6;
-    const int K = chord_beats(a);
+    const int K = beat_count(a.beat_result, a.max_beats);
     if (K < 2) return;                                                     // result[0 .. 2] stay 0
     const int S = 12 * a.n_qualities + 1;
     const int n_chunks = (K + WAVE - 1) / WAVE;
@@ -241,16 +212,13 @@ __global__ __launch_bounds__(CHORD_THREADS) void chord_path_kernel(ChordArgs a) 
 }  // namespace
 
 int launch_track_chords(const ChordArgs& a, hipStream_t stream) {
-    if (a.n_programs < 1 || a.n_programs > BAR_MAX_PROGRAMS || a.drum_program < 0 || a.drum_program >= a.n_programs) return -1;
+    if (int e = slot_check_programs(a)) return e;
     if (a.n_qualities < 1 || a.n_qualities > CHORD_QUALITIES) return -2;
     for (int k = 0; k < a.n_qualities; ++k)
         if (a.qualities[k] < 0 || a.qualities[k] >= CHORD_QUALITIES) return -2;
-    if (a.near_div < 2 || a.bass_div < 1 || a.w_bass < 0 || a.w_bass > 1024 || a.w_none < 0 || a.w_none > 1024 || a.change_cost < 0 ||
-        a.change_cost_down < 0 || !(a.frames_per_second > 0.0))
-        return -3;
-    if (a.n_frames < 1 || a.n_frames > BAR_MAX_FRAMES || a.n < 0 || a.n > BAR_MAX_NOTES || (a.n && !a.notes)) return -4;
-    if (a.max_beats < 1 || a.max_beats > BAR_MAX_BEATS) return -5;
-    if (!a.beats || !a.beat_result || !a.chroma || !a.bass || !a.back || !a.chord || !a.result) return -6;
+    if (a.bass_div < 1 || a.w_bass < 0 || a.w_bass > 1024 || a.w_none < 0 || a.w_none > 1024 || a.change_cost < 0 || a.change_cost_down < 0) return -3;
+    if (int e = slot_check_call(a)) return e;
+    if (!a.bass || !a.back || !a.chord) return -6;
     const unsigned beat_blocks = (unsigned)((a.max_beats + CHORD_THREADS - 1) / CHORD_THREADS);
     chord_clear_kernel<<<beat_blocks < (unsigned)CHORD_CLEAR_BLOCKS ? beat_blocks : (unsigned)CHORD_CLEAR_BLOCKS, CHORD_THREADS, 0, stream>>>(a);
     if (a.n) chord_features_kernel<<<(unsigned)((a.n + CHORD_THREADS - 1) / CHORD_THREADS), CHORD_THREADS, 0, stream>>>(a);

@@ -595,12 +595,8 @@ class TaskManager:
             raise ValueError("velocity and audio go together")
         if n == 0 or L == 0:
             if beats is not None:
-                none = {"beats": np.zeros(0, np.int32), "tempo": np.zeros(0, np.int32), "ticks": np.zeros((0, 2), np.int32)}
-                if bars is not None:
-                    none.update(metre=np.zeros(0, np.int32), bar_result=np.array([0, 0, 0, -1, 0, 0, 0, 0], np.int64))
-                if chords is not None:
-                    none.update(chord=np.zeros(0, np.int32), chord_result=np.zeros(8, np.int64))
-                return [], 0, none
+                from .tracking import empty
+                return [], 0, empty(bars is not None, chords is not None)
             return [], 0
         own = detokenizer is None
         if own:
@@ -613,38 +609,25 @@ class TaskManager:
             else:
                 rec_dev, counts = detokenizer.run_device(tokens, scores, torch.from_numpy(starts), float(end_sec))
                 vel_dev = velocity.run(audio, rec_dev, count=counts)[0] if velocity is not None else None
-                if beats is not None:
+                if beats is not None:                                    # under the device count, before it is copied back
+                    from . import tracking
                     from .beats import n_frames_of
-                    beats_dev, lags_dev, result_dev = beats.track(rec_dev, n_frames_of(end_sec, beats.params["frames_per_second"]), count=counts)
-                    ticks_dev = beats.positions(beats_dev, result_dev, rec_dev, counts, quantize)
+                    n_frames = n_frames_of(end_sec, beats.params["frames_per_second"])
+                    parts = tracking.launch_beats(beats, rec_dev, n_frames, counts, quantize)
                 n_notes, n_invalid = (int(v) for v in counts.cpu().tolist())
                 nb = n_notes * NOTE_RECORD.itemsize
-                parts = [rec_dev[:nb]] + ([vel_dev[:n_notes]] if velocity is not None else [])
-                if beats is not None:
-                    parts += [t.reshape(-1).view(torch.uint8) for t in (ticks_dev[:n_notes], result_dev, lags_dev, beats_dev)]
-                if bars is not None:                                     # on the live records: their number is known by now, the beats' is not
-                    metre_dev, bar_result_dev = bars.track(beats_dev, result_dev, rec_dev[:nb], n_frames_of(end_sec, beats.params["frames_per_second"]))
-                    parts += [t.view(torch.uint8) for t in (bar_result_dev, metre_dev)]
-                if chords is not None:                                   # the same, with the bars' metre where there is one
-                    chord_dev, chord_result_dev = chords.track(beats_dev, result_dev, metre_dev if bars is not None else None, rec_dev[:nb],
-                                                               n_frames_of(end_sec, beats.params["frames_per_second"]))
-                    parts += [t.view(torch.uint8) for t in (chord_result_dev, chord_dev)]
-                both = torch.cat(parts).cpu().numpy()
+                riders = [rec_dev[:nb]] + ([vel_dev[:n_notes]] if velocity is not None else [])
+                if beats is not None:                                    # bars and chords on the live records: their number is known by now, the beats' is not
+                    parts["ticks"] = parts["ticks"][:n_notes]
+                    tracking.launch_bars_chords(parts, bars, chords, rec_dev[:nb], n_frames)
+                    riders += tracking.pack(parts)
+                both = torch.cat(riders).cpu().numpy()
                 rec, o = both[:nb].view(NOTE_RECORD), nb
                 vel = None
                 if velocity is not None:
                     vel, o = both[o:o + n_notes].tolist(), o + n_notes
                 if beats is not None:
-                    ints = both[o:].view(np.int32)
-                    n_beats = int(ints[2 * n_notes:2 * n_notes + 8].view(np.int64)[0])
-                    o = 2 * n_notes + 8 + lags_dev.numel()
-                    tracked = {"beats": ints[o:o + n_beats].copy(), "tempo": ints[2 * n_notes + 8:o].copy(), "ticks": ints[:2 * n_notes].reshape(-1, 2).copy()}
-                    o += beats_dev.numel()
-                    if bars is not None:
-                        tracked.update(bar_result=ints[o:o + 16].view(np.int64).copy(), metre=ints[o + 16:o + 16 + (n_beats if n_beats >= 2 else 0)].copy())
-                        o += 16 + metre_dev.numel()
-                    if chords is not None:
-                        tracked.update(chord_result=ints[o:o + 16].view(np.int64).copy(), chord=ints[o + 16:o + 16 + (n_beats if n_beats >= 2 else 0)].copy())
+                    tracked = tracking.unpack(both[o:].view(np.int32), tracking.layout(parts))
         finally:
             if own:
                 detokenizer.close()

@@ -133,33 +133,21 @@ def transcribe(model, audio_info: Union[str, dict, np.ndarray], task_manager: Op
             constraint.close()
     end_sec = n_samples / cfg.sample_rate
     measurer = model.compile_note_velocity(**(velocity_params or {})) if velocity else None
-    tracker = tracked = bar_tracker = chord_tracker = None
+    chain = tracked = None
     try:
         if beats:
-            from .beats import DEFAULTS as BEAT_DEFAULTS, n_frames_of
-            fps = float((beat_params or {}).get("frames_per_second", BEAT_DEFAULTS["frames_per_second"]))
-            n_frames = n_frames_of(end_sec, fps)
-            tracker = model.compile_beat_tracker(n_frames, **(beat_params or {}))
-            if bars or chords:
-                from .bars import MAX_NOTES as BAR_MAX_NOTES
-                from .beats import max_beats
-                most = min(BAR_MAX_NOTES, max(1, int(segments.shape[0]) * cfg.n_channels * L))
-            if bars:
-                if float((bar_params or {}).get("frames_per_second", fps)) != fps:
-                    raise ValueError("bar_params' frames_per_second must be the beats'")
-                bar_tracker = model.compile_bar_tracker(max_beats(n_frames, tracker.lag_min), most, **{**(bar_params or {}), "frames_per_second": fps})
-            if chords:
-                if float((chord_params or {}).get("frames_per_second", fps)) != fps:
-                    raise ValueError("chord_params' frames_per_second must be the beats'")
-                chord_tracker = model.compile_chord_tracker(max_beats(n_frames, tracker.lag_min), most, **{**(chord_params or {}), "frames_per_second": fps})
+            from .bars import MAX_NOTES as BAR_MAX_NOTES
+            from .beats import n_frames_of
+            from .tracking import Chain, beats_fps, render
+            chain = Chain(model, n_frames_of(end_sec, beats_fps(beat_params)), min(BAR_MAX_NOTES, max(1, int(segments.shape[0]) * cfg.n_channels * L)),
+                          beat_params, (bar_params or {}) if bars else None, (chord_params or {}) if chords else None)
         in_place = device_detok and min_confidence is None                   # measured and tracked on the detokeniser's records where they lie
         if device_detok:
             extra = {}
             if in_place and measurer is not None:
                 extra.update(velocity=measurer, audio=segments.view(-1))
-            if in_place and tracker is not None:
-                extra.update(beats=tracker, quantize=quantize, **({"bars": bar_tracker} if bar_tracker is not None else {}),
-                             **({"chords": chord_tracker} if chord_tracker is not None else {}))
+            if in_place and chain is not None:
+                extra.update(beats=chain.beats, quantize=quantize, bars=chain.bars, chords=chain.chords)
             out = task_manager.tokens_to_notes_device(model, tokens, start_secs, end_sec, scores=scores, **extra)
             notes, tracked = out[0], (out[2] if len(out) > 2 else None)
         else:
@@ -168,47 +156,21 @@ def transcribe(model, audio_info: Union[str, dict, np.ndarray], task_manager: Op
             notes = drop_low_confidence(notes, float(min_confidence))
         if measurer is not None and not in_place:                           # the host's notes: one upload of their records, the same kernel
             notes = measurer.apply(segments.view(-1), notes)
-        if tracker is not None and tracked is None:                         # the same for the beats
-            rec_host = torch.from_numpy(to_records(list(notes)).view(np.uint8).reshape(-1).copy())
-            b, t, _, ticks = tracker.run(rec_host, n_frames, divisions=quantize)
-            tracked = {"beats": b, "tempo": t, "ticks": ticks}
-            if bar_tracker is not None:
-                tracked["metre"], tracked["bar_result"] = bar_tracker.run(b, rec_host, n_frames)
-            if chord_tracker is not None:
-                tracked["chord"], tracked["chord_result"] = chord_tracker.run(b, rec_host, n_frames, metre=tracked.get("metre"))
+        if chain is not None and tracked is None:                           # the same for the chain: up once, back once
+            tracked = chain.run(torch.from_numpy(to_records(list(notes)).view(np.uint8).reshape(-1).copy()), quantize)
     finally:
         if measurer is not None:
             measurer.close()
-        if chord_tracker is not None:
-            chord_tracker.close()
-        if bar_tracker is not None:
-            bar_tracker.close()
-        if tracker is not None:
-            tracker.close()
+        if chain is not None:
+            chain.close()
     os.makedirs(output_dir, exist_ok=True)
     if tracked is None:
         midi_path = write_midi(notes, os.path.join(output_dir, name + ".mid"))
         return (midi_path, notes) if return_notes else midi_path
-    from .beats import beat_summary
-    from .midi import notes_to_midi_bytes_on_beats
     midi_path = os.path.join(output_dir, name + ".mid")
-    markers = ()
-    if "chord" in tracked:
-        from .chords import chord_markers, chord_segments, chord_summary
-        markers = chord_markers(chord_segments(tracked["chord"], tracked["beats"]), tracked["beats"])
+    midi, info = render(notes, tracked, chain.fps)
     with open(midi_path, "wb") as f:
-        if "metre" in tracked:
-            from .midi import notes_to_midi_bytes_on_bars
-            f.write(notes_to_midi_bytes_on_bars(notes, tracked["ticks"], tracked["beats"], tracked["metre"], int(tracked["bar_result"][3]), fps, markers))
-        else:
-            f.write(notes_to_midi_bytes_on_beats(notes, tracked["ticks"], tracked["beats"], fps, markers))
-    info = beat_summary(tracked["beats"], tracked["tempo"], fps)
-    info["ticks"] = tracked["ticks"]
-    if "metre" in tracked:
-        from .bars import bar_summary
-        info.update(bar_summary(tracked["metre"], tracked["bar_result"], tracked["beats"], fps))
-    if "chord" in tracked:
-        info.update(chord_summary(tracked["chord"], tracked["chord_result"], tracked["beats"], fps))
+        f.write(midi)
     return (midi_path, notes, info) if return_notes else (midi_path, info)
 
 
