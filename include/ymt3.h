@@ -1003,6 +1003,25 @@ typedef struct ymt3_mc_cross_args {
 } ymt3_mc_cross_args;
 int ymt3_test_mc_cross_attention(ymt3_handle h, const ymt3_mc_cross_args* args, void* stream);
 
+/* Per-kernel test door of the mixture-of-experts decoder FFN's SEPARATE launches (csrc/moe.hip; the one-launch restatement moe_chain.hip is
+ * tied to them by the bit-identity test).  Same rules as the doors above.  ymt3_test_moe_stage: launch_moe_stage with no routing trace.
+ * stage 0 router: xn[r] = R(h[r] * rsqrt(sum_t ssq[t][r] / 512 + eps) * gain) (bf16), sel[2r], sel[2r + 1] = the two largest of
+ *           xn[r] . router[e] (e < E), ties to the lower id, gate[2r], gate[2r + 1] = their softmax; rows r in [row0, row0 + R)
+ * stage 1 expert wi: hidden[2 row0 + p] = R(relu(xn[row0 + (p >> 1)] . wi[sel[2 row0 + p]]^T)) for the pairs p in [0, 2R)
+ * stage 2 expert wo: y[2 row0 + p] = gate[2 row0 + p] * (hidden[2 row0 + p] . wo[sel[2 row0 + p]]^T)
+ * stage 3 combine:   h[r] += y[2r] + y[2r + 1]; ssq[0][r] = sum(h[r]^2), ssq[1..31][r] = 0
+ * fp8 != 0 (stages 1, 2): weights wi_q8 / wo_q8 (OCP e4m3, same shapes) with one fp32 scale per expert (wi_s / wo_s [E]); the activation
+ * rows are quantised per row by the kernel.  A pair whose sel lies outside [0, E) is written by no stage.  d_model = 512, d_ff = 2048,
+ * top_k = 2, 2 <= E <= 16, 1 <= R <= 1536, ssq_stride >= row0 + R; only the pointers the stage reads or writes are looked at. */
+typedef struct ymt3_moe_args {
+    float* h; const float* gain; float* ssq; const void* router; const void* wi; const void* wo;
+    const void* wi_q8; const void* wo_q8; const float* wi_s; const float* wo_s;
+    void* xn; int32_t* sel; float* gate; void* hidden; float* y;
+    int32_t ssq_stride, fp8, row0, R, E, top_k, d_model, d_ff;
+    float eps;
+} ymt3_moe_args;
+int ymt3_test_moe_stage(ymt3_handle h, int stage, const ymt3_moe_args* args, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -672,6 +672,40 @@ def test_moe_chain_is_bit_identical_to_the_five_launches(fp8, monkeypatch):
     old.close()
 
 
+@pytest.mark.parametrize("fp8", [0, 1], ids=["bf16", "fp8"])
+def test_moe_chain_is_bit_identical_to_the_five_launches_under_one_sided_routing(fp8, monkeypatch):
+    """The test above meets balanced routing only.  Here every layer's eight router rows are identical, so every logit of a row is the same
+    fp32 value (experts 0..7 share one summation order) and every row picks experts (0, 1) with gates 0.5: at B = 64 two experts hold 64
+    pairs each (four full chunks) and six hold none; B = 33 leaves a ragged chunk, B = 1 one pair each.  Ids, logits and the recorded
+    choices must equal the five launches' bit for bit (tests/test_moe_kernels.py pins those launches to their contracts)."""
+    from yourmt3_amd.config import FFN_MOE
+    cfg = YMT3Config(segment_samples=8191, max_decode_len=64, dec_ffn=FFN_MOE, moe_fp8=fp8, eos_id=-1)
+    W = make_weights(cfg, seed=1234)
+    for k in [k for k in W if k.endswith(".router")]:
+        W[k] = W[k][:1].expand_as(W[k]).contiguous()
+    monkeypatch.setenv("YMT3_DEBUG_HOOKS", "1")
+    monkeypatch.setenv("YMT3_NO_MOE_CHAIN", "1")
+    old = _model(cfg, max_batch=64, weights=W)
+    monkeypatch.delenv("YMT3_NO_MOE_CHAIN")
+    new = _model(cfg, max_batch=64, weights=W)
+    monkeypatch.delenv("YMT3_DEBUG_HOOKS")
+    n = 16
+    tr_new, tr_old = new.moe_trace(n), old.moe_trace(n)
+    e1 = new.encode(new.logmel(O.synthetic_audio(2, cfg).cuda()))
+    assert new.profile_decode(e1, 8, stride=4)["ffn_wi_gemm"]["launches"] == 0 and old.profile_decode(e1, 8, stride=4)["ffn_wi_gemm"]["launches"] > 0
+    want = torch.tensor([0, 1], dtype=torch.int32, device=tr_new.device)
+    for B in (1, 33, 64):
+        a = O.synthetic_audio(B, cfg, seed=50 + B).cuda()
+        e = new.encode(new.logmel(a))
+        t_new, l_new = new.decode(e, n, return_logits=True)
+        t_old, l_old = old.decode(e, n, return_logits=True)
+        assert torch.equal(t_new, t_old) and torch.equal(l_new, l_old), B
+        assert torch.equal(tr_new[:n, :, :B], tr_old[:n, :, :B]), B
+        assert bool((tr_new[:n, :, :B] == want).all()) and bool((tr_old[:n, :, :B] == want).all()), B
+    new.close()
+    old.close()
+
+
 def _full_size_properties(cfg, B, seed, probe, probe_len=1):
     """Size-independent properties of one BASELINE config at its full size (far beyond what the CPU oracle checks in
     seconds): shape / id range, bitwise reproducibility, independence of a segment from the rest of the batch,

@@ -38,7 +38,7 @@ SYMBOLS = [
     "ymt3_bars_create", "ymt3_bars_destroy", "ymt3_track_bars",
     "ymt3_chords_create", "ymt3_chords_destroy", "ymt3_track_chords",
     "ymt3_test_gemm_ex", "ymt3_test_rmsnorm", "ymt3_test_enc_attention", "ymt3_test_seq_attention", "ymt3_test_spec_embed",
-    "ymt3_test_dec_gemm", "ymt3_test_dec_attention", "ymt3_test_mc_cross_attention",
+    "ymt3_test_dec_gemm", "ymt3_test_dec_attention", "ymt3_test_mc_cross_attention", "ymt3_test_moe_stage",
 ]
 
 _lib = None
@@ -123,6 +123,13 @@ class McCrossArgs(ctypes.Structure):
     """ymt3_mc_cross_args of include/ymt3.h"""
     _fields_ = [(n, ctypes.c_void_p) for n in ("x_f32", "gain", "ssq", "wq", "k", "v", "out")] + [
         (n, ctypes.c_int32) for n in ("row0", "n_seg", "n_channels", "H", "T", "ssq_stride", "d")] + [("eps", ctypes.c_float)]
+
+
+class MoeArgs(ctypes.Structure):
+    """ymt3_moe_args of include/ymt3.h"""
+    _fields_ = [(n, ctypes.c_void_p) for n in ("h", "gain", "ssq", "router", "wi", "wo", "wi_q8", "wo_q8", "wi_s", "wo_s", "xn", "sel", "gate",
+                                               "hidden", "y")] + [
+        (n, ctypes.c_int32) for n in ("ssq_stride", "fp8", "row0", "R", "E", "top_k", "d_model", "d_ff")] + [("eps", ctypes.c_float)]
 
 
 class YMT3Error(RuntimeError):
@@ -321,6 +328,8 @@ def load() -> ctypes.CDLL:
     lib.ymt3_test_spec_embed.restype = i32
     lib.ymt3_test_dec_gemm.argtypes = [vp, i32, ctypes.POINTER(DecGemmArgs), vp]
     lib.ymt3_test_dec_gemm.restype = i32
+    lib.ymt3_test_moe_stage.argtypes = [vp, i32, ctypes.POINTER(MoeArgs), vp]
+    lib.ymt3_test_moe_stage.restype = i32
     lib.ymt3_test_dec_attention.argtypes = [vp, ctypes.POINTER(DecAttnArgs), vp]
     lib.ymt3_test_dec_attention.restype = i32
     lib.ymt3_test_mc_cross_attention.argtypes = [vp, ctypes.POINTER(McCrossArgs), vp]

@@ -7,6 +7,10 @@
 //     (e0,e1) = the two largest logits, ties to the lower expert id; gates = softmax(l[e0], l[e1])
 //     y_j     = R( relu(xn . wi[e_j]^T) ) . wo[e_j]^T           dense ReLU FFN of expert e_j
 //     h      += g0*y_0 + g1*y_1                                 fp32, slot order fixed
+// The tie rule is a rule on the fp32 logits: the scan below goes up the expert ids with strict >, in both slots.  Experts 0..7 (8-lane
+// groups: 64 sequential fmas, a 3-step tree) and experts 8..15 (64 lanes of 8 fmas, a 6-step tree) sum in two orders, so across that
+// boundary two MATHEMATICALLY equal logits of ordinary values need not be equal in fp32 and the lower id need not win; logits that are
+// exact in fp32 tie exactly in either order (tests/test_moe_kernels.py pins pairs (7, 8) and (8, 15) that way).  DESIGN.md section 28.
 //
 // Three kernels (four launches per layer), no float atomics, every reduction in a fixed order (bitwise reproducible):
 //   moe_router_kernel   one wave per row: norm from the carried sum(h^2) partials, router dots, top-2, gates

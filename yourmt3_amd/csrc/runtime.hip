@@ -2118,6 +2118,39 @@ extern "C" int ymt3_test_mc_cross_attention(ymt3_handle h, const ymt3_mc_cross_a
     HIP_TRY(hipGetLastError());
     return YMT3_OK;
 }
+
+extern "C" int ymt3_test_moe_stage(ymt3_handle h, int stage, const ymt3_moe_args* args, void* stream) {
+    int rc = check_call(h, 0);
+    if (rc) return rc;
+    if (!args) FAIL(YMT3_ERR_ARG, "%s: args is null", __func__);
+    const ymt3_moe_args& c = *args;
+    DOOR_REQUIRE(stage >= 0 && stage <= 3);
+    DOOR_REQUIRE(c.d_model == 512 && c.d_ff == 2048 && c.top_k == 2);
+    DOOR_REQUIRE(c.E >= 2 && c.E <= 16);
+    DOOR_REQUIRE(c.R >= 1 && c.R <= 1536 && c.row0 >= 0 && c.row0 <= 0xffff && c.ssq_stride >= c.row0 + c.R);
+    const bool fp8 = c.fp8 != 0;
+    if (stage == 0) {
+        DOOR_PTR(c.h); DOOR_PTR(c.gain); DOOR_PTR(c.ssq); DOOR_PTR(c.router); DOOR_PTR(c.xn); DOOR_PTR(c.sel); DOOR_PTR(c.gate);
+    } else if (stage == 1) {
+        DOOR_PTR(c.xn); DOOR_PTR(c.sel); DOOR_PTR(c.hidden);
+        if (fp8) { DOOR_PTR(c.wi_q8); DOOR_PTR(c.wi_s); } else DOOR_PTR(c.wi);
+    } else if (stage == 2) {
+        DOOR_PTR(c.hidden); DOOR_PTR(c.sel); DOOR_PTR(c.gate); DOOR_PTR(c.y);
+        if (fp8) { DOOR_PTR(c.wo_q8); DOOR_PTR(c.wo_s); } else DOOR_PTR(c.wo);
+    } else {
+        DOOR_PTR(c.h); DOOR_PTR(c.y); DOOR_PTR(c.ssq);
+    }
+    MoeArgs a{};                    // sel_trace stays null: the router records nothing and reads no DecodeShared
+    a.h = c.h; a.gain = c.gain; a.ssq = c.ssq; a.ssq_stride = c.ssq_stride; a.router = static_cast<const bf16_t*>(c.router);
+    a.wi = static_cast<const bf16_t*>(c.wi); a.wo = static_cast<const bf16_t*>(c.wo);
+    a.wi_q8 = static_cast<const uint8_t*>(c.wi_q8); a.wo_q8 = static_cast<const uint8_t*>(c.wo_q8); a.wi_s = c.wi_s; a.wo_s = c.wo_s;
+    a.fp8 = fp8 ? 1 : 0;
+    a.xn = static_cast<bf16_t*>(c.xn); a.sel = c.sel; a.gate = c.gate; a.hidden = static_cast<bf16_t*>(c.hidden); a.y = c.y;
+    a.row0 = c.row0; a.R = c.R; a.E = c.E; a.top_k = c.top_k; a.d_model = c.d_model; a.d_ff = c.d_ff; a.eps = c.eps;
+    LAUNCH(launch_moe_stage(stage, a, (hipStream_t)stream));
+    HIP_TRY(hipGetLastError());
+    return YMT3_OK;
+}
 #undef DOOR_PTR
 #undef DOOR_REQUIRE
 

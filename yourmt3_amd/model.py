@@ -1260,3 +1260,38 @@ class YourMT3:
         c = _lib.McCrossArgs(x.data_ptr(), gain.data_ptr(), ssq.data_ptr(), wq.data_ptr(), k.data_ptr(), v.data_ptr(), out.data_ptr(), row0, n_seg,
                              n_channels, H, T, ssq_stride, 512, float(eps))
         _lib.check(self._lib.ymt3_test_mc_cross_attention(self._handle, ctypes.byref(c), self._stream()))
+
+    def test_moe_stage(self, stage: int, *, R: int, E: int, row0: int = 0, eps: float = 1e-6, fp8: bool = False,
+                       ssq_stride: Optional[int] = None, h: Optional[torch.Tensor] = None, gain: Optional[torch.Tensor] = None,
+                       ssq: Optional[torch.Tensor] = None, router: Optional[torch.Tensor] = None, wi: Optional[torch.Tensor] = None,
+                       wo: Optional[torch.Tensor] = None, wi_q8: Optional[torch.Tensor] = None, wo_q8: Optional[torch.Tensor] = None,
+                       wi_s: Optional[torch.Tensor] = None, wo_s: Optional[torch.Tensor] = None, xn: Optional[torch.Tensor] = None,
+                       sel: Optional[torch.Tensor] = None, gate: Optional[torch.Tensor] = None, hidden: Optional[torch.Tensor] = None,
+                       y: Optional[torch.Tensor] = None, d_model: int = 512, d_ff: int = 2048, top_k: int = 2) -> None:
+        """ymt3_test_moe_stage (include/ymt3.h): stage 0 router, 1 expert wi, 2 expert wo, 3 combine.  Every row-indexed tensor starts at row 0
+        (pair-indexed ones at pair 0) and must reach row0 + R (2 (row0 + R)); outputs are written in place.  Only the tensors the stage reads
+        or writes are needed."""
+        need, rows = self._need, row0 + R
+        need(0 <= stage <= 3, "a stage in 0..3")
+        need(d_model == 512 and d_ff == 2048 and top_k == 2, "d_model == 512, d_ff == 2048, top_k == 2")
+        need(2 <= E <= 16, "2 <= E <= 16")
+        need(1 <= R <= 1536 and 0 <= row0 <= 0xffff, "1 <= R <= 1536, 0 <= row0")
+        ssq_stride = rows if ssq_stride is None else ssq_stride
+        need(ssq_stride >= rows, "ssq_stride >= row0 + R")
+        bf, f32 = torch.bfloat16, torch.float32
+        want = {0: ("h", "gain", "ssq", "router", "xn", "sel", "gate"),
+                1: ("xn", "sel", "hidden") + (("wi_q8", "wi_s") if fp8 else ("wi",)),
+                2: ("hidden", "sel", "gate", "y") + (("wo_q8", "wo_s") if fp8 else ("wo",)),
+                3: ("h", "y", "ssq")}[stage]
+        spec = dict(h=(h, f32, rows * d_model), gain=(gain, f32, d_model), ssq=(ssq, f32, 31 * ssq_stride + rows), router=(router, bf, E * d_model),
+                    wi=(wi, bf, E * d_ff * d_model), wo=(wo, bf, E * d_ff * d_model), wi_q8=(wi_q8, torch.uint8, E * d_ff * d_model),
+                    wo_q8=(wo_q8, torch.uint8, E * d_ff * d_model), wi_s=(wi_s, f32, E), wo_s=(wo_s, f32, E), xn=(xn, bf, rows * d_model),
+                    sel=(sel, torch.int32, 2 * rows), gate=(gate, f32, 2 * rows), hidden=(hidden, bf, 2 * rows * d_ff), y=(y, f32, 2 * rows * d_model))
+        for name in want:
+            t, dtype, n = spec[name]
+            need(t is not None, f"{name} in stage {stage}")
+            self._door(name, t, dtype, n)
+        p = lambda name: spec[name][0].data_ptr() if name in want else None
+        c = _lib.MoeArgs(*[p(n) for n in ("h", "gain", "ssq", "router", "wi", "wo", "wi_q8", "wo_q8", "wi_s", "wo_s", "xn", "sel", "gate", "hidden", "y")],
+                         ssq_stride, int(bool(fp8)), row0, R, E, top_k, d_model, d_ff, float(eps))
+        _lib.check(self._lib.ymt3_test_moe_stage(self._handle, int(stage), ctypes.byref(c), self._stream()))
