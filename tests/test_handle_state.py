@@ -1,8 +1,9 @@
 """Decoder parity along the axis of the handle's HISTORY: a handle that has been through any other call gives the bits of a fresh handle.
 
-A ymt3_handle carries state from call to call: the cache of captured step graphs (kernel arguments frozen at capture), the per-call host
-modes (slot mode, beam width, the layer-0 table switch, early stop), the device loop state (DecodeShared, finished / row_state / row_pos,
-the beam buffers), counters that are right only if the previous call left them at zero (ticket, chain_sync, pair_rows, step_sync),
+A ymt3_handle carries state from call to call: the cache of captured step graphs (kernel arguments frozen at capture, filed under a key
+derived from the call's step shape), the host settings that outlive a call (early stop, abort recovery, the debug traces; the per-call
+modes -- slot mode, beam width, the layer-0 table switch -- travel in the step shape and are no longer kept on the handle, which this file
+keeps holding to account), the device loop state (DecodeShared, finished / row_state / row_pos, the beam buffers), counters that are right only if the previous call left them at zero (ticket, chain_sync, pair_rows, step_sync),
 buffers no call clears (the K/V cache, the MoE buffers, ckv, the logits) and objects the caller creates and destroys mid-life
 (constraints, detokenisers, resampler filters).  The other axis files meet a handle fresh, or in whatever order a module's tests happen
 to run.  Here the order is the subject.

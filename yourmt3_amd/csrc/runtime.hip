@@ -43,18 +43,30 @@ struct StepGraph {
     hipGraphExec_t exec = nullptr;
     bool merged = false;            // the captured steps contain merged kernels (GEMM chain / attention pair): their abort word must be looked at
 };
-// What a cached step graph was captured for: everything that changes a captured launch and is not read from device memory.
+// The host-side inputs of one decoder step: everything that decides its launches and is not read from device memory.  Built once per
+// call (step_shape, chain_shape) and passed down by value; nothing about a step is kept on the handle between calls.
 enum StepMode { SM_LOCKSTEP = 0, SM_BEAM, SM_SLOT, SM_SLOT_BEAM };
-struct StepKey {
+struct StepShape {
     StepMode mode = SM_LOCKSTEP;
     int B = 0;                      // segments of the call (lock-step, beam) or slots (slot modes)
-    int n_chains = 1, chain = 0;    // chains the call used, and which of them this graph serves
-    int beams = 0;                  // W of a beam call, 0 otherwise
-    int steps = 1;                  // decode steps in the graph (set by step_graph)
+    int W = 0;                      // beams per group of a beam call, 0 otherwise
+    int n_chains = 1, chain = 0;    // chains the call uses, and which of them this step belongs to
+    int row0 = 0, R = 0;            // the step's rows [row0, row0 + R): the chain's share of the call's rows
+    bool solo = true;               // the only decode stream of the handle while it runs (n_chains == 1)
+    bool qkv0 = false;              // layer 0's q / k / v come from the table (qkv0_applies): the steps launch no layer-0 projection
+    bool profiled = false;          // ymt3_profile_decode's call: its launch sequence is the one the profile classes are defined by
+    bool slot() const { return mode == SM_SLOT || mode == SM_SLOT_BEAM; }     // rows at their own positions (row_pos / row_out / row_prompt)
+};
+// What a cached step graph is filed under.  Derived from the shape (step_key) and from nothing else: row0, R, solo and qkv0 follow from
+// (mode, B, W, n_chains, chain) and the handle's create-time configuration, and a profiled call replays no graph.
+struct StepKey {
+    StepMode mode;
+    int B, n_chains, chain, beams, steps;       // steps: decode steps in the graph
     bool operator<(const StepKey& o) const {
         return std::tie(mode, B, n_chains, chain, beams, steps) < std::tie(o.mode, o.B, o.n_chains, o.chain, o.beams, o.steps);
     }
 };
+static StepKey step_key(const StepShape& S, int steps) { return StepKey{S.mode, S.B, S.n_chains, S.chain, S.W, steps}; }
 
 // The decoder's weights, looked up in the blob once (create_impl: bind_dec_weights) with the dtype and minimum size the kernels rely on.
 struct LayerW {
@@ -103,13 +115,12 @@ struct ymt3_ctx {
     float* opart = nullptr;             // [maxR][H][d]: per-head O-projection partials of the self-attention kernel (fold_o)
     MoeArgs moe{};                      // scratch pointers of the MoE FFN (dec_ffn == YMT3_FFN_MOE)
     int* finished = nullptr;
-    // slot mode (ymt3_transcribe_stream): per-row positions and output offsets; launch_step wires them in while set
+    // slot modes (ymt3_transcribe_stream*): per-row positions and output offsets, wired into the launches of a step whose shape says slot()
     int* row_pos = nullptr;             // [maxR]
     long long* row_out = nullptr;       // [maxR]
     long long* row_prompt = nullptr;    // [maxR]: slot mode, offset of the row's prompt in the caller's prompt buffer
     int* row_state = nullptr;           // [maxR]: every row's token-automaton state (include/ymt3.h, constraints)
     int* host_rows = nullptr;           // pinned [maxR]: copy of `finished` for the host's retire/admit decisions
-    bool slot_mode = false;
     DecodeShared* shared = nullptr;     // [MAX_CHAINS] per-chain loop state
     DecodeShared* test_shared = nullptr;   // the decoder test doors' own block (ymt3_test_dec_gemm / _dec_attention), allocated at first use
     hipStream_t cap_stream = nullptr;
@@ -122,9 +133,11 @@ struct ymt3_ctx {
     // Round 3, many rows: with 168-256 rows of one channel the attention kernels are bandwidth-bound and the GEMMs between them latency-bound, and
     // two chains of 84-128 rows do overlap: 626 against 690 ms per batch of 256, -6 % at 176 and 192 (profiles/r03_chains_many_rows.txt; -1 % at 160, slower from
     // 512).  `auto_chains` (YMT3_CHAINS unset) takes two chains exactly there -- both halves and the whole stay in the same kernel regime (8-wave
-    // attention, 16-row-tile GEMMs, no folded O-projection), so the ids do not depend on the choice (tested).
+    // attention, 16-row-tile GEMMs, no folded O-projection), so the ids do not depend on the choice (tested); decode_run checks just that
+    // on the plans of the whole and of both halves (bits_agree) before it takes them.
     bool auto_chains = true;
-    int last_chains = 1;
+    int last_chains = 1;                    // chains of the last decode call (ymt3_last_decode_chains)
+    bool last_qkv0 = false;                 // the last decode call took layer 0's q / k / v from the table (ymt3_qkv0_table_active)
     hipStream_t chain_stream[8] = {};
     hipEvent_t fork_ev = nullptr, join_ev[8] = {};
     std::map<StepKey, StepGraph> step_graphs;
@@ -136,7 +149,6 @@ struct ymt3_ctx {
     bool gemm_chain = true;                 // cross O -> FFN-in -> FFN-out -> next QKV / lm_head as one launch (dec_chain.hip; YMT3_NO_GEMM_CHAIN=1: four launches)
     unsigned* chain_sync = nullptr;         // [CHAIN_SYNC_WORDS] device: the chain kernel's arrival counters + sticky abort word
     unsigned* chain_host_abort = nullptr;   // pinned: set by the chain kernel together with the abort word; checked at every call
-    bool step_merged = false;               // set by launch_step: the step it just captured / launched contains merged kernels
     bool forced_abort = false;              // ymt3_debug_force_stage_abort: raise the host word after the next decode call, as a kernel would during it
     // What happens when a merged kernel gives up waiting (ymt3_set_abort_recovery): 1 (default) = every decode call that ran merged kernels ends
     // by waiting for its stream and looking at the abort word; an abort re-runs the call through the separate launches (same bits) and the
@@ -153,9 +165,8 @@ struct ymt3_ctx {
     bool step_tiles_free = false;           // YMT3_STEP_TILES_FREE=1 (A/B): the step kernel's four row tiles as independent pipelines instead of in step
     // Layer 0's QKV projection as a table (kernels.h, ArgmaxArgs::qkv0): [vocab][3 * inner] bf16, built at create for a one-channel decoder
     // (YMT3_NO_QKV0_TABLE=1: not built; neither under YMT3_STAMP nor with the per-step kernel, whose launch sequences stay as they were).
-    // qkv0_call: the decode call being built gathers from it and its steps launch no layer-0 projection (decided per call, see qkv0_decide).
+    // Whether a call gathers from it is decided per call (qkv0_applies) and carried in the call's StepShape.
     bf16_t* qkv0_table = nullptr;
-    bool qkv0_call = false;
     unsigned* ticket = nullptr;             // [maxR / 32 + 1] lines: the argmax kernel's two-level ticket (many rows)
     unsigned* step_sync = nullptr;          // [STEP_SYNC_LINES] counter lines of that kernel (zeroed by the step's argmax kernel / before a decode call)
     // sampled per-kernel-class timing (ymt3_profile_decode): events bracket single launches
@@ -169,9 +180,8 @@ struct ymt3_ctx {
     int prof_step0 = 0;                     // ymt3_debug_decode_start: the next decode call begins at this position (one shot)
     int32_t* moe_trace = nullptr;           // ymt3_debug_moe_trace: caller's [steps][layers][rows][2] buffer the MoE router records its choices in
     int moe_trace_steps = 0, moe_trace_rows = 0;
-    // beam search (include/ymt3.h): all scratch is sized at create by the handle's rows and max_decode_len.  beam_W > 0 only while a beam
-    // call builds its steps: launch_step then addresses the self-attention cache through the ancestry table and ends with the selection kernel
-    int beam_W = 0;
+    // beam search (include/ymt3.h): all scratch is sized at create by the handle's rows and max_decode_len.  A step whose shape has W > 0
+    // addresses the self-attention cache through the ancestry table and ends with the selection kernel
     BeamArgs beam{};                        // the scratch pointers (anc, fed_tok, run, finished slots, ...)
     BeamShared* beam_shared = nullptr;      // device: the call's parameters and the debug trace pointers
     BeamShared beam_trace{};                // ymt3_debug_beam_trace: host copy of the trace fields (carried into every call's parameters)
@@ -306,7 +316,7 @@ extern "C" void ymt3_destroy(ymt3_handle h) {
 }
 
 extern "C" size_t ymt3_device_bytes(ymt3_handle h) { return h ? h->dev_bytes : 0; }
-extern "C" int ymt3_qkv0_table_active(ymt3_handle h) { return h && h->qkv0_call ? 1 : 0; }
+extern "C" int ymt3_qkv0_table_active(ymt3_handle h) { return h && h->last_qkv0 ? 1 : 0; }
 
 // Layer 0's QKV projection over the whole vocabulary (kernels.h, ArgmaxArgs::qkv0): the decode step's own two kernels -- embed_row, then the
 // 16-row-tile dec_gemm_kernel<DG_NORM_QKV_CACHE> writing its packed rows to the table -- with the token ids as rows, in chunks of 256 (below
@@ -864,57 +874,84 @@ extern "C" int ymt3_encode(ymt3_handle h, const float* mel_dev, int B, void* enc
 }
 
 // the beam kernels' arguments for R rows of W beams: the handle's scratch, the step's buffers, the embedding tables
-static BeamArgs beam_args(ymt3_handle h, int R, int W, DecodeShared* shared) {
+static BeamArgs beam_args(ymt3_handle h, int R, int W, DecodeShared* shared, bool slot) {
     const ymt3_config& k = h->cfg;
     BeamArgs b = h->beam;
     b.logits = h->logits; b.h = h->h_dec; b.shared = shared; b.beam = h->beam_shared; b.finished = h->finished; b.ssq = h->ssq; b.ssq_stride = h->maxR;
     b.R = R; b.V = k.vocab; b.d = k.d_model; b.n_channels = k.n_channels; b.eos_id = k.eos_id; b.pad_id = k.pad_id; b.W = W; b.row_state = h->row_state;
-    if (h->slot_mode) { b.row_pos = h->row_pos; b.row_out = h->row_out; b.row_prompt = h->row_prompt; }
+    if (slot) { b.row_pos = h->row_pos; b.row_out = h->row_out; b.row_prompt = h->row_prompt; }
     b.embed = h->dec.embed; b.chan_embed = h->dec.chan_embed;
     return b;
 }
 
 // what every user of ArgmaxArgs fills alike for R rows (the step's feeding kernel, decode_init, the slot kernels): loop state, the
-// embedding tables, the automaton states and, in slot mode, the per-row positions and offsets
-static ArgmaxArgs argmax_base(ymt3_handle h, int R) {
+// embedding tables, the automaton states and, in a slot mode, the per-row positions and offsets
+static ArgmaxArgs argmax_base(ymt3_handle h, int R, bool slot) {
     const ymt3_config& k = h->cfg;
     ArgmaxArgs a{};
     a.h = h->h_dec; a.shared = h->shared; a.finished = h->finished; a.ssq = h->ssq; a.ssq_stride = h->maxR;
     a.R = R; a.V = k.vocab; a.d = k.d_model; a.n_channels = k.n_channels; a.eos_id = k.eos_id; a.pad_id = k.pad_id;
     a.embed = h->dec.embed; a.chan_embed = h->dec.chan_embed; a.row_state = h->row_state;
-    if (h->slot_mode) { a.row_pos = h->row_pos; a.row_out = h->row_out; a.row_prompt = h->row_prompt; }
+    if (slot) { a.row_pos = h->row_pos; a.row_out = h->row_out; a.row_prompt = h->row_prompt; }
     return a;
 }
 
-// From how many rows on the decode GEMMs take the mid-size tiles (DecGemmArgs::mid_rows).  The qkv0 table's gate and the step's regime ask
-// here, so that the table and the launch it replaces agree on the tile kernel.
-static int mid_threshold(ymt3_handle h) { return h->mid_rows > 0 ? h->mid_rows : (h->mid_rows < 0 ? DEC_GEMM_MID_ROWS : 1 << 30); }
+// The two row-count thresholds at which a launcher takes a kernel that sums in another order, so that a step's bits depend on which side
+// of them its R lies.  The qkv0 table's gate, plan_step and decode_run's two-chains rule all ask here.
+// Do R rows take the mid-size tile decode GEMMs?  launch_dec_gemm's rule over DecGemmArgs::mid_rows, which every GEMM of a step gets from
+// the handle (YMT3_DEC_GEMM_MID_ROWS at create; < 0: DEC_GEMM_MID_ROWS, 0: never); they accumulate K in one chain, not in eight slices.
+static bool gemm_mid_tiles(ymt3_handle h, int R) { return h->mid_rows != 0 && R >= (h->mid_rows > 0 ? h->mid_rows : DEC_GEMM_MID_ROWS); }
+// Do R rows take the 2-waves-per-(row, head) attention?  launch_dec_attention's `many`: beyond 2048 (row, head) workgroups, or forced by
+// DecAttnArgs::force_many.  (That launcher holds the figure as a literal; it is repeated here and nowhere else in this file.)
+static bool attn_many_rows(ymt3_handle h, int R) { return h->force_2wave || R * h->cfg.n_heads > 2048; }
 
 // Does a decode call whose largest step has `rows` rows take layer 0's q / k / v from the table?  Only where the launch it replaces is the
 // 16-row-tile kernel, whose bits the table holds (the mid-size tiles accumulate K differently); never a beam call (its selection kernels
 // do not gather) and never the profiled call (ymt3_profile_decode keeps the launch sequence its classes are defined by).
-static void qkv0_decide(ymt3_handle h, int rows, bool beam, bool profiled) {
-    h->qkv0_call = h->qkv0_table && !beam && !profiled && h->cfg.n_channels == 1 && rows < mid_threshold(h);
+static bool qkv0_applies(ymt3_handle h, int rows, bool beam, bool profiled) {
+    return h->qkv0_table && !beam && !profiled && h->cfg.n_channels == 1 && !gemm_mid_tiles(h, rows);
 }
 // the feeding kernels' side of it: where the fed id's table row goes
-static void qkv0_wire(ymt3_handle h, ArgmaxArgs* a) {
-    if (!h->qkv0_call) return;
+static void qkv0_wire(ymt3_handle h, bool qkv0, ArgmaxArgs* a) {
+    if (!qkv0) return;
     a->qkv0 = h->qkv0_table; a->q0 = h->dq; a->kcache0 = h->kcache; a->vcache0 = h->vcache; a->H = h->cfg.n_heads; a->L = h->cfg.max_decode_len;
 }
 
-// Which kernels a step of rows [row0, row0 + R) takes.  Every choice gives the same bits; they differ in launches and time.
+// The shape of a call's steps: `R` rows in all, cut into n_chains contiguous, near-equal row ranges (chain_shape picks one).
+static StepShape step_shape(ymt3_handle h, StepMode mode, int B, int W, int R, int n_chains, bool profiled) {
+    StepShape S;
+    S.mode = mode; S.B = B; S.W = W; S.n_chains = n_chains; S.R = R; S.solo = n_chains == 1; S.profiled = profiled;
+    S.qkv0 = qkv0_applies(h, (R + n_chains - 1) / n_chains, W > 0, profiled);      // (the largest chain's rows)
+    return S;
+}
+static StepShape chain_shape(StepShape S, int c) {
+    const int R = S.R, n = S.n_chains;
+    S.chain = c;
+    S.row0 = c * (R / n) + std::min(c, R % n);
+    S.R = R / n + (c < R % n ? 1 : 0);
+    return S;
+}
+
+// Which kernels a step takes: a pure function of the handle's create-time configuration and the step's shape.  mid_tiles and attn_many
+// name kernels that sum in another order (bits_agree); every other choice gives the same bits and differs in launches and time.
 struct StepPlan {
     int rows_kv;            // decoder rows per segment's cross-attention K/V: n_channels, times W in a beam call
+    bool mid_tiles, attn_many;
     bool fold_combine, mc, fold, merged_regime, chain, pair_ok, moe_chain, stepk;
+    bool merged() const { return chain || pair_ok || moe_chain; }      // the step holds merged kernels: their abort word must be looked at
 };
-static StepPlan plan_step(ymt3_handle h, int row0, int R, bool solo) {
+static bool bits_agree(const StepPlan& a, const StepPlan& b) { return a.mid_tiles == b.mid_tiles && a.attn_many == b.attn_many; }
+static StepPlan plan_step(ymt3_handle h, const StepShape& S) {
     const ymt3_config& k = h->cfg;
-    const int d = k.d_model, inner = h->inner, H = k.n_heads, bW = h->beam_W;
+    const int d = k.d_model, inner = h->inner, H = k.n_heads, bW = S.W, row0 = S.row0, R = S.R;
+    const bool solo = S.solo;
     StepPlan p{};
+    p.mid_tiles = gemm_mid_tiles(h, R);
+    p.attn_many = attn_many_rows(h, R);
     // MoE with the combine folded away: after an MoE FFN the residual stream is hcur + (y[2r] + y[2r+1]) until the next norm GEMM
     // (the next layer's QKV projection, or lm_head) has formed it; that QKV kernel stores it to the other buffer, which the rest of
     // its layer then uses.  Needs the 16-row decode GEMMs (below the mid-size tile threshold).
-    p.fold_combine = k.dec_ffn == YMT3_FFN_MOE && h->moe_fold_combine && R < mid_threshold(h);
+    p.fold_combine = k.dec_ffn == YMT3_FFN_MOE && h->moe_fold_combine && !p.mid_tiles;
     // all channels of a segment share its cross-attention K/V: one workgroup per (segment, head) serves them together (mc_cross_attn.hip)
     // (a beam call: the W beams of a group share their segment's K/V exactly as channels do -- rows_kv = n_channels * W rows per segment)
     p.rows_kv = k.n_channels * (bW > 0 ? bW : 1);
@@ -959,216 +996,318 @@ static NextStage next_stage(ymt3_handle h, int l) {
     return {false, N.wqkv, N.ln1, DG_NORM_QKV_CACHE, 3 * h->inner, h->kcache + next_cache, h->vcache + next_cache};
 }
 
-// one decoder step of rows [row0, row0 + R) = 8 kernels per layer + lm_head + argmax, all reading the
-// position from the chain's DecodeShared
-static int launch_step(ymt3_handle h, int B, int row0, int R, DecodeShared* shared, hipStream_t s, bool solo = true) {
-    const ymt3_config& k = h->cfg;
-    const int d = k.d_model, inner = h->inner, H = k.n_heads, L = k.max_decode_len;
-    const size_t layer_cache = (size_t)h->maxR * H * L * 64;
-    const size_t slab = (size_t)B * H * h->T * 64;
-    const DecWeights& D = h->dec;
-    h->stamp_n = 0;
-    const int mtiles = (R + 15) / 16;
-    const StepPlan P = plan_step(h, row0, R, solo);
-    const bool fold = P.fold, mc = P.mc, chain = P.chain, moe_chain = P.moe_chain;
-    const int bW = h->beam_W;
-    float* hcur = h->h_dec;
-    const float* pend = nullptr;
-    h->step_merged = chain || P.pair_ok || moe_chain;
-    bool qkv_done = false, lm_done = false;         // the previous layer's chain launch already did this layer's QKV / the lm_head
-    for (int l = 0; l < k.n_dec_layers; ++l) {
-        const LayerW& W = D.layer[(size_t)l];
+// ---------------------------------------------------------------- one decoder step
+// What one stage of a step hands to the next.
+struct StepCarry {
+    float* hcur;            // the residual buffer in use.  Set: h_dec at the step's start; moved to the other buffer by whoever forms h + (y0 + y1) there -- the QKV
+                            // projection with a pending combine (layer_projection), the MoE chain's next-QKV stage (layer_tail).  Read: every launch on the stream
+    const float* pend;      // MoE with the combine folded away: expert outputs still to be added.  Set: layer_tail's separate stages.  Consumed: the next
+                            // layer_projection, or the lm_head
+    bool qkv_done;          // the next layer's QKV projection is done.  Set: layer_tail's merged launch.  Consumed: the next layer_projection
+    bool lm_done;           // so is the lm_head.  Set: the last layer's merged launch.  Consumed: Step::run
+};
+// One step being launched: its shape, the plan that follows from it, the chain's loop state (every kernel reads the position from it, or
+// from row_pos in a slot mode) and the stream; then one argument builder per kind of launch, and the stages that launch them.
+// A builder returns a freshly value-initialised struct holding the fields its launcher and kernel read (the kernels take the struct by
+// value; what a launch does not read stays zero).  No struct is changed after a launch has used it, none serves two launches.
+struct Step {
+    ymt3_handle h;
+    StepShape S;
+    StepPlan P;
+    DecodeShared* shared;
+    hipStream_t s;
+    const ymt3_config& k() const { return h->cfg; }
+    const LayerW& W(int l) const { return h->dec.layer[(size_t)l]; }
+    const int* row_pos() const { return S.slot() ? h->row_pos : nullptr; }
+    size_t layer_cache(int l) const { return (size_t)l * h->maxR * k().n_heads * k().max_decode_len * 64; }       // layer l's self-attention K (or V)
+    bf16_t* cross_kv(int l, int v) const { return h->ckv + (size_t)(2 * l + v) * S.B * k().n_heads * h->T * 64; }  // layer l's cross-attention K (v = 1: V) slabs
+    float* other(const float* hcur) const { return hcur == h->h_dec ? h->h_dec2 : h->h_dec; }                      // MoE: the residual buffer not in use
+
+    // the decode GEMMs: every one reads its rows, the sum(h^2) partials (norm prologue: read; DG_RESID: written), the tile threshold, its stamp slot
+    DecGemmArgs gemm_base(int cls, const bf16_t* Wt, int N, int K) const {
         DecGemmArgs a{};
-        a.row0 = row0; a.R = R; a.eps = k.ln_eps; a.H = H; a.L = L; a.shared = shared; a.ssq = h->ssq; a.ssq_stride = h->maxR;
-        a.row_pos = h->slot_mode ? h->row_pos : nullptr;
-        a.mid_rows = h->mid_rows;
-        // self-attention block
-        a.x_f32 = hcur; a.gain = W.ln1; a.W = W.wqkv; a.N = 3 * inner; a.K = d; a.out_bf16 = h->dq;
-        if (pend) {                                  // the previous layer's expert outputs are still to be added: x -> the other buffer
-            a.pend_y = pend;
-            a.h_out = hcur == h->h_dec ? h->h_dec2 : h->h_dec;
-        }
-        a.kcache = h->kcache + l * layer_cache; a.vcache = h->vcache + l * layer_cache;
-        // (layer 0 under the table: the kernel that fed the rows has written q and this position's k / v already; no combine is ever pending here)
-        if (!qkv_done && !(l == 0 && h->qkv0_call && !pend)) {
-            a.stamp = next_stamp(h, PC_QKV, a.N / 16 * mtiles);
-            PLAUNCH(PC_QKV, launch_dec_gemm(DG_NORM_QKV_CACHE, a, s));
-        }
-        qkv_done = false;
-        if (pend) { hcur = a.h_out; pend = nullptr; a.pend_y = nullptr; a.h_out = nullptr; }
-        if (P.stepk) {
-            StepArgs sa{};
-            sa.n_layers = k.n_dec_layers; sa.R = R; sa.T = h->T; sa.L = L; sa.ssq_stride = h->maxR; sa.eps = k.ln_eps;
-            sa.tiles_free = h->step_tiles_free ? 1 : 0;
-            sa.q = h->dq; sa.attn = h->dattn; sa.opart = h->opart; sa.h = hcur; sa.ssq = h->ssq; sa.dff = h->dff; sa.logits = h->logits;
-            sa.bias = D.bias_dist; sa.shared = shared; sa.row_pos = a.row_pos;
-            sa.sync = h->step_sync; sa.pair_rows = h->pair_rows; sa.abort_word = h->chain_sync + CHAIN_ABORT_WORD; sa.host_abort = h->chain_host_abort;
-            for (int j = 0; j < k.n_dec_layers; ++j) {
-                const LayerW& J = D.layer[(size_t)j];
-                const NextStage ns = next_stage(h, j);
-                StepLayer& SL = sa.layer[j];
-                SL.wo = J.wo; SL.wq_c = J.wq_c; SL.wo_c = J.wo_c; SL.wi = J.wi; SL.wo2 = J.wo2; SL.w3 = ns.w3;
-                SL.ln2 = J.ln2; SL.ln3 = J.ln3; SL.gain3 = ns.gain3;
-                SL.kself = h->kcache + (size_t)j * layer_cache; SL.vself = h->vcache + (size_t)j * layer_cache;
-                SL.kcross = h->ckv + (size_t)(2 * j) * slab; SL.vcross = h->ckv + (size_t)(2 * j + 1) * slab;
-                SL.knext = ns.kcache; SL.vnext = ns.vcache;
-                SL.N3 = ns.N3; SL.last = ns.last ? 1 : 0;
-            }
-            sa.stamp = next_stamp(h, PC_STEP, ((R + 15) / 16) * 128);
-            PLAUNCH(PC_STEP, launch_dec_step(sa, s));
-            lm_done = true;
-            break;
-        }
+        a.row0 = S.row0; a.R = S.R; a.W = Wt; a.N = N; a.K = K; a.ssq = h->ssq; a.ssq_stride = h->maxR; a.mid_rows = h->mid_rows;
+        a.stamp = next_stamp(h, cls, a.N / 16 * ((S.R + 15) / 16));
+        return a;
+    }
+    // out = norm(x) * gain . W^T: cross Q-projection, FFN-in; the base of the QKV projection and the lm_head
+    DecGemmArgs gemm_norm(int cls, const float* x, const float* gain, const bf16_t* Wt, int N, bf16_t* out) const {
+        DecGemmArgs a = gemm_base(cls, Wt, N, k().d_model);
+        a.x_f32 = x; a.gain = gain; a.eps = k().ln_eps; a.out_bf16 = out;
+        return a;
+    }
+    // hcur += in . W^T: self and cross O-projection, FFN-out; part: the folded self-attention O-projection's partials, added first (cross O only)
+    DecGemmArgs gemm_resid(int cls, const bf16_t* in, const bf16_t* Wt, int K, float* hcur, const float* part = nullptr) const {
+        DecGemmArgs a = gemm_base(cls, Wt, k().d_model, K);
+        a.a_bf16 = in; a.out_f32 = hcur; a.part = part;
+        return a;
+    }
+    // layer l's QKV projection: q to dq, this position's k / v into the layer's cache slabs; a pending combine is formed in the prologue
+    // and the completed residual row stored to the other buffer
+    DecGemmArgs qkv_args(int l, const StepCarry& y) const {
+        DecGemmArgs a = gemm_norm(PC_QKV, y.hcur, W(l).ln1, W(l).wqkv, 3 * h->inner, h->dq);
+        a.kcache = h->kcache + layer_cache(l); a.vcache = h->vcache + layer_cache(l); a.H = k().n_heads; a.L = k().max_decode_len;
+        a.shared = shared; a.row_pos = row_pos();
+        if (y.pend) { a.pend_y = y.pend; a.h_out = other(y.hcur); }
+        return a;
+    }
+    DecGemmArgs lm_head_args(const StepCarry& y) const {
+        DecGemmArgs a = gemm_norm(PC_LM_HEAD, y.hcur, h->dec.ln_f, h->dec.lm_head, k().vocab, nullptr);
+        a.out_f32 = h->logits;
+        a.pend_y = y.pend;                               // the last layer's expert outputs, if their combine was folded away
+        return a;
+    }
+    // the self-attention half of layer l: its cache slabs up to the row's position; with the fold it ends in the head's O-projection partial
+    DecAttnArgs self_attn_args(int l) const {
+        const int L = k().max_decode_len;
         DecAttnArgs t{};
-        t.q = h->dq; t.k = a.kcache; t.v = a.vcache; t.out = h->dattn; t.bias = D.bias_dist; t.shared = shared; t.row0 = row0;
-        t.n_keys_const = 0; t.slab_keys = L; t.rows_per_kv = 1; t.R = R; t.H = H; t.bias_stride = L;
-        t.row_pos = a.row_pos; t.force_many = h->force_2wave ? 1 : 0;
-        if (fold) { t.wo = W.wo; t.opart = h->opart; }
-        const bool pair = P.pair_ok && fold;
-        DecAttnArgs ts = t;                          // the self-attention half
-        if (bW > 0) {
-            const BeamAttn ba{h->beam.anc, h->beam.anc_rows, h->beam.anc_pitch, bW};
-            t.stamp = next_stamp(h, PC_SELF_ATTN, R * H);
-            PLAUNCH(PC_SELF_ATTN, launch_dec_attention_beam(t, ba, s));
-        } else if (!pair) {
-            t.stamp = next_stamp(h, PC_SELF_ATTN, R * H);
-            PLAUNCH(PC_SELF_ATTN, launch_dec_attention(true, t, s));
-        }
-        t.wo = nullptr; t.opart = nullptr;
-        a.a_bf16 = h->dattn; a.W = W.wo; a.N = d; a.K = inner; a.out_f32 = hcur;
-        if (!fold) {
-            a.stamp = next_stamp(h, PC_SELF_O, a.N / 16 * mtiles);
-            PLAUNCH(PC_SELF_O, launch_dec_gemm(DG_RESID, a, s));
-        }
-        // cross-attention block: the query projection is fused into the attention kernel (YMT3_NO_FUSEQ=1 keeps
-        // the separate skinny GEMM, for A/B measurements)
-        t.k = h->ckv + (size_t)(2 * l) * slab; t.v = h->ckv + (size_t)(2 * l + 1) * slab; t.bias = nullptr;
-        t.n_keys_const = h->T; t.slab_keys = h->T; t.rows_per_kv = P.rows_kv;
-        if (fold) t.ipart = h->opart;
-        if (mc) {
-            // all channels of a segment share its K/V: one workgroup per (segment, head) serves them together
-            McCrossArgs mcx{};
-            mcx.x_f32 = hcur; mcx.gain = W.ln2; mcx.ssq = h->ssq; mcx.ssq_stride = h->maxR; mcx.eps = k.ln_eps;
-            mcx.wq = W.wq_c; mcx.k = t.k + (size_t)(row0 / P.rows_kv) * H * h->T * 64; mcx.v = t.v + (size_t)(row0 / P.rows_kv) * H * h->T * 64;
-            mcx.out = h->dattn; mcx.row0 = row0; mcx.n_seg = R / P.rows_kv; mcx.n_channels = P.rows_kv; mcx.H = H; mcx.T = h->T;
-            PLAUNCH(PC_CROSS_ATTN, launch_mc_cross_attention(mcx, s));
-        } else if (h->fuse_q) {
-            t.wq = W.wq_c; t.x_f32 = hcur; t.gain = W.ln2; t.ssq = h->ssq; t.ssq_stride = h->maxR; t.eps = k.ln_eps;
-        } else {
-            a.gain = W.ln2; a.W = W.wq_c; a.N = inner; a.K = d; a.out_bf16 = h->dq;
-            a.stamp = next_stamp(h, PC_CROSS_Q, a.N / 16 * mtiles);
-            PLAUNCH(PC_CROSS_Q, launch_dec_gemm(DG_NORM_BF16, a, s));
-        }
-        if (pair) {
-            if (chain || moe_chain) t.chain_sync = h->chain_sync;
-            ts.stamp = t.stamp = next_stamp(h, PC_ATTN_PAIR, R * H);
-            PLAUNCH(PC_ATTN_PAIR, launch_dec_attention_pair(ts, t, h->pair_rows, h->chain_sync + CHAIN_ABORT_WORD, h->chain_host_abort, s));
-        } else if (!mc) {
-            if (chain) t.chain_sync = h->chain_sync;
-            t.stamp = next_stamp(h, PC_CROSS_ATTN, R * H);
-            PLAUNCH(PC_CROSS_ATTN, launch_dec_attention(false, t, s));
-        }
-        if (chain) {
-            const NextStage ns = next_stage(h, l);
-            ChainArgs cg{};
-            cg.w0 = W.wo_c; cg.w1 = W.wi; cg.w2 = W.wo2; cg.w3 = ns.w3;
-            cg.attn = h->dattn; cg.part = h->opart; cg.h = hcur; cg.ssq = h->ssq; cg.ssq_stride = h->maxR;
-            cg.gain1 = W.ln3; cg.gain3 = ns.gain3;
-            cg.dff = h->dff; cg.d_ff = k.d_ff;
-            cg.mode3 = ns.mode3; cg.N3 = ns.N3;
-            cg.out_q = h->dq; cg.kcache = ns.kcache; cg.vcache = ns.vcache;
-            cg.logits = h->logits; cg.H = H; cg.L = L; cg.shared = shared; cg.row_pos = a.row_pos; cg.row0 = row0; cg.R = R; cg.eps = k.ln_eps;
-            cg.sync = h->chain_sync; cg.host_abort = h->chain_host_abort;
-            { static const int nsub_env = [] { const char* e = getenv("YMT3_CHAIN_NSUB"); return e ? (int)strtol(e, nullptr, 16) : 0; }(); cg.nsub = nsub_env; }
-            cg.stamp = next_stamp(h, PC_CHAIN, 256);
-            PLAUNCH(PC_CHAIN, launch_dec_chain(cg, s));
-            if (ns.last) lm_done = true; else qkv_done = true;
-            continue;
-        }
-        if (moe_chain) {
-            const NextStage ns = next_stage(h, l);
-            MoeChainArgs mc2{};
-            mc2.wo_c = W.wo_c; mc2.w3 = ns.w3;
-            if (k.moe_fp8) { mc2.wi = W.wi_q8; mc2.wo = W.wo_q8; mc2.wi_s = W.wi_s; mc2.wo_s = W.wo_s; }
-            else { mc2.wi = W.wi; mc2.wo = W.wo2; }
-            mc2.attn = h->dattn; mc2.h = hcur; mc2.part = h->opart; mc2.ssq = h->ssq; mc2.ssq_stride = h->maxR;
-            mc2.gain_r = W.ln3; mc2.router = W.router; mc2.xn = h->moe.xn; mc2.sel = h->moe.sel; mc2.gate = h->moe.gate; mc2.hidden = h->moe.hidden; mc2.y = h->moe.y;
-            mc2.gain3 = ns.gain3; mc2.mode3 = ns.mode3; mc2.N3 = ns.N3;
-            mc2.h_out = ns.last ? nullptr : (hcur == h->h_dec ? h->h_dec2 : h->h_dec);
-            mc2.out_q = h->dq; mc2.kcache = ns.kcache; mc2.vcache = ns.vcache;
-            mc2.logits = h->logits; mc2.H = H; mc2.L = L; mc2.shared = shared; mc2.row_pos = a.row_pos;
-            mc2.R = R; mc2.E = k.n_experts; mc2.fp8 = k.moe_fp8; mc2.eps = k.ln_eps;
-            mc2.sync = h->chain_sync; mc2.host_abort = h->chain_host_abort;
-            mc2.sel_trace = h->slot_mode ? nullptr : h->moe_trace; mc2.layer = l; mc2.n_layers = k.n_dec_layers;
-            mc2.trace_rows = h->moe_trace_rows; mc2.trace_steps = h->moe_trace_steps;
-            mc2.stamp = next_stamp(h, PC_CHAIN, 256);
-            PLAUNCH(PC_CHAIN, launch_moe_chain(mc2, s));
-            if (ns.last) lm_done = true;
-            else { qkv_done = true; hcur = mc2.h_out; }
-            continue;
-        }
-        a.a_bf16 = h->dattn; a.W = W.wo_c; a.N = d; a.K = inner;
-        a.part = fold ? h->opart : nullptr;
-        a.stamp = next_stamp(h, PC_CROSS_O, a.N / 16 * mtiles);
-        PLAUNCH(PC_CROSS_O, launch_dec_gemm(DG_RESID, a, s));
-        a.part = nullptr;
-        // feed-forward block
-        if (k.dec_ffn == YMT3_FFN_MOE) {
-            MoeArgs mo = h->moe;
-            mo.h = hcur; mo.gain = W.ln3; mo.ssq = h->ssq; mo.ssq_stride = h->maxR;
-            mo.router = W.router; mo.wi = W.wi; mo.wo = W.wo2; mo.row0 = row0; mo.R = R;
-            mo.wi_q8 = W.wi_q8; mo.wo_q8 = W.wo_q8; mo.wi_s = W.wi_s; mo.wo_s = W.wo_s; mo.fp8 = k.moe_fp8;
-            mo.sel_trace = h->slot_mode ? nullptr : h->moe_trace; mo.shared = shared; mo.layer = l; mo.n_layers = k.n_dec_layers;
-            mo.trace_rows = h->moe_trace_rows; mo.trace_steps = h->moe_trace_steps;
-            { ProfScope _ps(h, PC_FFN_WI, s); LAUNCH(launch_moe_stage(0, mo, s)); LAUNCH(launch_moe_stage(1, mo, s)); }
-            { ProfScope _ps(h, PC_FFN_WO, s); LAUNCH(launch_moe_stage(2, mo, s)); if (!P.fold_combine) LAUNCH(launch_moe_stage(3, mo, s)); }
-            if (P.fold_combine) pend = mo.y;
-        } else {
-            a.gain = W.ln3; a.W = W.wi; a.N = k.d_ff; a.K = d; a.out_bf16 = h->dff;
-            a.stamp = next_stamp(h, PC_FFN_WI, a.N / 16 * mtiles);
-            PLAUNCH(PC_FFN_WI, launch_dec_gemm(DG_NORM_BF16_RELU, a, s));
-            a.a_bf16 = h->dff; a.W = W.wo2; a.N = d; a.K = k.d_ff;
-            a.stamp = next_stamp(h, PC_FFN_WO, a.N / 16 * mtiles);
-            PLAUNCH(PC_FFN_WO, launch_dec_gemm(DG_RESID, a, s));
-        }
+        t.q = h->dq; t.k = h->kcache + layer_cache(l); t.v = h->vcache + layer_cache(l); t.out = h->dattn; t.bias = h->dec.bias_dist;
+        t.shared = shared; t.row_pos = row_pos(); t.row0 = S.row0; t.R = S.R; t.H = k().n_heads;
+        t.slab_keys = L; t.bias_stride = L; t.rows_per_kv = 1; t.force_many = h->force_2wave ? 1 : 0;
+        if (P.fold) { t.wo = W(l).wo; t.opart = h->opart; }
+        return t;
     }
-    DecGemmArgs a{};
-    a.row0 = row0; a.R = R; a.eps = k.ln_eps; a.H = H; a.L = L; a.shared = shared; a.ssq = h->ssq; a.ssq_stride = h->maxR;
-    a.mid_rows = h->mid_rows;
-    a.x_f32 = hcur; a.gain = D.ln_f; a.W = D.lm_head; a.N = k.vocab; a.K = d; a.out_f32 = h->logits;
-    a.pend_y = pend;                                 // the last layer's expert outputs, if their combine was folded away
-    if (!lm_done) {
-        a.stamp = next_stamp(h, PC_LM_HEAD, a.N / 16 * mtiles);
-        PLAUNCH(PC_LM_HEAD, launch_dec_gemm(DG_NORM_LOGITS, a, s));
+    // the cross-attention half of layer l, per row: the segment's T keys.  Fused query projection (default): the kernel norms the residual
+    // row itself -- with the fold, h + the self-attention's partials.  Else q comes from the separate projection's dq.
+    DecAttnArgs cross_attn_args(int l, const float* hcur) const {
+        DecAttnArgs t{};
+        t.k = cross_kv(l, 0); t.v = cross_kv(l, 1); t.out = h->dattn;
+        t.n_keys_const = h->T; t.slab_keys = h->T; t.rows_per_kv = P.rows_kv; t.row0 = S.row0; t.R = S.R; t.H = k().n_heads;
+        t.force_many = h->force_2wave ? 1 : 0;           // (the launcher's choice of the unfused kernel; it refuses the fold with it)
+        if (h->fuse_q) {
+            t.wq = W(l).wq_c; t.x_f32 = hcur; t.gain = W(l).ln2; t.ssq = h->ssq; t.ssq_stride = h->maxR; t.eps = k().ln_eps;
+            if (P.fold) t.ipart = h->opart;
+        } else t.q = h->dq;
+        if (P.chain || P.moe_chain) t.chain_sync = h->chain_sync;      // it zeroes the arrival counters of the merged tail launched next
+        return t;
     }
-    if (bW > 0) {
-        BeamArgs b = beam_args(h, R, bW, shared);
-        b.stamp = next_stamp(h, PC_ARGMAX, R / bW);
-        PLAUNCH(PC_ARGMAX, launch_beam_select(b, s));
+    // all channels (beams) of a segment share its cross-attention K/V: one workgroup per (segment, head) serves them together, query projection fused
+    McCrossArgs mc_cross_args(int l, const float* hcur) const {
+        const size_t seg0 = (size_t)(S.row0 / P.rows_kv) * k().n_heads * h->T * 64;
+        McCrossArgs mcx{};
+        mcx.x_f32 = hcur; mcx.gain = W(l).ln2; mcx.ssq = h->ssq; mcx.ssq_stride = h->maxR; mcx.eps = k().ln_eps;
+        mcx.wq = W(l).wq_c; mcx.k = cross_kv(l, 0) + seg0; mcx.v = cross_kv(l, 1) + seg0;
+        mcx.out = h->dattn; mcx.row0 = S.row0; mcx.n_seg = S.R / P.rows_kv; mcx.n_channels = P.rows_kv; mcx.H = k().n_heads; mcx.T = h->T;
+        return mcx;
+    }
+    // GEMM chain (dec_chain.hip): layer l's cross O-projection, FFN-in, FFN-out and `ns` as one launch
+    ChainArgs chain_args(int l, float* hcur, const NextStage& ns) const {
+        ChainArgs cg{};
+        cg.w0 = W(l).wo_c; cg.w1 = W(l).wi; cg.w2 = W(l).wo2; cg.w3 = ns.w3;
+        cg.attn = h->dattn; cg.part = h->opart; cg.h = hcur; cg.ssq = h->ssq; cg.ssq_stride = h->maxR;
+        cg.gain1 = W(l).ln3; cg.gain3 = ns.gain3;
+        cg.dff = h->dff; cg.d_ff = k().d_ff;
+        cg.mode3 = ns.mode3; cg.N3 = ns.N3;
+        cg.out_q = h->dq; cg.kcache = ns.kcache; cg.vcache = ns.vcache;
+        cg.logits = h->logits; cg.H = k().n_heads; cg.L = k().max_decode_len; cg.shared = shared; cg.row_pos = row_pos();
+        cg.row0 = S.row0; cg.R = S.R; cg.eps = k().ln_eps;
+        cg.sync = h->chain_sync; cg.host_abort = h->chain_host_abort;
+        { static const int nsub_env = [] { const char* e = getenv("YMT3_CHAIN_NSUB"); return e ? (int)strtol(e, nullptr, 16) : 0; }(); cg.nsub = nsub_env; }
+        cg.stamp = next_stamp(h, PC_CHAIN, 256);
+        return cg;
+    }
+    // MoE chain (moe_chain.hip): cross O-projection -> router -> expert FFN-in -> expert FFN-out -> `ns`, which also forms the combine
+    MoeChainArgs moe_chain_args(int l, float* hcur, const NextStage& ns) const {
+        MoeChainArgs mc2{};
+        mc2.wo_c = W(l).wo_c; mc2.w3 = ns.w3;
+        if (k().moe_fp8) { mc2.wi = W(l).wi_q8; mc2.wo = W(l).wo_q8; mc2.wi_s = W(l).wi_s; mc2.wo_s = W(l).wo_s; }
+        else { mc2.wi = W(l).wi; mc2.wo = W(l).wo2; }
+        mc2.attn = h->dattn; mc2.h = hcur; mc2.part = h->opart; mc2.ssq = h->ssq; mc2.ssq_stride = h->maxR;
+        mc2.gain_r = W(l).ln3; mc2.router = W(l).router; mc2.xn = h->moe.xn; mc2.sel = h->moe.sel; mc2.gate = h->moe.gate; mc2.hidden = h->moe.hidden; mc2.y = h->moe.y;
+        mc2.gain3 = ns.gain3; mc2.mode3 = ns.mode3; mc2.N3 = ns.N3;
+        mc2.h_out = ns.last ? nullptr : other(hcur);
+        mc2.out_q = h->dq; mc2.kcache = ns.kcache; mc2.vcache = ns.vcache;
+        mc2.logits = h->logits; mc2.H = k().n_heads; mc2.L = k().max_decode_len; mc2.shared = shared; mc2.row_pos = row_pos();
+        mc2.R = S.R; mc2.E = k().n_experts; mc2.fp8 = k().moe_fp8; mc2.eps = k().ln_eps;
+        mc2.sync = h->chain_sync; mc2.host_abort = h->chain_host_abort;
+        mc2.sel_trace = S.slot() ? nullptr : h->moe_trace; mc2.layer = l; mc2.n_layers = k().n_dec_layers;      // (no trace in a slot mode: its rows are at their own steps)
+        mc2.trace_rows = h->moe_trace_rows; mc2.trace_steps = h->moe_trace_steps;
+        mc2.stamp = next_stamp(h, PC_CHAIN, 256);
+        return mc2;
+    }
+    // the MoE FFN of layer l as separate stages: router, expert FFN-in, expert FFN-out, combine
+    MoeArgs moe_stage_args(int l, float* hcur) const {
+        MoeArgs mo = h->moe;
+        mo.h = hcur; mo.gain = W(l).ln3; mo.ssq = h->ssq; mo.ssq_stride = h->maxR;
+        mo.router = W(l).router; mo.wi = W(l).wi; mo.wo = W(l).wo2; mo.row0 = S.row0; mo.R = S.R;
+        mo.wi_q8 = W(l).wi_q8; mo.wo_q8 = W(l).wo_q8; mo.wi_s = W(l).wi_s; mo.wo_s = W(l).wo_s; mo.fp8 = k().moe_fp8;
+        mo.sel_trace = S.slot() ? nullptr : h->moe_trace; mo.shared = shared; mo.layer = l; mo.n_layers = k().n_dec_layers;
+        mo.trace_rows = h->moe_trace_rows; mo.trace_steps = h->moe_trace_steps;
+        return mo;
+    }
+    // the per-step kernel (dec_step.hip): every layer's attention pair and GEMM chain
+    StepArgs step_kernel_args() const {
+        StepArgs sa{};
+        sa.n_layers = k().n_dec_layers; sa.R = S.R; sa.T = h->T; sa.L = k().max_decode_len; sa.ssq_stride = h->maxR; sa.eps = k().ln_eps;
+        sa.tiles_free = h->step_tiles_free ? 1 : 0;
+        sa.q = h->dq; sa.attn = h->dattn; sa.opart = h->opart; sa.h = h->h_dec; sa.ssq = h->ssq; sa.dff = h->dff; sa.logits = h->logits;
+        sa.bias = h->dec.bias_dist; sa.shared = shared; sa.row_pos = row_pos();
+        sa.sync = h->step_sync; sa.pair_rows = h->pair_rows; sa.abort_word = h->chain_sync + CHAIN_ABORT_WORD; sa.host_abort = h->chain_host_abort;
+        for (int j = 0; j < k().n_dec_layers; ++j) {
+            const LayerW& J = W(j);
+            const NextStage ns = next_stage(h, j);
+            StepLayer& SL = sa.layer[j];
+            SL.wo = J.wo; SL.wq_c = J.wq_c; SL.wo_c = J.wo_c; SL.wi = J.wi; SL.wo2 = J.wo2; SL.w3 = ns.w3;
+            SL.ln2 = J.ln2; SL.ln3 = J.ln3; SL.gain3 = ns.gain3;
+            SL.kself = h->kcache + layer_cache(j); SL.vself = h->vcache + layer_cache(j);
+            SL.kcross = cross_kv(j, 0); SL.vcross = cross_kv(j, 1);
+            SL.knext = ns.kcache; SL.vnext = ns.vcache;
+            SL.N3 = ns.N3; SL.last = ns.last ? 1 : 0;
+        }
+        sa.stamp = next_stamp(h, PC_STEP, ((S.R + 15) / 16) * 128);
+        return sa;
+    }
+
+    // The end of every step: the selection kernel picks the rows' next ids from the logits, advances the loop state and embeds the ids
+    // (gathering layer 0's q / k / v where the shape says so).  A beam step: the groups' top-W continuations.
+    int selection() const {
+        if (S.W > 0) {
+            BeamArgs b = beam_args(h, S.R, S.W, shared, S.slot());
+            b.stamp = next_stamp(h, PC_ARGMAX, S.R / S.W);
+            PLAUNCH(PC_ARGMAX, launch_beam_select(b, s));
+            return YMT3_OK;
+        }
+        ArgmaxArgs g = argmax_base(h, S.R, S.slot());
+        g.logits = h->logits; g.shared = shared; g.row0 = S.row0;
+        qkv0_wire(h, S.qkv0, &g);
+        if (S.solo) g.ticket = h->ticket;                // (row ranges of several chains would share groups)
+        if (P.stepk) { g.zero_sync = h->step_sync; g.zero_lines = k().n_dec_layers * STEP_SYNC_LINES_PER_LAYER; }
+        g.stamp = next_stamp(h, PC_ARGMAX, S.R);
+        PLAUNCH(PC_ARGMAX, launch_argmax_embed(g, s));
         return YMT3_OK;
     }
-    ArgmaxArgs g = argmax_base(h, R);
-    g.logits = h->logits; g.shared = shared; g.row0 = row0;
-    qkv0_wire(h, &g);
-    if (solo) g.ticket = h->ticket;                  // (row ranges of several chains would share groups)
-    if (P.stepk) { g.zero_sync = h->step_sync; g.zero_lines = k.n_dec_layers * STEP_SYNC_LINES_PER_LAYER; }
-    g.stamp = next_stamp(h, PC_ARGMAX, R);
-    PLAUNCH(PC_ARGMAX, launch_argmax_embed(g, s));
-    return YMT3_OK;
+    // The step kernel's regime (YMT3_STEP_KERNEL=1): layer 0's QKV projection unless the table provides it, every layer in one launch, selection.
+    int step_kernel_regime() const {
+        if (!S.qkv0) {
+            const DecGemmArgs a = qkv_args(0, StepCarry{h->h_dec, nullptr, false, false});
+            PLAUNCH(PC_QKV, launch_dec_gemm(DG_NORM_QKV_CACHE, a, s));
+        }
+        const StepArgs sa = step_kernel_args();
+        PLAUNCH(PC_STEP, launch_dec_step(sa, s));
+        return selection();
+    }
+    // A layer of the other regimes, part 1: its QKV projection -- unless the previous layer's merged tail did it, or (layer 0, no combine
+    // ever pending there) the kernel that fed the rows has written q and this position's k / v from the table.
+    int layer_projection(int l, StepCarry& y) const {
+        if (!y.qkv_done && !(l == 0 && S.qkv0 && !y.pend)) {
+            const DecGemmArgs a = qkv_args(l, y);
+            PLAUNCH(PC_QKV, launch_dec_gemm(DG_NORM_QKV_CACHE, a, s));
+        }
+        y.qkv_done = false;
+        if (y.pend) { y.hcur = other(y.hcur); y.pend = nullptr; }      // the projection has formed h + (y0 + y1) in the other buffer
+        return YMT3_OK;
+    }
+    // Part 2, attention.  Self: through the ancestry table (beam), inside the pair, or on its own; then its O-projection unless folded.  Cross:
+    // multi-channel, or per row -- after the separate query projection where that is not fused (YMT3_NO_FUSEQ=1) -- as the pair's second half or alone.
+    int layer_attention(int l, const StepCarry& y) const {
+        const int grid = S.R * k().n_heads;
+        if (S.W > 0) {
+            DecAttnArgs t = self_attn_args(l);
+            const BeamAttn ba{h->beam.anc, h->beam.anc_rows, h->beam.anc_pitch, S.W};
+            t.stamp = next_stamp(h, PC_SELF_ATTN, grid);
+            PLAUNCH(PC_SELF_ATTN, launch_dec_attention_beam(t, ba, s));
+        } else if (!P.pair_ok) {
+            DecAttnArgs t = self_attn_args(l);
+            t.stamp = next_stamp(h, PC_SELF_ATTN, grid);
+            PLAUNCH(PC_SELF_ATTN, launch_dec_attention(true, t, s));
+        }
+        if (!P.fold) {
+            const DecGemmArgs a = gemm_resid(PC_SELF_O, h->dattn, W(l).wo, h->inner, y.hcur);
+            PLAUNCH(PC_SELF_O, launch_dec_gemm(DG_RESID, a, s));
+        }
+        if (P.mc) {
+            const McCrossArgs mcx = mc_cross_args(l, y.hcur);
+            PLAUNCH(PC_CROSS_ATTN, launch_mc_cross_attention(mcx, s));
+            return YMT3_OK;
+        }
+        if (!h->fuse_q) {
+            const DecGemmArgs a = gemm_norm(PC_CROSS_Q, y.hcur, W(l).ln2, W(l).wq_c, h->inner, h->dq);
+            PLAUNCH(PC_CROSS_Q, launch_dec_gemm(DG_NORM_BF16, a, s));
+        }
+        DecAttnArgs t = cross_attn_args(l, y.hcur);
+        if (P.pair_ok) {
+            DecAttnArgs ts = self_attn_args(l);          // (the pair's two halves, built side by side: one stamp slot)
+            ts.stamp = t.stamp = next_stamp(h, PC_ATTN_PAIR, grid);
+            PLAUNCH(PC_ATTN_PAIR, launch_dec_attention_pair(ts, t, h->pair_rows, h->chain_sync + CHAIN_ABORT_WORD, h->chain_host_abort, s));
+        } else {
+            t.stamp = next_stamp(h, PC_CROSS_ATTN, grid);
+            PLAUNCH(PC_CROSS_ATTN, launch_dec_attention(false, t, s));
+        }
+        return YMT3_OK;
+    }
+    // Part 3, the tail: cross O-projection, FFN and the next stage (next_stage) as one merged launch -- GEMM chain or MoE chain -- or the cross
+    // O-projection and the FFN as separate launches, which leave the next stage to the next layer_projection / the lm_head.
+    int layer_tail(int l, StepCarry& y) const {
+        if (P.chain || P.moe_chain) {
+            const NextStage ns = next_stage(h, l);
+            if (P.chain) {
+                const ChainArgs cg = chain_args(l, y.hcur, ns);
+                PLAUNCH(PC_CHAIN, launch_dec_chain(cg, s));
+            } else {
+                const MoeChainArgs mc2 = moe_chain_args(l, y.hcur, ns);
+                PLAUNCH(PC_CHAIN, launch_moe_chain(mc2, s));
+                if (!ns.last) y.hcur = mc2.h_out;
+            }
+            (ns.last ? y.lm_done : y.qkv_done) = true;
+            return YMT3_OK;
+        }
+        {
+            const DecGemmArgs a = gemm_resid(PC_CROSS_O, h->dattn, W(l).wo_c, h->inner, y.hcur, P.fold ? h->opart : nullptr);
+            PLAUNCH(PC_CROSS_O, launch_dec_gemm(DG_RESID, a, s));
+        }
+        if (k().dec_ffn == YMT3_FFN_MOE) {
+            const MoeArgs mo = moe_stage_args(l, y.hcur);
+            { ProfScope _ps(h, PC_FFN_WI, s); LAUNCH(launch_moe_stage(0, mo, s)); LAUNCH(launch_moe_stage(1, mo, s)); }
+            { ProfScope _ps(h, PC_FFN_WO, s); LAUNCH(launch_moe_stage(2, mo, s)); if (!P.fold_combine) LAUNCH(launch_moe_stage(3, mo, s)); }
+            if (P.fold_combine) y.pend = mo.y;
+            return YMT3_OK;
+        }
+        {
+            const DecGemmArgs a = gemm_norm(PC_FFN_WI, y.hcur, W(l).ln3, W(l).wi, k().d_ff, h->dff);
+            PLAUNCH(PC_FFN_WI, launch_dec_gemm(DG_NORM_BF16_RELU, a, s));
+        }
+        const DecGemmArgs a = gemm_resid(PC_FFN_WO, h->dff, W(l).wo2, k().d_ff, y.hcur);
+        PLAUNCH(PC_FFN_WO, launch_dec_gemm(DG_RESID, a, s));
+        return YMT3_OK;
+    }
+    // per layer QKV projection, attention, tail; then lm_head and selection
+    int run() const {
+        if (P.stepk) return step_kernel_regime();
+        StepCarry y{h->h_dec, nullptr, false, false};
+        for (int l = 0; l < k().n_dec_layers; ++l) {
+            int rc = layer_projection(l, y);
+            if (!rc) rc = layer_attention(l, y);
+            if (!rc) rc = layer_tail(l, y);
+            if (rc) return rc;
+        }
+        if (!y.lm_done) {
+            const DecGemmArgs a = lm_head_args(y);
+            PLAUNCH(PC_LM_HEAD, launch_dec_gemm(DG_NORM_LOGITS, a, s));
+        }
+        return selection();
+    }
+};
+
+// One decoder step of shape S, every kernel reading the position from the chain's DecodeShared (or row_pos).  *merged is raised when
+// the step holds merged kernels.
+static int launch_step(ymt3_handle h, const StepShape& S, DecodeShared* shared, hipStream_t s, bool* merged = nullptr) {
+    const Step step{h, S, plan_step(h, S), shared, s};
+    h->stamp_n = 0;
+    if (merged && step.P.merged()) *merged = true;
+    return step.run();
 }
 
-// The cached graph of G consecutive steps of rows [row0, row0 + R) under `key`, captured on first use.  A capture that fails leaves
+// The cached graph of G consecutive steps of shape S, filed under step_key(S, G) and captured on first use.  A capture that fails leaves
 // nothing behind: the capture is ended, what it recorded destroyed and the cache left without the entry.  *merged is raised when the
 // graph holds merged kernels.
-static int step_graph(ymt3_handle h, StepKey key, int B, int row0, int R, DecodeShared* shared, bool solo, int G, hipGraphExec_t* out,
-                      bool* merged = nullptr) {
-    key.steps = G;
+static int step_graph(ymt3_handle h, const StepShape& S, DecodeShared* shared, int G, hipGraphExec_t* out, bool* merged = nullptr) {
+    const StepKey key = step_key(S, G);
     auto it = h->step_graphs.find(key);
     if (it == h->step_graphs.end()) {
         StepGraph sg;
         HIP_TRY(hipStreamBeginCapture(h->cap_stream, hipStreamCaptureModeThreadLocal));
         int rc = 0;
-        for (int i = 0; i < G && !rc; ++i) rc = launch_step(h, B, row0, R, shared, h->cap_stream, solo);
+        for (int i = 0; i < G && !rc; ++i) rc = launch_step(h, S, shared, h->cap_stream, &sg.merged);
         hipError_t e = hipStreamEndCapture(h->cap_stream, &sg.graph);
         if (!rc && e != hipSuccess) { ymt3_set_error("hipStreamEndCapture: %s", hipGetErrorString(e)); rc = YMT3_ERR_HIP; }
         if (!rc && (e = hipGraphInstantiate(&sg.exec, sg.graph, nullptr, nullptr, 0)) != hipSuccess) {
@@ -1179,11 +1318,27 @@ static int step_graph(ymt3_handle h, StepKey key, int B, int row0, int R, Decode
             if (sg.graph) (void)hipGraphDestroy(sg.graph);
             return rc;
         }
-        sg.merged = h->step_merged;
         it = h->step_graphs.emplace(key, sg).first;
     }
     *out = it->second.exec;
     if (merged && it->second.merged) *merged = true;
+    return YMT3_OK;
+}
+
+// a6: the cross-attention K/V of every decoder layer in one GEMM over `n_seg` encoded segments, stored as per-(segment, head) slabs from
+// segment `first` on in a call whose layers each hold `call_segs` segments.  A lock-step call: (enc, B); a slot admission: (enc, 1, slot, slots).
+static int launch_cross_kv(ymt3_handle h, const bf16_t* enc, int n_seg, int first, int call_segs, hipStream_t s) {
+    const ymt3_config& k = h->cfg;
+    const int d = k.d_model;
+    GemmArgs g{enc, h->wkv_all, h->ckv + (size_t)first * k.n_heads * h->T * 64, nullptr, n_seg * h->T, k.n_dec_layers * 2 * h->inner, d, d, d, 0, h->T, k.n_heads, call_segs};
+    LAUNCH(launch_gemm(EPI_KV_HEADMAJOR, g, s));
+    return YMT3_OK;
+}
+static int launch_cross_kv(ymt3_handle h, const bf16_t* enc, int B, hipStream_t s) { return launch_cross_kv(h, enc, B, 0, B, s); }
+
+// before a greedy call's init kernel: the step kernel's counter lines start at zero (each step's selection kernel zeroes them again)
+static int zero_step_sync(ymt3_handle h, hipStream_t s) {
+    if (h->step_kernel && h->step_sync) HIP_TRY(hipMemsetAsync(h->step_sync, 0, (size_t)STEP_SYNC_LINES * CHAIN_LINE * sizeof(unsigned), s));
     return YMT3_OK;
 }
 
@@ -1256,31 +1411,35 @@ static int decode_run(ymt3_handle h, const bf16_t* enc, int B, int n_steps, cons
     const ymt3_config& k = h->cfg;
     bool merged = false;                      // some step of this call ran merged kernels
     const int n_total = n_prompt + n_steps;   // steps launched
-    const int d = k.d_model, R = B * k.n_channels;
-    // a6: cross-attention K/V of every decoder layer in one GEMM, stored as per-(segment, head) slabs
-    GemmArgs g{enc, h->wkv_all, h->ckv, nullptr, B * h->T, k.n_dec_layers * 2 * h->inner, d, d, d, 0, h->T, k.n_heads, B};
-    LAUNCH(launch_gemm(EPI_KV_HEADMAJOR, g, s));
+    const int R = B * k.n_channels;
+    const bool profiled = prof_stride > 0;
+    int rc = launch_cross_kv(h, enc, B, s);
+    if (rc) return rc;
 
-    ArgmaxArgs a = argmax_base(h, R);
+    ArgmaxArgs a = argmax_base(h, R, false);
     // chains: contiguous, near-equal row ranges
-    int n_chains = (!h->use_graph || prof_stride > 0 || k.dec_ffn == YMT3_FFN_MOE) ? 1 : h->n_chains;   // MoE pair tables are per handle
+    int n_chains = (!h->use_graph || profiled || k.dec_ffn == YMT3_FFN_MOE) ? 1 : h->n_chains;   // MoE pair tables are per handle
     // the early-stop loop (replay_early_stop) runs one chain; with forced tokens the trajectory is fixed, so it is not used
     const bool early = h->early_stop_interval > 0 && k.eos_id >= 0 && !forced;
-    if (h->auto_chains && n_chains == 1 && h->use_graph && prof_stride == 0 && k.dec_ffn != YMT3_FFN_MOE && k.n_channels == 1 && R >= 168 && R <= 256 &&
-        !early)
-        n_chains = 2;
+    if (h->auto_chains && n_chains == 1 && h->use_graph && !profiled && k.dec_ffn != YMT3_FFN_MOE && k.n_channels == 1 && R >= 168 && R <= 256 &&
+        !early) {
+        // (see auto_chains) ... and only where the ids cannot depend on the choice: the whole batch as one chain and both halves take
+        // kernels that sum in the same order
+        const StepShape two = step_shape(h, SM_LOCKSTEP, B, 0, R, 2, false);
+        const StepPlan whole = plan_step(h, step_shape(h, SM_LOCKSTEP, B, 0, R, 1, false));
+        if (bits_agree(whole, plan_step(h, chain_shape(two, 0))) && bits_agree(whole, plan_step(h, chain_shape(two, 1)))) n_chains = 2;
+    }
     if (n_chains > R) n_chains = R;
+    const StepShape S = step_shape(h, SM_LOCKSTEP, B, 0, R, n_chains, profiled);
     h->last_chains = n_chains;
-    qkv0_decide(h, (R + n_chains - 1) / n_chains, false, prof_stride > 0);      // (the largest chain's rows)
-    qkv0_wire(h, &a);
-    if (h->step_kernel && h->step_sync) HIP_TRY(hipMemsetAsync(h->step_sync, 0, (size_t)STEP_SYNC_LINES * CHAIN_LINE * sizeof(unsigned), s));
+    h->last_qkv0 = S.qkv0;
+    qkv0_wire(h, S.qkv0, &a);
+    rc = zero_step_sync(h, s);
+    if (rc) return rc;
     LAUNCH(launch_decode_init(a, n_chains, n_steps, step0, tokens, forced, logits_out, prompt, n_prompt, scores, cv, s));
     h->last_steps = n_total;
-    int row0[9];
-    row0[0] = 0;
-    for (int c = 0; c < n_chains; ++c) row0[c + 1] = row0[c] + R / n_chains + (c < R % n_chains ? 1 : 0);
 
-    if (!h->use_graph || prof_stride > 0) {
+    if (!h->use_graph || profiled) {
         // sampled steps (mid-stride: unbiased mean position) bracket every launch; the stride-1 unsampled steps that
         // follow each of them are bracketed as ONE span, which gives the true step time the per-launch brackets are
         // calibrated against (an event pair adds stream time of its own)
@@ -1298,10 +1457,9 @@ static int decode_run(ymt3_handle h, const bf16_t* enc, int B, int n_steps, cons
                 }
             }
             h->prof_on = sampled;
-            int rc = launch_step(h, B, 0, R, h->shared, s);
+            rc = launch_step(h, S, h->shared, s, &merged);
             h->prof_on = false;
             if (rc) return rc;
-            merged = merged || h->step_merged;
         }
         if (h->prof_span_open) {            // a span the loop never closed: drop it (its end event was never recorded)
             (void)hipEventRecord(h->prof_ev[h->prof_span_idx], s);
@@ -1312,18 +1470,15 @@ static int decode_run(ymt3_handle h, const bf16_t* enc, int B, int n_steps, cons
         // every chain's one-step graph, and its G-step graph where the call has G steps to replay at once
         const int G = h->graph_steps;
         const bool stop_early = early && n_chains == 1;
-        StepKey key;
-        key.B = B; key.n_chains = n_chains;
         hipGraphExec_t one[8], many[8] = {};
         auto chain_graphs = [&](int steps, hipGraphExec_t* out) -> int {
             for (int c = 0; c < n_chains; ++c) {
-                key.chain = c;
-                int rc = step_graph(h, key, B, row0[c], row0[c + 1] - row0[c], h->shared + c, n_chains == 1, steps, &out[c], &merged);
-                if (rc) return rc;
+                int rcg = step_graph(h, chain_shape(S, c), h->shared + c, steps, &out[c], &merged);
+                if (rcg) return rcg;
             }
             return YMT3_OK;
         };
-        int rc = chain_graphs(1, one);
+        rc = chain_graphs(1, one);
         if (!rc && !stop_early && G > 1 && n_total >= G) rc = chain_graphs(G, many);
         if (rc) return rc;
         if (stop_early) {
@@ -1367,7 +1522,7 @@ static int decode_run(ymt3_handle h, const bf16_t* enc, int B, int n_steps, cons
             HIP_TRY(hipStreamSynchronize(s));
             if (h->forced_abort && h->chain_host_abort) *h->chain_host_abort = 1u;      // debug hook: as a kernel would have during the call
             if (h->chain_host_abort && *static_cast<volatile unsigned*>(h->chain_host_abort)) {
-                int rc = merged_fallback(h);
+                rc = merged_fallback(h);
                 if (rc) return rc;
                 return decode_run(h, enc, B, n_steps, prompt, n_prompt, tokens, scores, forced, logits_out, cv, s, prof_stride, step0);
             }
@@ -1467,9 +1622,7 @@ static int score_impl(ymt3_handle h, const bf16_t* enc, int B, int n_steps, cons
                       const int32_t* lengths, float* scores, float* logits_out, hipStream_t s) {
     const ymt3_config& k = h->cfg;
     const int d = k.d_model, inner = h->inner, H = k.n_heads, T = h->T, R = B * k.n_channels, L = n_prompt + n_steps;
-    // a6: cross-attention K/V of every decoder layer in one GEMM, as the decode calls
-    GemmArgs g{enc, h->wkv_all, h->ckv, nullptr, B * T, k.n_dec_layers * 2 * inner, d, d, d, 0, T, H, B};
-    LAUNCH(launch_gemm(EPI_KV_HEADMAJOR, g, s));
+    if (int rc = launch_cross_kv(h, enc, B, s)) return rc;      // as the decode calls
     SeqEmbedArgs e{};
     e.h = h->h_enc; e.prompt = prompt; e.tokens = tokens; e.L = L; e.n_prompt = n_prompt; e.n_steps = n_steps; e.V = k.vocab; e.d = d;
     e.n_channels = k.n_channels; e.pad_id = k.pad_id;
@@ -1560,37 +1713,33 @@ static int beam_check(ymt3_handle h, int B, int n_steps, const int32_t* prompt, 
     return 0;
 }
 
-// One chain, lock-step, the separate launches (launch_step with beam_W set); the step graphs are cached under a mode of their own (SM_BEAM: B, W).
+// One chain, lock-step, the separate launches (a step shape with W set); the step graphs are cached under a mode of their own (SM_BEAM: B, W).
 static int decode_beam_impl(ymt3_handle h, const bf16_t* enc, int B, int n_steps, const int32_t* prompt, int n_prompt, const ymt3_beam_params* p,
                             int32_t* tokens, float* seq_scores, float* token_scores, const ConstraintView& cv, hipStream_t s) {
     const ymt3_config& k = h->cfg;
-    const int W = p->num_beams, d = k.d_model, R = B * k.n_channels * W, n_total = n_prompt + n_steps;
-    GemmArgs g{enc, h->wkv_all, h->ckv, nullptr, B * h->T, k.n_dec_layers * 2 * h->inner, d, d, d, 0, h->T, k.n_heads, B};
-    LAUNCH(launch_gemm(EPI_KV_HEADMAJOR, g, s));
-    const BeamArgs b = beam_args(h, R, W, h->shared);
+    const int W = p->num_beams, R = B * k.n_channels * W, n_total = n_prompt + n_steps;
+    int rc = launch_cross_kv(h, enc, B, s);
+    if (rc) return rc;
+    const StepShape S = step_shape(h, SM_BEAM, B, W, R, 1, false);
+    const BeamArgs b = beam_args(h, R, W, h->shared, false);
     BeamShared params = h->beam_trace;
     params.alpha = p->length_penalty; params.tokens_out = tokens; params.seq_out = seq_scores; params.tok_out = token_scores;
     h->last_chains = 1;
-    qkv0_decide(h, R, true, false);
+    h->last_qkv0 = S.qkv0;
     LAUNCH(launch_beam_init(b, n_steps, prompt, n_prompt, cv, params, s));
     h->last_steps = n_total;
-    struct BeamGuard { ymt3_ctx* c; ~BeamGuard() { c->beam_W = 0; } } guard{h};
-    h->beam_W = W;
-    StepKey key;
-    key.mode = SM_BEAM; key.B = B; key.beams = W;
     const int G = h->graph_steps;
     hipGraphExec_t many = nullptr, one = nullptr;
-    int rc = YMT3_OK;
     if (!h->use_graph) {
-        for (int t = 0; t < n_total && !rc; ++t) rc = launch_step(h, B, 0, R, h->shared, s);
+        for (int t = 0; t < n_total && !rc; ++t) rc = launch_step(h, S, h->shared, s);
     } else if (h->early_stop_interval > 0) {
         int emitted = 0;
-        rc = step_graph(h, key, B, 0, R, h->shared, true, 1, &one);
+        rc = step_graph(h, S, h->shared, 1, &one);
         if (!rc) rc = replay_early_stop(h, one, n_prompt, n_steps, s, &emitted);
     } else {
         // (the one-step graph is captured only by a call with a tail)
-        if (G > 1 && n_total >= G) rc = step_graph(h, key, B, 0, R, h->shared, true, G, &many);
-        if (!rc && (!many || n_total % G)) rc = step_graph(h, key, B, 0, R, h->shared, true, 1, &one);
+        if (G > 1 && n_total >= G) rc = step_graph(h, S, h->shared, G, &many);
+        if (!rc && (!many || n_total % G)) rc = step_graph(h, S, h->shared, 1, &one);
         if (!rc) rc = replay(many, G, one, n_total, s);
     }
     if (rc) return rc;
@@ -1653,14 +1802,15 @@ extern "C" int ymt3_debug_beam_trace(ymt3_handle h, int32_t* trace_dev, float* r
 // kept busy from the queue of segments: a round is `interval` steps of all slots (one replayed graph, cached under `key`), then the host
 // reads the per-row `finished` flags, retires the segments whose rows have all stopped and admits the next pending ones into the freed
 // slots: log-mel + encoder batched over the admissions, cross-K/V written into each slot's slabs, then start(slot, segment).
-// retire(slot) launches whatever leaves the slot's results in the caller's buffers.  The caller has set the handle's mode (slot_mode,
-// beam_W) and launched its init kernel.  watch_abort: the steps may hold merged kernels; restart() runs when one gave up.
+// retire(slot) launches whatever leaves the slot's results in the caller's buffers.  `S`: the shape of the queue's steps (a slot mode, S.B
+// slots, S.R = slots * rows rows); the caller has launched its init kernel.  watch_abort: the steps may hold merged kernels; restart() runs
+// when one gave up.
 template <class Start, class Retire, class Restart>
-static int run_slot_queue(ymt3_handle h, const float* audio_dev, int n_segments, int slots, int rows, int interval, int n_total, const StepKey& key,
+static int run_slot_queue(ymt3_handle h, const float* audio_dev, int n_segments, const StepShape& S, int rows, int interval, int n_total,
                           bool watch_abort, Start start, Retire retire, Restart restart, hipStream_t s) {
     const ymt3_config& k = h->cfg;
-    const int R = slots * rows, d = k.d_model, T = h->T, H = k.n_heads;
-    const size_t S = (size_t)k.segment_samples;
+    const int slots = S.B, R = S.R, d = k.d_model, T = h->T;
+    const size_t seg_samples = (size_t)k.segment_samples;
     int rc;
     hipGraphExec_t exec = nullptr;
     // one replayed graph per round of `interval` steps when that is at most 64 steps (a graph launch costs ~7 us of stream time on
@@ -1673,21 +1823,19 @@ static int run_slot_queue(ymt3_handle h, const float* audio_dev, int n_segments,
     HIP_TRY(hipMemsetAsync(h->row_out, 0, (size_t)R * sizeof(long long), s));
     HIP_TRY(hipMemsetAsync(h->row_prompt, 0, (size_t)R * sizeof(long long), s));
     if (h->use_graph) {
-        rc = step_graph(h, key, slots, 0, R, h->shared, true, per_graph, &exec);
+        rc = step_graph(h, S, h->shared, per_graph, &exec);
         if (rc) return rc;
     }
 
     std::vector<int> slot_seg((size_t)slots, -1), free_slots;
     auto admit = [&](int first_seg, int nb) -> int {
-        LAUNCH(launch_logmel(h->fe, audio_dev + (size_t)first_seg * S, h->mel, nb, s));
+        LAUNCH(launch_logmel(h->fe, audio_dev + (size_t)first_seg * seg_samples, h->mel, nb, s));
         int rce = encode_impl(h, h->mel, nb, h->enc_out, s);
         if (rce) return rce;
         for (int i = 0; i < nb; ++i) {
             const int slot = free_slots[(size_t)i];
-            GemmArgs g{h->enc_out + (size_t)i * T * d, h->wkv_all, h->ckv + (size_t)slot * H * T * 64, nullptr,
-                       T, k.n_dec_layers * 2 * h->inner, d, d, d, 0, T, H, slots};
-            LAUNCH(launch_gemm(EPI_KV_HEADMAJOR, g, s));
-            rce = start(slot, first_seg + i);
+            rce = launch_cross_kv(h, h->enc_out + (size_t)i * T * d, 1, slot, slots, s);
+            if (!rce) rce = start(slot, first_seg + i);
             if (rce) return rce;
             slot_seg[(size_t)slot] = first_seg + i;
         }
@@ -1705,7 +1853,7 @@ static int run_slot_queue(ymt3_handle h, const float* audio_dev, int n_segments,
         if (round > max_rounds) FAIL(YMT3_ERR_HIP, "slot scheduler made no progress (%d live, %d admitted of %d)", live, next, n_segments);
         for (int i = 0; i < interval; i += exec ? per_graph : 1) {
             if (exec) HIP_TRY(hipGraphLaunch(exec, s));
-            else { int rcs = launch_step(h, slots, 0, R, h->shared, s); if (rcs) return rcs; }
+            else { int rcs = launch_step(h, S, h->shared, s); if (rcs) return rcs; }
         }
         HIP_TRY(hipMemcpyAsync(h->host_rows, h->finished, (size_t)R * sizeof(int), hipMemcpyDeviceToHost, s));
         HIP_TRY(hipStreamSynchronize(s));
@@ -1764,18 +1912,16 @@ extern "C" int ymt3_transcribe_stream_constrained(ymt3_handle h, const float* au
     hipStream_t s = (hipStream_t)stream;
     const int K = k.n_channels, R = slots * K;
 
-    struct ModeGuard { ymt3_ctx* c; ~ModeGuard() { c->slot_mode = false; } } guard{h};
-    h->slot_mode = true;
-    ArgmaxArgs a = argmax_base(h, R);        // (slot mode: with the per-row positions and offsets)
-    qkv0_decide(h, R, false, false);
-    qkv0_wire(h, &a);
-    if (h->step_kernel && h->step_sync) HIP_TRY(hipMemsetAsync(h->step_sync, 0, (size_t)STEP_SYNC_LINES * CHAIN_LINE * sizeof(unsigned), s));
+    const StepShape S = step_shape(h, SM_SLOT, slots, 0, R, 1, false);
+    ArgmaxArgs a = argmax_base(h, R, true);  // (slot mode: with the per-row positions and offsets)
+    h->last_qkv0 = S.qkv0;
+    qkv0_wire(h, S.qkv0, &a);
+    rc = zero_step_sync(h, s);
+    if (rc) return rc;
     ConstraintView cv_init = cv;
     cv_init.start = nullptr;                  // (the rows' states are seeded at admission, from their segment's start states)
     LAUNCH(launch_decode_init(a, 1, n_steps, 0, tokens_dev, nullptr, nullptr, prompt_dev, n_prompt, scores_dev, cv_init, s));
 
-    StepKey key;
-    key.mode = SM_SLOT; key.B = slots;
     auto start = [&](int slot, int seg) -> int {
         ConstraintView cv_seg = cv;
         if (cv.start) cv_seg.start = cv.start + (size_t)seg * K;
@@ -1794,7 +1940,7 @@ extern "C" int ymt3_transcribe_stream_constrained(ymt3_handle h, const float* au
         return ymt3_transcribe_stream_constrained(h, audio_dev, n_segments, n_steps, prompt_dev, n_prompt, tokens_dev, scores_dev, slots, interval,
                                                   constraint, start_state_dev, stream);
     };
-    return run_slot_queue(h, audio_dev, n_segments, slots, K, interval, n_prompt + n_steps, key, true, start, retire, restart, s);
+    return run_slot_queue(h, audio_dev, n_segments, S, K, interval, n_prompt + n_steps, true, start, retire, restart, s);
 }
 
 extern "C" int ymt3_transcribe_stream_scored(ymt3_handle h, const float* audio_dev, int n_segments, int n_steps, const int32_t* prompt_dev,
@@ -1815,7 +1961,7 @@ extern "C" int ymt3_transcribe_stream(ymt3_handle h, const float* audio_dev, int
 
 // Beam search under continuous batching (include/ymt3.h): the queue loop above with slots of n_channels * W rows.  A slot is started by
 // beam_slot_start_kernel and harvested by the result kernel over its groups when all of them are done; the steps are launch_step's beam
-// steps with per-row positions (slot_mode and beam_W both set).  Every per-call and per-slot value lives in device memory, so the step
+// steps with per-row positions (mode SM_SLOT_BEAM).  Every per-call and per-slot value lives in device memory, so the step
 // graph depends on (slots, W, steps per graph) only.
 extern "C" int ymt3_transcribe_stream_beam(ymt3_handle h, const float* audio_dev, int n_segments, int n_steps, const int32_t* prompt_dev,
                                            int n_prompt, const ymt3_beam_params* params, int32_t* tokens_dev, float* seq_scores_dev,
@@ -1841,20 +1987,16 @@ extern "C" int ymt3_transcribe_stream_beam(ymt3_handle h, const float* audio_dev
     hipStream_t s = (hipStream_t)stream;
     const int rows = K * W, R = slots * rows;
 
-    struct ModeGuard { ymt3_ctx* c; ~ModeGuard() { c->slot_mode = false; c->beam_W = 0; } } guard{h};
-    h->slot_mode = true;
-    h->beam_W = W;
-    const BeamArgs b = beam_args(h, R, W, h->shared);
+    const StepShape S = step_shape(h, SM_SLOT_BEAM, slots, W, R, 1, false);
+    const BeamArgs b = beam_args(h, R, W, h->shared, true);
     BeamShared bp = h->beam_trace;
     bp.alpha = params->length_penalty; bp.tokens_out = tokens_dev; bp.seq_out = seq_scores_dev; bp.tok_out = token_scores_dev;
     h->last_chains = 1;
-    qkv0_decide(h, R, true, false);
+    h->last_qkv0 = S.qkv0;
     ConstraintView cv_init = cv;
     cv_init.start = nullptr;                  // (the groups' states are seeded at admission, from their segment's start states)
     LAUNCH(launch_beam_init(b, n_steps, prompt_dev, n_prompt, cv_init, bp, s));
 
-    StepKey key;
-    key.mode = SM_SLOT_BEAM; key.B = slots; key.beams = W;
     const int N = params->num_return;
     auto start = [&](int slot, int seg) -> int {
         ConstraintView cv_seg = cv;
@@ -1867,7 +2009,7 @@ extern "C" int ymt3_transcribe_stream_beam(ymt3_handle h, const float* audio_dev
         return YMT3_OK;
     };
     auto restart = []() -> int { return YMT3_OK; };      // (beam steps hold no merged kernel)
-    return run_slot_queue(h, audio_dev, n_segments, slots, rows, interval, n_prompt + n_steps, key, false, start, retire, restart, s);
+    return run_slot_queue(h, audio_dev, n_segments, S, rows, interval, n_prompt + n_steps, false, start, retire, restart, s);
 }
 
 extern "C" int ymt3_test_gemm(ymt3_handle h, const void* a_dev, const void* w_dev, float* c_dev, int M, int N, int K, void* stream) {
