@@ -1022,6 +1022,35 @@ typedef struct ymt3_moe_args {
 } ymt3_moe_args;
 int ymt3_test_moe_stage(ymt3_handle h, int stage, const ymt3_moe_args* args, void* stream);
 
+/* Per-kernel test doors of the full-sequence scoring pass (csrc/dec_seq.hip), one production launcher each.  Same rules as the doors above;
+ * none touches handle state.  Rows are [row0, row0 + n_rows) of prompt / tokens / lengths / scores / logits (indexed by the ABSOLUTE row);
+ * h, q, out and xn start at the launch's first row.  d == 512, L == n_prompt + n_steps.
+ * ymt3_test_seq_embed: launch_seq_embed.  h f32 [n_rows * L][512] = embed[fed id] (+ chan_embed[row % n_channels]): position 0 feeds pad_id,
+ *   1 .. P the prompt, P + j + 1 tokens[j], every id clamped into [0, V).  chan_embed needs n_channels >= 1.
+ * ymt3_test_dec_seq_attention: launch_dec_seq_attention.  Query row (r, t) at q + r * q_seq + t * ldq + 64 h, key / value row (b, t) at
+ *   k|v + b * kv_seq + h * kv_head + t * ldkv with b = (row0 + r) / rows_per_kv, output row at out + r * o_seq + t * ldo + 64 h.  causal != 0:
+ *   n_keys == L <= bias_stride, keys <= query, + bias[h][query - key] (f32 [H][bias_stride]); else every one of n_keys keys, no bias.  ldq, ldo
+ *   >= 64 H, ldkv >= 64, strides multiples of 8 elements, H and n_rows <= 65535.
+ * ymt3_test_seq_lm_head: launch_seq_lm_head_score.  xn bf16 [M][512] (M == n_rows * L), W bf16 [V][512], V % 16 == 0: scores[row][j] =
+ *   logit[tokens[row][j]] - lse for j = position - n_prompt >= 0 (exactly 0.0 for j >= lengths[row] clamped into [0, n_steps]; lengths may be
+ *   NULL), logits[row][j][V] when not NULL; prompt positions write nothing. */
+typedef struct ymt3_seq_embed_args {
+    float* h; const void* embed; const void* chan_embed; const int32_t* prompt; const int32_t* tokens;
+    int32_t row0, n_rows, L, n_prompt, n_steps, V, d, n_channels, pad_id;
+} ymt3_seq_embed_args;
+int ymt3_test_seq_embed(ymt3_handle h, const ymt3_seq_embed_args* args, void* stream);
+typedef struct ymt3_dec_seq_attn_args {
+    const void* q; const void* k; const void* v; void* out; const float* bias;
+    int64_t q_seq, kv_seq, o_seq;
+    int32_t ldq, ldkv, ldo, kv_head, row0, n_rows, L, n_keys, rows_per_kv, H, bias_stride, causal;
+} ymt3_dec_seq_attn_args;
+int ymt3_test_dec_seq_attention(ymt3_handle h, const ymt3_dec_seq_attn_args* args, void* stream);
+typedef struct ymt3_seq_lm_head_args {
+    const void* xn; const void* W; const int32_t* tokens; const int32_t* lengths; float* scores; float* logits;
+    int32_t M, L, n_prompt, n_steps, V, d, row0;
+} ymt3_seq_lm_head_args;
+int ymt3_test_seq_lm_head(ymt3_handle h, const ymt3_seq_lm_head_args* args, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -6,6 +6,11 @@ all positions of a row go through the layers at once.  Self-attention is causal 
 bias -- and, like the cross-attention, rounds its softmax numerators to bf16 (`attention(round_p=True)`, the MFMA kernels'
 contract).  The step oracle (O.decoder_step) keeps them in f32: the two are different correct evaluation orders of one model, and
 tests/test_score_pass_cpu.py pins this restatement to it within the project's parity tolerances.
+
+`attention(round_p=True)` rounds exp(s - GLOBAL max).  dec_seq_attn_kernel streams the keys in tiles of 64 and rounds exp(s - the running
+max after the current tile), then rescales both accumulators in fp32: the kernel's contract is that tile schedule
+(tests/seq_kernel_model.py::attention_tiles, DESIGN.md section 30).  The two are the same arithmetic only up to 64 keys; beyond, this
+oracle is another correct evaluation order, compared within tolerances, never bit for bit.
 """
 from typing import Optional
 
@@ -27,7 +32,7 @@ def teacher_forward(enc_out: torch.Tensor, W, cfg, tokens: torch.Tensor, prompt:
     h = W["dec.embed"][fed]
     if K > 1:
         h = h + W["dec.chan_embed"][torch.arange(R) % K][:, None, :]
-    h = h.float()
+    h = h if h.dtype == torch.float64 else h.float()                    # (double weights: a float64 run with the same rounding points)
     dist = torch.arange(L)[:, None] - torch.arange(L)[None, :]          # query - key
     bias = O.decoder_bias_by_distance(W["dec.relbias"], L, cfg)[:, dist.clamp(min=0)]             # (H, L, L)
     bias = bias.masked_fill(dist < 0, float("-inf"))[None]

@@ -39,6 +39,7 @@ SYMBOLS = [
     "ymt3_chords_create", "ymt3_chords_destroy", "ymt3_track_chords",
     "ymt3_test_gemm_ex", "ymt3_test_rmsnorm", "ymt3_test_enc_attention", "ymt3_test_seq_attention", "ymt3_test_spec_embed",
     "ymt3_test_dec_gemm", "ymt3_test_dec_attention", "ymt3_test_mc_cross_attention", "ymt3_test_moe_stage",
+    "ymt3_test_seq_embed", "ymt3_test_dec_seq_attention", "ymt3_test_seq_lm_head",
 ]
 
 _lib = None
@@ -130,6 +131,24 @@ class MoeArgs(ctypes.Structure):
     _fields_ = [(n, ctypes.c_void_p) for n in ("h", "gain", "ssq", "router", "wi", "wo", "wi_q8", "wo_q8", "wi_s", "wo_s", "xn", "sel", "gate",
                                                "hidden", "y")] + [
         (n, ctypes.c_int32) for n in ("ssq_stride", "fp8", "row0", "R", "E", "top_k", "d_model", "d_ff")] + [("eps", ctypes.c_float)]
+
+
+class SeqEmbedArgs(ctypes.Structure):
+    """ymt3_seq_embed_args of include/ymt3.h"""
+    _fields_ = [(n, ctypes.c_void_p) for n in ("h", "embed", "chan_embed", "prompt", "tokens")] + [
+        (n, ctypes.c_int32) for n in ("row0", "n_rows", "L", "n_prompt", "n_steps", "V", "d", "n_channels", "pad_id")]
+
+
+class DecSeqAttnArgs(ctypes.Structure):
+    """ymt3_dec_seq_attn_args of include/ymt3.h"""
+    _fields_ = [(n, ctypes.c_void_p) for n in ("q", "k", "v", "out", "bias")] + [(n, ctypes.c_int64) for n in ("q_seq", "kv_seq", "o_seq")] + [
+        (n, ctypes.c_int32) for n in ("ldq", "ldkv", "ldo", "kv_head", "row0", "n_rows", "L", "n_keys", "rows_per_kv", "H", "bias_stride", "causal")]
+
+
+class SeqLmHeadArgs(ctypes.Structure):
+    """ymt3_seq_lm_head_args of include/ymt3.h"""
+    _fields_ = [(n, ctypes.c_void_p) for n in ("xn", "W", "tokens", "lengths", "scores", "logits")] + [
+        (n, ctypes.c_int32) for n in ("M", "L", "n_prompt", "n_steps", "V", "d", "row0")]
 
 
 class YMT3Error(RuntimeError):
@@ -334,6 +353,9 @@ def load() -> ctypes.CDLL:
     lib.ymt3_test_dec_attention.restype = i32
     lib.ymt3_test_mc_cross_attention.argtypes = [vp, ctypes.POINTER(McCrossArgs), vp]
     lib.ymt3_test_mc_cross_attention.restype = i32
+    for name, struct in (("ymt3_test_seq_embed", SeqEmbedArgs), ("ymt3_test_dec_seq_attention", DecSeqAttnArgs), ("ymt3_test_seq_lm_head", SeqLmHeadArgs)):
+        getattr(lib, name).argtypes = [vp, ctypes.POINTER(struct), vp]
+        getattr(lib, name).restype = i32
     for n in ("ymt3_logmel", "ymt3_encode", "ymt3_decode_greedy", "ymt3_transcribe_segments", "ymt3_test_gemm"):
         getattr(lib, n).restype = i32
     if lib.ymt3_abi_version() != 3:

@@ -14,9 +14,12 @@
 // of K and V are 256 KB, more than the LDS, so keys stream through LDS in tiles of 64 (double buffered: the next tile's global loads
 // are in flight under the current tile's math, one barrier per tile) with f32 running max and sum.
 //
-// Numerics contract: e = exp(s - running max) rounded to bf16 for P.V, the normaliser sums the unrounded f32 e,
-// output rounded to bf16 -- the encoder kernel's contract, oracle/ymt3_oracle.py::attention(round_p=True), not the step kernels'
-// all-f32 softmax.  A rescale by exp(old max - new max) multiplies the f32 accumulators and the f32 sum alike.
+// Numerics contract (DESIGN.md sections 2 and 30): THE TILE SCHEDULE.  e = exp(s - running max AFTER the current 64-key tile) rounded to bf16
+// for P.V, the normaliser sums the unrounded f32 e, a rescale by exp(old max - new max) multiplies the f32 accumulators and the f32 sum
+// alike, output rounded to bf16 (tests/seq_kernel_model.py::attention_tiles states it in float64).  Up to 64 keys that is the encoder
+// kernel's contract, oracle/ymt3_oracle.py::attention(round_p=True), bit for bit; beyond, the oracle rounds exp(s - GLOBAL max), another
+// grid for P wherever a later tile raises the maximum: the same model in another correct arithmetic, compared within tolerances only.
+// Not the step kernels' all-f32 softmax.
 #include "common.h"
 #include "kernels.h"
 

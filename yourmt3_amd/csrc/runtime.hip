@@ -2293,6 +2293,71 @@ extern "C" int ymt3_test_moe_stage(ymt3_handle h, int stage, const ymt3_moe_args
     HIP_TRY(hipGetLastError());
     return YMT3_OK;
 }
+
+extern "C" int ymt3_test_seq_embed(ymt3_handle h, const ymt3_seq_embed_args* args, void* stream) {
+    int rc = check_call(h, 0);
+    if (rc) return rc;
+    if (!args) FAIL(YMT3_ERR_ARG, "%s: args is null", __func__);
+    const ymt3_seq_embed_args& c = *args;
+    DOOR_PTR(c.h); DOOR_PTR(c.embed); DOOR_PTR(c.tokens);
+    if (c.chan_embed) { DOOR_PTR(c.chan_embed); DOOR_REQUIRE(c.n_channels >= 1); }
+    if (c.n_prompt > 0) DOOR_PTR(c.prompt);
+    DOOR_REQUIRE(c.row0 >= 0 && c.n_rows >= 1 && c.n_prompt >= 0 && c.n_steps >= 1 && c.L == c.n_prompt + c.n_steps && c.V >= 1 && c.d == 512);
+    SeqEmbedArgs a{};
+    a.h = c.h; a.embed = static_cast<const bf16_t*>(c.embed); a.chan_embed = static_cast<const bf16_t*>(c.chan_embed);
+    a.prompt = c.n_prompt > 0 ? c.prompt : nullptr; a.tokens = c.tokens;
+    a.row0 = c.row0; a.n_rows = c.n_rows; a.L = c.L; a.n_prompt = c.n_prompt; a.n_steps = c.n_steps; a.V = c.V; a.d = c.d;
+    a.n_channels = c.n_channels; a.pad_id = c.pad_id;
+    LAUNCH(launch_seq_embed(a, (hipStream_t)stream));
+    HIP_TRY(hipGetLastError());
+    return YMT3_OK;
+}
+
+extern "C" int ymt3_test_dec_seq_attention(ymt3_handle h, const ymt3_dec_seq_attn_args* args, void* stream) {
+    int rc = check_call(h, 0);
+    if (rc) return rc;
+    if (!args) FAIL(YMT3_ERR_ARG, "%s: args is null", __func__);
+    const ymt3_dec_seq_attn_args& c = *args;
+    DOOR_PTR(c.q); DOOR_PTR(c.k); DOOR_PTR(c.v); DOOR_PTR(c.out);
+    DOOR_REQUIRE(c.row0 >= 0 && c.n_rows >= 1 && c.n_rows <= 65535 && c.L >= 1 && c.n_keys >= 1 && c.rows_per_kv >= 1 && c.H >= 1 && c.H <= 65535);
+    DOOR_REQUIRE(c.ldq >= c.H * 64 && c.ldo >= c.H * 64 && c.ldkv >= 64 && c.kv_head >= 64 && c.q_seq >= 0 && c.kv_seq >= 0 && c.o_seq >= 0);
+    // heads inside a key's row (ldkv >= H * 64 when kv_head == 64), or keys inside a head's slab (head-major): no two (head, key) rows overlap
+    DOOR_REQUIRE(c.ldkv >= (long long)(c.H - 1) * c.kv_head + 64 || c.kv_head >= (long long)(c.n_keys - 1) * c.ldkv + 64);
+    DOOR_REQUIRE((c.ldq | c.ldkv | c.ldo | c.kv_head) % 8 == 0 && (c.q_seq | c.kv_seq | c.o_seq) % 8 == 0);
+    if (c.causal) {                 // the kernel clamps a distance beyond the table silently
+        DOOR_PTR(c.bias);
+        DOOR_REQUIRE(c.n_keys == c.L && c.L <= c.bias_stride);
+    } else {
+        DOOR_REQUIRE(c.bias == nullptr);
+    }
+    SeqAttnDecArgs a{};
+    a.q = static_cast<const bf16_t*>(c.q); a.k = static_cast<const bf16_t*>(c.k); a.v = static_cast<const bf16_t*>(c.v);
+    a.out = static_cast<bf16_t*>(c.out); a.bias = c.bias; a.q_seq = c.q_seq; a.kv_seq = c.kv_seq; a.o_seq = c.o_seq;
+    a.ldq = c.ldq; a.ldkv = c.ldkv; a.ldo = c.ldo; a.kv_head = c.kv_head; a.row0 = c.row0; a.n_rows = c.n_rows; a.L = c.L; a.n_keys = c.n_keys;
+    a.rows_per_kv = c.rows_per_kv; a.H = c.H; a.bias_stride = c.bias_stride;
+    LAUNCH(launch_dec_seq_attention(c.causal != 0, a, (hipStream_t)stream));
+    HIP_TRY(hipGetLastError());
+    return YMT3_OK;
+}
+
+extern "C" int ymt3_test_seq_lm_head(ymt3_handle h, const ymt3_seq_lm_head_args* args, void* stream) {
+    int rc = check_call(h, 0);
+    if (rc) return rc;
+    if (!args) FAIL(YMT3_ERR_ARG, "%s: args is null", __func__);
+    const ymt3_seq_lm_head_args& c = *args;
+    DOOR_PTR(c.xn); DOOR_PTR(c.W); DOOR_PTR(c.tokens); DOOR_PTR(c.scores);
+    if (c.lengths) DOOR_PTR(c.lengths);
+    if (c.logits) DOOR_PTR(c.logits);
+    DOOR_REQUIRE(c.row0 >= 0 && c.M >= 1 && c.L >= 1 && c.M % c.L == 0 && c.n_prompt >= 0 && c.n_steps >= 1 && c.L == c.n_prompt + c.n_steps);
+    DOOR_REQUIRE(c.d == 512 && c.V >= 16 && c.V % 16 == 0);
+    SeqLmHeadArgs a{};
+    a.xn = static_cast<const bf16_t*>(c.xn); a.W = static_cast<const bf16_t*>(c.W); a.tokens = c.tokens; a.lengths = c.lengths;
+    a.scores = c.scores; a.logits = c.logits; a.M = c.M; a.L = c.L; a.n_prompt = c.n_prompt; a.n_steps = c.n_steps; a.V = c.V; a.d = c.d;
+    a.row0 = c.row0;
+    LAUNCH(launch_seq_lm_head_score(a, (hipStream_t)stream));
+    HIP_TRY(hipGetLastError());
+    return YMT3_OK;
+}
 #undef DOOR_PTR
 #undef DOOR_REQUIRE
 

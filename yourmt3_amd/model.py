@@ -1295,3 +1295,76 @@ class YourMT3:
         c = _lib.MoeArgs(*[p(n) for n in ("h", "gain", "ssq", "router", "wi", "wo", "wi_q8", "wo_q8", "wi_s", "wo_s", "xn", "sel", "gate", "hidden", "y")],
                          ssq_stride, int(bool(fp8)), row0, R, E, top_k, d_model, d_ff, float(eps))
         _lib.check(self._lib.ymt3_test_moe_stage(self._handle, int(stage), ctypes.byref(c), self._stream()))
+
+    # ---- full-sequence scoring pass (csrc/dec_seq.hip), validated before the library is touched like the decoder doors above
+    def test_seq_embed(self, *, h: torch.Tensor, embed: torch.Tensor, tokens: torch.Tensor, n_rows: int, n_prompt: int, n_steps: int, V: int,
+                       pad_id: int, row0: int = 0, L: Optional[int] = None, prompt: Optional[torch.Tensor] = None,
+                       chan_embed: Optional[torch.Tensor] = None, n_channels: int = 1, d: int = 512) -> None:
+        """ymt3_test_seq_embed (include/ymt3.h): h [n_rows * L][512] starts at the launch's first row; prompt / tokens are indexed by the
+        absolute row and must reach row0 + n_rows."""
+        need, rows = self._need, row0 + n_rows
+        L = n_prompt + n_steps if L is None else L
+        need(row0 >= 0 and n_rows >= 1 and n_prompt >= 0 and n_steps >= 1 and V >= 1 and d == 512, "0 <= row0, n_rows >= 1, n_prompt >= 0, n_steps >= 1, V >= 1, d == 512")
+        need(L == n_prompt + n_steps, "L == n_prompt + n_steps")
+        need(chan_embed is None or n_channels >= 1, "n_channels >= 1 with chan_embed")
+        need(n_prompt == 0 or prompt is not None, "a prompt when n_prompt > 0")
+        self._door("h", h, torch.float32, n_rows * L * d)
+        self._door("embed", embed, torch.bfloat16, V * d)
+        self._door("tokens", tokens, torch.int32, rows * n_steps)
+        if n_prompt > 0:
+            self._door("prompt", prompt, torch.int32, rows * n_prompt)
+        if chan_embed is not None:
+            self._door("chan_embed", chan_embed, torch.bfloat16, n_channels * d)
+        p = lambda t: t.data_ptr() if t is not None else None
+        c = _lib.SeqEmbedArgs(p(h), p(embed), p(chan_embed), p(prompt) if n_prompt > 0 else None, p(tokens), row0, n_rows, L, n_prompt, n_steps, V, d,
+                              n_channels, pad_id)
+        _lib.check(self._lib.ymt3_test_seq_embed(self._handle, ctypes.byref(c), self._stream()))
+
+    def test_dec_seq_attention(self, *, causal: bool, q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, out: torch.Tensor, n_rows: int, L: int,
+                               n_keys: int, H: int, ldq: int, ldkv: int, ldo: int, kv_head: int, q_seq: int, kv_seq: int, o_seq: int,
+                               row0: int = 0, rows_per_kv: int = 1, bias: Optional[torch.Tensor] = None, bias_stride: int = 0) -> None:
+        """ymt3_test_dec_seq_attention (include/ymt3.h).  q / out start at the launch's first row; k / v hold the slabs of kv rows
+        0 .. (row0 + n_rows - 1) / rows_per_kv.  q, k, v may be views into one fused buffer."""
+        need = self._need
+        need(row0 >= 0 and 1 <= n_rows <= 65535 and L >= 1 and n_keys >= 1 and rows_per_kv >= 1 and 1 <= H <= 65535,
+             "0 <= row0, 1 <= n_rows <= 65535, L >= 1, n_keys >= 1, rows_per_kv >= 1, 1 <= H <= 65535")
+        need(ldq >= H * 64 and ldo >= H * 64 and ldkv >= 64 and kv_head >= 64 and min(q_seq, kv_seq, o_seq) >= 0,
+             "ldq, ldo >= H * 64, ldkv, kv_head >= 64, non-negative row strides")
+        need(ldkv >= (H - 1) * kv_head + 64 or kv_head >= (n_keys - 1) * ldkv + 64, "ldkv >= H * 64 (kv_head == 64), or head-major slabs")
+        need(all(x % 8 == 0 for x in (ldq, ldkv, ldo, kv_head, q_seq, kv_seq, o_seq)), "strides that are multiples of 8 elements")
+        if causal:
+            need(bias is not None and n_keys == L and L <= bias_stride, "a bias and n_keys == L <= bias_stride (causal)")
+            self._door("bias", bias, torch.float32, H * bias_stride)
+        else:
+            need(bias is None, "no bias (cross-attention)")
+        kv_rows = (row0 + n_rows - 1) // rows_per_kv + 1
+        kv_reach = (kv_rows - 1) * kv_seq + (H - 1) * kv_head + (n_keys - 1) * ldkv + 64
+        self._door("q", q, torch.bfloat16, (n_rows - 1) * q_seq + (L - 1) * ldq + H * 64)
+        self._door("k", k, torch.bfloat16, kv_reach)
+        self._door("v", v, torch.bfloat16, kv_reach)
+        self._door("out", out, torch.bfloat16, (n_rows - 1) * o_seq + (L - 1) * ldo + H * 64)
+        c = _lib.DecSeqAttnArgs(q.data_ptr(), k.data_ptr(), v.data_ptr(), out.data_ptr(), bias.data_ptr() if causal else None, q_seq, kv_seq, o_seq,
+                                ldq, ldkv, ldo, kv_head, row0, n_rows, L, n_keys, rows_per_kv, H, bias_stride if causal else 0, int(bool(causal)))
+        _lib.check(self._lib.ymt3_test_dec_seq_attention(self._handle, ctypes.byref(c), self._stream()))
+
+    def test_seq_lm_head(self, *, xn: torch.Tensor, W: torch.Tensor, tokens: torch.Tensor, scores: torch.Tensor, M: int, L: int, n_prompt: int,
+                         n_steps: int, V: int, row0: int = 0, lengths: Optional[torch.Tensor] = None, logits: Optional[torch.Tensor] = None,
+                         d: int = 512) -> None:
+        """ymt3_test_seq_lm_head (include/ymt3.h): xn [M][512] starts at the launch's first row; tokens / lengths / scores / logits are indexed
+        by the absolute row and must reach row0 + M / L."""
+        need = self._need
+        need(row0 >= 0 and M >= 1 and L >= 1 and n_prompt >= 0 and n_steps >= 1 and d == 512, "0 <= row0, M >= 1, L >= 1, n_prompt >= 0, n_steps >= 1, d == 512")
+        need(M % L == 0 and L == n_prompt + n_steps, "M % L == 0 and L == n_prompt + n_steps")
+        need(V >= 16 and V % 16 == 0, "V a positive multiple of 16")
+        rows = row0 + M // L
+        self._door("xn", xn, torch.bfloat16, M * d)
+        self._door("W", W, torch.bfloat16, V * d)
+        self._door("tokens", tokens, torch.int32, rows * n_steps)
+        self._door("scores", scores, torch.float32, rows * n_steps)
+        if lengths is not None:
+            self._door("lengths", lengths, torch.int32, rows)
+        if logits is not None:
+            self._door("logits", logits, torch.float32, rows * n_steps * V)
+        p = lambda t: t.data_ptr() if t is not None else None
+        c = _lib.SeqLmHeadArgs(p(xn), p(W), p(tokens), p(lengths), p(scores), p(logits), M, L, n_prompt, n_steps, V, d, row0)
+        _lib.check(self._lib.ymt3_test_seq_lm_head(self._handle, ctypes.byref(c), self._stream()))
