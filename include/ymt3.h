@@ -872,6 +872,56 @@ int  ymt3_track_chords(ymt3_handle h, ymt3_chords c, const int32_t* beats_dev, c
                        const int32_t* count_dev /* may be NULL */, long long n_frames, int32_t* chord_dev, long long chord_cap,
                        long long* result_dev /* [8] */, void* stream);
 
+/* ---- sections over note records and tracked beats ---------------------------------------------------------------------------------
+ * A ymt3_sections object gives the beats their form: where a new section starts, and one letter per section, equal for sections that
+ * repeat, from the records and the beats where ymt3_track_beats left them, and optionally the metre ymt3_track_bars wrote.  The rules
+ * are this project's own, UNVERIFIED against any package; the host specification is track_sections of
+ * yourmt3_amd/sections.py, and every output equals it bit for bit: everything is an integer, and times stay f64 until they are known to
+ * lie inside the frames.  Integer divisions below are floor divisions.
+ *
+ * Parameters (ymt3_sections_create refuses, YMT3_ERR_ARG, what is outside): frames_per_second finite and > 0; near_div (nd) in [2, 64];
+ * 1 <= n_programs <= 256, drum_program in [0, n_programs); context (w) in [1, 16]; kernel_beats (L) in [2, 64]; min_len (m) in [1, 256];
+ * peak_div in [1, 1024]; same_dist in [0, 32768]; len_num in [1, 16]; max_sections (M) in [1, 64]; max_beats in [1, 2^20 + 1];
+ * max_notes in [1, 2^20].
+ *   chroma      the bars' and the chords' c[i][pc] over the bars' slots (K beats, K read from beat_result_dev[0] on the device and
+ *               clamped to [0, max_beats]); n[i][pc] = c[i][pc] 1024 / max(sum of c[i], 1) (64 bits); empty[i] = (sum of c[i] = 0).
+ *   context     f[i][pc] = sum over d < w of n[min(i + d, K - 1)][pc]; the sum of f[i] is at most 1024 w.
+ *   similarity  D(i, j) = sum over pc of |f[i][pc] - f[j][pc]| <= 2048 w <= 32768; S(i, j) = 2048 w - D(i, j) >= 0.
+ *   novelty     L_i = min(L, i, K - i), t[u] = L - u; nov[i] = sum over u, v < L_i of t[u] t[v] (S(i-1-u, i-1-v) + S(i+u, i+v)
+ *               - S(i-1-u, i+v) - S(i+u, i-1-v)), signed, 64 bits; nov[0] = 0.  The quadrants are cut alike at the ends, nothing is
+ *               zero-padded.  The sum of t[u] t[v] is at most (64 65 / 2)^2 < 2^23 per quadrant and S < 2^16: |nov| < 2^41.
+ *   boundaries  candidates C: every i in [1, K), with metre_dev only those with metre_dev[i] & 255 = 0; top = the largest nov among C (0
+ *               if C is empty).  i in C is a peak if nov[i] > 0, peak_div nov[i] >= top, and no j in C with 0 < |j - i| <= m has the
+ *               larger key (nov[j], -j): a larger novelty, or an equal one at a smaller index.  Of more than M - 1 peaks the M - 1 with
+ *               the largest key are kept.  Section starts: beat 0 and the kept peaks in time order; section s is [a_s, a_{s+1}), a_n = K.
+ *   labels      a section whose beats are all empty is silent: label 255, it neither takes nor gives a letter.  For two others,
+ *               m_st = min(len_s, len_t), d(s, t) = (sum over k < m_st of D(a_s + k, a_t + k)) / m_st (the sum is below 2^35); they are
+ *               the same if len_num m_st >= max(len_s, len_t) and d(s, t) <= same_dist.  In time order, s takes the label of the
+ *               earliest earlier non-silent t that is the same as it, else the next unused label from 0.
+ * ymt3_track_sections: beats_dev / beat_result_dev as ymt3_track_beats wrote them; metre_dev as ymt3_track_bars wrote it (at least K
+ * entries), or NULL; notes_dev / n_notes / count_dev as there, n_notes at most the object's max_notes.  section_dev[i] = 65536 start +
+ * 256 s + label for i < K (start = 1 on a section's first beat), the rest is left alone; section_cap, its length, is at least the
+ * object's max_beats.  novelty_dev[i] = nov[i] for i < K, or NULL (at least max_beats entries otherwise).  result_dev[8]: the number of
+ * sections, the number of distinct letters, top, skipped records, the number of peaks before the cap, the number of silent sections, 0,
+ * 0.  With K < 2 nothing is written to section_dev or novelty_dev and result_dev = {0, 0, 0, skipped, 0, 0, 0, 0}.
+ * Asynchronous on `stream`, allocates nothing, reads nothing back and leaves the handle's decode state alone.  The object's scratch
+ * (89 bytes per beat and 4 KiB) is used by the call: calls on one object are ordered by their stream.  YMT3_ERR_ARG, with handle and
+ * object still usable, for a NULL or misaligned beats_dev, beat_result_dev, section_dev or result_dev, a misaligned metre_dev or
+ * novelty_dev, a NULL notes_dev with n_notes > 0, a misaligned notes_dev or count_dev, n_notes outside [0, max_notes], n_frames outside
+ * [1, 2^20], section_cap below the object's max_beats.  Sections are compared beat by beat along their diagonal: the same chords in
+ * another order are another section; transposed repeats and functional names are out of scope. */
+typedef struct ymt3_section_params {
+    double  frames_per_second;
+    int32_t near_div, n_programs, drum_program, context, kernel_beats, min_len, peak_div, same_dist, len_num, max_sections;
+} ymt3_section_params;
+typedef struct ymt3_sections_s* ymt3_sections;
+int  ymt3_sections_create(ymt3_handle h, const ymt3_section_params* params, long long max_beats, long long max_notes, ymt3_sections* out);
+void ymt3_sections_destroy(ymt3_sections c);
+int  ymt3_track_sections(ymt3_handle h, ymt3_sections c, const int32_t* beats_dev, const long long* beat_result_dev,
+                         const int32_t* metre_dev /* may be NULL */, const void* notes_dev, long long n_notes,
+                         const int32_t* count_dev /* may be NULL */, long long n_frames, int32_t* section_dev, long long section_cap,
+                         long long* novelty_dev /* may be NULL */, long long* result_dev /* [8] */, void* stream);
+
 /* Measurement hook (bench.py `roofline`): decode eagerly (no graph) and bracket every kernel launch of
  * every `stride`-th step (positions stride/2, 3*stride/2, ...) with HIP events on `stream`; synchronises the stream before returning.
  * Classes: 0 qkv+cache GEMM, 1 self-attention, 2 self O-proj, 3 cross Q GEMM, 4 cross-attention,

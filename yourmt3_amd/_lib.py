@@ -37,6 +37,7 @@ SYMBOLS = [
     "ymt3_beats_create", "ymt3_beats_destroy", "ymt3_track_beats", "ymt3_beat_positions",
     "ymt3_bars_create", "ymt3_bars_destroy", "ymt3_track_bars",
     "ymt3_chords_create", "ymt3_chords_destroy", "ymt3_track_chords",
+    "ymt3_sections_create", "ymt3_sections_destroy", "ymt3_track_sections",
     "ymt3_test_gemm_ex", "ymt3_test_rmsnorm", "ymt3_test_enc_attention", "ymt3_test_seq_attention", "ymt3_test_spec_embed",
     "ymt3_test_dec_gemm", "ymt3_test_dec_attention", "ymt3_test_mc_cross_attention", "ymt3_test_moe_stage",
     "ymt3_test_seq_embed", "ymt3_test_dec_seq_attention", "ymt3_test_seq_lm_head",
@@ -97,6 +98,13 @@ class ChordParams(ctypes.Structure):
     _fields_ = [("frames_per_second", ctypes.c_double), ("n_qualities", ctypes.c_int32), ("qualities", ctypes.c_int32 * 8)] + [
         (n, ctypes.c_int32) for n in ("near_div", "bass_div", "w_bass", "w_none", "change_cost", "change_cost_down", "n_programs", "drum_program",
                                       "reserved")]
+
+
+class SectionParams(ctypes.Structure):
+    """ymt3_section_params of include/ymt3.h"""
+    _fields_ = [("frames_per_second", ctypes.c_double)] + [
+        (n, ctypes.c_int32) for n in ("near_div", "n_programs", "drum_program", "context", "kernel_beats", "min_len", "peak_div", "same_dist", "len_num",
+                                      "max_sections")]
 
 
 class SeqAttnArgs(ctypes.Structure):
@@ -334,6 +342,12 @@ def load() -> ctypes.CDLL:
     lib.ymt3_chords_destroy.restype = None
     lib.ymt3_track_chords.argtypes = [vp, vp, vp, vp, vp, vp, ll, vp, ll, vp, ll, vp, vp]
     lib.ymt3_track_chords.restype = i32
+    lib.ymt3_sections_create.argtypes = [vp, ctypes.POINTER(SectionParams), ll, ll, ctypes.POINTER(vp)]
+    lib.ymt3_sections_create.restype = i32
+    lib.ymt3_sections_destroy.argtypes = [vp]
+    lib.ymt3_sections_destroy.restype = None
+    lib.ymt3_track_sections.argtypes = [vp, vp, vp, vp, vp, vp, ll, vp, ll, vp, ll, vp, vp, vp]
+    lib.ymt3_track_sections.restype = i32
     f32 = ctypes.c_float
     lib.ymt3_test_gemm_ex.argtypes = [vp, i32, vp, vp, vp, vp, i32, i32, i32, i32, i32, i32, i32, i32, i32, vp]
     lib.ymt3_test_gemm_ex.restype = i32

@@ -318,6 +318,35 @@ struct ChordArgs {
 };
 int launch_track_chords(const ChordArgs& a, hipStream_t stream);
 
+// ---------------------------------------------------------------- sections over note records and beats (sections.hip; include/ymt3.h, sections)
+constexpr int SECTION_MAX_SECTIONS = 64, SECTION_MAX_KERNEL = 64, SECTION_MAX_CONTEXT = 16, SECTION_MAX_MIN_LEN = 256;
+constexpr int SECTION_F_WORDS = 16;                                     // per beat: f[12] as 16-bit words, [12] the empty flag, three spare
+constexpr int SECTION_ACC_WORDS = 4;                                    // the biased top, the number of peaks, two spare
+struct SectionArgs {
+    double frames_per_second;
+    int n_programs, drum_program;
+    int near_div, context, kernel_beats, min_len, peak_div, same_dist, len_num, max_sections;
+    const int32_t* beats;                 // [K] frames, strictly ascending
+    const long long* beat_result;         // track_beats' result: [0] is K, clamped to [0, max_beats]
+    long long max_beats;                  // the object's: what the scratch below holds
+    const int32_t* metre;                 // [K] 256 m + k of every beat, or null
+    const DetokNote* notes;               // [n]
+    long long n;
+    const int32_t* count;                 // device count (or null): min(n, max(*count, 0)) records are live
+    long long n_frames;
+    unsigned* chroma;                     // [max_beats][12] c
+    unsigned short* f;                    // [max_beats][SECTION_F_WORDS]
+    long long* nov;                       // [max_beats]
+    unsigned char* peak;                  // [max_beats] 1: a peak
+    unsigned long long* acc;              // [SECTION_ACC_WORDS]
+    int32_t* starts;                      // [SECTION_MAX_SECTIONS + 2]: a_0 .. a_n, then the number of sections at [SECTION_MAX_SECTIONS + 1]
+    unsigned char* same;                  // [SECTION_MAX_SECTIONS][SECTION_MAX_SECTIONS]: [s][t], t < s: the same; [s][s]: s is silent
+    int32_t* section;                     // [>= max_beats]: the first K are written
+    long long* novelty;                   // [>= max_beats] or null: the first K are written
+    long long* result;                    // [8]: sections, letters, top, skipped, peaks, silent sections, 0, 0
+};
+int launch_track_sections(const SectionArgs& a, hipStream_t stream);
+
 // ---------------------------------------------------------------- dense GEMM (gemm.hip)
 // C[M][N] (+)= A[M][K] (bf16, row stride lda) * W[N][K]^T (bf16, row stride ldw), fp32 accumulate.
 enum GemmEpilogue {

@@ -1,6 +1,6 @@
 // The note-side objects of the C ABI (include/ymt3.h): detokeniser and its incremental state, tokeniser, note metrics, piano roll / frame
-// metrics, aligner, note velocities, beat tracker, bar tracker, chord tracker.  Host logic only: argument checks, scratch, and the launches of detok.hip, tok.hip, metrics.hip, roll.hip,
-// align.hip, velocity.hip, beats.hip, bars.hip and chords.hip.  Of the handle they need the device and the configuration (runtime.h).  What they have in common is written once, at the top: the
+// metrics, aligner, note velocities, beat tracker, bar tracker, chord tracker, section tracker.  Host logic only: argument checks, scratch, and the launches of detok.hip, tok.hip, metrics.hip, roll.hip,
+// align.hip, velocity.hip, beats.hip, bars.hip, chords.hip and sections.hip.  Of the handle they need the device and the configuration (runtime.h).  What they have in common is written once, at the top: the
 // create prologue, the owner check, the program and record-array checks, and the scratch list that both *_create and *_destroy walk.
 #include <algorithm>
 #include <cmath>
@@ -864,5 +864,80 @@ extern "C" int ymt3_track_chords(ymt3_handle h, ymt3_chords c, const int32_t* be
     a.chroma = c->chroma; a.bass = c->bass; a.back = c->back;
     a.chord = chord_dev; a.result = result_dev;
     LAUNCH(launch_track_chords(a, static_cast<hipStream_t>(stream)));
+    return YMT3_OK;
+}
+
+// ---------------------------------------------------------------- sections over note records and beats (include/ymt3.h)
+struct ymt3_sections_s {
+    ymt3_handle owner;
+    int device;
+    ymt3_section_params p;
+    long long max_beats, max_notes;
+    unsigned* chroma = nullptr;             // [max_beats][12]
+    unsigned short* f = nullptr;            // [max_beats][SECTION_F_WORDS]
+    long long* nov = nullptr;               // [max_beats]
+    unsigned char* peak = nullptr;          // [max_beats]
+    unsigned long long* acc = nullptr;      // [SECTION_ACC_WORDS]
+    int32_t* starts = nullptr;              // [SECTION_MAX_SECTIONS + 2]
+    unsigned char* same = nullptr;          // [SECTION_MAX_SECTIONS][SECTION_MAX_SECTIONS]
+};
+
+static std::vector<Slot> slots(ymt3_sections c) {
+    const size_t B = (size_t)c->max_beats;
+    return {slot(&c->chroma, B * 12 * sizeof(unsigned)), slot(&c->f, B * SECTION_F_WORDS * sizeof(unsigned short)), slot(&c->nov, B * sizeof(long long)),
+            slot(&c->peak, B), slot(&c->acc, SECTION_ACC_WORDS * sizeof(unsigned long long)),
+            slot(&c->starts, (SECTION_MAX_SECTIONS + 2) * sizeof(int32_t), nullptr, true),
+            slot(&c->same, (size_t)SECTION_MAX_SECTIONS * SECTION_MAX_SECTIONS, nullptr, true)};
+}
+extern "C" void ymt3_sections_destroy(ymt3_sections c) { destroy_object(c); }
+
+extern "C" int ymt3_sections_create(ymt3_handle h, const ymt3_section_params* params, long long max_beats, long long max_notes, ymt3_sections* out) {
+    if (const int rc = create_prologue(reinterpret_cast<void**>(out), h, params, "params")) return rc;
+    const ymt3_section_params& p = *params;
+    if (!std::isfinite(p.frames_per_second) || p.frames_per_second <= 0) FAIL(YMT3_ERR_ARG, "frames_per_second=%g must be finite and > 0", p.frames_per_second);
+    const struct { const char* name; int v, lo, hi; } ranged[] = {{"near_div", p.near_div, 2, 64}, {"context", p.context, 1, SECTION_MAX_CONTEXT},
+                                                                  {"kernel_beats", p.kernel_beats, 2, SECTION_MAX_KERNEL},
+                                                                  {"min_len", p.min_len, 1, SECTION_MAX_MIN_LEN}, {"peak_div", p.peak_div, 1, 1024},
+                                                                  {"same_dist", p.same_dist, 0, 32768}, {"len_num", p.len_num, 1, 16},
+                                                                  {"max_sections", p.max_sections, 1, SECTION_MAX_SECTIONS}};
+    for (const auto& q : ranged)
+        if (q.v < q.lo || q.v > q.hi) FAIL(YMT3_ERR_ARG, "%s=%d outside [%d, %d]", q.name, q.v, q.lo, q.hi);
+    if (const int rc = check_programs(p.n_programs, p.drum_program, BAR_MAX_PROGRAMS, "")) return rc;
+    if (max_beats < 1 || max_beats > BAR_MAX_BEATS) FAIL(YMT3_ERR_ARG, "max_beats=%lld outside [1, %lld]", max_beats, BAR_MAX_BEATS);
+    if (max_notes < 1 || max_notes > BAR_MAX_NOTES) FAIL(YMT3_ERR_ARG, "max_notes=%lld outside [1, %lld]", max_notes, BAR_MAX_NOTES);
+    HIP_TRY(hipSetDevice(handle_device(h)));
+    ymt3_sections c = new ymt3_sections_s{h, handle_device(h), p, max_beats, max_notes};
+    return allocate_object(c, slots(c), "section tracker scratch", out);
+}
+
+extern "C" int ymt3_track_sections(ymt3_handle h, ymt3_sections c, const int32_t* beats_dev, const long long* beat_result_dev, const int32_t* metre_dev,
+                                   const void* notes_dev, long long n_notes, const int32_t* count_dev, long long n_frames, int32_t* section_dev,
+                                   long long section_cap, long long* novelty_dev, long long* result_dev, void* stream) {
+    if (const int rc = check_owner(h, c, "section tracker")) return rc;
+    if (!beats_dev) FAIL(YMT3_ERR_ARG, "beats_dev is NULL");
+    if (reinterpret_cast<uintptr_t>(beats_dev) % 4) FAIL(YMT3_ERR_ARG, "beats_dev is not aligned to 4 bytes");
+    if (!beat_result_dev) FAIL(YMT3_ERR_ARG, "beat_result_dev is NULL");
+    if (reinterpret_cast<uintptr_t>(beat_result_dev) % 8) FAIL(YMT3_ERR_ARG, "beat_result_dev is not aligned to 8 bytes");
+    if (reinterpret_cast<uintptr_t>(metre_dev) % 4) FAIL(YMT3_ERR_ARG, "metre_dev is not aligned to 4 bytes");
+    if (const int rc = check_count("n_notes", n_notes, c->max_notes, "max_notes")) return rc;
+    if (const int rc = check_record_ptr("notes_dev", notes_dev, n_notes)) return rc;
+    if (reinterpret_cast<uintptr_t>(count_dev) % 4) FAIL(YMT3_ERR_ARG, "count_dev is not aligned to 4 bytes");
+    if (n_frames < 1 || n_frames > BAR_MAX_FRAMES) FAIL(YMT3_ERR_ARG, "n_frames=%lld outside [1, %lld]", n_frames, BAR_MAX_FRAMES);
+    if (!section_dev) FAIL(YMT3_ERR_ARG, "section_dev is NULL");
+    if (reinterpret_cast<uintptr_t>(section_dev) % 4) FAIL(YMT3_ERR_ARG, "section_dev is not aligned to 4 bytes");
+    if (section_cap < c->max_beats) FAIL(YMT3_ERR_ARG, "section_cap=%lld below the section tracker's max_beats=%lld", section_cap, c->max_beats);
+    if (reinterpret_cast<uintptr_t>(novelty_dev) % 8) FAIL(YMT3_ERR_ARG, "novelty_dev is not aligned to 8 bytes");
+    if (!result_dev) FAIL(YMT3_ERR_ARG, "result_dev is NULL");
+    if (reinterpret_cast<uintptr_t>(result_dev) % 8) FAIL(YMT3_ERR_ARG, "result_dev is not aligned to 8 bytes");
+    HIP_TRY(hipSetDevice(c->device));
+    SectionArgs a{};
+    a.frames_per_second = c->p.frames_per_second; a.n_programs = c->p.n_programs; a.drum_program = c->p.drum_program;
+    a.near_div = c->p.near_div; a.context = c->p.context; a.kernel_beats = c->p.kernel_beats; a.min_len = c->p.min_len; a.peak_div = c->p.peak_div;
+    a.same_dist = c->p.same_dist; a.len_num = c->p.len_num; a.max_sections = c->p.max_sections;
+    a.beats = beats_dev; a.beat_result = beat_result_dev; a.max_beats = c->max_beats; a.metre = metre_dev;
+    a.notes = static_cast<const DetokNote*>(notes_dev); a.n = n_notes; a.count = n_notes ? count_dev : nullptr; a.n_frames = n_frames;
+    a.chroma = c->chroma; a.f = c->f; a.nov = c->nov; a.peak = c->peak; a.acc = c->acc; a.starts = c->starts; a.same = c->same;
+    a.section = section_dev; a.novelty = novelty_dev; a.result = result_dev;
+    LAUNCH(launch_track_sections(a, static_cast<hipStream_t>(stream)));
     return YMT3_OK;
 }

@@ -619,6 +619,14 @@ class YourMT3:
         from .chords import ChordTracker                                # (not a name of this module: chords.py builds on it)
         return ChordTracker(self, max_beats, max_notes, **params)
 
+    def compile_section_tracker(self, max_beats: int, max_notes: int, **params):
+        """The device section tracker (include/ymt3.h, sections; the rules and the host specification: yourmt3_amd/sections.py) with
+        scratch for `max_beats` beats and calls of up to `max_notes` records.  `params`: frames_per_second, near_div, context,
+        kernel_beats, min_len, peak_div, same_dist, len_num, max_sections, n_programs, drum_program (sections.DEFAULTS).  -> a
+        sections.SectionTracker, closed with the model."""
+        from .sections import SectionTracker                            # (not a name of this module: sections.py builds on it)
+        return SectionTracker(self, max_beats, max_notes, **params)
+
     def compile_ingest_stream(self, sample_rate: int, n_channels: int = 1, dtype=torch.int16, max_chunk_frames: int = 1 << 16) -> IngestStream:
         """Streaming form of ingest() (include/ymt3.h, streaming ingest) for `n_channels`-channel PCM of `dtype` (int16 or float32) at
         `sample_rate`, pushed in chunks of at most `max_chunk_frames` frames."""

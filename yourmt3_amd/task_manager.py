@@ -557,7 +557,8 @@ class TaskManager:
         return table
 
     def tokens_to_notes_device(self, model, tokens, start_secs: Sequence[float], end_sec: float, scores=None,
-                               detokenizer=None, velocity=None, audio=None, beats=None, quantize: int = 0, bars=None, chords=None):
+                               detokenizer=None, velocity=None, audio=None, beats=None, quantize: int = 0, bars=None, chords=None,
+                               sections=None):
         """tokens_to_notes on the device -> (notes, n_invalid).  `tokens`: (n, K, L) integer ids on `model`'s GPU (any strides whose
         last dimension is contiguous, e.g. hypothesis 0 of a beam call's (n, K, N, L)); `scores`: the matching (n, K, L) f32 token scores
         or None; `start_secs` must be strictly increasing.  `detokenizer`: a YourMT3.compile_detokenizer object to reuse (None: one is
@@ -574,13 +575,18 @@ class TaskManager:
         (int32 (n_beats,), 256 m + k) and "bar_result" (int64 (8,), bars.track_bars' result).
         `chords`: a YourMT3.compile_chord_tracker object (it needs `beats`; with `bars` it uses their metre): a chord per beat, tracked on
         the same records and beats where they lie, riding back in the same copy: the third element gains "chord" (int32 (n_beats,),
-        256 bass + label) and "chord_result" (int64 (8,), chords.track_chords' result)."""
+        256 bass + label) and "chord_result" (int64 (8,), chords.track_chords' result).
+        `sections`: a YourMT3.compile_section_tracker object (it needs `beats`; with `bars` it uses their metre): the song's form, tracked
+        on the same records and beats where they lie, riding back in the same copy: the third element gains "section" (int32 (n_beats,),
+        65536 start + 256 s + label), "novelty" (int64 (n_beats,)) and "section_result" (int64 (8,), sections.track_sections' result)."""
         import torch
 
         if bars is not None and beats is None:
             raise ValueError("bars without beats: the bar tracker works on the beat tracker's beats")
         if chords is not None and beats is None:
             raise ValueError("chords without beats: the chord tracker works on the beat tracker's beats")
+        if sections is not None and beats is None:
+            raise ValueError("sections without beats: the section tracker works on the beat tracker's beats")
         starts = np.asarray(list(start_secs), np.float64)
         if tokens.dim() != 3 or tokens.shape[1] != self.num_decoding_channels:
             raise ValueError(f"tokens must be (n, {self.num_decoding_channels}, L), got {tuple(tokens.shape)}")
@@ -596,7 +602,7 @@ class TaskManager:
         if n == 0 or L == 0:
             if beats is not None:
                 from .tracking import empty
-                return [], 0, empty(bars is not None, chords is not None)
+                return [], 0, empty(bars is not None, chords is not None, sections is not None)
             return [], 0
         own = detokenizer is None
         if own:
@@ -619,7 +625,7 @@ class TaskManager:
                 riders = [rec_dev[:nb]] + ([vel_dev[:n_notes]] if velocity is not None else [])
                 if beats is not None:                                    # bars and chords on the live records: their number is known by now, the beats' is not
                     parts["ticks"] = parts["ticks"][:n_notes]
-                    tracking.launch_bars_chords(parts, bars, chords, rec_dev[:nb], n_frames)
+                    tracking.launch_bars_chords(parts, bars, chords, rec_dev[:nb], n_frames, sections=sections)
                     riders += tracking.pack(parts)
                 both = torch.cat(riders).cpu().numpy()
                 rec, o = both[:nb].view(NOTE_RECORD), nb

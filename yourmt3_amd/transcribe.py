@@ -18,6 +18,7 @@ from .velocity import estimate_velocities  # noqa: F401  (its home is velocity.p
 from .beats import estimate_beats  # noqa: F401  (the same for beats.py)
 from .bars import estimate_bars  # noqa: F401  (and for bars.py)
 from .chords import estimate_chords  # noqa: F401  (and for chords.py)
+from .sections import estimate_sections  # noqa: F401  (and for sections.py)
 
 
 def transcribe(model, audio_info: Union[str, dict, np.ndarray], task_manager: Optional[TaskManager] = None, bsz: int = 8,
@@ -26,7 +27,7 @@ def transcribe(model, audio_info: Union[str, dict, np.ndarray], task_manager: Op
                min_confidence: Optional[float] = None, constrained: bool = False, programs=None, num_beams: int = 1,
                length_penalty: float = 1.0, device_detok: bool = False, velocity: bool = False, velocity_params: Optional[dict] = None,
                beats: bool = False, quantize: int = 0, beat_params: Optional[dict] = None, bars: bool = False, bar_params: Optional[dict] = None,
-               chords: bool = False, chord_params: Optional[dict] = None):
+               chords: bool = False, chord_params: Optional[dict] = None, sections: bool = False, section_params: Optional[dict] = None):
     """`continuous=True` decodes the file's segments through `bsz` slots with continuous batching
     (YourMT3.inference_stream: segments leave at EOS and the next ones enter) instead of fixed batches; same ids.
     `subtask`: for a task-conditioned TaskManager (e.g. "singing_drum_v1"), the sub-task whose task tokens prompt every
@@ -65,7 +66,13 @@ def transcribe(model, audio_info: Union[str, dict, np.ndarray], task_manager: Op
     one marker (FF 06) per run of equal chords into the .mid's conductor track, at the tick of the run's first beat.  `chord_params`:
     chords.DEFAULTS' keys (frames_per_second is the beats').  In every decode mode and with both detokenisers the same bytes.  The info
     dict gains "chords" ([(start_sec, end_sec, name)], e.g. "Am", "G7", "C/E", "N") and "chord_labels" (every beat's 12 q + r, 255 for
-    N).  Off, nothing changes by a byte."""
+    N).  Off, nothing changes by a byte.
+    `sections=True` (it needs `beats=True`) finds the song's form on the device (YourMT3.compile_section_tracker; include/ymt3.h, sections;
+    the rules: yourmt3_amd/sections.py), on the same kept notes and beats, after the bars and with their metre when `bars=True`, and
+    writes one marker (FF 06) per section start into the .mid's conductor track, "[A]", "[B]" and so on, before a chord's marker of
+    the same tick; a silent section gets none.  `section_params`: sections.DEFAULTS' keys (frames_per_second is the beats').  In every
+    decode mode and with both detokenisers the same bytes.  The info dict gains "sections" ([(start_sec, end_sec, name)], "N" for a
+    silent one) and "section_labels" (every beat's label, 255 in a silent section).  Off, nothing changes by a byte."""
     if velocity_params is not None and not velocity:
         raise ValueError("velocity_params without velocity=True")
     if (beat_params is not None or quantize) and not beats:
@@ -78,6 +85,10 @@ def transcribe(model, audio_info: Union[str, dict, np.ndarray], task_manager: Op
         raise ValueError("chords=True without beats=True")
     if chord_params is not None and not chords:
         raise ValueError("chord_params without chords=True")
+    if sections and not beats:
+        raise ValueError("sections=True without beats=True")
+    if section_params is not None and not sections:
+        raise ValueError("section_params without sections=True")
     num_beams = int(num_beams)
     if num_beams < 1:
         raise ValueError(f"num_beams={num_beams} must be >= 1")
@@ -140,14 +151,15 @@ def transcribe(model, audio_info: Union[str, dict, np.ndarray], task_manager: Op
             from .beats import n_frames_of
             from .tracking import Chain, beats_fps, render
             chain = Chain(model, n_frames_of(end_sec, beats_fps(beat_params)), min(BAR_MAX_NOTES, max(1, int(segments.shape[0]) * cfg.n_channels * L)),
-                          beat_params, (bar_params or {}) if bars else None, (chord_params or {}) if chords else None)
+                          beat_params, (bar_params or {}) if bars else None, (chord_params or {}) if chords else None,
+                          (section_params or {}) if sections else None)
         in_place = device_detok and min_confidence is None                   # measured and tracked on the detokeniser's records where they lie
         if device_detok:
             extra = {}
             if in_place and measurer is not None:
                 extra.update(velocity=measurer, audio=segments.view(-1))
             if in_place and chain is not None:
-                extra.update(beats=chain.beats, quantize=quantize, bars=chain.bars, chords=chain.chords)
+                extra.update(beats=chain.beats, quantize=quantize, bars=chain.bars, chords=chain.chords, sections=chain.sections)
             out = task_manager.tokens_to_notes_device(model, tokens, start_secs, end_sec, scores=scores, **extra)
             notes, tracked = out[0], (out[2] if len(out) > 2 else None)
         else:
@@ -242,7 +254,7 @@ class LiveTranscriber:
     audio of its onset has left the device.  estimate_velocities() on the recording puts them onto the session's MIDI file afterwards.
     Beats (transcribe(beats=True)) are not part of a live session either: the tempo path looks at the whole file.  estimate_beats() on the
     session's notes tracks them afterwards.  Bars and key (transcribe(bars=True)) build on the beats and are out of scope here for the same
-    reason: estimate_bars() on the session's notes finds them afterwards; chords (transcribe(chords=True)) likewise, by estimate_chords()."""
+    reason: estimate_bars() on the session's notes finds them afterwards; chords (transcribe(chords=True)) likewise, by estimate_chords(), and sections (transcribe(sections=True)) by estimate_sections()."""
 
     def __init__(self, model, sample_rate: int, n_channels: int = 1, dtype=torch.int16, task_manager: Optional[TaskManager] = None,
                  max_chunk_frames: int = 1 << 16, bsz: Optional[int] = None, max_token_length: Optional[int] = None,
