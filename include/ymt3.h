@@ -922,6 +922,52 @@ int  ymt3_track_sections(ymt3_handle h, ymt3_sections c, const int32_t* beats_de
                          const int32_t* count_dev /* may be NULL */, long long n_frames, int32_t* section_dev, long long section_cap,
                          long long* novelty_dev /* may be NULL */, long long* result_dev /* [8] */, void* stream);
 
+/* ---- hands over note records -------------------------------------------------------------------------------------------------------
+ * A ymt3_hands object gives every note of the piano programs a hand, from the records where ymt3_detokenize left them: at every onset
+ * slice the keyboard is cut at a split point, and the split points of the piece are one cheapest path.  It needs no beats.  The rules
+ * are this project's own, UNVERIFIED against any package; the host specification is split_hands of
+ * yourmt3_amd/hands.py, and every output equals it bit for bit: everything is an integer, and times stay f64 until they are known to
+ * lie inside the frames.  Integer divisions below are floor divisions.
+ *
+ * Parameters (ymt3_hands_create refuses, YMT3_ERR_ARG, what is outside): frames_per_second finite and > 0; slice_frames in [1, 64];
+ * span in [1, 127]; cut_min in [0, 127]; middle and mid_free in [0, 128]; every w_* in [0, 1024]; rest_slots in [1, 2^20];
+ * 1 <= n_programs <= 256, drum_program in [0, n_programs); 0 <= program_lo <= program_hi < n_programs; max_frames in [1, 2^20];
+ * max_notes in [1, 2^20].
+ *   selected    a record the note rule counts (ymt3_note_metrics), not a drum, program_lo <= program <= program_hi, whose span
+ *               [F(on), max(F(off), F(on) + 1)) clipped to [0, n_frames) is not empty; its slot q = (the span's first frame) / slice_frames.
+ *   slices      the occupied slots in ascending order, t = 0 .. T-1, Q_t the slot, P_t the SET of pitches selected into it.
+ *   states      s in [0, 128]: L = {p in P_t : p < s}, R = {p in P_t : p >= s}; span(X) = max X - min X, 0 for an empty X;
+ *               class_t(s) = 0 if L is empty, 2 if R is empty, 1 otherwise.
+ *   emission    e_t(s) = w_span (max(0, span(L) - span) + max(0, span(R) - span)) + cut_t(s) + w_mid max(0, |s - middle| - mid_free);
+ *               cut_t(s) = w_cut max(0, cut_min - (min R - max L)) + w_centre (|2 s - (max L + min R + 1)| / 2) where class_t(s) = 1, else 0.
+ *   transition  x_t(s', s) = 0 if Q_t - Q_{t-1} >= rest_slots, else w_move |s - s'| + w_switch [{class_{t-1}(s'), class_t(s)} = {0, 2}].
+ *   path        C_0 = e_0; C_t(s) = e_t(s) + min over s' of (C_{t-1}(s') + x_t(s', s)), back_t(s) the SMALLEST minimiser; s_{T-1} the
+ *               smallest minimiser of C_{T-1}, s_{t-1} = back_t(s_t); total = min C_{T-1} (64 bits; e <= 454 656 and x <= 132 096, so
+ *               a step's costs lie within 2^20 of each other).
+ * ymt3_split_hands: notes_dev / n_notes / count_dev as ymt3_track_beats takes them, n_notes at most the object's max_notes; n_frames
+ * in [1, max_frames].  hand_dev[i] for i below the live count: 1 (right) if the record's pitch >= s_t of its slice, 0 (left) otherwise,
+ * 255 if it is not selected; the rest is left alone.  split_dev[t] = 256 Q_t + s_t for t < T, or NULL; max_slices, its length, is at
+ * least min(n_notes, ceil(n_frames / slice_frames)).  result_dev[8]: T, selected records, left records, right records, total, skipped
+ * records (those the note rule does not count), hand-overs on the path (the t >= 1 with Q_t - Q_{t-1} < rest_slots and
+ * {class_{t-1}(s_{t-1}), class_t(s_t)} = {0, 2}), 0.  With T = 0 every live hand is 255 and result_dev = {0, 0, 0, 0, 0, skipped, 0, 0}.
+ * Asynchronous on `stream`, allocates nothing, reads nothing back (T stays on the device) and leaves the handle's decode state alone.
+ * The object's scratch (20 bytes per slot of ceil(max_frames / slice_frames), 153 bytes per slice of min(max_notes, slots)) is used by
+ * the call: calls on one object are ordered by their stream.  YMT3_ERR_ARG, with handle and object still usable, for n_notes outside
+ * [0, max_notes], a NULL notes_dev or hand_dev with n_notes > 0, a misaligned notes_dev, count_dev, split_dev or result_dev, n_frames
+ * outside [1, max_frames], max_slices too small for a split_dev that is given, a NULL result_dev.  Sounding notes are not held across
+ * slices, there are two voices and no more, and only the program range is split. */
+typedef struct ymt3_hand_params {
+    double  frames_per_second;
+    int32_t slice_frames, program_lo, program_hi, span, w_span, cut_min, w_cut, w_centre, middle, mid_free, w_mid, w_move, w_switch, rest_slots,
+            n_programs, drum_program;
+} ymt3_hand_params;                                                         /* 72 bytes, no padding */
+typedef struct ymt3_hands_s* ymt3_hands;
+int  ymt3_hands_create(ymt3_handle h, const ymt3_hand_params* params, long long max_frames, long long max_notes, ymt3_hands* out);
+void ymt3_hands_destroy(ymt3_hands c);
+int  ymt3_split_hands(ymt3_handle h, ymt3_hands c, const void* notes_dev, long long n_notes, const int32_t* count_dev /* may be NULL */,
+                      long long n_frames, uint8_t* hand_dev, int32_t* split_dev /* may be NULL */, long long max_slices,
+                      long long* result_dev /* [8] */, void* stream);
+
 /* Measurement hook (bench.py `roofline`): decode eagerly (no graph) and bracket every kernel launch of
  * every `stride`-th step (positions stride/2, 3*stride/2, ...) with HIP events on `stream`; synchronises the stream before returning.
  * Classes: 0 qkv+cache GEMM, 1 self-attention, 2 self O-proj, 3 cross Q GEMM, 4 cross-attention,

@@ -3,7 +3,7 @@
 
 __all__ = ["YMT3Config", "YourMT3", "TaskManager", "transcribe", "score_notes", "evaluate", "note_metrics", "NoteMetrics", "piano_roll", "frame_metrics",
            "FrameMetricCounts", "PianoRoll", "baseline_config", "LiveTranscriber", "NoteStream", "dtw_align", "warp_notes", "Alignment", "Aligner",
-           "align", "note_velocities", "NoteVelocity", "estimate_velocities", "track_beats", "beat_positions", "BeatTracker", "estimate_beats", "track_bars", "BarTracker", "estimate_bars", "track_chords", "ChordTracker", "estimate_chords", "track_sections", "SectionTracker", "estimate_sections"]
+           "align", "note_velocities", "NoteVelocity", "estimate_velocities", "track_beats", "beat_positions", "BeatTracker", "estimate_beats", "track_bars", "BarTracker", "estimate_bars", "track_chords", "ChordTracker", "estimate_chords", "track_sections", "SectionTracker", "estimate_sections", "split_hands", "HandSplitter", "estimate_hands"]
 
 
 def __getattr__(name):
@@ -67,4 +67,7 @@ def __getattr__(name):
     if name in ("track_sections", "SectionTracker", "estimate_sections"):
         from . import sections
         return getattr(sections, name)
+    if name in ("split_hands", "HandSplitter", "estimate_hands"):
+        from . import hands
+        return getattr(hands, name)
     raise AttributeError(name)

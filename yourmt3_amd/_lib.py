@@ -38,6 +38,7 @@ SYMBOLS = [
     "ymt3_bars_create", "ymt3_bars_destroy", "ymt3_track_bars",
     "ymt3_chords_create", "ymt3_chords_destroy", "ymt3_track_chords",
     "ymt3_sections_create", "ymt3_sections_destroy", "ymt3_track_sections",
+    "ymt3_hands_create", "ymt3_hands_destroy", "ymt3_split_hands",
     "ymt3_test_gemm_ex", "ymt3_test_rmsnorm", "ymt3_test_enc_attention", "ymt3_test_seq_attention", "ymt3_test_spec_embed",
     "ymt3_test_dec_gemm", "ymt3_test_dec_attention", "ymt3_test_mc_cross_attention", "ymt3_test_moe_stage",
     "ymt3_test_seq_embed", "ymt3_test_dec_seq_attention", "ymt3_test_seq_lm_head",
@@ -105,6 +106,13 @@ class SectionParams(ctypes.Structure):
     _fields_ = [("frames_per_second", ctypes.c_double)] + [
         (n, ctypes.c_int32) for n in ("near_div", "n_programs", "drum_program", "context", "kernel_beats", "min_len", "peak_div", "same_dist", "len_num",
                                       "max_sections")]
+
+
+class HandParams(ctypes.Structure):
+    """ymt3_hand_params of include/ymt3.h"""
+    _fields_ = [("frames_per_second", ctypes.c_double)] + [
+        (n, ctypes.c_int32) for n in ("slice_frames", "program_lo", "program_hi", "span", "w_span", "cut_min", "w_cut", "w_centre", "middle", "mid_free",
+                                      "w_mid", "w_move", "w_switch", "rest_slots", "n_programs", "drum_program")]
 
 
 class SeqAttnArgs(ctypes.Structure):
@@ -348,6 +356,12 @@ def load() -> ctypes.CDLL:
     lib.ymt3_sections_destroy.restype = None
     lib.ymt3_track_sections.argtypes = [vp, vp, vp, vp, vp, vp, ll, vp, ll, vp, ll, vp, vp, vp]
     lib.ymt3_track_sections.restype = i32
+    lib.ymt3_hands_create.argtypes = [vp, ctypes.POINTER(HandParams), ll, ll, ctypes.POINTER(vp)]
+    lib.ymt3_hands_create.restype = i32
+    lib.ymt3_hands_destroy.argtypes = [vp]
+    lib.ymt3_hands_destroy.restype = None
+    lib.ymt3_split_hands.argtypes = [vp, vp, vp, ll, vp, ll, vp, vp, ll, vp, vp]
+    lib.ymt3_split_hands.restype = i32
     f32 = ctypes.c_float
     lib.ymt3_test_gemm_ex.argtypes = [vp, i32, vp, vp, vp, vp, i32, i32, i32, i32, i32, i32, i32, i32, i32, vp]
     lib.ymt3_test_gemm_ex.restype = i32

@@ -347,6 +347,36 @@ struct SectionArgs {
 };
 int launch_track_sections(const SectionArgs& a, hipStream_t stream);
 
+// ---------------------------------------------------------------- hands over note records (hands.hip; include/ymt3.h, hands)
+constexpr int HAND_STATES = 129;                                        // the split points 0 .. 128
+constexpr int HAND_BACK_ROW = 132;                                      // bytes per slice of back-pointers: one per state, padded to words
+constexpr int HAND_ACC_WORDS = 4;                                       // T, s_{T-1}, two spare
+constexpr int HAND_MAX_SLICE_FRAMES = 64, HAND_MAX_WEIGHT = 1024;
+constexpr long long HAND_MAX_REST = 1LL << 20;
+__host__ __device__ inline long long hand_slots(long long n_frames, int slice_frames) { return (n_frames + slice_frames - 1) / slice_frames; }
+struct HandArgs {
+    double frames_per_second;
+    int n_programs, drum_program;
+    int slice_frames, program_lo, program_hi, span, w_span, cut_min, w_cut, w_centre, middle, mid_free, w_mid, w_move, w_switch, rest_slots;
+    const DetokNote* notes;               // [n]
+    long long n;
+    const int32_t* count;                 // device count (or null): min(n, max(*count, 0)) records are live
+    long long n_frames;
+    long long n_slots;                    // hand_slots(n_frames, slice_frames): at most the object's slots
+    long long max_slices;                 // the object's: min(max_notes, hand_slots(max_frames)) slices fit the scratch below
+    uint4* sets;                          // [the object's slots] 128 pitch bits per slot
+    int32_t* slice_of;                    // [the object's slots] slot -> t, written for the occupied slots
+    uint4* cset;                          // [max_slices] P_t
+    int32_t* slot_of;                     // [max_slices] Q_t
+    unsigned char* back;                  // [max_slices][HAND_BACK_ROW] back_t(s)
+    unsigned char* cut;                   // [max_slices] s_t
+    unsigned long long* acc;              // [HAND_ACC_WORDS]
+    uint8_t* hand;                        // [n]: the live ones are written
+    int32_t* split;                       // [>= min(n, n_slots)] or null: the first T are written
+    long long* result;                    // [8]: slices, selected, left, right, total, skipped, hand-overs, 0
+};
+int launch_split_hands(const HandArgs& a, hipStream_t stream);
+
 // ---------------------------------------------------------------- dense GEMM (gemm.hip)
 // C[M][N] (+)= A[M][K] (bf16, row stride lda) * W[N][K]^T (bf16, row stride ldw), fp32 accumulate.
 enum GemmEpilogue {

@@ -1,6 +1,6 @@
 // The note-side objects of the C ABI (include/ymt3.h): detokeniser and its incremental state, tokeniser, note metrics, piano roll / frame
-// metrics, aligner, note velocities, beat tracker, bar tracker, chord tracker, section tracker.  Host logic only: argument checks, scratch, and the launches of detok.hip, tok.hip, metrics.hip, roll.hip,
-// align.hip, velocity.hip, beats.hip, bars.hip, chords.hip and sections.hip.  Of the handle they need the device and the configuration (runtime.h).  What they have in common is written once, at the top: the
+// metrics, aligner, note velocities, beat tracker, bar tracker, chord tracker, section tracker, hand splitter.  Host logic only: argument checks, scratch, and the launches of detok.hip, tok.hip, metrics.hip, roll.hip,
+// align.hip, velocity.hip, beats.hip, bars.hip, chords.hip, sections.hip and hands.hip.  Of the handle they need the device and the configuration (runtime.h).  What they have in common is written once, at the top: the
 // create prologue, the owner check, the program and record-array checks, and the scratch list that both *_create and *_destroy walk.
 #include <algorithm>
 #include <cmath>
@@ -939,5 +939,77 @@ extern "C" int ymt3_track_sections(ymt3_handle h, ymt3_sections c, const int32_t
     a.chroma = c->chroma; a.f = c->f; a.nov = c->nov; a.peak = c->peak; a.acc = c->acc; a.starts = c->starts; a.same = c->same;
     a.section = section_dev; a.novelty = novelty_dev; a.result = result_dev;
     LAUNCH(launch_track_sections(a, static_cast<hipStream_t>(stream)));
+    return YMT3_OK;
+}
+
+// ---------------------------------------------------------------- hands over note records (include/ymt3.h)
+struct ymt3_hands_s {
+    ymt3_handle owner;
+    int device;
+    ymt3_hand_params p;
+    long long max_frames, max_notes, slots, max_slices;     // slots = hand_slots(max_frames); max_slices = min(max_notes, slots)
+    uint4* sets = nullptr;                  // [slots]
+    int32_t* slice_of = nullptr;            // [slots]
+    uint4* cset = nullptr;                  // [max_slices]
+    int32_t* slot_of = nullptr;             // [max_slices]
+    unsigned char* back = nullptr;          // [max_slices][HAND_BACK_ROW]
+    unsigned char* cut = nullptr;           // [max_slices]
+    unsigned long long* acc = nullptr;      // [HAND_ACC_WORDS]
+};
+
+static std::vector<Slot> slots(ymt3_hands c) {
+    const size_t S = (size_t)c->slots, T = (size_t)c->max_slices;
+    return {slot(&c->sets, S * sizeof(uint4)), slot(&c->slice_of, S * sizeof(int32_t)), slot(&c->cset, T * sizeof(uint4)),
+            slot(&c->slot_of, T * sizeof(int32_t)), slot(&c->back, T * HAND_BACK_ROW), slot(&c->cut, T),
+            slot(&c->acc, HAND_ACC_WORDS * sizeof(unsigned long long))};
+}
+extern "C" void ymt3_hands_destroy(ymt3_hands c) { destroy_object(c); }
+
+extern "C" int ymt3_hands_create(ymt3_handle h, const ymt3_hand_params* params, long long max_frames, long long max_notes, ymt3_hands* out) {
+    if (const int rc = create_prologue(reinterpret_cast<void**>(out), h, params, "params")) return rc;
+    const ymt3_hand_params& p = *params;
+    if (!std::isfinite(p.frames_per_second) || p.frames_per_second <= 0) FAIL(YMT3_ERR_ARG, "frames_per_second=%g must be finite and > 0", p.frames_per_second);
+    const struct { const char* name; int v, lo, hi; } ranged[] = {
+        {"slice_frames", p.slice_frames, 1, HAND_MAX_SLICE_FRAMES}, {"span", p.span, 1, 127}, {"w_span", p.w_span, 0, HAND_MAX_WEIGHT}, {"cut_min", p.cut_min, 0, 127},
+        {"w_cut", p.w_cut, 0, HAND_MAX_WEIGHT}, {"w_centre", p.w_centre, 0, HAND_MAX_WEIGHT}, {"middle", p.middle, 0, 128}, {"mid_free", p.mid_free, 0, 128},
+        {"w_mid", p.w_mid, 0, HAND_MAX_WEIGHT}, {"w_move", p.w_move, 0, HAND_MAX_WEIGHT}, {"w_switch", p.w_switch, 0, HAND_MAX_WEIGHT},
+        {"rest_slots", p.rest_slots, 1, (int)HAND_MAX_REST}};
+    for (const auto& q : ranged)
+        if (q.v < q.lo || q.v > q.hi) FAIL(YMT3_ERR_ARG, "%s=%d outside [%d, %d]", q.name, q.v, q.lo, q.hi);
+    if (const int rc = check_programs(p.n_programs, p.drum_program, BAR_MAX_PROGRAMS, "")) return rc;
+    if (p.program_lo < 0 || p.program_lo > p.program_hi || p.program_hi >= p.n_programs)
+        FAIL(YMT3_ERR_ARG, "program_lo=%d, program_hi=%d must satisfy 0 <= program_lo <= program_hi < n_programs=%d", p.program_lo, p.program_hi, p.n_programs);
+    if (max_frames < 1 || max_frames > BAR_MAX_FRAMES) FAIL(YMT3_ERR_ARG, "max_frames=%lld outside [1, %lld]", max_frames, BAR_MAX_FRAMES);
+    if (max_notes < 1 || max_notes > BAR_MAX_NOTES) FAIL(YMT3_ERR_ARG, "max_notes=%lld outside [1, %lld]", max_notes, BAR_MAX_NOTES);
+    HIP_TRY(hipSetDevice(handle_device(h)));
+    const long long n_slots = hand_slots(max_frames, p.slice_frames);
+    ymt3_hands c = new ymt3_hands_s{h, handle_device(h), p, max_frames, max_notes, n_slots, std::min(max_notes, n_slots)};
+    return allocate_object(c, slots(c), "hand splitter scratch", out);
+}
+
+extern "C" int ymt3_split_hands(ymt3_handle h, ymt3_hands c, const void* notes_dev, long long n_notes, const int32_t* count_dev, long long n_frames,
+                                uint8_t* hand_dev, int32_t* split_dev, long long max_slices, long long* result_dev, void* stream) {
+    if (const int rc = check_owner(h, c, "hand splitter")) return rc;
+    if (const int rc = check_count("n_notes", n_notes, c->max_notes, "max_notes")) return rc;
+    if (const int rc = check_record_ptr("notes_dev", notes_dev, n_notes)) return rc;
+    if (reinterpret_cast<uintptr_t>(count_dev) % 4) FAIL(YMT3_ERR_ARG, "count_dev is not aligned to 4 bytes");
+    if (n_frames < 1 || n_frames > c->max_frames) FAIL(YMT3_ERR_ARG, "n_frames=%lld outside [1, max_frames=%lld]", n_frames, c->max_frames);
+    if (n_notes && !hand_dev) FAIL(YMT3_ERR_ARG, "hand_dev is NULL");
+    if (reinterpret_cast<uintptr_t>(split_dev) % 4) FAIL(YMT3_ERR_ARG, "split_dev is not aligned to 4 bytes");
+    const long long n_slots = hand_slots(n_frames, c->p.slice_frames), need = std::min(n_notes, n_slots);
+    if (split_dev && max_slices < need) FAIL(YMT3_ERR_ARG, "max_slices=%lld below min(n_notes, ceil(n_frames / slice_frames)) = %lld", max_slices, need);
+    if (!result_dev) FAIL(YMT3_ERR_ARG, "result_dev is NULL");
+    if (reinterpret_cast<uintptr_t>(result_dev) % 8) FAIL(YMT3_ERR_ARG, "result_dev is not aligned to 8 bytes");
+    HIP_TRY(hipSetDevice(c->device));
+    HandArgs a{};
+    a.frames_per_second = c->p.frames_per_second; a.n_programs = c->p.n_programs; a.drum_program = c->p.drum_program;
+    a.slice_frames = c->p.slice_frames; a.program_lo = c->p.program_lo; a.program_hi = c->p.program_hi; a.span = c->p.span; a.w_span = c->p.w_span;
+    a.cut_min = c->p.cut_min; a.w_cut = c->p.w_cut; a.w_centre = c->p.w_centre; a.middle = c->p.middle; a.mid_free = c->p.mid_free; a.w_mid = c->p.w_mid;
+    a.w_move = c->p.w_move; a.w_switch = c->p.w_switch; a.rest_slots = c->p.rest_slots;
+    a.notes = static_cast<const DetokNote*>(notes_dev); a.n = n_notes; a.count = n_notes ? count_dev : nullptr; a.n_frames = n_frames;
+    a.n_slots = n_slots; a.max_slices = c->max_slices;
+    a.sets = c->sets; a.slice_of = c->slice_of; a.cset = c->cset; a.slot_of = c->slot_of; a.back = c->back; a.cut = c->cut; a.acc = c->acc;
+    a.hand = hand_dev; a.split = split_dev; a.result = result_dev;
+    LAUNCH(launch_split_hands(a, static_cast<hipStream_t>(stream)));
     return YMT3_OK;
 }

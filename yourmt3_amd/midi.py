@@ -67,15 +67,28 @@ def _fit_melodic_channels(by_prog: Dict[int, List[Note]]) -> Dict[int, List[Note
     return out
 
 
-def notes_to_midi_bytes(notes: Sequence[Note]) -> bytes:
-    return _smf_bytes(notes, {id(n): (_ticks(n.onset), _ticks(n.offset)) for n in notes}, [(0, TEMPO_US)])
+HAND_TRACKS = ((1, b"R.H."), (0, b"L.H."))  # (hand, track name) in the order of a split program's tracks: hands.RIGHT, hands.LEFT
 
 
-def _smf_bytes(notes: Sequence[Note], ticks: Dict[int, tuple], tempos, conductor_events=()) -> bytes:
+def notes_to_midi_bytes(notes: Sequence[Note], hands=None) -> bytes:
+    """`hands`: None, or every note's hand in the notes' order (hands.split_hands: 1 right, 0 left, 255 none): a melodic program with a
+    note of hand 0 or 1 is written as two tracks on its one channel (_smf_bytes).  Without them the bytes are the same as before."""
+    return _smf_bytes(notes, {id(n): (_ticks(n.onset), _ticks(n.offset)) for n in notes}, [(0, TEMPO_US)], hands=hands)
+
+
+def _smf_bytes(notes: Sequence[Note], ticks: Dict[int, tuple], tempos, conductor_events=(), hands=None) -> bytes:
     """The file of `notes`: ticks[id(note)] = (onset tick, offset tick); `tempos` = [(tick, microseconds per beat)], ascending;
     `conductor_events` = [(tick, the bytes of a meta event)], ascending, merged into the conductor track before the tempo of the same tick.  The
     ticks are keyed by the note objects' identity: everything below, _fit_melodic_channels included, regroups the SAME objects and never
-    copies a note (equal notes may carry different ticks, so the notes' values cannot be the key)."""
+    copies a note (equal notes may carry different ticks, so the notes' values cannot be the key).  `hands`: None, or a hand per note in
+    the notes' order, keyed by identity in the same way.  A melodic program with any note of hand 0 or 1 becomes two tracks on its one
+    channel, the right hand's and then the left's, each opening with its name (FF 03, "R.H." / "L.H."), the program change in the first
+    of them only.  The one-voice-per-(channel, pitch) rule runs over the program's notes together, before they are divided: a span
+    belongs to the hand of the note that opened it, a note of hand 255 in such a program goes with the right, a hand without a span
+    gets no track."""
+    if hands is not None and len(hands) != len(notes):
+        raise ValueError(f"{len(notes)} notes but {len(hands)} hands")
+    hand_of = {} if hands is None else {id(n): int(h) for n, h in zip(notes, hands)}
     by_prog: Dict[int, List[Note]] = {}
     for n in notes:
         by_prog.setdefault(DRUM_PROGRAM if n.is_drum else n.program, []).append(n)
@@ -104,21 +117,31 @@ def _smf_bytes(notes: Sequence[Note], ticks: Dict[int, tuple], tempos, conductor
                 continue
             if sp and sp[-1][1] > on:
                 sp[-1][1] = on
-            sp.append([on, off, n.velocity])
-        for pitch, sp in spans.items():
-            for on, off, vel in sp:
-                ev.append((on, 1, pitch, vel))
-                ev.append((off, 0, pitch, 0))
-        ev.sort(key=lambda e: (e[0], e[1]))            # offsets before onsets at the same tick
-        body = bytearray()
-        if prog != DRUM_PROGRAM:
-            body += b"\x00" + bytes([0xC0 | ch, gm_program(prog)])
-        last = 0
-        for tick, on, pitch, vel in ev:
-            body += _vlq(tick - last) + bytes([(0x90 if on else 0x80) | ch, pitch & 0x7F, vel & 0x7F])
-            last = tick
-        body += b"\x00\xff\x2f\x00"
-        tracks.append(bytes(body))
+            sp.append([on, off, n.velocity, 0 if hand_of.get(id(n)) == 0 else 1])
+        split = prog != DRUM_PROGRAM and any(hand_of.get(id(n)) in (0, 1) for n in ns)
+        first = True
+        for hand, name in HAND_TRACKS if split else ((None, b""),):
+            ev = []
+            for pitch, sp in spans.items():
+                for on, off, vel, h in sp:
+                    if hand is None or h == hand:
+                        ev.append((on, 1, pitch, vel))
+                        ev.append((off, 0, pitch, 0))
+            if split and not ev:
+                continue
+            ev.sort(key=lambda e: (e[0], e[1]))        # offsets before onsets at the same tick
+            body = bytearray()
+            if split:
+                body += b"\x00\xff\x03" + bytes([len(name)]) + name
+            if prog != DRUM_PROGRAM and first:
+                body += b"\x00" + bytes([0xC0 | ch, gm_program(prog)])
+            first = False
+            last = 0
+            for tick, on, pitch, vel in ev:
+                body += _vlq(tick - last) + bytes([(0x90 if on else 0x80) | ch, pitch & 0x7F, vel & 0x7F])
+                last = tick
+            body += b"\x00\xff\x2f\x00"
+            tracks.append(bytes(body))
     out = b"MThd" + struct.pack(">IHHH", 6, 1, len(tracks), TICKS_PER_BEAT)
     for t in tracks:
         out += b"MTrk" + struct.pack(">I", len(t)) + t
@@ -136,48 +159,57 @@ def _marker_events(markers):
     return out
 
 
-def notes_to_midi_bytes_on_beats(notes: Sequence[Note], ticks, beats, frames_per_second: float = 100.0, markers=()) -> bytes:
+def notes_to_midi_bytes_on_beats(notes: Sequence[Note], ticks, beats, frames_per_second: float = 100.0, markers=(), hands=None) -> bytes:
     """notes_to_midi_bytes with a tempo map: `ticks` (n, 2), every note's onset and offset tick at 480 per beat (beats.beat_positions or
     BeatTracker.positions, in the notes' order), `beats` the beats' frames at `frames_per_second`.  The tempo track starts with the first
     interval's tempo at tick 0 and sets interval i's, rint((b[i+1] - b[i]) / fps 1e6) microseconds per beat, at tick (n0 + i) 480
     (beats.tempo_map); played back, the file keeps the performance's timing, after a lead-in of beats.lead_sec.  A note without ticks
     (-1: a NaN time) is left out.  With fewer than two beats there is no map: the bytes are notes_to_midi_bytes'.  `markers` = [(tick,
     text)], ascending (chords.chord_markers: a chord symbol at its first beat), go into the conductor track as FF 06 events; without
-    them the bytes are the same as before."""
+    them the bytes are the same as before.  `hands` as notes_to_midi_bytes takes them."""
     from .beats import tempo_map
     notes = list(notes)
     tempos = tempo_map(beats, frames_per_second)
     if not tempos:
-        return notes_to_midi_bytes(notes)
+        return notes_to_midi_bytes(notes, hands)
     pairs = [(int(a), int(b)) for a, b in ticks]
     if len(pairs) != len(notes):
         raise ValueError(f"{len(notes)} notes but {len(pairs)} tick pairs")
-    kept = [(n, t) for n, t in zip(notes, pairs) if t[0] >= 0 and (t[1] >= 0 or n.is_drum)]
-    return _smf_bytes([n for n, _ in kept], {id(n): t for n, t in kept}, tempos, _marker_events(markers))
+    kept, kept_hands = _with_ticks(notes, pairs, hands)
+    return _smf_bytes([n for n, _ in kept], {id(n): t for n, t in kept}, tempos, _marker_events(markers), kept_hands)
 
 
-def notes_to_midi_bytes_on_bars(notes: Sequence[Note], ticks, beats, metre, key: int = -1, frames_per_second: float = 100.0, markers=()) -> bytes:
+def _with_ticks(notes, pairs, hands):
+    """the notes that have ticks with them, and those notes' hands (None without hands)"""
+    if hands is not None and len(hands) != len(notes):
+        raise ValueError(f"{len(notes)} notes but {len(hands)} hands")
+    keep = [t[0] >= 0 and (t[1] >= 0 or n.is_drum) for n, t in zip(notes, pairs)]
+    kept = [(n, t) for n, t, k in zip(notes, pairs, keep) if k]
+    return kept, None if hands is None else [h for h, k in zip(hands, keep) if k]
+
+
+def notes_to_midi_bytes_on_bars(notes: Sequence[Note], ticks, beats, metre, key: int = -1, frames_per_second: float = 100.0, markers=(), hands=None) -> bytes:
     """notes_to_midi_bytes_on_beats with bar lines and a key: `metre` (256 m + k of every beat) and `key` as bars.track_bars or
     BarTracker give them.  The conductor track gains one FF 58 04 nn 02 18 08 (nn/4) per entry of bars.time_signatures and one
     FF 59 02 sf mi at tick 0 (bars.key_signature; none for key -1), in tick order with the tempo events.  Without downbeats (fewer
     than two beats among them) the bytes are exactly notes_to_midi_bytes_on_beats'.  `markers` as there: at one tick after the time and
-    key signatures and before the tempo."""
+    key signatures and before the tempo.  `hands` as notes_to_midi_bytes takes them."""
     from .bars import key_signature, time_signatures
     from .beats import tempo_map
     notes = list(notes)
     signatures = time_signatures(metre, beats)
     tempos = tempo_map(beats, frames_per_second)
     if not signatures or not tempos:
-        return notes_to_midi_bytes_on_beats(notes, ticks, beats, frames_per_second, markers)
+        return notes_to_midi_bytes_on_beats(notes, ticks, beats, frames_per_second, markers, hands)
     pairs = [(int(a), int(b)) for a, b in ticks]
     if len(pairs) != len(notes):
         raise ValueError(f"{len(notes)} notes but {len(pairs)} tick pairs")
-    kept = [(n, t) for n, t in zip(notes, pairs) if t[0] >= 0 and (t[1] >= 0 or n.is_drum)]
+    kept, kept_hands = _with_ticks(notes, pairs, hands)
     events = [(tick, b"\xff\x58\x04" + bytes([nn, 2, 24, 8])) for tick, nn in signatures]
     if int(key) >= 0:
         sf, mi = key_signature(key)
         events.insert(1 if events[0][0] == 0 else 0, (0, b"\xff\x59\x02" + bytes([sf & 0xFF, mi])))
-    return _smf_bytes([n for n, _ in kept], {id(n): t for n, t in kept}, tempos, events + _marker_events(markers))
+    return _smf_bytes([n for n, _ in kept], {id(n): t for n, t in kept}, tempos, events + _marker_events(markers), kept_hands)
 
 
 def write_midi(notes: Sequence[Note], path: str) -> str:
@@ -192,10 +224,11 @@ def read_midi_notes(data: bytes) -> List[Note]:
     _, fmt, ntrk, tpb = struct.unpack(">IHHH", data[4:14])
     pos, notes = 14, []
     sec = lambda t: t * TEMPO_US / (tpb * 1e6)
+    progs: Dict[int, int] = {}                          # by channel: a split program's second track has no program change of its own
     for _ in range(ntrk):
         assert data[pos:pos + 4] == b"MTrk"
         ln = struct.unpack(">I", data[pos + 4:pos + 8])[0]
-        p, end, tick, prog, open_ = pos + 8, pos + 8 + ln, 0, 0, {}
+        p, end, tick, open_ = pos + 8, pos + 8 + ln, 0, {}
         while p < end:
             d = 0
             while True:
@@ -208,7 +241,7 @@ def read_midi_notes(data: bytes) -> List[Note]:
             if st == 0xFF:
                 ml = data[p + 1]; p += 2 + ml
             elif st & 0xF0 == 0xC0:
-                prog = data[p]; p += 1
+                progs[st & 0x0F] = data[p]; p += 1
             elif st & 0xF0 in (0x90, 0x80):
                 pitch, vel = data[p], data[p + 1]; p += 2
                 drum = (st & 0x0F) == 9
@@ -216,7 +249,7 @@ def read_midi_notes(data: bytes) -> List[Note]:
                     open_[pitch] = (tick, vel)
                 elif pitch in open_:
                     on, v = open_.pop(pitch)
-                    notes.append(Note(sec(on), sec(tick), drum, DRUM_PROGRAM if drum else prog, pitch, v))
+                    notes.append(Note(sec(on), sec(tick), drum, DRUM_PROGRAM if drum else progs.get(st & 0x0F, 0), pitch, v))
         pos = end
     return sorted(notes)
 
@@ -270,7 +303,7 @@ def read_midi_on_beats(data: bytes):
             if payload[0] == 0x51:
                 tempos.append((tick, int.from_bytes(payload[1:], "big")))
         elif st & 0xF0 == 0xC0:
-            prog[track] = payload[0]
+            prog[st & 0x0F] = payload[0]                # by channel: a split program's second track has no program change of its own
         elif st & 0xF0 in (0x90, 0x80):
             pitch, vel = payload[0], payload[1]
             drum = (st & 0x0F) == 9
@@ -278,7 +311,7 @@ def read_midi_on_beats(data: bytes):
                 open_[track, pitch] = (tick, vel)
             elif (track, pitch) in open_:
                 on, v = open_.pop((track, pitch))
-                raw.append((on, tick, drum, DRUM_PROGRAM if drum else prog.get(track, 0), pitch, v))
+                raw.append((on, tick, drum, DRUM_PROGRAM if drum else prog.get(st & 0x0F, 0), pitch, v))
     tempos = sorted(tempos) or [(0, TEMPO_US)]
     if tempos[0][0] != 0:
         tempos.insert(0, (0, TEMPO_US))
@@ -314,3 +347,49 @@ def read_midi_on_bars(data: bytes):
 def read_midi_markers(data: bytes):
     """the markers (FF 06) of a file, as the writers on the beats and on the bars write them -> [(tick, text)]"""
     return [(tick, bytes(payload[1:]).decode("utf-8")) for _, tick, st, payload in _track_events(data)[1] if st == 0xFF and payload[0] == 0x06]
+
+
+def read_midi_track_names(data: bytes) -> List[str]:
+    """the track names (FF 03) of a file, track by track"""
+    return [bytes(payload[1:]).decode("utf-8") for _, _, st, payload in _track_events(data)[1] if st == 0xFF and payload[0] == 0x03]
+
+
+def read_midi_open_notes(data: bytes) -> List[int]:
+    """per track, the note-ons and note-offs that do not pair up inside it: a note-on of a pitch that is sounding, a note-off of one that
+    is not, and what still sounds at the track's end.  All zero in a file of this module's writers."""
+    tpb, events = _track_events(data)
+    bad: Dict[int, int] = {}
+    sounding: Dict[int, set] = {}
+    for track, _, st, payload in events:
+        bad.setdefault(track, 0)
+        if st & 0xF0 in (0x90, 0x80):
+            on = st & 0xF0 == 0x90 and payload[1] > 0
+            held = sounding.setdefault(track, set())
+            if on == (payload[0] in held):
+                bad[track] += 1
+            (held.add if on else held.discard)(payload[0])
+    return [bad[t] + len(sounding.get(t, ())) for t in sorted(bad)]
+
+
+def read_midi_hands(data: bytes):
+    """Parse what notes_to_midi_bytes writes with `hands` -> [(note, hand)], sorted: the notes as read_midi_notes reads them, hand 1 for a
+    track named "R.H.", 0 for "L.H.", 255 for any other track."""
+    names = {name.decode(): hand for hand, name in HAND_TRACKS}
+    tpb, events = _track_events(data)
+    sec = lambda t: t * TEMPO_US / (tpb * 1e6)
+    out, progs, hand, open_ = [], {}, {}, {}
+    for track, tick, st, payload in events:
+        if st == 0xFF:
+            if payload[0] == 0x03:
+                hand[track] = names.get(bytes(payload[1:]).decode("utf-8"), 255)
+        elif st & 0xF0 == 0xC0:
+            progs[st & 0x0F] = payload[0]
+        elif st & 0xF0 in (0x90, 0x80):
+            pitch, vel = payload[0], payload[1]
+            drum = (st & 0x0F) == 9
+            if st & 0xF0 == 0x90 and vel > 0:
+                open_[track, pitch] = (tick, vel)
+            elif (track, pitch) in open_:
+                on, v = open_.pop((track, pitch))
+                out.append((Note(sec(on), sec(tick), drum, DRUM_PROGRAM if drum else progs.get(st & 0x0F, 0), pitch, v), hand.get(track, 255)))
+    return sorted(out)

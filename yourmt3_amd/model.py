@@ -627,6 +627,13 @@ class YourMT3:
         from .sections import SectionTracker                            # (not a name of this module: sections.py builds on it)
         return SectionTracker(self, max_beats, max_notes, **params)
 
+    def compile_hand_splitter(self, max_frames: int, max_notes: int, **params):
+        """The device hand splitter (include/ymt3.h, hands; the rules and the host specification: yourmt3_amd/hands.py) with scratch for
+        `max_frames` frames and calls of up to `max_notes` records.  `params`: hands.DEFAULTS' keys.  -> a hands.HandSplitter, closed
+        with the model."""
+        from .hands import HandSplitter                                 # (not a name of this module: hands.py builds on it)
+        return HandSplitter(self, max_frames, max_notes, **params)
+
     def compile_ingest_stream(self, sample_rate: int, n_channels: int = 1, dtype=torch.int16, max_chunk_frames: int = 1 << 16) -> IngestStream:
         """Streaming form of ingest() (include/ymt3.h, streaming ingest) for `n_channels`-channel PCM of `dtype` (int16 or float32) at
         `sample_rate`, pushed in chunks of at most `max_chunk_frames` frames."""

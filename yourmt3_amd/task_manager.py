@@ -558,7 +558,7 @@ class TaskManager:
 
     def tokens_to_notes_device(self, model, tokens, start_secs: Sequence[float], end_sec: float, scores=None,
                                detokenizer=None, velocity=None, audio=None, beats=None, quantize: int = 0, bars=None, chords=None,
-                               sections=None):
+                               sections=None, hands=None):
         """tokens_to_notes on the device -> (notes, n_invalid).  `tokens`: (n, K, L) integer ids on `model`'s GPU (any strides whose
         last dimension is contiguous, e.g. hypothesis 0 of a beam call's (n, K, N, L)); `scores`: the matching (n, K, L) f32 token scores
         or None; `start_secs` must be strictly increasing.  `detokenizer`: a YourMT3.compile_detokenizer object to reuse (None: one is
@@ -578,7 +578,11 @@ class TaskManager:
         256 bass + label) and "chord_result" (int64 (8,), chords.track_chords' result).
         `sections`: a YourMT3.compile_section_tracker object (it needs `beats`; with `bars` it uses their metre): the song's form, tracked
         on the same records and beats where they lie, riding back in the same copy: the third element gains "section" (int32 (n_beats,),
-        65536 start + 256 s + label), "novelty" (int64 (n_beats,)) and "section_result" (int64 (8,), sections.track_sections' result)."""
+        65536 start + 256 s + label), "novelty" (int64 (n_beats,)) and "section_result" (int64 (8,), sections.track_sections' result).
+        `hands`: a YourMT3.compile_hand_splitter object whose max_notes holds the detokeniser's capacity (it needs no beats): every note's
+        hand, found on the records where they lie under the device count (over the frames of `end_sec`), the bytes riding back in the
+        same copy: the last element (a third one is made if there is none) gains "hand" (uint8 (n,), in the returned notes' order, as
+        "ticks" are), "hand_result" (int64 (8,), hands.split_hands' result) and "hand_split" (int32 (T,), 256 slot + split point of every slice)."""
         import torch
 
         if bars is not None and beats is None:
@@ -600,16 +604,19 @@ class TaskManager:
         if (velocity is None) != (audio is None):
             raise ValueError("velocity and audio go together")
         if n == 0 or L == 0:
-            if beats is not None:
+            if beats is not None or hands is not None:
                 from .tracking import empty
-                return [], 0, empty(bars is not None, chords is not None, sections is not None)
+                none = empty(bars is not None, chords is not None, sections is not None) if beats is not None else {}
+                if hands is not None:
+                    none.update(hand=np.zeros(0, np.uint8), hand_result=np.zeros(8, np.int64), hand_split=np.zeros(0, np.int32))
+                return [], 0, none
             return [], 0
         own = detokenizer is None
         if own:
             detokenizer = model.compile_detokenizer(self, n, L)
         try:
-            tracked = None
-            if velocity is None and beats is None:
+            tracked = hand = None
+            if velocity is None and beats is None and hands is None:
                 rec, n_invalid = detokenizer.run(tokens, scores, torch.from_numpy(starts), float(end_sec))
                 vel = None
             else:
@@ -620,6 +627,9 @@ class TaskManager:
                     from .beats import n_frames_of
                     n_frames = n_frames_of(end_sec, beats.params["frames_per_second"])
                     parts = tracking.launch_beats(beats, rec_dev, n_frames, counts, quantize)
+                if hands is not None:                                    # under the device count too
+                    from .beats import n_frames_of
+                    hand_dev, hand_split, hand_result = hands.split(rec_dev, n_frames_of(end_sec, hands.params["frames_per_second"]), count=counts)
                 n_notes, n_invalid = (int(v) for v in counts.cpu().tolist())
                 nb = n_notes * NOTE_RECORD.itemsize
                 riders = [rec_dev[:nb]] + ([vel_dev[:n_notes]] if velocity is not None else [])
@@ -627,13 +637,20 @@ class TaskManager:
                     parts["ticks"] = parts["ticks"][:n_notes]
                     tracking.launch_bars_chords(parts, bars, chords, rec_dev[:nb], n_frames, sections=sections)
                     riders += tracking.pack(parts)
+                if hands is not None:                                    # last: the tracking parts keep their place
+                    riders += [hand_dev[:n_notes], hand_result.view(torch.uint8), hand_split.view(torch.uint8)]
                 both = torch.cat(riders).cpu().numpy()
                 rec, o = both[:nb].view(NOTE_RECORD), nb
                 vel = None
                 if velocity is not None:
                     vel, o = both[o:o + n_notes].tolist(), o + n_notes
                 if beats is not None:
-                    tracked = tracking.unpack(both[o:].view(np.int32), tracking.layout(parts))
+                    lay = tracking.layout(parts)
+                    words = sum(w for _, w in lay)
+                    tracked, o = tracking.unpack(both[o:o + 4 * words].view(np.int32), lay), o + 4 * words
+                if hands is not None:
+                    hand, hand_result = both[o:o + n_notes].copy(), both[o + n_notes:o + n_notes + 64].copy().view(np.int64)
+                    hand_split = both[o + n_notes + 64:].copy().view(np.int32)[:int(hand_result[0])]
         finally:
             if own:
                 detokenizer.close()
@@ -643,9 +660,13 @@ class TaskManager:
                                                     rec["pitch"].tolist(), rec["is_drum"].tolist(), rec["score"].astype(np.float64).tolist())]
         if vel is not None:
             notes = [replace(x, velocity=v) for x, v in zip(notes, vel)]
-        if tracked is not None:
+        if tracked is not None or hand is not None:
             order = sorted(range(len(notes)), key=notes.__getitem__)
-            tracked["ticks"] = tracked["ticks"][order]
+            tracked = {} if tracked is None else tracked
+            if "ticks" in tracked:
+                tracked["ticks"] = tracked["ticks"][order]
+            if hand is not None:
+                tracked["hand"], tracked["hand_result"], tracked["hand_split"] = hand[order], hand_result, hand_split
             return [notes[i] for i in order], n_invalid, tracked
         return sorted(notes), n_invalid
 

@@ -122,10 +122,11 @@ class Chain(contextlib.ExitStack):
         return unpack(torch.cat(pack(parts)).cpu().numpy().view(np.int32), layout(parts))
 
 
-def render(notes, tracked: dict, fps: float) -> Tuple[bytes, dict]:
+def render(notes, tracked: dict, fps: float, hands=None) -> Tuple[bytes, dict]:
     """-> (the bytes of the .mid on the bars when there is a metre, else on the beats, with one marker per chord when there are chords and
     one per section start, before a chord's of the same tick, when there are sections; the info dict: beat_summary, "ticks", then
-    bar_summary, chord_summary and section_summary where they were tracked)"""
+    bar_summary, chord_summary and section_summary where they were tracked).  `hands`: every note's hand in the notes' order, or None:
+    passed on to the writer (midi.notes_to_midi_bytes)."""
     from .beats import beat_summary
     from .midi import notes_to_midi_bytes_on_bars, notes_to_midi_bytes_on_beats
     b, ticks = tracked["beats"], tracked["ticks"]
@@ -140,9 +141,9 @@ def render(notes, tracked: dict, fps: float) -> Tuple[bytes, dict]:
     if "metre" in tracked:
         from .bars import bar_summary
         info.update(bar_summary(tracked["metre"], tracked["bar_result"], b, fps))
-        midi = notes_to_midi_bytes_on_bars(notes, ticks, b, tracked["metre"], int(tracked["bar_result"][3]), fps, markers)
+        midi = notes_to_midi_bytes_on_bars(notes, ticks, b, tracked["metre"], int(tracked["bar_result"][3]), fps, markers, hands)
     else:
-        midi = notes_to_midi_bytes_on_beats(notes, ticks, b, fps, markers)
+        midi = notes_to_midi_bytes_on_beats(notes, ticks, b, fps, markers, hands)
     if "chord" in tracked:
         info.update(chord_summary(tracked["chord"], tracked["chord_result"], b, fps))
     if "section" in tracked:

@@ -19,6 +19,7 @@ from .beats import estimate_beats  # noqa: F401  (the same for beats.py)
 from .bars import estimate_bars  # noqa: F401  (and for bars.py)
 from .chords import estimate_chords  # noqa: F401  (and for chords.py)
 from .sections import estimate_sections  # noqa: F401  (and for sections.py)
+from .hands import estimate_hands  # noqa: F401  (and for hands.py)
 
 
 def transcribe(model, audio_info: Union[str, dict, np.ndarray], task_manager: Optional[TaskManager] = None, bsz: int = 8,
@@ -27,7 +28,8 @@ def transcribe(model, audio_info: Union[str, dict, np.ndarray], task_manager: Op
                min_confidence: Optional[float] = None, constrained: bool = False, programs=None, num_beams: int = 1,
                length_penalty: float = 1.0, device_detok: bool = False, velocity: bool = False, velocity_params: Optional[dict] = None,
                beats: bool = False, quantize: int = 0, beat_params: Optional[dict] = None, bars: bool = False, bar_params: Optional[dict] = None,
-               chords: bool = False, chord_params: Optional[dict] = None, sections: bool = False, section_params: Optional[dict] = None):
+               chords: bool = False, chord_params: Optional[dict] = None, sections: bool = False, section_params: Optional[dict] = None,
+               hands: bool = False, hand_params: Optional[dict] = None):
     """`continuous=True` decodes the file's segments through `bsz` slots with continuous batching
     (YourMT3.inference_stream: segments leave at EOS and the next ones enter) instead of fixed batches; same ids.
     `subtask`: for a task-conditioned TaskManager (e.g. "singing_drum_v1"), the sub-task whose task tokens prompt every
@@ -72,7 +74,14 @@ def transcribe(model, audio_info: Union[str, dict, np.ndarray], task_manager: Op
     writes one marker (FF 06) per section start into the .mid's conductor track, "[A]", "[B]" and so on, before a chord's marker of
     the same tick; a silent section gets none.  `section_params`: sections.DEFAULTS' keys (frames_per_second is the beats').  In every
     decode mode and with both detokenisers the same bytes.  The info dict gains "sections" ([(start_sec, end_sec, name)], "N" for a
-    silent one) and "section_labels" (every beat's label, 255 in a silent section).  Off, nothing changes by a byte."""
+    silent one) and "section_labels" (every beat's label, 255 in a silent section).  Off, nothing changes by a byte.
+    `hands=True` gives every note of the piano programs a hand on the device (YourMT3.compile_hand_splitter; include/ymt3.h, hands; the
+    rules: yourmt3_amd/hands.py) and writes such a program as two tracks on its one channel, "R.H." and then "L.H.": a notation program
+    opens them as two staves.  It needs no beats and works with them: in every decode mode and with both detokenisers the same bytes
+    (the device one's records get their hands where they lie, the host's notes go up once), after `min_confidence` and `velocity`, on
+    the kept notes.  `hand_params`: hands.DEFAULTS' keys.  The info dict (made if there is none: the return value gains it as its last
+    element) gains "hand" (one per note, in the notes' order: 1 right, 0 left, 255 none), "hand_splits" ([(sec, split point)] of every
+    onset slice) and "hand_result" (hands.split_hands' eight numbers).  Off, nothing changes by a byte."""
     if velocity_params is not None and not velocity:
         raise ValueError("velocity_params without velocity=True")
     if (beat_params is not None or quantize) and not beats:
@@ -89,6 +98,8 @@ def transcribe(model, audio_info: Union[str, dict, np.ndarray], task_manager: Op
         raise ValueError("sections=True without beats=True")
     if section_params is not None and not sections:
         raise ValueError("section_params without sections=True")
+    if hand_params is not None and not hands:
+        raise ValueError("hand_params without hands=True")
     num_beams = int(num_beams)
     if num_beams < 1:
         raise ValueError(f"num_beams={num_beams} must be >= 1")
@@ -144,8 +155,15 @@ def transcribe(model, audio_info: Union[str, dict, np.ndarray], task_manager: Op
             constraint.close()
     end_sec = n_samples / cfg.sample_rate
     measurer = model.compile_note_velocity(**(velocity_params or {})) if velocity else None
-    chain = tracked = None
+    chain = tracked = splitter = handed = None
     try:
+        if hands:
+            from .beats import n_frames_of
+            from .hands import DEFAULTS as HAND_DEFAULTS, MAX_NOTES as HAND_MAX_NOTES, hand_summary
+            hand_p = {**HAND_DEFAULTS, **(hand_params or {})}
+            hand_frames = n_frames_of(end_sec, float(hand_p["frames_per_second"]))
+            capacity = max(1, int(segments.shape[0]) * cfg.n_channels * L)
+            splitter = model.compile_hand_splitter(hand_frames, min(HAND_MAX_NOTES, capacity), **(hand_params or {}))
         if beats:
             from .bars import MAX_NOTES as BAR_MAX_NOTES
             from .beats import n_frames_of
@@ -160,8 +178,13 @@ def transcribe(model, audio_info: Union[str, dict, np.ndarray], task_manager: Op
                 extra.update(velocity=measurer, audio=segments.view(-1))
             if in_place and chain is not None:
                 extra.update(beats=chain.beats, quantize=quantize, bars=chain.bars, chords=chain.chords, sections=chain.sections)
+            if in_place and splitter is not None and capacity <= splitter.max_notes:
+                extra.update(hands=splitter)
             out = task_manager.tokens_to_notes_device(model, tokens, start_secs, end_sec, scores=scores, **extra)
             notes, tracked = out[0], (out[2] if len(out) > 2 else None)
+            if "hands" in extra:
+                handed = tuple(tracked.pop(k) for k in ("hand", "hand_split", "hand_result"))
+                tracked = tracked if "beats" in extra else None
         else:
             notes = task_manager.tokens_to_notes(batches, start_secs, end_sec=end_sec, score_batches=score_batches)
         if min_confidence is not None:
@@ -170,17 +193,30 @@ def transcribe(model, audio_info: Union[str, dict, np.ndarray], task_manager: Op
             notes = measurer.apply(segments.view(-1), notes)
         if chain is not None and tracked is None:                           # the same for the chain: up once, back once
             tracked = chain.run(torch.from_numpy(to_records(list(notes)).view(np.uint8).reshape(-1).copy()), quantize)
+        if splitter is not None and handed is None:                         # and for the hands
+            if len(notes) > splitter.max_notes:
+                raise ValueError(f"{len(notes)} notes: the hands take at most {splitter.max_notes}")
+            handed = splitter.run(torch.from_numpy(to_records(list(notes)).view(np.uint8).reshape(-1).copy()), hand_frames)
     finally:
+        if splitter is not None:
+            splitter.close()
         if measurer is not None:
             measurer.close()
         if chain is not None:
             chain.close()
     os.makedirs(output_dir, exist_ok=True)
-    if tracked is None:
+    if tracked is None and handed is None:
         midi_path = write_midi(notes, os.path.join(output_dir, name + ".mid"))
         return (midi_path, notes) if return_notes else midi_path
     midi_path = os.path.join(output_dir, name + ".mid")
-    midi, info = render(notes, tracked, chain.fps)
+    hand = None if handed is None else [int(h) for h in handed[0].tolist()]
+    if tracked is None:
+        from .midi import notes_to_midi_bytes
+        midi, info = notes_to_midi_bytes(notes, hands=hand), {}
+    else:
+        midi, info = render(notes, tracked, chain.fps, hands=hand)
+    if handed is not None:
+        info.update(hand_summary(*handed, hand_p))
     with open(midi_path, "wb") as f:
         f.write(midi)
     return (midi_path, notes, info) if return_notes else (midi_path, info)
@@ -254,7 +290,9 @@ class LiveTranscriber:
     audio of its onset has left the device.  estimate_velocities() on the recording puts them onto the session's MIDI file afterwards.
     Beats (transcribe(beats=True)) are not part of a live session either: the tempo path looks at the whole file.  estimate_beats() on the
     session's notes tracks them afterwards.  Bars and key (transcribe(bars=True)) build on the beats and are out of scope here for the same
-    reason: estimate_bars() on the session's notes finds them afterwards; chords (transcribe(chords=True)) likewise, by estimate_chords(), and sections (transcribe(sections=True)) by estimate_sections()."""
+    reason: estimate_bars() on the session's notes finds them afterwards; chords (transcribe(chords=True)) likewise, by estimate_chords(), and sections (transcribe(sections=True)) by estimate_sections().
+    Hands (transcribe(hands=True)) are not part of a live session either: a split point is a path over the whole piece;
+    estimate_hands() on the session's notes finds them afterwards."""
 
     def __init__(self, model, sample_rate: int, n_channels: int = 1, dtype=torch.int16, task_manager: Optional[TaskManager] = None,
                  max_chunk_frames: int = 1 << 16, bsz: Optional[int] = None, max_token_length: Optional[int] = None,
