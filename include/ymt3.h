@@ -1098,6 +1098,82 @@ typedef struct ymt3_mc_cross_args {
     float eps;
 } ymt3_mc_cross_args;
 int ymt3_test_mc_cross_attention(ymt3_handle h, const ymt3_mc_cross_args* args, void* stream);
+/* The token-selection stage of the step (csrc/decode.hip: argmax_embed_kernel and its companions; csrc/beam.hip), by the same rules.  None of
+ * these kernels waits on another workgroup, so a door is a plain launch.  The loop state the kernels read from device memory lives in blocks
+ * owned by each door (a DecodeShared for ymt3_test_token_step; a DecodeShared and a BeamShared for ymt3_test_beam_step), never the handle's.
+ * Before the launch the door writes its block(s) from the arguments on `stream`: step, step0, n_steps, n_prompt, done_count = 0, n_unfinished
+ * = R, tokens_out, forced, logits_out, scores_out, prompt, c_allowed / c_next / c_words; alpha and the beam outputs.  keep_shared != 0 leaves
+ * the blocks as the previous call of the same door left them (init -> select -> ... -> finalize then shows what the init kernels wrote);
+ * such a call must repeat R, row0, n_steps, n_prompt and the presence of c_allowed, its step / step0 / output pointers are ignored, and the door
+ * checks it against the position it knows the block to hold.  state_out (int32[4], may be NULL) receives step, done_count, n_unfinished
+ * and n_steps of the door's DecodeShared after the launch.  ticket ([R / 32 + 1] lines of 32 words, zero before the launch) and zero_sync
+ * (zero_lines lines of 32 words) are caller buffers.  Values behind pointers (positions, states, next-state tables, offsets) are the
+ * caller's duty like the extents (yourmt3_amd/model.py checks both).
+ *
+ * ymt3_test_token_step, op =
+ *   0 decode_init   launch_decode_init with one chain: rows [0, R) (row0 must be 0): h = embed[pad_id] (+ chan_embed[r % n_channels]), ssq, finished
+ *                   = 0, row_state = c_start[r] clamped into [0, c_n_states) (0 without c_start), the layer-0 table row of pad_id at position step0;
+ *                   the block is written by the kernel (step = step0, n_unfinished = R, ...)
+ *   1 argmax_embed  launch_argmax_embed over rows [row0, row0 + R): lock-step at the block's `step` (emitted column step - step0 - n_prompt), or
+ *                   slot mode when row_pos is given (row_out, and row_prompt with n_prompt > 0; neither forced nor logits_out)
+ *   2 slot_start    launch_slot_start: rows [row0, row0 + n_channels); row_out[r] = first_out + channel * n_steps, row_prompt[r] = first_prompt +
+ *                   channel * n_prompt, position 0, c_start indexed by the channel
+ *   3 slot_retire   launch_slot_retire: PAD (scores 0.0) over [row_pos[r] + 1 - n_prompt, n_steps) of rows [row0, row0 + R) at row_out[r]
+ *   4 pad_tail      launch_pad_tail: PAD (scores 0.0) over [from, n_steps) of rows [row0, row0 + R); 0 <= from <= n_steps
+ *   5 qkv0_embed    launch_qkv0_embed: rows [0, R) of h / ssq = embed[v0 + i], no channel row (row0 == 0, v0 + R <= V)
+ * The selection rule of op 1 (first maximum over the allowed, non-NaN logits that compare greater than -3.4e38, else the lowest allowed
+ * index; EOS then PAD; clamped forced / prompt ids; the automaton follows the fed id and freezes after EOS) and its scores are the ones of
+ * the decode entry points above.  Rules the kernels have beyond those sections:
+ *   - a state that allows no token (ymt3_constraint_create refuses one; a raw table can hold it) emits V - 1, which it does not allow: the
+ *     score is -inf, as for a forced disallowed id;
+ *   - h[r] = f32(embed[fed]) + f32(chan_embed[r % n_channels]) in one fp32 add; ssq[0][r] = sum(h[r]^2) in fp32, ssq[1..31][r] = 0.0;
+ *   - layer-0 table (qkv0 [V][1536] bf16, H == 8, d == 512, one channel): the fed id's q third goes to q0[r]; the k / v thirds go to
+ *     kcache0 / vcache0[((r * 8 + head) * L + pos) * 64 ..] with pos = step + 1 (slot mode: the row's position after the step) only while
+ *     pos < L; at pos == L the q third is still written and the caches are not touched;
+ *   - slot mode: a stopped row (finished != 0) writes no token, score or state, keeps its position and feeds pad_id; the block's `step`
+ *     still advances by one per launch and means nothing there;
+ *   - after the launch: step + 1, done_count == 0, every ticket line zero, the zero_sync lines zero; with eos_id >= 0, n_unfinished = the
+ *     rows of [row0, row0 + R) whose finished flag is 0 (eos_id < 0 leaves n_unfinished alone).
+ *
+ * ymt3_test_beam_step, op = 0 beam_init (launch_beam_init; the kernel writes both blocks), 1 beam_select (launch_beam_select; slot mode when
+ * row_pos is given), 2 beam_finalize (launch_beam_finalize, N = hypotheses per group), 3 beam_slot_start (launch_beam_slot_start: the
+ * n_channels * W rows from row0, queue indices first_group + channel), 4 beam_slot_finalize (launch_beam_slot_finalize).  Rows [0, R), R a
+ * multiple of W <= 8, R <= anc_rows; anc u8 [2][anc_rows][anc_pitch], slot_anc u8 [R][anc_pitch], anc_pitch % 16 == 0, n_prompt + n_steps below
+ * anc_pitch and fed_pitch; fed_tok / fed_lp [R][fed_pitch]; run, fin_* [R]; n_fin [R / W]; tokens_out [G][N][n_steps], seq_out [G][N],
+ * tok_out [G][N][n_steps] (both may be NULL).  The selection follows the beam-search section above; what it leaves unsaid:
+ *   - the select of position t reads ancestry buffer t & 1 and writes rows 0 .. W - 1 of buffer (t + 1) & 1, whole 32-bit words 0 .. (t + 1) / 4:
+ *     entries 0 .. t are the parent's, entry t + 1 the row's own index; bytes of the last word beyond t + 1 are copied from the parent's row;
+ *   - a hypothesis entering a slot takes the lowest snapshot row (fin_store) not held by a surviving old slot, and slot_anc[that row] =
+ *     words 0 .. t / 4 of its parent's ancestry row; displaced slots free their rows for the same step's entries;
+ *   - prompt positions and done groups copy the ancestry rows with every row its own parent, and feed the prompt id / pad_id. */
+typedef struct ymt3_token_step_args {
+    const float* logits; float* h; const void* embed; const void* chan_embed;
+    int32_t* finished; float* ssq; int32_t* row_pos; int64_t* row_out; int64_t* row_prompt; int32_t* row_state;
+    uint32_t* ticket; uint32_t* zero_sync;
+    const void* qkv0; void* q0; void* kcache0; void* vcache0;
+    int32_t* tokens_out; const int32_t* forced; float* logits_out; float* scores_out; const int32_t* prompt;
+    const uint32_t* c_allowed; const int32_t* c_next; const int32_t* c_start;
+    int32_t* state_out;
+    int64_t first_out, first_prompt;
+    int32_t ssq_stride, row0, R, V, d, n_channels, eos_id, pad_id, zero_lines, H, L;
+    int32_t step, step0, n_steps, n_prompt, c_words, c_n_states, keep_shared, from, v0;
+} ymt3_token_step_args;
+int ymt3_test_token_step(ymt3_handle h, int op, const ymt3_token_step_args* args, void* stream);
+typedef struct ymt3_beam_step_args {
+    const float* logits; float* h; const void* embed; const void* chan_embed;
+    int32_t* finished; float* ssq; int32_t* row_state;
+    uint8_t* anc; int32_t* fed_tok; float* fed_lp; float* run;
+    float* fin_score; int32_t* fin_len; int32_t* fin_store; int32_t* fin_tok; float* fin_lp; int32_t* n_fin; uint8_t* slot_anc;
+    int32_t* row_pos; int64_t* row_out; int64_t* row_prompt;
+    const int32_t* prompt; const uint32_t* c_allowed; const int32_t* c_next; const int32_t* c_start;
+    int32_t* tokens_out; float* seq_out; float* tok_out;
+    int32_t* state_out;
+    int64_t first_group;
+    int32_t ssq_stride, R, V, d, n_channels, eos_id, pad_id, W, anc_rows, anc_pitch, fed_pitch;
+    int32_t step, n_steps, n_prompt, c_words, c_n_states, keep_shared, N, row0;
+    float alpha;
+} ymt3_beam_step_args;
+int ymt3_test_beam_step(ymt3_handle h, int op, const ymt3_beam_step_args* args, void* stream);
 
 /* Per-kernel test door of the mixture-of-experts decoder FFN's SEPARATE launches (csrc/moe.hip; the one-launch restatement moe_chain.hip is
  * tied to them by the bit-identity test).  Same rules as the doors above.  ymt3_test_moe_stage: launch_moe_stage with no routing trace.

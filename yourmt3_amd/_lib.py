@@ -42,6 +42,7 @@ SYMBOLS = [
     "ymt3_test_gemm_ex", "ymt3_test_rmsnorm", "ymt3_test_enc_attention", "ymt3_test_seq_attention", "ymt3_test_spec_embed",
     "ymt3_test_dec_gemm", "ymt3_test_dec_attention", "ymt3_test_mc_cross_attention", "ymt3_test_moe_stage",
     "ymt3_test_seq_embed", "ymt3_test_dec_seq_attention", "ymt3_test_seq_lm_head",
+    "ymt3_test_token_step", "ymt3_test_beam_step",
 ]
 
 _lib = None
@@ -165,6 +166,26 @@ class SeqLmHeadArgs(ctypes.Structure):
     """ymt3_seq_lm_head_args of include/ymt3.h"""
     _fields_ = [(n, ctypes.c_void_p) for n in ("xn", "W", "tokens", "lengths", "scores", "logits")] + [
         (n, ctypes.c_int32) for n in ("M", "L", "n_prompt", "n_steps", "V", "d", "row0")]
+
+
+class TokenStepArgs(ctypes.Structure):
+    """ymt3_token_step_args of include/ymt3.h"""
+    _fields_ = [(n, ctypes.c_void_p) for n in ("logits", "h", "embed", "chan_embed", "finished", "ssq", "row_pos", "row_out", "row_prompt", "row_state",
+                                               "ticket", "zero_sync", "qkv0", "q0", "kcache0", "vcache0", "tokens_out", "forced", "logits_out",
+                                               "scores_out", "prompt", "c_allowed", "c_next", "c_start", "state_out")] + [
+        (n, ctypes.c_int64) for n in ("first_out", "first_prompt")] + [
+        (n, ctypes.c_int32) for n in ("ssq_stride", "row0", "R", "V", "d", "n_channels", "eos_id", "pad_id", "zero_lines", "H", "L", "step", "step0",
+                                      "n_steps", "n_prompt", "c_words", "c_n_states", "keep_shared", "from_", "v0")]
+
+
+class BeamStepArgs(ctypes.Structure):
+    """ymt3_beam_step_args of include/ymt3.h"""
+    _fields_ = [(n, ctypes.c_void_p) for n in ("logits", "h", "embed", "chan_embed", "finished", "ssq", "row_state", "anc", "fed_tok", "fed_lp", "run",
+                                               "fin_score", "fin_len", "fin_store", "fin_tok", "fin_lp", "n_fin", "slot_anc", "row_pos", "row_out",
+                                               "row_prompt", "prompt", "c_allowed", "c_next", "c_start", "tokens_out", "seq_out", "tok_out",
+                                               "state_out")] + [("first_group", ctypes.c_int64)] + [
+        (n, ctypes.c_int32) for n in ("ssq_stride", "R", "V", "d", "n_channels", "eos_id", "pad_id", "W", "anc_rows", "anc_pitch", "fed_pitch", "step",
+                                      "n_steps", "n_prompt", "c_words", "c_n_states", "keep_shared", "N", "row0")] + [("alpha", ctypes.c_float)]
 
 
 class YMT3Error(RuntimeError):
@@ -383,6 +404,9 @@ def load() -> ctypes.CDLL:
     lib.ymt3_test_mc_cross_attention.restype = i32
     for name, struct in (("ymt3_test_seq_embed", SeqEmbedArgs), ("ymt3_test_dec_seq_attention", DecSeqAttnArgs), ("ymt3_test_seq_lm_head", SeqLmHeadArgs)):
         getattr(lib, name).argtypes = [vp, ctypes.POINTER(struct), vp]
+        getattr(lib, name).restype = i32
+    for name, struct in (("ymt3_test_token_step", TokenStepArgs), ("ymt3_test_beam_step", BeamStepArgs)):
+        getattr(lib, name).argtypes = [vp, i32, ctypes.POINTER(struct), vp]
         getattr(lib, name).restype = i32
     for n in ("ymt3_logmel", "ymt3_encode", "ymt3_decode_greedy", "ymt3_transcribe_segments", "ymt3_test_gemm"):
         getattr(lib, n).restype = i32

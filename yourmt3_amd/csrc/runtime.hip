@@ -123,6 +123,13 @@ struct ymt3_ctx {
     int* host_rows = nullptr;           // pinned [maxR]: copy of `finished` for the host's retire/admit decisions
     DecodeShared* shared = nullptr;     // [MAX_CHAINS] per-chain loop state
     DecodeShared* test_shared = nullptr;   // the decoder test doors' own block (ymt3_test_dec_gemm / _dec_attention), allocated at first use
+    // the token-selection doors' own blocks (ymt3_test_token_step / _beam_step) and what the host knows of them: the position the next launch
+    // reads and the call geometry they were written for (a keep_shared call is checked against these, not against its arguments)
+    struct DoorLoop { bool valid = false; int step = 0, step0 = 0, n_steps = 0, n_prompt = 0; bool constrained = false; int row0 = 0, R = 0; };
+    DecodeShared* test_tok_shared = nullptr;
+    DecodeShared* test_beam_shared = nullptr;
+    BeamShared* test_beam_params = nullptr;
+    DoorLoop test_tok_loop, test_beam_loop;
     hipStream_t cap_stream = nullptr;
     // Decode rows are independent, so a batch CAN be cut into `n_chains` contiguous row ranges whose step graphs replay
     // concurrently on separate HIP streams.  Measured on MI355X in both rounds (profiles/r01_chain_sweep.txt with one host thread
@@ -2355,6 +2362,267 @@ extern "C" int ymt3_test_seq_lm_head(ymt3_handle h, const ymt3_seq_lm_head_args*
     a.scores = c.scores; a.logits = c.logits; a.M = c.M; a.L = c.L; a.n_prompt = c.n_prompt; a.n_steps = c.n_steps; a.V = c.V; a.d = c.d;
     a.row0 = c.row0;
     LAUNCH(launch_seq_lm_head_score(a, (hipStream_t)stream));
+    HIP_TRY(hipGetLastError());
+    return YMT3_OK;
+}
+
+// The token-selection doors' own loop state: a DecodeShared and a BeamShared block per door (never the handle's, never the block of the doors
+// above), allocated at first use.  Both are written and read back by one-thread kernels on the caller's stream, so a door call stays asynchronous.
+template <typename T>
+__global__ void door_block_set_kernel(T* dst, T v) { *dst = v; }
+__global__ void door_state_out_kernel(const DecodeShared* sh, int32_t* out) {
+    out[0] = sh->step; out[1] = sh->done_count; out[2] = sh->n_unfinished; out[3] = sh->n_steps;
+}
+static int door_blocks(ymt3_ctx* c, DecodeShared** sh, BeamShared** bs) {
+    DecodeShared*& d = bs ? c->test_beam_shared : c->test_tok_shared;
+    if (!d) {
+        if (dev_alloc(c, (void**)&d, sizeof(DecodeShared))) return YMT3_ERR_HIP;
+        HIP_TRY(hipMemset(d, 0, sizeof(DecodeShared)));
+    }
+    if (bs && !c->test_beam_params) {
+        if (dev_alloc(c, (void**)&c->test_beam_params, sizeof(BeamShared))) return YMT3_ERR_HIP;
+        HIP_TRY(hipMemset(c->test_beam_params, 0, sizeof(BeamShared)));
+    }
+    *sh = d;
+    if (bs) *bs = c->test_beam_params;
+    return YMT3_OK;
+}
+
+extern "C" int ymt3_test_token_step(ymt3_handle h, int op, const ymt3_token_step_args* args, void* stream) {
+    int rc = check_call(h, 0);
+    if (rc) return rc;
+    if (!args) FAIL(YMT3_ERR_ARG, "%s: args is null", __func__);
+    const ymt3_token_step_args& c = *args;
+    hipStream_t s = (hipStream_t)stream;
+    DOOR_REQUIRE(op >= 0 && op <= 5);
+    DOOR_REQUIRE(c.R >= 1 && c.R <= 0xffff && c.row0 >= 0 && c.row0 <= 0xffff);
+    DOOR_REQUIRE(c.n_steps >= 1 && c.n_prompt >= 0);
+    if (c.state_out) DOOR_PTR(c.state_out);
+    const bool embeds = op != 3 && op != 4, slot = c.row_pos != nullptr;
+    ArgmaxArgs a{};
+    ConstraintView cv{};
+    if (embeds) {
+        DOOR_PTR(c.h); DOOR_PTR(c.embed); DOOR_PTR(c.ssq);
+        DOOR_REQUIRE(c.V >= 1 && c.d >= 1 && c.n_channels >= 1);
+        DOOR_REQUIRE(c.pad_id >= 0 && c.pad_id < c.V && c.eos_id < c.V);
+        if (c.chan_embed) DOOR_PTR(c.chan_embed);
+    }
+    if (op <= 2) {
+        DOOR_PTR(c.finished);
+        // the rows a launch covers: decode_init ignores row0 (rows [0, R)), slot_start restarts the n_channels rows of one segment
+        DOOR_REQUIRE(op != 0 || c.row0 == 0);
+        DOOR_REQUIRE(c.ssq_stride >= c.row0 + (op == 2 ? c.n_channels : c.R));
+        if (c.qkv0) {
+            DOOR_PTR(c.qkv0); DOOR_PTR(c.q0); DOOR_PTR(c.kcache0); DOOR_PTR(c.vcache0);
+            DOOR_REQUIRE(c.H * 64 * 3 == QKV0_COLS && c.d == QKV0_COLS / 3 && c.L >= 1 && c.chan_embed == nullptr && c.n_channels == 1);
+        }
+        if (c.row_state) DOOR_PTR(c.row_state);
+        if (c.c_allowed) {
+            DOOR_PTR(c.c_allowed); DOOR_PTR(c.c_next); DOOR_PTR(c.row_state);
+            DOOR_REQUIRE(c.c_n_states >= 1 && c.c_words >= 1 && c.c_words <= (1 << 20) && c.c_words * 32 >= c.V);
+        } else {
+            DOOR_REQUIRE(c.c_next == nullptr);
+        }
+        if (c.c_start) {
+            DOOR_PTR(c.c_start);
+            DOOR_REQUIRE(op != 1 && c.row_state != nullptr && c.c_n_states >= 1);
+        }
+        cv.allowed = c.c_allowed; cv.next = c.c_next; cv.words = c.c_words; cv.n_states = c.c_n_states; cv.start = c.c_start;
+    }
+    if (slot) {
+        DOOR_REQUIRE(op == 1 || op == 2 || op == 3);
+        DOOR_PTR(c.row_pos); DOOR_PTR(c.row_out);
+    } else {
+        DOOR_REQUIRE(op != 2 && op != 3);
+        DOOR_REQUIRE(c.row_out == nullptr && c.row_prompt == nullptr);
+    }
+    if (c.tokens_out) DOOR_PTR(c.tokens_out);
+    if (c.forced) DOOR_PTR(c.forced);
+    if (c.logits_out) DOOR_PTR(c.logits_out);
+    if (c.scores_out) DOOR_PTR(c.scores_out);
+    if (c.prompt) DOOR_PTR(c.prompt);
+    DOOR_REQUIRE(c.n_prompt == 0 || op >= 2 || c.prompt != nullptr);      // (slot_start only lays the prompt offsets out)
+    a.logits = c.logits; a.h = c.h; a.embed = static_cast<const bf16_t*>(c.embed); a.chan_embed = static_cast<const bf16_t*>(c.chan_embed);
+    a.finished = c.finished; a.ssq = c.ssq; a.ssq_stride = c.ssq_stride;
+    a.row0 = c.row0; a.R = c.R; a.V = c.V; a.d = c.d; a.n_channels = c.n_channels; a.eos_id = c.eos_id; a.pad_id = c.pad_id;
+    a.row_pos = c.row_pos; a.row_out = reinterpret_cast<const long long*>(c.row_out); a.row_prompt = reinterpret_cast<const long long*>(c.row_prompt);
+    a.ticket = c.ticket; a.zero_sync = c.zero_sync; a.zero_lines = c.zero_lines; a.row_state = c.row_state;
+    a.qkv0 = static_cast<const bf16_t*>(c.qkv0); a.q0 = static_cast<bf16_t*>(c.q0);
+    a.kcache0 = static_cast<bf16_t*>(c.kcache0); a.vcache0 = static_cast<bf16_t*>(c.vcache0); a.H = c.H; a.L = c.L;
+    static_assert(sizeof(long long) == sizeof(int64_t), "row_out / row_prompt are 64-bit offsets");
+    rc = door_blocks(h, &a.shared, nullptr);
+    if (rc) return rc;
+    switch (op) {
+    case 0:
+        DOOR_REQUIRE(c.step0 >= 0 && (c.qkv0 == nullptr || c.step0 < c.L));
+        DOOR_REQUIRE(c.forced == nullptr || c.tokens_out != nullptr);
+        LAUNCH(launch_decode_init(a, 1, c.n_steps, c.step0, c.tokens_out, c.forced, c.logits_out, c.prompt, c.n_prompt, c.scores_out, cv, s));
+        h->test_tok_loop = {true, c.step0, c.step0, c.n_steps, c.n_prompt, c.c_allowed != nullptr, 0, c.R};
+        break;
+    case 1: {
+        DOOR_PTR(c.logits); DOOR_PTR(c.tokens_out);
+        if (c.ticket) DOOR_PTR(c.ticket);
+        if (c.zero_sync) { DOOR_PTR(c.zero_sync); DOOR_REQUIRE(c.zero_lines >= 1); }
+        else DOOR_REQUIRE(c.zero_lines == 0);
+        ymt3_ctx::DoorLoop loop{true, slot ? 0 : c.step, slot ? 0 : c.step0, c.n_steps, c.n_prompt, c.c_allowed != nullptr, c.row0, c.R};
+        if (c.keep_shared) {
+            // the block as the previous call of this door left it: its geometry must be this call's (the extents were judged by it)
+            DOOR_REQUIRE(h->test_tok_loop.valid && h->test_tok_loop.n_steps == c.n_steps && h->test_tok_loop.n_prompt == c.n_prompt);
+            DOOR_REQUIRE(h->test_tok_loop.constrained == (c.c_allowed != nullptr));
+            // the rows too: n_unfinished and the extents of the block's output pointers were written and judged for them
+            DOOR_REQUIRE(h->test_tok_loop.row0 == c.row0 && h->test_tok_loop.R == c.R);
+            loop = h->test_tok_loop;
+        }
+        if (slot) {
+            // slot mode reads neither forced ids nor the logits copy; positions are per row (their values: the caller's, model.py)
+            DOOR_REQUIRE(c.forced == nullptr && c.logits_out == nullptr);
+            if (c.n_prompt > 0) DOOR_PTR(c.row_prompt);
+        } else {
+            // the emitted column of this step lies in [-n_prompt, n_steps); the table gather writes q at step + 1 <= L
+            DOOR_REQUIRE(loop.step0 >= 0 && loop.step >= loop.step0 && loop.step - loop.step0 - c.n_prompt < c.n_steps);
+            DOOR_REQUIRE(c.qkv0 == nullptr || loop.step < c.L);
+        }
+        if (!c.keep_shared) {
+            DecodeShared v{};
+            v.step = loop.step; v.step0 = loop.step0; v.done_count = 0; v.n_steps = c.n_steps; v.n_unfinished = c.R;
+            v.n_prompt = c.n_prompt; v.tokens_out = c.tokens_out; v.forced = c.forced; v.logits_out = c.logits_out; v.prompt = c.prompt;
+            v.scores_out = c.scores_out; v.c_allowed = c.c_allowed; v.c_next = c.c_next; v.c_words = c.c_words;
+            door_block_set_kernel<DecodeShared><<<1, 1, 0, s>>>(a.shared, v);
+        }
+        LAUNCH(launch_argmax_embed(a, s));
+        ++loop.step;                               // the last workgroup advances the block's position
+        h->test_tok_loop = loop;
+        break;
+    }
+    case 2:
+        DOOR_PTR(c.row_prompt);
+        DOOR_REQUIRE(c.first_out >= 0 && c.first_prompt >= 0);
+        LAUNCH(launch_slot_start(a, c.row0, c.first_out, c.n_steps, reinterpret_cast<long long*>(c.row_out), c.first_prompt, c.n_prompt,
+                                 reinterpret_cast<long long*>(c.row_prompt), cv, s));
+        break;
+    case 3:
+        DOOR_PTR(c.tokens_out);
+        LAUNCH(launch_slot_retire(a, c.row0, c.R, c.n_steps, c.n_prompt, c.tokens_out, c.scores_out, s));
+        break;
+    case 4:
+        DOOR_PTR(c.tokens_out);
+        DOOR_REQUIRE(c.from >= 0 && c.from <= c.n_steps);
+        LAUNCH(launch_pad_tail(c.tokens_out, c.scores_out, c.row0, c.R, c.n_steps, c.from, c.pad_id, s));
+        break;
+    default:
+        // rows [0, R) of h and ssq take the embeddings of ids [v0, v0 + R)
+        DOOR_REQUIRE(c.row0 == 0 && c.chan_embed == nullptr && c.v0 >= 0 && c.v0 + c.R <= c.V && c.ssq_stride >= c.R);
+        LAUNCH(launch_qkv0_embed(a, c.v0, c.R, s));
+        break;
+    }
+    if (c.state_out) door_state_out_kernel<<<1, 1, 0, s>>>(a.shared, c.state_out);
+    HIP_TRY(hipGetLastError());
+    return YMT3_OK;
+}
+
+extern "C" int ymt3_test_beam_step(ymt3_handle h, int op, const ymt3_beam_step_args* args, void* stream) {
+    int rc = check_call(h, 0);
+    if (rc) return rc;
+    if (!args) FAIL(YMT3_ERR_ARG, "%s: args is null", __func__);
+    const ymt3_beam_step_args& c = *args;
+    hipStream_t s = (hipStream_t)stream;
+    DOOR_REQUIRE(op >= 0 && op <= 4);
+    DOOR_PTR(c.h); DOOR_PTR(c.embed); DOOR_PTR(c.ssq); DOOR_PTR(c.finished); DOOR_PTR(c.anc); DOOR_PTR(c.slot_anc);
+    DOOR_PTR(c.fed_tok); DOOR_PTR(c.fed_lp); DOOR_PTR(c.run);
+    DOOR_PTR(c.fin_score); DOOR_PTR(c.fin_len); DOOR_PTR(c.fin_store); DOOR_PTR(c.fin_tok); DOOR_PTR(c.fin_lp); DOOR_PTR(c.n_fin);
+    if (c.chan_embed) DOOR_PTR(c.chan_embed);
+    if (c.state_out) DOOR_PTR(c.state_out);
+    DOOR_REQUIRE(c.W >= 1 && c.W <= BEAM_MAX && c.R >= 1 && c.R <= 0xffff && c.R % c.W == 0 && c.R <= c.anc_rows);
+    DOOR_REQUIRE(c.V >= 1 && c.d >= 1 && c.n_channels >= 1 && c.ssq_stride >= c.R);
+    DOOR_REQUIRE(c.pad_id >= 0 && c.pad_id < c.V && c.eos_id < c.V);
+    DOOR_REQUIRE(c.n_steps >= 1 && c.n_prompt >= 0 && (c.n_prompt == 0 || c.prompt != nullptr));
+    DOOR_REQUIRE(c.anc_pitch % 16 == 0 && c.anc_pitch <= 48 * 1024 && c.n_prompt + c.n_steps < c.anc_pitch && c.n_prompt + c.n_steps < c.fed_pitch);
+    if (c.prompt) DOOR_PTR(c.prompt);
+    if (c.row_state) DOOR_PTR(c.row_state);
+    if (c.c_allowed) {
+        DOOR_PTR(c.c_allowed); DOOR_PTR(c.c_next); DOOR_PTR(c.row_state);
+        DOOR_REQUIRE(c.c_n_states >= 1 && c.c_words >= 1 && c.c_words <= (1 << 20) && c.c_words * 32 >= c.V);
+    } else {
+        DOOR_REQUIRE(c.c_next == nullptr);
+    }
+    if (c.c_start) {
+        DOOR_PTR(c.c_start);
+        DOOR_REQUIRE((op == 0 || op == 3) && c.row_state != nullptr && c.c_n_states >= 1);
+    }
+    const bool slot = c.row_pos != nullptr;
+    if (slot) {
+        DOOR_REQUIRE(op == 1 || op == 3 || op == 4);
+        DOOR_PTR(c.row_pos); DOOR_PTR(c.row_out); DOOR_PTR(c.row_prompt);
+    } else {
+        DOOR_REQUIRE(op != 3 && op != 4 && c.row_out == nullptr && c.row_prompt == nullptr);
+    }
+    const ConstraintView cv{c.c_allowed, c.c_next, c.c_words, c.c_n_states, c.c_start};
+    BeamArgs a{};
+    a.logits = c.logits; a.h = c.h; a.embed = static_cast<const bf16_t*>(c.embed); a.chan_embed = static_cast<const bf16_t*>(c.chan_embed);
+    a.finished = c.finished; a.ssq = c.ssq; a.ssq_stride = c.ssq_stride;
+    a.R = c.R; a.V = c.V; a.d = c.d; a.n_channels = c.n_channels; a.eos_id = c.eos_id; a.pad_id = c.pad_id; a.W = c.W;
+    a.row_state = c.row_state; a.anc = c.anc; a.anc_rows = c.anc_rows; a.anc_pitch = c.anc_pitch;
+    a.fed_tok = c.fed_tok; a.fed_lp = c.fed_lp; a.fed_pitch = c.fed_pitch; a.run = c.run;
+    a.fin_score = c.fin_score; a.fin_len = c.fin_len; a.fin_store = c.fin_store; a.fin_tok = c.fin_tok; a.fin_lp = c.fin_lp; a.n_fin = c.n_fin;
+    a.slot_anc = c.slot_anc;
+    a.row_pos = c.row_pos; a.row_out = reinterpret_cast<long long*>(c.row_out); a.row_prompt = reinterpret_cast<long long*>(c.row_prompt);
+    rc = door_blocks(h, &a.shared, &a.beam);
+    if (rc) return rc;
+    BeamShared params{};
+    params.alpha = c.alpha; params.tokens_out = c.tokens_out; params.seq_out = c.seq_out; params.tok_out = c.tok_out;
+    if (op == 0 || !c.keep_shared) {
+        // what the kernels read from the blocks: the outputs and alpha (init, the result kernels, and select's length penalty)
+        DOOR_PTR(c.tokens_out);
+        if (c.seq_out) DOOR_PTR(c.seq_out);
+        if (c.tok_out) DOOR_PTR(c.tok_out);
+        DOOR_REQUIRE(c.alpha >= 0.f && c.alpha <= 16.f);
+    }
+    ymt3_ctx::DoorLoop loop{true, slot || op == 0 ? 0 : c.step, 0, c.n_steps, c.n_prompt, c.c_allowed != nullptr, 0, c.R};
+    if (c.keep_shared && op != 0 && op != 3) {
+        // the blocks as the previous call of this door left them: their geometry must be this call's (the extents were judged by it)
+        DOOR_REQUIRE(h->test_beam_loop.valid && h->test_beam_loop.n_steps == c.n_steps && h->test_beam_loop.n_prompt == c.n_prompt);
+        DOOR_REQUIRE(h->test_beam_loop.constrained == (c.c_allowed != nullptr));
+        DOOR_REQUIRE(h->test_beam_loop.R == c.R);
+        loop = h->test_beam_loop;
+    }
+    auto set_blocks = [&](int step) {
+        DecodeShared v{};
+        v.step = step; v.n_steps = c.n_steps; v.n_unfinished = c.R; v.n_prompt = c.n_prompt; v.prompt = c.prompt;
+        v.c_allowed = c.c_allowed; v.c_next = c.c_next; v.c_words = c.c_words;
+        door_block_set_kernel<DecodeShared><<<1, 1, 0, s>>>(a.shared, v);
+        door_block_set_kernel<BeamShared><<<1, 1, 0, s>>>(a.beam, params);
+    };
+    switch (op) {
+    case 0:
+        LAUNCH(launch_beam_init(a, c.n_steps, c.prompt, c.n_prompt, cv, params, s));
+        h->test_beam_loop = loop;
+        break;
+    case 1:
+        DOOR_PTR(c.logits);
+        // lock-step: position `step` writes ancestry entry and fed token step + 1, below both pitches by the rule above
+        if (!slot) DOOR_REQUIRE(loop.step >= 0 && loop.step - c.n_prompt < c.n_steps);
+        if (!c.keep_shared) set_blocks(loop.step);
+        LAUNCH(launch_beam_select(a, s));
+        if (!slot) ++loop.step;                    // the last workgroup advances the block's position (slot mode: the rows' own)
+        h->test_beam_loop = loop;
+        break;
+    case 2:
+        DOOR_REQUIRE(c.N >= 1 && c.N <= c.W);
+        if (!c.keep_shared) { set_blocks(loop.step); h->test_beam_loop = loop; }
+        LAUNCH(launch_beam_finalize(a, c.N, s));
+        break;
+    case 3:
+        DOOR_REQUIRE(c.row0 >= 0 && c.row0 % (c.n_channels * c.W) == 0 && c.row0 + c.n_channels * c.W <= c.R && c.first_group >= 0);
+        LAUNCH(launch_beam_slot_start(a, c.row0, c.first_group, c.n_prompt, cv, s));
+        break;
+    default:
+        DOOR_REQUIRE(c.N >= 1 && c.N <= c.W);
+        DOOR_REQUIRE(c.row0 >= 0 && c.row0 % (c.n_channels * c.W) == 0 && c.row0 + c.n_channels * c.W <= c.R);
+        if (!c.keep_shared) { set_blocks(0); h->test_beam_loop = loop; }
+        LAUNCH(launch_beam_slot_finalize(a, c.row0, c.N, s));
+        break;
+    }
+    if (c.state_out) door_state_out_kernel<<<1, 1, 0, s>>>(a.shared, c.state_out);
     HIP_TRY(hipGetLastError());
     return YMT3_OK;
 }

@@ -1383,3 +1383,223 @@ class YourMT3:
         p = lambda t: t.data_ptr() if t is not None else None
         c = _lib.SeqLmHeadArgs(p(xn), p(W), p(tokens), p(lengths), p(scores), p(logits), M, L, n_prompt, n_steps, V, d, row0)
         _lib.check(self._lib.ymt3_test_seq_lm_head(self._handle, ctypes.byref(c), self._stream()))
+
+    # ---- token selection (csrc/decode.hip: argmax_embed_kernel and its companions; csrc/beam.hip), validated before the library is touched like
+    # the doors above: geometry, every tensor's extent, then the VALUES the kernels follow (positions, offsets, states, next-state tables)
+    TOKEN_OPS = ("decode_init", "argmax_embed", "slot_start", "slot_retire", "pad_tail", "qkv0_embed")
+    BEAM_OPS = ("beam_init", "beam_select", "beam_finalize", "beam_slot_start", "beam_slot_finalize")
+
+    def _automaton(self, c_allowed, c_next, c_start, row_state, V: int, n_states: int, rows: int, n_start: int, lo: int = 0) -> int:
+        """extents and values of a raw automaton -> its words per state (0: none)"""
+        need = self._need
+        if c_allowed is None:
+            need(c_next is None, "c_next with c_allowed only")
+            words = 0
+        else:
+            words = (V + 31) // 32
+            need(n_states >= 1 and c_next is not None and row_state is not None, "c_next, row_state and c_n_states >= 1 (c_allowed)")
+            self._door("c_allowed", c_allowed, torch.int32, n_states * words)
+            self._door("c_next", c_next, torch.int32, n_states * V)
+            nx = c_next[:n_states * V]
+            need(bool(((nx >= 0) & (nx < n_states)).all()), f"every c_next in [0, {n_states})")
+        if row_state is not None:
+            self._door("row_state", row_state, torch.int32, rows)
+        if c_start is not None:
+            need(row_state is not None and n_states >= 1 and n_start >= 1, "row_state and c_n_states >= 1 (c_start)")
+            self._door("c_start", c_start, torch.int32, n_start)
+        elif c_allowed is not None and n_start == 0:             # a step: the states the kernel indexes the tables with
+            st = row_state[lo:rows]
+            need(bool(((st >= 0) & (st < n_states)).all()), f"every row_state in [0, {n_states})")
+        return words
+
+    def test_token_step(self, op: int, *, R: int, n_steps: int, row0: int = 0, V: int = 0, d: int = 512, n_channels: int = 1, eos_id: int = -1,
+                        pad_id: int = 0, n_prompt: int = 0, step: int = 0, step0: int = 0, keep_shared: bool = False,
+                        logits: Optional[torch.Tensor] = None, h: Optional[torch.Tensor] = None, embed: Optional[torch.Tensor] = None,
+                        chan_embed: Optional[torch.Tensor] = None, finished: Optional[torch.Tensor] = None, ssq: Optional[torch.Tensor] = None,
+                        ssq_stride: int = 0, row_pos: Optional[torch.Tensor] = None, row_out: Optional[torch.Tensor] = None,
+                        row_prompt: Optional[torch.Tensor] = None, row_state: Optional[torch.Tensor] = None, ticket: Optional[torch.Tensor] = None,
+                        zero_sync: Optional[torch.Tensor] = None, zero_lines: int = 0, qkv0: Optional[torch.Tensor] = None,
+                        q0: Optional[torch.Tensor] = None, kcache0: Optional[torch.Tensor] = None, vcache0: Optional[torch.Tensor] = None, L: int = 0,
+                        tokens_out: Optional[torch.Tensor] = None, forced: Optional[torch.Tensor] = None, logits_out: Optional[torch.Tensor] = None,
+                        scores_out: Optional[torch.Tensor] = None, prompt: Optional[torch.Tensor] = None, c_allowed: Optional[torch.Tensor] = None,
+                        c_next: Optional[torch.Tensor] = None, c_start: Optional[torch.Tensor] = None, c_n_states: int = 0,
+                        state_out: Optional[torch.Tensor] = None, first_out: int = 0, first_prompt: int = 0, from_: int = 0, v0: int = 0) -> None:
+        """ymt3_test_token_step (include/ymt3.h): op 0 decode_init, 1 argmax_embed, 2 slot_start, 3 slot_retire, 4 pad_tail, 5 qkv0_embed.  Every
+        row-indexed tensor starts at row 0 and must reach the launch's last row; outputs are written in place.  With keep_shared the loop
+        state is the previous call's: step, step0 and the output pointers of this call are not used."""
+        need = self._need
+        need(0 <= op <= 5 and 1 <= R <= 0xffff and 0 <= row0 <= 0xffff and n_steps >= 1 and n_prompt >= 0, "an op in 0..5, 1 <= R, 0 <= row0, n_steps >= 1, n_prompt >= 0")
+        slot = row_pos is not None
+        need(slot if op in (2, 3) else (not slot or op == 1), "row_pos with ops 1, 2 and 3 only, always with 2 and 3")
+        need(slot or (row_out is None and row_prompt is None), "row_out and row_prompt with row_pos only")
+        rows = row0 + (n_channels if op == 2 else R)
+        cells = rows * n_steps                                      # lock-step: [rows][n_steps]; slot mode: whatever the offsets reach
+        if op in (0, 1, 2, 5):
+            need(V >= 1 and d >= 1 and n_channels >= 1 and 0 <= pad_id < V and eos_id < V, "V, d, n_channels >= 1, pad_id in [0, V), eos_id < V")
+            need(h is not None and embed is not None and ssq is not None and ssq_stride >= rows, "h, embed, ssq with ssq_stride >= the last row")
+            need(op != 0 or row0 == 0, "row0 == 0 (decode_init)")
+            need(op != 5 or (row0 == 0 and chan_embed is None and v0 >= 0 and v0 + R <= V), "row0 == 0, no chan_embed, [v0, v0 + R) inside [0, V) (qkv0_embed)")
+            self._door("h", h, torch.float32, rows * d)
+            self._door("embed", embed, torch.bfloat16, V * d)
+            self._door("ssq", ssq, torch.float32, 31 * ssq_stride + rows)
+            if chan_embed is not None:
+                self._door("chan_embed", chan_embed, torch.bfloat16, n_channels * d)
+        words = 0
+        if op in (0, 1, 2):
+            need(finished is not None, "finished")
+            self._door("finished", finished, torch.int32, rows)
+            need(c_start is None or op != 1, "c_start with the init kernels only")
+            words = self._automaton(c_allowed, c_next, c_start, row_state, V, c_n_states, rows, 0 if op == 1 else (rows if op == 0 else n_channels), row0)
+            if qkv0 is not None:
+                need(q0 is not None and kcache0 is not None and vcache0 is not None and d == 512 and L >= 1 and chan_embed is None and n_channels == 1,
+                     "q0, kcache0, vcache0, d == 512, L >= 1, one channel without chan_embed (qkv0)")
+                self._door("qkv0", qkv0, torch.bfloat16, V * 1536)
+                self._door("q0", q0, torch.bfloat16, rows * 512)
+                self._door("kcache0", kcache0, torch.bfloat16, rows * 8 * L * 64)
+                self._door("vcache0", vcache0, torch.bfloat16, rows * 8 * L * 64)
+                need(op != 0 or 0 <= step0 < L, f"0 <= step0 < {L} (qkv0)")
+        if slot:
+            need(row_out is not None and (row_prompt is not None or (op == 1 and n_prompt == 0) or op == 3), "row_out, and row_prompt where prompts are read or written")
+            self._door("row_pos", row_pos, torch.int32, rows)
+            self._door("row_out", row_out, torch.int64, rows)
+            if row_prompt is not None:
+                self._door("row_prompt", row_prompt, torch.int64, rows)
+        if op != 5 and (op != 0 or tokens_out is not None) and op != 2:
+            need(tokens_out is not None, "tokens_out")
+            if not slot:
+                self._door("tokens_out", tokens_out, torch.int32, cells)
+        if op in (0, 1) and not slot:
+            for name, t, dt, n in (("forced", forced, torch.int32, cells), ("logits_out", logits_out, torch.float32, cells * V),
+                                   ("scores_out", scores_out, torch.float32, cells)):
+                if t is not None:
+                    self._door(name, t, dt, n)
+            need(n_prompt == 0 or prompt is not None, "prompt with n_prompt > 0")
+            if prompt is not None and n_prompt > 0:
+                self._door("prompt", prompt, torch.int32, rows * n_prompt)
+        if op == 4:
+            need(0 <= from_ <= n_steps, "0 <= from <= n_steps")
+            if scores_out is not None:
+                self._door("scores_out", scores_out, torch.float32, cells)
+        if slot and op in (1, 3):
+            need(forced is None and logits_out is None, "neither forced nor logits_out in slot mode")
+            for name, t, dt in (("tokens_out", tokens_out, torch.int32), ("scores_out", scores_out, torch.float32)):
+                if t is not None:
+                    self._door(name, t, dt, n_steps)
+            o, p = row_out[row0:rows], row_pos[row0:rows]
+            reach = min(t.numel() for t in (tokens_out, scores_out) if t is not None)
+            need(bool(((o >= 0) & (o + n_steps <= reach)).all()), "every row_out inside tokens_out (and scores_out)")
+            need(bool((p >= 0).all()), "every row_pos >= 0")
+            if op == 1:
+                live = finished[row0:rows] == 0
+                need(bool((p[live] < n_prompt + n_steps).all()), "every live row_pos < n_prompt + n_steps")
+                need(qkv0 is None or bool((p[live] < L).all()), "every live row_pos < L (qkv0)")
+                if n_prompt > 0:
+                    need(prompt is not None, "prompt with n_prompt > 0")
+                    self._door("prompt", prompt, torch.int32, n_prompt)
+                    q = row_prompt[row0:rows]
+                    need(bool(((q >= 0) & (q + n_prompt <= prompt.numel())).all()), "every row_prompt inside prompt")
+        if op == 1:
+            need(logits is not None, "logits")
+            self._door("logits", logits, torch.float32, rows * V)
+            need(slot or keep_shared or (0 <= step0 <= step and step - step0 - n_prompt < n_steps and (qkv0 is None or step < L)),
+                 "step0 <= step, the emitted column below n_steps, step < L with qkv0")
+            if ticket is not None:
+                self._door("ticket", ticket, torch.int32, (R // 32 + 1) * 32)
+            need((zero_sync is None) == (zero_lines == 0) and zero_lines >= 0, "zero_lines >= 1 with zero_sync, 0 without")
+            if zero_sync is not None:
+                self._door("zero_sync", zero_sync, torch.int32, zero_lines * 32)
+        if state_out is not None:
+            self._door("state_out", state_out, torch.int32, 4)
+        p = lambda t: t.data_ptr() if t is not None else None
+        c = _lib.TokenStepArgs(p(logits), p(h), p(embed), p(chan_embed), p(finished), p(ssq), p(row_pos), p(row_out), p(row_prompt), p(row_state),
+                               p(ticket), p(zero_sync), p(qkv0), p(q0), p(kcache0), p(vcache0), p(tokens_out), p(forced), p(logits_out),
+                               p(scores_out), p(prompt), p(c_allowed), p(c_next), p(c_start), p(state_out), first_out, first_prompt, ssq_stride, row0,
+                               R, V, d, n_channels, eos_id, pad_id, zero_lines, 8 if qkv0 is not None else 0, L, step, step0, n_steps, n_prompt, words,
+                               c_n_states, int(bool(keep_shared)), from_, v0)
+        _lib.check(self._lib.ymt3_test_token_step(self._handle, int(op), ctypes.byref(c), self._stream()))
+
+    def test_beam_step(self, op: int, *, R: int, W: int, V: int, n_steps: int, anc_rows: int, anc_pitch: int, fed_pitch: int, h: torch.Tensor,
+                       embed: torch.Tensor, finished: torch.Tensor, ssq: torch.Tensor, ssq_stride: int, anc: torch.Tensor, slot_anc: torch.Tensor,
+                       fed_tok: torch.Tensor, fed_lp: torch.Tensor, run: torch.Tensor, fin_score: torch.Tensor, fin_len: torch.Tensor,
+                       fin_store: torch.Tensor, fin_tok: torch.Tensor, fin_lp: torch.Tensor, n_fin: torch.Tensor, d: int = 512, n_channels: int = 1,
+                       eos_id: int = -1, pad_id: int = 0, n_prompt: int = 0, step: int = 0, keep_shared: bool = False, N: int = 1, row0: int = 0,
+                       alpha: float = 1.0, first_group: int = 0, logits: Optional[torch.Tensor] = None, chan_embed: Optional[torch.Tensor] = None,
+                       row_state: Optional[torch.Tensor] = None, row_pos: Optional[torch.Tensor] = None, row_out: Optional[torch.Tensor] = None,
+                       row_prompt: Optional[torch.Tensor] = None, prompt: Optional[torch.Tensor] = None, c_allowed: Optional[torch.Tensor] = None,
+                       c_next: Optional[torch.Tensor] = None, c_start: Optional[torch.Tensor] = None, c_n_states: int = 0,
+                       tokens_out: Optional[torch.Tensor] = None, seq_out: Optional[torch.Tensor] = None, tok_out: Optional[torch.Tensor] = None,
+                       state_out: Optional[torch.Tensor] = None, n_queue: int = 0) -> None:
+        """ymt3_test_beam_step (include/ymt3.h): op 0 beam_init, 1 beam_select, 2 beam_finalize, 3 beam_slot_start, 4 beam_slot_finalize over
+        rows [0, R) = R / W groups.  n_queue (slot mode): the groups the result tensors hold (row_out must stay below it)."""
+        need = self._need
+        need(0 <= op <= 4 and 1 <= W <= 8 and 1 <= R <= 0xffff and R % W == 0 and R <= anc_rows, "an op in 0..4, 1 <= W <= 8 dividing R, R <= anc_rows")
+        need(V >= 1 and d >= 1 and n_channels >= 1 and 0 <= pad_id < V and eos_id < V and ssq_stride >= R, "V, d, n_channels >= 1, pad_id in [0, V), eos_id < V, ssq_stride >= R")
+        need(n_steps >= 1 and n_prompt >= 0 and anc_pitch % 16 == 0 and anc_pitch <= 48 * 1024 and n_prompt + n_steps < min(anc_pitch, fed_pitch),
+             "n_prompt + n_steps below anc_pitch (a multiple of 16, at most 48 KiB) and fed_pitch")
+        need(1 <= N <= W and 0.0 <= alpha <= 16.0, "1 <= N <= W, 0 <= alpha <= 16")
+        slot = row_pos is not None
+        need(slot if op in (3, 4) else (not slot or op == 1), "row_pos with ops 1, 3 and 4 only, always with 3 and 4")
+        G = R // W
+        self._door("h", h, torch.float32, R * d)
+        self._door("embed", embed, torch.bfloat16, V * d)
+        self._door("ssq", ssq, torch.float32, 31 * ssq_stride + R)
+        self._door("anc", anc, torch.uint8, 2 * anc_rows * anc_pitch)
+        self._door("slot_anc", slot_anc, torch.uint8, R * anc_pitch)
+        self._door("fed_tok", fed_tok, torch.int32, R * fed_pitch)
+        self._door("fed_lp", fed_lp, torch.float32, R * fed_pitch)
+        for name, t, dt in (("finished", finished, torch.int32), ("run", run, torch.float32), ("fin_score", fin_score, torch.float32),
+                            ("fin_len", fin_len, torch.int32), ("fin_store", fin_store, torch.int32), ("fin_tok", fin_tok, torch.int32),
+                            ("fin_lp", fin_lp, torch.float32)):
+            self._door(name, t, dt, R)
+        self._door("n_fin", n_fin, torch.int32, G)
+        if chan_embed is not None:
+            self._door("chan_embed", chan_embed, torch.bfloat16, n_channels * d)
+        need(c_start is None or op in (0, 3), "c_start with the init kernels only")
+        words = self._automaton(c_allowed, c_next, c_start, row_state, V, c_n_states, R, 0 if op not in (0, 3) else (G if op == 0 else n_channels))
+        if slot:
+            need(row_out is not None and row_prompt is not None, "row_out and row_prompt (slot mode)")
+            for name, t in (("row_pos", row_pos), ("row_out", row_out), ("row_prompt", row_prompt)):
+                self._door(name, t, torch.int32 if t is row_pos else torch.int64, R)
+            need(op == 1 or (row0 >= 0 and row0 % (n_channels * W) == 0 and row0 + n_channels * W <= R), "row0 a slot boundary inside [0, R)")
+            n_groups = n_queue
+            need(op != 3 or (first_group >= 0 and first_group + n_channels <= n_queue), "the slot's queue indices below n_queue")
+            # what the launch follows: a stopped group (finished != 0: done, or an empty slot) reads neither its offsets nor its position
+            live = (finished[:R] == 0) if op == 1 else None
+            if op in (1, 4):
+                o = row_out[:R][live] if op == 1 else row_out[row0:row0 + n_channels * W]
+                need(bool(((o >= 0) & (o < n_queue)).all()), "every row_out in [0, n_queue)")
+            if op == 1:
+                p = row_pos[:R][live]
+                need(bool(((p >= 0) & (p < n_prompt + n_steps)).all()), "every live row_pos in [0, n_prompt + n_steps)")
+        else:
+            n_groups = G
+        if n_prompt > 0:
+            need(prompt is not None, "prompt with n_prompt > 0")
+            self._door("prompt", prompt, torch.int32, n_groups * n_prompt)
+            if slot and op == 1:
+                q = row_prompt[:R][live]
+                need(bool(((q >= 0) & (q + n_prompt <= prompt.numel())).all()), "every row_prompt inside prompt")
+        if op == 0 or not keep_shared:
+            need(tokens_out is not None, "tokens_out")
+            self._door("tokens_out", tokens_out, torch.int32, n_groups * N * n_steps)
+            if seq_out is not None:
+                self._door("seq_out", seq_out, torch.float32, n_groups * N)
+            if tok_out is not None:
+                self._door("tok_out", tok_out, torch.float32, n_groups * N * n_steps)
+        if op == 1:
+            need(logits is not None, "logits")
+            self._door("logits", logits, torch.float32, R * V)
+            need(slot or keep_shared or (0 <= step and step - n_prompt < n_steps), "0 <= step, the emitted column below n_steps")
+        if op in (2, 4):
+            lo, hi = (0, R) if op == 2 else (row0, row0 + n_channels * W)
+            fs, fl = fin_store[lo:hi], fin_len[lo:hi]
+            need(bool(((fs >= 0) & (fs < W)).all()) and bool(((fl >= 0) & (fl <= n_steps)).all()), "fin_store in [0, W), fin_len in [0, n_steps]")
+        if state_out is not None:
+            self._door("state_out", state_out, torch.int32, 4)
+        p = lambda t: t.data_ptr() if t is not None else None
+        c = _lib.BeamStepArgs(p(logits), p(h), p(embed), p(chan_embed), p(finished), p(ssq), p(row_state), p(anc), p(fed_tok), p(fed_lp), p(run),
+                              p(fin_score), p(fin_len), p(fin_store), p(fin_tok), p(fin_lp), p(n_fin), p(slot_anc), p(row_pos), p(row_out),
+                              p(row_prompt), p(prompt), p(c_allowed), p(c_next), p(c_start), p(tokens_out), p(seq_out), p(tok_out), p(state_out),
+                              first_group, ssq_stride, R, V, d, n_channels, eos_id, pad_id, W, anc_rows, anc_pitch, fed_pitch, step, n_steps, n_prompt,
+                              words, c_n_states, int(bool(keep_shared)), N, row0, float(alpha))
+        _lib.check(self._lib.ymt3_test_beam_step(self._handle, int(op), ctypes.byref(c), self._stream()))
